@@ -3,19 +3,27 @@
 
 A "step" is one launch of the hot path over one batch of synthetic input: E epochs x B tags, i.e. E*B updates
 (one update = gate + M Cauchy range factors + the reference's fixed `maximum_iteration` = 10 LM iterations +
-chi2).  All inputs and outputs are resident in HBM before the timed region; every step consumes
-fresh epochs of one long seeded random-walk stream (no buffer is re-read between steps).
+chi2).  Every step consumes fresh epochs of one long seeded random-walk stream (no buffer is re-read
+between steps).  Its inputs and outputs are resident in HBM before the timed region: all of them at the default sizes; a
+longer run generates the stream in chunks of steps that fit --resident-gib, each before its own timed region, and adds up
+the timed regions.
 
     python bench.py --gpus N --steps K --warmup W
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL only for the barrier and the
 max-over-ranks of the time: the path has no data-path collective; the batch is sharded by tag, "weak" scaling).
 
-Besides the headline (the top-level keys of the ONE JSON line), the line carries driver-timed secondary legs under
-"legs": cfg2 in the reference's numeric-Jacobian configuration, cfg3 (fusion kernel), cfg5 (64-pose windows) and cfg4
-(anchor self-calibration) — each with its own roofline and, at N = 1, cpu_baseline.  For N > 1 the window legs shard the
-SURVEY §8(e) totals (16 384 windows, 1 024 hypotheses) over the ranks ("strong"), cfg2/cfg3 keep 65 536 tags per GPU.
---legs none|all|comma list selects them (default all).
+A plain run does only what the headline needs: set up, warm up, time the K steps, print ONE JSON line (`value`,
+`ms_per_step`, the roofline of the timed kernel).  --dump-outputs DIR also writes what the last timed step returned
+(a fixed sample of the tags, dump_outputs()), so that two builds can be compared output for output.
+
+    python bench.py --gpus N --steps K --warmup W --full
+
+also runs, after the headline, the reporting collectives, the accuracy figures against the synthetic truth, the CPU
+baselines (at N = 1) and driver-timed secondary legs under "legs": cfg2 in the other Jacobian mode, cfg3 (fusion kernel),
+cfg5 (64-pose windows), cfg4 (anchor self-calibration), the window and node legs — each with its own roofline and, at
+N = 1, cpu_baseline.  For N > 1 the window legs shard the SURVEY §8(e) totals (16 384 windows, 1 024 hypotheses) over the
+ranks ("strong"), cfg2/cfg3 keep 65 536 tags per GPU.  --legs none|all|comma list selects them (default all).
 """
 import argparse
 import hashlib
@@ -299,6 +307,95 @@ def reporting_collectives(D, args, out_pos, out_chi2, out_trials, dist_tiles, E,
     if not out["all_gather"]["checksum_ok"]:
         raise SystemExit("bench.py: the all-gathered result slab does not match what the ranks sent")
     return out
+
+
+# HBM per update of the headline stream, for its M = 8 anchors: dist + err tiles (M4 = 2 tiles of 4 floats each) in, position, chi2,
+# LM trials out: 64 B + 33 B
+STEP_BYTES_PER_UPDATE = 2 * 2 * 16 + 3 * 8 + 8 + 1
+
+
+class SnapshotStream:
+    """localization_amd.synthetic.make_snapshot_stream_torch's stream, the same numbers bit for bit, generated K epochs at a time
+    (next(K1) then next(K2) = one next(K1 + K2)) and with a third of its launches: each epoch's five random draws still go to the
+    one seeded generator in their order, into batch buffers; the clamped walk stays a loop over epochs; everything else is computed
+    for BATCH epochs at once.  `p` is the truth of the last epoch generated, `init` the solver's starting positions."""
+    BATCH = 32
+
+    def __init__(self, B, seed, device, sigma=0.05, err=0.055, outlier_frac=0.01, vmax=5.0, dt=1.0 / 32.0):
+        import numpy as np
+        import torch
+        from localization_amd.synthetic import ANCHORS_8, HI, LO
+        self.torch, self.B, self.device = torch, B, device
+        self.sigma, self.outlier_frac, self.vstep = sigma, outlier_frac, vmax * dt
+        self.g = torch.Generator(device=device)
+        self.g.manual_seed(int(seed))
+        self.M = ANCHORS_8.shape[0]
+        self.M4 = (self.M + 3) // 4
+        self.a = torch.tensor(ANCHORS_8, dtype=torch.float64, device=device)          # [M,3]
+        self.lo = torch.tensor(LO, dtype=torch.float64, device=device)[:, None]
+        self.hi = torch.tensor(HI, dtype=torch.float64, device=device)[:, None]
+        self.p = self.lo + (self.hi - self.lo) * torch.rand((3, B), generator=self.g, device=device, dtype=torch.float64)
+        e = torch.zeros((self.M4 * 4, B), dtype=torch.float32, device=device)
+        e[:self.M] = err
+        self.err_tile = e.view(self.M4, 4, B).permute(0, 2, 1)                        # [M4,B,4]: every epoch's
+        self.init = np.repeat(ANCHORS_8.mean(axis=0)[:, None], B, axis=1).astype(np.float64)
+        n, f64 = self.BATCH, torch.float64
+        self.u_step = torch.empty((n, 3, B), dtype=f64, device=device)
+        self.u_speed = torch.empty((n, 1, B), dtype=f64, device=device)
+        self.u_noise = torch.empty((n, self.M, B), dtype=f64, device=device)
+        self.u_nlos = torch.empty((n, self.M, B), dtype=torch.float32, device=device)
+        self.u_out = torch.empty((n, self.M, B), dtype=f64, device=device)
+        self.walk = torch.empty((n, 3, B), dtype=f64, device=device)
+
+    def next(self, K):
+        """The next K epochs: (dist_tiles[K,M4,B,4] f32, err_tiles[K,M4,B,4] f32), contiguous."""
+        torch, g, B, M, M4 = self.torch, self.g, self.B, self.M, self.M4
+        dist_tiles = torch.zeros((K, M4, B, 4), dtype=torch.float32, device=self.device)
+        err_tiles = torch.zeros((K, M4, B, 4), dtype=torch.float32, device=self.device)
+        err_tiles[:] = self.err_tile
+        p = self.p
+        for k0 in range(0, K, self.BATCH):
+            n = min(self.BATCH, K - k0)
+            for j in range(n):   # the draws of one epoch, in make_snapshot_stream_torch's order
+                torch.randn((3, B), generator=g, out=self.u_step[j])
+                torch.rand((1, B), generator=g, out=self.u_speed[j])
+                torch.randn((M, B), generator=g, out=self.u_noise[j])
+                torch.rand((M, B), generator=g, out=self.u_nlos[j])
+                torch.rand((M, B), generator=g, out=self.u_out[j])
+            step = self.u_step[:n]
+            step = step * (self.u_speed[:n] * self.vstep / step.norm(dim=1, keepdim=True).clamp_min(1e-12))
+            for j in range(n):
+                torch.add(p, step[j], out=self.walk[j])
+                p = self.walk[j].clamp_(self.lo, self.hi)
+            d = (self.walk[:n, None, :, :] - self.a[None, :, :, None]).norm(dim=2)             # [n,M,B]
+            d = d + self.sigma * self.u_noise[:n]
+            nlos = self.u_nlos[:n] < self.outlier_frac
+            d = d + nlos * (1.0 + 2.0 * self.u_out[:n])
+            if M < M4 * 4:
+                d = torch.cat([d, d.new_zeros((n, M4 * 4 - M, B))], dim=1)
+            dist_tiles[k0:k0 + n] = d.to(torch.float32).view(n, M4, 4, B).permute(0, 1, 3, 2)
+            p = p.clone()    # (the walk buffer is overwritten by the next batch)
+        self.p = p
+        return dist_tiles, err_tiles
+DUMP_TAGS = 8192                  # --dump-outputs: tags sampled from the batch (all of them when B is smaller)
+DUMP_BYTES = 48 << 20             # ... and at most this many bytes: the last epochs of the step when E is large
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, pos, chi2, trials):
+    """What one step of the timed path returns ([E][3][B] positions, [E][B] chi2 and LM trials) for a fixed, seeded sample
+    of the tags, written as DIR/positions.npy (f64 [E'][3][n]), DIR/chi2.npy (f64 [E'][n]) and DIR/lm_trials.npy (f32 [E'][n])."""
+    import numpy as np
+    import torch
+    E, B = chi2.shape
+    n = min(B, DUMP_TAGS)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    e0 = E - max(1, min(E, DUMP_BYTES // (n * (3 * 8 + 8 + 4))))
+    ix = torch.from_numpy(idx).to(pos.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "positions.npy"), pos[e0:].index_select(2, ix).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "chi2.npy"), chi2[e0:].index_select(1, ix).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "lm_trials.npy"), trials[e0:].index_select(1, ix).cpu().numpy().astype(np.float32))
 
 
 def hbm_roofline(kernel, algo_bytes_per_launch, kern_ms_avg, n_launch, unit_note):
@@ -878,8 +975,20 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tags", type=int, default=2048)
     ap.add_argument("--cpu-epochs", type=int, default=96)
-    ap.add_argument("--legs", default="all", help="secondary legs: all, none, or a comma list of cfg2_analytic,cfg2_numeric,cfg3,cfg5,cfg4,cfg1_windows,cfg1_node,node_uwb_twist,node_uwb_pose_T500")
+    ap.add_argument("--legs", default=None, help="with --full: secondary legs, all (the default), none, or a comma list of cfg2_analytic,cfg2_numeric,cfg3,cfg5,cfg4,"
+                                                 "cfg1_windows,cfg1_node,node_uwb_twist,node_uwb_pose_T500,twist_windows")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the reporting collectives, the accuracy figures, the CPU baselines "
+                         "and the secondary legs (without it the run sets up, warms up, times the steps and prints the headline)")
+    ap.add_argument("--resident-gib", type=float, default=32.0,
+                    help="HBM for the resident part of the headline stream (inputs + outputs): longer runs generate it in chunks of steps, untimed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (a fixed sample of the tags: dump_outputs())")
     args = ap.parse_args()
+    if args.legs is None:
+        args.legs = "all"
+    elif not args.full and args.legs != "none":
+        ap.error("--legs selects secondary legs, which only run with --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Launched bare (`python bench.py --gpus N`): start the N ranks ourselves.  This happens BEFORE anything touches the
@@ -889,7 +998,7 @@ def main():
     import numpy as np
     import torch
     import localization_amd as la
-    from localization_amd.synthetic import ANCHORS_8, make_snapshot_stream_torch
+    from localization_amd.synthetic import ANCHORS_8
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (no CPU fallback)")
@@ -902,52 +1011,78 @@ def main():
 
     B, E, M = args.batch, args.epochs, 8
     total_steps = args.warmup + args.steps
-    # one long stream: every step reads fresh epochs (inputs (W+K)*E*B*64 B resident in HBM)
+    # one long stream: every step reads fresh epochs.  At most `chunk` steps of it (inputs 64 B + outputs 33 B per update) are
+    # resident at a time: the next chunk is generated untimed once the previous one has been solved (one chunk at the default sizes)
+    chunk = max(1, min(total_steps, int(args.resident_gib * 2**30) // (E * B * STEP_BYTES_PER_UPDATE)))
+    seed = args.seed + 1000 * rank
     if args.datagen == "torch":
-        stream = make_snapshot_stream_torch(B, E * total_steps, seed=args.seed + 1000 * rank, device=dev)
+        gen = SnapshotStream(B, seed, dev)
+        init = gen.init
     else:
+        if chunk < total_steps:
+            raise SystemExit(f"bench.py: --datagen numpy keeps the whole stream resident: at most {chunk} steps (warm-up included) at this size")
         from localization_amd.synthetic import make_snapshot_stream
-        hs = make_snapshot_stream(B, E * total_steps, seed=args.seed + 1000 * rank)
-        stream = {"dist_tiles": torch.from_numpy(la.pack_ranges(hs["dist"])).to(dev),
-                  "err_tiles": torch.from_numpy(la.pack_ranges(hs["err"])).to(dev),
-                  "init": hs["init"], "truth_last": torch.from_numpy(hs["truth"][-1]).to(dev)}
+        hs = make_snapshot_stream(B, E * total_steps, seed=seed)
+        init, truth_last = hs["init"], torch.from_numpy(hs["truth"][-1]).to(dev)
+        host_tiles = (torch.from_numpy(la.pack_ranges(hs["dist"])).to(dev), torch.from_numpy(la.pack_ranges(hs["err"])).to(dev))
         del hs
-    dist_t, err_t = stream["dist_tiles"], stream["err_tiles"]
     solver = la.SnapshotSolver(ANCHORS_8, B, maximum_iteration=10, distance_outlier=1.0, jacobian=args.jacobian,
                                lanes_per_instance=args.lpi, block_threads=args.block, device=D.local_rank)
-    solver.set_positions(stream["init"])
-    out_pos = torch.empty((total_steps * E, 3, B), dtype=torch.float64, device=dev)
-    out_chi2 = torch.empty((total_steps * E, B), dtype=torch.float64, device=dev)
-    out_trials = torch.empty((total_steps * E, B), dtype=torch.uint8, device=dev)
+    solver.set_positions(init)
+    out_pos = torch.empty((chunk * E, 3, B), dtype=torch.float64, device=dev)
+    out_chi2 = torch.empty((chunk * E, B), dtype=torch.float64, device=dev)
+    out_trials = torch.empty((chunk * E, B), dtype=torch.uint8, device=dev)
+    n_head = min(args.cpu_epochs, E * chunk)   # --full: the first epochs (CPU baseline sample), kept when later chunks replace them
 
-    def step(i):
-        sl = slice(i * E, (i + 1) * E)
-        solver.solve_device(dist_t[sl], err_t[sl], out_pos[sl], out_chi2[sl], out_trials[sl])
+    elapsed, timing = 0.0, False
+    dist_t = err_t = head = None
+    for c0 in range(0, total_steps, chunk):
+        c1 = min(total_steps, c0 + chunk)
+        dist_t = err_t = None   # (the previous chunk is freed before the next one is allocated)
+        dist_t, err_t = gen.next((c1 - c0) * E) if args.datagen == "torch" else host_tiles
 
-    for i in range(args.warmup):
-        step(i)
-    D.barrier()
-    solver.timing_begin(args.steps)
-    t0 = time.perf_counter()
-    for i in range(args.warmup, total_steps):
-        step(i)
-    D.barrier()
-    elapsed = D.max_over_ranks(time.perf_counter() - t0)
+        def step(i):
+            sl = slice((i - c0) * E, (i - c0 + 1) * E)
+            solver.solve_device(dist_t[sl], err_t[sl], out_pos[sl], out_chi2[sl], out_trials[sl])
+
+        for i in range(c0, min(c1, args.warmup)):
+            step(i)
+        if c1 > args.warmup:
+            D.barrier()
+            if not timing:
+                solver.timing_begin(args.steps)
+                timing = True
+            t0 = time.perf_counter()
+            for i in range(max(c0, args.warmup), c1):
+                step(i)
+            D.barrier()
+            elapsed += time.perf_counter() - t0
+        if c0 == 0 and args.full:
+            head = tuple(x[:n_head] if c1 == total_steps else x[:n_head].clone() for x in (dist_t, err_t, out_pos))
+    elapsed = D.max_over_ranks(elapsed)
     n_launch, kern_ms_total, kern_ms_avg = solver.timing_end()
+    if args.datagen == "torch":
+        truth_last = gen.p
+    n_res = c1 - c0                            # the steps still resident: the last chunk's
+    out_pos, out_chi2, out_trials = out_pos[:n_res * E], out_chi2[:n_res * E], out_trials[:n_res * E]
 
     updates_per_launch = float(B) * E
     total_updates = updates_per_launch * args.steps * n_gpus
     value = total_updates / elapsed
     achieved_gbs = ALGO_BYTES_PER_UPDATE * updates_per_launch / (kern_ms_avg * 1e-3) / 1e9
+    if args.dump_outputs and rank == 0:
+        last = slice((n_res - 1) * E, n_res * E)
+        dump_outputs(args.dump_outputs, out_pos[last], out_chi2[last], out_trials[last])
 
+    # over the resident steps (all of them at the default sizes): their warm-up steps are not summed
+    res_args = argparse.Namespace(**vars(args))
+    res_args.warmup = max(0, args.warmup - c0)
     # ---- the reporting collectives, AFTER the timed region (the solve path has none) -----------------------
-    coll = reporting_collectives(D, args, out_pos, out_chi2, out_trials, dist_t, E, total_steps, B)
+    coll = reporting_collectives(D, res_args, out_pos, out_chi2, out_trials, dist_t, E, n_res, B) if args.full else None
 
     res = None
     oracle_sample = None
     if rank == 0:
-        trials_mean = float(out_trials[args.warmup * E:].cpu().numpy().mean())
-        err_last = torch.from_numpy(np.sqrt(((out_pos[-1].cpu().numpy() - stream["truth_last"].cpu().numpy()) ** 2).sum(axis=0)))
         # HBM bytes per launch from the committed PMC passes (rocprofv3 cannot run inside this process); they apply to the
         # default launch shape AND to the kernel source they were measured on: a hash of the sources is stored with them
         pm, stale, ceiling = None, None, None
@@ -978,9 +1113,6 @@ def main():
                                         "the opt-in analytic fast mode (NOT the library default)",
                        "lanes_per_tag": solver.lanes_per_instance, "sharding": f"tags split over {n_gpus} GPU(s), no collective"},
             "lm_iterations_per_s": value * 10,
-            "mean_lm_trials_per_update": trials_mean,
-            "median_err_vs_truth_m": float(err_last.median().item()),
-            "frac_err_gt_0p5m": float((err_last > 0.5).double().mean().item()),
             "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved_gbs / HBM_PEAK_GBS, "frac_of_measured_copy_ceiling": achieved_gbs / HBM_COPY_GBS,
                          "traffic": pm["hbm_bytes_per_launch"] if pm else None, "traffic_unit": "bytes per launch",
@@ -1005,24 +1137,32 @@ def main():
                                              "valu_wave_insts_per_launch": pm.get("valu_wave_insts_per_launch"),
                                              "note": "(VALU + SALU wave-instructions per launch) x 64 lanes (PMC) / live kernel time, against the "
                                                      "measured one-wave-per-SIMD issue ceiling (tools/fp64_probe.hip): what actually bounds this kernel"}
-        if coll is not None:
-            res["collectives"] = coll
+    if rank == 0 and args.full:
+        res["mean_lm_trials_per_update"] = float(out_trials[res_args.warmup * E:].cpu().numpy().mean())
+        err_last = torch.from_numpy(np.sqrt(((out_pos[-1].cpu().numpy() - truth_last.cpu().numpy()) ** 2).sum(axis=0)))
+        res["median_err_vs_truth_m"] = float(err_last.median().item())
+        res["frac_err_gt_0p5m"] = float((err_last > 0.5).double().mean().item())
+        res["collectives"] = coll
         if not args.no_cpu_baseline and n_gpus == 1:
-            n_t, n_e = min(args.cpu_tags, B), min(args.cpu_epochs, E * total_steps)
-            res["cpu_baseline"], rp = cpu_baseline(ANCHORS_8, dist_t, err_t, stream["init"], n_t, n_e, out_pos, M, args.jacobian)
+            n_t, n_e = min(args.cpu_tags, B), n_head
+            res["cpu_baseline"], rp = cpu_baseline(ANCHORS_8, head[0], head[1], init, n_t, n_e, head[2], M, args.jacobian)
             oracle_sample = (n_e, n_t, rp)
             try:  # a secondary figure: a host that refuses worker processes must not cost the bench its JSON line
-                res["cpu_baseline_all_cores"] = cpu_baseline_all_cores(ANCHORS_8, dist_t, err_t, stream["init"], args.cpu_tags // 2,
-                                                                       min(args.cpu_epochs, E * total_steps), M)
+                res["cpu_baseline_all_cores"] = cpu_baseline_all_cores(ANCHORS_8, head[0], head[1], init, args.cpu_tags // 2, n_e, M)
             except Exception as exc:  # noqa: BLE001
                 res["cpu_baseline_all_cores"] = {"value": None, "error": f"{type(exc).__name__}: {exc}"}
     solver.close()
-    del out_pos, out_chi2, out_trials
+    del out_pos, out_chi2, out_trials, head
+    stream = {"dist_tiles": dist_t, "err_tiles": err_t, "init": init}   # the legs' input: the stream's first chunk
+    if args.full and c0 > 0:
+        del dist_t, err_t, stream
+        torch.cuda.empty_cache()
+        stream = dict(zip(("dist_tiles", "err_tiles"), SnapshotStream(B, seed, dev).next(chunk * E)), init=init)
 
     # ---- secondary legs (every rank takes part: they carry their own barriers) ------------------------------------------------
     other = "analytic" if args.jacobian == "numeric" else "numeric"
     all_legs = ["cfg2_" + other, "cfg3", "cfg5", "cfg4", "cfg1_windows", "cfg1_node", "node_uwb_twist", "node_uwb_pose_T500", "twist_windows"]
-    want = [] if args.legs == "none" else (all_legs if args.legs == "all" else args.legs.split(","))
+    want = [] if args.legs == "none" or not args.full else (all_legs if args.legs == "all" else args.legs.split(","))
     legs = {}
     for name in want:
         try:
@@ -1051,7 +1191,7 @@ def main():
         out["n_gpus"] = n_gpus
         legs[name] = out
         torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         if legs:
             res["legs"] = legs
         oth = legs.get("cfg2_" + other, {})
@@ -1062,6 +1202,7 @@ def main():
                                       "note": "`value` is the numeric-Jacobian mode every library entry point defaults to (the reference's configuration); "
                                               "this is the opt-in analytic mode (loc_snapshot_params.jacobian)" if other == "analytic" else
                                               "`value` was run with --jacobian analytic (opt-in fast mode); this is the library default"} if oth else None
+    if rank == 0:
         print(json.dumps(res))
     D.close()
 

@@ -10,7 +10,16 @@ from localization_amd import ate, bag
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF_BAG = "/root/reference/bag/data_example.bag"
+
+
+@pytest.fixture(scope="module")
+def ref_bag(tmp_path_factory):
+    """The reference's recording bag/data_example.bag, stored xz-compressed as tests/golden/data_example.bag.xz."""
+    import lzma
+    path = tmp_path_factory.mktemp("bag") / "data_example.bag"
+    with lzma.open(os.path.join(GOLD, "data_example.bag.xz")) as f:
+        path.write_bytes(f.read())
+    return str(path)
 
 
 def test_associate_and_horn_alignment_known_answers():
@@ -88,14 +97,13 @@ def test_native_ate_tool_matches_the_numpy_evaluation(tmp_path):
     assert r.returncode == 1 and "matching timestamp pairs" in r.stderr
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BAG), reason="the reference tree exists only in the build container")
-def test_bag_reader_reproduces_the_committed_fixture():
+def test_bag_reader_reproduces_the_committed_fixture(ref_bag):
     z = np.load(os.path.join(GOLD, "bag_example.npz"))
-    conns, msgs = bag.read_bag(REF_BAG)
+    conns, msgs = bag.read_bag(ref_bag)
     types = {c.topic: c.msg_type for c in conns.values()}
     assert types["/uwb_endorange_info"] == "uwb_driver/UwbRange" and types["/imu/data"] == "sensor_msgs/Imu"
     assert [c.md5sum for c in conns.values() if c.msg_type == "uwb_driver/UwbRange"] == ["1b3efd633e416bfcfbaaf891dd23ac23"]
-    ev = list(bag.events(REF_BAG))
+    ev = list(bag.events(ref_bag))
     rng = [e for e in ev if e["kind"] == "range"]; imu = [e for e in ev if e["kind"] == "imu"]; tru = [e for e in ev if e["kind"] == "truth"]
     assert (len(rng), len(imu), len(tru)) == (1444, 4514, 1965)
     assert np.array_equal(np.array([e["distance"] for e in rng], dtype=np.float32), z["uwb_distance"][np.argsort(z["uwb_rectime"], kind="stable")])
@@ -157,14 +165,12 @@ def test_lz4_frame_decoder():
             lz4frame.decompress(bytes(good[:cut]), 9000)
 
 
-def test_lz4_chunks_are_read(tmp_path):
+def test_lz4_chunks_are_read(tmp_path, ref_bag):
     """The reference bag re-chunked with compression=lz4 (chunks re-encoded here with pyarrow's LZ4-frame codec) decodes
     to the same event stream as the original."""
     pa = pytest.importorskip("pyarrow")
-    if not os.path.exists(REF_BAG):
-        pytest.skip("reference bag not present")
     import struct
-    buf = open(REF_BAG, "rb").read()
+    buf = open(ref_bag, "rb").read()
     out = bytearray(buf[:13])
     pos = 13
     n_chunks = 0
@@ -182,7 +188,7 @@ def test_lz4_chunks_are_read(tmp_path):
     assert n_chunks == 3
     path = tmp_path / "lz4.bag"
     path.write_bytes(bytes(out))
-    a, b = list(bag.events(REF_BAG)), list(bag.events(str(path)))
+    a, b = list(bag.events(ref_bag)), list(bag.events(str(path)))
     assert len(a) == len(b) and a == b
 
 

@@ -200,3 +200,18 @@ def test_bench_reporting_collectives_two_ranks_gloo(tmp_path):
     assert v[3] >= 0 and res["all_reduce"]["bytes"] == 32
     assert res["all_gather"]["checksum_ok"] is True and res["all_gather"]["bytes"] == 2 * 4 * 48 * 8 and res["all_gather"]["slab_shape_per_rank"] == [4, 48]
     assert res["bytes"] == 32 + 3072 and res["ms"] > 0
+
+
+def test_bench_stream_is_the_library_stream_in_chunks():
+    """bench.py's SnapshotStream (batched draws, resumable) gives make_snapshot_stream_torch's numbers bit for bit, across its
+    batch boundaries and however the epochs are split between next() calls (on the host here; on the device in the GPU tests)."""
+    import importlib.util
+    from localization_amd.synthetic import make_snapshot_stream_torch
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    B, K = 97, 75
+    ref = make_snapshot_stream_torch(B, K, seed=11, device="cpu")
+    s = bench.SnapshotStream(B, 11, "cpu")
+    parts = [s.next(k) for k in (1, 40, 34)]
+    assert torch.equal(torch.cat([p[0] for p in parts]), ref["dist_tiles"]) and torch.equal(torch.cat([p[1] for p in parts]), ref["err_tiles"])
+    assert torch.equal(s.p, ref["truth_last"]) and np.array_equal(s.init, ref["init"])

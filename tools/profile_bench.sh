@@ -1,13 +1,13 @@
 #!/bin/bash
 # rocprofv3 evidence for the headline kernel (snapshot_lm_kernel) and the fusion kernel on the GPU box:
 #   tools/profile_bench.sh OUTDIR
-# 1. bench.py default run (JSON line)  2. the same under --kernel-trace --stats  3. four --pmc passes of a short numpy-fed run
+# 1. bench.py --full run (JSON line)  2. the same under --kernel-trace --stats  3. four --pmc passes of a short numpy-fed run
 # (separate passes, never combined with a trace domain)  4. the same three for tests/perf/bench_fusion.py.
 set -eo pipefail
 OUT=$1
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "[profile_bench] default run done"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_bench" -o t -- python3 bench.py --no-cpu-baseline --legs none > "$OUT/bench_under_rocprof.json" 2>/dev/null
 head -6 "$(find "$OUT/trace_bench" -name '*kernel_stats.csv' | head -1)" > "$OUT/kernel_stats_head.csv"

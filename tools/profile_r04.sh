@@ -33,7 +33,7 @@ if want cfg2; then
   profile cfg2_analytic snapshot_lm_kernel -- python3 bench.py $SHORT --jacobian analytic
 fi
 if want cfg3; then   # the bench's own cfg3 leg (both modes in one run: fusion_lm_kernel<1> = numeric = `value`, <0> = analytic)
-  ALSO_TAG=cfg3_analytic ALSO_KER="fusion_lm_kernel<0>" profile cfg3_numeric "fusion_lm_kernel<1>" -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --legs cfg3 --datagen numpy
+  ALSO_TAG=cfg3_analytic ALSO_KER="fusion_lm_kernel<0>" profile cfg3_numeric "fusion_lm_kernel<1>" -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --legs cfg3 --datagen numpy
 fi
 W="tests/perf/bench_window.py --reps 3 --no-latency --cpu-n 0 --jacobian numeric"
 if want cfg5; then
