@@ -26,7 +26,8 @@ extern "C" {
 #define LOC_ABI_VERSION 4 /* 2: jacobian mode for every solver, resident window solves, loc_node_add_rl_range;
                            * 3: numeric (g2o) Jacobians are the default everywhere, loc_shard_*, loc_window_last_kernel_kind;
                            * 4: loc_window_set_option / _last_host_timing, loc_node_flush_tail / _last_kernel_kind, loc_fusion_timing_*;
-                           *    a large loc_window_solve_host drops the resident batch */
+                           *    a large loc_window_solve_host drops the resident batch;
+                           *    (additive, same version) loc_window_covariance_host / _resident / loc_window_last_covariance_ms */
 
 typedef enum loc_status {
     LOC_OK = 0,
@@ -296,6 +297,35 @@ void* loc_window_poses_device(loc_window* w);   /* double [B][nv_max][12] */
 void* loc_window_result_device(loc_window* w);  /* double [B][8] */
 int loc_window_timing_begin(loc_window* w, int32_t max_launches);
 int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, double* avg_ms);
+/* Marginal pose covariances of CHAIN windows: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
+ * (rho'_e = 1 / (1 + chi2_e) on every range edge and on every EdgeSE3 whose robust flag is set — g2o's robustInformation without rho''; priors
+ * not robustified; range Jacobians in the handle's mode, loc_window_set_jacobian; no LM damping), in g2o VertexSE3's minimal coordinates
+ * [dt (body frame), dq_xyz] applied as x * fromVectorMQT(d); Sigma_i = [H^-1]_ii.  Unlike g2o's computeMarginals (which re-factors the H of the
+ * last linearisation, one step behind x) the result is a function of the returned estimate alone.  A coordinate whose diagonal entry of H is
+ * exactly 0 (a rotation without lever arm or rotation prior; every rotation of a translation-only batch) is excluded: its rows / columns are 0
+ * and its bit is set in the mask.  A window whose block Cholesky meets a pivot that is not finite or not positive (the solve kernels' test), or
+ * that is at most 1e-11 of its coordinate's diagonal entry of H (numerically singular: a rank-deficient H leaves pivots of rounding size and
+ * either sign — e.g. a window that ranges ONE anchor per pose, as every configuration under cfg/ does: 2T - 1 rank-one terms for 3T translations),
+ * gets LOC_ERR_SINGULAR and NaN in all its blocks; the other windows are not affected.  Same host layouts as loc_window_solve_host:
+ *   cov    double [n][nv_max][36]  row-major 6x6 per pose slot (slots >= nv: 0)
+ *   mask   int32  [n][nv_max]      excluded coordinates, bits 0-5 = tx ty tz qx qy qz
+ *   status int32  [n]              LOC_OK or LOC_ERR_SINGULAR (that window's blocks NaN)
+ * LOC_ERR_UNSUPPORTED (nothing written) unless every window is a chain of <= 64 poses (nv_max <= 64) without endpoint-1 lever arms (the handle
+ * has none set: loc_window_set_endpoint1_offsets(w, 0, NULL)): every pose-to-pose edge, range or EdgeSE3, joins consecutive slots (several per
+ * pair, a missing link, any edge order).
+ * Stateless: does not change the handle's resident batch, last kernel kind / ms, topology cache or options.  Synchronous.  Small calls (inputs
+ * and outputs within the 4 MiB staging block) travel as loc_window_solve_host's small ones do; larger ones stage through a device block of
+ * their own — unlike a large loc_window_solve_host they leave the resident batch intact. */
+int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses,
+                               const int32_t* r_idx, const double* r_val, const int32_t* p_idx, const double* p_val,
+                               const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask, int32_t* status);
+/* The same for the uploaded batch at loc_window_poses_device()'s current content (after loc_window_solve_resident: the solved poses),
+ * asynchronous on hip_stream (NULL = the handle's own stream; it waits for the last resident launch), into caller-owned device arrays of the
+ * layouts above.  LOC_ERR_INVALID before the first resident solve of an upload.  The batch's structure is checked once per upload: for an
+ * upload that no solve kernel already classified as a chain, on the first call, which then copies the uploaded tables back and is synchronous. */
+int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev);
+/* kernel time of the last covariance launch of this handle (HIP events on its stream; a resident launch is waited for), milliseconds */
+int loc_window_last_covariance_ms(loc_window* w, double* ms);
 
 /* ================================================================================================
  * Node front-end — `class Localization` behind the ABI (one moving tag, its ring window, its anchors).

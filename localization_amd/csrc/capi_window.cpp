@@ -98,6 +98,14 @@ struct loc_window {
     bool timing = false;
     // small calls (a node's single window): all inputs travel as one page-locked block, all outputs as another
     char *h_stage = nullptr, *d_stage = nullptr;
+    // marginal covariances (loc_window_covariance_*): a device block of their own for batches beyond the staging block, HIP events of
+    // their own (the solve's last_kernel_ms stays as it is), the resident batch's verdict (set by loc_window_upload)
+    char* d_cov = nullptr;
+    size_t cov_cap = 0;
+    hipEvent_t cov_ev0 = nullptr, cov_ev1 = nullptr;
+    bool cov_pending = false;       // the events of a resident covariance launch have not been read yet
+    double cov_ms = 0.0;
+    int resident_cov = 0;           // 3 / 6: the resident batch's block size; 0: not a covariance batch; -1: not classified yet
 };
 static constexpr size_t kStageBytes = 4u << 20;
 
@@ -146,6 +154,9 @@ int loc_window_destroy(loc_window* w) {
     if (w->ev0) (void)hipEventDestroy(w->ev0);
     if (w->ev1) (void)hipEventDestroy(w->ev1);
     if (w->resident_done) (void)hipEventDestroy(w->resident_done);
+    if (w->d_cov) (void)hipFree(w->d_cov);
+    if (w->cov_ev0) (void)hipEventDestroy(w->cov_ev0);
+    if (w->cov_ev1) (void)hipEventDestroy(w->cov_ev1);
     if (w->stream) (void)hipStreamDestroy(w->stream);
     delete w;
     return LOC_OK;
@@ -188,6 +199,7 @@ int loc_window_create(loc_window** out, int32_t device, int64_t batch, const loc
         (e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreate(&w->ev0)) != hipSuccess || (e = hipEventCreate(&w->ev1)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&w->resident_done, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreate(&w->cov_ev0)) != hipSuccess || (e = hipEventCreate(&w->cov_ev1)) != hipSuccess ||
         (n_anchors > 0 && (e = hipMemcpy(w->d_anchors, anchors, (size_t)n_anchors * 3 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess)) {
         loc_window_destroy(w);
         return locamd_fail_hip(e, "loc_window_create");
@@ -719,6 +731,55 @@ static unsigned long long hash_structure(const loc_window* w, int64_t n, const i
     return h;
 }
 
+// The chain scan: every pose-to-pose edge (range or SE3) of every window joins consecutive pose slots.  ordered: edges are also listed
+// in the order of their later pose and priors in pose order (what the lane-per-window and wave-per-window solve kernels walk); the
+// covariance pass takes any order.  single_pairs / se3_pairs: batch_topology's pair counts (only meaningful for chain batches, where
+// every range was scanned).
+static void chain_scan(const loc_window* w, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* p_idx, const int32_t* s_idx,
+                       bool ordered, bool& chain, bool& single_pairs, bool& se3_pairs) {
+    const locamd::WindowCaps& c = w->caps;
+    std::atomic<bool> a_chain{true}, a_single{true}, a_single_r{true}, a_single_s{true}, a_any_s{false};
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
+        bool chain_l = true, single_l = true, single_r = true, single_s = true, any_s = false;
+        for (int64_t i = lo; i < hi && chain_l && a_chain.load(std::memory_order_relaxed); ++i) {
+            const int32_t* cn = counts + i * 4;
+            if (cn[3] != 0) { single_l = false; any_s = true; }
+            int last = 0;
+            for (int e = 0; e < cn[3]; ++e) {   // EdgeSE3 factors: between consecutive poses, ordered by their later pose (addTwistEdge)
+                const int32_t* ix = s_idx + ((size_t)i * c.ns_max + e) * 4;
+                const int key2 = ix[1] > ix[0] ? ix[1] : ix[0];
+                if ((ordered && key2 < last) || (ix[0] - ix[1] != 1 && ix[1] - ix[0] != 1)) { chain_l = false; break; }
+                if (key2 == last) single_s = false;   // (a second EdgeSE3 on the same pair; poses are numbered from 0, so `last` = 0 is no pair)
+                last = key2;
+            }
+            last = 0;
+            int last_pair = -1;
+            for (int e = 0; e < cn[1] && chain_l; ++e) {
+                const int32_t* ix = r_idx + ((size_t)i * c.nr_max + e) * 2;
+                const int key2 = ix[1] > ix[0] ? ix[1] : ix[0];
+                if (ordered && key2 < last) chain_l = false;
+                if (ix[1] >= 0) { if (key2 == last_pair) { single_l = false; single_r = false; } last_pair = key2; }
+                last = key2;
+                if (ix[1] >= 0 && ix[0] - ix[1] != 1 && ix[1] - ix[0] != 1) chain_l = false;
+            }
+            last = 0;
+            for (int e = 0; e < cn[2] && chain_l && ordered; ++e) {
+                const int32_t v = p_idx[(size_t)i * c.np_max + e];
+                if (v < last) chain_l = false;
+                last = v;
+            }
+        }
+        if (!chain_l) a_chain.store(false);
+        if (!single_l) a_single.store(false);
+        if (!single_r) a_single_r.store(false);
+        if (!single_s) a_single_s.store(false);
+        if (any_s) a_any_s.store(true);
+    });
+    chain = a_chain.load();
+    single_pairs = a_single.load();
+    se3_pairs = a_any_s.load() && a_single_r.load() && a_single_s.load();
+}
+
 // what the batch qualifies for BY ITS STRUCTURE: LOC_WINDOW_KERNEL_GENERAL, _CHAIN (block-tridiagonal, 6-DoF), _CHAIN3, _ARROW3 or _TREE
 // (for _ARROW3 the edge lists are left in w->h_a*)
 // which: the set of host-built tables ARROW3 / TREE fill (0: a loc_window_solve_host call, 1: the resident batch).
@@ -741,48 +802,7 @@ static int batch_topology(loc_window* w, int which, int64_t n, const int32_t* co
     bool single_pairs = true;   // no EdgeSE3 anywhere and at most one range edge per pair of consecutive poses (wave6_lm_kernel's rank-1 couplings)
     bool se3_pairs = false;     // EdgeSE3 factors, at most one per pair of consecutive poses, and at most one range edge per pair (wave6_lm_kernel<JAC, true>)
     if (hit) { chain = tc.chain; single_pairs = tc.single_pairs; se3_pairs = tc.se3_pairs; }
-    if (!hit) {
-        std::atomic<bool> a_chain{true}, a_single{true}, a_single_r{true}, a_single_s{true}, a_any_s{false};
-        parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
-            bool chain_l = true, single_l = true, single_r = true, single_s = true, any_s = false;
-            for (int64_t i = lo; i < hi && chain_l && a_chain.load(std::memory_order_relaxed); ++i) {
-                const int32_t* cn = counts + i * 4;
-                if (cn[3] != 0) { single_l = false; any_s = true; }
-                int last = 0;
-                for (int e = 0; e < cn[3]; ++e) {   // EdgeSE3 factors: between consecutive poses, ordered by their later pose (addTwistEdge)
-                    const int32_t* ix = s_idx + ((size_t)i * c.ns_max + e) * 4;
-                    const int key2 = ix[1] > ix[0] ? ix[1] : ix[0];
-                    if (key2 < last || (ix[0] - ix[1] != 1 && ix[1] - ix[0] != 1)) { chain_l = false; break; }
-                    if (key2 == last) single_s = false;   // (a second EdgeSE3 on the same pair; poses are numbered from 0, so `last` = 0 is no pair)
-                    last = key2;
-                }
-                last = 0;
-                int last_pair = -1;
-                for (int e = 0; e < cn[1] && chain_l; ++e) {
-                    const int32_t* ix = r_idx + ((size_t)i * c.nr_max + e) * 2;
-                    const int key2 = ix[1] > ix[0] ? ix[1] : ix[0];
-                    if (key2 < last) chain_l = false;
-                    if (ix[1] >= 0) { if (key2 == last_pair) { single_l = false; single_r = false; } last_pair = key2; }
-                    last = key2;
-                    if (ix[1] >= 0 && ix[0] - ix[1] != 1 && ix[1] - ix[0] != 1) chain_l = false;
-                }
-                last = 0;
-                for (int e = 0; e < cn[2] && chain_l; ++e) {
-                    const int32_t v = p_idx[(size_t)i * c.np_max + e];
-                    if (v < last) chain_l = false;
-                    last = v;
-                }
-            }
-            if (!chain_l) a_chain.store(false);
-            if (!single_l) a_single.store(false);
-            if (!single_r) a_single_r.store(false);
-            if (!single_s) a_single_s.store(false);
-            if (any_s) a_any_s.store(true);
-        });
-        chain = a_chain.load();
-        single_pairs = a_single.load();   // (only meaningful for chain batches, where every range was scanned)
-        se3_pairs = a_any_s.load() && a_single_r.load() && a_single_s.load();
-    }
+    if (!hit) chain_scan(w, n, counts, r_idx, p_idx, s_idx, true, chain, single_pairs, se3_pairs);
     if (use_cache && !hit) { tc.valid = true; tc.key = key; tc.n = n; tc.chain = chain; tc.single_pairs = single_pairs; tc.se3_pairs = se3_pairs; tc.tree_tried = false; tc.tree_ok = false; }
     if (chain) {
         if (translation_only(w, n, counts, poses, r_val, p_val)) return LOC_WINDOW_KERNEL_CHAIN3;
@@ -853,6 +873,17 @@ static int pick_kernel(const loc_window* w, int64_t n, int topology) {
     if (topology == LOC_WINDOW_KERNEL_CHAIN3 && !w->opt.chain3) return LOC_WINDOW_KERNEL_CHAIN;   // the 6-DoF kernel on a translation-only batch (A/B runs, tests)
     return topology;
 }
+// The block size the covariance pass computes a batch with (covariance_kernel.hip): 3 for translation-only batches, 6 otherwise; 0 = not
+// covered (LOC_ERR_UNSUPPORTED): a window that is not a chain (in any edge order), more than 64 poses, lever arms on endpoint 1.
+static int covariance_kind(const loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                           const int32_t* p_idx, const double* p_val, const int32_t* s_idx) {
+    if (w->has_off1 || w->caps.nv_max > 64 || locamd::window_covariance_lds_bytes(w->caps, false) > 160 * 1024) return 0;
+    bool chain = false, single_pairs = false, se3_pairs = false;
+    chain_scan(w, n, counts, r_idx, p_idx, s_idx, false, chain, single_pairs, se3_pairs);
+    if (!chain) return 0;
+    return translation_only(w, n, counts, poses, r_val, p_val) ? 3 : 6;
+}
+
 static hipError_t launch_any(loc_window* w, int which, const locamd::WindowArgs& a, hipStream_t st, int kind) {
     loc_window::WinAux& A = w->aux[which];
     w->last_kind = kind;
@@ -1099,7 +1130,7 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     LOC_HIP(hipStreamSynchronize(w->stream));
     if (int rc = wait_resident(w)) return rc;
     // (a failing step below must not leave a half-described resident batch behind: nothing is resident until everything is)
-    w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_min_anchors = 0;
+    w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_min_anchors = 0; w->resident_cov = 0;
     if (!w->d_poses_in) LOC_HIP(hipMalloc((void**)&w->d_poses_in, (size_t)w->B * c.nv_max * 12 * sizeof(double)));
     LOC_HIP(hipMemcpy(w->d_counts, counts, N * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
     LOC_HIP(hipMemcpy(w->d_poses_in, poses, N * c.nv_max * 12 * sizeof(double), hipMemcpyHostToDevice));
@@ -1126,6 +1157,11 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
         }
     w->resident_min_anchors = max_anchor;
     w->resident_topology = topology;
+    // the block size of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
+    // classified by the first loc_window_covariance_resident call (an upload costs nothing more for callers that never ask)
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3) w->resident_cov = 3;
+    else if (topology == LOC_WINDOW_KERNEL_CHAIN || topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) w->resident_cov = 6;
+    else w->resident_cov = -1;
     w->resident_solved = false;
     w->n_resident = n;
     return LOC_OK;
@@ -1207,6 +1243,146 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
 int loc_window_last_kernel_ms(loc_window* w, double* ms) {
     if (!w || !ms) return locamd_fail(LOC_ERR_INVALID, "null");
     *ms = w->last_ms;
+    return LOC_OK;
+}
+
+// ---- marginal covariances (covariance_kernel.hip) -------------------------------------------------------------------------------------
+int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                               const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
+                               int32_t* status) {
+    if (!cov || !mask || !status) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
+    {
+        const int rc = validate_instances(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val);
+        if (rc != LOC_OK) return rc;
+    }
+    const int kind = covariance_kind(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx);
+    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host: every window must be a chain of <= 64 poses without endpoint-1 lever arms");
+    const locamd::WindowCaps& c = w->caps;
+    LOC_HIP(hipSetDevice(w->device));
+    {
+        const int rc = flush_anchors(w);
+        if (rc != LOC_OK) return rc;
+    }
+    const size_t N = (size_t)n;
+    // one block: outputs [cov | mask | status], then the inputs [poses | counts | r_val | p_val | s_val | r_idx | p_idx | s_idx]
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t sz[11] = {al(N * c.nv_max * 36 * sizeof(double)), al(N * c.nv_max * sizeof(int32_t)), al(N * sizeof(int32_t)),
+                           al(N * c.nv_max * 12 * sizeof(double)), al(N * 4 * sizeof(int32_t)), al(N * c.nr_max * 5 * sizeof(double)),
+                           al(N * c.np_max * 18 * sizeof(double)), al(N * c.ns_max * 48 * sizeof(double)), al(N * c.nr_max * 2 * sizeof(int32_t)),
+                           al(N * c.np_max * sizeof(int32_t)), al(N * c.ns_max * 4 * sizeof(int32_t))};
+    size_t off[12]; off[0] = 0;
+    for (int i = 0; i < 11; ++i) off[i + 1] = off[i] + sz[i];
+    const void* src[8] = {poses, counts, r_val, p_val, s_val, r_idx, p_idx, s_idx};
+    const size_t bytes[8] = {N * c.nv_max * 12 * sizeof(double), N * 4 * sizeof(int32_t), N * c.nr_max * 5 * sizeof(double), N * c.np_max * 18 * sizeof(double),
+                             N * c.ns_max * 48 * sizeof(double), N * c.nr_max * 2 * sizeof(int32_t), N * c.np_max * sizeof(int32_t), N * c.ns_max * 4 * sizeof(int32_t)};
+    hipStream_t st = w->stream;
+    char* d;
+    const bool small = off[11] <= kStageBytes;
+    if (small) {   // (the staging block of loc_window_solve_host: free between calls, never used by a resident launch)
+        if (!w->h_stage) LOC_HIP(hipHostMalloc((void**)&w->h_stage, kStageBytes, hipHostMallocDefault));
+        if (!w->d_stage) LOC_HIP(hipMalloc((void**)&w->d_stage, kStageBytes));
+        for (int k = 0; k < 8; ++k) if (bytes[k]) std::memcpy(w->h_stage + off[3 + k], src[k], bytes[k]);
+        d = w->d_stage;
+        LOC_HIP(hipMemcpyAsync(d + off[3], w->h_stage + off[3], off[11] - off[3], hipMemcpyHostToDevice, st));
+    } else {       // a device block of the covariance's own: the resident batch's arrays are not touched
+        if (w->cov_cap < off[11]) {
+            if (w->d_cov) (void)hipFree(w->d_cov);
+            w->d_cov = nullptr; w->cov_cap = 0;
+            LOC_HIP(hipMalloc((void**)&w->d_cov, off[11]));
+            w->cov_cap = off[11];
+        }
+        d = w->d_cov;
+        for (int k = 0; k < 8; ++k) if (bytes[k]) LOC_HIP(hipMemcpyAsync(d + off[3 + k], src[k], bytes[k], hipMemcpyHostToDevice, st));
+    }
+    locamd::WindowArgs a;
+    a.poses = (double*)(d + off[3]); a.poses_in = a.poses; a.counts = (const int32_t*)(d + off[4]);
+    a.r_val = (const double*)(d + off[5]); a.p_val = (const double*)(d + off[6]); a.s_val = (const double*)(d + off[7]);
+    a.r_idx = (const int32_t*)(d + off[8]); a.p_idx = (const int32_t*)(d + off[9]); a.s_idx = (const int32_t*)(d + off[10]);
+    a.r_off1 = nullptr; a.anchors = w->d_anchors; a.result = nullptr; a.workspace = nullptr;
+    a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->natural_order; a.caps = c;
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    hipError_t e = locamd::launch_window_covariance(a, kind == 3, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    if (small) {
+        LOC_HIP(hipMemcpyAsync(w->h_stage, d, off[3], hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipStreamSynchronize(st));
+        std::memcpy(cov, w->h_stage + off[0], N * c.nv_max * 36 * sizeof(double));
+        std::memcpy(mask, w->h_stage + off[1], N * c.nv_max * sizeof(int32_t));
+        std::memcpy(status, w->h_stage + off[2], N * sizeof(int32_t));
+    } else {
+        LOC_HIP(hipMemcpyAsync(cov, d + off[0], N * c.nv_max * 36 * sizeof(double), hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipMemcpyAsync(mask, d + off[1], N * c.nv_max * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipMemcpyAsync(status, d + off[2], N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipStreamSynchronize(st));
+    }
+    float ms = 0;
+    LOC_HIP(hipEventElapsedTime(&ms, w->cov_ev0, w->cov_ev1));
+    w->cov_ms = ms;
+    w->cov_pending = false;
+    return LOC_OK;
+}
+
+int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev) {
+    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
+    if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
+    LOC_HIP(hipSetDevice(w->device));
+    if (w->resident_cov < 0 && !w->has_off1 && w->caps.nv_max <= 64) {
+        // first call on an upload no solve kernel classified as a chain: the uploaded tables come back once and are scanned on the host
+        if (int rc = wait_resident(w)) return rc;
+        const locamd::WindowCaps& c = w->caps;
+        const size_t N = (size_t)w->n_resident;
+        std::vector<int32_t> counts(N * 4), ridx(N * c.nr_max * 2 + 1), pidx(N * c.np_max + 1), sidx(N * c.ns_max * 4 + 1);
+        std::vector<double> poses(N * c.nv_max * 12), rval(N * c.nr_max * 5 + 1), pval(N * c.np_max * 18 + 1);
+        LOC_HIP(hipMemcpy(counts.data(), w->d_counts, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        LOC_HIP(hipMemcpy(poses.data(), w->d_poses_in, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (c.nr_max) {
+            LOC_HIP(hipMemcpy(ridx.data(), w->d_ridx, N * c.nr_max * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+            LOC_HIP(hipMemcpy(rval.data(), w->d_rval, N * c.nr_max * 5 * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (c.np_max) {
+            LOC_HIP(hipMemcpy(pidx.data(), w->d_pidx, N * c.np_max * sizeof(int32_t), hipMemcpyDeviceToHost));
+            LOC_HIP(hipMemcpy(pval.data(), w->d_pval, N * c.np_max * 18 * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (c.ns_max) LOC_HIP(hipMemcpy(sidx.data(), w->d_sidx, N * c.ns_max * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        w->resident_cov = covariance_kind(w, (int64_t)N, counts.data(), poses.data(), ridx.data(), rval.data(), pidx.data(), pval.data(), sidx.data());
+    }
+    if (w->has_off1 || w->caps.nv_max > 64 || w->resident_cov <= 0)
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident: every window must be a chain of <= 64 poses without endpoint-1 lever arms");
+    {
+        const int rc = flush_anchors(w);
+        if (rc != LOC_OK) return rc;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    locamd::WindowArgs a;
+    a.counts = w->d_counts; a.poses = w->d_poses; a.poses_in = w->d_poses; a.r_idx = w->d_ridx; a.r_val = w->d_rval; a.p_idx = w->d_pidx;
+    a.p_val = w->d_pval; a.s_idx = w->d_sidx; a.s_val = w->d_sval; a.r_off1 = nullptr; a.anchors = w->d_anchors; a.result = nullptr;
+    a.workspace = nullptr; a.n_anchors = w->n_anchors; a.B = (int)w->n_resident; a.iterations = w->iterations; a.jacobian = w->jacobian;
+    a.natural_order = w->natural_order; a.caps = w->caps;
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    hipError_t e = locamd::launch_window_covariance(a, w->resident_cov == 3, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    // whatever overwrites the resident arrays next waits for this launch as well
+    LOC_HIP(hipEventRecord(w->resident_done, st));
+    w->resident_inflight = true;
+    w->cov_pending = true;
+    return LOC_OK;
+}
+
+int loc_window_last_covariance_ms(loc_window* w, double* ms) {
+    if (!w || !ms) return locamd_fail(LOC_ERR_INVALID, "null");
+    if (w->cov_pending) {
+        LOC_HIP(hipSetDevice(w->device));
+        LOC_HIP(hipEventSynchronize(w->cov_ev1));
+        float t = 0;
+        LOC_HIP(hipEventElapsedTime(&t, w->cov_ev0, w->cov_ev1));
+        w->cov_ms = t;
+        w->cov_pending = false;
+    }
+    *ms = w->cov_ms;
     return LOC_OK;
 }
 

@@ -1,0 +1,397 @@
+// gfx950 (MI355X / CDNA4): marginal pose covariances of CHAIN windows of <= 64 poses, one WAVE per window.
+//
+// What it computes: for a window with estimate x (the poses in WindowArgs::poses — the solve's output),
+//   H = sum_e J_e^T (rho'_e Omega_e) J_e  at x, no LM damping,
+// rho'_e = 1 / (1 + chi2_e) on every range edge and on every EdgeSE3 whose robust flag is set (g2o's robustInformation without rho''),
+// priors plain; range Jacobians as the handle's mode says (g2o central differences, delta = 1e-9: range_jac_numeric; or analytic), the
+// prior and EdgeSE3 ones analytic as in the solve kernels.  Coordinates: g2o VertexSE3's minimal increment [dt (body frame), dq_xyz]
+// applied as x * fromVectorMQT(d).  Output per pose slot v: Sigma_v = [H^-1]_vv (6x6, row-major).
+// Unconstrained coordinates (a diagonal entry of H exactly 0.0 — H is a sum of J^T W J with W > 0, so its row and column are 0) are
+// excluded: the diagonal is taken as 1 in the factorisation, the output rows / columns are 0 and the coordinate's bit is set in the
+// pose's mask (bits 0-5: tx ty tz qx qy qz).  A window whose factorisation meets a pivot that fails window_kernel.hip's test (its
+// reciprocal square root is NaN / inf: not finite or <= 0) or that is at most 1e-11 of its coordinate's diagonal entry of H (numerically
+// singular: a rank-deficient H) gets status LOC_ERR_SINGULAR and NaN in every block.
+//
+// Mapping (one workgroup of one wave per window):
+//   * linearisation: lane = edge (chunks of 64), the edge's Jacobian blocks / its share of H into a record in LDS; the shared device
+//     helpers do the work (range_jac_numeric: window_device.h, chain_se3_terms<true>: se3_edge_device.h);
+//   * assembly: lane = entry (r, c) of a D x D block, the records of a chunk added in edge order (no atomics: every entry is owned by one
+//     lane, so the result is the same bits on every run): H_ii and H_{i+1,i} in LDS (64 x 2 x 36 doubles = 36 KB for 64 poses);
+//   * block-tridiagonal factorisation, pose after pose: S_0 = H_00, K_i = H_{i+1,i} S_i^-1, S_{i+1} = H_{i+1,i+1} - K_i H_{i,i+1}; every
+//     lane factors S_i (Cholesky, pivots checked) in its registers and keeps entry (r, c) of S_i^-1 = L^-T L^-1;
+//   * selected inversion, backwards: Sigma_{n-1} = S_{n-1}^-1, Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (lane = entry).
+// D = 3 for translation-only batches (capi_window.cpp: translation_only — 3x3 blocks, the rotation bits always set), D = 6 otherwise.
+#include "se3_edge_device.h"
+
+#include <float.h>
+#include <math.h>
+
+#include <atomic>
+
+namespace locamd {
+
+namespace {
+
+extern __shared__ double cvlds[];
+
+constexpr int kCovChunk = 64;   // edges linearised per pass (one per lane)
+constexpr double kCovRelPivot = 1e-11;   // relative pivot threshold
+constexpr int kCovSRec = 21 + 21 + 36;   // EdgeSE3 record: H_ii, H_jj (lower triangles), the coupling block (rows: the later pose, column-major)
+
+// LDS layout of one window (offsets in doubles; the int tables follow the doubles)
+struct CovLayout {
+    int hd, ho, kb, dg, rrec, prec, srec, ints, ri, pi, si, mk;
+    size_t bytes;
+};
+__host__ __device__ inline CovLayout cov_layout(int nvl, int D, bool priors, bool se3) {
+    CovLayout l;
+    const int DD = D * D;
+    int p = 0;
+    l.hd = p; p += nvl * DD;                   // H_ii -> S_i -> S_i^-1 -> Sigma_i
+    l.ho = p; p += nvl * DD;                   // H_{i+1,i} -> K_i
+    l.kb = p; p += DD;                         // K_i / T of the current step
+    l.dg = p; p += nvl * D;                    // diag(H) of every coordinate (the scale of the relative pivot test)
+    l.rrec = p; p += kCovChunk * (1 + 2 * D);  // range: rho' info, J0 (D), J1 (D)
+    l.prec = p; if (priors) p += kCovChunk * 21;
+    l.srec = p; if (se3) p += kCovChunk * kCovSRec;
+    l.ints = p;
+    int q = 0;
+    l.ri = q; q += 2 * kCovChunk;
+    l.pi = q; if (priors) q += kCovChunk;
+    l.si = q; if (se3) q += 2 * kCovChunk;
+    l.mk = q; q += nvl;
+    l.bytes = (size_t)p * sizeof(double) + (size_t)q * sizeof(int);
+    return l;
+}
+
+#define CV_TRI(r, c) ((r) >= (c) ? (r) * ((r) + 1) / 2 + (c) : (c) * ((c) + 1) / 2 + (r))
+
+// one unary EdgeSE3Prior at X: its J^T W J (lower triangle, 21) — window_kernel.hip: evaluate_edges, unary priors
+__device__ __forceinline__ void cov_prior_block(const double* val, const double* X, double* rec) {
+    double RE[9], tE[3], q[4];
+    mat_mul(val, X, RE);
+    mat_vec(val, X + 9, tE);
+    mat_to_quat(RE, q);
+    quat_normalize_sign(q);
+    double J[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) J[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
+    quat_right_jac(q, 1.0, J, 6);
+    const double* W = val + 12;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int cc = 0; cc <= r; ++cc) {
+            double h = 0.0;
+            if ((r < 3) == (cc < 3)) {
+#pragma unroll
+                for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) h += J[i * 6 + r] * W[i] * J[i * 6 + cc];
+            }
+            rec[r * (r + 1) / 2 + cc] = h;
+        }
+}
+
+// one range edge (no lever arm on endpoint 1): rho' info, J0 (D columns of the pose carrying the lever arm), J1 (D columns of the other pose)
+template <int D, int JAC>
+__device__ __forceinline__ void cov_range_rec(const double* X0, const double* X1, const double* p1, bool pose1, const double* val, double* rec) {
+    const double meas = val[0], info = val[1];
+    const double off[3] = {val[2], val[3], val[4]};
+    double J0[6] = {0, 0, 0, 0, 0, 0}, J1[6] = {0, 0, 0, 0, 0, 0};
+    double err;
+    if (JAC == 0) {
+        double p0[3];
+        mat_vec(X0, off, p0);
+        double u[3] = {(p0[0] + X0[9]) - p1[0], (p0[1] + X0[10]) - p1[1], (p0[2] + X0[11]) - p1[2]};
+        const double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        err = meas - n;
+        const double inv = n > 0.0 ? 1.0 / n : 0.0;   // coincident endpoints: J = 0 (what the central difference gives)
+        u[0] *= inv; u[1] *= inv; u[2] *= inv;
+        double uR[3];
+        mat_tvec(X0, u, uR);
+        J0[0] = -uR[0]; J0[1] = -uR[1]; J0[2] = -uR[2];
+        J0[3] = 2.0 * (uR[1] * off[2] - uR[2] * off[1]);   // dp0/dv = -2 R0 [o]x  =>  de/dv0 = 2 (uR x o)
+        J0[4] = 2.0 * (uR[2] * off[0] - uR[0] * off[2]);
+        J0[5] = 2.0 * (uR[0] * off[1] - uR[1] * off[0]);
+        if (pose1) {
+            double uR1[3];
+            mat_tvec(X1, u, uR1);
+            J1[0] = uR1[0]; J1[1] = uR1[1]; J1[2] = uR1[2];
+        }
+    } else {
+        err = range_error_plain(X0, X0 + 9, off, p1, meas);
+        J0[0] = range_jac_numeric<0>(X0, off, X1, p1, 0, meas);
+        J0[1] = range_jac_numeric<1>(X0, off, X1, p1, 0, meas);
+        J0[2] = range_jac_numeric<2>(X0, off, X1, p1, 0, meas);
+        if (D == 6) {
+            J0[3] = range_jac_numeric<3>(X0, off, X1, p1, 0, meas);
+            J0[4] = range_jac_numeric<4>(X0, off, X1, p1, 0, meas);
+            J0[5] = range_jac_numeric<5>(X0, off, X1, p1, 0, meas);
+        }
+        if (pose1) {   // (without a lever arm, rotating endpoint 1 does not move its point: those columns are exactly 0)
+            J1[0] = range_jac_numeric<0>(X0, off, X1, p1, 1, meas);
+            J1[1] = range_jac_numeric<1>(X0, off, X1, p1, 1, meas);
+            J1[2] = range_jac_numeric<2>(X0, off, X1, p1, 1, meas);
+        }
+    }
+    const double chi = err * (info * err);
+    rec[0] = (1.0 / (1.0 + chi)) * info;   // rho' Omega
+#pragma unroll
+    for (int k = 0; k < D; ++k) { rec[1 + k] = J0[k]; rec[1 + D + k] = J1[k]; }
+}
+
+template <int D, int JAC>
+__global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int nvl, bool priors, bool se3, double* cov, int32_t* mask, int32_t* status) {
+    constexpr int DD = D * D;
+    constexpr int RS = 1 + 2 * D;
+    const int lane = threadIdx.x;
+    const long long inst = blockIdx.x;
+    const WindowCaps& cp = a.caps;
+    const int nvm = cp.nv_max;
+    const CovLayout lay = cov_layout(nvl, D, priors, se3);
+    double* Hd = cvlds + lay.hd;
+    double* Ho = cvlds + lay.ho;
+    double* Kb = cvlds + lay.kb;
+    double* dg = cvlds + lay.dg;
+    double* rrec = cvlds + lay.rrec;
+    double* prec = cvlds + lay.prec;
+    double* srec = cvlds + lay.srec;
+    int* ib = reinterpret_cast<int*>(cvlds + lay.ints);
+    int* ri = ib + lay.ri;
+    int* pi = ib + lay.pi;
+    int* si = ib + lay.si;
+    int* mk = ib + lay.mk;
+    const int nv = a.counts[inst * 4 + 0], nr = a.counts[inst * 4 + 1], np = a.counts[inst * 4 + 2], ns = se3 ? a.counts[inst * 4 + 3] : 0;
+    const double* P = a.poses + (size_t)inst * nvm * 12;
+    const int r = lane / D, c = lane % D;
+    const bool ent = lane < DD;
+    for (int k = lane; k < nv * DD; k += 64) { Hd[k] = 0.0; Ho[k] = 0.0; }
+
+    // ---- linearisation + assembly --------------------------------------------------------------------------------------------------
+    for (int e0 = 0; e0 < nr; e0 += kCovChunk) {
+        __syncthreads();
+        const int e = e0 + lane;
+        if (e < nr) {
+            const int32_t* ix = a.r_idx + ((size_t)inst * cp.nr_max + e) * 2;
+            const double* val = a.r_val + ((size_t)inst * cp.nr_max + e) * 5;
+            const int v0 = ix[0], v1 = ix[1];
+            double X0[12], X1[12], p1[3];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) X0[k] = P[v0 * 12 + k];
+            const int v1c = v1 >= 0 ? v1 : v0;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) X1[k] = P[v1c * 12 + k];
+            if (v1 >= 0) { p1[0] = X1[9]; p1[1] = X1[10]; p1[2] = X1[11]; }
+            else { const double* an = a.anchors + (size_t)(-1 - v1) * 3; p1[0] = an[0]; p1[1] = an[1]; p1[2] = an[2]; }
+            cov_range_rec<D, JAC>(X0, X1, p1, v1 >= 0, val, rrec + lane * RS);
+            ri[2 * lane] = v0; ri[2 * lane + 1] = v1;
+        }
+        __syncthreads();
+        if (ent) {
+            const int m = min(kCovChunk, nr - e0);
+            for (int k = 0; k < m; ++k) {
+                const double* q = rrec + k * RS;
+                const int a0 = ri[2 * k], a1 = ri[2 * k + 1];
+                const double w = q[0];
+                Hd[a0 * DD + lane] += w * (q[1 + r] * q[1 + c]);
+                if (a1 >= 0) {
+                    Hd[a1 * DD + lane] += w * (q[1 + D + r] * q[1 + D + c]);
+                    if (a1 == a0 + 1) Ho[a0 * DD + lane] += w * (q[1 + D + r] * q[1 + c]);   // rows: the later pose
+                    else Ho[a1 * DD + lane] += w * (q[1 + r] * q[1 + D + c]);
+                }
+            }
+        }
+    }
+    for (int e0 = 0; e0 < np; e0 += kCovChunk) {
+        __syncthreads();
+        const int e = e0 + lane;
+        if (e < np) {
+            const int v = a.p_idx[(size_t)inst * cp.np_max + e];
+            cov_prior_block(a.p_val + ((size_t)inst * cp.np_max + e) * 18, P + v * 12, prec + lane * 21);
+            pi[lane] = v;
+        }
+        __syncthreads();
+        if (ent) {
+            const int m = min(kCovChunk, np - e0);
+            for (int k = 0; k < m; ++k) Hd[pi[k] * DD + lane] += prec[k * 21 + CV_TRI(r, c)];
+        }
+    }
+    if (D == 6) {
+        for (int e0 = 0; e0 < ns; e0 += kCovChunk) {
+            __syncthreads();
+            const int e = e0 + lane;
+            if (e < ns) {
+                const int32_t* ix = a.s_idx + ((size_t)inst * cp.ns_max + e) * 4;
+                const int vi = ix[0], vj = ix[1];
+                double Xi[12], Xj[12], bi[6], bj[6], rterm;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) { Xi[k] = P[vi * 12 + k]; Xj[k] = P[vj * 12 + k]; }
+                double* q = srec + lane * kCovSRec;
+                chain_se3_terms<true>(Xi, Xj, a.s_val + ((size_t)inst * cp.ns_max + e) * 48, ix[2] != 0, vj > vi, q, q + 21, q + 42, bi, bj, rterm);
+                si[2 * lane] = vi; si[2 * lane + 1] = vj;
+            }
+            __syncthreads();
+            if (ent) {
+                const int m = min(kCovChunk, ns - e0);
+                for (int k = 0; k < m; ++k) {
+                    const double* q = srec + k * kCovSRec;
+                    const int vi = si[2 * k], vj = si[2 * k + 1];
+                    Hd[vi * DD + lane] += q[CV_TRI(r, c)];
+                    Hd[vj * DD + lane] += q[21 + CV_TRI(r, c)];
+                    Ho[min(vi, vj) * DD + lane] += q[42 + 6 * c + r];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- excluded coordinates: a diagonal entry exactly 0 (its row and column are 0 as well) ---------------------------------------------
+    if (lane < nv) {
+        int bits = D == 3 ? 0x38 : 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            if (Hd[lane * DD + k * D + k] == 0.0) { bits |= 1 << k; Hd[lane * DD + k * D + k] = 1.0; }
+            dg[lane * D + k] = Hd[lane * DD + k * D + k];
+        }
+        mk[lane] = bits;
+    }
+    __syncthreads();
+
+    // ---- forward: S_i, its Cholesky factor, S_i^-1, K_i ------------------------------------------------------------------------------
+    bool ok = true;
+    for (int i = 0; i < nv; ++i) {
+        double A[D][D];
+#pragma unroll
+        for (int cc = 0; cc < D; ++cc)
+#pragma unroll
+            for (int rr = cc; rr < D; ++rr) A[rr][cc] = Hd[i * DD + rr * D + cc];
+        double ig[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            // numerically singular: the pivot is at most kCovRelPivot of the coordinate's diagonal entry of H (a rank-deficient H leaves pivots of
+            // rounding size, 1e-16 .. 1e-14 of it, and of either sign: the absolute test alone would pass half of them); NaN fails as well
+            ok = ok && A[j][j] > kCovRelPivot * dg[i * D + j];
+            const double g = pivot_rsqrt(A[j][j]);
+            ig[j] = g;
+#pragma unroll
+            for (int i2 = j + 1; i2 < D; ++i2) A[i2][j] *= g;
+#pragma unroll
+            for (int i2 = j + 1; i2 < D; ++i2)
+#pragma unroll
+                for (int cc = j + 1; cc <= i2; ++cc) A[i2][cc] = __builtin_fma(-A[i2][j], A[cc][j], A[i2][cc]);
+        }
+        double sg = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) sg += ig[j];
+        ok = ok && sg < DBL_MAX;   // (a pivot <= 0 or not finite: NaN / inf — window_kernel.hip's test)
+        // L^-1 (lower): diagonal ig, below it -ig_i sum_k L_ik Linv_kc
+        double Li[D][D];
+#pragma unroll
+        for (int cc = 0; cc < D; ++cc) {
+            Li[cc][cc] = ig[cc];
+#pragma unroll
+            for (int rr = cc + 1; rr < D; ++rr) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = cc; k < rr; ++k) s = __builtin_fma(A[rr][k], Li[k][cc], s);
+                Li[rr][cc] = -ig[rr] * s;
+            }
+        }
+        double sinv = 0.0;   // entry (r, c) of S_i^-1 = L^-T L^-1
+        if (ent) {
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+                if (k >= r && k >= c) sinv = __builtin_fma(Li[k][r], Li[k][c], sinv);
+        }
+        __syncthreads();
+        if (ent) Hd[i * DD + lane] = sinv;
+        __syncthreads();
+        if (i + 1 < nv) {
+            double kr = 0.0;   // K_i = H_{i+1,i} S_i^-1
+            if (ent) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) kr = __builtin_fma(Ho[i * DD + r * D + k], Hd[i * DD + k * D + c], kr);
+                Kb[lane] = kr;
+            }
+            __syncthreads();
+            double s = 0.0;    // (K_i H_{i,i+1})_rc = sum_k K_rk H_{i+1,i}[c][k]
+            if (ent) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) s = __builtin_fma(Kb[r * D + k], Ho[i * DD + c * D + k], s);
+            }
+            __syncthreads();
+            if (ent) { Ho[i * DD + lane] = kr; Hd[(i + 1) * DD + lane] -= s; }
+            __syncthreads();
+        }
+    }
+    // ---- backward: Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i ---------------------------------------------------------------------------
+    for (int i = nv - 2; i >= 0; --i) {
+        if (ent) {
+            double t = 0.0;   // T = Sigma_{i+1} K_i
+#pragma unroll
+            for (int k = 0; k < D; ++k) t = __builtin_fma(Hd[(i + 1) * DD + r * D + k], Ho[i * DD + k * D + c], t);
+            Kb[lane] = t;
+        }
+        __syncthreads();
+        if (ent) {
+            double s = Hd[i * DD + lane];
+#pragma unroll
+            for (int k = 0; k < D; ++k) s = __builtin_fma(Ho[i * DD + k * D + r], Kb[k * D + c], s);
+            Hd[i * DD + lane] = s;
+        }
+        __syncthreads();
+    }
+    // ---- output: symmetric 6x6 per slot, excluded rows / columns 0, NaN for a singular window --------------------------------------
+    double* out = cov + (size_t)inst * nvm * 36;
+    for (int k = lane; k < nvm * 36; k += 64) {
+        const int v = k / 36, rr = (k % 36) / 6, cc = k % 6;
+        double x = 0.0;
+        if (v < nv) {
+            if (!ok) x = __builtin_nan("");
+            else if (rr < D && cc < D && !((mk[v] >> rr) & 1) && !((mk[v] >> cc) & 1))
+                x = (Hd[v * DD + rr * D + cc] + Hd[v * DD + cc * D + rr]) * 0.5;
+        }
+        out[k] = x;
+    }
+    for (int v = lane; v < nvm; v += 64) mask[(size_t)inst * nvm + v] = v < nv ? mk[v] : 0;
+    if (lane == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+}
+#undef CV_TRI
+
+template <int D, int JAC>
+hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
+    static std::atomic<uint64_t> attr_set{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&covariance_kernel<D, JAC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        attr_set.fetch_or(bit, std::memory_order_release);
+    }
+    hipLaunchKernelGGL((covariance_kernel<D, JAC>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3) {
+    return cov_layout(c.nv_max, d3 ? 3 : 6, c.np_max > 0, !d3 && c.ns_max > 0).bytes;
+}
+
+hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
+    if (a.B <= 0) return hipSuccess;
+    if (a.caps.nv_max > 64) return hipErrorInvalidValue;
+    const bool priors = a.caps.np_max > 0, se3 = !d3 && a.caps.ns_max > 0;
+    const size_t lds = window_covariance_lds_bytes(a.caps, d3);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (d3) return a.jacobian ? launch_cov_t<3, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream)
+                              : launch_cov_t<3, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream);
+    return a.jacobian ? launch_cov_t<6, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream)
+                      : launch_cov_t<6, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream);
+}
+
+}  // namespace locamd

@@ -105,6 +105,11 @@ struct TreeSched {
                               //      consecutive columns); roots: nv - nroots, nv - nroots + 1, ...
     int nv, nr, np, ns, depth, nroots, nlev, max_se3_per_node, nu, max_r_per_node;
 };
+// marginal pose covariances of chain windows of <= 64 poses at a.poses (covariance_kernel.hip): one wave per window, 3x3 blocks for
+// translation-only batches (d3), 6x6 otherwise; cov [B][nv_max][36], mask [B][nv_max], status [B] (device arrays)
+size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3);
+hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

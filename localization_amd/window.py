@@ -141,6 +141,42 @@ class WindowSolver:
         check(self.L.loc_window_download(self.h, wb.poses.ctypes.data_as(dp), wb.result.ctypes.data_as(dp)))
         return wb.result
 
+    # ---- marginal pose covariances at the given (solved) estimates (loc_window_covariance_*)
+    def covariance(self, wb: WindowBatch, out=None):
+        """Sigma_i = [H^-1]_ii of every pose of every window at wb.poses (chain windows of <= 64 poses).  Returns (cov [B][nv_max][6][6],
+        mask [B][nv_max] — excluded coordinates, bits 0-5 = tx ty tz qx qy qz —, status [B]: 0 or LOC_ERR_SINGULAR, that window's blocks NaN)."""
+        assert wb.caps == self.caps and wb.B <= self.B
+        if getattr(wb, "r_off1", None) is not None:   # (refused here: the handle's endpoint-1 lever arms belong to its solves and stay as they are)
+            raise _lib.LocalizationAmdError(-5, "covariance: windows with endpoint-1 lever arms are not supported")
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if out is None:
+            out = (np.zeros((wb.B, self.caps[0], 6, 6)), np.zeros((wb.B, self.caps[0]), dtype=np.int32), np.zeros(wb.B, dtype=np.int32))
+        cov, mask, status = out   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
+        assert cov.dtype == np.float64 and cov.size >= wb.B * self.caps[0] * 36 and cov.flags["C_CONTIGUOUS"]
+        assert mask.dtype == np.int32 and mask.size >= wb.B * self.caps[0] and status.dtype == np.int32 and status.size >= wb.B
+        check(self.L.loc_window_covariance_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
+                                                wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
+                                                wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
+                                                wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp),
+                                                cov.ctypes.data_as(dp), mask.ctypes.data_as(ip), status.ctypes.data_as(ip)))
+        return cov, mask, status
+
+    def covariance_resident(self, cov, mask, status, stream=None):
+        """The same for the uploaded batch at its solved poses (after solve_resident), asynchronous, into torch device tensors: cov float64
+        [B][nv_max][6][6] (or [..][36]), mask int32 [B][nv_max], status int32 [B].  stream: a torch stream (None: the handle's own stream)."""
+        import torch
+        n = getattr(self, "_resident", 0)
+        for t, dt, numel in ((cov, torch.float64, n * self.caps[0] * 36), (mask, torch.int32, n * self.caps[0]), (status, torch.int32, n)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= numel
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_covariance_resident(self.h, st, C.c_void_p(cov.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                    C.c_void_p(status.data_ptr())))
+
+    def last_covariance_ms(self):
+        ms = C.c_double()
+        check(self.L.loc_window_last_covariance_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def timing_begin(self, max_launches):
         check(self.L.loc_window_timing_begin(self.h, int(max_launches)))
 
