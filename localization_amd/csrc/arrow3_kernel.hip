@@ -45,8 +45,8 @@
 // slower), or in LDS with one row of the trailing update per lane (1.7x slower: 36 dependent LDS round trips per step);
 // B transposed to [border row][component][chain row] (coalesced for the thread-parallel phases, but the forward sweep's 39 lanes
 // then touch 39 cache lines per load: the sweep +20 %, the whole solve +7 %).
-#include "window_kernel.h"
-#include "device_math.h"
+#include "window_device.h"
+#include "lm_damping.h"
 
 #include <float.h>
 #include <math.h>
@@ -89,57 +89,7 @@ extern __shared__ double ldsA[];
 #endif
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_or_zero(double v, double identity) {
-    const int ilo = __double2loint(identity), ihi = __double2hiint(identity);
-    const int lo = __builtin_amdgcn_update_dpp(ilo, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(ihi, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-// the value of lane - 1 / lane + 1 (wave_shr:1 / wave_shl:1 cross the 16-lane rows on gfx9; no neighbour: 0), of lane l (wave-uniform l)
-__device__ __forceinline__ double lane_from_prev(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_from_next(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double read_lane_dyn(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double read_lane63(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum(double v) {   // DPP row shifts + row broadcasts: every lane gets the same bits
-    v += dpp_or_zero<0x111, 0xF>(v, 0.0);
-    v += dpp_or_zero<0x112, 0xF>(v, 0.0);
-    v += dpp_or_zero<0x114, 0xF>(v, 0.0);
-    v += dpp_or_zero<0x118, 0xF>(v, 0.0);
-    v += dpp_or_zero<0x142, 0xA>(v, 0.0);
-    v += dpp_or_zero<0x143, 0xC>(v, 0.0);
-    return read_lane63(v);
-}
-__device__ __forceinline__ double wave_max(double v) {   // non-negative inputs
-    v = fmax(v, dpp_or_zero<0x111, 0xF>(v, 0.0));
-    v = fmax(v, dpp_or_zero<0x112, 0xF>(v, 0.0));
-    v = fmax(v, dpp_or_zero<0x114, 0xF>(v, 0.0));
-    v = fmax(v, dpp_or_zero<0x118, 0xF>(v, 0.0));
-    v = fmax(v, dpp_or_zero<0x142, 0xA>(v, 0.0));
-    v = fmax(v, dpp_or_zero<0x143, 0xC>(v, 0.0));
-    return read_lane63(v);
-}
-// one wave per workgroup: LDS operations of a wave execute in order; the fence keeps the compiler from moving them
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// the same for data that only THIS wave exchanges through LDS while global loads are in flight: the workgroup-scope fences of wsync()
+// wave_sync() for data that only THIS wave exchanges through LDS while global loads are in flight: the workgroup-scope fences of wave_sync()
 // also wait for every outstanding global load (vmcnt(0)) — in the forward sweep that serialised the prefetch of the next B rows
 // (an HBM round trip per four rows).  LDS operations of one wave complete in order; this waits for them only.
 __device__ __forceinline__ void wsync_lds() {
@@ -171,35 +121,6 @@ __device__ __forceinline__ void map3_scan(Map3& m, const int lane) {
     map3_scan_step<0x142, 0xA>(m, ((lane >> 4) & 1) != 0);
     map3_scan_step<0x143, 0xC>(m, lane >= 32);
 }
-__device__ __forceinline__ double pivot_rsqrtA(double d) {   // window_kernel.hip: pivot_rsqrt
-    const double y = __builtin_amdgcn_rsq(d);
-    const double t = d * y;
-    const double e = __builtin_fma(-t, y, 1.0);
-    const double pq = __builtin_fma(0.375, e, 0.5);
-    const double ye = y * e;
-    return __builtin_fma(ye, pq, y);
-}
-
-#pragma clang fp contract(off)
-__device__ __forceinline__ double sq3_plainA(double dx, double dy, double dz) { return dx * dx + dy * dy + dz * dz; }
-// g2o's central difference along axis D of endpoint `which` (chain3_kernel.hip: range_jac_numeric3); NEAR: the perturbed norms
-// from the central one n0 (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers)
-template <int D, bool NEAR>
-__device__ __forceinline__ double range_jac_numericA(const double* p0, const double* p1, int which, double meas, double n0, double h0) {
-    constexpr double delta = 1e-9;
-    constexpr double scalar = 1.0 / (2 * delta);
-    double a[3] = {p0[0], p0[1], p0[2]}, b[3] = {p1[0], p1[1], p1[2]}, am[3] = {p0[0], p0[1], p0[2]}, bm[3] = {p1[0], p1[1], p1[2]};
-    if (which == 0) { a[D] = delta + p0[D]; am[D] = -delta + p0[D]; }
-    else { b[D] = delta + p1[D]; bm[D] = -delta + p1[D]; }
-    const double xp = sq3_plainA(a[0] - b[0], a[1] - b[1], a[2] - b[2]), xm = sq3_plainA(am[0] - bm[0], am[1] - bm[1], am[2] - bm[2]);
-    const double ep = meas - (NEAR ? sqrt_ieee_near_c(xp, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xp));
-    const double em = meas - (NEAR ? sqrt_ieee_near_c(xm, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xm));
-    double bak = ep;
-    bak -= em;
-    return scalar * bak;
-}
-#pragma clang fp contract(fast)
-
 // where one instance's arrays live
 struct ArrowCtx {
     // LDS (doubles)
@@ -253,7 +174,7 @@ __device__ __forceinline__ EdgeTerms range_terms(const double* p0, const double*
         const double x = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
         sqrt_and_rsqrt(x, n, inv_n);
         if (!(x > 0.0)) { n = 0.0; inv_n = 0.0; }   // coincident endpoints: J = 0, what the central difference gives
-    } else { x0 = sq3_plainA(u[0], u[1], u[2]); n = sqrt_ieee_unscaled_h(x0, h0); }
+    } else { x0 = sq_norm_plain(u[0], u[1], u[2]); n = sqrt_ieee_unscaled_h(x0, h0); }
     const double err = meas - n;
     t.chi = err * (info * err);
     const double aux = 1.0 + t.chi;
@@ -266,22 +187,22 @@ __device__ __forceinline__ EdgeTerms range_terms(const double* p0, const double*
         } else {
             t.J1[0] = 0.0; t.J1[1] = 0.0; t.J1[2] = 0.0;
             if (x0 >= 1e-5 && x0 < 1e300) {   // endpoints more than ~3 mm apart
-                t.J0[0] = range_jac_numericA<0, true>(p0, p1, 0, meas, n, h0);
-                t.J0[1] = range_jac_numericA<1, true>(p0, p1, 0, meas, n, h0);
-                t.J0[2] = range_jac_numericA<2, true>(p0, p1, 0, meas, n, h0);
+                t.J0[0] = range_jac_numeric_t<0, true>(p0, p1, 0, meas, n, h0);
+                t.J0[1] = range_jac_numeric_t<1, true>(p0, p1, 0, meas, n, h0);
+                t.J0[2] = range_jac_numeric_t<2, true>(p0, p1, 0, meas, n, h0);
                 if (moving1) {
-                    t.J1[0] = range_jac_numericA<0, true>(p0, p1, 1, meas, n, h0);
-                    t.J1[1] = range_jac_numericA<1, true>(p0, p1, 1, meas, n, h0);
-                    t.J1[2] = range_jac_numericA<2, true>(p0, p1, 1, meas, n, h0);
+                    t.J1[0] = range_jac_numeric_t<0, true>(p0, p1, 1, meas, n, h0);
+                    t.J1[1] = range_jac_numeric_t<1, true>(p0, p1, 1, meas, n, h0);
+                    t.J1[2] = range_jac_numeric_t<2, true>(p0, p1, 1, meas, n, h0);
                 }
             } else {
-                t.J0[0] = range_jac_numericA<0, false>(p0, p1, 0, meas, n, h0);
-                t.J0[1] = range_jac_numericA<1, false>(p0, p1, 0, meas, n, h0);
-                t.J0[2] = range_jac_numericA<2, false>(p0, p1, 0, meas, n, h0);
+                t.J0[0] = range_jac_numeric_t<0, false>(p0, p1, 0, meas, n, h0);
+                t.J0[1] = range_jac_numeric_t<1, false>(p0, p1, 0, meas, n, h0);
+                t.J0[2] = range_jac_numeric_t<2, false>(p0, p1, 0, meas, n, h0);
                 if (moving1) {
-                    t.J1[0] = range_jac_numericA<0, false>(p0, p1, 1, meas, n, h0);
-                    t.J1[1] = range_jac_numericA<1, false>(p0, p1, 1, meas, n, h0);
-                    t.J1[2] = range_jac_numericA<2, false>(p0, p1, 1, meas, n, h0);
+                    t.J1[0] = range_jac_numeric_t<0, false>(p0, p1, 1, meas, n, h0);
+                    t.J1[1] = range_jac_numeric_t<1, false>(p0, p1, 1, meas, n, h0);
+                    t.J1[2] = range_jac_numeric_t<2, false>(p0, p1, 1, meas, n, h0);
                 }
             }
         }
@@ -605,13 +526,13 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
             double uu, uv, vvq, ub, vb;
             {
                 double a00 = pk[0] + lambda, a10 = pk[1], a11 = pk[2] + lambda, a20 = pk[3], a21 = pk[4], a22 = pk[5] + lambda;
-                const double i0 = pivot_rsqrtA(a00);
+                const double i0 = pivot_rsqrt(a00);
                 a10 *= i0; a20 *= i0;
                 a11 = __builtin_fma(-a10, a10, a11); a21 = __builtin_fma(-a20, a10, a21); a22 = __builtin_fma(-a20, a20, a22);
-                const double i1 = pivot_rsqrtA(a11);
+                const double i1 = pivot_rsqrt(a11);
                 a21 *= i1;
                 a22 = __builtin_fma(-a21, a21, a22);
-                const double i2 = pivot_rsqrtA(a22);
+                const double i2 = pivot_rsqrt(a22);
                 double P0 = u0 * i0, Q0 = vn0 * i0, R0 = pk[6] * i0;
                 double P1 = __builtin_fma(-P0, a10, u1) * i1, Q1 = __builtin_fma(-Q0, a10, vn1) * i1, R1 = __builtin_fma(-R0, a10, pk[7]) * i1;
                 double P2 = __builtin_fma(-P1, a21, __builtin_fma(-P0, a20, u2)) * i2, Q2 = __builtin_fma(-Q1, a21, __builtin_fma(-Q0, a20, vn2)) * i2;
@@ -630,19 +551,19 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
                 al = __builtin_fma(kuv, uv, vvq);
                 be = __builtin_fma(kuv, __builtin_fma(-pbe, uu, ub), __builtin_fma(-pbe, uv, vb));
             }
-            cal = read_lane_dyn(al, rows - 1); cbe = read_lane_dyn(be, rows - 1);
+            cal = read_lane(al, rows - 1); cbe = read_lane(be, rows - 1);
             // S_p = A_p - alpha_p u u^T = G_p G_p^T; y_p; g of the next row
             const double su0 = ain * u0, su1 = ain * u1, su2 = ain * u2;
             double a00 = __builtin_fma(-su0, u0, pk[0] + lambda), a10 = __builtin_fma(-su1, u0, pk[1]), a11 = __builtin_fma(-su1, u1, pk[2] + lambda);
             double a20 = __builtin_fma(-su2, u0, pk[3]), a21 = __builtin_fma(-su2, u1, pk[4]), a22 = __builtin_fma(-su2, u2, pk[5] + lambda);
             const double r0 = __builtin_fma(-u0, bin, pk[6]), r1 = __builtin_fma(-u1, bin, pk[7]), r2 = __builtin_fma(-u2, bin, pk[8]);
-            const double ig0 = pivot_rsqrtA(a00);
+            const double ig0 = pivot_rsqrt(a00);
             a10 *= ig0; a20 *= ig0;
             a11 = __builtin_fma(-a10, a10, a11); a21 = __builtin_fma(-a20, a10, a21); a22 = __builtin_fma(-a20, a20, a22);
-            const double ig1 = pivot_rsqrtA(a11);
+            const double ig1 = pivot_rsqrt(a11);
             a21 *= ig1;
             a22 = __builtin_fma(-a21, a21, a22);
-            const double ig2 = pivot_rsqrtA(a22);
+            const double ig2 = pivot_rsqrt(a22);
             if (__ballot(live && !((ig0 + ig1) + ig2 < DBL_MAX))) ok = false;
             const double y0 = r0 * ig0;
             const double y1 = __builtin_fma(-y0, a10, r1) * ig1;
@@ -652,7 +573,7 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
             const double z2 = __builtin_fma(-z1, a21, __builtin_fma(-z0, a20, vn2)) * ig2;
             double g0 = lane_from_prev(z0), g1 = lane_from_prev(z1), g2 = lane_from_prev(z2);
             if (lane == 0) { g0 = cg0; g1 = cg1; g2 = cg2; }
-            cg0 = read_lane_dyn(z0, rows - 1); cg1 = read_lane_dyn(z1, rows - 1); cg2 = read_lane_dyn(z2, rows - 1);
+            cg0 = read_lane(z0, rows - 1); cg1 = read_lane(z1, rows - 1); cg2 = read_lane(z2, rows - 1);
             if (live) {
                 double* gz = c.GZ + 12 * p;
                 gz[0] = a10; gz[1] = a20; gz[2] = a21; gz[3] = ig0; gz[4] = ig1; gz[5] = ig2; gz[6] = y0; gz[7] = y1; gz[8] = y2;
@@ -660,7 +581,7 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
             }
         }
     }
-    wsync();
+    wave_sync();
 #if defined(LOCAMD_ARROW_TIMING) && LOCAMD_ARROW_TIMING == 3
     AT(2);   // (level 3: slot 2 = the chain's factor alone, slot 6 += the border rows + matrix cores)
 #endif
@@ -787,13 +708,13 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
             const int j0 = 3 * J;
             double d00 = c.S[tri(j0, j0)], d10 = c.S[tri(j0 + 1, j0)], d11 = c.S[tri(j0 + 1, j0 + 1)];
             double d20 = c.S[tri(j0 + 2, j0)], d21 = c.S[tri(j0 + 2, j0 + 1)], d22 = c.S[tri(j0 + 2, j0 + 2)];
-            const double g0 = pivot_rsqrtA(d00);
+            const double g0 = pivot_rsqrt(d00);
             d10 *= g0; d20 *= g0;
             d11 = __builtin_fma(-d10, d10, d11); d21 = __builtin_fma(-d20, d10, d21); d22 = __builtin_fma(-d20, d20, d22);
-            const double g1 = pivot_rsqrtA(d11);
+            const double g1 = pivot_rsqrt(d11);
             d21 *= g1;
             d22 = __builtin_fma(-d21, d21, d22);
-            const double g2 = pivot_rsqrtA(d22);
+            const double g2 = pivot_rsqrt(d22);
             ok = ok && ((g0 + g1) + g2 < DBL_MAX);
             __syncthreads();   // (everybody has read the diagonal block)
             if (tid == 0) { c.S[tri(j0 + 1, j0)] = d10; c.S[tri(j0 + 2, j0)] = d20; c.S[tri(j0 + 2, j0 + 1)] = d21; c.RA[j0] = g0; c.RA[j0 + 1] = g1; c.RA[j0 + 2] = g2; }
@@ -847,7 +768,7 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
 #pragma unroll
         for (int j = DM - 1; j >= 0; --j) {
             if (j < D) {
-                const double xj = read_lane_dyn(y * rinv, j);
+                const double xj = read_lane(y * rinv, j);
                 if (lane == j) xv = xj;
                 y = __builtin_fma(-col[j], xj, y);
             }
@@ -910,9 +831,9 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
             const double bz = m.b0 * cz0 + m.b1 * cz1 + m.b2 * cz2;   // (every lane's composite starts at the chunk's first row: b = that row's g)
             const double z0 = __builtin_fma(m.a0, bz, m.c0), z1 = __builtin_fma(m.a1, bz, m.c1), z2 = __builtin_fma(m.a2, bz, m.c2);
             if (live) { c.GZ[12 * p + 6] = z0; c.GZ[12 * p + 7] = z1; c.GZ[12 * p + 8] = z2; }
-            cz0 = read_lane_dyn(z0, rows - 1); cz1 = read_lane_dyn(z1, rows - 1); cz2 = read_lane_dyn(z2, rows - 1);
+            cz0 = read_lane(z0, rows - 1); cz1 = read_lane(z1, rows - 1); cz2 = read_lane(z2, rows - 1);
         }
-        wsync();
+        wave_sync();
         // x_p = G_p^-T (z_p - g_{p+1} (u_{p+1} . x_{p+1})), chunks from the segment's end
         double cx0 = 0.0, cx1 = 0.0, cx2 = 0.0, cu0 = 0.0, cu1 = 0.0, cu2 = 0.0, cg0 = 0.0, cg1 = 0.0, cg2 = 0.0;   // x, u, g of the row after this chunk
         const int nchunks = (s1 - s0 + 63) / 64;
@@ -943,9 +864,9 @@ __device__ __forceinline__ bool arrow_solve(const ArrowCtx& c, double lambda, in
             const double bx = m.b0 * cx0 + m.b1 * cx1 + m.b2 * cx2;   // (b of every lane's composite: u of the row after the chunk)
             const double x0 = __builtin_fma(m.a0, bx, m.c0), x1 = __builtin_fma(m.a1, bx, m.c1), x2 = __builtin_fma(m.a2, bx, m.c2);
             if (live) { c.GZ[12 * p + 6] = x0; c.GZ[12 * p + 7] = x1; c.GZ[12 * p + 8] = x2; }
-            cx0 = read_lane_dyn(x0, rows - 1); cx1 = read_lane_dyn(x1, rows - 1); cx2 = read_lane_dyn(x2, rows - 1);
-            cu0 = read_lane_dyn(u0, rows - 1); cu1 = read_lane_dyn(u1, rows - 1); cu2 = read_lane_dyn(u2, rows - 1);
-            cg0 = read_lane_dyn(G[9], rows - 1); cg1 = read_lane_dyn(G[10], rows - 1); cg2 = read_lane_dyn(G[11], rows - 1);
+            cx0 = read_lane(x0, rows - 1); cx1 = read_lane(x1, rows - 1); cx2 = read_lane(x2, rows - 1);
+            cu0 = read_lane(u0, rows - 1); cu1 = read_lane(u1, rows - 1); cu2 = read_lane(u2, rows - 1);
+            cg0 = read_lane(G[9], rows - 1); cg1 = read_lane(G[10], rows - 1); cg2 = read_lane(G[11], rows - 1);
         }
     }
     __syncthreads();
@@ -1018,8 +939,6 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
     if (tid < 16) c.red[tid] = 0.0;
     __threadfence_block();
     __syncthreads();
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, trials = 0, terminated = 0, buf = 0, shared_edges = 0;
     AT_DECL;
@@ -1036,7 +955,7 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
             AT(1);
             cur_chi = chi_lin;
             last_plain = plain;
-            if (it == 0) { lambda = tau * md; ni = 2.0; }
+            if (it == 0) { lambda = lm_tau * md; ni = 2.0; }
             int q = 0;
             double rho = 0.0;
             do {
@@ -1057,12 +976,13 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
                 AT(7);
                 last_plain = plain2;
                 if (!ok) temp_chi = DBL_MAX;
-                rho = (cur_chi - temp_chi) / (sc + 1e-3);
+                rho = (cur_chi - temp_chi) / (sc + lm_scale_eps);
                 if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
+                    // (lm_damping.h: lm_lambda_accepted, written out — called, it changes this kernel's machine code)
                     const double r21 = 2.0 * rho - 1.0;
                     double alpha = 1.0 - r21 * r21 * r21;
-                    alpha = fmin(alpha, good_hi);
-                    lambda *= fmax(good_lo, alpha);
+                    alpha = fmin(alpha, lm_good_hi);
+                    lambda *= fmax(lm_good_lo, alpha);
                     ni = 2.0;
                     cur_chi = temp_chi;
                     buf = 1 - buf;   // the trial state is the state
@@ -1071,9 +991,9 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
                     ni *= 2.0;
                 }
                 ++q;
-            } while (rho < 0.0 && q < max_trials);
+            } while (rho < 0.0 && q < lm_max_trials);
             ++it;
-            if (q == max_trials || rho == 0.0) { terminated = 1; break; }
+            if (q == lm_max_trials || rho == 0.0) { terminated = 1; break; }
         }
     }
     __syncthreads();

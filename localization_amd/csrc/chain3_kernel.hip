@@ -29,8 +29,8 @@
 // else 9 numbers) and the packed edges are requested one pose ahead.  Tried and dropped: scoring the trial state inside the
 // back-substitution (two dependent sweeps per trial instead of three) with H requested two poses ahead — 144 bytes of scratch
 // spills and no gain (1.77 ms): at 1 024 resident waves the kernel moves ~4 TB/s and is bound by that, not by the sweep count.
-#include "window_kernel.h"
-#include "device_math.h"
+#include "window_device.h"
+#include "lm_damping.h"
 
 #include <float.h>
 #include <math.h>
@@ -59,37 +59,6 @@ size_t window_chain3_workspace_doubles(const WindowCaps& c, long long B) {
 namespace {
 
 extern __shared__ double lds3[];
-
-__device__ __forceinline__ double pivot_rsqrt3(double d) {   // window_kernel.hip: pivot_rsqrt
-    const double y = __builtin_amdgcn_rsq(d);
-    const double t = d * y;
-    const double e = __builtin_fma(-t, y, 1.0);
-    const double pq = __builtin_fma(0.375, e, 0.5);
-    const double ye = y * e;
-    return __builtin_fma(ye, pq, y);
-}
-
-#pragma clang fp contract(off)
-// ||d|| the way a plain CPU build of computeError evaluates it (numeric_jacobian.h: range_error_plain with a zero lever arm)
-__device__ __forceinline__ double sq3_plain(double dx, double dy, double dz) { return dx * dx + dy * dy + dz * dz; }
-// g2o's central difference of e = meas - ||p0 - p1|| along axis D of endpoint `which`'s translation (numeric_jacobian.h /
-// window_kernel.hip: range_jac_numeric with R = I and a zero lever arm: X * fromVectorMQT(+-delta e_D) = (I, t +- delta e_D))
-// NEAR: the perturbed norms from the central one n0 (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers)
-template <int D, bool NEAR>
-__device__ __forceinline__ double range_jac_numeric3(const double* p0, const double* p1, int which, double meas, double n0, double h0) {
-    constexpr double delta = 1e-9;
-    constexpr double scalar = 1.0 / (2 * delta);
-    double a[3] = {p0[0], p0[1], p0[2]}, b[3] = {p1[0], p1[1], p1[2]}, am[3] = {p0[0], p0[1], p0[2]}, bm[3] = {p1[0], p1[1], p1[2]};
-    if (which == 0) { a[D] = delta + p0[D]; am[D] = -delta + p0[D]; }
-    else { b[D] = delta + p1[D]; bm[D] = -delta + p1[D]; }
-    const double xp = sq3_plain(a[0] - b[0], a[1] - b[1], a[2] - b[2]), xm = sq3_plain(am[0] - bm[0], am[1] - bm[1], am[2] - bm[2]);
-    const double ep = meas - (NEAR ? sqrt_ieee_near_c(xp, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xp));
-    const double em = meas - (NEAR ? sqrt_ieee_near_c(xm, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xm));
-    double bak = ep;
-    bak -= em;
-    return scalar * bak;
-}
-#pragma clang fp contract(fast)
 
 // where a window's arrays live: H, coupling blocks, x, edges in the HBM slab; (G, y) and the translations in LDS or in the slab
 struct Ctx3 {
@@ -169,7 +138,7 @@ __device__ __forceinline__ void chain3_sweep(const WindowArgs& a, const Ctx3& c,
             double u[3] = {p0[0] - p1[0], p0[1] - p1[1], p0[2] - p1[2]};
             double n = 0.0, x0 = 0.0, h0 = 0.0;
             if (JAC == 0) n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-            else { x0 = sq3_plain(u[0], u[1], u[2]); n = sqrt_ieee_unscaled_h(x0, h0); }
+            else { x0 = sq_norm_plain(u[0], u[1], u[2]); n = sqrt_ieee_unscaled_h(x0, h0); }
             const double err = meas - n;
             const double chi = err * (info * err);
             const double aux = 1.0 + chi;
@@ -185,22 +154,22 @@ __device__ __forceinline__ void chain3_sweep(const WindowArgs& a, const Ctx3& c,
                 } else {
                     J1[0] = 0; J1[1] = 0; J1[2] = 0;
                     if (x0 >= 1e-5 && x0 < 1e300) {   // endpoints more than ~3 mm apart
-                        J0[0] = range_jac_numeric3<0, true>(p0, p1, 0, meas, n, h0);
-                        J0[1] = range_jac_numeric3<1, true>(p0, p1, 0, meas, n, h0);
-                        J0[2] = range_jac_numeric3<2, true>(p0, p1, 0, meas, n, h0);
+                        J0[0] = range_jac_numeric_t<0, true>(p0, p1, 0, meas, n, h0);
+                        J0[1] = range_jac_numeric_t<1, true>(p0, p1, 0, meas, n, h0);
+                        J0[2] = range_jac_numeric_t<2, true>(p0, p1, 0, meas, n, h0);
                         if (v1 >= 0) {
-                            J1[0] = range_jac_numeric3<0, true>(p0, p1, 1, meas, n, h0);
-                            J1[1] = range_jac_numeric3<1, true>(p0, p1, 1, meas, n, h0);
-                            J1[2] = range_jac_numeric3<2, true>(p0, p1, 1, meas, n, h0);
+                            J1[0] = range_jac_numeric_t<0, true>(p0, p1, 1, meas, n, h0);
+                            J1[1] = range_jac_numeric_t<1, true>(p0, p1, 1, meas, n, h0);
+                            J1[2] = range_jac_numeric_t<2, true>(p0, p1, 1, meas, n, h0);
                         }
                     } else {
-                        J0[0] = range_jac_numeric3<0, false>(p0, p1, 0, meas, n, h0);
-                        J0[1] = range_jac_numeric3<1, false>(p0, p1, 0, meas, n, h0);
-                        J0[2] = range_jac_numeric3<2, false>(p0, p1, 0, meas, n, h0);
+                        J0[0] = range_jac_numeric_t<0, false>(p0, p1, 0, meas, n, h0);
+                        J0[1] = range_jac_numeric_t<1, false>(p0, p1, 0, meas, n, h0);
+                        J0[2] = range_jac_numeric_t<2, false>(p0, p1, 0, meas, n, h0);
                         if (v1 >= 0) {
-                            J1[0] = range_jac_numeric3<0, false>(p0, p1, 1, meas, n, h0);
-                            J1[1] = range_jac_numeric3<1, false>(p0, p1, 1, meas, n, h0);
-                            J1[2] = range_jac_numeric3<2, false>(p0, p1, 1, meas, n, h0);
+                            J1[0] = range_jac_numeric_t<0, false>(p0, p1, 1, meas, n, h0);
+                            J1[1] = range_jac_numeric_t<1, false>(p0, p1, 1, meas, n, h0);
+                            J1[2] = range_jac_numeric_t<2, false>(p0, p1, 1, meas, n, h0);
                         }
                     }
                 }
@@ -402,7 +371,7 @@ __device__ __forceinline__ bool chain3_factor_solve(const Ctx3& c, int nv, doubl
         double ig[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const double g = pivot_rsqrt3(A[j][j]);
+            const double g = pivot_rsqrt(A[j][j]);
             ig[j] = g;
 #pragma unroll
             for (int i2 = j + 1; i2 < 3; ++i2) A[i2][j] *= g;
@@ -535,8 +504,6 @@ __global__ void __launch_bounds__(64, 1) chain3_lm_kernel(const WindowArgs a, do
             for (int k = 0; k < 3; ++k) { P3(e, 1 + k) = pval[18 * e + 9 + k]; P3(e, 4 + k) = pval[18 * e + 12 + k]; }
         }
     }
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, q = 0, trials = 0, terminated = 0, buf = 0, shared_edges = 0;
     unsigned long long ho_kind = 0;
@@ -548,7 +515,7 @@ __global__ void __launch_bounds__(64, 1) chain3_lm_kernel(const WindowArgs a, do
                 double plain, md;
                 chain3_sweep<true, JAC, LT>(a, c, nv, nr, np, buf, cur_chi, plain, md, ho_kind, shared_edges);
                 last_plain = plain;
-                if (it == 0) { lambda = tau * md; ni = 2.0; }
+                if (it == 0) { lambda = lm_tau * md; ni = 2.0; }
                 q = 0;
                 need_lin = false;
             }
@@ -561,14 +528,11 @@ __global__ void __launch_bounds__(64, 1) chain3_lm_kernel(const WindowArgs a, do
             chain3_sweep<false, JAC, LT>(a, c, nv, nr, np, 1 - buf, temp_chi, plain2, md2, unused_kind, unused_shared);
             last_plain = plain2;
             if (!ok2) temp_chi = DBL_MAX;
-            const double scale = sc + 1e-3;
+            const double scale = sc + lm_scale_eps;
             const double rho = (cur_chi - temp_chi) / scale;
             bool iteration_over;
             if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
-                const double r21 = 2.0 * rho - 1.0;
-                double alpha = 1.0 - r21 * r21 * r21;
-                alpha = fmin(alpha, good_hi);
-                lambda *= fmax(good_lo, alpha);
+                lambda = lm_lambda_accepted(lambda, rho);
                 ni = 2.0;
                 cur_chi = temp_chi;
                 buf = 1 - buf;   // the trial state is the state
@@ -578,12 +542,12 @@ __global__ void __launch_bounds__(64, 1) chain3_lm_kernel(const WindowArgs a, do
                 lambda *= ni;
                 ni *= 2.0;      // (pop: the state was never overwritten)
                 ++q;
-                iteration_over = !(rho < 0.0 && q < max_trials);
+                iteration_over = !(rho < 0.0 && q < lm_max_trials);
             }
             if (iteration_over) {
                 ++it;
                 need_lin = true;
-                if (q == max_trials || rho == 0.0) { terminated = 1; done = true; }
+                if (q == lm_max_trials || rho == 0.0) { terminated = 1; done = true; }
                 if (it >= a.iterations) done = true;
             }
         }

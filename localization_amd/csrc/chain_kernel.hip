@@ -1,6 +1,7 @@
 // gfx950 (MI355X / CDNA4): chain_lm_kernel — chain windows, one LANE per window (split out of window_kernel.hip; the general solver and
 // the shared residual / g2o semantics are described there).
 #include "se3_edge_device.h"
+#include "lm_damping.h"
 
 namespace locamd {
 
@@ -604,8 +605,6 @@ __global__ void __launch_bounds__(64, 1) chain_lm_kernel(const WindowArgs a, dou
             }
         }
     }
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, q = 0, trials = 0, terminated = 0, buf = 0, shared_edges = 0;
     unsigned long long ho_kind = 0;
@@ -617,7 +616,7 @@ __global__ void __launch_bounds__(64, 1) chain_lm_kernel(const WindowArgs a, dou
                 double plain, md;
                 chain_sweep<true, JAC, SE3>(a, slab, inst, nv, nr, np, ns, buf, cur_chi, plain, md, ho_kind, shared_edges);
                 last_plain = plain;
-                if (it == 0) { lambda = tau * md; ni = 2.0; }
+                if (it == 0) { lambda = lm_tau * md; ni = 2.0; }
                 q = 0;
                 need_lin = false;
             }
@@ -631,14 +630,11 @@ __global__ void __launch_bounds__(64, 1) chain_lm_kernel(const WindowArgs a, dou
             chain_sweep<false, JAC, SE3>(a, slab, inst, nv, nr, np, ns, 1 - buf, temp_chi, plain2, md2, unused_kind, unused_shared);
             last_plain = plain2;
             if (!ok2) temp_chi = DBL_MAX;
-            const double scale = sc + 1e-3;
+            const double scale = sc + lm_scale_eps;
             const double rho = (cur_chi - temp_chi) / scale;
             bool iteration_over;
             if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
-                const double r21 = 2.0 * rho - 1.0;
-                double alpha = 1.0 - r21 * r21 * r21;
-                alpha = fmin(alpha, good_hi);
-                lambda *= fmax(good_lo, alpha);
+                lambda = lm_lambda_accepted(lambda, rho);
                 ni = 2.0;
                 cur_chi = temp_chi;
                 buf = 1 - buf;   // the trial state is the state
@@ -648,12 +644,12 @@ __global__ void __launch_bounds__(64, 1) chain_lm_kernel(const WindowArgs a, dou
                 lambda *= ni;
                 ni *= 2.0;      // (pop: the state was never overwritten)
                 ++q;
-                iteration_over = !(rho < 0.0 && q < max_trials);
+                iteration_over = !(rho < 0.0 && q < lm_max_trials);
             }
             if (iteration_over) {
                 ++it;
                 need_lin = true;
-                if (q == max_trials || rho == 0.0) { terminated = 1; done = true; }
+                if (q == lm_max_trials || rho == 0.0) { terminated = 1; done = true; }
                 if (it >= a.iterations) done = true;
             }
         }

@@ -17,6 +17,7 @@
 #include "fusion_kernel.h"
 #include "device_math.h"
 #include "numeric_jacobian.h"
+#include "lm_damping.h"
 
 #include <float.h>
 #include <math.h>
@@ -293,9 +294,6 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
     for (int j = 0; j < M8; ++j) { ax[j] = a.anchors[j * 3 + 0]; ay[j] = a.anchors[j * 3 + 1]; az[j] = a.anchors[j * 3 + 2]; }
     const double ox = a.offset[0], oy = a.offset[1], oz = a.offset[2];
 
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
-
     // ---- epoch data movement (see snapshot_kernel.hip for the window scheme) -----------------------------------------
     auto convert = [&](const float (&df)[M8], const float (&sf)[M8], const double (&im)[8], double (&dd)[M8], double (&ww)[M8],
                        double (&Rm)[9], double (&pi)[3]) {
@@ -415,7 +413,7 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
         const Pose T = oplus(X, x);
         const bool gate_now = active && init && (a.gate > 0.0) && (k >= a.gate_from_epoch);
         // computeScale needs the step and the accepted b only: formed here, so x is dead across the edge loop
-        double scale = 1e-3;
+        double scale = lm_scale_eps;
 #pragma unroll
         for (int i = 0; i < 6; ++i) scale = __builtin_fma(x[i], __builtin_fma(lambda, x[i], cur.b[i]), scale);
         const Sys6 tr = evaluate6<JAC>(T, ax, ay, az, ep, ox, oy, oz, gate_now, a.gate);
@@ -430,7 +428,7 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
                 double md = 0.0, tr6 = 0.0;
 #pragma unroll
                 for (int i = 0; i < 6; ++i) { md = fmax(md, fabs(tr.h[hidx(i, i)])); tr6 += tr.h[hidx(i, i)]; }
-                lambda = tau * md;  // computeLambdaInit
+                lambda = lm_tau * md;  // computeLambdaInit
                 ni = 2.0;
                 it = 0; q = 0; trials = 0;
                 finished = (a.iterations <= 0) || !(tr6 > 0.0);
@@ -441,10 +439,11 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
                 ++trials;
                 last_chi = tr.chi;
                 if (accept) {
+                    // (lm_damping.h: lm_lambda_accepted, written out — called, it changes this kernel's machine code)
                     const double r21 = 2.0 * rho - 1.0;
                     double alpha = 1.0 - r21 * r21 * r21;
-                    alpha = fmin(alpha, good_hi);
-                    lambda *= fmax(good_lo, alpha);
+                    alpha = fmin(alpha, lm_good_hi);
+                    lambda *= fmax(lm_good_lo, alpha);
                     ni = 2.0;
                     cur_chi = temp_chi;
                     X = T;
@@ -454,10 +453,10 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
                     ni *= 2.0;
                 }
                 ++q;
-                const bool again = (rho < 0.0) && (q < max_trials);
+                const bool again = (rho < 0.0) && (q < lm_max_trials);
                 if (!again) {
                     ++it;
-                    finished = (q == max_trials) || (rho == 0.0) || (it >= a.iterations);
+                    finished = (q == lm_max_trials) || (rho == 0.0) || (it >= a.iterations);
                     q = 0;
                 }
             }

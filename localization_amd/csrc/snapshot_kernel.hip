@@ -36,6 +36,7 @@
 //     192-byte anchor table, so there is no L2 reuse to steer: blockIdx -> XCD mapping is left to the dispatcher.
 #include "snapshot_kernel.h"
 #include "device_math.h"
+#include "lm_damping.h"
 
 #include <float.h>
 #include <math.h>
@@ -260,9 +261,6 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const SnapshotArgs a) 
         az[j] = a.anchors[(m0 + j) * 3 + 2];
     }
 
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
-
     // Epoch window [c, c+1]: every live lane of the wave works on epoch c or c+1.
     //   d, w   (registers): this lane's current epoch (k)
     //   s_next (LDS)      : epoch c+1, already converted to (measurement, information) for ALL lanes
@@ -367,7 +365,7 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const SnapshotArgs a) 
         const double temp_chi = ok2 ? tr.rchi : DBL_MAX;
         double scale = x0 * __builtin_fma(lambda, x0, cur.b0) + x1 * __builtin_fma(lambda, x1, cur.b1) +
                        x2 * __builtin_fma(lambda, x2, cur.b2);  // computeScale
-        scale += 1e-3;
+        scale += lm_scale_eps;
         const double rho = (cur_chi - temp_chi) * fast_rcp(scale);
         const bool accept = lm && (rho > 0.0) && (fabs(temp_chi) < DBL_MAX) && ok2;
         if (first || accept) {  // the trial's system is the next iteration's system (discardTop); first: it IS the system
@@ -375,19 +373,18 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const SnapshotArgs a) 
             cur_chi = tr.rchi;
             px = tx; py = ty; pz = tz;  // (first: tx == px)
         }
-        const double r21 = 2.0 * rho - 1.0;
-        const double lam_acc = lambda * fmax(good_lo, fmin(1.0 - r21 * r21 * r21, good_hi));
-        const double lam_first = tau * fmax(fabs(tr.h00), fmax(fabs(tr.h11), fabs(tr.h22)));  // computeLambdaInit
+        const double lam_acc = lm_lambda_accepted(lambda, rho);
+        const double lam_first = lm_tau * fmax(fabs(tr.h00), fmax(fabs(tr.h11), fabs(tr.h22)));  // computeLambdaInit
         lambda = first ? lam_first : (accept ? lam_acc : (lm ? lambda * ni : lambda));
         ni = (first || accept) ? 2.0 : (lm ? ni * 2.0 : ni);
         last_chi = active ? tr.chi : last_chi;
         trials = first ? 0 : trials + (lm ? 1 : 0);
         q = first ? 0 : q + (lm ? 1 : 0);
-        const bool end_iter = lm && !((rho < 0.0) && (q < max_trials));
+        const bool end_iter = lm && !((rho < 0.0) && (q < lm_max_trials));
         it = first ? 0 : it + (end_iter ? 1 : 0);
         // no active edge ("0 vertices to optimize") or nothing to iterate; LM: Terminate (10 failed trials or rho == 0) or done
         const bool finished = (first && ((a.iterations <= 0) || !((tr.h00 + tr.h11 + tr.h22) > 0.0))) ||
-                              (end_iter && ((q == max_trials) || (rho == 0.0) || (it >= a.iterations)));
+                              (end_iter && ((q == lm_max_trials) || (rho == 0.0) || (it >= a.iterations)));
         q = end_iter ? 0 : q;
         init = active ? false : init;
 

@@ -1,6 +1,7 @@
 // gfx950 (MI355X / CDNA4): tree_lm_kernel / tree_wave_kernel — forest windows of ONE shared topology (BASELINE config 5; split out of
 // window_kernel.hip; the general solver and the shared residual / g2o semantics are described there).
 #include "se3_edge_device.h"
+#include "lm_damping.h"
 
 namespace locamd {
 
@@ -520,8 +521,6 @@ __global__ void __launch_bounds__(64, 1) tree_lm_kernel(const WindowArgs a, cons
             for (int k = 0; k < 48; ++k) slab[(soff + (size_t)i * 48 + k) * 64] = sval[48 * e + k];
         }
     }
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, q = 0, trials = 0, terminated = 0, buf = 0, shared_edges = 0;
     bool need_lin = true;
@@ -532,7 +531,7 @@ __global__ void __launch_bounds__(64, 1) tree_lm_kernel(const WindowArgs a, cons
                 double plain, md;
                 tree_sweep<true, JAC>(a, ts, slab, nv, buf, cur_chi, plain, md, shared_edges);
                 last_plain = plain;
-                if (it == 0) { lambda = tau * md; ni = 2.0; }
+                if (it == 0) { lambda = lm_tau * md; ni = 2.0; }
                 q = 0;
                 need_lin = false;
             }
@@ -544,14 +543,11 @@ __global__ void __launch_bounds__(64, 1) tree_lm_kernel(const WindowArgs a, cons
             tree_sweep<false, JAC>(a, ts, slab, nv, 1 - buf, temp_chi, plain2, md2, unused_shared);
             last_plain = plain2;
             if (!ok2) temp_chi = DBL_MAX;
-            const double scale = sc + 1e-3;
+            const double scale = sc + lm_scale_eps;
             const double rho = (cur_chi - temp_chi) / scale;
             bool iteration_over;
             if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
-                const double r21 = 2.0 * rho - 1.0;
-                double alpha = 1.0 - r21 * r21 * r21;
-                alpha = fmin(alpha, good_hi);
-                lambda *= fmax(good_lo, alpha);
+                lambda = lm_lambda_accepted(lambda, rho);
                 ni = 2.0;
                 cur_chi = temp_chi;
                 buf = 1 - buf;
@@ -561,12 +557,12 @@ __global__ void __launch_bounds__(64, 1) tree_lm_kernel(const WindowArgs a, cons
                 lambda *= ni;
                 ni *= 2.0;
                 ++q;
-                iteration_over = !(rho < 0.0 && q < max_trials);
+                iteration_over = !(rho < 0.0 && q < lm_max_trials);
             }
             if (iteration_over) {
                 ++it;
                 need_lin = true;
-                if (q == max_trials || rho == 0.0) { terminated = 1; done = true; }
+                if (q == lm_max_trials || rho == 0.0) { terminated = 1; done = true; }
                 if (it >= a.iterations) done = true;
             }
         }

@@ -29,6 +29,7 @@
 // LDS: 48 x 64 + 27 x 65 doubles = 38 680 B per wave, four waves per CU.  Nodes with more than two range edges, or priors, take
 // (correct, slower) generic loops over the tables in memory.
 #include "se3_edge_device.h"
+#include "lm_damping.h"
 
 namespace locamd {
 namespace {
@@ -363,13 +364,12 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
     for (int k = 0; k < 36; ++k) HO[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < 15; ++k) Gs[k] = 0.0;
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, trials = 0, terminated = 0, shared_edges = 0;
     const bool active = nv > 0 && ts.nr + ts.np + ts.ns > 0 && a.iterations > 0;
     // (the lambdas are always_inline: inlined before the first SROA / InstCombine round — as ordinary lambdas the pose arrays they take by
     //  pointer stayed in memory long enough for `c ? A[k] : B[k]` to become a load through a selected POINTER, which pins both arrays in scratch)
+    // (window_device.h: wave_sync, written out — called, it changes this kernel's register assignment)
     auto wsync = []() __attribute__((always_inline)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
                 for (int r = 0; r < 6; ++r) md = fmax(md, fabs(HD[r * (r + 1) / 2 + r]));
                 cur_chi = wave_sum(rs);
                 last_plain = wave_sum(cs);
-                if (it == 0) { lambda = tau * wave_max(node ? md : 0.0); ni = 2.0; shared_edges = (int)wave_sum(node && nbin >= 2 ? (double)nbin : 0.0); }
+                if (it == 0) { lambda = lm_tau * wave_max(node ? md : 0.0); ni = 2.0; shared_edges = (int)wave_sum(node && nbin >= 2 ? (double)nbin : 0.0); }
                 wsync();
             }
             TW_T(7);
@@ -629,7 +629,7 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
 #pragma unroll
                     for (int k = 0; k < 12; ++k) Xb[k] = Xa[k];
                 }
-                const double scale = wave_sum(sc) + 1e-3;
+                const double scale = wave_sum(sc) + lm_scale_eps;
                 ++trials;
                 TW_T(5);
                 // ---- score the trial state -------------------------------------------------------------------------------------------------
@@ -646,10 +646,7 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
                 if (!all_ok) temp_chi = DBL_MAX;
                 rho = (cur_chi - temp_chi) / scale;
                 if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
-                    const double r21 = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - r21 * r21 * r21;
-                    alpha = fmin(alpha, good_hi);
-                    lambda *= fmax(good_lo, alpha);
+                    lambda = lm_lambda_accepted(lambda, rho);
                     ni = 2.0;
                     cur_chi = temp_chi;
 #pragma unroll
@@ -659,9 +656,9 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
                     ni *= 2.0;
                 }
                 ++q;
-            } while (rho < 0.0 && q < max_trials);
+            } while (rho < 0.0 && q < lm_max_trials);
             ++it;
-            if (q == max_trials || rho == 0.0) { terminated = 1; break; }
+            if (q == lm_max_trials || rho == 0.0) { terminated = 1; break; }
         }
     }
     if (node) {

@@ -25,8 +25,8 @@
 //     of this trial and of the next ones (what LM would try after a rejection), and are scored in LM's order;
 //   * nothing but the poses and the per-edge records ever leaves registers; no barriers (one wave per workgroup), no HBM
 //     workspace, 6 KB of LDS for a ten-pose window; 168 registers: three waves per SIMD in batches (3.7e7 windows/s).
-#include "window_kernel.h"
-#include "device_math.h"
+#include "window_device.h"
+#include "lm_damping.h"
 
 #include <float.h>
 #include <math.h>
@@ -45,75 +45,6 @@ extern __shared__ double w3lds[];
 #define W3_T0() do {} while (0)
 #define W3_T(k) do {} while (0)
 #endif
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double w3_dpp(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, CTRL == 0x138 || CTRL == 0x130);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, CTRL == 0x138 || CTRL == 0x130);
-    return __hiloint2double(hi, lo);
-}
-// value of lane l (wave-uniform l) in every lane — through SGPRs
-__device__ __forceinline__ double w3_bcast(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-// the value of lane - 1 / lane + 1 (wave_shr:1 / wave_shl:1 cross the 16-lane rows on gfx9; no neighbour: 0)
-__device__ __forceinline__ double w3_from_prev(double v) { return w3_dpp<0x138, 0xF>(v); }
-__device__ __forceinline__ double w3_from_next(double v) { return w3_dpp<0x130, 0xF>(v); }
-__device__ __forceinline__ double w3_sum(double v) {   // DPP row shifts + row broadcasts: one fixed order, every lane gets the same bits
-    v += w3_dpp<0x111, 0xF>(v);
-    v += w3_dpp<0x112, 0xF>(v);
-    v += w3_dpp<0x114, 0xF>(v);
-    v += w3_dpp<0x118, 0xF>(v);
-    v += w3_dpp<0x142, 0xA>(v);
-    v += w3_dpp<0x143, 0xC>(v);
-    return w3_bcast(v, 63);
-}
-__device__ __forceinline__ double w3_max(double v) {   // non-negative inputs
-    v = fmax(v, w3_dpp<0x111, 0xF>(v));
-    v = fmax(v, w3_dpp<0x112, 0xF>(v));
-    v = fmax(v, w3_dpp<0x114, 0xF>(v));
-    v = fmax(v, w3_dpp<0x118, 0xF>(v));
-    v = fmax(v, w3_dpp<0x142, 0xA>(v));
-    v = fmax(v, w3_dpp<0x143, 0xC>(v));
-    return w3_bcast(v, 63);
-}
-// one wave per workgroup: the LDS operations of a wave execute in order; the fences keep the compiler from moving them
-__device__ __forceinline__ void w3_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ double w3_pivot_rsqrt(double d) {   // window_kernel.hip: pivot_rsqrt
-    const double y = __builtin_amdgcn_rsq(d);
-    const double t = d * y;
-    const double e = __builtin_fma(-t, y, 1.0);
-    const double pq = __builtin_fma(0.375, e, 0.5);
-    const double ye = y * e;
-    return __builtin_fma(ye, pq, y);
-}
-
-#pragma clang fp contract(off)
-// ||d|| the way a plain CPU build of computeError evaluates it (numeric_jacobian.h: range_error_plain with a zero lever arm)
-__device__ __forceinline__ double w3_sq_plain(double dx, double dy, double dz) { return dx * dx + dy * dy + dz * dz; }
-// g2o's central difference of e = meas - ||p0 - p1|| along axis D of endpoint `which`'s translation (R = I, zero lever arm:
-// X * fromVectorMQT(+-delta e_D) = (I, t +- delta e_D); chain3_kernel.hip: range_jac_numeric3)
-// NEAR: the perturbed norms from the central one n0 (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers)
-template <int D, bool NEAR>
-__device__ __forceinline__ double w3_jac_numeric(const double* p0, const double* p1, int which, double meas, double n0, double h0) {
-    constexpr double delta = 1e-9;
-    constexpr double scalar = 1.0 / (2 * delta);
-    double a[3] = {p0[0], p0[1], p0[2]}, b[3] = {p1[0], p1[1], p1[2]}, am[3] = {p0[0], p0[1], p0[2]}, bm[3] = {p1[0], p1[1], p1[2]};
-    if (which == 0) { a[D] = delta + p0[D]; am[D] = -delta + p0[D]; }
-    else { b[D] = delta + p1[D]; bm[D] = -delta + p1[D]; }
-    const double xp = w3_sq_plain(a[0] - b[0], a[1] - b[1], a[2] - b[2]), xm = w3_sq_plain(am[0] - bm[0], am[1] - bm[1], am[2] - bm[2]);
-    const double ep = meas - (NEAR ? sqrt_ieee_near_c(xp, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xp));
-    const double em = meas - (NEAR ? sqrt_ieee_near_c(xm, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xm));
-    double bak = ep;
-    bak -= em;
-    return scalar * bak;
-}
-#pragma clang fp contract(fast)
 
 // LDS of one window (doubles first, then ints)
 struct W3Lds {
@@ -175,7 +106,7 @@ __device__ __forceinline__ void w3_edge(const W3Lds& l, const double* T, const W
         if (!(x > 0.0)) { n = 0.0; inv = 0.0; }   // coincident endpoints: J = 0, what the central difference gives
         err = meas - n;
     } else {
-        x0 = w3_sq_plain(u[0], u[1], u[2]);
+        x0 = sq_norm_plain(u[0], u[1], u[2]);
         n0 = sqrt_ieee_unscaled_h(x0, h0);
         err = meas - n0;
     }
@@ -191,19 +122,19 @@ __device__ __forceinline__ void w3_edge(const W3Lds& l, const double* T, const W
             J1[0] = u[0]; J1[1] = u[1]; J1[2] = u[2];
         } else {
             if (x0 >= 1e-5 && x0 < 1e300) {   // endpoints more than ~3 mm apart
-                J0[0] = w3_jac_numeric<0, true>(p0, p1, 0, meas, n0, h0);
-                J0[1] = w3_jac_numeric<1, true>(p0, p1, 0, meas, n0, h0);
-                J0[2] = w3_jac_numeric<2, true>(p0, p1, 0, meas, n0, h0);
-                J1[0] = w3_jac_numeric<0, true>(p0, p1, 1, meas, n0, h0);
-                J1[1] = w3_jac_numeric<1, true>(p0, p1, 1, meas, n0, h0);
-                J1[2] = w3_jac_numeric<2, true>(p0, p1, 1, meas, n0, h0);
+                J0[0] = range_jac_numeric_t<0, true>(p0, p1, 0, meas, n0, h0);
+                J0[1] = range_jac_numeric_t<1, true>(p0, p1, 0, meas, n0, h0);
+                J0[2] = range_jac_numeric_t<2, true>(p0, p1, 0, meas, n0, h0);
+                J1[0] = range_jac_numeric_t<0, true>(p0, p1, 1, meas, n0, h0);
+                J1[1] = range_jac_numeric_t<1, true>(p0, p1, 1, meas, n0, h0);
+                J1[2] = range_jac_numeric_t<2, true>(p0, p1, 1, meas, n0, h0);
             } else {
-                J0[0] = w3_jac_numeric<0, false>(p0, p1, 0, meas, n0, h0);
-                J0[1] = w3_jac_numeric<1, false>(p0, p1, 0, meas, n0, h0);
-                J0[2] = w3_jac_numeric<2, false>(p0, p1, 0, meas, n0, h0);
-                J1[0] = w3_jac_numeric<0, false>(p0, p1, 1, meas, n0, h0);
-                J1[1] = w3_jac_numeric<1, false>(p0, p1, 1, meas, n0, h0);
-                J1[2] = w3_jac_numeric<2, false>(p0, p1, 1, meas, n0, h0);
+                J0[0] = range_jac_numeric_t<0, false>(p0, p1, 0, meas, n0, h0);
+                J0[1] = range_jac_numeric_t<1, false>(p0, p1, 0, meas, n0, h0);
+                J0[2] = range_jac_numeric_t<2, false>(p0, p1, 0, meas, n0, h0);
+                J1[0] = range_jac_numeric_t<0, false>(p0, p1, 1, meas, n0, h0);
+                J1[1] = range_jac_numeric_t<1, false>(p0, p1, 1, meas, n0, h0);
+                J1[2] = range_jac_numeric_t<2, false>(p0, p1, 1, meas, n0, h0);
             }
         }
         const double wr = info * fast_rcp(aux), wre = -wr * err;
@@ -239,12 +170,12 @@ __device__ __forceinline__ void w3_edges(const W3Lds& l, const W3Edge& E0, int n
         rsum += chi;
         csum += chi;
     }
-    robust_chi = w3_sum(rsum);
-    plain_chi = w3_sum(csum);
+    robust_chi = wave_sum(rsum);
+    plain_chi = wave_sum(csum);
 }
 
 // TWO trial states scored in one pass (windows of <= 32 edges and <= 32 priors): state A by lanes 0 .. 31, state B by lanes 32 .. 63, every
-// lane with the edge of its position in its half.  The sums are the DPP tree of w3_sum read where a half has been summed — lanes 31 and 63
+// lane with the edge of its position in its half.  The sums are the DPP tree of wave_sum read where a half has been summed — lanes 31 and 63
 // after the row_bcast:15 step — which is bit for bit what the whole-wave sum of ONE state gives (its other rows add zeros).
 template <int JAC>
 __device__ __forceinline__ void w3_edges_dual(const W3Lds& l, const W3Edge& E0, int nvm, int nr, int np, int bufA, int bufB, int lane,
@@ -262,13 +193,13 @@ __device__ __forceinline__ void w3_edges_dual(const W3Lds& l, const W3Edge& E0, 
         rsum += chi;
         csum += chi;
     }
-    rsum += w3_dpp<0x111, 0xF>(rsum); csum += w3_dpp<0x111, 0xF>(csum);
-    rsum += w3_dpp<0x112, 0xF>(rsum); csum += w3_dpp<0x112, 0xF>(csum);
-    rsum += w3_dpp<0x114, 0xF>(rsum); csum += w3_dpp<0x114, 0xF>(csum);
-    rsum += w3_dpp<0x118, 0xF>(rsum); csum += w3_dpp<0x118, 0xF>(csum);
-    rsum += w3_dpp<0x142, 0xA>(rsum); csum += w3_dpp<0x142, 0xA>(csum);
-    chiA = w3_bcast(rsum, 31); plainA = w3_bcast(csum, 31);
-    chiB = w3_bcast(rsum, 63); plainB = w3_bcast(csum, 63);
+    rsum += dpp_or_zero<0x111, 0xF>(rsum, 0.0); csum += dpp_or_zero<0x111, 0xF>(csum, 0.0);
+    rsum += dpp_or_zero<0x112, 0xF>(rsum, 0.0); csum += dpp_or_zero<0x112, 0xF>(csum, 0.0);
+    rsum += dpp_or_zero<0x114, 0xF>(rsum, 0.0); csum += dpp_or_zero<0x114, 0xF>(csum, 0.0);
+    rsum += dpp_or_zero<0x118, 0xF>(rsum, 0.0); csum += dpp_or_zero<0x118, 0xF>(csum, 0.0);
+    rsum += dpp_or_zero<0x142, 0xA>(rsum, 0.0); csum += dpp_or_zero<0x142, 0xA>(csum, 0.0);
+    chiA = read_lane(rsum, 31); plainA = read_lane(csum, 31);
+    chiB = read_lane(rsum, 63); plainB = read_lane(csum, 63);
 }
 
 template <int JAC>
@@ -326,7 +257,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             for (int k = 0; k < 3; ++k) { l.pv[6 * q + k] = pval[18 * q + 9 + k]; l.pv[6 * q + 3 + k] = pval[18 * q + 12 + k]; }
         }
     }
-    w3_sync();
+    wave_sync();
     int deg = 0, nbin = 0;   // (lanes 0 .. nv-1: pose = lane)
     for (int e = 0; e < nr; ++e) {
         const int v0 = l.eidx[2 * e], v1 = l.eidx[2 * e + 1];
@@ -350,14 +281,14 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             if (v1 == lane) { if (v0 == lane - 1) kc = k; l.epos[2 * e + 1] = k++; }
         }
     }
-    const int shared_edges = (int)w3_sum(lane < nv && nbin >= 2 ? (double)nbin : 0.0);
+    const int shared_edges = (int)wave_sum(lane < nv && nbin >= 2 ? (double)nbin : 0.0);
     // no pair of consecutive poses with more than one edge (the reference's own window: one smoothness edge per pair): every
     // coupling block is a rank-1 product (w J_p) J_{p-1}^T, and the sweeps below hand two numbers from pose to pose instead of nine
     const bool rank1 = __ballot(lane < nv && nbin >= 2) == 0ull;
     deg = __shfl(deg, pp, 64);   // every group's lane of pose pp
     lst = __shfl(lst, pp, 64);
     kc = __shfl(kc, pp, 64);
-    w3_sync();
+    wave_sync();
     W3Edge E0;
     E0.v0 = 0; E0.v1 = -1; E0.s0 = 0; E0.s1 = -1; E0.meas = 0.0; E0.info = 0.0; E0.fx = 0.0; E0.fy = 0.0; E0.fz = 0.0;
     // (speculative trials are scored two at a time when a window's edges fit half a wave: the upper half keeps the same edges)
@@ -366,8 +297,6 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
     W3_T(0);
 
     // ---- Levenberg-Marquardt (g2o: OptimizationAlgorithmLevenberg::solve), wave-uniform control flow ---------------
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     constexpr int NSLOT = 5;   // translation buffers in LDS: the state + up to four trial states
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, q = 0, trials = 0, terminated = 0, cur = 0, jlast = 0;
@@ -386,7 +315,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             double plain;
             w3_edges<true, JAC>(l, E0, nvm, nr, np, cur, lane, cur_chi, plain);
             last_plain = plain;
-            w3_sync();
+            wave_sync();
             W3_T(1);
             // pose pp: its edges' blocks in creation order (every group's lane of the pose holds the same numbers)
 #pragma unroll
@@ -437,14 +366,14 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
 #pragma unroll
                 for (int rr = 0; rr < 3; ++rr) {
                     u[rr] = uu_[rr];
-                    vnext[rr] = w3_from_next(vv_[rr]);
+                    vnext[rr] = lane_from_next(vv_[rr]);
 #pragma unroll
                     for (int cc = 0; cc <= rr; ++cc) UU[rr * (rr + 1) / 2 + cc] = uu_[rr] * uu_[cc];
                 }
             }
             if (it == 0) {
                 const double md = fmax(fmax(fabs(D[0]), fabs(D[2])), fabs(D[5]));
-                lambda = tau * w3_max(pose ? md : 0.0);
+                lambda = lm_tau * wave_max(pose ? md : 0.0);
                 ni = 2.0;
             }
             q = 0;
@@ -482,7 +411,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
                 }
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    const double g = w3_pivot_rsqrt(A[j][j]);
+                    const double g = pivot_rsqrt(A[j][j]);
                     ig[j] = g;
 #pragma unroll
                     for (int i2 = j + 1; i2 < 3; ++i2) A[i2][j] *= g;
@@ -526,7 +455,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             {
                 double al = 0.0, be = 0.0;
                 for (int r = 0; r < nv; ++r) {
-                    const double pal = w3_from_prev(al), pbe = w3_from_prev(be);
+                    const double pal = lane_from_prev(al), pbe = lane_from_prev(be);
                     if (pose) {
                         bin = pbe;
                         den = __builtin_fma(-pal, uu, 1.0);
@@ -543,7 +472,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             {
                 double ga = 0.0, gin = 0.0, cfin = 0.0;
                 for (int r = 0; r < nv; ++r) {
-                    const double pga = w3_from_next(ga);
+                    const double pga = lane_from_next(ga);
                     if (pose) {
                         gin = pga;
                         cfin = __builtin_fma(-pga, uv, __builtin_fma(-bin, uu, ub));   // u^T A^-1 (b - beta u - gamma v)
@@ -561,9 +490,9 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             // pose p through DPP the same way
             double g10 = 0.0, g20 = 0.0, g21 = 0.0, ig[3] = {0.0, 0.0, 0.0}, y[3] = {0.0, 0.0, 0.0};   // this pose's factor (strict lower part, inverse pivots), y
             for (int r = 0; r < nv; ++r) {
-                const double pg10 = w3_from_prev(g10), pg20 = w3_from_prev(g20), pg21 = w3_from_prev(g21);
-                const double pig[3] = {w3_from_prev(ig[0]), w3_from_prev(ig[1]), w3_from_prev(ig[2])};
-                const double py[3] = {w3_from_prev(y[0]), w3_from_prev(y[1]), w3_from_prev(y[2])};
+                const double pg10 = lane_from_prev(g10), pg20 = lane_from_prev(g20), pg21 = lane_from_prev(g21);
+                const double pig[3] = {lane_from_prev(ig[0]), lane_from_prev(ig[1]), lane_from_prev(ig[2])};
+                const double py[3] = {lane_from_prev(y[0]), lane_from_prev(y[1]), lane_from_prev(y[2])};
                 if (pose) {
                     double A[3][3], rhs[3];
     #pragma unroll
@@ -602,7 +531,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
                         }
     #pragma unroll
                     for (int j = 0; j < 3; ++j) {
-                        const double g = w3_pivot_rsqrt(A[j][j]);
+                        const double g = pivot_rsqrt(A[j][j]);
                         ig[j] = g;
     #pragma unroll
                         for (int i2 = j + 1; i2 < 3; ++i2) A[i2][j] *= g;
@@ -628,7 +557,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
             // back-substitution the same way, from the right neighbour: v = H_{p+1,p}^T x_{p+1}
             double vo[3] = {0.0, 0.0, 0.0};
             for (int r = 0; r < nv; ++r) {
-                const double v[3] = {w3_from_next(vo[0]), w3_from_next(vo[1]), w3_from_next(vo[2])};
+                const double v[3] = {lane_from_next(vo[0]), lane_from_next(vo[1]), lane_from_next(vo[2])};
                 if (pose) {
                     double t[3] = {y[0], y[1], y[2]};
                     // z = G_p^-1 v (forward substitution), t -= z
@@ -686,19 +615,19 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { sc += X[k] * (mylam * X[k] + b[k]); d[k] = s[k] + X[k]; }
             }
-            // (the DPP tree of w3_sum, read where a group's lanes have been summed: the same bits as the whole-wave sum of one group)
-            sc += w3_dpp<0x111, 0xF>(sc);
-            sc += w3_dpp<0x112, 0xF>(sc);
-            sc += w3_dpp<0x114, 0xF>(sc);
-            sc += w3_dpp<0x118, 0xF>(sc);
+            // (the DPP tree of wave_sum, read where a group's lanes have been summed: the same bits as the whole-wave sum of one group)
+            sc += dpp_or_zero<0x111, 0xF>(sc, 0.0);
+            sc += dpp_or_zero<0x112, 0xF>(sc, 0.0);
+            sc += dpp_or_zero<0x114, 0xF>(sc, 0.0);
+            sc += dpp_or_zero<0x118, 0xF>(sc, 0.0);
             const double s16 = sc;
-            sc += w3_dpp<0x142, 0xA>(sc);
+            sc += dpp_or_zero<0x142, 0xA>(sc, 0.0);
             const double s32 = sc;
-            sc += w3_dpp<0x143, 0xC>(sc);
+            sc += dpp_or_zero<0x143, 0xC>(sc, 0.0);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) scv[g] = W == 16 ? w3_bcast(s16, 16 * g + 15) : (W == 32 ? w3_bcast(s32, 32 * (g & 1) + 31) : w3_bcast(sc, 63));
+            for (int g = 0; g < 4; ++g) scv[g] = W == 16 ? read_lane(s16, 16 * g + 15) : (W == 32 ? read_lane(s32, 32 * (g & 1) + 31) : read_lane(sc, 63));
         }
-        w3_sync();
+        wave_sync();
         // ---- consume the trials in LM's order until one is accepted (or the iteration ends) -------------------------------------------
         bool iteration_over = false;
         double rho = 0.0;
@@ -723,13 +652,10 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
                 ++trials;
                 jlast = g;
                 if ((bad >> (g * W)) & group_mask) temp_chi = DBL_MAX;
-                const double scale = scv[g] + 1e-3;
+                const double scale = scv[g] + lm_scale_eps;
                 rho = (cur_chi - temp_chi) / scale;
                 if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
-                    const double r21 = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - r21 * r21 * r21;
-                    alpha = fmin(alpha, good_hi);
-                    lambda = lamv[g] * fmax(good_lo, alpha);
+                    lambda = lm_lambda_accepted(lamv[g], rho);
                     ni = 2.0;
                     cur_chi = temp_chi;
                     cur = slot;   // the trial state is the state
@@ -739,7 +665,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
                     lambda = lamv[g] * niv[g];
                     ni = 2.0 * niv[g];      // (pop: the state was never overwritten)
                     ++q;
-                    iteration_over = !(rho < 0.0 && q < max_trials);
+                    iteration_over = !(rho < 0.0 && q < lm_max_trials);
                 }
             }
         }
@@ -747,7 +673,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
         if (iteration_over) {
             ++it;
             need_lin = true;
-            if (q == max_trials || rho == 0.0) { terminated = 1; done = true; }
+            if (q == lm_max_trials || rho == 0.0) { terminated = 1; done = true; }
             if (it >= a.iterations) done = true;
         }
         W3_T(6);

@@ -28,6 +28,7 @@
 // pass), LM — is shared with the rank-1 kernel.  Measured: cfg/uwb_twist.yaml's 15-pose window 0.29 ms (window_lm_kernel 0.64), 0.32 ms
 // per range message through the node (the oracle: 0.34 ms), 4.5e6 windows/s in batches (chain_lm_kernel: 2.7e6).
 #include "se3_edge_device.h"
+#include "lm_damping.h"
 
 #include <float.h>
 #include <math.h>
@@ -48,66 +49,6 @@ extern __shared__ double w6lds[];
 #define W6_T(k) do {} while (0)
 #endif
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double w6_dpp(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, CTRL == 0x138 || CTRL == 0x130);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, CTRL == 0x138 || CTRL == 0x130);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double w6_bcast(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-// the value of lane - 1 / lane + 1 (wave_shr:1 / wave_shl:1 cross the 16-lane rows on gfx9; no neighbour: 0)
-__device__ __forceinline__ double w6_from_prev(double v) { return w6_dpp<0x138, 0xF>(v); }
-__device__ __forceinline__ double w6_from_next(double v) { return w6_dpp<0x130, 0xF>(v); }
-__device__ __forceinline__ double w6_sum(double v) {
-    v += w6_dpp<0x111, 0xF>(v);
-    v += w6_dpp<0x112, 0xF>(v);
-    v += w6_dpp<0x114, 0xF>(v);
-    v += w6_dpp<0x118, 0xF>(v);
-    v += w6_dpp<0x142, 0xA>(v);
-    v += w6_dpp<0x143, 0xC>(v);
-    return w6_bcast(v, 63);
-}
-__device__ __forceinline__ double w6_max(double v) {   // non-negative inputs
-    v = fmax(v, w6_dpp<0x111, 0xF>(v));
-    v = fmax(v, w6_dpp<0x112, 0xF>(v));
-    v = fmax(v, w6_dpp<0x114, 0xF>(v));
-    v = fmax(v, w6_dpp<0x118, 0xF>(v));
-    v = fmax(v, w6_dpp<0x142, 0xA>(v));
-    v = fmax(v, w6_dpp<0x143, 0xC>(v));
-    return w6_bcast(v, 63);
-}
-__device__ __forceinline__ void w6_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ double w6_pivot_rsqrt(double d) {   // window_kernel.hip: pivot_rsqrt
-    const double y = __builtin_amdgcn_rsq(d);
-    const double t = d * y;
-    const double e = __builtin_fma(-t, y, 1.0);
-    const double pq = __builtin_fma(0.375, e, 0.5);
-    const double ye = y * e;
-    return __builtin_fma(ye, pq, y);
-}
-
-// ---- small SE3 algebra (row-major 3x3; window_kernel.hip's) ------------------------------------------------------------------
-__device__ __forceinline__ void w6_mat_mul(const double* A, const double* B, double* C) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3 + 0] * B[0 * 3 + j] + A[i * 3 + 1] * B[1 * 3 + j] + A[i * 3 + 2] * B[2 * 3 + j];
-}
-__device__ __forceinline__ void w6_mat_vec(const double* A, const double* v, double* o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = A[i * 3 + 0] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
-}
-__device__ __forceinline__ void w6_mat_tvec(const double* A, const double* v, double* o) {  // A^T v
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = A[0 * 3 + i] * v[0] + A[1 * 3 + i] * v[1] + A[2 * 3 + i] * v[2];
-}
 // Eigen::Quaternion(Matrix3) — q = (w, x, y, z); the square root and its reciprocal from one v_rsq_f64 seed (device_math.h:
 // sqrt_and_rsqrt, 1e-16 / 4e-15 relative: the prior's error and Jacobian carry them at that level)
 __device__ __forceinline__ void w6_mat_to_quat(const double* R, double* q) {
@@ -139,16 +80,6 @@ __device__ __forceinline__ void w6_quat_normalize_sign(double* q) {
     if (q[0] < 0) s = -s;
     q[0] *= s; q[1] *= s; q[2] *= s; q[3] *= s;
 }
-// Eigen toRotationMatrix (no normalisation)
-__device__ __forceinline__ void w6_quat_to_mat(const double* q, double* R) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-
 #pragma clang fp contract(off)
 // the squared distance of range_error_plain (numeric_jacobian.h), same operation order: |(R off + t) - q1|^2
 __device__ __forceinline__ double w6_range_sq_plain(const double* R, const double* t, const double* off, const double* q1) {
@@ -158,7 +89,7 @@ __device__ __forceinline__ double w6_range_sq_plain(const double* R, const doubl
     const double dx = (px + t[0]) - q1[0], dy = (py + t[1]) - q1[1], dz = (pz + t[2]) - q1[2];
     return dx * dx + dy * dy + dz * dz;
 }
-// one column of g2o's numeric Jacobian (window_kernel.hip: range_jac_numeric; delta = 1e-9 through VertexSE3::oplus) of endpoint
+// one column of g2o's numeric Jacobian (window_device.h: range_jac_numeric; delta = 1e-9 through VertexSE3::oplus) of endpoint
 // `which` (0: the pose carrying the lever arm, 1: the other pose — no lever arm there: its point is its translation).
 // NEAR: the perturbed norms from the central one (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers).
 template <int D, bool NEAR>
@@ -254,7 +185,7 @@ __device__ __forceinline__ void w6_edge(const W6Lds& l, const double* P, const W
     double err, inv = 0.0, u[3] = {0.0, 0.0, 0.0}, x0 = 0.0, n0 = 0.0, h0 = 0.0;
     if (JAC == 0) {
         double p0[3];
-        w6_mat_vec(X0, off, p0);
+        mat_vec(X0, off, p0);
         u[0] = (p0[0] + X0[9]) - p1[0]; u[1] = (p0[1] + X0[10]) - p1[1]; u[2] = (p0[2] + X0[11]) - p1[2];
         const double x = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
         double n;
@@ -275,7 +206,7 @@ __device__ __forceinline__ void w6_edge(const W6Lds& l, const double* P, const W
         if (JAC == 0) {
             u[0] *= inv; u[1] *= inv; u[2] *= inv;
             double uR[3];
-            w6_mat_tvec(X0, u, uR);   // (u^T R0)^T
+            mat_tvec(X0, u, uR);   // (u^T R0)^T
             J0[0] = -uR[0]; J0[1] = -uR[1]; J0[2] = -uR[2];
             // dp0/dv = -2 R0 [o]x  =>  de/dv0 = 2 (uR x o)
             J0[3] = 2.0 * (uR[1] * off[2] - uR[2] * off[1]);
@@ -283,7 +214,7 @@ __device__ __forceinline__ void w6_edge(const W6Lds& l, const double* P, const W
             J0[5] = 2.0 * (uR[0] * off[1] - uR[1] * off[0]);
             if (v1 >= 0) {
                 double uR1[3];
-                w6_mat_tvec(X1, u, uR1);
+                mat_tvec(X1, u, uR1);
                 J1[0] = uR1[0]; J1[1] = uR1[1]; J1[2] = uR1[2];   // (no lever arm on endpoint 1: its rotation does not move its point)
             }
         } else {
@@ -348,8 +279,8 @@ __device__ __forceinline__ void w6_prior(const W6Lds& l, const double* P, int q,
 #pragma unroll
     for (int k = 0; k < 12; ++k) X[k] = P[v * 12 + k];
     double RE[9], tE[3], qq[4];
-    w6_mat_mul(val, X, RE);
-    w6_mat_vec(val, X + 9, tE);
+    mat_mul(val, X, RE);
+    mat_vec(val, X + 9, tE);
     tE[0] += val[9]; tE[1] += val[10]; tE[2] += val[11];
     w6_mat_to_quat(RE, qq);
     w6_quat_normalize_sign(qq);
@@ -400,19 +331,19 @@ __device__ __forceinline__ void w6_edges(const W6Lds& l, const W6Edge& E0, int n
     if (lane < nr) w6_edge<FULL, JAC>(l, P, E0, tm, rsum, csum);
     for (int e = lane + 64; e < nr; e += 64) w6_edge<FULL, JAC>(l, P, w6_load_edge(l, e), tm, rsum, csum);
     for (int q = lane; q < np; q += 64) w6_prior<FULL>(l, P, q, rsum, csum);
-    robust_chi = w6_sum(rsum);
-    plain_chi = w6_sum(csum);
+    robust_chi = wave_sum(rsum);
+    plain_chi = wave_sum(csum);
 }
 
-// the sums of lanes 0 .. 31 and of lanes 32 .. 63: the DPP tree of w6_sum read after the row_bcast:15 step — bit for bit the whole-wave sum of
+// the sums of lanes 0 .. 31 and of lanes 32 .. 63: the DPP tree of wave_sum read after the row_bcast:15 step — bit for bit the whole-wave sum of
 // values that sit in one half only
 __device__ __forceinline__ void w6_half_sums(double v, double& lo, double& hi) {
-    v += w6_dpp<0x111, 0xF>(v);
-    v += w6_dpp<0x112, 0xF>(v);
-    v += w6_dpp<0x114, 0xF>(v);
-    v += w6_dpp<0x118, 0xF>(v);
-    v += w6_dpp<0x142, 0xA>(v);
-    lo = w6_bcast(v, 31); hi = w6_bcast(v, 63);
+    v += dpp_or_zero<0x111, 0xF>(v, 0.0);
+    v += dpp_or_zero<0x112, 0xF>(v, 0.0);
+    v += dpp_or_zero<0x114, 0xF>(v, 0.0);
+    v += dpp_or_zero<0x118, 0xF>(v, 0.0);
+    v += dpp_or_zero<0x142, 0xA>(v, 0.0);
+    lo = read_lane(v, 31); hi = read_lane(v, 63);
 }
 // TWO trial states scored in one pass (windows of <= 32 range edges and <= 32 priors): state A by lanes 0 .. 31, state B by lanes 32 .. 63, every
 // lane with the edge of its position in its half (wave3_kernel.hip: w3_edges_dual)
@@ -533,7 +464,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
             if (pose && qq >= 0 && ((i2 == pp && j2 == qq) || (i2 == qq && j2 == pp))) { se.e = e; se.i = i2; se.j = j2; se.robust = r2 != 0; }
         }
     }
-    w6_sync();
+    wave_sync();
     int deg = 0;   // (lanes 0 .. nv-1: pose = lane)
     for (int e = 0; e < nr; ++e) {
         const int v0 = l.eidx[2 * e], v1 = l.eidx[2 * e + 1];
@@ -577,7 +508,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
     if (SE3) kc = qq < 0 ? -1 : (qq == pp + 1 ? kcr : kc);   // the record of the edge to the SENDER
     pdeg = __shfl(pdeg, pp, 64);
     plst = __shfl(plst, pp, 64);
-    w6_sync();
+    wave_sync();
     W6Edge E0;
     E0.v0 = 0; E0.v1 = -1; E0.s0 = 0; E0.s1 = -1; E0.meas = 0.0; E0.info = 0.0; E0.ox = 0.0; E0.oy = 0.0; E0.oz = 0.0; E0.fx = 0.0; E0.fy = 0.0; E0.fz = 0.0;
     // (speculative trials are scored two at a time when a window's edges fit half a wave: the upper half keeps the same edges)
@@ -586,8 +517,6 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
     W6_T(0);
 
     // ---- Levenberg-Marquardt (g2o: OptimizationAlgorithmLevenberg::solve), wave-uniform control flow ---------------
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
     int it = 0, q = 0, trials = 0, terminated = 0, cur = 0, jlast = 0;
     bool need_lin = true;
@@ -616,11 +545,11 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                     const double chi = w6_se3<true>(l, l.pose + (size_t)cur * nvm * 12, se, se.e, pp, own, oth, K, rterm);
                     if (grp == 0) { rs = rterm; cs = chi; }
                 }
-                cur_chi += w6_sum(rs);
-                plain += w6_sum(cs);
+                cur_chi += wave_sum(rs);
+                plain += wave_sum(cs);
             }
             last_plain = plain;
-            w6_sync();
+            wave_sync();
             W6_T(1);
 #pragma unroll
             for (int k = 0; k < 21; ++k) D[k] = 0.0;
@@ -657,20 +586,20 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                 }
             }
 #pragma unroll
-            for (int c = 0; c < 6; ++c) vnext[c] = w6_from_next(vv[c]);
+            for (int c = 0; c < 6; ++c) vnext[c] = lane_from_next(vv[c]);
             if (SE3) {
                 // the EdgeSE3's shares: own, and the NEXT lane (whose sender this lane is) hands down what its edge gives this lane's pose
                 // (zeros from a lane without one); the pair's coupling block = the EdgeSE3's + the range edge's rank-1 part.  The middle pose's
                 // H_mm and b_m stay split over its two lanes (the second holds the share of ITS edge): every use below is a sum over both.
 #pragma unroll
-                for (int k = 0; k < 21; ++k) D[k] += own[k] + w6_from_next(oth[k]);
+                for (int k = 0; k < 21; ++k) D[k] += own[k] + lane_from_next(oth[k]);
 #pragma unroll
-                for (int k = 0; k < 6; ++k) b[k] += own[21 + k] + w6_from_next(oth[21 + k]);
+                for (int k = 0; k < 6; ++k) b[k] += own[21 + k] + lane_from_next(oth[21 + k]);
 #pragma unroll
                 for (int c = 0; c < 6; ++c)
 #pragma unroll
                     for (int r = 0; r < 6; ++r) K[6 * c + r] = __builtin_fma(u[r], vv[c], K[6 * c + r]);
-                if (it == 0) shared_edges = (int)w6_sum(grp == 0 && se.e >= 0 && kc >= 0 ? 2.0 : 0.0);
+                if (it == 0) shared_edges = (int)wave_sum(grp == 0 && se.e >= 0 && kc >= 0 ? 2.0 : 0.0);
             }
             if (it == 0) {
                 double md = 0.0;
@@ -680,7 +609,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                     if (SE3 && nv > 1) { const double t = __shfl(dg, grp * W + nv, 64); dg = mid ? dg + t : (dup ? 0.0 : dg); }   // (the middle pose's diagonal: both lanes' shares)
                     md = fmax(md, fabs(dg));
                 }
-                lambda = tau * w6_max(pose ? md : 0.0);
+                lambda = lm_tau * wave_max(pose ? md : 0.0);
                 ni = 2.0;
             }
             q = 0;
@@ -720,7 +649,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                 }
     #pragma unroll
                 for (int j = 0; j < 6; ++j) {
-                    const double g = w6_pivot_rsqrt(A[j][j]);
+                    const double g = pivot_rsqrt(A[j][j]);
                     ig[j] = g;
     #pragma unroll
                     for (int i2 = j + 1; i2 < 6; ++i2) A[i2][j] *= g;
@@ -766,7 +695,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
             {
                 double al = 0.0, be = 0.0;
                 for (int r = 0; r < nv; ++r) {
-                    const double pal = w6_from_prev(al), pbe = w6_from_prev(be);
+                    const double pal = lane_from_prev(al), pbe = lane_from_prev(be);
                     if (pose) {
                         bin = pbe;
                         den = __builtin_fma(-pal, uu, 1.0);
@@ -784,7 +713,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
             {
                 double ga = 0.0, gin = 0.0, cfin = 0.0;
                 for (int r = 0; r < nv; ++r) {
-                    const double pga = w6_from_next(ga);
+                    const double pga = lane_from_next(ga);
                     if (pose) {
                         gin = pga;
                         cfin = __builtin_fma(-pga, uv, __builtin_fma(-bin, uu, ub));   // u^T A^-1 (b - beta u - gamma v)
@@ -819,7 +748,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
             auto factor = [&](double (&A)[6][6], double* rhs) __attribute__((always_inline)) {   // A = G G^T in place, ig, Gl; rhs <- G^-1 rhs = yv
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
-                    const double g = w6_pivot_rsqrt(A[j][j]);
+                    const double g = pivot_rsqrt(A[j][j]);
                     ig[j] = g;
 #pragma unroll
                     for (int i2 = j + 1; i2 < 6; ++i2) A[i2][j] *= g;
@@ -841,9 +770,9 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
             for (int r = 0; r < reps; ++r) {
                 double Gq[15], iq[6], yq[6];
 #pragma unroll
-                for (int k = 0; k < 15; ++k) Gq[k] = w6_from_prev(Gl[k]);
+                for (int k = 0; k < 15; ++k) Gq[k] = lane_from_prev(Gl[k]);
 #pragma unroll
-                for (int k = 0; k < 6; ++k) { iq[k] = w6_from_prev(ig[k]); yq[k] = w6_from_prev(yv[k]); }
+                for (int k = 0; k < 6; ++k) { iq[k] = lane_from_prev(ig[k]); yq[k] = lane_from_prev(yv[k]); }
                 if (pose) {
                     // W = G_q^-1 K^T, one forward substitution per row rr of K.  (A chain's first pose has no sender: W stays 0, and what the
                     // lane before it holds — another chain's or group's end, possibly not finite — is not looked at.)
@@ -935,7 +864,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                 for (int r = 0; r + 1 < reps; ++r) {
                     double tq[6];
 #pragma unroll
-                    for (int k = 0; k < 6; ++k) tq[k] = w6_from_next(tn[k]);
+                    for (int k = 0; k < 6; ++k) tq[k] = lane_from_next(tn[k]);
                     if (pose && !mid && !dup) back(tq);
                 }
             }
@@ -977,26 +906,26 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                 double Rd[9];
                 const double ww = 1.0 - (X[3] * X[3] + X[4] * X[4] + X[5] * X[5]);
                 if (ww < 0) { Rd[0] = 1; Rd[1] = 0; Rd[2] = 0; Rd[3] = 0; Rd[4] = 1; Rd[5] = 0; Rd[6] = 0; Rd[7] = 0; Rd[8] = 1; }
-                else { const double qd[4] = {sqrt(ww), X[3], X[4], X[5]}; w6_quat_to_mat(qd, Rd); }
+                else { const double qd[4] = {sqrt(ww), X[3], X[4], X[5]}; quat_to_mat(qd, Rd); }
                 double Rn[9], tn[3];
-                w6_mat_mul(Xc, Rd, Rn);
-                w6_mat_vec(Xc, X, tn);
+                mat_mul(Xc, Rd, Rn);
+                mat_vec(Xc, X, tn);
 #pragma unroll
                 for (int k = 0; k < 9; ++k) d[k] = Rn[k];
                 d[9] = Xc[9] + tn[0]; d[10] = Xc[10] + tn[1]; d[11] = Xc[11] + tn[2];
             }
-            sc += w6_dpp<0x111, 0xF>(sc);
-            sc += w6_dpp<0x112, 0xF>(sc);
-            sc += w6_dpp<0x114, 0xF>(sc);
-            sc += w6_dpp<0x118, 0xF>(sc);
+            sc += dpp_or_zero<0x111, 0xF>(sc, 0.0);
+            sc += dpp_or_zero<0x112, 0xF>(sc, 0.0);
+            sc += dpp_or_zero<0x114, 0xF>(sc, 0.0);
+            sc += dpp_or_zero<0x118, 0xF>(sc, 0.0);
             const double s16 = sc;
-            sc += w6_dpp<0x142, 0xA>(sc);
+            sc += dpp_or_zero<0x142, 0xA>(sc, 0.0);
             const double s32 = sc;
-            sc += w6_dpp<0x143, 0xC>(sc);
+            sc += dpp_or_zero<0x143, 0xC>(sc, 0.0);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) scv[g] = W == 16 ? w6_bcast(s16, 16 * g + 15) : (W == 32 ? w6_bcast(s32, 32 * (g & 1) + 31) : w6_bcast(sc, 63));
+            for (int g = 0; g < 4; ++g) scv[g] = W == 16 ? read_lane(s16, 16 * g + 15) : (W == 32 ? read_lane(s32, 32 * (g & 1) + 31) : read_lane(sc, 63));
         }
-        w6_sync();
+        wave_sync();
         // ---- consume the trials in LM's order until one is accepted (or the iteration ends) -------------------------------------------
         bool iteration_over = false;
         double rho = 0.0;
@@ -1025,8 +954,8 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                         if (SE3) {   // the EdgeSE3 factors, group 0's lanes
                             double rs = 0.0, cs = 0.0;
                             if (grp == 0 && se.e >= 0) cs = w6_se3<false>(l, l.pose + (size_t)slot * nvm * 12, se, se.e, pp, nullptr, nullptr, nullptr, rs);
-                            tchi[g] += w6_sum(rs);
-                            tplain[g] += w6_sum(cs);
+                            tchi[g] += wave_sum(rs);
+                            tplain[g] += wave_sum(cs);
                         }
                     }
                 }
@@ -1036,13 +965,14 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                 ++trials;
                 jlast = g;
                 if ((bad >> (g * W)) & group_mask) temp_chi = DBL_MAX;
-                const double scale = scv[g] + 1e-3;
+                const double scale = scv[g] + lm_scale_eps;
                 rho = (cur_chi - temp_chi) / scale;
                 if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {
+                    // (lm_damping.h: lm_lambda_accepted, written out — called, it changes this kernel's machine code)
                     const double r21 = 2.0 * rho - 1.0;
                     double alpha = 1.0 - r21 * r21 * r21;
-                    alpha = fmin(alpha, good_hi);
-                    lambda = lamv[g] * fmax(good_lo, alpha);
+                    alpha = fmin(alpha, lm_good_hi);
+                    lambda = lamv[g] * fmax(lm_good_lo, alpha);
                     ni = 2.0;
                     cur_chi = temp_chi;
                     cur = slot;   // the trial state is the state
@@ -1052,7 +982,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
                     lambda = lamv[g] * niv[g];
                     ni = 2.0 * niv[g];      // (pop: the state was never overwritten)
                     ++q;
-                    iteration_over = !(rho < 0.0 && q < max_trials);
+                    iteration_over = !(rho < 0.0 && q < lm_max_trials);
                 }
             }
         }
@@ -1060,7 +990,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
         if (iteration_over) {
             ++it;
             need_lin = true;
-            if (q == max_trials || rho == 0.0) { terminated = 1; done = true; }
+            if (q == lm_max_trials || rho == 0.0) { terminated = 1; done = true; }
             if (it >= a.iterations) done = true;
         }
         W6_T(6);

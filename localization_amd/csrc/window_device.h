@@ -1,6 +1,8 @@
 // Device helpers shared by the window kernels (window_kernel.hip: the general sparse solver; chain_kernel.hip: one lane per chain
-// window; tree_kernel.hip: forest windows of one shared topology): wave / block reductions on the VALU, 3x3 / quaternion algebra,
-// g2o's numeric range Jacobian column, the pivot reciprocal square root.  Everything is internal to the including translation unit.
+// window; tree_kernel.hip: forest windows of one shared topology; tree_wave_kernel.hip, covariance_kernel.hip and wave6_kernel.hip
+// through se3_edge_device.h; the translation-only chain3_kernel.hip, wave3_kernel.hip and arrow3_kernel.hip): lane primitives and
+// wave / block reductions on the VALU, 3x3 / quaternion algebra, g2o's numeric range Jacobian columns, the pivot reciprocal square
+// root.  Everything is internal to the including translation unit.
 #pragma once
 #include "window_kernel.h"
 #include "device_math.h"
@@ -21,8 +23,20 @@ __device__ __forceinline__ double dpp_or_zero(double v, double identity) {
     const int hi = __builtin_amdgcn_update_dpp(ihi, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double read_lane63(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
+// the value of lane l (wave-uniform l) in every lane, through SGPRs
+__device__ __forceinline__ double read_lane(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+// the value of lane - 1 / lane + 1 (wave_shr:1 / wave_shl:1 cross the 16-lane rows on gfx9; no neighbour: 0)
+__device__ __forceinline__ double lane_from_prev(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane_from_next(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xF, 0xF, true);
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double wave_sum(double v) {
@@ -32,7 +46,7 @@ __device__ __forceinline__ double wave_sum(double v) {
     v += dpp_or_zero<0x118, 0xF>(v, 0.0);  // row_shr:8  -> lane 15 of each row holds the row sum
     v += dpp_or_zero<0x142, 0xA>(v, 0.0);  // row_bcast:15 into rows 1 and 3
     v += dpp_or_zero<0x143, 0xC>(v, 0.0);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
-    return read_lane63(v);
+    return read_lane(v, 63);
 }
 __device__ __forceinline__ double wave_max(double v) {  // for non-negative inputs (identity 0)
     v = fmax(v, dpp_or_zero<0x111, 0xF>(v, 0.0));
@@ -41,7 +55,14 @@ __device__ __forceinline__ double wave_max(double v) {  // for non-negative inpu
     v = fmax(v, dpp_or_zero<0x118, 0xF>(v, 0.0));
     v = fmax(v, dpp_or_zero<0x142, 0xA>(v, 0.0));
     v = fmax(v, dpp_or_zero<0x143, 0xC>(v, 0.0));
-    return read_lane63(v);
+    return read_lane(v, 63);
+}
+// a wave that exchanges data through LDS with itself alone (one wave per workgroup, or a section one wave runs by itself): its LDS
+// operations execute in order; the fences keep the compiler from moving them
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // ---- several waves per window (NW > 1: windows of 65 .. 512 poses, whose structure tables fill a CU's LDS so that ONE window
@@ -50,9 +71,7 @@ __device__ __forceinline__ double wave_max(double v) {  // for non-negative inpu
 template <bool SOLO>
 __device__ __forceinline__ void sync_() {
     if (SOLO) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        wave_sync();
     } else {
         __syncthreads();
     }
@@ -201,6 +220,25 @@ __device__ __forceinline__ double range_jac_numeric(const double* X0, const doub
         ep = range_error_plain(X0, X0 + 9, off, tp, meas);
         em = range_error_plain(X0, X0 + 9, off, tm, meas);
     }
+    double bak = ep;
+    bak -= em;
+    return scalar * bak;
+}
+// ||d||^2 the way a plain CPU build of computeError evaluates it (numeric_jacobian.h: range_error_plain with a zero lever arm)
+__device__ __forceinline__ double sq_norm_plain(double dx, double dy, double dz) { return dx * dx + dy * dy + dz * dz; }
+// The translation-only windows (chain3, wave3, arrow3): g2o's central difference of e = meas - ||p0 - p1|| along axis D of endpoint
+// `which`'s translation — range_jac_numeric with R = I and a zero lever arm: X * fromVectorMQT(+-delta e_D) = (I, t +- delta e_D).
+// NEAR: the perturbed norms from the central one n0 (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers).
+template <int D, bool NEAR>
+__device__ __forceinline__ double range_jac_numeric_t(const double* p0, const double* p1, int which, double meas, double n0, double h0) {
+    constexpr double delta = 1e-9;
+    constexpr double scalar = 1.0 / (2 * delta);
+    double a[3] = {p0[0], p0[1], p0[2]}, b[3] = {p1[0], p1[1], p1[2]}, am[3] = {p0[0], p0[1], p0[2]}, bm[3] = {p1[0], p1[1], p1[2]};
+    if (which == 0) { a[D] = delta + p0[D]; am[D] = -delta + p0[D]; }
+    else { b[D] = delta + p1[D]; bm[D] = -delta + p1[D]; }
+    const double xp = sq_norm_plain(a[0] - b[0], a[1] - b[1], a[2] - b[2]), xm = sq_norm_plain(am[0] - bm[0], am[1] - bm[1], am[2] - bm[2]);
+    const double ep = meas - (NEAR ? sqrt_ieee_near_c(xp, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xp));
+    const double em = meas - (NEAR ? sqrt_ieee_near_c(xm, n0, h0, (h0 * h0) * (h0 + h0)) : sqrt_ieee_unscaled(xm));
     double bak = ep;
     bak -= em;
     return scalar * bak;

@@ -33,6 +33,7 @@
 //   * all LM control flow is uniform over the instance's threads (sums are DPP reductions, combined across the waves in wave
 //     order: every thread holds the same bits).
 #include "window_device.h"
+#include "lm_damping.h"
 
 #include <atomic>
 
@@ -2683,8 +2684,6 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
         compute_incidence_wide<SP, NW>(L, lane, nv, nr, np, ns);
     }
 
-    constexpr double tau = 1e-5, good_lo = 1.0 / 3.0, good_hi = 2.0 / 3.0;
-    constexpr int max_trials = 10;
     double lambda = 0.0, ni = 2.0, cur_chi = 0.0, last_plain = 0.0;
 #ifdef LOCAMD_WINDOW_TIMING
     if (lane == 0 && LOCAMD_WINDOW_TIMING < 2) L.tim[0] += clock64() - t_start;
@@ -2717,7 +2716,7 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
         if (it == 0) {  // computeLambdaInit
             double md = 0.0;
             for (int j = lane; j < n; j += NT) md = fmax(md, fabs(L.Hs[sky<SP>(L, j, j)]));
-            lambda = tau * block_max<NW>(md, L.red, lane);
+            lambda = lm_tau * block_max<NW>(md, L.red, lane);
             ni = 2.0;
         }
         double rho = 0.0;
@@ -2764,13 +2763,14 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
             if (!ok2) temp_chi = DBL_MAX;
             double sc = 0.0;
             for (int j = lane; j < n; j += NT) sc += L.x[j] * (lambda * L.x[j] + L.b[j]);  // computeScale
-            const double scale = block_sum<NW>(sc, L.red, lane) + 1e-3;
+            const double scale = block_sum<NW>(sc, L.red, lane) + lm_scale_eps;
             rho = (cur_chi - temp_chi) / scale;
             if (rho > 0.0 && fabs(temp_chi) <= DBL_MAX) {  // g2o: rho > 0 && isfinite(tempChi)
+                // (lm_damping.h: lm_lambda_accepted, written out — called, it changes this kernel's machine code)
                 const double r21 = 2.0 * rho - 1.0;
                 double alpha = 1.0 - r21 * r21 * r21;
-                alpha = fmin(alpha, good_hi);
-                lambda *= fmax(good_lo, alpha);
+                alpha = fmin(alpha, lm_good_hi);
+                lambda *= fmax(lm_good_lo, alpha);
                 ni = 2.0;
                 cur_chi = temp_chi;
             } else {
@@ -2780,8 +2780,8 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
             }
             __syncthreads();
             ++q;
-        } while (rho < 0.0 && q < max_trials);
-        if (q == max_trials || rho == 0.0) { ok = false; terminated = 1; }
+        } while (rho < 0.0 && q < lm_max_trials);
+        if (q == lm_max_trials || rho == 0.0) { ok = false; terminated = 1; }
     }
 
     if (SP) { for (int i = lane; i < nv * 12; i += NT) gpose[i] = L.pose[L.perm[i / 12] * 12 + i % 12]; }
