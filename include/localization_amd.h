@@ -27,7 +27,8 @@ extern "C" {
                            * 3: numeric (g2o) Jacobians are the default everywhere, loc_shard_*, loc_window_last_kernel_kind;
                            * 4: loc_window_set_option / _last_host_timing, loc_node_flush_tail / _last_kernel_kind, loc_fusion_timing_*;
                            *    a large loc_window_solve_host drops the resident batch;
-                           *    (additive, same version) loc_window_covariance_host / _resident / loc_window_last_covariance_ms */
+                           *    (additive, same version) loc_window_covariance_host / _resident / loc_window_last_covariance_ms;
+                           *    (additive, same version) loc_snapshot_solve_device_cov / _host_kmb_cov, loc_fusion_solve_device_cov / _host_kmb_cov */
 
 typedef enum loc_status {
     LOC_OK = 0,
@@ -139,6 +140,23 @@ int loc_snapshot_solve_host(loc_snapshot* s, int32_t epochs, const float* dist_t
  * (loc_host_alloc); with pageable memory the result is the same, the copies just do not overlap.  Synchronous. */
 int loc_snapshot_solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* dist_kmb_host, const float* err_kmb_host,
                                 double* out_pos_host, double* out_chi2_host, uint8_t* out_trials_host);
+
+/* Per-update marginal covariances: the same solve, bit for bit (positions, chi2, trials), plus for every tag and epoch
+ * Sigma = H^-1 with H = sum_m J_m^T (rho'_m Omega_m) J_m the undamped system of the update AT the emitted position: rho'_m = 1 / (1 + chi2_m)
+ * (Cauchy), J_m in the handle's Jacobian mode, over the update's active ranges only — "the gate's weights": a range the outlier gate
+ * rejected on the prior (or an invalid slot) is not in H.  H is the one the LM loop already holds, so nothing is relinearised.
+ *   cov    double [K][6][B]  xx xy xz yy yz zz; NaN when singular
+ *   mask   int32  [K][B]     bits 0-2 = tx ty tz: a coordinate whose diagonal entry of H is exactly 0 is excluded (its entries are 0)
+ *   status int32  [K][B]     LOC_OK, or LOC_ERR_SINGULAR: a pivot of H's LDL^T is not finite, not positive or at most 1e-11 of its
+ *                            diagonal entry
+ * A tag without an active range gets every mask bit, zeros and LOC_OK.  LOC_ERR_INVALID (nothing launched) if a handle or any of the three
+ * covariance pointers is NULL; the other arguments as loc_snapshot_solve_device / _host_kmb (host arrays for the _host_kmb form). */
+int loc_snapshot_solve_device_cov(loc_snapshot* s, int32_t epochs, const float* dist_dev, const float* err_dev,
+                                  double* out_pos_dev, double* out_chi2_dev, uint8_t* out_trials_dev,
+                                  double* out_cov_dev, int32_t* out_cov_mask_dev, int32_t* out_cov_status_dev, void* hip_stream);
+int loc_snapshot_solve_host_kmb_cov(loc_snapshot* s, int32_t epochs, const float* dist_kmb_host, const float* err_kmb_host,
+                                    double* out_pos_host, double* out_chi2_host, uint8_t* out_trials_host,
+                                    double* out_cov_host, int32_t* out_cov_mask_host, int32_t* out_cov_status_host);
 
 /* Page-locked host memory for the host paths above (hipHostMalloc / hipHostFree). */
 int loc_host_alloc(void** out, size_t bytes);
@@ -448,6 +466,17 @@ int loc_fusion_solve_host(loc_fusion* f, int32_t epochs, const float* dist_tiles
  * is pipelined like loc_snapshot_solve_host_kmb (page-locked buffers from loc_host_alloc overlap the copies). */
 int loc_fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_kmb_host, const float* err_kmb_host,
                               const double* imu_host, double* out_pose_host, double* out_chi2_host, uint8_t* out_trials_host);
+/* Per-update marginal covariances of the 6-DoF pose, as loc_snapshot_solve_*_cov: H also holds the IMU prior's
+ * term; coordinates are g2o VertexSE3's minimal increment [dt (body frame), dq_xyz] applied as X * fromVectorMQT(d).
+ *   cov    double [K][21][B]  row-major upper triangle of the 6x6 Sigma in [tx ty tz qx qy qz]; NaN when singular
+ *   mask   int32  [K][B]      bits 0-5 = tx ty tz qx qy qz excluded (an exactly zero diagonal entry of H)
+ *   status int32  [K][B]      LOC_OK or LOC_ERR_SINGULAR */
+int loc_fusion_solve_device_cov(loc_fusion* f, int32_t epochs, const float* dist_dev, const float* err_dev, const double* imu_dev,
+                                double* out_pose_dev, double* out_chi2_dev, uint8_t* out_trials_dev,
+                                double* out_cov_dev, int32_t* out_cov_mask_dev, int32_t* out_cov_status_dev, void* hip_stream);
+int loc_fusion_solve_host_kmb_cov(loc_fusion* f, int32_t epochs, const float* dist_kmb_host, const float* err_kmb_host,
+                                  const double* imu_host, double* out_pose_host, double* out_chi2_host, uint8_t* out_trials_host,
+                                  double* out_cov_host, int32_t* out_cov_mask_host, int32_t* out_cov_status_host);
 int loc_fusion_last_kernel_ms(loc_fusion* f, double* ms);
 /* per-launch HIP-event pairs on the launch stream, as loc_snapshot_timing_* */
 int loc_fusion_timing_begin(loc_fusion* f, int32_t max_launches);

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "loc_snapshot_set_positions", "loc_snapshot_get_positions", "loc_snapshot_positions_device",
     "loc_snapshot_epochs_done", "loc_snapshot_set_epochs_done",
     "loc_snapshot_pack_ranges_host", "loc_snapshot_solve_device", "loc_snapshot_solve_host",
-    "loc_snapshot_solve_host_kmb", "loc_host_alloc", "loc_host_free",
+    "loc_snapshot_solve_host_kmb", "loc_snapshot_solve_device_cov", "loc_snapshot_solve_host_kmb_cov", "loc_host_alloc", "loc_host_free",
     "loc_snapshot_timing_begin", "loc_snapshot_timing_end",
     "loc_window_create", "loc_window_destroy", "loc_window_set_anchors", "loc_window_lds_bytes", "loc_window_solve_host",
     "loc_window_last_kernel_ms", "loc_window_set_endpoint1_offsets", "loc_window_set_jacobian", "loc_window_set_ordering", "loc_window_set_chain_threshold", "loc_window_last_kernel_kind", "loc_window_set_option", "loc_window_last_host_timing", "loc_window_upload",
@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "loc_nodes_release_batch_cache",
     "loc_fusion_default_params", "loc_fusion_create", "loc_fusion_destroy", "loc_fusion_set_poses", "loc_fusion_get_poses",
     "loc_fusion_solve_device", "loc_fusion_solve_host", "loc_fusion_solve_host_kmb", "loc_fusion_last_kernel_ms", "loc_fusion_timing_begin", "loc_fusion_timing_end",
+    "loc_fusion_solve_device_cov", "loc_fusion_solve_host_kmb_cov",
 ]
 
 
@@ -84,6 +85,10 @@ def lib():
     L.loc_snapshot_solve_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.loc_snapshot_solve_host.argtypes = [vp, C.c_int32, fp, fp, dp, dp, C.POINTER(C.c_uint8)]
     L.loc_snapshot_solve_host_kmb.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.loc_snapshot_solve_device_cov.argtypes = [vp, C.c_int32] + [vp] * 9
+    L.loc_snapshot_solve_host_kmb_cov.argtypes = [vp, C.c_int32] + [vp] * 8
+    L.loc_fusion_solve_device_cov.argtypes = [vp, C.c_int32] + [vp] * 10
+    L.loc_fusion_solve_host_kmb_cov.argtypes = [vp, C.c_int32] + [vp] * 9
     L.loc_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.loc_host_free.argtypes = [vp]
     L.loc_snapshot_timing_begin.argtypes = [vp, C.c_int32]
@@ -112,6 +117,22 @@ def lib():
     L.loc_window_last_covariance_ms.argtypes = [vp, dp]
     _LIB = L
     return L
+
+
+def unpack_covariance(packed, n):
+    """[K][n(n+1)/2][B] row-major upper triangles (the covariance outputs' layout) -> full symmetric [K][B][n][n]"""
+    import numpy as np
+    p = np.asarray(packed)
+    K, T, B = p.shape
+    assert T == n * (n + 1) // 2
+    out = np.empty((K, B, n, n), dtype=p.dtype)
+    i = 0
+    for r in range(n):
+        for c in range(r, n):
+            out[:, :, r, c] = p[:, i, :]
+            out[:, :, c, r] = p[:, i, :]
+            i += 1
+    return out
 
 
 def check(rc):

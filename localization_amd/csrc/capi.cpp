@@ -51,6 +51,10 @@ struct loc_snapshot {
     double *d_out_pos = nullptr, *d_out_chi2 = nullptr;
     uint8_t* d_out_trials = nullptr;
     int staged_epochs = 0;
+    // covariance outputs of the pipelined host path (loc_snapshot_solve_host_kmb_cov), allocated on its first call
+    double* d_out_cov = nullptr;
+    int32_t *d_out_cov_mask = nullptr, *d_out_cov_status = nullptr;
+    int cov_epochs = 0;
     long long epochs_done = 0;
     // pipelined host path (loc_snapshot_solve_host_kmb): raw [K][M][B] staging, copy streams, per-chunk events
     float *d_raw_dist = nullptr, *d_raw_err = nullptr;
@@ -179,6 +183,9 @@ int loc_snapshot_destroy(loc_snapshot* s) {
     for (hipEvent_t ev : s->pipe_ev) (void)hipEventDestroy(ev);
     if (s->d_raw_dist) (void)hipFree(s->d_raw_dist);
     if (s->d_raw_err) (void)hipFree(s->d_raw_err);
+    if (s->d_out_cov) (void)hipFree(s->d_out_cov);
+    if (s->d_out_cov_mask) (void)hipFree(s->d_out_cov_mask);
+    if (s->d_out_cov_status) (void)hipFree(s->d_out_cov_status);
     if (s->in_stream) (void)hipStreamDestroy(s->in_stream);
     if (s->out_stream) (void)hipStreamDestroy(s->out_stream);
     if (s->d_anchors) (void)hipFree(s->d_anchors);
@@ -235,9 +242,11 @@ int loc_snapshot_pack_ranges_host(const loc_snapshot* s, int32_t epochs, const f
     return LOC_OK;
 }
 
-int loc_snapshot_solve_device(loc_snapshot* s, int32_t epochs, const float* dist_dev, const float* err_dev,
-                              double* out_pos_dev, double* out_chi2_dev, uint8_t* out_trials_dev, void* hip_stream) {
-    if (!s) return fail(LOC_ERR_INVALID, "null handle");
+}  // extern "C"
+
+// the device path of both forms: cov == nullptr launches the plain solve, otherwise its COV twin
+static int solve_device(loc_snapshot* s, int32_t epochs, const float* dist_dev, const float* err_dev, double* out_pos_dev,
+                        double* out_chi2_dev, uint8_t* out_trials_dev, double* cov, int32_t* cov_mask, int32_t* cov_status, void* hip_stream) {
     if (epochs <= 0 || !dist_dev || !err_dev || !out_pos_dev || !out_chi2_dev) return fail(LOC_ERR_INVALID, "solve arguments");
     if (((uintptr_t)dist_dev | (uintptr_t)err_dev) & 15u) return fail(LOC_ERR_INVALID, "range tiles must be 16-byte aligned");
     LOC_HIP(hipSetDevice(s->device));
@@ -252,11 +261,36 @@ int loc_snapshot_solve_device(loc_snapshot* s, int32_t epochs, const float* dist
     }
     const bool timed = s->timing && (size_t)(s->ev_used + 2) <= s->ev.size();
     if (timed) LOC_HIP(hipEventRecord(s->ev[s->ev_used], st));
-    hipError_t e = locamd::launch_snapshot(a, s->M_PAD, s->lpi, s->prm.jacobian, s->prm.block_threads, st);
+    hipError_t e;
+    if (!cov) {
+        e = locamd::launch_snapshot(a, s->M_PAD, s->lpi, s->prm.jacobian, s->prm.block_threads, st);
+    } else {
+        locamd::SnapshotCovArgs ca;
+        static_cast<locamd::SnapshotArgs&>(ca) = a;
+        ca.out_cov = cov; ca.out_cov_mask = cov_mask; ca.out_cov_status = cov_status;
+        e = locamd::launch_snapshot_cov(ca, s->M_PAD, s->lpi, s->prm.jacobian, s->prm.block_threads, st);
+    }
     if (e != hipSuccess) return fail_hip(e, "launch_snapshot");
     if (timed) { LOC_HIP(hipEventRecord(s->ev[s->ev_used + 1], st)); s->ev_used += 2; }
     s->epochs_done += epochs;
     return LOC_OK;
+}
+
+extern "C" {
+
+int loc_snapshot_solve_device(loc_snapshot* s, int32_t epochs, const float* dist_dev, const float* err_dev,
+                              double* out_pos_dev, double* out_chi2_dev, uint8_t* out_trials_dev, void* hip_stream) {
+    if (!s) return fail(LOC_ERR_INVALID, "null handle");
+    return solve_device(s, epochs, dist_dev, err_dev, out_pos_dev, out_chi2_dev, out_trials_dev, nullptr, nullptr, nullptr, hip_stream);
+}
+
+int loc_snapshot_solve_device_cov(loc_snapshot* s, int32_t epochs, const float* dist_dev, const float* err_dev,
+                                  double* out_pos_dev, double* out_chi2_dev, uint8_t* out_trials_dev,
+                                  double* out_cov_dev, int32_t* out_cov_mask_dev, int32_t* out_cov_status_dev, void* hip_stream) {
+    if (!s) return fail(LOC_ERR_INVALID, "null handle");
+    if (!out_cov_dev || !out_cov_mask_dev || !out_cov_status_dev) return fail(LOC_ERR_INVALID, "covariance outputs: all three are required");
+    return solve_device(s, epochs, dist_dev, err_dev, out_pos_dev, out_chi2_dev, out_trials_dev, out_cov_dev, out_cov_mask_dev,
+                        out_cov_status_dev, hip_stream);
 }
 
 int loc_snapshot_solve_host(loc_snapshot* s, int32_t epochs, const float* dist_h, const float* err_h,
@@ -278,9 +312,11 @@ int loc_snapshot_solve_host(loc_snapshot* s, int32_t epochs, const float* dist_h
     return LOC_OK;
 }
 
-int loc_snapshot_solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* dist_kmb, const float* err_kmb,
-                                double* out_pos_h, double* out_chi2_h, uint8_t* out_trials_h) {
-    if (!s) return fail(LOC_ERR_INVALID, "null handle");
+}  // extern "C"
+
+// the pipelined host path of both forms: cov == nullptr solves without covariances (and never allocates their staging)
+static int solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* dist_kmb, const float* err_kmb, double* out_pos_h,
+                          double* out_chi2_h, uint8_t* out_trials_h, double* cov_h, int32_t* cov_mask_h, int32_t* cov_status_h) {
     if (epochs <= 0 || !dist_kmb || !err_kmb || !out_pos_h || !out_chi2_h) return fail(LOC_ERR_INVALID, "solve arguments");
     LOC_HIP(hipSetDevice(s->device));
     const size_t B = (size_t)s->B, M = (size_t)s->M, M4 = (size_t)s->M4;
@@ -293,6 +329,16 @@ int loc_snapshot_solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* di
         LOC_HIP(hipMalloc((void**)&s->d_raw_err, sizeof(float) * M * B * (size_t)epochs));
         s->raw_epochs = epochs;
     }
+    if (cov_h && epochs > s->cov_epochs) {
+        if (s->d_out_cov) (void)hipFree(s->d_out_cov);
+        if (s->d_out_cov_mask) (void)hipFree(s->d_out_cov_mask);
+        if (s->d_out_cov_status) (void)hipFree(s->d_out_cov_status);
+        s->d_out_cov = nullptr; s->d_out_cov_mask = s->d_out_cov_status = nullptr; s->cov_epochs = 0;
+        LOC_HIP(hipMalloc((void**)&s->d_out_cov, sizeof(double) * 6 * B * (size_t)epochs));
+        LOC_HIP(hipMalloc((void**)&s->d_out_cov_mask, sizeof(int32_t) * B * (size_t)epochs));
+        LOC_HIP(hipMalloc((void**)&s->d_out_cov_status, sizeof(int32_t) * B * (size_t)epochs));
+        s->cov_epochs = epochs;
+    }
     if (!s->in_stream) LOC_HIP(hipStreamCreateWithFlags(&s->in_stream, hipStreamNonBlocking));
     if (!s->out_stream) LOC_HIP(hipStreamCreateWithFlags(&s->out_stream, hipStreamNonBlocking));
     // chunks of ~8 MB per input array: small enough that copy-in, solve and copy-out of neighbouring chunks overlap,
@@ -303,7 +349,8 @@ int loc_snapshot_solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* di
         if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
         return at.type == hipMemoryTypeHost;
     };
-    const bool overlap = pinned(dist_kmb) && pinned(err_kmb) && pinned(out_pos_h) && pinned(out_chi2_h);
+    const bool overlap = pinned(dist_kmb) && pinned(err_kmb) && pinned(out_pos_h) && pinned(out_chi2_h) &&
+                         (!cov_h || (pinned(cov_h) && pinned(cov_mask_h) && pinned(cov_status_h)));
     const int ce = overlap ? (int)std::max<size_t>(1, (8u << 20) / (M * B * sizeof(float))) : epochs;
     const int nchunks = (epochs + ce - 1) / ce;
     while ((int)s->pipe_ev.size() < 2 * nchunks) {
@@ -321,18 +368,41 @@ int loc_snapshot_solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* di
         hipError_t e = locamd::launch_pack_kmb(s->d_raw_dist + roff, s->d_dist + toff, s->B, s->M, s->M4, kc, 0.f, s->own_stream);
         if (e == hipSuccess) e = locamd::launch_pack_kmb(s->d_raw_err + roff, s->d_err + toff, s->B, s->M, s->M4, kc, 0.f, s->own_stream);
         if (e != hipSuccess) return fail_hip(e, "launch_pack_kmb");
-        int rc = loc_snapshot_solve_device(s, kc, s->d_dist + toff, s->d_err + toff, s->d_out_pos + (size_t)k0 * 3 * B,
-                                           s->d_out_chi2 + (size_t)k0 * B, s->d_out_trials + (size_t)k0 * B, s->own_stream);
+        int rc = solve_device(s, kc, s->d_dist + toff, s->d_err + toff, s->d_out_pos + (size_t)k0 * 3 * B, s->d_out_chi2 + (size_t)k0 * B,
+                              s->d_out_trials + (size_t)k0 * B, cov_h ? s->d_out_cov + (size_t)k0 * 6 * B : nullptr,
+                              cov_h ? s->d_out_cov_mask + (size_t)k0 * B : nullptr, cov_h ? s->d_out_cov_status + (size_t)k0 * B : nullptr,
+                              s->own_stream);
         if (rc != LOC_OK) return rc;
         LOC_HIP(hipEventRecord(s->pipe_ev[2 * c + 1], s->own_stream));
         LOC_HIP(hipStreamWaitEvent(s->out_stream, s->pipe_ev[2 * c + 1], 0));
         LOC_HIP(hipMemcpyAsync(out_pos_h + (size_t)k0 * 3 * B, s->d_out_pos + (size_t)k0 * 3 * B, sizeof(double) * 3 * B * (size_t)kc, hipMemcpyDeviceToHost, s->out_stream));
         LOC_HIP(hipMemcpyAsync(out_chi2_h + (size_t)k0 * B, s->d_out_chi2 + (size_t)k0 * B, sizeof(double) * B * (size_t)kc, hipMemcpyDeviceToHost, s->out_stream));
         if (out_trials_h) LOC_HIP(hipMemcpyAsync(out_trials_h + (size_t)k0 * B, s->d_out_trials + (size_t)k0 * B, B * (size_t)kc, hipMemcpyDeviceToHost, s->out_stream));
+        if (cov_h) {
+            LOC_HIP(hipMemcpyAsync(cov_h + (size_t)k0 * 6 * B, s->d_out_cov + (size_t)k0 * 6 * B, sizeof(double) * 6 * B * (size_t)kc, hipMemcpyDeviceToHost, s->out_stream));
+            LOC_HIP(hipMemcpyAsync(cov_mask_h + (size_t)k0 * B, s->d_out_cov_mask + (size_t)k0 * B, sizeof(int32_t) * B * (size_t)kc, hipMemcpyDeviceToHost, s->out_stream));
+            LOC_HIP(hipMemcpyAsync(cov_status_h + (size_t)k0 * B, s->d_out_cov_status + (size_t)k0 * B, sizeof(int32_t) * B * (size_t)kc, hipMemcpyDeviceToHost, s->out_stream));
+        }
     }
     LOC_HIP(hipStreamSynchronize(s->out_stream));
     LOC_HIP(hipStreamSynchronize(s->own_stream));
     return LOC_OK;
+}
+
+extern "C" {
+
+int loc_snapshot_solve_host_kmb(loc_snapshot* s, int32_t epochs, const float* dist_kmb, const float* err_kmb,
+                                double* out_pos_h, double* out_chi2_h, uint8_t* out_trials_h) {
+    if (!s) return fail(LOC_ERR_INVALID, "null handle");
+    return solve_host_kmb(s, epochs, dist_kmb, err_kmb, out_pos_h, out_chi2_h, out_trials_h, nullptr, nullptr, nullptr);
+}
+
+int loc_snapshot_solve_host_kmb_cov(loc_snapshot* s, int32_t epochs, const float* dist_kmb, const float* err_kmb,
+                                    double* out_pos_h, double* out_chi2_h, uint8_t* out_trials_h,
+                                    double* out_cov_h, int32_t* out_cov_mask_h, int32_t* out_cov_status_h) {
+    if (!s) return fail(LOC_ERR_INVALID, "null handle");
+    if (!out_cov_h || !out_cov_mask_h || !out_cov_status_h) return fail(LOC_ERR_INVALID, "covariance outputs: all three are required");
+    return solve_host_kmb(s, epochs, dist_kmb, err_kmb, out_pos_h, out_chi2_h, out_trials_h, out_cov_h, out_cov_mask_h, out_cov_status_h);
 }
 
 int loc_host_alloc(void** out, size_t bytes) {

@@ -42,6 +42,10 @@ struct loc_fusion {
     int raw_epochs = 0;
     hipStream_t in_stream = nullptr, out_stream = nullptr;
     std::vector<hipEvent_t> pipe_ev;
+    // covariance outputs of the pipelined host path (loc_fusion_solve_host_kmb_cov), allocated on its first call
+    double* d_out_cov = nullptr;
+    int32_t *d_out_cov_mask = nullptr, *d_out_cov_status = nullptr;
+    int cov_epochs = 0;
 };
 
 static int fusion_ensure_staging(loc_fusion* f, int32_t epochs);
@@ -69,6 +73,9 @@ int loc_fusion_destroy(loc_fusion* f) {
     for (hipEvent_t ev : f->ev) (void)hipEventDestroy(ev);
     if (f->d_raw_dist) (void)hipFree(f->d_raw_dist);
     if (f->d_raw_err) (void)hipFree(f->d_raw_err);
+    if (f->d_out_cov) (void)hipFree(f->d_out_cov);
+    if (f->d_out_cov_mask) (void)hipFree(f->d_out_cov_mask);
+    if (f->d_out_cov_status) (void)hipFree(f->d_out_cov_status);
     if (f->in_stream) (void)hipStreamDestroy(f->in_stream);
     if (f->out_stream) (void)hipStreamDestroy(f->out_stream);
     if (f->d_anchors) (void)hipFree(f->d_anchors);
@@ -135,9 +142,11 @@ int loc_fusion_get_poses(loc_fusion* f, double* pose) {
     return LOC_OK;
 }
 
-int loc_fusion_solve_device(loc_fusion* f, int32_t epochs, const float* dist, const float* err, const double* imu,
-                            double* out_pose, double* out_chi2, uint8_t* out_trials, void* hip_stream) {
-    if (!f) return locamd_fail(LOC_ERR_INVALID, "null handle");
+}  // extern "C"
+
+// the device path of both forms: cov == nullptr launches the plain solve, otherwise its COV twin
+static int fusion_solve_device(loc_fusion* f, int32_t epochs, const float* dist, const float* err, const double* imu, double* out_pose,
+                               double* out_chi2, uint8_t* out_trials, double* cov, int32_t* cov_mask, int32_t* cov_status, void* hip_stream) {
     if (epochs <= 0 || !dist || !err || !imu || !out_pose || !out_chi2) return locamd_fail(LOC_ERR_INVALID, "solve arguments");
     if (((uintptr_t)dist | (uintptr_t)err | (uintptr_t)imu) & 15u) return locamd_fail(LOC_ERR_INVALID, "inputs must be 16-byte aligned");
     LOC_HIP(hipSetDevice(f->device));
@@ -152,13 +161,37 @@ int loc_fusion_solve_device(loc_fusion* f, int32_t epochs, const float* dist, co
     const bool pair = f->timing && (size_t)(f->ev_used + 2) <= f->ev.size();
     LOC_HIP(hipEventRecord(f->ev0, st));
     if (pair) LOC_HIP(hipEventRecord(f->ev[f->ev_used], st));
-    hipError_t e = locamd::launch_fusion(a, f->prm.block_threads, st);
+    hipError_t e;
+    if (!cov) {
+        e = locamd::launch_fusion(a, f->prm.block_threads, st);
+    } else {
+        locamd::FusionCovArgs ca;
+        static_cast<locamd::FusionArgs&>(ca) = a;
+        ca.out_cov = cov; ca.out_cov_mask = cov_mask; ca.out_cov_status = cov_status;
+        e = locamd::launch_fusion_cov(ca, f->prm.block_threads, st);
+    }
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_fusion");
     if (pair) { LOC_HIP(hipEventRecord(f->ev[f->ev_used + 1], st)); f->ev_used += 2; }
     LOC_HIP(hipEventRecord(f->ev1, st));
     f->timed = true;
     f->epochs_done += epochs;
     return LOC_OK;
+}
+
+extern "C" {
+
+int loc_fusion_solve_device(loc_fusion* f, int32_t epochs, const float* dist, const float* err, const double* imu,
+                            double* out_pose, double* out_chi2, uint8_t* out_trials, void* hip_stream) {
+    if (!f) return locamd_fail(LOC_ERR_INVALID, "null handle");
+    return fusion_solve_device(f, epochs, dist, err, imu, out_pose, out_chi2, out_trials, nullptr, nullptr, nullptr, hip_stream);
+}
+
+int loc_fusion_solve_device_cov(loc_fusion* f, int32_t epochs, const float* dist, const float* err, const double* imu,
+                                double* out_pose, double* out_chi2, uint8_t* out_trials,
+                                double* out_cov, int32_t* out_cov_mask, int32_t* out_cov_status, void* hip_stream) {
+    if (!f) return locamd_fail(LOC_ERR_INVALID, "null handle");
+    if (!out_cov || !out_cov_mask || !out_cov_status) return locamd_fail(LOC_ERR_INVALID, "covariance outputs: all three are required");
+    return fusion_solve_device(f, epochs, dist, err, imu, out_pose, out_chi2, out_trials, out_cov, out_cov_mask, out_cov_status, hip_stream);
 }
 
 int loc_fusion_solve_host(loc_fusion* f, int32_t epochs, const float* dist_h, const float* err_h, const double* imu_h,
@@ -181,9 +214,12 @@ int loc_fusion_solve_host(loc_fusion* f, int32_t epochs, const float* dist_h, co
     return LOC_OK;
 }
 
-int loc_fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_kmb, const float* err_kmb, const double* imu_h,
-                              double* out_pose_h, double* out_chi2_h, uint8_t* out_trials_h) {
-    if (!f) return locamd_fail(LOC_ERR_INVALID, "null handle");
+}  // extern "C"
+
+// the pipelined host path of both forms: cov == nullptr solves without covariances (and never allocates their staging)
+static int fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_kmb, const float* err_kmb, const double* imu_h,
+                                 double* out_pose_h, double* out_chi2_h, uint8_t* out_trials_h, double* cov_h, int32_t* cov_mask_h,
+                                 int32_t* cov_status_h) {
     if (epochs <= 0 || !dist_kmb || !err_kmb || !imu_h || !out_pose_h || !out_chi2_h) return locamd_fail(LOC_ERR_INVALID, "solve arguments");
     LOC_HIP(hipSetDevice(f->device));
     const size_t B = (size_t)f->B, M = (size_t)f->M;
@@ -196,6 +232,16 @@ int loc_fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_k
         LOC_HIP(hipMalloc((void**)&f->d_raw_err, sizeof(float) * M * B * (size_t)epochs));
         f->raw_epochs = epochs;
     }
+    if (cov_h && epochs > f->cov_epochs) {
+        if (f->d_out_cov) (void)hipFree(f->d_out_cov);
+        if (f->d_out_cov_mask) (void)hipFree(f->d_out_cov_mask);
+        if (f->d_out_cov_status) (void)hipFree(f->d_out_cov_status);
+        f->d_out_cov = nullptr; f->d_out_cov_mask = f->d_out_cov_status = nullptr; f->cov_epochs = 0;
+        LOC_HIP(hipMalloc((void**)&f->d_out_cov, sizeof(double) * 21 * B * (size_t)epochs));
+        LOC_HIP(hipMalloc((void**)&f->d_out_cov_mask, sizeof(int32_t) * B * (size_t)epochs));
+        LOC_HIP(hipMalloc((void**)&f->d_out_cov_status, sizeof(int32_t) * B * (size_t)epochs));
+        f->cov_epochs = epochs;
+    }
     if (!f->in_stream) LOC_HIP(hipStreamCreateWithFlags(&f->in_stream, hipStreamNonBlocking));
     if (!f->out_stream) LOC_HIP(hipStreamCreateWithFlags(&f->out_stream, hipStreamNonBlocking));
     // same chunked three-stream pipeline as loc_snapshot_solve_host_kmb (capi.cpp); pageable buffers go as one chunk
@@ -204,7 +250,8 @@ int loc_fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_k
         if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
         return at.type == hipMemoryTypeHost;
     };
-    const bool overlap = pinned(dist_kmb) && pinned(err_kmb) && pinned(imu_h) && pinned(out_pose_h) && pinned(out_chi2_h);
+    const bool overlap = pinned(dist_kmb) && pinned(err_kmb) && pinned(imu_h) && pinned(out_pose_h) && pinned(out_chi2_h) &&
+                         (!cov_h || (pinned(cov_h) && pinned(cov_mask_h) && pinned(cov_status_h)));
     const int ce = overlap ? (int)std::max<size_t>(1, (8u << 20) / (B * 8 * sizeof(double))) : epochs;
     const int nchunks = (epochs + ce - 1) / ce;
     while ((int)f->pipe_ev.size() < 2 * nchunks) {
@@ -223,18 +270,42 @@ int loc_fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_k
         hipError_t e = locamd::launch_pack_kmb(f->d_raw_dist + roff, f->d_dist + toff, f->B, f->M, 2, kc, 0.f, f->stream);
         if (e == hipSuccess) e = locamd::launch_pack_kmb(f->d_raw_err + roff, f->d_err + toff, f->B, f->M, 2, kc, 0.f, f->stream);
         if (e != hipSuccess) return locamd_fail_hip(e, "launch_pack_kmb");
-        int rc = loc_fusion_solve_device(f, kc, f->d_dist + toff, f->d_err + toff, f->d_imu + ioff, f->d_out_pose + (size_t)k0 * 7 * B,
-                                         f->d_out_chi2 + (size_t)k0 * B, f->d_out_trials + (size_t)k0 * B, f->stream);
+        int rc = fusion_solve_device(f, kc, f->d_dist + toff, f->d_err + toff, f->d_imu + ioff, f->d_out_pose + (size_t)k0 * 7 * B,
+                                     f->d_out_chi2 + (size_t)k0 * B, f->d_out_trials + (size_t)k0 * B,
+                                     cov_h ? f->d_out_cov + (size_t)k0 * 21 * B : nullptr, cov_h ? f->d_out_cov_mask + (size_t)k0 * B : nullptr,
+                                     cov_h ? f->d_out_cov_status + (size_t)k0 * B : nullptr, f->stream);
         if (rc != LOC_OK) return rc;
         LOC_HIP(hipEventRecord(f->pipe_ev[2 * c + 1], f->stream));
         LOC_HIP(hipStreamWaitEvent(f->out_stream, f->pipe_ev[2 * c + 1], 0));
         LOC_HIP(hipMemcpyAsync(out_pose_h + (size_t)k0 * 7 * B, f->d_out_pose + (size_t)k0 * 7 * B, sizeof(double) * 7 * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
         LOC_HIP(hipMemcpyAsync(out_chi2_h + (size_t)k0 * B, f->d_out_chi2 + (size_t)k0 * B, sizeof(double) * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
         if (out_trials_h) LOC_HIP(hipMemcpyAsync(out_trials_h + (size_t)k0 * B, f->d_out_trials + (size_t)k0 * B, B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
+        if (cov_h) {
+            LOC_HIP(hipMemcpyAsync(cov_h + (size_t)k0 * 21 * B, f->d_out_cov + (size_t)k0 * 21 * B, sizeof(double) * 21 * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
+            LOC_HIP(hipMemcpyAsync(cov_mask_h + (size_t)k0 * B, f->d_out_cov_mask + (size_t)k0 * B, sizeof(int32_t) * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
+            LOC_HIP(hipMemcpyAsync(cov_status_h + (size_t)k0 * B, f->d_out_cov_status + (size_t)k0 * B, sizeof(int32_t) * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
+        }
     }
     LOC_HIP(hipStreamSynchronize(f->out_stream));
     LOC_HIP(hipStreamSynchronize(f->stream));
     return LOC_OK;
+}
+
+extern "C" {
+
+int loc_fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dist_kmb, const float* err_kmb, const double* imu_h,
+                              double* out_pose_h, double* out_chi2_h, uint8_t* out_trials_h) {
+    if (!f) return locamd_fail(LOC_ERR_INVALID, "null handle");
+    return fusion_solve_host_kmb(f, epochs, dist_kmb, err_kmb, imu_h, out_pose_h, out_chi2_h, out_trials_h, nullptr, nullptr, nullptr);
+}
+
+int loc_fusion_solve_host_kmb_cov(loc_fusion* f, int32_t epochs, const float* dist_kmb, const float* err_kmb, const double* imu_h,
+                                  double* out_pose_h, double* out_chi2_h, uint8_t* out_trials_h,
+                                  double* out_cov_h, int32_t* out_cov_mask_h, int32_t* out_cov_status_h) {
+    if (!f) return locamd_fail(LOC_ERR_INVALID, "null handle");
+    if (!out_cov_h || !out_cov_mask_h || !out_cov_status_h) return locamd_fail(LOC_ERR_INVALID, "covariance outputs: all three are required");
+    return fusion_solve_host_kmb(f, epochs, dist_kmb, err_kmb, imu_h, out_pose_h, out_chi2_h, out_trials_h, out_cov_h, out_cov_mask_h,
+                                 out_cov_status_h);
 }
 
 int loc_fusion_last_kernel_ms(loc_fusion* f, double* ms) {

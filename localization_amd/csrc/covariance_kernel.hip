@@ -22,6 +22,7 @@
 //   * selected inversion, backwards: Sigma_{n-1} = S_{n-1}^-1, Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (lane = entry).
 // D = 3 for translation-only batches (capi_window.cpp: translation_only — 3x3 blocks, the rotation bits always set), D = 6 otherwise.
 #include "se3_edge_device.h"
+#include "cov_device.h"
 
 #include <float.h>
 #include <math.h>
@@ -35,7 +36,6 @@ namespace {
 extern __shared__ double cvlds[];
 
 constexpr int kCovChunk = 64;   // edges linearised per pass (one per lane)
-constexpr double kCovRelPivot = 1e-11;   // relative pivot threshold
 constexpr int kCovSRec = 21 + 21 + 36;   // EdgeSE3 record: H_ii, H_jj (lower triangles), the coupling block (rows: the later pose, column-major)
 
 // LDS layout of one window (offsets in doubles; the int tables follow the doubles)

@@ -23,6 +23,16 @@ struct FusionArgs {
     int jacobian;          // 0: analytic range Jacobians, 1: g2o's central differences (delta = 1e-9)
 };
 
+// The COV = true kernels' arguments: the solve's, plus each update's marginal covariance of the pose, SoA over tags.
+// Coordinates: VertexSE3's minimal increment [dt (body), dq_xyz].
+struct FusionCovArgs : FusionArgs {
+    double* out_cov;          // [K][21][B]: row-major upper triangle of the 6x6 H^-1 (NaN when singular)
+    int32_t* out_cov_mask;    // [K][B]: bits 0-5 = tx ty tz qx qy qz excluded (an exactly zero diagonal entry of H)
+    int32_t* out_cov_status;  // [K][B]: LOC_OK or LOC_ERR_SINGULAR
+};
+
 hipError_t launch_fusion(const FusionArgs& a, int block_threads, hipStream_t stream);
+// The same solve (bit for bit) with the covariance outputs as well; hipErrorInvalidValue if any of them is null.
+hipError_t launch_fusion_cov(const FusionCovArgs& a, int block_threads, hipStream_t stream);
 
 }  // namespace locamd

@@ -18,9 +18,12 @@
 #include "device_math.h"
 #include "numeric_jacobian.h"
 #include "lm_damping.h"
+#include "cov_device.h"
 
 #include <float.h>
 #include <math.h>
+
+#include <type_traits>
 
 namespace locamd {
 
@@ -276,8 +279,10 @@ constexpr int NEXT_DOUBLES = 28;
 constexpr int RAW_PIECES = 8;
 constexpr int FUSION_LDS_BYTES = 2 * NEXT_DOUBLES * 256 * 8 + RAW_PIECES * 256 * 16;
 
-template <int JAC>
-__global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
+// COV: also the update's marginal covariance (cov_device.h) from `cur`, the undamped system at the pose it emits; COV = false is the
+// plain solve, instruction for instruction
+template <int JAC, bool COV>
+__global__ void __launch_bounds__(256) fusion_lm_kernel(const std::conditional_t<COV, FusionCovArgs, FusionArgs> a) {
     __shared__ __attribute__((aligned(16))) char lds_bytes[FUSION_LDS_BYTES];
     double* const s_ep = reinterpret_cast<double*>(lds_bytes);                            // [2][28][256]
     float4* const s_raw = reinterpret_cast<float4*>(lds_bytes + 2 * NEXT_DOUBLES * 256 * 8);  // [8][256]
@@ -471,6 +476,17 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
                 op[3 * B] = qq[1]; op[4 * B] = qq[2]; op[5 * B] = qq[3]; op[6 * B] = qq[0];
                 a.out_chi2[(long long)k * B + inst] = last_chi;
                 if (a.out_trials) a.out_trials[(long long)k * B + inst] = (uint8_t)(trials > 255 ? 255 : trials);
+                if constexpr (COV) {
+                    double hc[21];
+#pragma unroll
+                    for (int i = 0; i < 21; ++i) hc[i] = cur.h[i];
+                    int msk;
+                    const bool cok = cov_invert_packed<6>(hc, msk);
+#pragma unroll
+                    for (int i = 0; i < 21; ++i) a.out_cov[((long long)k * 21 + i) * B + inst] = hc[i];
+                    a.out_cov_mask[(long long)k * B + inst] = msk;
+                    a.out_cov_status[(long long)k * B + inst] = cok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+                }
                 if (k + 1 >= K) {
                     exhausted = true;
                     a.pose[0 * B + inst] = X.t[0]; a.pose[1 * B + inst] = X.t[1]; a.pose[2 * B + inst] = X.t[2];
@@ -501,17 +517,25 @@ __global__ void __launch_bounds__(256) fusion_lm_kernel(const FusionArgs a) {
     }
 }
 
-}  // namespace
-
-hipError_t launch_fusion(const FusionArgs& a, int block_threads, hipStream_t stream) {
+template <bool COV, class Args>
+hipError_t launch_t(const Args& a, int block_threads, hipStream_t stream) {
     if (a.B <= 0 || a.K <= 0) return hipErrorInvalidValue;
     if (block_threads <= 0) block_threads = 256;
     if (block_threads % 64 || block_threads > 256) return hipErrorInvalidValue;
     const long long blocks = (a.B + block_threads - 1) / block_threads;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (a.jacobian) hipLaunchKernelGGL(fusion_lm_kernel<1>, dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, a);
-    else hipLaunchKernelGGL(fusion_lm_kernel<0>, dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, a);
+    if (a.jacobian) hipLaunchKernelGGL((fusion_lm_kernel<1, COV>), dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, a);
+    else hipLaunchKernelGGL((fusion_lm_kernel<0, COV>), dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, a);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_fusion(const FusionArgs& a, int block_threads, hipStream_t stream) { return launch_t<false>(a, block_threads, stream); }
+
+hipError_t launch_fusion_cov(const FusionCovArgs& a, int block_threads, hipStream_t stream) {
+    if (!a.out_cov || !a.out_cov_mask || !a.out_cov_status) return hipErrorInvalidValue;
+    return launch_t<true>(a, block_threads, stream);
 }
 
 }  // namespace locamd

@@ -21,8 +21,17 @@ struct SnapshotArgs {
     int gate_from_epoch;  // epochs k < gate_from_epoch run un-gated (reference warm-up, localization.cpp:309)
 };
 
+// The COV = true kernels' arguments: the solve's, plus each update's marginal covariance of the position, SoA over tags.
+struct SnapshotCovArgs : SnapshotArgs {
+    double* out_cov;          // [K][6][B]: xx xy xz yy yz zz of H^-1 at the emitted position (NaN when singular)
+    int32_t* out_cov_mask;    // [K][B]: bits 0-2 = tx ty tz excluded (an exactly zero diagonal entry of H)
+    int32_t* out_cov_status;  // [K][B]: LOC_OK or LOC_ERR_SINGULAR
+};
+
 // Returns hipSuccess or the launch error; hipErrorInvalidValue if (m_pad, lpi, jac) has no instantiation.
 hipError_t launch_snapshot(const SnapshotArgs& a, int m_pad, int lpi, int jac, int block_threads, hipStream_t stream);
+// The same solve (bit for bit) with the covariance outputs as well; hipErrorInvalidValue if any of them is null.
+hipError_t launch_snapshot_cov(const SnapshotCovArgs& a, int m_pad, int lpi, int jac, int block_threads, hipStream_t stream);
 // true if a kernel exists for this combination
 bool snapshot_supported(int m_pad, int lpi);
 // [K][M][B] float (anchor-major SoA, the layout a host caller naturally holds) -> float4 tiles [K][M4][B][4], slots

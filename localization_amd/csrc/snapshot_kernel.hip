@@ -37,9 +37,12 @@
 #include "snapshot_kernel.h"
 #include "device_math.h"
 #include "lm_damping.h"
+#include "cov_device.h"
 
 #include <float.h>
 #include <math.h>
+
+#include <type_traits>
 
 namespace locamd {
 
@@ -235,8 +238,10 @@ template <int APL> struct SnapshotLds {
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef const __attribute__((address_space(1))) void* glb_void_ptr;
 
-template <int LPI, int APL, int JAC>
-__global__ void __launch_bounds__(256) snapshot_lm_kernel(const SnapshotArgs a) {
+// COV: also the update's marginal covariance (cov_device.h) from `cur`, the undamped system at the estimate it emits; COV = false is
+// the plain solve, instruction for instruction
+template <int LPI, int APL, int JAC, bool COV>
+__global__ void __launch_bounds__(256) snapshot_lm_kernel(const std::conditional_t<COV, SnapshotCovArgs, SnapshotArgs> a) {
     __shared__ __attribute__((aligned(16))) char lds_bytes[SnapshotLds<APL>::BYTES];
     double2* const s_next = reinterpret_cast<double2*>(lds_bytes);
     float4* const s_raw = reinterpret_cast<float4*>(lds_bytes + SnapshotLds<APL>::NEXT_BYTES);
@@ -397,6 +402,16 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const SnapshotArgs a) 
                     a.out_pos[((long long)k * 3 + 2) * B + inst] = pz;
                     a.out_chi2[(long long)k * B + inst] = last_chi;
                     if (a.out_trials) a.out_trials[(long long)k * B + inst] = (uint8_t)(trials > 255 ? 255 : trials);
+                    if constexpr (COV) {
+                        // every lane of the tag holds these bits (DPP butterflies): lane g == 0 inverts them
+                        double hc[6] = {cur.h00, cur.h01, cur.h02, cur.h11, cur.h12, cur.h22};
+                        int msk;
+                        const bool cok = cov_invert_packed<3>(hc, msk);
+#pragma unroll
+                        for (int i = 0; i < 6; ++i) a.out_cov[((long long)k * 6 + i) * B + inst] = hc[i];
+                        a.out_cov_mask[(long long)k * B + inst] = msk;
+                        a.out_cov_status[(long long)k * B + inst] = cok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+                    }
                 }
                 if (k + 1 >= K) {
                     exhausted = true;
@@ -431,18 +446,40 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const SnapshotArgs a) 
     }
 }
 
-template <int LPI, int APL, int JAC>
-hipError_t launch_one(const SnapshotArgs& a, int block_threads, hipStream_t stream) {
+template <int LPI, int APL, int JAC, bool COV, class Args>
+hipError_t launch_one(const Args& a, int block_threads, hipStream_t stream) {
     const long long lanes = a.B * LPI;
     const long long blocks = (lanes + block_threads - 1) / block_threads;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((snapshot_lm_kernel<LPI, APL, JAC>), dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, a);
+    hipLaunchKernelGGL((snapshot_lm_kernel<LPI, APL, JAC, COV>), dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, a);
     return hipGetLastError();
 }
 
-template <int LPI, int APL>
-hipError_t launch_jac(const SnapshotArgs& a, int jac, int block_threads, hipStream_t stream) {
-    return jac == 0 ? launch_one<LPI, APL, 0>(a, block_threads, stream) : launch_one<LPI, APL, 1>(a, block_threads, stream);
+template <int LPI, int APL, bool COV, class Args>
+hipError_t launch_jac(const Args& a, int jac, int block_threads, hipStream_t stream) {
+    return jac == 0 ? launch_one<LPI, APL, 0, COV>(a, block_threads, stream) : launch_one<LPI, APL, 1, COV>(a, block_threads, stream);
+}
+
+template <bool COV, class Args>
+hipError_t launch_mapping(const Args& a, int m_pad, int lpi, int jac, int block_threads, hipStream_t stream) {
+    if (!snapshot_supported(m_pad, lpi)) return hipErrorInvalidValue;
+    if (block_threads <= 0) block_threads = 256;
+    if (block_threads % 64 || block_threads > 256) return hipErrorInvalidValue;
+    switch (m_pad * 100 + lpi) {
+        case 401: return launch_jac<1, 4, COV>(a, jac, block_threads, stream);
+        case 402: return launch_jac<2, 2, COV>(a, jac, block_threads, stream);
+        case 404: return launch_jac<4, 1, COV>(a, jac, block_threads, stream);
+        case 801: return launch_jac<1, 8, COV>(a, jac, block_threads, stream);
+        case 802: return launch_jac<2, 4, COV>(a, jac, block_threads, stream);
+        case 804: return launch_jac<4, 2, COV>(a, jac, block_threads, stream);
+        case 808: return launch_jac<8, 1, COV>(a, jac, block_threads, stream);
+        case 1201: return launch_jac<1, 12, COV>(a, jac, block_threads, stream);
+        case 1601: return launch_jac<1, 16, COV>(a, jac, block_threads, stream);
+        case 1602: return launch_jac<2, 8, COV>(a, jac, block_threads, stream);
+        case 1604: return launch_jac<4, 4, COV>(a, jac, block_threads, stream);
+        case 1608: return launch_jac<8, 2, COV>(a, jac, block_threads, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
@@ -485,24 +522,12 @@ bool snapshot_supported(int m_pad, int lpi) {
 }
 
 hipError_t launch_snapshot(const SnapshotArgs& a, int m_pad, int lpi, int jac, int block_threads, hipStream_t stream) {
-    if (!snapshot_supported(m_pad, lpi)) return hipErrorInvalidValue;
-    if (block_threads <= 0) block_threads = 256;
-    if (block_threads % 64 || block_threads > 256) return hipErrorInvalidValue;
-    switch (m_pad * 100 + lpi) {
-        case 401: return launch_jac<1, 4>(a, jac, block_threads, stream);
-        case 402: return launch_jac<2, 2>(a, jac, block_threads, stream);
-        case 404: return launch_jac<4, 1>(a, jac, block_threads, stream);
-        case 801: return launch_jac<1, 8>(a, jac, block_threads, stream);
-        case 802: return launch_jac<2, 4>(a, jac, block_threads, stream);
-        case 804: return launch_jac<4, 2>(a, jac, block_threads, stream);
-        case 808: return launch_jac<8, 1>(a, jac, block_threads, stream);
-        case 1201: return launch_jac<1, 12>(a, jac, block_threads, stream);
-        case 1601: return launch_jac<1, 16>(a, jac, block_threads, stream);
-        case 1602: return launch_jac<2, 8>(a, jac, block_threads, stream);
-        case 1604: return launch_jac<4, 4>(a, jac, block_threads, stream);
-        case 1608: return launch_jac<8, 2>(a, jac, block_threads, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_mapping<false>(a, m_pad, lpi, jac, block_threads, stream);
+}
+
+hipError_t launch_snapshot_cov(const SnapshotCovArgs& a, int m_pad, int lpi, int jac, int block_threads, hipStream_t stream) {
+    if (!a.out_cov || !a.out_cov_mask || !a.out_cov_status) return hipErrorInvalidValue;
+    return launch_mapping<true>(a, m_pad, lpi, jac, block_threads, stream);
 }
 
 }  // namespace locamd

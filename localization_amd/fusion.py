@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .snapshot import pack_ranges
+from .snapshot import _check_cov_host, _check_cov_outputs, pack_ranges
 
 
 class FusionParams(C.Structure):
@@ -40,6 +40,7 @@ class FusionSolver:
             raise _lib.LocalizationAmdError(_lib.LOC_ERR_NO_DEVICE, "no HIP device visible: localization_amd has no CPU fallback")
         anchors = np.ascontiguousarray(anchors, dtype=np.float64)
         self.M, self.B, self.device, self.L = anchors.shape[0], int(batch), int(device), L
+        self._pinned = []
         prm = FusionParams()
         L.loc_fusion_default_params(C.byref(prm))
         prm.maximum_iteration = int(maximum_iteration); prm.distance_outlier = float(distance_outlier)
@@ -52,6 +53,9 @@ class FusionSolver:
 
     def close(self):
         if getattr(self, "h", None):
+            for p in getattr(self, "_pinned", []):
+                self.L.loc_host_free(p)
+            self._pinned = []
             self.L.loc_fusion_destroy(self.h)
             self.h = None
 
@@ -84,26 +88,70 @@ class FusionSolver:
                                            pose.ctypes.data_as(dp), chi2.ctypes.data_as(dp), trials.ctypes.data_as(C.POINTER(C.c_uint8))))
         return pose, chi2, trials
 
-    def solve_stream(self, dist_kmb, err_kmb, imu_kb8):
-        """The pipelined host path (loc_fusion_solve_host_kmb): natural [K][M][B] arrays, tiles packed on the GPU."""
+    def solve_stream(self, dist_kmb, err_kmb, imu_kb8, covariance=False, out=None):
+        """The pipelined host path (loc_fusion_solve_host_kmb): natural [K][M][B] arrays, tiles packed on the GPU.
+        covariance=True (loc_fusion_solve_host_kmb_cov) returns (pose, chi2, trials, cov, mask, status) with cov unpacked to full
+        symmetric [K][B][6][6] in [tx ty tz qx qy qz]; `out` = (pose, chi2, trials, cov [K][21][B], mask, status) to reuse (e.g. pinned)
+        output arrays there."""
         d = np.ascontiguousarray(dist_kmb, dtype=np.float32); e = np.ascontiguousarray(err_kmb, dtype=np.float32)
         imu = np.ascontiguousarray(imu_kb8, dtype=np.float64)
         K = d.shape[0]
         assert d.shape == (K, self.M, self.B) and e.shape == d.shape and imu.shape == (K, self.B, 8)
-        pose = np.empty((K, 7, self.B)); chi2 = np.empty((K, self.B)); trials = np.empty((K, self.B), dtype=np.uint8)
-        self.L.loc_fusion_solve_host_kmb.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
-        check(self.L.loc_fusion_solve_host_kmb(self.h, K, d.ctypes.data, e.ctypes.data, imu.ctypes.data, pose.ctypes.data,
-                                               chi2.ctypes.data, trials.ctypes.data))
-        return pose, chi2, trials
+        if not covariance:
+            pose = np.empty((K, 7, self.B)); chi2 = np.empty((K, self.B)); trials = np.empty((K, self.B), dtype=np.uint8)
+            self.L.loc_fusion_solve_host_kmb.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+            check(self.L.loc_fusion_solve_host_kmb(self.h, K, d.ctypes.data, e.ctypes.data, imu.ctypes.data, pose.ctypes.data,
+                                                   chi2.ctypes.data, trials.ctypes.data))
+            return pose, chi2, trials
+        if out is None:
+            out = (np.empty((K, 7, self.B)), np.empty((K, self.B)), np.empty((K, self.B), dtype=np.uint8),
+                   np.empty((K, 21, self.B)), np.empty((K, self.B), dtype=np.int32), np.empty((K, self.B), dtype=np.int32))
+        pose, chi2, trials, cov, mask, status = out
+        assert pose.shape == (K, 7, self.B) and pose.dtype == np.float64 and chi2.shape == (K, self.B) and trials.shape == (K, self.B)
+        _check_cov_host(cov, mask, status, K, 21, self.B)
+        check(self.L.loc_fusion_solve_host_kmb_cov(self.h, K, d.ctypes.data, e.ctypes.data, imu.ctypes.data, pose.ctypes.data,
+                                                   chi2.ctypes.data, trials.ctypes.data, cov.ctypes.data, mask.ctypes.data,
+                                                   status.ctypes.data))
+        return pose, chi2, trials, _lib.unpack_covariance(cov, 6), mask, status
 
-    def solve_device(self, dist_tiles, err_tiles, imu, out_pose, out_chi2, out_trials=None):
+    def pinned(self, shape, dtype):
+        """A page-locked numpy array (loc_host_alloc); freed when the solver is closed."""
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        p = C.c_void_p()
+        check(self.L.loc_host_alloc(C.byref(p), n))
+        self._pinned.append(p)
+        return np.frombuffer((C.c_char * n).from_address(p.value), dtype=dtype).reshape(shape)
+
+    def alloc_outputs(self, K, trials=True, covariance=False):
+        """(pose [K][7][B], chi2, trials) device tensors; with covariance=True also (cov [K][21][B] f64, mask [K][B] i32, status [K][B] i32)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = (torch.empty((K, 7, self.B), dtype=torch.float64, device=dev), torch.empty((K, self.B), dtype=torch.float64, device=dev),
+               torch.empty((K, self.B), dtype=torch.uint8, device=dev) if trials else None)
+        if not covariance:
+            return out
+        return out + (torch.empty((K, 21, self.B), dtype=torch.float64, device=dev), torch.empty((K, self.B), dtype=torch.int32, device=dev),
+                      torch.empty((K, self.B), dtype=torch.int32, device=dev))
+
+    def solve_device(self, dist_tiles, err_tiles, imu, out_pose, out_chi2, out_trials=None, out_cov=None, out_cov_mask=None,
+                     out_cov_status=None):
+        """Asynchronous on the current torch stream.  out_cov / out_cov_mask / out_cov_status (all three or none): each update's
+        marginal covariance of the pose (loc_fusion_solve_device_cov: [K][21][B], [K][B] mask bits, [K][B] status)."""
         import torch
         K = dist_tiles.shape[0]
         assert tuple(dist_tiles.shape) == (K, 2, self.B, 4) and tuple(imu.shape) == (K, self.B, 8)
         assert tuple(out_pose.shape) == (K, 7, self.B) and tuple(out_chi2.shape) == (K, self.B)
         for x in (dist_tiles, err_tiles, imu, out_pose, out_chi2):
             assert x.is_contiguous()
+        cov = _check_cov_outputs(torch, (out_cov, out_cov_mask, out_cov_status), K, 21, self.B, dist_tiles.device)
         stream = torch.cuda.current_stream(dist_tiles.device).cuda_stream
+        if cov:
+            check(self.L.loc_fusion_solve_device_cov(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(), imu.data_ptr(),
+                                                     out_pose.data_ptr(), out_chi2.data_ptr(),
+                                                     out_trials.data_ptr() if out_trials is not None else None,
+                                                     out_cov.data_ptr(), out_cov_mask.data_ptr(), out_cov_status.data_ptr(),
+                                                     C.c_void_p(stream)))
+            return
         check(self.L.loc_fusion_solve_device(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(), imu.data_ptr(),
                                              out_pose.data_ptr(), out_chi2.data_ptr(),
                                              out_trials.data_ptr() if out_trials is not None else None, C.c_void_p(stream)))

@@ -27,6 +27,26 @@ def unpack_ranges(tiles, M):
     return np.ascontiguousarray(t.transpose(0, 1, 3, 2).reshape(K, M4 * 4, B)[:, :M, :])
 
 
+def _check_cov_outputs(t, outs, K, T, B, dev):
+    """all three covariance output tensors or none; True if given"""
+    given = [x is not None for x in outs]
+    if not any(given):
+        return False
+    if not all(given):
+        raise ValueError("out_cov, out_cov_mask and out_cov_status go together: pass all three or none")
+    cov, mask, status = outs
+    assert tuple(cov.shape) == (K, T, B) and cov.dtype == t.float64 and cov.is_contiguous() and cov.device == dev
+    for x in (mask, status):
+        assert tuple(x.shape) == (K, B) and x.dtype == t.int32 and x.is_contiguous() and x.device == dev
+    return True
+
+
+def _check_cov_host(cov, mask, status, K, T, B):
+    assert cov.shape == (K, T, B) and cov.dtype == np.float64 and cov.flags.c_contiguous
+    for x in (mask, status):
+        assert x.shape == (K, B) and x.dtype == np.int32 and x.flags.c_contiguous
+
+
 class SnapshotSolver:
     """B independent tags sharing one anchor map; each `solve` call runs K epochs of
     gate -> Cauchy range factors -> g2o-style LM (reference localization.cpp:297-376 cost, :164-170 solve)."""
@@ -92,15 +112,21 @@ class SnapshotSolver:
     def to_device_tiles(self, x_kmb, pad_value=0.0):
         return self.torch.from_numpy(pack_ranges(x_kmb, pad_value)).to(self.dev)
 
-    def alloc_outputs(self, K, trials=True):
+    def alloc_outputs(self, K, trials=True, covariance=False):
+        """(pos, chi2, trials) device tensors; with covariance=True also (cov [K][6][B] f64, mask [K][B] i32, status [K][B] i32)."""
         t = self.torch
         out_pos = t.empty((K, 3, self.B), dtype=t.float64, device=self.dev)
         out_chi2 = t.empty((K, self.B), dtype=t.float64, device=self.dev)
         out_trials = t.empty((K, self.B), dtype=t.uint8, device=self.dev) if trials else None
-        return out_pos, out_chi2, out_trials
+        if not covariance:
+            return out_pos, out_chi2, out_trials
+        return (out_pos, out_chi2, out_trials, t.empty((K, 6, self.B), dtype=t.float64, device=self.dev),
+                t.empty((K, self.B), dtype=t.int32, device=self.dev), t.empty((K, self.B), dtype=t.int32, device=self.dev))
 
-    def solve_device(self, dist_tiles, err_tiles, out_pos, out_chi2, out_trials=None):
-        """Asynchronous on the current torch stream. Tensors: float32 [K][M4][B][4], outputs as alloc_outputs."""
+    def solve_device(self, dist_tiles, err_tiles, out_pos, out_chi2, out_trials=None, out_cov=None, out_cov_mask=None, out_cov_status=None):
+        """Asynchronous on the current torch stream. Tensors: float32 [K][M4][B][4], outputs as alloc_outputs.
+        out_cov / out_cov_mask / out_cov_status (all three or none): each update's marginal covariance of the position
+        (loc_snapshot_solve_device_cov: [K][6][B] xx xy xz yy yz zz, [K][B] mask bits, [K][B] LOC_OK / LOC_ERR_SINGULAR)."""
         t = self.torch
         K = dist_tiles.shape[0]
         assert tuple(dist_tiles.shape) == (K, self.M4, self.B, 4) and dist_tiles.dtype == t.float32
@@ -112,7 +138,15 @@ class SnapshotSolver:
             assert tuple(out_trials.shape) == (K, self.B) and out_trials.dtype == t.uint8
         for x in (dist_tiles, err_tiles, out_pos, out_chi2):
             assert x.device == self.dev
+        cov = _check_cov_outputs(t, (out_cov, out_cov_mask, out_cov_status), K, 6, self.B, self.dev)
         stream = t.cuda.current_stream(self.dev).cuda_stream
+        if cov:
+            check(self.L.loc_snapshot_solve_device_cov(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(),
+                                                       out_pos.data_ptr(), out_chi2.data_ptr(),
+                                                       out_trials.data_ptr() if out_trials is not None else None,
+                                                       out_cov.data_ptr(), out_cov_mask.data_ptr(), out_cov_status.data_ptr(),
+                                                       C.c_void_p(stream)))
+            return
         check(self.L.loc_snapshot_solve_device(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(),
                                                out_pos.data_ptr(), out_chi2.data_ptr(),
                                                out_trials.data_ptr() if out_trials is not None else None,
@@ -141,19 +175,29 @@ class SnapshotSolver:
         self._pinned.append(p)
         return np.frombuffer((C.c_char * n).from_address(p.value), dtype=dtype).reshape(shape)
 
-    def solve_stream(self, dist_kmb, err_kmb, out=None):
+    def solve_stream(self, dist_kmb, err_kmb, out=None, covariance=False):
         """The pipelined host path (loc_snapshot_solve_host_kmb): [K][M][B] float32 host arrays in their natural layout,
         packed into tiles on the GPU, copy-in / solve / copy-out overlapped.  `out` = (pos, chi2, trials) to reuse
-        (e.g. pinned) output arrays."""
+        (e.g. pinned) output arrays.  covariance=True (loc_snapshot_solve_host_kmb_cov) returns (pos, chi2, trials, cov, mask,
+        status) with cov unpacked to full symmetric [K][B][3][3]; `out` then also holds the packed [K][6][B] f64, mask and
+        status [K][B] int32 arrays."""
         d = np.ascontiguousarray(dist_kmb, dtype=np.float32); e = np.ascontiguousarray(err_kmb, dtype=np.float32)
         K = d.shape[0]
         assert d.shape == (K, self.M, self.B) and e.shape == d.shape
         if out is None:
             out = (np.empty((K, 3, self.B)), np.empty((K, self.B)), np.empty((K, self.B), dtype=np.uint8))
-        pos, chi2, trials = out
+            if covariance:
+                out += (np.empty((K, 6, self.B)), np.empty((K, self.B), dtype=np.int32), np.empty((K, self.B), dtype=np.int32))
+        pos, chi2, trials = out[:3]
         assert pos.shape == (K, 3, self.B) and pos.dtype == np.float64 and chi2.shape == (K, self.B) and trials.shape == (K, self.B)
-        check(self.L.loc_snapshot_solve_host_kmb(self.h, K, d.ctypes.data, e.ctypes.data, pos.ctypes.data, chi2.ctypes.data, trials.ctypes.data))
-        return pos, chi2, trials
+        if not covariance:
+            check(self.L.loc_snapshot_solve_host_kmb(self.h, K, d.ctypes.data, e.ctypes.data, pos.ctypes.data, chi2.ctypes.data, trials.ctypes.data))
+            return pos, chi2, trials
+        cov, mask, status = out[3:]
+        _check_cov_host(cov, mask, status, K, 6, self.B)
+        check(self.L.loc_snapshot_solve_host_kmb_cov(self.h, K, d.ctypes.data, e.ctypes.data, pos.ctypes.data, chi2.ctypes.data,
+                                                     trials.ctypes.data, cov.ctypes.data, mask.ctypes.data, status.ctypes.data))
+        return pos, chi2, trials, _lib.unpack_covariance(cov, 3), mask, status
 
     # ---- HIP-event kernel timing -------------------------------------------------------------------
     def timing_begin(self, max_launches):
