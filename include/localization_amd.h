@@ -315,7 +315,7 @@ void* loc_window_poses_device(loc_window* w);   /* double [B][nv_max][12] */
 void* loc_window_result_device(loc_window* w);  /* double [B][8] */
 int loc_window_timing_begin(loc_window* w, int32_t max_launches);
 int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, double* avg_ms);
-/* Marginal pose covariances of CHAIN windows: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
+/* Marginal pose covariances of CHAIN windows and of FOREST batches: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
  * (rho'_e = 1 / (1 + chi2_e) on every range edge and on every EdgeSE3 whose robust flag is set — g2o's robustInformation without rho''; priors
  * not robustified; range Jacobians in the handle's mode, loc_window_set_jacobian; no LM damping), in g2o VertexSE3's minimal coordinates
  * [dt (body frame), dq_xyz] applied as x * fromVectorMQT(d); Sigma_i = [H^-1]_ii.  Unlike g2o's computeMarginals (which re-factors the H of the
@@ -328,9 +328,14 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
  *   cov    double [n][nv_max][36]  row-major 6x6 per pose slot (slots >= nv: 0)
  *   mask   int32  [n][nv_max]      excluded coordinates, bits 0-5 = tx ty tz qx qy qz
  *   status int32  [n]              LOC_OK or LOC_ERR_SINGULAR (that window's blocks NaN)
- * LOC_ERR_UNSUPPORTED (nothing written) unless every window is a chain of <= 64 poses (nv_max <= 64) without endpoint-1 lever arms (the handle
- * has none set: loc_window_set_endpoint1_offsets(w, 0, NULL)): every pose-to-pose edge, range or EdgeSE3, joins consecutive slots (several per
- * pair, a missing link, any edge order).
+ * Covered (nv_max <= 64, no endpoint-1 lever arms: the handle has none set, loc_window_set_endpoint1_offsets(w, 0, NULL)), LOC_ERR_UNSUPPORTED
+ * with nothing written otherwise:
+ *   - chains (checked first): every pose-to-pose edge of every window, range or EdgeSE3, joins consecutive slots (several per pair, a missing
+ *     link, any edge order);
+ *   - forests, iff the handle would solve the batch on a forest kernel: option "tree" != 0, n at least the forest threshold (256 windows, or
+ *     the chain threshold where loc_window_set_chain_threshold lowered it: 1 serves a single window), every window the same counts and index
+ *     tables, 2 <= nv <= 64, and the pose-to-pose edges form a forest (several edges per pair, either direction, several trees, isolated
+ *     poses).  Always 6x6 blocks.  A tree that no range, prior or lever arm ties to the world is singular (LOC_ERR_SINGULAR for its window).
  * Stateless: does not change the handle's resident batch, last kernel kind / ms, topology cache or options.  Synchronous.  Small calls (inputs
  * and outputs within the 4 MiB staging block) travel as loc_window_solve_host's small ones do; larger ones stage through a device block of
  * their own — unlike a large loc_window_solve_host they leave the resident batch intact. */
@@ -339,8 +344,10 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
                                const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask, int32_t* status);
 /* The same for the uploaded batch at loc_window_poses_device()'s current content (after loc_window_solve_resident: the solved poses),
  * asynchronous on hip_stream (NULL = the handle's own stream; it waits for the last resident launch), into caller-owned device arrays of the
- * layouts above.  LOC_ERR_INVALID before the first resident solve of an upload.  The batch's structure is checked once per upload: for an
- * upload that no solve kernel already classified as a chain, on the first call, which then copies the uploaded tables back and is synchronous. */
+ * layouts above.  LOC_ERR_INVALID before the first resident solve of an upload.  The batch's structure is checked once per upload: an upload
+ * that loc_window_upload classified as a chain or as a forest (whose schedule, already on the device, the pass walks) needs nothing more;
+ * for any other upload the first call copies the uploaded tables back, classifies them (chain, then forest under the rule above, into
+ * tables of the covariance's own) and is synchronous. */
 int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev);
 /* kernel time of the last covariance launch of this handle (HIP events on its stream; a resident launch is waited for), milliseconds */
 int loc_window_last_covariance_ms(loc_window* w, double* ms);

@@ -105,9 +105,18 @@ struct loc_window {
     hipEvent_t cov_ev0 = nullptr, cov_ev1 = nullptr;
     bool cov_pending = false;       // the events of a resident covariance launch have not been read yet
     double cov_ms = 0.0;
-    int resident_cov = 0;           // 3 / 6: the resident batch's block size; 0: not a covariance batch; -1: not classified yet
+    int resident_cov = 0;           // 3 / 6: the resident chain batch's block size; kCovForest / kCovForestOwn: a forest batch on aux[1]'s /
+                                    // cov_aux[1]'s schedule; 0: not a covariance batch; -1: not classified yet
+    // forest batches (forest_covariance_kernel.hip): the schedules the covariance pass builds itself — [0] for loc_window_covariance_host
+    // (kept with the hash of the structure it was built for), [1] for a resident batch no solve classified as a forest.  Never aux[0] /
+    // aux[1]: the host path's topology cache and the resident solve rely on those.
+    WinAux cov_aux[2];
+    bool cov_sched_valid = false;
+    unsigned long long cov_sched_key = 0;
+    int64_t cov_sched_n = 0;
 };
 static constexpr size_t kStageBytes = 4u << 20;
+static constexpr int kCovForest = 7, kCovForestOwn = 8;   // loc_window::resident_cov
 
 // The host passes over a batch (validation, structure hash, chain / translation-only scans) are O(instances x edges) and run in front of a
 // kernel of a millisecond or two: batches of >= 4 096 instances are split over up to eight threads (f(lo, hi) on disjoint instance ranges).
@@ -146,7 +155,8 @@ int loc_window_destroy(loc_window* w) {
     void* ptrs[] = {w->d_anchors, w->d_counts, w->d_ridx, w->d_pidx, w->d_sidx, w->d_poses, w->d_rval, w->d_pval, w->d_sval, w->d_result, w->d_workspace, w->d_poses_in,
                     w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_tree_ws, w->d_arrow_ws,
                     w->aux[0].d_tsched, w->aux[0].d_ahdr, w->aux[0].d_arslot, w->aux[0].d_arec, w->aux[0].d_aprec,
-                    w->aux[1].d_tsched, w->aux[1].d_ahdr, w->aux[1].d_arslot, w->aux[1].d_arec, w->aux[1].d_aprec};
+                    w->aux[1].d_tsched, w->aux[1].d_ahdr, w->aux[1].d_arslot, w->aux[1].d_arec, w->aux[1].d_aprec,
+                    w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : w->ev) (void)hipEventDestroy(e);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -512,8 +522,7 @@ static hipError_t upload_arrow_aux(loc_window* w, int which, int64_t n, hipStrea
 // edges form a forest.  Builds the elimination schedule tree_lm_kernel walks: nodes in post-order (children before their parent,
 // a node's children heavy subtree first so that the leaves of one parent are consecutive), per node its parent and its edges.
 // Layout of the int table: node[nv] par[nv] r_off[nv+1] r_list[nr] p_off[nv+1] p_list[np] s_off[nv+1] s_list[ns] r_idx[2 nr] s_idx[4 ns].
-static bool build_tree_sched(loc_window* w, int which, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* p_idx, const int32_t* s_idx) {
-    loc_window::WinAux& A = w->aux[which];
+static bool build_tree_sched(loc_window* w, loc_window::WinAux& A, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* p_idx, const int32_t* s_idx) {
     const locamd::WindowCaps& c = w->caps;
     const int nv = counts[0], nr = counts[1], np = counts[2], ns = counts[3];
     if (nv < 2 || nv > 64 || w->has_off1) return false;
@@ -664,8 +673,8 @@ static bool build_tree_sched(loc_window* w, int which, int64_t n, const int32_t*
     A.tsched.nv = nv; A.tsched.nr = nr; A.tsched.np = np; A.tsched.ns = ns; A.tsched.depth = maxdepth + 1; A.tsched.nroots = nroots;
     return true;
 }
-static hipError_t upload_tree_sched(loc_window* w, int which, hipStream_t st) {
-    loc_window::WinAux& A = w->aux[which];
+// solve: the schedule is for a solve kernel (tree_lm_kernel's workspace is allocated); the covariance pass needs the tables alone
+static hipError_t upload_tree_sched(loc_window* w, loc_window::WinAux& A, hipStream_t st, bool solve = true) {
     hipError_t e;
     if (A.tsched_cap < A.h_tsched.size()) {
         if (A.d_tsched) (void)hipFree(A.d_tsched);
@@ -673,7 +682,7 @@ static hipError_t upload_tree_sched(loc_window* w, int which, hipStream_t st) {
         if ((e = hipMalloc((void**)&A.d_tsched, A.h_tsched.size() * sizeof(int32_t))) != hipSuccess) return e;
         A.tsched_cap = A.h_tsched.size();
     }
-    if (!w->d_tree_ws && (e = hipMalloc((void**)&w->d_tree_ws, locamd::window_tree_workspace_doubles(w->caps, w->B) * sizeof(double))) != hipSuccess) return e;
+    if (solve && !w->d_tree_ws && (e = hipMalloc((void**)&w->d_tree_ws, locamd::window_tree_workspace_doubles(w->caps, w->B) * sizeof(double))) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(A.d_tsched, A.h_tsched.data(), A.h_tsched.size() * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     locamd::TreeSched& ts = A.tsched;
@@ -826,7 +835,7 @@ static int batch_topology(loc_window* w, int which, int64_t n, const int32_t* co
             if (hit && tc.tree_tried) {
                 if (tc.tree_ok) return LOC_WINDOW_KERNEL_TREE;   // (aux[0]'s schedule is still the one built for this structure)
             } else {
-                const bool ok = build_tree_sched(w, which, n, counts, r_idx, p_idx, s_idx);
+                const bool ok = build_tree_sched(w, w->aux[which], n, counts, r_idx, p_idx, s_idx);
                 if (use_cache) { tc.tree_tried = true; tc.tree_ok = ok; }
                 if (ok) return LOC_WINDOW_KERNEL_TREE;
             }
@@ -875,13 +884,31 @@ static int pick_kernel(const loc_window* w, int64_t n, int topology) {
 }
 // The block size the covariance pass computes a batch with (covariance_kernel.hip): 3 for translation-only batches, 6 otherwise; 0 = not
 // covered (LOC_ERR_UNSUPPORTED): a window that is not a chain (in any edge order), more than 64 poses, lever arms on endpoint 1.
-static int covariance_kind(const loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
-                           const int32_t* p_idx, const double* p_val, const int32_t* s_idx) {
-    if (w->has_off1 || w->caps.nv_max > 64 || locamd::window_covariance_lds_bytes(w->caps, false) > 160 * 1024) return 0;
+// Batches that are not chains: kCovForestOwn when the handle would solve the batch on a forest kernel (batch_topology's rule: option "tree",
+// tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `forest`, a table set of the
+// covariance's own that the caller then sends to the device (need_upload).  keyed (the host path): the set is kept with the hash of the
+// structure it was built for, and a batch of the same structure reuses it, device copy included.
+static int covariance_kind(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                           const int32_t* p_idx, const double* p_val, const int32_t* s_idx, loc_window::WinAux* forest, bool keyed, bool& need_upload) {
+    need_upload = false;
+    if (w->has_off1 || w->caps.nv_max > 64) return 0;
     bool chain = false, single_pairs = false, se3_pairs = false;
     chain_scan(w, n, counts, r_idx, p_idx, s_idx, false, chain, single_pairs, se3_pairs);
-    if (!chain) return 0;
-    return translation_only(w, n, counts, poses, r_val, p_val) ? 3 : 6;
+    if (chain) {
+        if (locamd::window_covariance_lds_bytes(w->caps, false) > 160 * 1024) return 0;
+        return translation_only(w, n, counts, poses, r_val, p_val) ? 3 : 6;
+    }
+    if (w->opt.tree == 0 || n < tree_min_batch(w)) return 0;
+    unsigned long long key = 0;
+    if (keyed) {
+        key = hash_structure(w, n, counts, r_idx, p_idx, s_idx);
+        if (w->cov_sched_valid && w->cov_sched_key == key && w->cov_sched_n == n) return kCovForestOwn;
+        w->cov_sched_valid = false;   // (valid again once the caller has uploaded the new tables)
+        w->cov_sched_key = key; w->cov_sched_n = n;
+    }
+    if (!build_tree_sched(w, *forest, n, counts, r_idx, p_idx, s_idx)) return 0;
+    need_upload = true;
+    return kCovForestOwn;
 }
 
 static hipError_t launch_any(loc_window* w, int which, const locamd::WindowArgs& a, hipStream_t st, int kind) {
@@ -1051,7 +1078,7 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
             const bool events = w->opt.kernel_events || !zero_copy;
             if (events) LOC_HIP(hipEventRecord(w->ev0, st));
             if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, 0, n, st));
-            if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, 0, st));
+            if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->aux[0], st));
             const auto t_launch = clk::now();
             hipError_t e = launch_any(w, 0, a, st, kind);
             if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
@@ -1099,7 +1126,7 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
     a.workspace = w->d_workspace;
     a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.caps = c;
     if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, 0, n, st));
-    if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, 0, st));
+    if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->aux[0], st));
     LOC_HIP(hipEventRecord(w->ev0, st));
     hipError_t e = launch_any(w, 0, a, st, kind);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
@@ -1148,7 +1175,7 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     }
     const int topology = batch_topology(w, 1, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx);
     if (topology == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, 1, n, w->stream));
-    if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, 1, w->stream));
+    if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->aux[1], w->stream));
     int max_anchor = 0;   // anchors referenced: v1 = -1 - anchor
     for (int64_t i = 0; i < n; ++i)
         for (int e = 0; e < counts[i * 4 + 1]; ++e) {
@@ -1161,7 +1188,13 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     // classified by the first loc_window_covariance_resident call (an upload costs nothing more for callers that never ask)
     if (topology == LOC_WINDOW_KERNEL_CHAIN3) w->resident_cov = 3;
     else if (topology == LOC_WINDOW_KERNEL_CHAIN || topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) w->resident_cov = 6;
-    else w->resident_cov = -1;
+    else if (topology == LOC_WINDOW_KERNEL_TREE) {
+        // a forest the solve kernels take: the covariance pass walks the schedule just built and uploaded (aux[1]) — unless the batch is
+        // a chain in some edge order, which the chain pass serves as before
+        bool chain = false, single_pairs = false, se3_pairs = false;
+        chain_scan(w, n, counts, r_idx, p_idx, s_idx, false, chain, single_pairs, se3_pairs);
+        w->resident_cov = chain ? -1 : kCovForest;
+    } else w->resident_cov = -1;
     w->resident_solved = false;
     w->n_resident = n;
     return LOC_OK;
@@ -1246,7 +1279,7 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
     return LOC_OK;
 }
 
-// ---- marginal covariances (covariance_kernel.hip) -------------------------------------------------------------------------------------
+// ---- marginal covariances (covariance_kernel.hip: chains; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
 int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
                                const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
                                int32_t* status) {
@@ -1255,10 +1288,16 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
         const int rc = validate_instances(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val);
         if (rc != LOC_OK) return rc;
     }
-    const int kind = covariance_kind(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx);
-    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host: every window must be a chain of <= 64 poses without endpoint-1 lever arms");
+    bool sched_upload = false;
+    const int kind = covariance_kind(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, &w->cov_aux[0], true, sched_upload);
+    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host: every window must be a chain of <= 64 poses, or the batch a forest of one shared "
+                                                       "topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold); no endpoint-1 lever arms");
     const locamd::WindowCaps& c = w->caps;
     LOC_HIP(hipSetDevice(w->device));
+    if (sched_upload) {
+        LOC_HIP(upload_tree_sched(w, w->cov_aux[0], w->stream, false));
+        w->cov_sched_valid = true;
+    }
     {
         const int rc = flush_anchors(w);
         if (rc != LOC_OK) return rc;
@@ -1301,7 +1340,8 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     a.r_off1 = nullptr; a.anchors = w->d_anchors; a.result = nullptr; a.workspace = nullptr;
     a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->natural_order; a.caps = c;
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = locamd::launch_window_covariance(a, kind == 3, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st);
+    hipError_t e = kind == kCovForestOwn ? locamd::launch_window_forest_covariance(a, w->cov_aux[0].tsched, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st)
+                                         : locamd::launch_window_covariance(a, kind == 3, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     if (small) {
@@ -1346,10 +1386,16 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
             LOC_HIP(hipMemcpy(pval.data(), w->d_pval, N * c.np_max * 18 * sizeof(double), hipMemcpyDeviceToHost));
         }
         if (c.ns_max) LOC_HIP(hipMemcpy(sidx.data(), w->d_sidx, N * c.ns_max * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
-        w->resident_cov = covariance_kind(w, (int64_t)N, counts.data(), poses.data(), ridx.data(), rval.data(), pidx.data(), pval.data(), sidx.data());
+        bool sched_upload = false;
+        const int kind = covariance_kind(w, (int64_t)N, counts.data(), poses.data(), ridx.data(), rval.data(), pidx.data(), pval.data(), sidx.data(), &w->cov_aux[1], false, sched_upload);
+        if (sched_upload) LOC_HIP(upload_tree_sched(w, w->cov_aux[1], w->stream, false));
+        w->resident_cov = kind;
     }
-    if (w->has_off1 || w->caps.nv_max > 64 || w->resident_cov <= 0)
-        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident: every window must be a chain of <= 64 poses without endpoint-1 lever arms");
+    // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
+    const bool forest = w->resident_cov == kCovForest || w->resident_cov == kCovForestOwn;
+    if (w->has_off1 || w->caps.nv_max > 64 || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)))
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident: every window must be a chain of <= 64 poses, or the batch a forest of one shared "
+                                                "topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold); no endpoint-1 lever arms");
     {
         const int rc = flush_anchors(w);
         if (rc != LOC_OK) return rc;
@@ -1362,7 +1408,8 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     a.workspace = nullptr; a.n_anchors = w->n_anchors; a.B = (int)w->n_resident; a.iterations = w->iterations; a.jacobian = w->jacobian;
     a.natural_order = w->natural_order; a.caps = w->caps;
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = locamd::launch_window_covariance(a, w->resident_cov == 3, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
+    hipError_t e = forest ? locamd::launch_window_forest_covariance(a, (w->resident_cov == kCovForest ? w->aux[1] : w->cov_aux[1]).tsched, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st)
+                          : locamd::launch_window_covariance(a, w->resident_cov == 3, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     // whatever overwrites the resident arrays next waits for this launch as well

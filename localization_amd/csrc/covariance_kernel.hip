@@ -21,11 +21,7 @@
 //     lane factors S_i (Cholesky, pivots checked) in its registers and keeps entry (r, c) of S_i^-1 = L^-T L^-1;
 //   * selected inversion, backwards: Sigma_{n-1} = S_{n-1}^-1, Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (lane = entry).
 // D = 3 for translation-only batches (capi_window.cpp: translation_only — 3x3 blocks, the rotation bits always set), D = 6 otherwise.
-#include "se3_edge_device.h"
-#include "cov_device.h"
-
-#include <float.h>
-#include <math.h>
+#include "cov_block_device.h"
 
 #include <atomic>
 
@@ -34,9 +30,6 @@ namespace locamd {
 namespace {
 
 extern __shared__ double cvlds[];
-
-constexpr int kCovChunk = 64;   // edges linearised per pass (one per lane)
-constexpr int kCovSRec = 21 + 21 + 36;   // EdgeSE3 record: H_ii, H_jj (lower triangles), the coupling block (rows: the later pose, column-major)
 
 // LDS layout of one window (offsets in doubles; the int tables follow the doubles)
 struct CovLayout {
@@ -62,85 +55,6 @@ __host__ __device__ inline CovLayout cov_layout(int nvl, int D, bool priors, boo
     l.mk = q; q += nvl;
     l.bytes = (size_t)p * sizeof(double) + (size_t)q * sizeof(int);
     return l;
-}
-
-#define CV_TRI(r, c) ((r) >= (c) ? (r) * ((r) + 1) / 2 + (c) : (c) * ((c) + 1) / 2 + (r))
-
-// one unary EdgeSE3Prior at X: its J^T W J (lower triangle, 21) — window_kernel.hip: evaluate_edges, unary priors
-__device__ __forceinline__ void cov_prior_block(const double* val, const double* X, double* rec) {
-    double RE[9], tE[3], q[4];
-    mat_mul(val, X, RE);
-    mat_vec(val, X + 9, tE);
-    mat_to_quat(RE, q);
-    quat_normalize_sign(q);
-    double J[36];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) J[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
-    quat_right_jac(q, 1.0, J, 6);
-    const double* W = val + 12;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int cc = 0; cc <= r; ++cc) {
-            double h = 0.0;
-            if ((r < 3) == (cc < 3)) {
-#pragma unroll
-                for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) h += J[i * 6 + r] * W[i] * J[i * 6 + cc];
-            }
-            rec[r * (r + 1) / 2 + cc] = h;
-        }
-}
-
-// one range edge (no lever arm on endpoint 1): rho' info, J0 (D columns of the pose carrying the lever arm), J1 (D columns of the other pose)
-template <int D, int JAC>
-__device__ __forceinline__ void cov_range_rec(const double* X0, const double* X1, const double* p1, bool pose1, const double* val, double* rec) {
-    const double meas = val[0], info = val[1];
-    const double off[3] = {val[2], val[3], val[4]};
-    double J0[6] = {0, 0, 0, 0, 0, 0}, J1[6] = {0, 0, 0, 0, 0, 0};
-    double err;
-    if (JAC == 0) {
-        double p0[3];
-        mat_vec(X0, off, p0);
-        double u[3] = {(p0[0] + X0[9]) - p1[0], (p0[1] + X0[10]) - p1[1], (p0[2] + X0[11]) - p1[2]};
-        const double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        err = meas - n;
-        const double inv = n > 0.0 ? 1.0 / n : 0.0;   // coincident endpoints: J = 0 (what the central difference gives)
-        u[0] *= inv; u[1] *= inv; u[2] *= inv;
-        double uR[3];
-        mat_tvec(X0, u, uR);
-        J0[0] = -uR[0]; J0[1] = -uR[1]; J0[2] = -uR[2];
-        J0[3] = 2.0 * (uR[1] * off[2] - uR[2] * off[1]);   // dp0/dv = -2 R0 [o]x  =>  de/dv0 = 2 (uR x o)
-        J0[4] = 2.0 * (uR[2] * off[0] - uR[0] * off[2]);
-        J0[5] = 2.0 * (uR[0] * off[1] - uR[1] * off[0]);
-        if (pose1) {
-            double uR1[3];
-            mat_tvec(X1, u, uR1);
-            J1[0] = uR1[0]; J1[1] = uR1[1]; J1[2] = uR1[2];
-        }
-    } else {
-        err = range_error_plain(X0, X0 + 9, off, p1, meas);
-        J0[0] = range_jac_numeric<0>(X0, off, X1, p1, 0, meas);
-        J0[1] = range_jac_numeric<1>(X0, off, X1, p1, 0, meas);
-        J0[2] = range_jac_numeric<2>(X0, off, X1, p1, 0, meas);
-        if (D == 6) {
-            J0[3] = range_jac_numeric<3>(X0, off, X1, p1, 0, meas);
-            J0[4] = range_jac_numeric<4>(X0, off, X1, p1, 0, meas);
-            J0[5] = range_jac_numeric<5>(X0, off, X1, p1, 0, meas);
-        }
-        if (pose1) {   // (without a lever arm, rotating endpoint 1 does not move its point: those columns are exactly 0)
-            J1[0] = range_jac_numeric<0>(X0, off, X1, p1, 1, meas);
-            J1[1] = range_jac_numeric<1>(X0, off, X1, p1, 1, meas);
-            J1[2] = range_jac_numeric<2>(X0, off, X1, p1, 1, meas);
-        }
-    }
-    const double chi = err * (info * err);
-    rec[0] = (1.0 / (1.0 + chi)) * info;   // rho' Omega
-#pragma unroll
-    for (int k = 0; k < D; ++k) { rec[1 + k] = J0[k]; rec[1 + D + k] = J1[k]; }
 }
 
 template <int D, int JAC>
@@ -216,7 +130,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
         __syncthreads();
         if (ent) {
             const int m = min(kCovChunk, np - e0);
-            for (int k = 0; k < m; ++k) Hd[pi[k] * DD + lane] += prec[k * 21 + CV_TRI(r, c)];
+            for (int k = 0; k < m; ++k) Hd[pi[k] * DD + lane] += prec[k * 21 + LOCAMD_CV_TRI(r, c)];
         }
     }
     if (D == 6) {
@@ -239,8 +153,8 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
                 for (int k = 0; k < m; ++k) {
                     const double* q = srec + k * kCovSRec;
                     const int vi = si[2 * k], vj = si[2 * k + 1];
-                    Hd[vi * DD + lane] += q[CV_TRI(r, c)];
-                    Hd[vj * DD + lane] += q[21 + CV_TRI(r, c)];
+                    Hd[vi * DD + lane] += q[LOCAMD_CV_TRI(r, c)];
+                    Hd[vj * DD + lane] += q[21 + LOCAMD_CV_TRI(r, c)];
                     Ho[min(vi, vj) * DD + lane] += q[42 + 6 * c + r];
                 }
             }
@@ -248,15 +162,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
     }
     __syncthreads();
     // ---- excluded coordinates: a diagonal entry exactly 0 (its row and column are 0 as well) ---------------------------------------------
-    if (lane < nv) {
-        int bits = D == 3 ? 0x38 : 0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            if (Hd[lane * DD + k * D + k] == 0.0) { bits |= 1 << k; Hd[lane * DD + k * D + k] = 1.0; }
-            dg[lane * D + k] = Hd[lane * DD + k * D + k];
-        }
-        mk[lane] = bits;
-    }
+    if (lane < nv) mk[lane] = cov_exclude_zero_diagonal<D>(Hd + lane * DD, dg + lane * D);
     __syncthreads();
 
     // ---- forward: S_i, its Cholesky factor, S_i^-1, K_i ------------------------------------------------------------------------------
@@ -358,7 +264,6 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
     for (int v = lane; v < nvm; v += 64) mask[(size_t)inst * nvm + v] = v < nv ? mk[v] : 0;
     if (lane == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
 }
-#undef CV_TRI
 
 template <int D, int JAC>
 hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {

@@ -110,6 +110,11 @@ struct TreeSched {
 size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3);
 hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
 
+// the same for forest windows of ONE shared topology of <= 64 poses (forest_covariance_kernel.hip): one wave per window on the solve
+// kernels' elimination schedule, always 6x6 blocks
+size_t window_forest_covariance_lds_bytes(const TreeSched& ts);
+hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);
