@@ -315,7 +315,7 @@ void* loc_window_poses_device(loc_window* w);   /* double [B][nv_max][12] */
 void* loc_window_result_device(loc_window* w);  /* double [B][8] */
 int loc_window_timing_begin(loc_window* w, int32_t max_launches);
 int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, double* avg_ms);
-/* Marginal pose covariances of CHAIN windows and of FOREST batches: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
+/* Marginal pose covariances of CHAIN windows and of ARROWHEAD and FOREST batches: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
  * (rho'_e = 1 / (1 + chi2_e) on every range edge and on every EdgeSE3 whose robust flag is set — g2o's robustInformation without rho''; priors
  * not robustified; range Jacobians in the handle's mode, loc_window_set_jacobian; no LM damping), in g2o VertexSE3's minimal coordinates
  * [dt (body frame), dq_xyz] applied as x * fromVectorMQT(d); Sigma_i = [H^-1]_ii.  Unlike g2o's computeMarginals (which re-factors the H of the
@@ -328,11 +328,17 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
  *   cov    double [n][nv_max][36]  row-major 6x6 per pose slot (slots >= nv: 0)
  *   mask   int32  [n][nv_max]      excluded coordinates, bits 0-5 = tx ty tz qx qy qz
  *   status int32  [n]              LOC_OK or LOC_ERR_SINGULAR (that window's blocks NaN)
- * Covered (nv_max <= 64, no endpoint-1 lever arms: the handle has none set, loc_window_set_endpoint1_offsets(w, 0, NULL)), LOC_ERR_UNSUPPORTED
- * with nothing written otherwise:
- *   - chains (checked first): every pose-to-pose edge of every window, range or EdgeSE3, joins consecutive slots (several per pair, a missing
+ * Covered (no endpoint-1 lever arms: the handle has none set, loc_window_set_endpoint1_offsets(w, 0, NULL)), LOC_ERR_UNSUPPORTED with nothing
+ * written otherwise; tested in this order:
+ *   - chains (nv_max <= 64): every pose-to-pose edge of every window, range or EdgeSE3, joins consecutive slots (several per pair, a missing
  *     link, any edge order);
- *   - forests, iff the handle would solve the batch on a forest kernel: option "tree" != 0, n at least the forest threshold (256 windows, or
+ *   - arrowheads (anchor self-calibration: a tag trajectory whose poses range to 1 .. 12 unknown nodes, the window's LAST pose slots), iff the
+ *     handle would solve the batch on arrow3_lm_kernel: option "arrow3" admits it (-1, the default: handles with nv_max > 64 only; 1: whenever
+ *     the batch qualifies; 0: never), the batch is translation-only (no EdgeSE3, identity rotations, zero lever arms, priors without rotation
+ *     information) and has that kernel's structure (at most one edge per pair of consecutive chain poses, every other pose-to-pose edge ends in
+ *     the border; its anchor, record and LDS limits).  Any nv_max that kernel takes.  3x3 blocks: every rotation bit is set.  The unknown
+ *     nodes' covariances are the blocks of their pose slots;
+ *   - forests (nv_max <= 64), iff the handle would solve the batch on a forest kernel: option "tree" != 0, n at least the forest threshold (256 windows, or
  *     the chain threshold where loc_window_set_chain_threshold lowered it: 1 serves a single window), every window the same counts and index
  *     tables, 2 <= nv <= 64, and the pose-to-pose edges form a forest (several edges per pair, either direction, several trees, isolated
  *     poses).  Always 6x6 blocks.  A tree that no range, prior or lever arm ties to the world is singular (LOC_ERR_SINGULAR for its window).

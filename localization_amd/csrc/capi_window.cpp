@@ -53,7 +53,7 @@ struct loc_window {
         int32_t *d_ahdr = nullptr, *d_arslot = nullptr;
         double *d_arec = nullptr, *d_aprec = nullptr;
         size_t arec_cap = 0, aprec_cap = 0;   // doubles allocated
-        int arrow_nb_max = 0, arrow_jmax = 0, arrow_jpmax = 0;
+        int arrow_nb_max = 0, arrow_jmax = 0, arrow_jpmax = 0, arrow_list_cap = 0;
         int arrow_jch[16] = {0}, arrow_jpch[16] = {0};   // records per chunk of 64 rows (the most any row of the chunk has, over the batch)
         std::vector<int32_t> h_ahdr, h_arslot;
         std::vector<double> h_arec, h_aprec;
@@ -106,17 +106,23 @@ struct loc_window {
     bool cov_pending = false;       // the events of a resident covariance launch have not been read yet
     double cov_ms = 0.0;
     int resident_cov = 0;           // 3 / 6: the resident chain batch's block size; kCovForest / kCovForestOwn: a forest batch on aux[1]'s /
-                                    // cov_aux[1]'s schedule; 0: not a covariance batch; -1: not classified yet
+                                    // cov_aux[1]'s schedule; kCovArrow: an arrowhead batch; 0: not a covariance batch; -1: not classified yet
     // forest batches (forest_covariance_kernel.hip): the schedules the covariance pass builds itself — [0] for loc_window_covariance_host
     // (kept with the hash of the structure it was built for), [1] for a resident batch no solve classified as a forest.  Never aux[0] /
     // aux[1]: the host path's topology cache and the resident solve rely on those.
+    // arrowhead batches (arrow_covariance_kernel.hip): cov_aux[.] takes build_arrow_aux's structure test (never aux[.]: the solve's packed
+    // tables stay as they are); the kernel's HBM workspace (records, B, Y, the poses' edge lists), one for the host path and one for the
+    // resident batch, allocated on first use and grown on demand
+    double* d_cov_ws[2] = {nullptr, nullptr};
+    size_t cov_ws_cap[2] = {0, 0};   // doubles
+    int cov_list_cap[2] = {0, 0};    // list size the batch was classified with
     WinAux cov_aux[2];
     bool cov_sched_valid = false;
     unsigned long long cov_sched_key = 0;
     int64_t cov_sched_n = 0;
 };
 static constexpr size_t kStageBytes = 4u << 20;
-static constexpr int kCovForest = 7, kCovForestOwn = 8;   // loc_window::resident_cov
+static constexpr int kCovForest = 7, kCovForestOwn = 8, kCovArrow = 9;   // loc_window::resident_cov
 
 // The host passes over a batch (validation, structure hash, chain / translation-only scans) are O(instances x edges) and run in front of a
 // kernel of a millisecond or two: batches of >= 4 096 instances are split over up to eight threads (f(lo, hi) on disjoint instance ranges).
@@ -156,7 +162,7 @@ int loc_window_destroy(loc_window* w) {
                     w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_tree_ws, w->d_arrow_ws,
                     w->aux[0].d_tsched, w->aux[0].d_ahdr, w->aux[0].d_arslot, w->aux[0].d_arec, w->aux[0].d_aprec,
                     w->aux[1].d_tsched, w->aux[1].d_ahdr, w->aux[1].d_arslot, w->aux[1].d_arec, w->aux[1].d_aprec,
-                    w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched};
+                    w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched, w->d_cov_ws[0], w->d_cov_ws[1]};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : w->ev) (void)hipEventDestroy(e);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -359,9 +365,10 @@ static bool translation_only(const loc_window* w, int64_t n, const int32_t* coun
 // rows (separators first, then the original border in slot order).  A chain row owns its edges to anchors, to border poses and
 // to the previous chain row; a border row those to lower-index border poses and to anchors.  Every row's edges (creation order)
 // and priors are packed as records [chunk of 64 rows][slot][lane].
-static bool build_arrow_aux(loc_window* w, int which, int64_t n, const int32_t* counts, const int32_t* r_idx, const double* r_val, const int32_t* p_idx,
-                            const double* p_val) {
-    loc_window::WinAux& A = w->aux[which];
+// A.arrow_list_cap: the most edges and priors any pose in front of the nb0 border slots has (arrow_covariance_kernel.hip's list size).
+// structure_only: the test alone, for the covariance pass — A is a table set of the covariance's own and nothing is packed.
+static bool build_arrow_aux(loc_window* w, loc_window::WinAux& A, int64_t n, const int32_t* counts, const int32_t* r_idx, const double* r_val, const int32_t* p_idx,
+                            const double* p_val, bool structure_only = false) {
     const locamd::WindowCaps& c = w->caps;
     const int NW = 4;
     const int nchunk = (c.nv_max + 63) / 64;
@@ -370,7 +377,7 @@ static bool build_arrow_aux(loc_window* w, int which, int64_t n, const int32_t* 
     std::vector<int32_t> cls, nedge, nprior, pairs;
     std::vector<int> seps;
     // pass 1: structure, record counts
-    int nb_max = 0, jmax = 1, jpmax = 1;
+    int nb_max = 0, jmax = 1, jpmax = 1, list_cap = 1;
     int jch[16], jpch[16];
     for (int k = 0; k < 16; ++k) { jch[k] = 1; jpch[k] = 1; }
     for (int64_t i = 0; i < n; ++i) {
@@ -432,9 +439,23 @@ static bool build_arrow_aux(loc_window* w, int which, int64_t n, const int32_t* 
             if (row / 64 < 16 && nprior[row] > jpch[row / 64]) jpch[row / 64] = nprior[row];
         }
         if (nb > nb_max) nb_max = nb;
+        {
+            std::vector<int32_t>& deg = nedge;   // (its row counts are not needed any more)
+            deg.assign((size_t)nv, 0);
+            for (int e = 0; e < nr; ++e) {
+                const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
+                if (structure_only && v1 == v0) return false;   // (pass 2's test: a range from a border pose to itself)
+                ++deg[v0];
+                if (v1 >= 0) ++deg[v1];
+            }
+            for (int e = 0; e < np; ++e) ++deg[pi[e]];
+            for (int v = 0; v < n0; ++v) if (deg[v] > list_cap) list_cap = deg[v];
+        }
     }
     if (jmax > 64 || jpmax > 16 || nb_max > 15) return false;
     if (locamd::window_arrow3_lds_bytes(c, nb_max) > 160 * 1024 - 512) return false;
+    A.arrow_list_cap = list_cap;
+    if (structure_only) return true;
     // pass 2: the records
     const size_t rec_per = (size_t)nchunk * jmax * 64 * 3, prec_per = (size_t)nchunk * jpmax * 64 * 7;
     A.h_arec.assign((size_t)n * rec_per, -1.0);
@@ -826,7 +847,7 @@ static int batch_topology(loc_window* w, int which, int64_t n, const int32_t* co
         // (option "arrow3": 0 = never, 1 = whenever the batch qualifies; default: windows of more than 64 poses — below that the
         //  wave-per-window kernel keeps everything in LDS and is the better choice)
         const bool want = w->opt.arrow3 >= 0 ? w->opt.arrow3 == 1 : c.nv_max > 64;
-        if (want && translation_only(w, n, counts, poses, r_val, p_val) && build_arrow_aux(w, which, n, counts, r_idx, r_val, p_idx, p_val)) return LOC_WINDOW_KERNEL_ARROW3;
+        if (want && translation_only(w, n, counts, poses, r_val, p_val) && build_arrow_aux(w, w->aux[which], n, counts, r_idx, r_val, p_idx, p_val)) return LOC_WINDOW_KERNEL_ARROW3;
     }
     {
         // (option "tree" = 0: never.  One wave per window, so any batch gains; the host-side comparison of the index tables is only worth
@@ -883,21 +904,35 @@ static int pick_kernel(const loc_window* w, int64_t n, int topology) {
     return topology;
 }
 // The block size the covariance pass computes a batch with (covariance_kernel.hip): 3 for translation-only batches, 6 otherwise; 0 = not
-// covered (LOC_ERR_UNSUPPORTED): a window that is not a chain (in any edge order), more than 64 poses, lever arms on endpoint 1.
-// Batches that are not chains: kCovForestOwn when the handle would solve the batch on a forest kernel (batch_topology's rule: option "tree",
-// tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `forest`, a table set of the
-// covariance's own that the caller then sends to the device (need_upload).  keyed (the host path): the set is kept with the hash of the
-// structure it was built for, and a batch of the same structure reuses it, device copy included.
+// covered (LOC_ERR_UNSUPPORTED): lever arms on endpoint 1, or a batch none of the three tests below takes.  In this order:
+// 1. windows of <= 64 poses that are chains (in any edge order): 3 / 6;
+// 2. kCovArrow when the handle would solve the batch on arrow3_lm_kernel (batch_topology's rule: option "arrow3" — by default windows of
+//    more than 64 poses only —, translation_only, build_arrow_aux's verdict) — arrow_covariance_kernel.hip; the structure test runs on `own`,
+//    a table set of the covariance's own, and the list size goes to w->cov_list_cap[keyed ? 0 : 1];
+// 3. windows of <= 64 poses: kCovForestOwn when the handle would solve the batch on a forest kernel (batch_topology's rule: option "tree",
+//    tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `own`, which the caller then sends
+//    to the device (need_upload).  keyed (the host path): the set is kept with the hash of the structure it was built for, and a batch of
+//    the same structure reuses it, device copy included.
+static bool arrow_covariance_wanted(const loc_window* w) { return !w->has_off1 && (w->opt.arrow3 >= 0 ? w->opt.arrow3 == 1 : w->caps.nv_max > 64); }
 static int covariance_kind(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
-                           const int32_t* p_idx, const double* p_val, const int32_t* s_idx, loc_window::WinAux* forest, bool keyed, bool& need_upload) {
+                           const int32_t* p_idx, const double* p_val, const int32_t* s_idx, loc_window::WinAux* own, bool keyed, bool& need_upload) {
     need_upload = false;
-    if (w->has_off1 || w->caps.nv_max > 64) return 0;
-    bool chain = false, single_pairs = false, se3_pairs = false;
-    chain_scan(w, n, counts, r_idx, p_idx, s_idx, false, chain, single_pairs, se3_pairs);
-    if (chain) {
-        if (locamd::window_covariance_lds_bytes(w->caps, false) > 160 * 1024) return 0;
-        return translation_only(w, n, counts, poses, r_val, p_val) ? 3 : 6;
+    if (w->has_off1) return 0;
+    const bool small = w->caps.nv_max <= 64;
+    if (small) {
+        bool chain = false, single_pairs = false, se3_pairs = false;
+        chain_scan(w, n, counts, r_idx, p_idx, s_idx, false, chain, single_pairs, se3_pairs);
+        if (chain) {
+            if (locamd::window_covariance_lds_bytes(w->caps, false) > 160 * 1024) return 0;
+            return translation_only(w, n, counts, poses, r_val, p_val) ? 3 : 6;
+        }
     }
+    if (arrow_covariance_wanted(w) && locamd::window_arrow_covariance_lds_bytes(w->caps) <= 160 * 1024 && translation_only(w, n, counts, poses, r_val, p_val) &&
+        build_arrow_aux(w, *own, n, counts, r_idx, r_val, p_idx, p_val, true)) {
+        w->cov_list_cap[keyed ? 0 : 1] = own->arrow_list_cap;
+        return kCovArrow;
+    }
+    if (!small) return 0;
     if (w->opt.tree == 0 || n < tree_min_batch(w)) return 0;
     unsigned long long key = 0;
     if (keyed) {
@@ -906,9 +941,19 @@ static int covariance_kind(loc_window* w, int64_t n, const int32_t* counts, cons
         w->cov_sched_valid = false;   // (valid again once the caller has uploaded the new tables)
         w->cov_sched_key = key; w->cov_sched_n = n;
     }
-    if (!build_tree_sched(w, *forest, n, counts, r_idx, p_idx, s_idx)) return 0;
+    if (!build_tree_sched(w, *own, n, counts, r_idx, p_idx, s_idx)) return 0;
     need_upload = true;
     return kCovForestOwn;
+}
+// the arrowhead pass's workspace for n windows with lists of `cap` entries (which: 0 the host path's, 1 the resident batch's)
+static hipError_t grow_cov_workspace(loc_window* w, int which, int64_t n, int cap) {
+    const size_t need = (size_t)n * locamd::window_arrow_covariance_workspace_doubles(w->caps, cap);
+    if (w->cov_ws_cap[which] >= need) return hipSuccess;
+    if (w->d_cov_ws[which]) (void)hipFree(w->d_cov_ws[which]);
+    w->d_cov_ws[which] = nullptr; w->cov_ws_cap[which] = 0;
+    hipError_t e = hipMalloc((void**)&w->d_cov_ws[which], need * sizeof(double));
+    if (e == hipSuccess) w->cov_ws_cap[which] = need;
+    return e;
 }
 
 static hipError_t launch_any(loc_window* w, int which, const locamd::WindowArgs& a, hipStream_t st, int kind) {
@@ -1194,6 +1239,9 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
         bool chain = false, single_pairs = false, se3_pairs = false;
         chain_scan(w, n, counts, r_idx, p_idx, s_idx, false, chain, single_pairs, se3_pairs);
         w->resident_cov = chain ? -1 : kCovForest;
+    } else if (topology == LOC_WINDOW_KERNEL_ARROW3) {   // (never a chain: build_arrow_aux wants a border)
+        w->resident_cov = kCovArrow;
+        w->cov_list_cap[1] = w->aux[1].arrow_list_cap;
     } else w->resident_cov = -1;
     w->resident_solved = false;
     w->n_resident = n;
@@ -1279,7 +1327,7 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
     return LOC_OK;
 }
 
-// ---- marginal covariances (covariance_kernel.hip: chains; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
+// ---- marginal covariances (covariance_kernel.hip: chains; arrow_covariance_kernel.hip: arrowheads; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
 int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
                                const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
                                int32_t* status) {
@@ -1290,10 +1338,12 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     }
     bool sched_upload = false;
     const int kind = covariance_kind(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, &w->cov_aux[0], true, sched_upload);
-    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host: every window must be a chain of <= 64 poses, or the batch a forest of one shared "
-                                                       "topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold); no endpoint-1 lever arms");
+    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host: every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle "
+                                                       "solves on arrow3_lm_kernel (option arrow3), or a forest of one shared topology of <= 64 poses that the handle solves on "
+                                                       "a forest kernel (option tree, batch threshold); no endpoint-1 lever arms");
     const locamd::WindowCaps& c = w->caps;
     LOC_HIP(hipSetDevice(w->device));
+    if (kind == kCovArrow) LOC_HIP(grow_cov_workspace(w, 0, n, w->cov_list_cap[0]));
     if (sched_upload) {
         LOC_HIP(upload_tree_sched(w, w->cov_aux[0], w->stream, false));
         w->cov_sched_valid = true;
@@ -1340,7 +1390,8 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     a.r_off1 = nullptr; a.anchors = w->d_anchors; a.result = nullptr; a.workspace = nullptr;
     a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->natural_order; a.caps = c;
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = kind == kCovForestOwn ? locamd::launch_window_forest_covariance(a, w->cov_aux[0].tsched, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st)
+    hipError_t e = kind == kCovArrow ? locamd::launch_window_arrow_covariance(a, w->d_cov_ws[0], w->cov_list_cap[0], (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st)
+                 : kind == kCovForestOwn ? locamd::launch_window_forest_covariance(a, w->cov_aux[0].tsched, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st)
                                          : locamd::launch_window_covariance(a, kind == 3, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
@@ -1368,7 +1419,7 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
     if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
     LOC_HIP(hipSetDevice(w->device));
-    if (w->resident_cov < 0 && !w->has_off1 && w->caps.nv_max <= 64) {
+    if (w->resident_cov < 0 && !w->has_off1) {
         // first call on an upload no solve kernel classified as a chain: the uploaded tables come back once and are scanned on the host
         if (int rc = wait_resident(w)) return rc;
         const locamd::WindowCaps& c = w->caps;
@@ -1392,10 +1443,18 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
         w->resident_cov = kind;
     }
     // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
+    // (an arrowhead batch likewise while option "arrow3" still admits it)
     const bool forest = w->resident_cov == kCovForest || w->resident_cov == kCovForestOwn;
-    if (w->has_off1 || w->caps.nv_max > 64 || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)))
-        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident: every window must be a chain of <= 64 poses, or the batch a forest of one shared "
-                                                "topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold); no endpoint-1 lever arms");
+    const bool arrow = w->resident_cov == kCovArrow;
+    if (w->has_off1 || (w->caps.nv_max > 64 && !arrow) || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)) ||
+        (arrow && (!arrow_covariance_wanted(w) || locamd::window_arrow_covariance_lds_bytes(w->caps) > 160 * 1024)))
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident: every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle solves on "
+                                                "arrow3_lm_kernel (option arrow3), or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel "
+                                                "(option tree, batch threshold); no endpoint-1 lever arms");
+    if (arrow && w->cov_ws_cap[1] < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, w->cov_list_cap[1])) {
+        if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
+        LOC_HIP(grow_cov_workspace(w, 1, w->n_resident, w->cov_list_cap[1]));
+    }
     {
         const int rc = flush_anchors(w);
         if (rc != LOC_OK) return rc;
@@ -1408,7 +1467,8 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     a.workspace = nullptr; a.n_anchors = w->n_anchors; a.B = (int)w->n_resident; a.iterations = w->iterations; a.jacobian = w->jacobian;
     a.natural_order = w->natural_order; a.caps = w->caps;
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = forest ? locamd::launch_window_forest_covariance(a, (w->resident_cov == kCovForest ? w->aux[1] : w->cov_aux[1]).tsched, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st)
+    hipError_t e = arrow ? locamd::launch_window_arrow_covariance(a, w->d_cov_ws[1], w->cov_list_cap[1], (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st)
+                 : forest ? locamd::launch_window_forest_covariance(a, (w->resident_cov == kCovForest ? w->aux[1] : w->cov_aux[1]).tsched, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st)
                           : locamd::launch_window_covariance(a, w->resident_cov == 3, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));

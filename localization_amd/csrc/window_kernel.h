@@ -115,6 +115,13 @@ hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, i
 size_t window_forest_covariance_lds_bytes(const TreeSched& ts);
 hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
 
+// the same for translation-only arrowhead windows (arrow_covariance_kernel.hip: the windows arrow3_lm_kernel solves; border = the last slots
+// by build_arrow_aux's rule, recomputed on the device), one workgroup per window, 3x3 blocks.  ws: [B][window_arrow_covariance_workspace_doubles]
+// in HBM (edge records, B, Y = A^-1 B and a list of `cap` edges per pose); cap: the most edges and priors any pose in front of the border has
+size_t window_arrow_covariance_lds_bytes(const WindowCaps& c);
+size_t window_arrow_covariance_workspace_doubles(const WindowCaps& c, int cap);
+hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

@@ -143,8 +143,10 @@ class WindowSolver:
 
     # ---- marginal pose covariances at the given (solved) estimates (loc_window_covariance_*)
     def covariance(self, wb: WindowBatch, out=None):
-        """Sigma_i = [H^-1]_ii of every pose of every window at wb.poses: chain windows of <= 64 poses, and forest batches (one shared topology,
-        <= 64 poses) whenever the handle would solve them on a forest kernel (option "tree", batch threshold).  Returns (cov [B][nv_max][6][6],
+        """Sigma_i = [H^-1]_ii of every pose of every window at wb.poses: chain windows of <= 64 poses, arrowhead batches (anchor
+        self-calibration; the unknown anchors are the last pose slots) whenever the handle would solve them on arrow3_lm_kernel (option
+        "arrow3"; by default handles of more than 64 poses), and forest batches (one shared topology, <= 64 poses) whenever the handle
+        would solve them on a forest kernel (option "tree", batch threshold).  Returns (cov [B][nv_max][6][6],
         mask [B][nv_max] — excluded coordinates, bits 0-5 = tx ty tz qx qy qz —, status [B]: 0 or LOC_ERR_SINGULAR, that window's blocks NaN)."""
         assert wb.caps == self.caps and wb.B <= self.B
         if getattr(wb, "r_off1", None) is not None:   # (refused here: the handle's endpoint-1 lever arms belong to its solves and stay as they are)
