@@ -52,7 +52,6 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <atomic>
 
 namespace locamd {
 
@@ -1016,16 +1015,8 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
 
 template <int JAC, int NTI>
 hipError_t launch_arrow3_t(const WindowArgs& a, const ArrowAux& x, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&arrow3_lm_kernel<JAC, NTI>>(160 * 1024 - 512);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&arrow3_lm_kernel<JAC, NTI>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((arrow3_lm_kernel<JAC, NTI>), dim3((unsigned)a.B), dim3(64 * ARROW_NW), lds, stream, a, x);
     return hipGetLastError();
 }

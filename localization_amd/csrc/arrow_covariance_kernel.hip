@@ -8,14 +8,17 @@
 // r_idx); chain = the nc = nv - nb slots before it, one segment, no separators.  With
 //   H = [ A  B ; B^T  C ],   A block-tridiagonal (nc blocks), B dense 3 nc x 3 nb, C dense 3 nb x 3 nb (3 nb <= 36),
 //   Y = A^-1 B,   S = C - B^T Y:   [H^-1]_border = S^-1,   [H^-1]_ii = [A^-1]_ii + Y_i S^-1 Y_i^T  (chain pose i).
-// The pivot test (cov_device.h: kCovRelPivot of the coordinate's diagonal entry of H) covers A's block pivots and S's Cholesky pivots.
+// The pivot test (cov_block_device.h: cov_pivot_above_noise, kCovRelPivot of the coordinate's diagonal entry of H) covers A's block pivots
+// (step 3) and S's Cholesky pivots (step 5).
 //
 // Schedule (no atomics; every sum is taken in edge order by the one thread that owns its entry: the same bits on every run):
 //   1. linearise, lane = edge, chunks of 256: the record (rho' info, J0, J1) goes to LDS and to the window's HBM workspace.  Of every
 //      chunk the border threads (lane = entry (r, c) of border slot b) add their shares of C from LDS, and the pose threads
 //      (lane = chain pose) note which edges touch their pose (a list per pose in the workspace, `cap` entries each);
 //   2. assemble, lane = chain pose: the pose's list gives H_ii, H_{i+1,i} (LDS) and the pose's rows of B (workspace, [chain row][36]);
-//   3. factor A, one lane: S_0 = H_00, K_i = H_{i+1,i} S_i^-1, S_{i+1} = H_{i+1,i+1} - K_i H_{i,i+1} (covariance_kernel.hip's recurrence);
+//   3. factor A, one lane: S_0 = H_00, K_i = H_{i+1,i} S_i^-1, S_{i+1} = H_{i+1,i+1} - K_i H_{i,i+1} (covariance_kernel.hip's recurrence).  The
+//      3 x 3 Cholesky and L^-1 are cov_chol_inverse's loops written out: called through that function (and with cov_range_edge for the
+//      fetch of step 1) the pass measured 1 % slower than before, more than its run-to-run spread;
 //   4. solve A Y = B, lane = border column: forward w_i = S_i^-1 (b_i - K_{i-1} z_{i-1}), backward y_i = w_i - K_i^T y_{i+1}; the backward
 //      sweep also sums the lane's column of B^T Y in registers.  A lane of another wave meanwhile runs the chain pass's selected
 //      inversion Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i for [A^-1]_ii;
@@ -23,8 +26,6 @@
 //   6. chain marginals, lane = chain pose; 7. the store (cov_store_window's rules).
 #include "cov_block_device.h"
 #include "window_kernel.h"
-
-#include <atomic>
 
 namespace locamd {
 
@@ -273,7 +274,7 @@ __global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const Wind
             double g[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                ok = ok && A[j][j] > kCovRelPivot * dg[i * 3 + j];
+                ok = ok && cov_pivot_above_noise(A[j][j], dg[i * 3 + j]);
                 g[j] = pivot_rsqrt(A[j][j]);
 #pragma unroll
                 for (int i2 = j + 1; i2 < 3; ++i2) A[i2][j] *= g[j];
@@ -445,7 +446,7 @@ __global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const Wind
         }
         if (tid == j) {
             const double g = pivot_rsqrt(s);
-            if (!(s > kCovRelPivot * dg[nc * 3 + j]) || !(g < DBL_MAX)) flag[1] = 0;
+            if (!cov_pivot_above_noise(s, dg[nc * 3 + j]) || !(g < DBL_MAX)) flag[1] = 0;
             ig[j] = g;
             C[j * BS + j] = s * g;
         }
@@ -518,16 +519,8 @@ __global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const Wind
 
 template <int JAC>
 hipError_t launch_arrow_cov_t(const WindowArgs& a, double* ws, int cap, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&arrow_covariance_kernel<JAC>>(160 * 1024);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&arrow_covariance_kernel<JAC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((arrow_covariance_kernel<JAC>), dim3((unsigned)a.B), dim3(kAcThreads), lds, stream, a, ws, cap, cov, mask, status);
     return hipGetLastError();
 }

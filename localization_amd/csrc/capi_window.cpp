@@ -1328,6 +1328,17 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
 }
 
 // ---- marginal covariances (covariance_kernel.hip: chains; arrow_covariance_kernel.hip: arrowheads; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
+#define LOC_COV_UNSUPPORTED ": every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle solves on arrow3_lm_kernel (option arrow3), " \
+                            "or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold); no endpoint-1 lever arms"
+
+// the pass of a batch of covariance_kind's `kind`; which: 0 = loc_window_covariance_host's table set and workspace, 1 = the resident batch's
+// (a forest that loc_window_upload classified, kCovForest, walks the solve's schedule aux[1]; kCovForestOwn the covariance's own)
+static hipError_t launch_covariance(loc_window* w, int which, int kind, const locamd::WindowArgs& a, double* cov, int32_t* mask, int32_t* status, hipStream_t st) {
+    if (kind == kCovArrow) return locamd::launch_window_arrow_covariance(a, w->d_cov_ws[which], w->cov_list_cap[which], cov, mask, status, st);
+    if (kind == kCovForest) return locamd::launch_window_forest_covariance(a, w->aux[1].tsched, cov, mask, status, st);
+    if (kind == kCovForestOwn) return locamd::launch_window_forest_covariance(a, w->cov_aux[which].tsched, cov, mask, status, st);
+    return locamd::launch_window_covariance(a, kind == 3, cov, mask, status, st);
+}
 int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
                                const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
                                int32_t* status) {
@@ -1338,9 +1349,7 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     }
     bool sched_upload = false;
     const int kind = covariance_kind(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, &w->cov_aux[0], true, sched_upload);
-    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host: every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle "
-                                                       "solves on arrow3_lm_kernel (option arrow3), or a forest of one shared topology of <= 64 poses that the handle solves on "
-                                                       "a forest kernel (option tree, batch threshold); no endpoint-1 lever arms");
+    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host" LOC_COV_UNSUPPORTED);
     const locamd::WindowCaps& c = w->caps;
     LOC_HIP(hipSetDevice(w->device));
     if (kind == kCovArrow) LOC_HIP(grow_cov_workspace(w, 0, n, w->cov_list_cap[0]));
@@ -1390,9 +1399,7 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     a.r_off1 = nullptr; a.anchors = w->d_anchors; a.result = nullptr; a.workspace = nullptr;
     a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->natural_order; a.caps = c;
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = kind == kCovArrow ? locamd::launch_window_arrow_covariance(a, w->d_cov_ws[0], w->cov_list_cap[0], (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st)
-                 : kind == kCovForestOwn ? locamd::launch_window_forest_covariance(a, w->cov_aux[0].tsched, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st)
-                                         : locamd::launch_window_covariance(a, kind == 3, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st);
+    const hipError_t e = launch_covariance(w, 0, kind, a, (double*)(d + off[0]), (int32_t*)(d + off[1]), (int32_t*)(d + off[2]), st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     if (small) {
@@ -1448,9 +1455,7 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     const bool arrow = w->resident_cov == kCovArrow;
     if (w->has_off1 || (w->caps.nv_max > 64 && !arrow) || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)) ||
         (arrow && (!arrow_covariance_wanted(w) || locamd::window_arrow_covariance_lds_bytes(w->caps) > 160 * 1024)))
-        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident: every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle solves on "
-                                                "arrow3_lm_kernel (option arrow3), or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel "
-                                                "(option tree, batch threshold); no endpoint-1 lever arms");
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
     if (arrow && w->cov_ws_cap[1] < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, w->cov_list_cap[1])) {
         if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
         LOC_HIP(grow_cov_workspace(w, 1, w->n_resident, w->cov_list_cap[1]));
@@ -1467,9 +1472,7 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     a.workspace = nullptr; a.n_anchors = w->n_anchors; a.B = (int)w->n_resident; a.iterations = w->iterations; a.jacobian = w->jacobian;
     a.natural_order = w->natural_order; a.caps = w->caps;
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = arrow ? locamd::launch_window_arrow_covariance(a, w->d_cov_ws[1], w->cov_list_cap[1], (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st)
-                 : forest ? locamd::launch_window_forest_covariance(a, (w->resident_cov == kCovForest ? w->aux[1] : w->cov_aux[1]).tsched, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st)
-                          : locamd::launch_window_covariance(a, w->resident_cov == 3, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
+    const hipError_t e = launch_covariance(w, 1, w->resident_cov, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     // whatever overwrites the resident arrays next waits for this launch as well

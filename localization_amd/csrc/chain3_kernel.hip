@@ -570,16 +570,8 @@ __global__ void __launch_bounds__(64, 1) chain3_lm_kernel(const WindowArgs a, do
 
 template <int JAC, bool LG, bool LT>
 hipError_t launch_chain3_t(const WindowArgs& a, double* ws, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&chain3_lm_kernel<JAC, LG, LT>>(160 * 1024 - 512);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain3_lm_kernel<JAC, LG, LT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     const unsigned blocks = (unsigned)((a.B + 63) / 64);
     hipLaunchKernelGGL((chain3_lm_kernel<JAC, LG, LT>), dim3(blocks), dim3(64), lds, stream, a, ws);
     return hipGetLastError();

@@ -1,7 +1,9 @@
-// What the wave-per-window covariance passes do alike (covariance_kernel.hip: chain windows; forest_covariance_kernel.hip: forest windows;
-// DESIGN.md §2 / §4): the per-edge records of the linearisation (range, unary prior, the EdgeSE3 record's layout) and the rule for
-// excluded coordinates.  (The block factorisation, the K^T Sigma K update and the store are NOT here: moved into functions they change
-// the chain kernel's code — DESIGN.md §4 — so each kernel keeps its own.)  Internal to the including translation unit.
+// What the window covariance passes do alike (covariance_kernel.hip: chain windows; forest_covariance_kernel.hip: forest windows;
+// arrow_covariance_kernel.hip: arrowhead windows): the per-edge records of the linearisation (range, unary prior, the
+// EdgeSE3 record's layout), the rule for excluded coordinates, the relative pivot rule behind LOC_ERR_SINGULAR (cov_pivot_above_noise:
+// all three passes), and the block steps of the two wave-per-window passes — the register Cholesky with its pivot tests and L^-1
+// (cov_chol_inverse), the elimination of one block, the K^T Sigma K update and the store; the chain is the forest with parent = next
+// pose.  (The arrowhead pass keeps its one-lane 3 x 3 loops: DESIGN.md §4.)  Internal to the including translation unit.
 #pragma once
 #include "se3_edge_device.h"
 #include "cov_device.h"
@@ -94,6 +96,20 @@ __device__ __forceinline__ void cov_range_rec(const double* X0, const double* X1
     for (int k = 0; k < D; ++k) { rec[1 + k] = J0[k]; rec[1 + D + k] = J1[k]; }
 }
 
+// one range edge (v0, v1) of a window with poses P: endpoint 1 is pose v1, or the fixed anchor -1 - v1 (identity rotation); the record of cov_range_rec
+template <int D, int JAC>
+__device__ __forceinline__ void cov_range_edge(const double* P, const double* anchors, int v0, int v1, const double* val, double* rec) {
+    double X0[12], X1[12], p1[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X0[k] = P[v0 * 12 + k];
+    const int v1c = v1 >= 0 ? v1 : v0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X1[k] = P[v1c * 12 + k];
+    if (v1 >= 0) { p1[0] = X1[9]; p1[1] = X1[10]; p1[2] = X1[11]; }
+    else { const double* an = anchors + (size_t)(-1 - v1) * 3; p1[0] = an[0]; p1[1] = an[1]; p1[2] = an[2]; }
+    cov_range_rec<D, JAC>(X0, X1, p1, v1 >= 0, val, rec);
+}
+
 // excluded coordinates of pose `v`'s assembled diagonal block: a diagonal entry exactly 0 (its row and column are 0 as well) is taken as
 // 1 and gets its mask bit; dgv: diag(H) of the pose's coordinates (the scale of the relative pivot test).  Returns the mask.
 template <int D>
@@ -105,6 +121,131 @@ __device__ __forceinline__ int cov_exclude_zero_diagonal(double* Hv, double* dgv
         dgv[k] = Hv[k * D + k];
     }
     return bits;
+}
+
+// ---- the block steps ------------------------------------------------------------------------------------------------------------------
+// the relative half of the pivot rule: a pivot at most kCovRelPivot of its coordinate's diagonal entry of H is numerically
+// singular (a rank-deficient H leaves pivots of rounding size, 1e-16 .. 1e-14 of it, and of either sign: the absolute test alone would pass
+// half of them); NaN fails as well
+__device__ __forceinline__ bool cov_pivot_above_noise(double pivot, double diag) { return pivot > kCovRelPivot * diag; }
+
+// Cholesky of one D x D block in the thread's registers, pivots checked, and the inverse of its factor.  A: the block (row-major, its lower
+// triangle is read); dgv: diag(H) of its coordinates; Li: L^-1 (its lower triangle is written).  ok: cleared by a pivot that is not finite,
+// not positive or not above the noise of its coordinate.  No LDS writes, no barriers.
+template <int D>
+__device__ __forceinline__ void cov_chol_inverse(const double* A_, const double* dgv, bool& ok, double (&Li)[D][D]) {
+    double A[D][D];
+#pragma unroll
+    for (int cc = 0; cc < D; ++cc)
+#pragma unroll
+        for (int rr = cc; rr < D; ++rr) A[rr][cc] = A_[rr * D + cc];
+    double ig[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        ok = ok && cov_pivot_above_noise(A[j][j], dgv[j]);
+        const double g = pivot_rsqrt(A[j][j]);
+        ig[j] = g;
+#pragma unroll
+        for (int i2 = j + 1; i2 < D; ++i2) A[i2][j] *= g;
+#pragma unroll
+        for (int i2 = j + 1; i2 < D; ++i2)
+#pragma unroll
+            for (int cc = j + 1; cc <= i2; ++cc) A[i2][cc] = __builtin_fma(-A[i2][j], A[cc][j], A[i2][cc]);
+    }
+    double sg = 0.0;
+#pragma unroll
+    for (int j = 0; j < D; ++j) sg += ig[j];
+    ok = ok && sg < DBL_MAX;   // (a pivot <= 0 or not finite: NaN / inf — window_kernel.hip's test)
+    // L^-1 (lower): diagonal ig, below it -ig_i sum_k L_ik Linv_kc
+#pragma unroll
+    for (int cc = 0; cc < D; ++cc) {
+        Li[cc][cc] = ig[cc];
+#pragma unroll
+        for (int rr = cc + 1; rr < D; ++rr) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = cc; k < rr; ++k) s = __builtin_fma(A[rr][k], Li[k][cc], s);
+            Li[rr][cc] = -ig[rr] * s;
+        }
+    }
+}
+
+// The wave-per-window passes, lane = entry (r, c) of a D x D block (ent: the lane has one).  Chain windows: parent = the next pose.
+// Eliminates node i (pose slot i of the window's LDS blocks: Hd = diagonal blocks, Ho = the blocks H_{parent,node} with the parent's rows, dg =
+// diag(H)): Hd[i] holds S_i, the node's diagonal block minus its children's shares.  Every lane factors S_i (cov_chol_inverse) in its
+// registers; S_i^-1 = L^-T L^-1 replaces S_i.  With a parent (slot ip): K_i = H_{ip,i} S_i^-1 replaces Ho[i] and Hd[ip] loses K_i H_{i,ip}.
+// Kb: one D x D exchange block.  ok: cleared by a failed pivot.
+template <int D>
+__device__ __forceinline__ void cov_eliminate_block(double* Hd, double* Ho, const double* dg, double* Kb, int i, bool has_parent, int ip, int lane, int r, int c, bool ent, bool& ok) {
+    constexpr int DD = D * D;
+    double Li[D][D];
+    cov_chol_inverse<D>(Hd + i * DD, dg + i * D, ok, Li);
+    double sinv = 0.0;   // entry (r, c) of S_i^-1 = L^-T L^-1
+    if (ent) {
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+            if (k >= r && k >= c) sinv = __builtin_fma(Li[k][r], Li[k][c], sinv);
+    }
+    __syncthreads();
+    if (ent) Hd[i * DD + lane] = sinv;
+    __syncthreads();
+    if (has_parent) {
+        double kr = 0.0;   // K_i = H_{ip,i} S_i^-1
+        if (ent) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) kr = __builtin_fma(Ho[i * DD + r * D + k], Hd[i * DD + k * D + c], kr);
+            Kb[lane] = kr;
+        }
+        __syncthreads();
+        double s = 0.0;    // (K_i H_{i,ip})_rc = sum_k K_rk H_{ip,i}[c][k]
+        if (ent) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) s = __builtin_fma(Kb[r * D + k], Ho[i * DD + c * D + k], s);
+        }
+        __syncthreads();
+        if (ent) { Ho[i * DD + lane] = kr; Hd[ip * DD + lane] -= s; }
+        __syncthreads();
+    }
+}
+
+// selected inversion, node i with parent ip: Sigma_i = S_i^-1 + K_i^T Sigma_ip K_i (Hd[i]: S_i^-1 in, Sigma_i out; Hd[ip]: the parent's finished
+// Sigma; Ho[i]: K_i)
+template <int D>
+__device__ __forceinline__ void cov_back_substitute_block(double* Hd, const double* Ho, double* Kb, int i, int ip, int lane, int r, int c, bool ent) {
+    constexpr int DD = D * D;
+    if (ent) {
+        double t = 0.0;   // T = Sigma_ip K_i
+#pragma unroll
+        for (int k = 0; k < D; ++k) t = __builtin_fma(Hd[ip * DD + r * D + k], Ho[i * DD + k * D + c], t);
+        Kb[lane] = t;
+    }
+    __syncthreads();
+    if (ent) {
+        double s = Hd[i * DD + lane];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s = __builtin_fma(Ho[i * DD + k * D + r], Kb[k * D + c], s);
+        Hd[i * DD + lane] = s;
+    }
+    __syncthreads();
+}
+
+// output of window `inst`: symmetric 6x6 per slot ((a + a^T) / 2), excluded rows / columns 0, slots >= nv 0, NaN for a singular window
+template <int D>
+__device__ __forceinline__ void cov_store_window(const double* Hd, const int* mk, int nv, int nvm, bool ok, int lane, long long inst, double* cov, int32_t* mask, int32_t* status) {
+    constexpr int DD = D * D;
+    double* out = cov + (size_t)inst * nvm * 36;
+    for (int k = lane; k < nvm * 36; k += 64) {
+        const int v = k / 36, rr = (k % 36) / 6, cc = k % 6;
+        double x = 0.0;
+        if (v < nv) {
+            if (!ok) x = __builtin_nan("");
+            else if (rr < D && cc < D && !((mk[v] >> rr) & 1) && !((mk[v] >> cc) & 1))
+                x = (Hd[v * DD + rr * D + cc] + Hd[v * DD + cc * D + rr]) * 0.5;
+        }
+        out[k] = x;
+    }
+    for (int v = lane; v < nvm; v += 64) mask[(size_t)inst * nvm + v] = v < nv ? mk[v] : 0;
+    if (lane == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
 }
 
 }  // namespace

@@ -18,12 +18,11 @@
 //   * assembly: lane = entry (r, c) of a D x D block, the records of a chunk added in edge order (no atomics: every entry is owned by one
 //     lane, so the result is the same bits on every run): H_ii and H_{i+1,i} in LDS (64 x 2 x 36 doubles = 36 KB for 64 poses);
 //   * block-tridiagonal factorisation, pose after pose: S_0 = H_00, K_i = H_{i+1,i} S_i^-1, S_{i+1} = H_{i+1,i+1} - K_i H_{i,i+1}; every
-//     lane factors S_i (Cholesky, pivots checked) in its registers and keeps entry (r, c) of S_i^-1 = L^-T L^-1;
-//   * selected inversion, backwards: Sigma_{n-1} = S_{n-1}^-1, Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (lane = entry).
+//     lane factors S_i (Cholesky, pivots checked) in its registers and keeps entry (r, c) of S_i^-1 = L^-T L^-1 (cov_eliminate_block);
+//   * selected inversion, backwards: Sigma_{n-1} = S_{n-1}^-1, Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (lane = entry; cov_back_substitute_block).
 // D = 3 for translation-only batches (capi_window.cpp: translation_only — 3x3 blocks, the rotation bits always set), D = 6 otherwise.
 #include "cov_block_device.h"
-
-#include <atomic>
+#include "window_kernel.h"
 
 namespace locamd {
 
@@ -92,6 +91,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
             const int32_t* ix = a.r_idx + ((size_t)inst * cp.nr_max + e) * 2;
             const double* val = a.r_val + ((size_t)inst * cp.nr_max + e) * 5;
             const int v0 = ix[0], v1 = ix[1];
+            // (cov_range_edge's fetch, written out: through the helper covariance_kernel<3, 0> is allocated 78 VGPRs, not 80 — DESIGN.md §4)
             double X0[12], X1[12], p1[3];
 #pragma unroll
             for (int k = 0; k < 12; ++k) X0[k] = P[v0 * 12 + k];
@@ -165,118 +165,17 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
     if (lane < nv) mk[lane] = cov_exclude_zero_diagonal<D>(Hd + lane * DD, dg + lane * D);
     __syncthreads();
 
-    // ---- forward: S_i, its Cholesky factor, S_i^-1, K_i ------------------------------------------------------------------------------
+    // ---- forward: S_i, its Cholesky factor, S_i^-1, K_i; backward: Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (the parent of pose i is pose i + 1) ----
     bool ok = true;
-    for (int i = 0; i < nv; ++i) {
-        double A[D][D];
-#pragma unroll
-        for (int cc = 0; cc < D; ++cc)
-#pragma unroll
-            for (int rr = cc; rr < D; ++rr) A[rr][cc] = Hd[i * DD + rr * D + cc];
-        double ig[D];
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            // numerically singular: the pivot is at most kCovRelPivot of the coordinate's diagonal entry of H (a rank-deficient H leaves pivots of
-            // rounding size, 1e-16 .. 1e-14 of it, and of either sign: the absolute test alone would pass half of them); NaN fails as well
-            ok = ok && A[j][j] > kCovRelPivot * dg[i * D + j];
-            const double g = pivot_rsqrt(A[j][j]);
-            ig[j] = g;
-#pragma unroll
-            for (int i2 = j + 1; i2 < D; ++i2) A[i2][j] *= g;
-#pragma unroll
-            for (int i2 = j + 1; i2 < D; ++i2)
-#pragma unroll
-                for (int cc = j + 1; cc <= i2; ++cc) A[i2][cc] = __builtin_fma(-A[i2][j], A[cc][j], A[i2][cc]);
-        }
-        double sg = 0.0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) sg += ig[j];
-        ok = ok && sg < DBL_MAX;   // (a pivot <= 0 or not finite: NaN / inf — window_kernel.hip's test)
-        // L^-1 (lower): diagonal ig, below it -ig_i sum_k L_ik Linv_kc
-        double Li[D][D];
-#pragma unroll
-        for (int cc = 0; cc < D; ++cc) {
-            Li[cc][cc] = ig[cc];
-#pragma unroll
-            for (int rr = cc + 1; rr < D; ++rr) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = cc; k < rr; ++k) s = __builtin_fma(A[rr][k], Li[k][cc], s);
-                Li[rr][cc] = -ig[rr] * s;
-            }
-        }
-        double sinv = 0.0;   // entry (r, c) of S_i^-1 = L^-T L^-1
-        if (ent) {
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-                if (k >= r && k >= c) sinv = __builtin_fma(Li[k][r], Li[k][c], sinv);
-        }
-        __syncthreads();
-        if (ent) Hd[i * DD + lane] = sinv;
-        __syncthreads();
-        if (i + 1 < nv) {
-            double kr = 0.0;   // K_i = H_{i+1,i} S_i^-1
-            if (ent) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) kr = __builtin_fma(Ho[i * DD + r * D + k], Hd[i * DD + k * D + c], kr);
-                Kb[lane] = kr;
-            }
-            __syncthreads();
-            double s = 0.0;    // (K_i H_{i,i+1})_rc = sum_k K_rk H_{i+1,i}[c][k]
-            if (ent) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) s = __builtin_fma(Kb[r * D + k], Ho[i * DD + c * D + k], s);
-            }
-            __syncthreads();
-            if (ent) { Ho[i * DD + lane] = kr; Hd[(i + 1) * DD + lane] -= s; }
-            __syncthreads();
-        }
-    }
-    // ---- backward: Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i ---------------------------------------------------------------------------
-    for (int i = nv - 2; i >= 0; --i) {
-        if (ent) {
-            double t = 0.0;   // T = Sigma_{i+1} K_i
-#pragma unroll
-            for (int k = 0; k < D; ++k) t = __builtin_fma(Hd[(i + 1) * DD + r * D + k], Ho[i * DD + k * D + c], t);
-            Kb[lane] = t;
-        }
-        __syncthreads();
-        if (ent) {
-            double s = Hd[i * DD + lane];
-#pragma unroll
-            for (int k = 0; k < D; ++k) s = __builtin_fma(Ho[i * DD + k * D + r], Kb[k * D + c], s);
-            Hd[i * DD + lane] = s;
-        }
-        __syncthreads();
-    }
-    // ---- output: symmetric 6x6 per slot, excluded rows / columns 0, NaN for a singular window --------------------------------------
-    double* out = cov + (size_t)inst * nvm * 36;
-    for (int k = lane; k < nvm * 36; k += 64) {
-        const int v = k / 36, rr = (k % 36) / 6, cc = k % 6;
-        double x = 0.0;
-        if (v < nv) {
-            if (!ok) x = __builtin_nan("");
-            else if (rr < D && cc < D && !((mk[v] >> rr) & 1) && !((mk[v] >> cc) & 1))
-                x = (Hd[v * DD + rr * D + cc] + Hd[v * DD + cc * D + rr]) * 0.5;
-        }
-        out[k] = x;
-    }
-    for (int v = lane; v < nvm; v += 64) mask[(size_t)inst * nvm + v] = v < nv ? mk[v] : 0;
-    if (lane == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+    for (int i = 0; i < nv; ++i) cov_eliminate_block<D>(Hd, Ho, dg, Kb, i, i + 1 < nv, i + 1, lane, r, c, ent, ok);
+    for (int i = nv - 2; i >= 0; --i) cov_back_substitute_block<D>(Hd, Ho, Kb, i, i + 1, lane, r, c, ent);
+    cov_store_window<D>(Hd, mk, nv, nvm, ok, lane, inst, cov, mask, status);
 }
 
 template <int D, int JAC>
 hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC>>(160 * 1024);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&covariance_kernel<D, JAC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((covariance_kernel<D, JAC>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status);
     return hipGetLastError();
 }

@@ -13,12 +13,11 @@
 //     kFcSe3Chunk = 32: the three kinds of records share one LDS region, which keeps a 64-pose window at 60 KB — two windows per CU);
 //   * assembly: lane = entry (r, c), the records of a chunk added in edge order (no atomics, every entry owned by one lane: the same
 //     bits on every run): H_vv and H_{parent(v),v} by pose slot (every node has one parent: two blocks per pose);
-//   * the two sweeps node after node in schedule order (cov_eliminate_block / cov_back_substitute_block): a parent collects from its
-//     children in schedule order.
+//   * the two sweeps node after node in schedule order (cov_eliminate_block / cov_back_substitute_block of cov_block_device.h, the
+//     chain pass's steps with "parent" in place of "next pose"): a parent collects from its children in schedule order.
 // Every window of the batch has the schedule's counts and index tables (the host compared them), so the loops below are uniform.
 #include "cov_block_device.h"
-
-#include <atomic>
+#include "window_kernel.h"
 
 namespace locamd {
 
@@ -54,121 +53,6 @@ __host__ __device__ inline ForestCovLayout forest_cov_layout(int nv, bool priors
     return l;
 }
 
-// The block steps below are the chain pass's (covariance_kernel.hip: its forward / backward loops and its store) with "parent" in place of
-// "next pose"; they stay a copy because the chain kernel's code changes when its loops are moved into functions.
-// Eliminates node i (pose slot i of the window's LDS blocks: Hd = diagonal blocks, Ho = the blocks H_{parent,node} with the parent's rows, dg =
-// diag(H)): Hd[i] holds S_i, the node's diagonal block minus its children's shares.  Every lane factors S_i (Cholesky, pivots checked) in its
-// registers; S_i^-1 = L^-T L^-1 replaces S_i.  With a parent (slot ip): K_i = H_{ip,i} S_i^-1 replaces Ho[i] and Hd[ip] loses K_i H_{i,ip}.
-// Kb: one D x D exchange block.  ok: cleared by a pivot that is not finite, not positive or at most kCovRelPivot of its coordinate's
-// diagonal entry of H.
-template <int D>
-__device__ __forceinline__ void cov_eliminate_block(double* Hd, double* Ho, const double* dg, double* Kb, int i, bool has_parent, int ip, int lane, int r, int c, bool ent, bool& ok) {
-    constexpr int DD = D * D;
-    double A[D][D];
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc)
-#pragma unroll
-        for (int rr = cc; rr < D; ++rr) A[rr][cc] = Hd[i * DD + rr * D + cc];
-    double ig[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        // numerically singular: the pivot is at most kCovRelPivot of the coordinate's diagonal entry of H (a rank-deficient H leaves pivots of
-        // rounding size, 1e-16 .. 1e-14 of it, and of either sign: the absolute test alone would pass half of them); NaN fails as well
-        ok = ok && A[j][j] > kCovRelPivot * dg[i * D + j];
-        const double g = pivot_rsqrt(A[j][j]);
-        ig[j] = g;
-#pragma unroll
-        for (int i2 = j + 1; i2 < D; ++i2) A[i2][j] *= g;
-#pragma unroll
-        for (int i2 = j + 1; i2 < D; ++i2)
-#pragma unroll
-            for (int cc = j + 1; cc <= i2; ++cc) A[i2][cc] = __builtin_fma(-A[i2][j], A[cc][j], A[i2][cc]);
-    }
-    double sg = 0.0;
-#pragma unroll
-    for (int j = 0; j < D; ++j) sg += ig[j];
-    ok = ok && sg < DBL_MAX;   // (a pivot <= 0 or not finite: NaN / inf — window_kernel.hip's test)
-    // L^-1 (lower): diagonal ig, below it -ig_i sum_k L_ik Linv_kc
-    double Li[D][D];
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc) {
-        Li[cc][cc] = ig[cc];
-#pragma unroll
-        for (int rr = cc + 1; rr < D; ++rr) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = cc; k < rr; ++k) s = __builtin_fma(A[rr][k], Li[k][cc], s);
-            Li[rr][cc] = -ig[rr] * s;
-        }
-    }
-    double sinv = 0.0;   // entry (r, c) of S_i^-1 = L^-T L^-1
-    if (ent) {
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-            if (k >= r && k >= c) sinv = __builtin_fma(Li[k][r], Li[k][c], sinv);
-    }
-    __syncthreads();
-    if (ent) Hd[i * DD + lane] = sinv;
-    __syncthreads();
-    if (has_parent) {
-        double kr = 0.0;   // K_i = H_{ip,i} S_i^-1
-        if (ent) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) kr = __builtin_fma(Ho[i * DD + r * D + k], Hd[i * DD + k * D + c], kr);
-            Kb[lane] = kr;
-        }
-        __syncthreads();
-        double s = 0.0;    // (K_i H_{i,ip})_rc = sum_k K_rk H_{ip,i}[c][k]
-        if (ent) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) s = __builtin_fma(Kb[r * D + k], Ho[i * DD + c * D + k], s);
-        }
-        __syncthreads();
-        if (ent) { Ho[i * DD + lane] = kr; Hd[ip * DD + lane] -= s; }
-        __syncthreads();
-    }
-}
-
-// selected inversion, node i with parent ip: Sigma_i = S_i^-1 + K_i^T Sigma_ip K_i (Hd[i]: S_i^-1 in, Sigma_i out; Hd[ip]: the parent's finished
-// Sigma; Ho[i]: K_i)
-template <int D>
-__device__ __forceinline__ void cov_back_substitute_block(double* Hd, const double* Ho, double* Kb, int i, int ip, int lane, int r, int c, bool ent) {
-    constexpr int DD = D * D;
-    if (ent) {
-        double t = 0.0;   // T = Sigma_ip K_i
-#pragma unroll
-        for (int k = 0; k < D; ++k) t = __builtin_fma(Hd[ip * DD + r * D + k], Ho[i * DD + k * D + c], t);
-        Kb[lane] = t;
-    }
-    __syncthreads();
-    if (ent) {
-        double s = Hd[i * DD + lane];
-#pragma unroll
-        for (int k = 0; k < D; ++k) s = __builtin_fma(Ho[i * DD + k * D + r], Kb[k * D + c], s);
-        Hd[i * DD + lane] = s;
-    }
-    __syncthreads();
-}
-
-// output of window `inst`: symmetric 6x6 per slot ((a + a^T) / 2), excluded rows / columns 0, slots >= nv 0, NaN for a singular window
-template <int D>
-__device__ __forceinline__ void cov_store_window(const double* Hd, const int* mk, int nv, int nvm, bool ok, int lane, long long inst, double* cov, int32_t* mask, int32_t* status) {
-    constexpr int DD = D * D;
-    double* out = cov + (size_t)inst * nvm * 36;
-    for (int k = lane; k < nvm * 36; k += 64) {
-        const int v = k / 36, rr = (k % 36) / 6, cc = k % 6;
-        double x = 0.0;
-        if (v < nv) {
-            if (!ok) x = __builtin_nan("");
-            else if (rr < D && cc < D && !((mk[v] >> rr) & 1) && !((mk[v] >> cc) & 1))
-                x = (Hd[v * DD + rr * D + cc] + Hd[v * DD + cc * D + rr]) * 0.5;
-        }
-        out[k] = x;
-    }
-    for (int v = lane; v < nvm; v += 64) mask[(size_t)inst * nvm + v] = v < nv ? mk[v] : 0;
-    if (lane == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
-}
-
 template <int JAC>
 __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs a, const TreeSched ts, double* cov, int32_t* mask, int32_t* status) {
     constexpr int D = 6, DD = 36, RS = 13;
@@ -201,15 +85,7 @@ __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs 
         if (e < nr) {
             const double* val = a.r_val + ((size_t)inst * cp.nr_max + e) * 5;
             const int v0 = ts.r_idx[2 * e], v1 = ts.r_idx[2 * e + 1];
-            double X0[12], X1[12], p1[3];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) X0[k] = P[v0 * 12 + k];
-            const int v1c = v1 >= 0 ? v1 : v0;
-#pragma unroll
-            for (int k = 0; k < 12; ++k) X1[k] = P[v1c * 12 + k];
-            if (v1 >= 0) { p1[0] = X1[9]; p1[1] = X1[10]; p1[2] = X1[11]; }
-            else { const double* an = a.anchors + (size_t)(-1 - v1) * 3; p1[0] = an[0]; p1[1] = an[1]; p1[2] = an[2]; }
-            cov_range_rec<D, JAC>(X0, X1, p1, v1 >= 0, val, rec + lane * RS);
+            cov_range_edge<D, JAC>(P, a.anchors, v0, v1, val, rec + lane * RS);
             ei[2 * lane] = v0; ei[2 * lane + 1] = v1;
         }
         __syncthreads();
@@ -288,16 +164,8 @@ __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs 
 
 template <int JAC>
 hipError_t launch_forest_cov_t(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC>>(160 * 1024);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&forest_covariance_kernel<JAC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((forest_covariance_kernel<JAC>), dim3((unsigned)a.B), dim3(64), lds, stream, a, ts, cov, mask, status);
     return hipGetLastError();
 }

@@ -33,7 +33,6 @@
 #include <float.h>
 #include <math.h>
 
-#include <atomic>
 
 namespace locamd {
 
@@ -1022,16 +1021,8 @@ size_t window_wave6_lds_bytes(const WindowCaps& c, bool se3) {
 namespace {
 template <int JAC, bool SE3>
 hipError_t launch_wave6_t(const WindowArgs& a, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&wave6_lm_kernel<JAC, SE3>>((int)kWave6MaxLds);
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wave6_lm_kernel<JAC, SE3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWave6MaxLds);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((wave6_lm_kernel<JAC, SE3>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
     return hipGetLastError();
 }

@@ -3,7 +3,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace locamd {
+
+// Host side of every launch that asks for more than 64 KiB of dynamic LDS: the opt-in is per device and per kernel (instantiation), so
+// each instantiation of this helper keeps one flag word, a bit per device, and asks the runtime once.
+template <auto Kernel>
+inline hipError_t allow_dynamic_lds(int bytes) {
+    static std::atomic<uint64_t> attr_set{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (attr_set.load(std::memory_order_acquire) & bit) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) attr_set.fetch_or(bit, std::memory_order_release);
+    return e;
+}
 
 // Per-batch capacities; every instance owns fixed-size slices of the arrays below.
 struct WindowCaps {

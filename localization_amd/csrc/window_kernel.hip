@@ -35,7 +35,6 @@
 #include "window_device.h"
 #include "lm_damping.h"
 
-#include <atomic>
 
 namespace locamd {
 
@@ -2811,18 +2810,8 @@ constexpr size_t WIDE_STATIC_LDS = 4096;   // >= the static LDS of the several-w
 
 template <bool GLOBAL_A, int JAC, bool SP, int W, int NW = 1>
 static hipError_t launch_window_t(const WindowArgs& a, size_t lds, hipStream_t stream) {
-    // the opt-in to more than 64 KiB of dynamic LDS is per device (and per kernel instantiation)
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds<&window_lm_kernel<GLOBAL_A, JAC, SP, W, NW>>(160 * 1024 - (NW > 1 ? WIDE_STATIC_LDS : 512));  // static LDS on top
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&window_lm_kernel<GLOBAL_A, JAC, SP, W, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (NW > 1 ? WIDE_STATIC_LDS : 512));  // static LDS on top
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((window_lm_kernel<GLOBAL_A, JAC, SP, W, NW>), dim3((unsigned)a.B), dim3(64 * NW), lds, stream, a);
     return hipGetLastError();
 }
