@@ -1,0 +1,464 @@
+// Structure analysis of a batch of windows.  Host code only: no HIP runtime call in this file.
+#include "window_structure.h"
+
+#include <cstring>
+#include <algorithm>
+#include <atomic>
+#include <thread>
+#include <utility>
+#include <vector>
+
+namespace locamd {
+
+// The host passes over a batch (validation, structure hash, chain / translation-only scans) are O(instances x edges) and run in front of a
+// kernel of a millisecond or two: batches of >= 4 096 instances are split over up to eight threads (f(lo, hi) on disjoint instance ranges).
+template <class F>
+static void parallel_chunks(int64_t n, F&& f) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int nt = n >= 4096 ? (int)std::min<unsigned>(8u, hw ? hw : 1u) : 1;
+    if (nt <= 1) { f((int64_t)0, n, 0); return; }
+    const int64_t per = (n + nt - 1) / nt;
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back([&f, t, per, n] { f(std::min(n, t * per), std::min(n, (t + 1) * per), t); });
+    f((int64_t)0, std::min(n, per), 0);
+    for (auto& x : th) x.join();
+}
+
+// Host-side shape check of every instance: 0, or WHICH check failed first (the caller words the error: capi_window.cpp, validate_instances)
+int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b) {
+    std::atomic<int> first_bad{0};
+    parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int) {
+        auto check = [&](int64_t i) -> int {
+            const int32_t* cn = b.counts + i * 4;
+            if (cn[0] < 0 || cn[0] > c.nv_max || cn[1] < 0 || cn[1] > c.nr_max || cn[2] < 0 || cn[2] > c.np_max || cn[3] < 0 || cn[3] > c.ns_max) return 1;
+            for (int e = 0; e < cn[1]; ++e) {
+                const int32_t* ix = b.r_idx + ((size_t)i * c.nr_max + e) * 2;
+                if (ix[0] < 0 || ix[0] >= cn[0] || ix[1] >= cn[0] || ix[1] < -n_anchors || ix[0] == ix[1]) return 2;
+                if (ix[1] >= 0 && (ix[0] - ix[1] > c.bw_max || ix[1] - ix[0] > c.bw_max)) return 3;
+            }
+            for (int e = 0; e < cn[2]; ++e) {
+                const int32_t v = b.p_idx[(size_t)i * c.np_max + e];
+                if (v < 0 || v >= cn[0]) return 4;
+            }
+            for (int e = 0; e < cn[3]; ++e) {
+                const int32_t* ix = b.s_idx + ((size_t)i * c.ns_max + e) * 4;
+                if (ix[0] < 0 || ix[0] >= cn[0] || ix[1] < 0 || ix[1] >= cn[0] || ix[0] == ix[1]) return 5;
+                if (ix[0] - ix[1] > c.bw_max || ix[1] - ix[0] > c.bw_max) return 6;
+            }
+            return 0;
+        };
+        for (int64_t i = lo; i < hi && first_bad.load(std::memory_order_relaxed) == 0; ++i) {
+            const int bad = check(i);
+            if (bad) { int zero = 0; first_bad.compare_exchange_strong(zero, bad); return; }
+        }
+    });
+    return first_bad.load();
+}
+
+// translation-only (the exact 3-DoF reduction, chain3_kernel.hip / arrow3_kernel.hip): no EdgeSE3, every lever arm zero, every
+// rotation the identity, priors with an identity measurement rotation and no rotation information
+bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b) {
+    static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (n_anchors > 500000) return false;   // (the packed endpoint word of chain3 holds 2^19 anchors)
+    std::atomic<bool> all{true};
+    parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int) {
+        auto one = [&](int64_t i) {
+            const int32_t* cn = b.counts + i * 4;
+            if (cn[3] != 0 || cn[0] > 1048575) return false;
+            for (int e = 0; e < cn[1]; ++e) {
+                const double* v = b.r_val + ((size_t)i * c.nr_max + e) * 5;
+                if (v[2] != 0.0 || v[3] != 0.0 || v[4] != 0.0) return false;
+            }
+            for (int p = 0; p < cn[0]; ++p)
+                if (std::memcmp(b.poses + ((size_t)i * c.nv_max + p) * 12, I9, sizeof(I9)) != 0) return false;
+            for (int e = 0; e < cn[2]; ++e) {
+                const double* v = b.p_val + ((size_t)i * c.np_max + e) * 18;
+                if (std::memcmp(v, I9, sizeof(I9)) != 0 || v[15] != 0.0 || v[16] != 0.0 || v[17] != 0.0) return false;
+            }
+            return true;
+        };
+        for (int64_t i = lo; i < hi && all.load(std::memory_order_relaxed); ++i)
+            if (!one(i)) { all.store(false); return; }
+    });
+    return all.load();
+}
+
+// The chain scan: every pose-to-pose edge (range or SE3) of every window joins consecutive pose slots.  ordered: edges are also listed
+// in the order of their later pose and priors in pose order (what the lane-per-window and wave-per-window solve kernels walk); the
+// covariance pass takes any order.  single_pairs / se3_pairs: batch_topology's pair counts (only meaningful for chain batches, where
+// every range was scanned).
+void chain_scan(const WindowCaps& c, const HostBatch& b, bool ordered, bool& chain, bool& single_pairs, bool& se3_pairs) {
+    std::atomic<bool> a_chain{true}, a_single{true}, a_single_r{true}, a_single_s{true}, a_any_s{false};
+    parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int) {
+        bool chain_l = true, single_l = true, single_r = true, single_s = true, any_s = false;
+        for (int64_t i = lo; i < hi && chain_l && a_chain.load(std::memory_order_relaxed); ++i) {
+            const int32_t* cn = b.counts + i * 4;
+            if (cn[3] != 0) { single_l = false; any_s = true; }
+            int last = 0;
+            for (int e = 0; e < cn[3]; ++e) {   // EdgeSE3 factors: between consecutive poses, ordered by their later pose (addTwistEdge)
+                const int32_t* ix = b.s_idx + ((size_t)i * c.ns_max + e) * 4;
+                const int key2 = ix[1] > ix[0] ? ix[1] : ix[0];
+                if ((ordered && key2 < last) || (ix[0] - ix[1] != 1 && ix[1] - ix[0] != 1)) { chain_l = false; break; }
+                if (key2 == last) single_s = false;   // (a second EdgeSE3 on the same pair; poses are numbered from 0, so `last` = 0 is no pair)
+                last = key2;
+            }
+            last = 0;
+            int last_pair = -1;
+            for (int e = 0; e < cn[1] && chain_l; ++e) {
+                const int32_t* ix = b.r_idx + ((size_t)i * c.nr_max + e) * 2;
+                const int key2 = ix[1] > ix[0] ? ix[1] : ix[0];
+                if (ordered && key2 < last) chain_l = false;
+                if (ix[1] >= 0) { if (key2 == last_pair) { single_l = false; single_r = false; } last_pair = key2; }
+                last = key2;
+                if (ix[1] >= 0 && ix[0] - ix[1] != 1 && ix[1] - ix[0] != 1) chain_l = false;
+            }
+            last = 0;
+            for (int e = 0; e < cn[2] && chain_l && ordered; ++e) {
+                const int32_t v = b.p_idx[(size_t)i * c.np_max + e];
+                if (v < last) chain_l = false;
+                last = v;
+            }
+        }
+        if (!chain_l) a_chain.store(false);
+        if (!single_l) a_single.store(false);
+        if (!single_r) a_single_r.store(false);
+        if (!single_s) a_single_s.store(false);
+        if (any_s) a_any_s.store(true);
+    });
+    chain = a_chain.load();
+    single_pairs = a_single.load();
+    se3_pairs = a_any_s.load() && a_single_r.load() && a_single_s.load();
+}
+
+// 64-bit hash of a batch's STRUCTURE: n, the counts and the used entries of the index tables (never the measurements)
+unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const HostBatch& b) {
+    unsigned long long part[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // one hash per thread's instance range, combined in range order
+    parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int t) {
+        unsigned long long h = 0x9e3779b97f4a7c15ull + (unsigned long long)t;
+        auto mix = [&h](const int32_t* p, size_t cnt) {
+            size_t i = 0;
+            for (; i + 2 <= cnt; i += 2) {
+                unsigned long long v;
+                std::memcpy(&v, p + i, 8);
+                h = (h ^ v) * 0xff51afd7ed558ccdull;
+                h ^= h >> 32;
+            }
+            if (i < cnt) { h = (h ^ (unsigned long long)(uint32_t)p[i]) * 0xc4ceb9fe1a85ec53ull; h ^= h >> 29; }
+        };
+        for (int64_t i = lo; i < hi; ++i) {
+            const int32_t* cn = b.counts + i * 4;
+            mix(cn, 4);
+            if (cn[1]) mix(b.r_idx + (size_t)i * c.nr_max * 2, (size_t)cn[1] * 2);
+            if (cn[2]) mix(b.p_idx + (size_t)i * c.np_max, (size_t)cn[2]);
+            if (cn[3]) mix(b.s_idx + (size_t)i * c.ns_max * 4, (size_t)cn[3] * 4);
+        }
+        part[t & 7] = h;
+    });
+    unsigned long long h = 0x9e3779b97f4a7c15ull ^ (unsigned long long)b.n ^ (has_off1 ? 0x51ull << 56 : 0);
+    for (int t = 0; t < 8; ++t) { h = (h ^ part[t]) * 0xff51afd7ed558ccdull; h ^= h >> 32; }
+    return h;
+}
+
+// CHAIN + BORDER ("arrowhead": BASELINE config 4, anchor self-calibration — a tag trajectory whose poses range to a few nodes that
+// are unknowns themselves, localization.cpp:94-98).  The border of an instance = its last nb0 pose slots, nb0 = the smallest number
+// such that every pose-to-pose edge between NON-consecutive slots has an endpoint there; the other poses form the chain (one edge
+// per consecutive pair at most).  The chain is cut into up to four segments at separator poses, which join the border (one level of
+// nested dissection: arrow3_lm_kernel sweeps the segments with one wave each).  Rows = chain rows segment by segment, then border
+// rows (separators first, then the original border in slot order).  A chain row owns its edges to anchors, to border poses and
+// to the previous chain row; a border row those to lower-index border poses and to anchors.  Every row's edges (creation order)
+// and priors are packed as records [chunk of 64 rows][slot][lane].
+// A.arrow_list_cap: the most edges and priors any pose in front of the nb0 border slots has (arrow_covariance_kernel.hip's list size).
+// structure_only: the test alone, for the covariance pass — A is a table set of the covariance's own and nothing is packed.
+bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only) {
+    const int NW = 4;
+    const int nchunk = (c.nv_max + 63) / 64;
+    A.h_ahdr.assign((size_t)b.n * 8, 0);
+    A.h_arslot.assign((size_t)b.n * c.nv_max, 0);
+    std::vector<int32_t> cls, nedge, nprior, pairs;
+    std::vector<int> seps;
+    // pass 1: structure, record counts
+    int nb_max = 0, jmax = 1, jpmax = 1, list_cap = 1;
+    int jch[16], jpch[16];
+    for (int k = 0; k < 16; ++k) { jch[k] = 1; jpch[k] = 1; }
+    for (int64_t i = 0; i < b.n; ++i) {
+        const int32_t* cn = b.counts + i * 4;
+        const int nv = cn[0], nr = cn[1], np = cn[2];
+        const int32_t* ri = b.r_idx + (size_t)i * c.nr_max * 2;
+        int nb0 = 0;
+        for (int e = 0; e < nr; ++e) {
+            const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
+            if (v1 < 0) {
+                if (-1 - v1 >= kArrowMaxAnchors) return false;   // (the kernel keeps the anchor table in LDS)
+                continue;
+            }
+            const int hi = v0 > v1 ? v0 : v1, lo = v0 > v1 ? v1 : v0;
+            if (hi - lo != 1 && nv - hi > nb0) nb0 = nv - hi;
+        }
+        if (nb0 < 1 || nb0 > 12 || nv - nb0 < 2) return false;
+        const int n0 = nv - nb0;
+        int nseg = n0 / 24;
+        if (nseg > NW) nseg = NW;
+        if (nseg < 1) nseg = 1;
+        const int nb = nb0 + nseg - 1, nc = n0 - (nseg - 1);
+        cls.assign((size_t)nv, 0);
+        seps.clear();
+        for (int k = 1; k < nseg; ++k) seps.push_back((int)((long long)k * n0 / nseg));
+        int32_t* hdr = A.h_ahdr.data() + (size_t)i * 8;
+        int32_t* rslot = A.h_arslot.data() + (size_t)i * c.nv_max;
+        hdr[0] = nb; hdr[1] = nseg; hdr[2] = nc; hdr[3] = 0;
+        int q = 0, si = 0;
+        for (int v = 0; v < n0; ++v) {
+            if (si < (int)seps.size() && v == seps[si]) { cls[v] = -1 - si; rslot[nc + si] = v; ++si; hdr[3 + si] = q; continue; }
+            cls[v] = q; rslot[q] = v; ++q;
+        }
+        for (int s2 = nseg; s2 <= NW; ++s2) hdr[3 + s2] = nc;   // (segments nseg .. NW-1 are empty)
+        for (int v = n0; v < nv; ++v) { const int bs = (nseg - 1) + (v - n0); cls[v] = -1 - bs; rslot[nc + bs] = v; }
+        // owners
+        nedge.assign((size_t)nv, 0); nprior.assign((size_t)nv, 0); pairs.assign((size_t)nc + 1, 0);
+        for (int e = 0; e < nr; ++e) {
+            const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
+            int row;
+            if (v1 < 0) row = cls[v0] >= 0 ? cls[v0] : nc + (-1 - cls[v0]);
+            else {
+                const int c0 = cls[v0], c1 = cls[v1];
+                if (c0 >= 0 && c1 >= 0) {
+                    if (c0 - c1 != 1 && c1 - c0 != 1) return false;   // (cannot happen: non-consecutive edges end in the border)
+                    row = c0 > c1 ? c0 : c1;
+                    if (++pairs[row] > 1) return false;                // one edge per consecutive chain pair
+                } else if (c0 >= 0) row = c0;
+                else if (c1 >= 0) row = c1;
+                else row = nc + ((-1 - c0) > (-1 - c1) ? (-1 - c0) : (-1 - c1));
+            }
+            if (++nedge[row] > jmax) jmax = nedge[row];
+            if (row / 64 < 16 && nedge[row] > jch[row / 64]) jch[row / 64] = nedge[row];
+        }
+        const int32_t* pi = b.p_idx + (size_t)i * c.np_max;
+        for (int e = 0; e < np; ++e) {
+            const int cv = cls[pi[e]], row = cv >= 0 ? cv : nc + (-1 - cv);
+            if (++nprior[row] > jpmax) jpmax = nprior[row];
+            if (row / 64 < 16 && nprior[row] > jpch[row / 64]) jpch[row / 64] = nprior[row];
+        }
+        if (nb > nb_max) nb_max = nb;
+        {
+            std::vector<int32_t>& deg = nedge;   // (its row counts are not needed any more)
+            deg.assign((size_t)nv, 0);
+            for (int e = 0; e < nr; ++e) {
+                const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
+                if (structure_only && v1 == v0) return false;   // (pass 2's test: a range from a border pose to itself)
+                ++deg[v0];
+                if (v1 >= 0) ++deg[v1];
+            }
+            for (int e = 0; e < np; ++e) ++deg[pi[e]];
+            for (int v = 0; v < n0; ++v) if (deg[v] > list_cap) list_cap = deg[v];
+        }
+    }
+    if (jmax > 64 || jpmax > 16 || nb_max > 15) return false;
+    if (window_arrow3_lds_bytes(c, nb_max) > 160 * 1024 - 512) return false;
+    A.arrow_list_cap = list_cap;
+    if (structure_only) return true;
+    // pass 2: the records
+    const size_t rec_per = (size_t)nchunk * jmax * 64 * 3, prec_per = (size_t)nchunk * jpmax * 64 * 7;
+    A.h_arec.assign((size_t)b.n * rec_per, -1.0);
+    A.h_aprec.assign((size_t)b.n * prec_per, 0.0);
+    for (int64_t i = 0; i < b.n; ++i) {
+        const int32_t* cn = b.counts + i * 4;
+        const int nv = cn[0], nr = cn[1], np = cn[2];
+        const int32_t* ri = b.r_idx + (size_t)i * c.nr_max * 2;
+        const double* rv = b.r_val + (size_t)i * c.nr_max * 5;
+        const int32_t* hdr = A.h_ahdr.data() + (size_t)i * 8;
+        const int32_t* rslot = A.h_arslot.data() + (size_t)i * c.nv_max;
+        const int nb = hdr[0], nc = hdr[2];
+        cls.assign((size_t)nv, 0);
+        for (int r = 0; r < nc + nb; ++r) cls[rslot[r]] = r < nc ? r : -1 - (r - nc);
+        nedge.assign((size_t)nv, 0); nprior.assign((size_t)nv, 0);
+        double* rec = A.h_arec.data() + (size_t)i * rec_per;
+        for (int e = 0; e < nr; ++e) {
+            const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
+            int row, kind, idx, own0;
+            if (v1 < 0) { row = cls[v0] >= 0 ? cls[v0] : nc + (-1 - cls[v0]); kind = 0; idx = -1 - v1; own0 = 1; }
+            else {
+                const int c0 = cls[v0], c1 = cls[v1];
+                if (c0 >= 0 && c1 >= 0) { row = c0 > c1 ? c0 : c1; kind = 1; idx = 0; own0 = c0 > c1; }
+                else if (c0 >= 0) { row = c0; kind = 2; idx = -1 - c1; own0 = 1; }
+                else if (c1 >= 0) { row = c1; kind = 2; idx = -1 - c0; own0 = 0; }
+                else {
+                    const int b0 = -1 - c0, b1 = -1 - c1;
+                    if (b0 == b1) return false;
+                    row = nc + (b0 > b1 ? b0 : b1); kind = 2; idx = b0 > b1 ? b1 : b0; own0 = b0 > b1;
+                }
+            }
+            double* q = rec + (((size_t)(row / 64) * jmax + nedge[row]++) * 64 + row % 64) * 3;
+            q[0] = (double)((idx << 3) | (kind << 1) | own0); q[1] = rv[5 * e]; q[2] = rv[5 * e + 1];
+        }
+        const int32_t* pi = b.p_idx + (size_t)i * c.np_max;
+        const double* pv = b.p_val + (size_t)i * c.np_max * 18;
+        double* prec = A.h_aprec.data() + (size_t)i * prec_per;
+        for (int e = 0; e < np; ++e) {
+            const int cv = cls[pi[e]], row = cv >= 0 ? cv : nc + (-1 - cv);
+            double* q = prec + (((size_t)(row / 64) * jpmax + nprior[row]++) * 64 + row % 64) * 7;
+            q[0] = 1.0;
+            for (int k = 0; k < 3; ++k) { q[1 + k] = pv[18 * e + 9 + k]; q[4 + k] = pv[18 * e + 12 + k]; }
+        }
+    }
+    A.arrow_nb_max = nb_max; A.arrow_jmax = jmax; A.arrow_jpmax = jpmax;
+    for (int k = 0; k < 16; ++k) { A.arrow_jch[k] = jch[k]; A.arrow_jpch[k] = jpch[k]; }
+    return true;
+}
+
+// FOREST windows of ONE shared topology (BASELINE config 5: the key-frame star of addPoseEdge, localization.cpp:254-290, replayed
+// with different measurements in every instance): every instance has the same counts and index tables, and the pose-to-pose
+// edges form a forest.  Builds the elimination schedule tree_lm_kernel walks: nodes in post-order (children before their parent,
+// a node's children heavy subtree first so that the leaves of one parent are consecutive), per node its parent and its edges.
+// Layout of the int table: node[nv] par[nv] r_off[nv+1] r_list[nr] p_off[nv+1] p_list[np] s_off[nv+1] s_list[ns] r_idx[2 nr] s_idx[4 ns].
+bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
+    const int nv = b.counts[0], nr = b.counts[1], np = b.counts[2], ns = b.counts[3];
+    if (nv < 2 || nv > 64 || has_off1) return false;
+    for (int64_t i = 1; i < b.n; ++i) {   // one topology
+        if (std::memcmp(b.counts + i * 4, b.counts, 4 * sizeof(int32_t)) != 0) return false;
+        if (nr && std::memcmp(b.r_idx + (size_t)i * c.nr_max * 2, b.r_idx, (size_t)nr * 2 * sizeof(int32_t)) != 0) return false;
+        if (np && std::memcmp(b.p_idx + (size_t)i * c.np_max, b.p_idx, (size_t)np * sizeof(int32_t)) != 0) return false;
+        if (ns && std::memcmp(b.s_idx + (size_t)i * c.ns_max * 4, b.s_idx, (size_t)ns * 4 * sizeof(int32_t)) != 0) return false;
+    }
+    // adjacency (pairs joined by at least one edge); a forest has no cycle: union-find on the distinct pairs
+    std::vector<int> uf((size_t)nv);
+    for (int v = 0; v < nv; ++v) uf[(size_t)v] = v;
+    auto find = [&](int v) { while (uf[(size_t)v] != v) { uf[(size_t)v] = uf[(size_t)uf[(size_t)v]]; v = uf[(size_t)v]; } return v; };
+    std::vector<std::vector<int>> adj((size_t)nv);
+    auto join = [&](int u, int v) -> bool {
+        for (int x : adj[(size_t)u]) if (x == v) return true;   // a second edge on the same pair
+        const int ra = find(u), rb = find(v);
+        if (ra == rb) return false;                             // a cycle
+        uf[(size_t)ra] = rb;
+        adj[(size_t)u].push_back(v); adj[(size_t)v].push_back(u);
+        return true;
+    };
+    for (int e = 0; e < nr; ++e) if (b.r_idx[2 * e + 1] >= 0 && !join(b.r_idx[2 * e], b.r_idx[2 * e + 1])) return false;
+    for (int e = 0; e < ns; ++e) if (!join(b.s_idx[4 * e], b.s_idx[4 * e + 1])) return false;
+    // root of every component = its CENTRE (the middle of a longest path: two breadth-first searches), so that the elimination by
+    // height takes half as many steps as from an end (config 5's chain of eight keys: 6 levels instead of 9); parents towards the
+    // root; subtree sizes; post-order, heavy child first
+    std::vector<int> parent((size_t)nv, -2), size((size_t)nv, 1), order, stack, depth((size_t)nv, 0);
+    int nroots = 0, maxdepth = 0;
+    std::vector<int> bfs;
+    std::vector<int> seen((size_t)nv, 0), dist((size_t)nv, 0), from((size_t)nv, -1), centre_of;
+    auto far_from = [&](int start) {   // the farthest node from `start` inside its component (dist / from filled)
+        std::vector<int> q2{start};
+        std::vector<int> mark((size_t)nv, 0);
+        mark[(size_t)start] = 1; dist[(size_t)start] = 0; from[(size_t)start] = -1;
+        int last = start;
+        for (size_t h = 0; h < q2.size(); ++h) {
+            const int v = q2[h];
+            last = v;
+            for (int x : adj[(size_t)v]) if (!mark[(size_t)x]) { mark[(size_t)x] = 1; dist[(size_t)x] = dist[(size_t)v] + 1; from[(size_t)x] = v; q2.push_back(x); }
+        }
+        for (int v : q2) seen[(size_t)v] = 1;
+        return last;
+    };
+    for (int v0 = 0; v0 < nv; ++v0) {
+        if (seen[(size_t)v0]) continue;
+        const int a1 = far_from(v0);
+        const int b1 = far_from(a1);        // a1 .. b1: a longest path of this tree
+        int c1 = b1;
+        for (int step = dist[(size_t)b1] / 2; step > 0; --step) c1 = from[(size_t)c1];
+        centre_of.push_back(c1);
+    }
+    for (int root : centre_of) {
+        if (parent[(size_t)root] != -2) continue;
+        parent[(size_t)root] = -1; ++nroots;
+        const size_t b0 = bfs.size();
+        bfs.push_back(root);
+        for (size_t h = b0; h < bfs.size(); ++h) {
+            const int v = bfs[h];
+            for (int x : adj[(size_t)v]) if (parent[(size_t)x] == -2) { parent[(size_t)x] = v; depth[(size_t)x] = depth[(size_t)v] + 1; if (depth[(size_t)x] > maxdepth) maxdepth = depth[(size_t)x]; bfs.push_back(x); }
+        }
+        for (size_t h = bfs.size(); h-- > b0 + 1;) size[(size_t)parent[(size_t)bfs[h]]] += size[(size_t)bfs[h]];
+    }
+    std::vector<std::vector<int>> kids((size_t)nv);
+    for (int v = 0; v < nv; ++v) if (parent[(size_t)v] >= 0) kids[(size_t)parent[(size_t)v]].push_back(v);
+    for (auto& k : kids) std::stable_sort(k.begin(), k.end(), [&](int a2, int b2) { return size[(size_t)a2] > size[(size_t)b2]; });
+    // iterative post-order
+    for (int root = 0; root < nv; ++root) {
+        if (parent[(size_t)root] != -1) continue;
+        std::vector<std::pair<int, size_t>> st;
+        st.push_back({root, 0});
+        while (!st.empty()) {
+            auto& top = st.back();
+            if (top.second < kids[(size_t)top.first].size()) { const int ch = kids[(size_t)top.first][top.second++]; st.push_back({ch, 0}); }
+            else { order.push_back(top.first); st.pop_back(); }
+        }
+    }
+    if ((int)order.size() != nv) return false;
+    std::vector<int> pos((size_t)nv);
+    for (int k = 0; k < nv; ++k) pos[(size_t)order[(size_t)k]] = k;
+    // edges by node: a unary edge belongs to its pose; an edge between a node and its parent to the node (the child)
+    std::vector<std::vector<int>> re((size_t)nv), pe((size_t)nv), se((size_t)nv);
+    for (int e = 0; e < nr; ++e) {
+        const int v0 = b.r_idx[2 * e], v1 = b.r_idx[2 * e + 1];
+        if (v1 < 0) re[(size_t)pos[(size_t)v0]].push_back(e);
+        else re[(size_t)pos[(size_t)(parent[(size_t)v0] == v1 ? v0 : v1)]].push_back(e);
+    }
+    for (int e = 0; e < np; ++e) pe[(size_t)pos[(size_t)b.p_idx[e]]].push_back(e);
+    for (int e = 0; e < ns; ++e) {
+        const int vi = b.s_idx[4 * e], vj = b.s_idx[4 * e + 1];
+        se[(size_t)pos[(size_t)(parent[(size_t)vi] == vj ? vi : vj)]].push_back(e);
+    }
+    std::vector<int32_t>& t = A.h_tsched;
+    t.clear();
+    for (int k = 0; k < nv; ++k) t.push_back(order[(size_t)k]);
+    for (int k = 0; k < nv; ++k) { const int p = parent[(size_t)order[(size_t)k]]; t.push_back(p < 0 ? -1 : pos[(size_t)p]); }
+    auto lists = [&](const std::vector<std::vector<int>>& L) {
+        int acc = 0;
+        for (int k = 0; k < nv; ++k) { t.push_back(acc); acc += (int)L[(size_t)k].size(); }
+        t.push_back(acc);
+        for (int k = 0; k < nv; ++k) for (int e : L[(size_t)k]) t.push_back(e);
+    };
+    lists(re); lists(pe); lists(se);
+    for (int i = 0; i < 2 * nr; ++i) t.push_back(b.r_idx[i]);
+    for (int i = 0; i < 4 * ns; ++i) t.push_back(b.s_idx[i]);
+    // by pose slot (tree_wave_kernel): parent, height, children, edges
+    std::vector<int> height((size_t)nv, 0);
+    int hmax = 0;
+    for (int k = 0; k < nv; ++k) {   // (post-order: children before their parent)
+        const int v = order[(size_t)k], p = parent[(size_t)v];
+        if (p >= 0 && height[(size_t)p] < height[(size_t)v] + 1) height[(size_t)p] = height[(size_t)v] + 1;
+        if (height[(size_t)v] > hmax) hmax = height[(size_t)v];
+    }
+    for (int v = 0; v < nv; ++v) t.push_back(parent[(size_t)v]);
+    for (int v = 0; v < nv; ++v) t.push_back(height[(size_t)v]);
+    auto by_slot = [&](const std::vector<std::vector<int>>& L, bool positions) {   // L indexed by slot, or by schedule position
+        int acc = 0;
+        for (int v = 0; v < nv; ++v) { t.push_back(acc); acc += (int)L[(size_t)(positions ? pos[(size_t)v] : v)].size(); }
+        t.push_back(acc);
+        for (int v = 0; v < nv; ++v) for (int e : L[(size_t)(positions ? pos[(size_t)v] : v)]) t.push_back(e);
+    };
+    // (tree_wave_kernel wants a node's LEAF children first: their sums are taken in one parallel pass right after the leaves' level)
+    std::vector<std::vector<int>> kids_lf((size_t)nv);
+    std::vector<int> nleafkids((size_t)nv, 0);
+    for (int v = 0; v < nv; ++v) {
+        for (int ch : kids[(size_t)v]) if (height[(size_t)ch] == 0) { kids_lf[(size_t)v].push_back(ch); ++nleafkids[(size_t)v]; }
+        for (int ch : kids[(size_t)v]) if (height[(size_t)ch] != 0) kids_lf[(size_t)v].push_back(ch);
+    }
+    by_slot(kids_lf, false); by_slot(re, true); by_slot(pe, true); by_slot(se, true);
+    for (int v = 0; v < nv; ++v) t.push_back(nleafkids[(size_t)v]);
+    // the inner nodes, parents first (tree_wave_kernel sums over children with lane = entry, one inner node after the other)
+    int nu = 0;
+    for (int h = hmax; h >= 1; --h)
+        for (int v = 0; v < nv; ++v) if (height[(size_t)v] == h) { t.push_back(v); ++nu; }
+    A.tsched.nu = nu;
+    {   // a pose's position in the children list just emitted (by_slot(kids_lf)): parents in slot order, a parent's leaf children first
+        std::vector<int> kpos((size_t)nv, -1);
+        int at = 0;
+        for (int v = 0; v < nv; ++v) for (int ch : kids_lf[(size_t)v]) kpos[(size_t)ch] = at++;
+        for (int v = 0; v < nv; ++v) if (kpos[(size_t)v] < 0) kpos[(size_t)v] = at++;   // roots
+        for (int v = 0; v < nv; ++v) t.push_back(kpos[(size_t)v]);
+    }
+    A.tsched.nlev = hmax + 1;
+    A.tsched.max_se3_per_node = 0;
+    A.tsched.max_r_per_node = 0;
+    for (int k = 0; k < nv; ++k) if ((int)se[(size_t)k].size() > A.tsched.max_se3_per_node) A.tsched.max_se3_per_node = (int)se[(size_t)k].size();
+    for (int k = 0; k < nv; ++k) if ((int)re[(size_t)k].size() > A.tsched.max_r_per_node) A.tsched.max_r_per_node = (int)re[(size_t)k].size();
+    A.tsched.nv = nv; A.tsched.nr = nr; A.tsched.np = np; A.tsched.ns = ns; A.tsched.depth = maxdepth + 1; A.tsched.nroots = nroots;
+    return true;
+}
+
+}  // namespace locamd

@@ -1,0 +1,35 @@
+// Structure analysis of a batch of windows, free of any handle state (each pass is described at its definition in window_structure.cpp)
+#pragma once
+#include <vector>
+
+#include "window_kernel.h"
+#include "window_tables.h"
+
+namespace locamd {
+
+// Host-built tables (tree_wave / tree_lm: the elimination schedule; arrow3: row order + packed edge records): build_tree_sched /
+// build_arrow_aux fill the host vectors and the sizes, capi_window.cpp owns the device copies.
+struct WinAux {
+    int32_t* d_tsched = nullptr;
+    size_t tsched_cap = 0;
+    std::vector<int32_t> h_tsched;
+    TreeSched tsched{};
+    int32_t *d_ahdr = nullptr, *d_arslot = nullptr;
+    double *d_arec = nullptr, *d_aprec = nullptr;
+    size_t arec_cap = 0, aprec_cap = 0;   // doubles allocated
+    int arrow_nb_max = 0, arrow_jmax = 0, arrow_jpmax = 0, arrow_list_cap = 0;
+    int arrow_jch[16] = {0}, arrow_jpch[16] = {0};   // records per chunk of 64 rows (the most any row of the chunk has, over the batch)
+    std::vector<int32_t> h_ahdr, h_arslot;
+    std::vector<double> h_arec, h_aprec;
+};
+
+// 0, or the first check that failed: 1 counts exceed the capacities, 2 / 3 range edge (vertex index / poses further apart than bw_max),
+// 4 prior edge vertex index, 5 / 6 SE3 edge (as 2 / 3)
+int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b);
+bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b);
+void chain_scan(const WindowCaps& c, const HostBatch& b, bool ordered, bool& chain, bool& single_pairs, bool& se3_pairs);
+unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const HostBatch& b);
+bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only = false);   // fills A.h_a* and A.arrow_*
+bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);                // fills A.h_tsched and A.tsched's sizes
+
+}  // namespace locamd

@@ -1,0 +1,54 @@
+// The eight tables a batch of windows travels in (window_kernel.h: "Layout of one instance"), described ONCE for the host side:
+// capi_window.cpp allocates, stages, uploads and fetches by this description; a new table or a changed record width is an edit here.
+#pragma once
+#include <cstdint>
+#include <cstring>
+
+#include "window_kernel.h"
+
+namespace locamd {
+
+enum WindowTable { kPoses, kCounts, kRVal, kPVal, kSVal, kRIdx, kPIdx, kSIdx, kWindowTables };   // (the order of the staging blocks)
+
+// bytes of ONE instance in table t
+inline size_t table_bytes(const WindowCaps& c, int t) {
+    const size_t nv = c.nv_max, nr = c.nr_max, np = c.np_max, ns = c.ns_max;
+    const size_t bytes[kWindowTables] = {nv * 12 * sizeof(double), 4 * sizeof(int32_t), nr * 5 * sizeof(double), np * 18 * sizeof(double), ns * 48 * sizeof(double),
+                                         nr * 2 * sizeof(int32_t), np * sizeof(int32_t), ns * 4 * sizeof(int32_t)};
+    return bytes[t];
+}
+
+// a caller's batch: n instances and its eight host arrays (pointers only, nothing is owned)
+struct HostTables { const void* t[kWindowTables]; };
+struct HostBatch {
+    int64_t n;
+    const double* poses; const int32_t* counts; const double *r_val, *p_val, *s_val; const int32_t *r_idx, *p_idx, *s_idx;   // (WindowTable order)
+    HostTables tables() const { return {{poses, counts, r_val, p_val, s_val, r_idx, p_idx, s_idx}}; }
+};
+// where a kernel finds the tables: eight base pointers the device can read (device arrays, or the page-locked staging block)
+struct DeviceTables { void* t[kWindowTables]; };
+
+// One block for n instances: up to three prefix pieces, then the tables from first_table on in WindowTable order, every piece 16-byte
+// aligned; offsets of the pieces and the block's size.  The covariance pass has [cov | mask | status] in front of all eight tables.  The
+// solve's prefix is [poses | result], which come back as one copy, in front of the tables from kCounts on: tab[kPoses] = pre[0] = 0.
+struct BlockLayout { size_t pre[3], tab[kWindowTables], end; };
+inline BlockLayout pack_block(const WindowCaps& c, size_t n, const size_t* prefix_bytes, int n_prefix, int first_table) {
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    BlockLayout L{};
+    for (int k = 0; k < n_prefix; ++k) { L.pre[k] = L.end; L.end += al(prefix_bytes[k]); }
+    for (int t = first_table; t < kWindowTables; ++t) { L.tab[t] = L.end; L.end += al(n * table_bytes(c, t)); }
+    return L;
+}
+inline DeviceTables tables_at(char* base, const BlockLayout& L) {
+    DeviceTables d;
+    for (int t = 0; t < kWindowTables; ++t) d.t[t] = base + L.tab[t];
+    return d;
+}
+// the batch into the host side of a block
+inline void stage_tables(char* h, const BlockLayout& L, const WindowCaps& c, const HostBatch& b) {
+    const HostTables src = b.tables();
+    for (int t = 0; t < kWindowTables; ++t)
+        if (const size_t bytes = (size_t)b.n * table_bytes(c, t)) std::memcpy(h + L.tab[t], src.t[t], bytes);
+}
+
+}  // namespace locamd
