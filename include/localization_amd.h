@@ -27,7 +27,7 @@ extern "C" {
                            * 3: numeric (g2o) Jacobians are the default everywhere, loc_shard_*, loc_window_last_kernel_kind;
                            * 4: loc_window_set_option / _last_host_timing, loc_node_flush_tail / _last_kernel_kind, loc_fusion_timing_*;
                            *    a large loc_window_solve_host drops the resident batch;
-                           *    (additive, same version) loc_window_covariance_host / _resident / loc_window_last_covariance_ms;
+                           *    (additive, same version) loc_window_covariance_host / _resident / loc_window_last_covariance_ms / loc_window_covariance_plan;
                            *    (additive, same version) loc_snapshot_solve_device_cov / _host_kmb_cov, loc_fusion_solve_device_cov / _host_kmb_cov */
 
 typedef enum loc_status {
@@ -291,6 +291,8 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *   "topology_cache"   1 (default) / 0: reuse the structural verdict of the previous batch when counts and index tables hash the same
  *   "kernel_events"    1 (default; LOCAMD_KERNEL_EVENTS) / 0: no HIP events around the launch of a zero-copy solve (a handful of small windows);
  *                      loc_window_last_kernel_ms then reports launch-to-completion on the host clock.  The node's own handle runs with 0.
+ *   "covariance_general"  0 (default) / 1: loc_window_covariance_* also serve the batches their three structured passes decline (see there);
+ *                      looked at per call; a resident batch classified under one value is classified again after a change
  * LOC_ERR_INVALID for an unknown name or value. */
 int loc_window_set_option(loc_window* w, const char* name, int64_t value);
 /* Host-side cost of the last loc_window_solve_host call, milliseconds: [0] argument validation, [1] structure analysis (kernel
@@ -315,7 +317,7 @@ void* loc_window_poses_device(loc_window* w);   /* double [B][nv_max][12] */
 void* loc_window_result_device(loc_window* w);  /* double [B][8] */
 int loc_window_timing_begin(loc_window* w, int32_t max_launches);
 int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, double* avg_ms);
-/* Marginal pose covariances of CHAIN windows and of ARROWHEAD and FOREST batches: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
+/* Marginal pose covariances of CHAIN windows, of ARROWHEAD and FOREST batches and (option "covariance_general") of windows of any structure: for window b with estimate x, H = sum_e J_e^T (rho'_e Omega_e) J_e evaluated AT x
  * (rho'_e = 1 / (1 + chi2_e) on every range edge and on every EdgeSE3 whose robust flag is set — g2o's robustInformation without rho''; priors
  * not robustified; range Jacobians in the handle's mode, loc_window_set_jacobian; no LM damping), in g2o VertexSE3's minimal coordinates
  * [dt (body frame), dq_xyz] applied as x * fromVectorMQT(d); Sigma_i = [H^-1]_ii.  Unlike g2o's computeMarginals (which re-factors the H of the
@@ -341,7 +343,17 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
  *   - forests (nv_max <= 64), iff the handle would solve the batch on a forest kernel: option "tree" != 0, n at least the forest threshold (256 windows, or
  *     the chain threshold where loc_window_set_chain_threshold lowered it: 1 serves a single window), every window the same counts and index
  *     tables, 2 <= nv <= 64, and the pose-to-pose edges form a forest (several edges per pair, either direction, several trees, isolated
- *     poses).  Always 6x6 blocks.  A tree that no range, prior or lever arm ties to the world is singular (LOC_ERR_SINGULAR for its window).
+ *     poses).  Always 6x6 blocks.  A tree that no range, prior or lever arm ties to the world is singular (LOC_ERR_SINGULAR for its window);
+ *   - with loc_window_set_option(w, "covariance_general", 1) — default 0: the three tests above and nothing else, bit for bit — ANY batch the
+ *     tests above leave: chains and forests of more than 64 poses, ragged or mixed batches (another graph in every window), 6-DoF arrowheads,
+ *     windows with loops (an EdgeSE3 or a range that closes a cycle), any nv_max the handle takes.  Batches the tests above take keep their
+ *     kernels and their bits.  Always 6x6 blocks (a translation-only window gets its rotation bits from the exactly-zero rule).  One workgroup
+ *     per window: a block LDL^T with selected inversion on the ENVELOPE of the matrix IN THE CALLER'S POSE ORDER — pose slot i keeps the
+ *     blocks from the smallest slot an edge joins it to up to itself; there is no reordering, so work and memory depend on the slot order as
+ *     with loc_window_set_ordering(natural): a star packed leaves-first (as loc_node_* packs its key-frame windows) costs 2n - 1 blocks, the
+ *     same star packed key-first n (n + 1) / 2.  The envelopes live in a device workspace of the handle, allocated on first use and grown on
+ *     demand (a failed allocation is LOC_ERR_HIP); loc_window_covariance_plan reports its size beforehand.
+ *     Windows with endpoint-1 lever arms stay LOC_ERR_UNSUPPORTED under either value of the option.
  * Stateless: does not change the handle's resident batch, last kernel kind / ms, topology cache or options.  Synchronous.  Small calls (inputs
  * and outputs within the 4 MiB staging block) travel as loc_window_solve_host's small ones do; larger ones stage through a device block of
  * their own — unlike a large loc_window_solve_host they leave the resident batch intact. */
@@ -352,9 +364,20 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
  * asynchronous on hip_stream (NULL = the handle's own stream; it waits for the last resident launch), into caller-owned device arrays of the
  * layouts above.  LOC_ERR_INVALID before the first resident solve of an upload.  The batch's structure is checked once per upload: an upload
  * that loc_window_upload classified as a chain or as a forest (whose schedule, already on the device, the pass walks) needs nothing more;
- * for any other upload the first call copies the uploaded tables back, classifies them (chain, then forest under the rule above, into
- * tables of the covariance's own) and is synchronous. */
+ * for any other upload the first call copies the uploaded tables back, classifies them (chain, then arrowhead and forest under the rules above,
+ * into tables of the covariance's own, then the envelope pass where option "covariance_general" is 1) and is synchronous.  A batch held by
+ * the envelope pass is classified again (one more synchronous call) when option "arrow3", option "tree" or the forest threshold has changed
+ * since: the resident batch always takes the pass loc_window_covariance_host would take for the same tables. */
 int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev);
+/* What the envelope pass (option "covariance_general") would allocate for this batch, from the structure alone: no device, no handle.
+ * counts / r_idx / s_idx as loc_window_solve_host takes them (r_idx may be NULL when caps->nr_max is 0, s_idx likewise).
+ *   blocks_max       the largest envelope of the batch in 6x6 blocks: over a window's pose slots i, the sum of i - first(i) + 1, first(i) = the
+ *                    smallest slot a pose-to-pose edge (a range between two poses, an EdgeSE3) joins to slot i, i itself without one
+ *   workspace_bytes  n * ((blocks_max + nv_max) * 36 + nv_max * 6) * 8: every window's envelope, one column of it and diag(H)
+ * so that a caller can choose a slot order, or refuse, before touching the device.  LOC_ERR_INVALID: a count beyond the capacities or an
+ * edge index outside its window. */
+int loc_window_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
+                               int64_t* blocks_max, size_t* workspace_bytes);
 /* kernel time of the last covariance launch of this handle (HIP events on its stream; a resident launch is waited for), milliseconds */
 int loc_window_last_covariance_ms(loc_window* w, double* ms);
 

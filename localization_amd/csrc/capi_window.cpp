@@ -64,6 +64,7 @@ struct loc_window {
         int arrow3 = -1;                   // LOCAMD_ARROW3: -1 default (windows of more than 64 poses), 0 never, 1 whenever the batch qualifies
         int tree = -1;                     // LOCAMD_TREE: -1 default, 0 never, 2 the lane-per-window variant
         bool wave3 = true, wave6 = true, chain3 = true, zero_copy = true, topology_cache = true;
+        bool cov_general = false;          // "covariance_general" 1: whatever the three structured covariance passes decline goes to envelope_covariance_kernel.hip
         bool kernel_events = true;         // "kernel_events" 0: no HIP events around the launch of a zero-copy solve (loc_window_last_kernel_ms then reports launch-to-completion on the host clock)
     } opt;
     // structural verdict of the last host-path batch, keyed on a hash of (n, counts, index tables): a caller that replays one graph
@@ -92,7 +93,8 @@ struct loc_window {
     bool cov_pending = false;       // the events of a resident covariance launch have not been read yet
     double cov_ms = 0.0;
     int resident_cov = 0;           // 3 / 6: the resident chain batch's block size; kCovForest / kCovForestOwn: a forest batch on aux[1]'s /
-                                    // cov_aux[1]'s schedule; kCovArrow: an arrowhead batch; 0: not a covariance batch; -1: not classified yet
+                                    // cov_aux[1]'s schedule; kCovArrow: an arrowhead batch; kCovEnvelope: none of these, taken by the envelope
+                                    // pass (option "covariance_general"); 0: not a covariance batch; -1: not classified yet
     // forest batches (forest_covariance_kernel.hip): the schedules the covariance pass builds itself — [0] for loc_window_covariance_host
     // (kept with the hash of the structure it was built for), [1] for a resident batch no solve classified as a forest.  Never aux[0] /
     // aux[1]: the host path's topology cache and the resident solve rely on those.
@@ -103,13 +105,20 @@ struct loc_window {
     size_t cov_ws_cap[2] = {0, 0};   // doubles
     int cov_list_cap[2] = {0, 0};    // list size the batch was classified with
     locamd::WinAux cov_aux[2];
+    // any other batch (envelope_covariance_kernel.hip, option "covariance_general"): the kernel's HBM workspace (the envelope of every window,
+    // one column, diag(H)), one for the host path and one for the resident batch, grown on demand; the batch's largest envelope in blocks
+    double* d_env_ws[2] = {nullptr, nullptr};
+    size_t env_ws_cap[2] = {0, 0};   // doubles
+    long long env_blocks[2] = {0, 0};
+    long long env_switches = 0;      // cov_switches() when the resident batch was handed to the envelope pass: a change of the switches the three
+                                     // structured tests read classifies it again
     bool cov_sched_valid = false;
     unsigned long long cov_sched_key = 0;
     int64_t cov_sched_n = 0;
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
-static constexpr int kCovForest = 7, kCovForestOwn = 8, kCovArrow = 9;   // loc_window::resident_cov
+static constexpr int kCovForest = 7, kCovForestOwn = 8, kCovArrow = 9, kCovEnvelope = 10;   // loc_window::resident_cov
 
 extern "C" {
 
@@ -135,7 +144,7 @@ int loc_window_destroy(loc_window* w) {
                     w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_tree_ws, w->d_arrow_ws,
                     w->aux[0].d_tsched, w->aux[0].d_ahdr, w->aux[0].d_arslot, w->aux[0].d_arec, w->aux[0].d_aprec,
                     w->aux[1].d_tsched, w->aux[1].d_ahdr, w->aux[1].d_arslot, w->aux[1].d_arec, w->aux[1].d_aprec,
-                    w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched, w->d_cov_ws[0], w->d_cov_ws[1]};
+                    w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched, w->d_cov_ws[0], w->d_cov_ws[1], w->d_env_ws[0], w->d_env_ws[1]};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
     for (hipEvent_t e : w->ev) (void)hipEventDestroy(e);
@@ -443,7 +452,7 @@ static int pick_kernel(const loc_window* w, int64_t n, int topology) {
 //    tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `own`, which the caller then sends
 //    to the device (need_upload).  keyed (the host path): the set is kept with the hash of the structure it was built for, and a batch of
 //    the same structure reuses it, device copy included.
-static int covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::WinAux* own, bool keyed, bool& need_upload) {
+static int structured_covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::WinAux* own, bool keyed, bool& need_upload) {
     const locamd::WindowCaps& c = w->caps;
     need_upload = false;
     if (w->has_off1) return 0;
@@ -473,6 +482,32 @@ static int covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::Wi
     if (!locamd::build_tree_sched(c, w->has_off1, b, *own)) return 0;
     need_upload = true;
     return kCovForestOwn;
+}
+// the switches structured_covariance_kind reads besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold)
+static long long cov_switches(const loc_window* w) {
+    const long long mn = tree_min_batch(w);
+    return ((long long)(w->opt.arrow3 + 1) << 4 | (long long)(w->opt.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8);
+}
+// 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is kCovEnvelope —
+//    envelope_covariance_kernel.hip in the caller's pose order; the batch's largest envelope goes to w->env_blocks[keyed ? 0 : 1].
+static int covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::WinAux* own, bool keyed, bool& need_upload) {
+    const int kind = structured_covariance_kind(w, b, own, keyed, need_upload);
+    if (kind || w->has_off1 || !w->opt.cov_general) return kind;
+    if (locamd::window_envelope_covariance_lds_bytes(w->caps) > 160 * 1024) return 0;
+    const long long blocks = locamd::envelope_blocks_max(w->caps, b);
+    if (blocks < 0) return 0;   // (cannot happen: the tables were validated)
+    w->env_blocks[keyed ? 0 : 1] = blocks;
+    return kCovEnvelope;
+}
+// the envelope pass's workspace for n windows of at most `blocks` envelope blocks (which: 0 the host path's, 1 the resident batch's)
+static hipError_t grow_env_workspace(loc_window* w, int which, int64_t n, long long blocks) {
+    const size_t need = (size_t)n * locamd::window_envelope_covariance_workspace_doubles(w->caps, blocks);
+    if (w->env_ws_cap[which] >= need) return hipSuccess;
+    if (w->d_env_ws[which]) (void)hipFree(w->d_env_ws[which]);
+    w->d_env_ws[which] = nullptr; w->env_ws_cap[which] = 0;
+    hipError_t e = hipMalloc((void**)&w->d_env_ws[which], need * sizeof(double));
+    if (e == hipSuccess) w->env_ws_cap[which] = need;
+    return e;
 }
 // the arrowhead pass's workspace for n windows with lists of `cap` entries (which: 0 the host path's, 1 the resident batch's)
 static hipError_t grow_cov_workspace(loc_window* w, int which, int64_t n, int cap) {
@@ -563,6 +598,13 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
     if (k == "chain3") return flag(o.chain3);
     if (k == "zero_copy") return flag(o.zero_copy);
     if (k == "kernel_events") return flag(o.kernel_events);
+    if (k == "covariance_general") {
+        const bool before = o.cov_general;
+        const int rc = flag(o.cov_general);
+        // a resident batch the other value refused, or handed to the envelope pass, is classified again by the next covariance call
+        if (rc == LOC_OK && before != o.cov_general && w->n_resident > 0 && (w->resident_cov == 0 || w->resident_cov == kCovEnvelope)) w->resident_cov = -1;
+        return rc;
+    }
     if (k == "topology_cache") { w->topo_cache.valid = false; return flag(o.topology_cache); }
     return locamd_fail(LOC_ERR_INVALID, "set_option: unknown option name");
 }
@@ -809,12 +851,14 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
 
 // ---- marginal covariances (covariance_kernel.hip: chains; arrow_covariance_kernel.hip: arrowheads; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
 #define LOC_COV_UNSUPPORTED ": every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle solves on arrow3_lm_kernel (option arrow3), " \
-                            "or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold); no endpoint-1 lever arms"
+                            "or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold), " \
+                            "or option covariance_general must be 1 (any structure and length, in the caller's pose order); no endpoint-1 lever arms"
 
 // the pass of a batch of covariance_kind's `kind`; which: 0 = loc_window_covariance_host's table set and workspace, 1 = the resident batch's
 // (a forest that loc_window_upload classified, kCovForest, walks the solve's schedule aux[1]; kCovForestOwn the covariance's own)
 static hipError_t launch_covariance(loc_window* w, int which, int kind, const locamd::WindowArgs& a, double* cov, int32_t* mask, int32_t* status, hipStream_t st) {
     if (kind == kCovArrow) return locamd::launch_window_arrow_covariance(a, w->d_cov_ws[which], w->cov_list_cap[which], cov, mask, status, st);
+    if (kind == kCovEnvelope) return locamd::launch_window_envelope_covariance(a, w->d_env_ws[which], w->env_blocks[which], cov, mask, status, st);
     if (kind == kCovForest) return locamd::launch_window_forest_covariance(a, w->aux[1].tsched, cov, mask, status, st);
     if (kind == kCovForestOwn) return locamd::launch_window_forest_covariance(a, w->cov_aux[which].tsched, cov, mask, status, st);
     return locamd::launch_window_covariance(a, kind == 3, cov, mask, status, st);
@@ -831,6 +875,7 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     const locamd::WindowCaps& c = w->caps;
     LOC_HIP(hipSetDevice(w->device));
     if (kind == kCovArrow) LOC_HIP(grow_cov_workspace(w, 0, n, w->cov_list_cap[0]));
+    if (kind == kCovEnvelope) LOC_HIP(grow_env_workspace(w, 0, n, w->env_blocks[0]));
     if (sched_upload) {
         LOC_HIP(upload_tree_sched(w, w->cov_aux[0], w->stream, false));
         w->cov_sched_valid = true;
@@ -885,6 +930,20 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
     if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
     LOC_HIP(hipSetDevice(w->device));
+    // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
+    // (an arrowhead batch likewise while option "arrow3" still admits it; the envelope pass while option "covariance_general" is 1)
+    auto refused = [&] {
+        const bool forest = w->resident_cov == kCovForest || w->resident_cov == kCovForestOwn;
+        const bool arrow = w->resident_cov == kCovArrow, envelope = w->resident_cov == kCovEnvelope;
+        return w->has_off1 || (w->caps.nv_max > 64 && !arrow && !envelope) || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)) ||
+               (arrow && (!arrow3_wanted(w) || locamd::window_arrow_covariance_lds_bytes(w->caps) > 160 * 1024)) || (envelope && !w->opt.cov_general);
+    };
+    // (option "covariance_general": a structured verdict the handle's switches no longer admit is no verdict — the batch is classified under
+    //  the switches as they are now, and lands on the envelope pass)
+    if (w->resident_cov > 0 && w->resident_cov != kCovEnvelope && w->opt.cov_general && !w->has_off1 && refused()) w->resident_cov = -1;
+    // (and the other way round: the envelope pass holds the batch only while the three structured tests would still decline it — they are
+    //  run again when a switch they read has changed, so that the resident batch takes the pass loc_window_covariance_host takes)
+    if (w->resident_cov == kCovEnvelope && w->env_switches != cov_switches(w)) w->resident_cov = -1;
     if (w->resident_cov < 0 && !w->has_off1) {
         // first call on an upload no solve kernel classified as a chain: the uploaded tables come back once and are scanned on the host
         if (int rc = wait_resident(w)) return rc;
@@ -900,14 +959,14 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
         const int kind = covariance_kind(w, b, &w->cov_aux[1], false, sched_upload);
         if (sched_upload) LOC_HIP(upload_tree_sched(w, w->cov_aux[1], w->stream, false));
         w->resident_cov = kind;
+        w->env_switches = cov_switches(w);
     }
-    // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
-    // (an arrowhead batch likewise while option "arrow3" still admits it)
-    const bool forest = w->resident_cov == kCovForest || w->resident_cov == kCovForestOwn;
+    if (refused()) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
     const bool arrow = w->resident_cov == kCovArrow;
-    if (w->has_off1 || (w->caps.nv_max > 64 && !arrow) || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)) ||
-        (arrow && (!arrow3_wanted(w) || locamd::window_arrow_covariance_lds_bytes(w->caps) > 160 * 1024)))
-        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
+    if (w->resident_cov == kCovEnvelope && w->env_ws_cap[1] < (size_t)w->n_resident * locamd::window_envelope_covariance_workspace_doubles(w->caps, w->env_blocks[1])) {
+        if (int rc = wait_resident(w)) return rc;   // (as below)
+        LOC_HIP(grow_env_workspace(w, 1, w->n_resident, w->env_blocks[1]));
+    }
     if (arrow && w->cov_ws_cap[1] < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, w->cov_list_cap[1])) {
         if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
         LOC_HIP(grow_cov_workspace(w, 1, w->n_resident, w->cov_list_cap[1]));
@@ -924,6 +983,21 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     LOC_HIP(hipEventRecord(w->resident_done, st));
     w->resident_inflight = true;
     w->cov_pending = true;
+    return LOC_OK;
+}
+
+int loc_window_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
+                               int64_t* blocks_max, size_t* workspace_bytes) {
+    if (!caps || n <= 0 || !counts || !blocks_max || !workspace_bytes) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_plan arguments");
+    if (caps->nv_max <= 0 || caps->nv_max > 4096 || caps->nr_max < 0 || caps->np_max < 0 || caps->ns_max < 0)
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "window capacities (1 <= nv_max <= 4096)");
+    if ((caps->nr_max && !r_idx) || (caps->ns_max && !s_idx)) return locamd_fail(LOC_ERR_INVALID, "missing edge arrays");
+    const locamd::WindowCaps c = to_caps(caps);
+    const locamd::HostBatch b{n, nullptr, counts, nullptr, nullptr, nullptr, r_idx, nullptr, s_idx};
+    const long long blocks = locamd::envelope_blocks_max(c, b);
+    if (blocks < 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_plan: counts exceed capacities, or an edge vertex index is out of range");
+    *blocks_max = blocks;
+    *workspace_bytes = (size_t)n * locamd::window_envelope_covariance_workspace_doubles(c, blocks) * sizeof(double);
     return LOC_OK;
 }
 

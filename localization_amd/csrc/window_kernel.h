@@ -139,6 +139,13 @@ size_t window_arrow_covariance_lds_bytes(const WindowCaps& c);
 size_t window_arrow_covariance_workspace_doubles(const WindowCaps& c, int cap);
 hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
 
+// the same for windows of any structure and length (envelope_covariance_kernel.hip: what the three passes above decline), one workgroup per
+// window, 6x6 blocks, block LDL^T and selected inversion on the envelope of the caller's pose order.  blocks: the batch's largest envelope
+// (window_structure.cpp: envelope_blocks_max); ws: [B][window_envelope_covariance_workspace_doubles] in HBM (the envelope, one column, diag(H))
+size_t window_envelope_covariance_lds_bytes(const WindowCaps& c);
+size_t window_envelope_covariance_workspace_doubles(const WindowCaps& c, long long blocks);
+hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

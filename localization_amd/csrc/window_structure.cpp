@@ -159,6 +159,46 @@ unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const Host
     return h;
 }
 
+// The envelope (skyline) of every instance's block matrix in the caller's pose order, as envelope_covariance_kernel.hip lays it out: row i
+// holds the blocks (i, first[i]) .. (i, i).  Returns the largest block count of the batch, -1 when a count or an index is out of range
+// (loc_window_covariance_plan calls this on tables no handle has validated).
+long long envelope_blocks_max(const WindowCaps& c, const HostBatch& b) {
+    std::atomic<long long> most{0};
+    std::atomic<bool> bad{false};
+    parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int) {
+        std::vector<int32_t> first;
+        long long most_l = 0;
+        for (int64_t i = lo; i < hi; ++i) {
+            const int32_t* cn = b.counts + i * 4;
+            const int nv = cn[0], nr = cn[1], ns = cn[3];
+            if (nv < 0 || nv > c.nv_max || nr < 0 || nr > c.nr_max || ns < 0 || ns > c.ns_max) { bad.store(true); return; }
+            first.resize((size_t)nv);
+            for (int v = 0; v < nv; ++v) first[(size_t)v] = v;
+            auto join = [&](int v0, int v1) {
+                if (v0 < 0 || v0 >= nv || v1 >= nv) return false;
+                if (v1 < 0) return true;   // a fixed endpoint
+                const int up = v0 > v1 ? v0 : v1, dn = v0 > v1 ? v1 : v0;
+                if (dn < first[(size_t)up]) first[(size_t)up] = dn;
+                return true;
+            };
+            for (int e = 0; e < nr; ++e) {
+                const int32_t* ix = b.r_idx + ((size_t)i * c.nr_max + e) * 2;
+                if (!join(ix[0], ix[1])) { bad.store(true); return; }
+            }
+            for (int e = 0; e < ns; ++e) {
+                const int32_t* ix = b.s_idx + ((size_t)i * c.ns_max + e) * 4;
+                if (ix[1] < 0 || !join(ix[0], ix[1])) { bad.store(true); return; }
+            }
+            long long blocks = 0;
+            for (int v = 0; v < nv; ++v) blocks += v - first[(size_t)v] + 1;
+            if (blocks > most_l) most_l = blocks;
+        }
+        long long seen = most.load();
+        while (most_l > seen && !most.compare_exchange_weak(seen, most_l)) {}
+    });
+    return bad.load() ? -1 : most.load();
+}
+
 // CHAIN + BORDER ("arrowhead": BASELINE config 4, anchor self-calibration — a tag trajectory whose poses range to a few nodes that
 // are unknowns themselves, localization.cpp:94-98).  The border of an instance = its last nb0 pose slots, nb0 = the smallest number
 // such that every pose-to-pose edge between NON-consecutive slots has an endpoint there; the other poses form the chain (one edge

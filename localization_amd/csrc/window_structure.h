@@ -29,6 +29,9 @@ int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b);
 bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b);
 void chain_scan(const WindowCaps& c, const HostBatch& b, bool ordered, bool& chain, bool& single_pairs, bool& se3_pairs);
 unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const HostBatch& b);
+// the largest number of envelope blocks any instance has (envelope_covariance_kernel.hip's profile: sum over the pose slots i of
+// i - first[i] + 1, first[i] = the smallest slot a pose-to-pose edge joins to i); reads counts, r_idx and s_idx alone; -1: an index out of range
+long long envelope_blocks_max(const WindowCaps& c, const HostBatch& b);
 bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only = false);   // fills A.h_a* and A.arrow_*
 bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);                // fills A.h_tsched and A.tsched's sizes
 

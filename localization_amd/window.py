@@ -74,6 +74,17 @@ class WindowBatch:
         return self.poses[i, v, :9].reshape(3, 3).copy(), self.poses[i, v, 9:].copy()
 
 
+def covariance_plan(wb: WindowBatch):
+    """(blocks_max, workspace_bytes) of loc_window_covariance_plan: the largest envelope of wb's windows in 6x6 blocks, in their pose
+    order, and the device workspace the envelope pass (option "covariance_general") allocates for the batch.  Host only: no device."""
+    ip = C.POINTER(C.c_int32)
+    caps = WindowCaps(*wb.caps, -1)
+    blocks, nbytes = C.c_int64(), C.c_size_t()
+    check(lib().loc_window_covariance_plan(C.byref(caps), wb.B, wb.counts.ctypes.data_as(ip), wb.r_idx.ctypes.data_as(ip),
+                                           wb.s_idx.ctypes.data_as(ip), C.byref(blocks), C.byref(nbytes)))
+    return blocks.value, nbytes.value
+
+
 class WindowSolver:
     def __init__(self, anchors, batch, nv_max, nr_max, np_max=0, ns_max=0, maximum_iteration=10, device=0, bw_max=-1,
                  jacobian="numeric", natural_order=False, chain_threshold=None):
@@ -146,7 +157,8 @@ class WindowSolver:
         """Sigma_i = [H^-1]_ii of every pose of every window at wb.poses: chain windows of <= 64 poses, arrowhead batches (anchor
         self-calibration; the unknown anchors are the last pose slots) whenever the handle would solve them on arrow3_lm_kernel (option
         "arrow3"; by default handles of more than 64 poses), and forest batches (one shared topology, <= 64 poses) whenever the handle
-        would solve them on a forest kernel (option "tree", batch threshold).  Returns (cov [B][nv_max][6][6],
+        would solve them on a forest kernel (option "tree", batch threshold); with set_option("covariance_general", 1) any other batch
+        as well, on the envelope pass in the caller's pose order (covariance_plan reports its memory).  Returns (cov [B][nv_max][6][6],
         mask [B][nv_max] — excluded coordinates, bits 0-5 = tx ty tz qx qy qz —, status [B]: 0 or LOC_ERR_SINGULAR, that window's blocks NaN)."""
         assert wb.caps == self.caps and wb.B <= self.B
         if getattr(wb, "r_off1", None) is not None:   # (refused here: the handle's endpoint-1 lever arms belong to its solves and stay as they are)
@@ -174,6 +186,11 @@ class WindowSolver:
         st = None if stream is None else C.c_void_p(stream.cuda_stream)
         check(self.L.loc_window_covariance_resident(self.h, st, C.c_void_p(cov.data_ptr()), C.c_void_p(mask.data_ptr()),
                                                     C.c_void_p(status.data_ptr())))
+
+    def covariance_plan(self, wb: WindowBatch):
+        """covariance_plan(wb) for this handle's capacities"""
+        assert wb.caps == self.caps
+        return covariance_plan(wb)
 
     def last_covariance_ms(self):
         ms = C.c_double()
@@ -203,7 +220,8 @@ class WindowSolver:
 
     def set_option(self, name, value):
         """loc_window_set_option: the kernel-selection switches of this handle ("chain_min_batch", "arrow3", "tree", "wave3", "wave6",
-        "chain3", "zero_copy", "topology_cache")"""
+        "chain3", "zero_copy", "topology_cache", "kernel_events"; "covariance_general": 1 = covariance() / covariance_resident() also serve
+        the batches the chain, arrowhead and forest passes decline, default 0)"""
         self.L.loc_window_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
 
