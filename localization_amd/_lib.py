@@ -24,6 +24,11 @@ class SnapshotParams(C.Structure):
                 ("lanes_per_instance", C.c_int32), ("block_threads", C.c_int32)]
 
 
+class FusionParams(C.Structure):
+    _fields_ = [("maximum_iteration", C.c_int32), ("distance_outlier", C.c_double), ("gate_warmup_epochs", C.c_int32),
+                ("antenna_offset", C.c_double * 3), ("block_threads", C.c_int32), ("jacobian", C.c_int32)]
+
+
 def library_path():
     return _SO
 
@@ -87,8 +92,6 @@ def lib():
     L.loc_snapshot_solve_host_kmb.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
     L.loc_snapshot_solve_device_cov.argtypes = [vp, C.c_int32] + [vp] * 9
     L.loc_snapshot_solve_host_kmb_cov.argtypes = [vp, C.c_int32] + [vp] * 8
-    L.loc_fusion_solve_device_cov.argtypes = [vp, C.c_int32] + [vp] * 10
-    L.loc_fusion_solve_host_kmb_cov.argtypes = [vp, C.c_int32] + [vp] * 9
     L.loc_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.loc_host_free.argtypes = [vp]
     L.loc_snapshot_timing_begin.argtypes = [vp, C.c_int32]
@@ -116,6 +119,20 @@ def lib():
     L.loc_window_covariance_resident.argtypes = [vp, vp, vp, vp, vp]
     L.loc_window_last_covariance_ms.argtypes = [vp, dp]
     L.loc_window_covariance_plan.argtypes = [vp, C.c_int64, ip, ip, ip, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
+    L.loc_window_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
+    L.loc_fusion_default_params.argtypes = [C.POINTER(FusionParams)]; L.loc_fusion_default_params.restype = None
+    L.loc_fusion_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int64, C.c_int32, dp, C.POINTER(FusionParams)]
+    L.loc_fusion_destroy.argtypes = [vp]
+    L.loc_fusion_set_poses.argtypes = [vp, dp]
+    L.loc_fusion_get_poses.argtypes = [vp, dp]
+    L.loc_fusion_solve_device.argtypes = [vp, C.c_int32] + [vp] * 7
+    L.loc_fusion_solve_device_cov.argtypes = [vp, C.c_int32] + [vp] * 10
+    L.loc_fusion_solve_host.argtypes = [vp, C.c_int32, fp, fp, dp, dp, dp, C.POINTER(C.c_uint8)]
+    L.loc_fusion_solve_host_kmb.argtypes = [vp, C.c_int32] + [vp] * 6
+    L.loc_fusion_solve_host_kmb_cov.argtypes = [vp, C.c_int32] + [vp] * 9
+    L.loc_fusion_last_kernel_ms.argtypes = [vp, dp]
+    L.loc_fusion_timing_begin.argtypes = [vp, C.c_int32]
+    L.loc_fusion_timing_end.argtypes = [vp, ip, dp, dp]
     _LIB = L
     return L
 
@@ -147,3 +164,92 @@ def abi_version():
 
 def device_count():
     return lib().loc_device_count()
+
+
+class Handle:
+    """What the three solver classes share: the lifetime of a loc_<kind>_* handle (self.h, self.L; _prefix names the kind) and the
+    HIP-event timing of its launches."""
+    _prefix = None   # "loc_snapshot" / "loc_fusion" / "loc_window"
+
+    def _fn(self, name):
+        return getattr(self.L, f"{self._prefix}_{name}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- HIP-event kernel timing -------------------------------------------------------------------
+    def timing_begin(self, max_launches):
+        check(self._fn("timing_begin")(self.h, int(max_launches)))
+
+    def timing_end(self):
+        n = C.c_int32(); tot = C.c_double(); avg = C.c_double()
+        check(self._fn("timing_end")(self.h, C.byref(n), C.byref(tot), C.byref(avg)))
+        return n.value, tot.value, avg.value
+
+
+class EpochSolver(Handle):
+    """The snapshot and fusion solvers (self.B tags on GPU self.device): page-locked host arrays that live as long as the handle,
+    and the per-update outputs — the state is [K][n_state][B], a covariance [K][n_cov][B]."""
+
+    def close(self):
+        if getattr(self, "h", None):
+            for p in getattr(self, "_pinned", []):
+                self.L.loc_host_free(p)
+            self._pinned = []
+        super().close()
+
+    def pinned(self, shape, dtype):
+        """A page-locked numpy array (loc_host_alloc); freed when the solver is closed."""
+        import numpy as np
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        p = C.c_void_p()
+        check(self.L.loc_host_alloc(C.byref(p), n))
+        self._pinned = getattr(self, "_pinned", []) + [p]
+        return np.frombuffer((C.c_char * n).from_address(p.value), dtype=dtype).reshape(shape)
+
+    def _device_outputs(self, K, n_state, n_cov, trials, covariance):
+        """(state, chi2, trials) device tensors; with covariance also (cov f64, mask [K][B] i32, status [K][B] i32)"""
+        import torch as t
+        dev = t.device("cuda", self.device)
+        out = (t.empty((K, n_state, self.B), dtype=t.float64, device=dev), t.empty((K, self.B), dtype=t.float64, device=dev),
+               t.empty((K, self.B), dtype=t.uint8, device=dev) if trials else None)
+        if covariance:
+            out += (t.empty((K, n_cov, self.B), dtype=t.float64, device=dev),) + tuple(t.empty((K, self.B), dtype=t.int32, device=dev) for _ in range(2))
+        return out
+
+    def _host_outputs(self, K, n_state, n_cov, covariance):
+        import numpy as np
+        out = (np.empty((K, n_state, self.B)), np.empty((K, self.B)), np.empty((K, self.B), dtype=np.uint8))
+        if covariance:
+            out += (np.empty((K, n_cov, self.B)), np.empty((K, self.B), dtype=np.int32), np.empty((K, self.B), dtype=np.int32))
+        return out
+
+    def _cov_device_args(self, outs, K, n_cov, dev):
+        """all three covariance output tensors or none: their device pointers, [] if none"""
+        import torch as t
+        given = [x is not None for x in outs]
+        if not any(given):
+            return []
+        if not all(given):
+            raise ValueError("out_cov, out_cov_mask and out_cov_status go together: pass all three or none")
+        cov, mask, status = outs
+        assert tuple(cov.shape) == (K, n_cov, self.B) and cov.dtype == t.float64 and cov.is_contiguous() and cov.device == dev
+        for x in (mask, status):
+            assert tuple(x.shape) == (K, self.B) and x.dtype == t.int32 and x.is_contiguous() and x.device == dev
+        return [cov.data_ptr(), mask.data_ptr(), status.data_ptr()]
+
+    def _cov_host_args(self, outs, K, n_cov):
+        import numpy as np
+        cov, mask, status = outs
+        assert cov.shape == (K, n_cov, self.B) and cov.dtype == np.float64 and cov.flags.c_contiguous
+        for x in (mask, status):
+            assert x.shape == (K, self.B) and x.dtype == np.int32 and x.flags.c_contiguous
+        return [cov.ctypes.data, mask.ctypes.data, status.ctypes.data]

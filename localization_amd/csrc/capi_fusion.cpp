@@ -1,23 +1,12 @@
 // C ABI of the batched fusion snapshot solver (BASELINE config 3). Host side only.
-#include "../../include/localization_amd.h"
-
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
 
+#include "capi_host.h"
 #include "fusion_kernel.h"
 #include "snapshot_kernel.h"  // launch_pack_kmb
-
-extern int locamd_fail(int code, const char* what);
-extern int locamd_fail_hip(hipError_t e, const char* where);
-#define LOC_HIP(expr)                                              \
-    do {                                                           \
-        hipError_t _e = (expr);                                    \
-        if (_e != hipSuccess) return locamd_fail_hip(_e, #expr);   \
-    } while (0)
 
 struct loc_fusion {
     int device = 0;
@@ -26,34 +15,23 @@ struct loc_fusion {
     loc_fusion_params prm{};
     double *d_anchors = nullptr, *d_offset = nullptr, *d_pose = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // loc_fusion_last_kernel_ms: around the last launch
     bool timed = false;
-    std::vector<hipEvent_t> ev;   // loc_fusion_timing_*: one pair per launch
-    int ev_used = 0;
-    bool timing = false;
     long long epochs_done = 0;
-    // staging for the host path
+    // staging buffers of both host paths: range tiles and IMU in, results out
     float *d_dist = nullptr, *d_err = nullptr;
     double *d_imu = nullptr, *d_out_pose = nullptr, *d_out_chi2 = nullptr;
     uint8_t* d_out_trials = nullptr;
-    int staged = 0;
-    // pipelined host path (loc_fusion_solve_host_kmb)
-    float *d_raw_dist = nullptr, *d_raw_err = nullptr;
-    int raw_epochs = 0;
-    hipStream_t in_stream = nullptr, out_stream = nullptr;
-    std::vector<hipEvent_t> pipe_ev;
-    // covariance outputs of the pipelined host path (loc_fusion_solve_host_kmb_cov), allocated on its first call
-    double* d_out_cov = nullptr;
-    int32_t *d_out_cov_mask = nullptr, *d_out_cov_status = nullptr;
-    int cov_epochs = 0;
+    size_t staged = 0;
+    locamd::HostPipeline pipe;   // loc_fusion_solve_host_kmb
+    locamd::LaunchTimer timer;   // loc_fusion_timing_*
 };
 
-static int fusion_ensure_staging(loc_fusion* f, int32_t epochs);
-
-static void fusion_free_staging(loc_fusion* f) {
-    void* p[] = {f->d_dist, f->d_err, f->d_imu, f->d_out_pose, f->d_out_chi2, f->d_out_trials};
-    for (void* x : p) if (x) (void)hipFree(x);
-    f->d_dist = f->d_err = nullptr; f->d_imu = f->d_out_pose = f->d_out_chi2 = nullptr; f->d_out_trials = nullptr; f->staged = 0;
+static int fusion_ensure_staging(loc_fusion* f, int32_t epochs) {
+    const size_t KB = (size_t)epochs * (size_t)f->B, nf = KB * 2 * 4;
+    LOC_HIP(locamd::grow_buffers(f->staged, (size_t)epochs, {{f->d_dist, nf * sizeof(float)}, {f->d_err, nf * sizeof(float)}, {f->d_imu, KB * 8 * sizeof(double)},
+            {f->d_out_pose, KB * 7 * sizeof(double)}, {f->d_out_chi2, KB * sizeof(double)}, {f->d_out_trials, KB}}));
+    return LOC_OK;
 }
 
 extern "C" {
@@ -68,19 +46,10 @@ void loc_fusion_default_params(loc_fusion_params* p) {
 int loc_fusion_destroy(loc_fusion* f) {
     if (!f) return LOC_OK;
     (void)hipSetDevice(f->device);
-    fusion_free_staging(f);
-    for (hipEvent_t ev : f->pipe_ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : f->ev) (void)hipEventDestroy(ev);
-    if (f->d_raw_dist) (void)hipFree(f->d_raw_dist);
-    if (f->d_raw_err) (void)hipFree(f->d_raw_err);
-    if (f->d_out_cov) (void)hipFree(f->d_out_cov);
-    if (f->d_out_cov_mask) (void)hipFree(f->d_out_cov_mask);
-    if (f->d_out_cov_status) (void)hipFree(f->d_out_cov_status);
-    if (f->in_stream) (void)hipStreamDestroy(f->in_stream);
-    if (f->out_stream) (void)hipStreamDestroy(f->out_stream);
-    if (f->d_anchors) (void)hipFree(f->d_anchors);
-    if (f->d_offset) (void)hipFree(f->d_offset);
-    if (f->d_pose) (void)hipFree(f->d_pose);
+    f->pipe.destroy();
+    f->timer.destroy();
+    void* bufs[] = {f->d_dist, f->d_err, f->d_imu, f->d_out_pose, f->d_out_chi2, f->d_out_trials, f->d_anchors, f->d_offset, f->d_pose};
+    for (void* p : bufs) if (p) (void)hipFree(p);
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
     if (f->stream) (void)hipStreamDestroy(f->stream);
@@ -158,9 +127,8 @@ static int fusion_solve_device(loc_fusion* f, int32_t epochs, const float* dist,
     a.jacobian = f->prm.jacobian;
     const long long left = (long long)f->prm.gate_warmup_epochs - f->epochs_done;
     a.gate_from_epoch = left > 0 ? (int)(left > epochs ? epochs : left) : 0;
-    const bool pair = f->timing && (size_t)(f->ev_used + 2) <= f->ev.size();
     LOC_HIP(hipEventRecord(f->ev0, st));
-    if (pair) LOC_HIP(hipEventRecord(f->ev[f->ev_used], st));
+    LOC_HIP(f->timer.start(st));
     hipError_t e;
     if (!cov) {
         e = locamd::launch_fusion(a, f->prm.block_threads, st);
@@ -171,7 +139,7 @@ static int fusion_solve_device(loc_fusion* f, int32_t epochs, const float* dist,
         e = locamd::launch_fusion_cov(ca, f->prm.block_threads, st);
     }
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_fusion");
-    if (pair) { LOC_HIP(hipEventRecord(f->ev[f->ev_used + 1], st)); f->ev_used += 2; }
+    LOC_HIP(f->timer.stop(st));
     LOC_HIP(hipEventRecord(f->ev1, st));
     f->timed = true;
     f->epochs_done += epochs;
@@ -224,71 +192,21 @@ static int fusion_solve_host_kmb(loc_fusion* f, int32_t epochs, const float* dis
     LOC_HIP(hipSetDevice(f->device));
     const size_t B = (size_t)f->B, M = (size_t)f->M;
     if (int rc = fusion_ensure_staging(f, epochs)) return rc;
-    if (epochs > f->raw_epochs) {
-        if (f->d_raw_dist) (void)hipFree(f->d_raw_dist);
-        if (f->d_raw_err) (void)hipFree(f->d_raw_err);
-        f->d_raw_dist = f->d_raw_err = nullptr; f->raw_epochs = 0;
-        LOC_HIP(hipMalloc((void**)&f->d_raw_dist, sizeof(float) * M * B * (size_t)epochs));
-        LOC_HIP(hipMalloc((void**)&f->d_raw_err, sizeof(float) * M * B * (size_t)epochs));
-        f->raw_epochs = epochs;
-    }
-    if (cov_h && epochs > f->cov_epochs) {
-        if (f->d_out_cov) (void)hipFree(f->d_out_cov);
-        if (f->d_out_cov_mask) (void)hipFree(f->d_out_cov_mask);
-        if (f->d_out_cov_status) (void)hipFree(f->d_out_cov_status);
-        f->d_out_cov = nullptr; f->d_out_cov_mask = f->d_out_cov_status = nullptr; f->cov_epochs = 0;
-        LOC_HIP(hipMalloc((void**)&f->d_out_cov, sizeof(double) * 21 * B * (size_t)epochs));
-        LOC_HIP(hipMalloc((void**)&f->d_out_cov_mask, sizeof(int32_t) * B * (size_t)epochs));
-        LOC_HIP(hipMalloc((void**)&f->d_out_cov_status, sizeof(int32_t) * B * (size_t)epochs));
-        f->cov_epochs = epochs;
-    }
-    if (!f->in_stream) LOC_HIP(hipStreamCreateWithFlags(&f->in_stream, hipStreamNonBlocking));
-    if (!f->out_stream) LOC_HIP(hipStreamCreateWithFlags(&f->out_stream, hipStreamNonBlocking));
-    // same chunked three-stream pipeline as loc_snapshot_solve_host_kmb (capi.cpp); pageable buffers go as one chunk
-    auto pinned = [](const void* p) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return at.type == hipMemoryTypeHost;
-    };
-    const bool overlap = pinned(dist_kmb) && pinned(err_kmb) && pinned(imu_h) && pinned(out_pose_h) && pinned(out_chi2_h) &&
-                         (!cov_h || (pinned(cov_h) && pinned(cov_mask_h) && pinned(cov_status_h)));
-    const int ce = overlap ? (int)std::max<size_t>(1, (8u << 20) / (B * 8 * sizeof(double))) : epochs;
-    const int nchunks = (epochs + ce - 1) / ce;
-    while ((int)f->pipe_ev.size() < 2 * nchunks) {
-        hipEvent_t ev;
-        LOC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        f->pipe_ev.push_back(ev);
-    }
-    for (int c = 0; c < nchunks; ++c) {
-        const int k0 = c * ce, kc = std::min(ce, epochs - k0);
-        const size_t roff = (size_t)k0 * M * B, rn = (size_t)kc * M * B, toff = (size_t)k0 * 2 * B * 4, ioff = (size_t)k0 * B * 8;
-        LOC_HIP(hipMemcpyAsync(f->d_raw_dist + roff, dist_kmb + roff, rn * sizeof(float), hipMemcpyHostToDevice, f->in_stream));
-        LOC_HIP(hipMemcpyAsync(f->d_raw_err + roff, err_kmb + roff, rn * sizeof(float), hipMemcpyHostToDevice, f->in_stream));
-        LOC_HIP(hipMemcpyAsync(f->d_imu + ioff, imu_h + ioff, (size_t)kc * B * 8 * sizeof(double), hipMemcpyHostToDevice, f->in_stream));
-        LOC_HIP(hipEventRecord(f->pipe_ev[2 * c], f->in_stream));
-        LOC_HIP(hipStreamWaitEvent(f->stream, f->pipe_ev[2 * c], 0));
-        hipError_t e = locamd::launch_pack_kmb(f->d_raw_dist + roff, f->d_dist + toff, f->B, f->M, 2, kc, 0.f, f->stream);
-        if (e == hipSuccess) e = locamd::launch_pack_kmb(f->d_raw_err + roff, f->d_err + toff, f->B, f->M, 2, kc, 0.f, f->stream);
-        if (e != hipSuccess) return locamd_fail_hip(e, "launch_pack_kmb");
-        int rc = fusion_solve_device(f, kc, f->d_dist + toff, f->d_err + toff, f->d_imu + ioff, f->d_out_pose + (size_t)k0 * 7 * B,
-                                     f->d_out_chi2 + (size_t)k0 * B, f->d_out_trials + (size_t)k0 * B,
-                                     cov_h ? f->d_out_cov + (size_t)k0 * 21 * B : nullptr, cov_h ? f->d_out_cov_mask + (size_t)k0 * B : nullptr,
-                                     cov_h ? f->d_out_cov_status + (size_t)k0 * B : nullptr, f->stream);
-        if (rc != LOC_OK) return rc;
-        LOC_HIP(hipEventRecord(f->pipe_ev[2 * c + 1], f->stream));
-        LOC_HIP(hipStreamWaitEvent(f->out_stream, f->pipe_ev[2 * c + 1], 0));
-        LOC_HIP(hipMemcpyAsync(out_pose_h + (size_t)k0 * 7 * B, f->d_out_pose + (size_t)k0 * 7 * B, sizeof(double) * 7 * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
-        LOC_HIP(hipMemcpyAsync(out_chi2_h + (size_t)k0 * B, f->d_out_chi2 + (size_t)k0 * B, sizeof(double) * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
-        if (out_trials_h) LOC_HIP(hipMemcpyAsync(out_trials_h + (size_t)k0 * B, f->d_out_trials + (size_t)k0 * B, B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
-        if (cov_h) {
-            LOC_HIP(hipMemcpyAsync(cov_h + (size_t)k0 * 21 * B, f->d_out_cov + (size_t)k0 * 21 * B, sizeof(double) * 21 * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
-            LOC_HIP(hipMemcpyAsync(cov_mask_h + (size_t)k0 * B, f->d_out_cov_mask + (size_t)k0 * B, sizeof(int32_t) * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
-            LOC_HIP(hipMemcpyAsync(cov_status_h + (size_t)k0 * B, f->d_out_cov_status + (size_t)k0 * B, sizeof(int32_t) * B * (size_t)kc, hipMemcpyDeviceToHost, f->out_stream));
-        }
-    }
-    LOC_HIP(hipStreamSynchronize(f->out_stream));
-    LOC_HIP(hipStreamSynchronize(f->stream));
-    return LOC_OK;
+    locamd::HostPipeline& p = f->pipe;
+    if (int rc = p.prepare((size_t)epochs, B, M, cov_h ? 21 : 0)) return rc;
+    const size_t raw = M * B * sizeof(float), flags = B * sizeof(int32_t);   // bytes per epoch
+    // (the IMU array sizes the chunks)
+    return p.run(f->stream, epochs, 2, {{dist_kmb, p.d_raw_dist, raw}, {err_kmb, p.d_raw_err, raw}, {imu_h, f->d_imu, B * 8 * sizeof(double)}},
+                 {{out_pose_h, f->d_out_pose, 7 * B * sizeof(double)}, {out_chi2_h, f->d_out_chi2, B * sizeof(double)}, {out_trials_h, f->d_out_trials, B, false},
+                  {cov_h, p.d_cov, 21 * B * sizeof(double)}, {cov_mask_h, p.d_cov_mask, flags}, {cov_status_h, p.d_cov_status, flags}},
+                 [&](int k0, int kc) {
+                     const size_t roff = (size_t)k0 * M * B, toff = (size_t)k0 * 2 * B * 4, o = (size_t)k0 * B;
+                     hipError_t e = locamd::launch_pack_kmb(p.d_raw_dist + roff, f->d_dist + toff, f->B, f->M, 2, kc, 0.f, f->stream);
+                     if (e == hipSuccess) e = locamd::launch_pack_kmb(p.d_raw_err + roff, f->d_err + toff, f->B, f->M, 2, kc, 0.f, f->stream);
+                     if (e != hipSuccess) return locamd_fail_hip(e, "launch_pack_kmb");
+                     return fusion_solve_device(f, kc, f->d_dist + toff, f->d_err + toff, f->d_imu + 8 * o, f->d_out_pose + 7 * o, f->d_out_chi2 + o, f->d_out_trials + o,
+                                                cov_h ? p.d_cov + 21 * o : nullptr, cov_h ? p.d_cov_mask + o : nullptr, cov_h ? p.d_cov_status + o : nullptr, f->stream);
+                 });
 }
 
 extern "C" {
@@ -320,48 +238,10 @@ int loc_fusion_last_kernel_ms(loc_fusion* f, double* ms) {
 }
 
 int loc_fusion_timing_begin(loc_fusion* f, int32_t max_launches) {
-    if (!f || max_launches <= 0) return locamd_fail(LOC_ERR_INVALID, "timing_begin");
-    LOC_HIP(hipSetDevice(f->device));
-    while ((int)f->ev.size() < 2 * max_launches) {
-        hipEvent_t ev;
-        LOC_HIP(hipEventCreate(&ev));
-        f->ev.push_back(ev);
-    }
-    f->ev_used = 0;
-    f->timing = true;
-    return LOC_OK;
+    return f ? f->timer.begin(f->device, max_launches) : locamd_fail(LOC_ERR_INVALID, "timing_begin");
 }
 int loc_fusion_timing_end(loc_fusion* f, int32_t* n_launches, double* total_ms, double* avg_ms) {
-    if (!f) return locamd_fail(LOC_ERR_INVALID, "timing_end");
-    LOC_HIP(hipSetDevice(f->device));
-    f->timing = false;
-    double tot = 0;
-    const int n = f->ev_used / 2;
-    for (int i = 0; i < n; ++i) {
-        LOC_HIP(hipEventSynchronize(f->ev[2 * i + 1]));
-        float ms = 0;
-        LOC_HIP(hipEventElapsedTime(&ms, f->ev[2 * i], f->ev[2 * i + 1]));
-        tot += ms;
-    }
-    if (n_launches) *n_launches = n;
-    if (total_ms) *total_ms = tot;
-    if (avg_ms) *avg_ms = n ? tot / n : 0.0;
-    f->ev_used = 0;
-    return LOC_OK;
+    return f ? f->timer.end(f->device, n_launches, total_ms, avg_ms) : locamd_fail(LOC_ERR_INVALID, "timing_end");
 }
 
 }  // extern "C"
-
-static int fusion_ensure_staging(loc_fusion* f, int32_t epochs) {
-    if (epochs <= f->staged) return LOC_OK;
-    const size_t B = (size_t)f->B, K = (size_t)epochs, nf = K * 2 * B * 4;
-    fusion_free_staging(f);
-    LOC_HIP(hipMalloc((void**)&f->d_dist, nf * sizeof(float)));
-    LOC_HIP(hipMalloc((void**)&f->d_err, nf * sizeof(float)));
-    LOC_HIP(hipMalloc((void**)&f->d_imu, K * B * 8 * sizeof(double)));
-    LOC_HIP(hipMalloc((void**)&f->d_out_pose, K * 7 * B * sizeof(double)));
-    LOC_HIP(hipMalloc((void**)&f->d_out_chi2, K * B * sizeof(double)));
-    LOC_HIP(hipMalloc((void**)&f->d_out_trials, K * B));
-    f->staged = epochs;
-    return LOC_OK;
-}

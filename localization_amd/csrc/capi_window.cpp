@@ -1,8 +1,4 @@
 // C ABI of the batched sliding-window solver (see include/localization_amd.h). Host side only.
-#include "../../include/localization_amd.h"
-
-#include <hip/hip_runtime.h>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,20 +8,13 @@
 #include <string>
 #include <vector>
 
+#include "capi_host.h"
 #include "window_kernel.h"
 #include "window_structure.h"
 #include "window_tables.h"
 
 using locamd::kPoses;
 using locamd::kCounts;
-
-extern int locamd_fail(int code, const char* what);
-extern int locamd_fail_hip(hipError_t e, const char* where);
-#define LOC_HIP(expr)                                              \
-    do {                                                           \
-        hipError_t _e = (expr);                                    \
-        if (_e != hipSuccess) return locamd_fail_hip(_e, #expr);   \
-    } while (0)
 
 struct loc_window {
     int device = 0;
@@ -80,9 +69,7 @@ struct loc_window {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_ms = 0.0;
-    std::vector<hipEvent_t> ev;     // loc_window_timing_*: one pair per resident launch
-    int ev_used = 0;
-    bool timing = false;
+    locamd::LaunchTimer timer;      // loc_window_timing_*: one pair per resident launch
     // small calls (a node's single window): all inputs travel as one page-locked block, all outputs as another
     char *h_stage = nullptr, *d_stage = nullptr;
     // marginal covariances (loc_window_covariance_*): a device block of their own for batches beyond the staging block, HIP events of
@@ -147,7 +134,7 @@ int loc_window_destroy(loc_window* w) {
                     w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched, w->d_cov_ws[0], w->d_cov_ws[1], w->d_env_ws[0], w->d_env_ws[1]};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
-    for (hipEvent_t e : w->ev) (void)hipEventDestroy(e);
+    w->timer.destroy();
     if (w->h_stage) (void)hipHostFree(w->h_stage);
     if (w->d_stage) (void)hipFree(w->d_stage);
     if (w->ev0) (void)hipEventDestroy(w->ev0);
@@ -502,22 +489,12 @@ static int covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::Wi
 // the envelope pass's workspace for n windows of at most `blocks` envelope blocks (which: 0 the host path's, 1 the resident batch's)
 static hipError_t grow_env_workspace(loc_window* w, int which, int64_t n, long long blocks) {
     const size_t need = (size_t)n * locamd::window_envelope_covariance_workspace_doubles(w->caps, blocks);
-    if (w->env_ws_cap[which] >= need) return hipSuccess;
-    if (w->d_env_ws[which]) (void)hipFree(w->d_env_ws[which]);
-    w->d_env_ws[which] = nullptr; w->env_ws_cap[which] = 0;
-    hipError_t e = hipMalloc((void**)&w->d_env_ws[which], need * sizeof(double));
-    if (e == hipSuccess) w->env_ws_cap[which] = need;
-    return e;
+    return locamd::grow_buffers(w->env_ws_cap[which], need, {{w->d_env_ws[which], need * sizeof(double)}});
 }
 // the arrowhead pass's workspace for n windows with lists of `cap` entries (which: 0 the host path's, 1 the resident batch's)
 static hipError_t grow_cov_workspace(loc_window* w, int which, int64_t n, int cap) {
     const size_t need = (size_t)n * locamd::window_arrow_covariance_workspace_doubles(w->caps, cap);
-    if (w->cov_ws_cap[which] >= need) return hipSuccess;
-    if (w->d_cov_ws[which]) (void)hipFree(w->d_cov_ws[which]);
-    w->d_cov_ws[which] = nullptr; w->cov_ws_cap[which] = 0;
-    hipError_t e = hipMalloc((void**)&w->d_cov_ws[which], need * sizeof(double));
-    if (e == hipSuccess) w->cov_ws_cap[which] = need;
-    return e;
+    return locamd::grow_buffers(w->cov_ws_cap[which], need, {{w->d_cov_ws[which], need * sizeof(double)}});
 }
 
 // The kernels' arguments for n instances of the tables d.  poses_in: nullptr = d's own poses (solved in place; the resident solve starts
@@ -785,13 +762,12 @@ int loc_window_solve_resident(loc_window* w, void* hip_stream) {
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
     const locamd::WindowArgs a = window_args(w, w->dev, w->n_resident, w->d_poses_in, w->d_anchors, w->d_result);
-    const bool timed = w->timing && (size_t)(w->ev_used + 2) <= w->ev.size();
-    if (timed) LOC_HIP(hipEventRecord(w->ev[w->ev_used], st));
+    LOC_HIP(w->timer.start(st));
     // (the batch-size threshold and the ordering override are looked at per solve: loc_window_set_chain_threshold /
     //  loc_window_set_ordering after the upload take effect)
     hipError_t e = launch_any(w, 1, a, st, pick_kernel(w, w->n_resident, w->resident_topology));
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
-    if (timed) { LOC_HIP(hipEventRecord(w->ev[w->ev_used + 1], st)); w->ev_used += 2; }
+    LOC_HIP(w->timer.stop(st));
     LOC_HIP(hipEventRecord(w->resident_done, st));
     w->resident_inflight = true;
     w->resident_solved = true;
@@ -813,34 +789,10 @@ void* loc_window_poses_device(loc_window* w) { return w ? w->dev.t[kPoses] : nul
 void* loc_window_result_device(loc_window* w) { return w ? (void*)w->d_result : nullptr; }
 
 int loc_window_timing_begin(loc_window* w, int32_t max_launches) {
-    if (!w || max_launches <= 0) return locamd_fail(LOC_ERR_INVALID, "timing_begin");
-    LOC_HIP(hipSetDevice(w->device));
-    while ((int)w->ev.size() < 2 * max_launches) {
-        hipEvent_t ev;
-        LOC_HIP(hipEventCreate(&ev));
-        w->ev.push_back(ev);
-    }
-    w->ev_used = 0;
-    w->timing = true;
-    return LOC_OK;
+    return w ? w->timer.begin(w->device, max_launches) : locamd_fail(LOC_ERR_INVALID, "timing_begin");
 }
 int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, double* avg_ms) {
-    if (!w) return locamd_fail(LOC_ERR_INVALID, "timing_end");
-    LOC_HIP(hipSetDevice(w->device));
-    w->timing = false;
-    double tot = 0;
-    const int n = w->ev_used / 2;
-    for (int i = 0; i < n; ++i) {
-        LOC_HIP(hipEventSynchronize(w->ev[2 * i + 1]));
-        float ms = 0;
-        LOC_HIP(hipEventElapsedTime(&ms, w->ev[2 * i], w->ev[2 * i + 1]));
-        tot += ms;
-    }
-    if (n_launches) *n_launches = n;
-    if (total_ms) *total_ms = tot;
-    if (avg_ms) *avg_ms = n ? tot / n : 0.0;
-    w->ev_used = 0;
-    return LOC_OK;
+    return w ? w->timer.end(w->device, n_launches, total_ms, avg_ms) : locamd_fail(LOC_ERR_INVALID, "timing_end");
 }
 
 int loc_window_last_kernel_ms(loc_window* w, double* ms) {
@@ -896,12 +848,7 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
         d = w->d_stage;
         LOC_HIP(hipMemcpyAsync(d + L.tab[kPoses], w->h_stage + L.tab[kPoses], L.end - L.tab[kPoses], hipMemcpyHostToDevice, st));
     } else {       // a device block of the covariance's own: the resident batch's arrays are not touched
-        if (w->cov_cap < L.end) {
-            if (w->d_cov) (void)hipFree(w->d_cov);
-            w->d_cov = nullptr; w->cov_cap = 0;
-            LOC_HIP(hipMalloc((void**)&w->d_cov, L.end));
-            w->cov_cap = L.end;
-        }
+        LOC_HIP(locamd::grow_buffers(w->cov_cap, L.end, {{w->d_cov, L.end}}));
         d = w->d_cov;
         LOC_HIP(copy_tables(c, N, locamd::tables_at(d, L).t, b.tables().t, hipMemcpyHostToDevice, &st));
     }

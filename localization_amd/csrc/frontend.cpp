@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-extern int locamd_fail(int code, const char* what);
+#include "capi_host.h"
 
 namespace {
 

@@ -4,43 +4,21 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
-from .snapshot import _check_cov_host, _check_cov_outputs, pack_ranges
+from ._lib import FusionParams, check, lib   # (FusionParams: part of this module's surface)
+from .snapshot import pack_ranges
 
 
-class FusionParams(C.Structure):
-    _fields_ = [("maximum_iteration", C.c_int32), ("distance_outlier", C.c_double), ("gate_warmup_epochs", C.c_int32),
-                ("antenna_offset", C.c_double * 3), ("block_threads", C.c_int32), ("jacobian", C.c_int32)]
-
-
-def _bind(L):
-    if getattr(L, "_fusion_bound", False):
-        return
-    vp, dp, fp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float)
-    L.loc_fusion_default_params.argtypes = [C.POINTER(FusionParams)]; L.loc_fusion_default_params.restype = None
-    L.loc_fusion_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int64, C.c_int32, dp, C.POINTER(FusionParams)]
-    L.loc_fusion_destroy.argtypes = [vp]
-    L.loc_fusion_set_poses.argtypes = [vp, dp]
-    L.loc_fusion_get_poses.argtypes = [vp, dp]
-    L.loc_fusion_solve_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    L.loc_fusion_solve_host.argtypes = [vp, C.c_int32, fp, fp, dp, dp, dp, C.POINTER(C.c_uint8)]
-    L.loc_fusion_last_kernel_ms.argtypes = [vp, dp]
-    L.loc_fusion_timing_begin.argtypes = [vp, C.c_int32]
-    L.loc_fusion_timing_end.argtypes = [vp, C.POINTER(C.c_int32), dp, dp]
-    L._fusion_bound = True
-
-
-class FusionSolver:
+class FusionSolver(_lib.EpochSolver):
     """B tags, each a 6-DoF pose: M <= 8 anchor ranges with an antenna lever arm + an IMU rotation prior per epoch."""
+    _prefix = "loc_fusion"
 
     def __init__(self, anchors, batch, antenna_offset=(0.0, 0.0, 0.0), maximum_iteration=10, distance_outlier=3.0,
                  gate_warmup_epochs=1, block_threads=0, device=0, jacobian="numeric"):
-        L = lib(); _bind(L)
+        L = lib()
         if L.loc_device_count() <= 0:
             raise _lib.LocalizationAmdError(_lib.LOC_ERR_NO_DEVICE, "no HIP device visible: localization_amd has no CPU fallback")
         anchors = np.ascontiguousarray(anchors, dtype=np.float64)
         self.M, self.B, self.device, self.L = anchors.shape[0], int(batch), int(device), L
-        self._pinned = []
         prm = FusionParams()
         L.loc_fusion_default_params(C.byref(prm))
         prm.maximum_iteration = int(maximum_iteration); prm.distance_outlier = float(distance_outlier)
@@ -50,20 +28,6 @@ class FusionSolver:
         h = C.c_void_p()
         check(L.loc_fusion_create(C.byref(h), self.device, self.B, self.M, anchors.ctypes.data_as(C.POINTER(C.c_double)), C.byref(prm)))
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            for p in getattr(self, "_pinned", []):
-                self.L.loc_host_free(p)
-            self._pinned = []
-            self.L.loc_fusion_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_poses(self, pose_7b):
         p = np.ascontiguousarray(pose_7b, dtype=np.float64)
@@ -97,41 +61,18 @@ class FusionSolver:
         imu = np.ascontiguousarray(imu_kb8, dtype=np.float64)
         K = d.shape[0]
         assert d.shape == (K, self.M, self.B) and e.shape == d.shape and imu.shape == (K, self.B, 8)
-        if not covariance:
-            pose = np.empty((K, 7, self.B)); chi2 = np.empty((K, self.B)); trials = np.empty((K, self.B), dtype=np.uint8)
-            self.L.loc_fusion_solve_host_kmb.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
-            check(self.L.loc_fusion_solve_host_kmb(self.h, K, d.ctypes.data, e.ctypes.data, imu.ctypes.data, pose.ctypes.data,
-                                                   chi2.ctypes.data, trials.ctypes.data))
-            return pose, chi2, trials
-        if out is None:
-            out = (np.empty((K, 7, self.B)), np.empty((K, self.B)), np.empty((K, self.B), dtype=np.uint8),
-                   np.empty((K, 21, self.B)), np.empty((K, self.B), dtype=np.int32), np.empty((K, self.B), dtype=np.int32))
-        pose, chi2, trials, cov, mask, status = out
+        if out is None or not covariance:   # (`out` is for the covariance form)
+            out = self._host_outputs(K, 7, 21, covariance)
+        pose, chi2, trials = out[:3]
         assert pose.shape == (K, 7, self.B) and pose.dtype == np.float64 and chi2.shape == (K, self.B) and trials.shape == (K, self.B)
-        _check_cov_host(cov, mask, status, K, 21, self.B)
-        check(self.L.loc_fusion_solve_host_kmb_cov(self.h, K, d.ctypes.data, e.ctypes.data, imu.ctypes.data, pose.ctypes.data,
-                                                   chi2.ctypes.data, trials.ctypes.data, cov.ctypes.data, mask.ctypes.data,
-                                                   status.ctypes.data))
-        return pose, chi2, trials, _lib.unpack_covariance(cov, 6), mask, status
-
-    def pinned(self, shape, dtype):
-        """A page-locked numpy array (loc_host_alloc); freed when the solver is closed."""
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        p = C.c_void_p()
-        check(self.L.loc_host_alloc(C.byref(p), n))
-        self._pinned.append(p)
-        return np.frombuffer((C.c_char * n).from_address(p.value), dtype=dtype).reshape(shape)
+        cov = self._cov_host_args(out[3:], K, 21) if covariance else []
+        fn = self.L.loc_fusion_solve_host_kmb_cov if covariance else self.L.loc_fusion_solve_host_kmb
+        check(fn(self.h, K, d.ctypes.data, e.ctypes.data, imu.ctypes.data, pose.ctypes.data, chi2.ctypes.data, trials.ctypes.data, *cov))
+        return (pose, chi2, trials, _lib.unpack_covariance(out[3], 6), out[4], out[5]) if covariance else (pose, chi2, trials)
 
     def alloc_outputs(self, K, trials=True, covariance=False):
         """(pose [K][7][B], chi2, trials) device tensors; with covariance=True also (cov [K][21][B] f64, mask [K][B] i32, status [K][B] i32)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        out = (torch.empty((K, 7, self.B), dtype=torch.float64, device=dev), torch.empty((K, self.B), dtype=torch.float64, device=dev),
-               torch.empty((K, self.B), dtype=torch.uint8, device=dev) if trials else None)
-        if not covariance:
-            return out
-        return out + (torch.empty((K, 21, self.B), dtype=torch.float64, device=dev), torch.empty((K, self.B), dtype=torch.int32, device=dev),
-                      torch.empty((K, self.B), dtype=torch.int32, device=dev))
+        return self._device_outputs(K, 7, 21, trials, covariance)
 
     def solve_device(self, dist_tiles, err_tiles, imu, out_pose, out_chi2, out_trials=None, out_cov=None, out_cov_mask=None,
                      out_cov_status=None):
@@ -143,28 +84,13 @@ class FusionSolver:
         assert tuple(out_pose.shape) == (K, 7, self.B) and tuple(out_chi2.shape) == (K, self.B)
         for x in (dist_tiles, err_tiles, imu, out_pose, out_chi2):
             assert x.is_contiguous()
-        cov = _check_cov_outputs(torch, (out_cov, out_cov_mask, out_cov_status), K, 21, self.B, dist_tiles.device)
-        stream = torch.cuda.current_stream(dist_tiles.device).cuda_stream
-        if cov:
-            check(self.L.loc_fusion_solve_device_cov(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(), imu.data_ptr(),
-                                                     out_pose.data_ptr(), out_chi2.data_ptr(),
-                                                     out_trials.data_ptr() if out_trials is not None else None,
-                                                     out_cov.data_ptr(), out_cov_mask.data_ptr(), out_cov_status.data_ptr(),
-                                                     C.c_void_p(stream)))
-            return
-        check(self.L.loc_fusion_solve_device(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(), imu.data_ptr(),
-                                             out_pose.data_ptr(), out_chi2.data_ptr(),
-                                             out_trials.data_ptr() if out_trials is not None else None, C.c_void_p(stream)))
+        cov = self._cov_device_args((out_cov, out_cov_mask, out_cov_status), K, 21, dist_tiles.device)
+        fn = self.L.loc_fusion_solve_device_cov if cov else self.L.loc_fusion_solve_device
+        check(fn(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(), imu.data_ptr(), out_pose.data_ptr(), out_chi2.data_ptr(),
+                 out_trials.data_ptr() if out_trials is not None else None, *cov,
+                 C.c_void_p(torch.cuda.current_stream(dist_tiles.device).cuda_stream)))
 
     def last_kernel_ms(self):
         ms = C.c_double()
         check(self.L.loc_fusion_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
-
-    def timing_begin(self, max_launches):
-        check(self.L.loc_fusion_timing_begin(self.h, int(max_launches)))
-
-    def timing_end(self):
-        n = C.c_int32(); tot = C.c_double(); avg = C.c_double()
-        check(self.L.loc_fusion_timing_end(self.h, C.byref(n), C.byref(tot), C.byref(avg)))
-        return n.value, tot.value, avg.value

@@ -27,29 +27,10 @@ def unpack_ranges(tiles, M):
     return np.ascontiguousarray(t.transpose(0, 1, 3, 2).reshape(K, M4 * 4, B)[:, :M, :])
 
 
-def _check_cov_outputs(t, outs, K, T, B, dev):
-    """all three covariance output tensors or none; True if given"""
-    given = [x is not None for x in outs]
-    if not any(given):
-        return False
-    if not all(given):
-        raise ValueError("out_cov, out_cov_mask and out_cov_status go together: pass all three or none")
-    cov, mask, status = outs
-    assert tuple(cov.shape) == (K, T, B) and cov.dtype == t.float64 and cov.is_contiguous() and cov.device == dev
-    for x in (mask, status):
-        assert tuple(x.shape) == (K, B) and x.dtype == t.int32 and x.is_contiguous() and x.device == dev
-    return True
-
-
-def _check_cov_host(cov, mask, status, K, T, B):
-    assert cov.shape == (K, T, B) and cov.dtype == np.float64 and cov.flags.c_contiguous
-    for x in (mask, status):
-        assert x.shape == (K, B) and x.dtype == np.int32 and x.flags.c_contiguous
-
-
-class SnapshotSolver:
+class SnapshotSolver(_lib.EpochSolver):
     """B independent tags sharing one anchor map; each `solve` call runs K epochs of
     gate -> Cauchy range factors -> g2o-style LM (reference localization.cpp:297-376 cost, :164-170 solve)."""
+    _prefix = "loc_snapshot"
 
     def __init__(self, anchors, batch, maximum_iteration=10, distance_outlier=1.0, jacobian="numeric",
                  lanes_per_instance=0, block_threads=0, device=0, gate_warmup_epochs=1):
@@ -79,23 +60,8 @@ class SnapshotSolver:
                                     anchors.ctypes.data_as(C.POINTER(C.c_double)), C.byref(prm)))
         self.h = h
         self.L = L
-        self._pinned = []
         self.M4 = L.loc_snapshot_anchor_groups(h)
         self.lanes_per_instance = L.loc_snapshot_lanes_per_instance(h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            for p in getattr(self, "_pinned", []):
-                self.L.loc_host_free(p)
-            self._pinned = []
-            self.L.loc_snapshot_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- state ------------------------------------------------------------------------------------
     def set_positions(self, pos_3b):
@@ -114,14 +80,7 @@ class SnapshotSolver:
 
     def alloc_outputs(self, K, trials=True, covariance=False):
         """(pos, chi2, trials) device tensors; with covariance=True also (cov [K][6][B] f64, mask [K][B] i32, status [K][B] i32)."""
-        t = self.torch
-        out_pos = t.empty((K, 3, self.B), dtype=t.float64, device=self.dev)
-        out_chi2 = t.empty((K, self.B), dtype=t.float64, device=self.dev)
-        out_trials = t.empty((K, self.B), dtype=t.uint8, device=self.dev) if trials else None
-        if not covariance:
-            return out_pos, out_chi2, out_trials
-        return (out_pos, out_chi2, out_trials, t.empty((K, 6, self.B), dtype=t.float64, device=self.dev),
-                t.empty((K, self.B), dtype=t.int32, device=self.dev), t.empty((K, self.B), dtype=t.int32, device=self.dev))
+        return self._device_outputs(K, 3, 6, trials, covariance)
 
     def solve_device(self, dist_tiles, err_tiles, out_pos, out_chi2, out_trials=None, out_cov=None, out_cov_mask=None, out_cov_status=None):
         """Asynchronous on the current torch stream. Tensors: float32 [K][M4][B][4], outputs as alloc_outputs.
@@ -138,19 +97,10 @@ class SnapshotSolver:
             assert tuple(out_trials.shape) == (K, self.B) and out_trials.dtype == t.uint8
         for x in (dist_tiles, err_tiles, out_pos, out_chi2):
             assert x.device == self.dev
-        cov = _check_cov_outputs(t, (out_cov, out_cov_mask, out_cov_status), K, 6, self.B, self.dev)
-        stream = t.cuda.current_stream(self.dev).cuda_stream
-        if cov:
-            check(self.L.loc_snapshot_solve_device_cov(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(),
-                                                       out_pos.data_ptr(), out_chi2.data_ptr(),
-                                                       out_trials.data_ptr() if out_trials is not None else None,
-                                                       out_cov.data_ptr(), out_cov_mask.data_ptr(), out_cov_status.data_ptr(),
-                                                       C.c_void_p(stream)))
-            return
-        check(self.L.loc_snapshot_solve_device(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(),
-                                               out_pos.data_ptr(), out_chi2.data_ptr(),
-                                               out_trials.data_ptr() if out_trials is not None else None,
-                                               C.c_void_p(stream)))
+        cov = self._cov_device_args((out_cov, out_cov_mask, out_cov_status), K, 6, self.dev)
+        fn = self.L.loc_snapshot_solve_device_cov if cov else self.L.loc_snapshot_solve_device
+        check(fn(self.h, K, dist_tiles.data_ptr(), err_tiles.data_ptr(), out_pos.data_ptr(), out_chi2.data_ptr(),
+                 out_trials.data_ptr() if out_trials is not None else None, *cov, C.c_void_p(t.cuda.current_stream(self.dev).cuda_stream)))
 
     # ---- host convenience (PCIe staged) --------------------------------------------------------------
     def solve(self, dist_kmb, err_kmb):
@@ -167,14 +117,6 @@ class SnapshotSolver:
                                              trials.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out_pos, out_chi2, trials
 
-    def pinned(self, shape, dtype):
-        """A page-locked numpy array (loc_host_alloc); freed when the solver is closed."""
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        p = C.c_void_p()
-        check(self.L.loc_host_alloc(C.byref(p), n))
-        self._pinned.append(p)
-        return np.frombuffer((C.c_char * n).from_address(p.value), dtype=dtype).reshape(shape)
-
     def solve_stream(self, dist_kmb, err_kmb, out=None, covariance=False):
         """The pipelined host path (loc_snapshot_solve_host_kmb): [K][M][B] float32 host arrays in their natural layout,
         packed into tiles on the GPU, copy-in / solve / copy-out overlapped.  `out` = (pos, chi2, trials) to reuse
@@ -185,25 +127,10 @@ class SnapshotSolver:
         K = d.shape[0]
         assert d.shape == (K, self.M, self.B) and e.shape == d.shape
         if out is None:
-            out = (np.empty((K, 3, self.B)), np.empty((K, self.B)), np.empty((K, self.B), dtype=np.uint8))
-            if covariance:
-                out += (np.empty((K, 6, self.B)), np.empty((K, self.B), dtype=np.int32), np.empty((K, self.B), dtype=np.int32))
+            out = self._host_outputs(K, 3, 6, covariance)
         pos, chi2, trials = out[:3]
         assert pos.shape == (K, 3, self.B) and pos.dtype == np.float64 and chi2.shape == (K, self.B) and trials.shape == (K, self.B)
-        if not covariance:
-            check(self.L.loc_snapshot_solve_host_kmb(self.h, K, d.ctypes.data, e.ctypes.data, pos.ctypes.data, chi2.ctypes.data, trials.ctypes.data))
-            return pos, chi2, trials
-        cov, mask, status = out[3:]
-        _check_cov_host(cov, mask, status, K, 6, self.B)
-        check(self.L.loc_snapshot_solve_host_kmb_cov(self.h, K, d.ctypes.data, e.ctypes.data, pos.ctypes.data, chi2.ctypes.data,
-                                                     trials.ctypes.data, cov.ctypes.data, mask.ctypes.data, status.ctypes.data))
-        return pos, chi2, trials, _lib.unpack_covariance(cov, 3), mask, status
-
-    # ---- HIP-event kernel timing -------------------------------------------------------------------
-    def timing_begin(self, max_launches):
-        check(self.L.loc_snapshot_timing_begin(self.h, int(max_launches)))
-
-    def timing_end(self):
-        n = C.c_int32(); tot = C.c_double(); avg = C.c_double()
-        check(self.L.loc_snapshot_timing_end(self.h, C.byref(n), C.byref(tot), C.byref(avg)))
-        return n.value, tot.value, avg.value
+        cov = self._cov_host_args(out[3:], K, 6) if covariance else []
+        fn = self.L.loc_snapshot_solve_host_kmb_cov if covariance else self.L.loc_snapshot_solve_host_kmb
+        check(fn(self.h, K, d.ctypes.data, e.ctypes.data, pos.ctypes.data, chi2.ctypes.data, trials.ctypes.data, *cov))
+        return (pos, chi2, trials, _lib.unpack_covariance(out[3], 3), out[4], out[5]) if covariance else (pos, chi2, trials)

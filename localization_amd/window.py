@@ -85,7 +85,9 @@ def covariance_plan(wb: WindowBatch):
     return blocks.value, nbytes.value
 
 
-class WindowSolver:
+class WindowSolver(_lib.Handle):
+    _prefix = "loc_window"
+
     def __init__(self, anchors, batch, nv_max, nr_max, np_max=0, ns_max=0, maximum_iteration=10, device=0, bw_max=-1,
                  jacobian="numeric", natural_order=False, chain_threshold=None):
         L = lib()
@@ -103,17 +105,6 @@ class WindowSolver:
         check(L.loc_window_set_ordering(h, int(bool(natural_order))))
         if chain_threshold is not None:   # smallest batch that takes the one-lane-per-window kernel for chain windows
             check(L.loc_window_set_chain_threshold(h, int(chain_threshold)))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.loc_window_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _endpoint1(self, wb):
         dp = C.POINTER(C.c_double)
@@ -197,14 +188,6 @@ class WindowSolver:
         check(self.L.loc_window_last_covariance_ms(self.h, C.byref(ms)))
         return ms.value
 
-    def timing_begin(self, max_launches):
-        check(self.L.loc_window_timing_begin(self.h, int(max_launches)))
-
-    def timing_end(self):
-        n = C.c_int32(); tot = C.c_double(); avg = C.c_double()
-        check(self.L.loc_window_timing_end(self.h, C.byref(n), C.byref(tot), C.byref(avg)))
-        return n.value, tot.value, avg.value
-
     KERNEL_KINDS = {-1: "none", 0: "window_lm_kernel", 1: "chain_lm_kernel", 2: "chain3_lm_kernel", 3: "arrow3_lm_kernel", 4: "tree_wave_kernel", 5: "tree_lm_kernel", 6: "wave3_lm_kernel", 7: "wave6_lm_kernel", 8: "wave6_lm_kernel<SE3>"}
 
     def last_kernel_kind(self):
@@ -222,7 +205,6 @@ class WindowSolver:
         """loc_window_set_option: the kernel-selection switches of this handle ("chain_min_batch", "arrow3", "tree", "wave3", "wave6",
         "chain3", "zero_copy", "topology_cache", "kernel_events"; "covariance_general": 1 = covariance() / covariance_resident() also serve
         the batches the chain, arrowhead and forest passes decline, default 0)"""
-        self.L.loc_window_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
 
     def last_host_timing(self):

@@ -100,6 +100,35 @@ def test_fusion_pipelined_host_path_equals_the_staged_one(gpu, B, K, M):
     a.close(); b.close()
 
 
+def test_fusion_pipelined_host_path_regrows_its_buffers_on_one_handle(gpu):
+    """One handle, loc_fusion_solve_host_kmb with 2 epochs, then 5 (every staging buffer is freed and allocated again; with
+    covariances, whose staging is first allocated on a handle that already holds the solve's), then 3 (nothing regrows), then the
+    staged loc_fusion_solve_host: each call bit-identical to the same call on a fresh handle.  6 anchors: padded tiles."""
+    import localization_amd as la
+    from localization_amd.synthetic import make_fusion_stream
+    B, M = 777, 6
+    s = make_fusion_stream(B, 5, seed=9)
+    dist, err = s["dist"][:, :M], s["err"][:, :M]
+
+    def solver():
+        return la.FusionSolver(s["anchors"][:M], B, antenna_offset=s["offset"], maximum_iteration=10, distance_outlier=3.0, jacobian="analytic")
+
+    def call(f, K, covariance):
+        f.set_poses(s["init"])
+        return f.solve_stream(dist[:K], err[:K], s["imu"][:K], covariance=covariance) if K else f.solve(dist, err, s["imu"])
+
+    used = solver()
+    for K, covariance in ((2, False), (5, True), (3, False), (0, False)):   # (0: the staged path, all epochs)
+        fresh = solver()
+        got, want = call(used, K, covariance), call(fresh, K, covariance)
+        assert len(got) == (6 if covariance else 3)
+        for i, (x, y) in enumerate(zip(got, want)):
+            assert np.array_equal(x, y, equal_nan=(i == 3)), (K, covariance, i)   # (i == 3: a singular update's covariance is NaN on both)
+        assert np.array_equal(used.get_poses(), fresh.get_poses())
+        fresh.close()
+    used.close()
+
+
 @pytest.mark.parametrize("offset", [(0.1, 0.0, -0.05), (1.5, 0.5, -0.8)])
 def test_fusion_numeric_mode_matches_numeric_oracle(gpu, offset):
     """The reference's configuration on both sides (g2o's central differences).  The short lever arm takes the perturbed norms from the

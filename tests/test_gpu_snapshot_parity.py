@@ -219,6 +219,35 @@ def test_pipelined_host_path_equals_the_staged_one(gpu, B, K, M):
     a.close(); b.close()
 
 
+def test_pipelined_host_path_regrows_its_buffers_on_one_handle(gpu):
+    """One handle, loc_snapshot_solve_host_kmb with 2 epochs, then 5 (every staging buffer is freed and allocated again; with
+    covariances, whose staging is first allocated on a handle that already holds the solve's), then 3 (nothing regrows), then the
+    staged loc_snapshot_solve_host: each call bit-identical to the same call on a fresh handle.  5 anchors: padded tiles."""
+    import localization_amd as la
+    from localization_amd.synthetic import ANCHORS_8, make_snapshot_stream
+    B, M = 1000, 5
+    s = make_snapshot_stream(B, 5, seed=3)
+    dist, err = s["dist"][:, :M], s["err"][:, :M]
+
+    def solver():
+        return la.SnapshotSolver(ANCHORS_8[:M], B, maximum_iteration=10, distance_outlier=1.0, jacobian="analytic")
+
+    def call(sv, K, covariance):
+        sv.set_positions(s["init"])
+        return sv.solve_stream(dist[:K], err[:K], covariance=covariance) if K else sv.solve(dist, err)
+
+    used = solver()
+    for K, covariance in ((2, False), (5, True), (3, False), (0, False)):   # (0: the staged path, all epochs)
+        fresh = solver()
+        got, want = call(used, K, covariance), call(fresh, K, covariance)
+        assert len(got) == (6 if covariance else 3)
+        for i, (x, y) in enumerate(zip(got, want)):
+            assert np.array_equal(x, y, equal_nan=(i == 3)), (K, covariance, i)   # (i == 3: a singular update's covariance is NaN on both)
+        assert np.array_equal(used.get_positions(), fresh.get_positions())
+        fresh.close()
+    used.close()
+
+
 def test_degenerate_inputs_start_on_an_anchor_and_non_finite_ranges(gpu):
     """Collisions and bad data, as the domain has them: (1) the estimate starts exactly ON an anchor (r = 0 for that edge:
     the analytic Jacobian is 0/0, g2o's numeric one is finite) — both Jacobian modes stay finite and match the oracle;

@@ -706,6 +706,45 @@ def test_large_host_solve_drops_the_resident_batch(gpu):
     solver.close()
 
 
+@pytest.mark.parametrize("kind", ["snapshot", "fusion", "window"])
+def test_launch_timer_records_no_more_launches_than_it_was_opened_for(gpu, kind):
+    """loc_*_timing_begin(2), three launches: the first two are timed (n == 2, total > 0, avg == total / 2); timing_end empties the
+    record (a second one returns n == 0) and closes it (a launch after it is not recorded)."""
+    import torch
+    import localization_amd as la
+    from localization_amd.snapshot import pack_ranges
+    from localization_amd.synthetic import make_fusion_stream, make_snapshot_stream
+    B, K = 256, 1
+    if kind == "snapshot":
+        s = make_snapshot_stream(B, K, seed=1)
+        solver = la.SnapshotSolver(s["anchors"], B, jacobian="analytic")
+        args = (solver.to_device_tiles(s["dist"]), solver.to_device_tiles(s["err"])) + solver.alloc_outputs(K)
+        launch = lambda: solver.solve_device(*args)
+    elif kind == "fusion":
+        s = make_fusion_stream(B, K, seed=1)
+        solver = la.FusionSolver(s["anchors"], B, antenna_offset=s["offset"], jacobian="analytic")
+        dev = torch.device("cuda", 0)
+        args = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (pack_ranges(s["dist"]), pack_ranges(s["err"]), s["imu"]))
+        args += solver.alloc_outputs(K)
+        launch = lambda: solver.solve_device(*args)
+    else:
+        T = 10
+        solver = la.WindowSolver(ANCH, 70, T, 2 * T, 0, 0, jacobian="analytic", bw_max=1)   # (70: the smallest resident batch of this file)
+        solver.upload(_chain_batch(la, 70, T, 5))
+        launch = solver.solve_resident
+    solver.timing_begin(2)
+    for _ in range(3):
+        launch()
+    torch.cuda.synchronize()
+    n, total, avg = solver.timing_end()
+    assert n == 2 and total > 0 and avg == total / 2, (n, total, avg)
+    assert solver.timing_end()[0] == 0
+    launch()
+    torch.cuda.synchronize()
+    assert solver.timing_end()[0] == 0
+    solver.close()
+
+
 def test_window_options_and_topology_cache(gpu):
     """loc_window_set_option replaces the environment switches (read once at create); the structural verdict of a host-path batch is
     cached on a hash of its counts / index tables: the same graph with new measurements skips the analysis, another structure does not;
