@@ -75,6 +75,9 @@ def _arrow_batch(la, rng, B, T, A, rich):
     (70, 6, True, "analytic"),      # two chunks of chain poses, two row tiles of border rows
     (40, 12, True, "analytic"),     # 36 border rows: three row tiles
     (130, 3, False, "numeric"),
+    (50, 3, True, "analytic"),      # chain lengths 44..50: one and two segments in one batch (the cut at 47 / 48)
+    (74, 3, True, "numeric"),       # 68..74: two and three segments (71 / 72)
+    (98, 3, True, "analytic"),      # 92..98: three and four segments (95 / 96)
 ])
 def test_arrow3_kernel_matches_6dof_oracle_and_general_kernel(gpu, T, A, rich, jac):
     import localization_amd as la
