@@ -28,6 +28,7 @@ extern "C" {
                            * 4: loc_window_set_option / _last_host_timing, loc_node_flush_tail / _last_kernel_kind, loc_fusion_timing_*;
                            *    a large loc_window_solve_host drops the resident batch;
                            *    (additive, same version) loc_window_covariance_host / _resident / loc_window_last_covariance_ms / loc_window_covariance_plan;
+                           *    (additive, same version) loc_window_joint_covariance_host / _resident / _plan;
                            *    (additive, same version) loc_snapshot_solve_device_cov / _host_kmb_cov, loc_fusion_solve_device_cov / _host_kmb_cov */
 
 typedef enum loc_status {
@@ -378,6 +379,35 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
  * edge index outside its window. */
 int loc_window_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
                                int64_t* blocks_max, size_t* workspace_bytes);
+/* Joint marginals: the calls above, and with them the cross blocks [H^-1]_ij of requested pairs of pose slots — what g2o's computeMarginals
+ * returns for a list of block index pairs.  Same H, coordinates, exclusion rule and pivot rule, same coverage and dispatch as
+ * loc_window_covariance_* (LOC_ERR_UNSUPPORTED with nothing written otherwise); every pass serves every pair.  The pair tables are HOST arrays
+ * in both variants:
+ *   npair_max    pair slots per window (0: no pairs — the call is loc_window_covariance_*, the pair arguments and cross may be NULL)
+ *   pair_counts  int32 [n]                 0 <= pair_counts[b] <= npair_max
+ *   pairs        int32 [n][npair_max][2]   pose slots (i, j) of window b, both in [0, nv_b); (i, i), (j, i) next to (i, j) and duplicates are allowed
+ *   cross        double [n][npair_max][36] cross[b][p] = [H^-1]_ij, row-major 6x6, rows: pose i's coordinates, columns: pose j's
+ * Rows of coordinates excluded in pose i and columns of coordinates excluded in pose j are 0 (3x3 passes: every rotation row / column).  (i, i)
+ * has the bits of cov[b][i]; (j, i) is the exact transpose of (i, j) (one is computed and transposed), duplicates have equal bits.  Two poses
+ * that nothing connects (different trees of a forest, an isolated pose) give exact zeros.  A LOC_ERR_SINGULAR window has NaN in all its
+ * requested blocks; slots p >= pair_counts[b] are written as 0.  Every pair is checked on the host before anything is launched: a count or a
+ * slot out of range is LOC_ERR_INVALID with nothing written.  cov, mask and status are those of the plain call (chains, arrowheads and
+ * forests: bit for bit).  On the envelope pass a requested pair counts as one more pose-to-pose edge of the envelope (first(max(i, j)) <=
+ * min(i, j)): the workspace grows by the blocks that adds, loc_window_joint_covariance_plan reports it.
+ * _resident: cross_dev is a device array like cov_dev; the pair tables are copied to a device table of the handle before the launch and the
+ * caller's arrays are not read after the call returns (a call may wait for the previous joint call's copy).
+ * _plan: loc_window_covariance_plan for the envelope with the pairs; without pairs its results are loc_window_covariance_plan's.
+ * LOC_ERR_INVALID also for a pair count or a pair's slot out of range. */
+int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses,
+                                     const int32_t* r_idx, const double* r_val, const int32_t* p_idx, const double* p_val,
+                                     const int32_t* s_idx, const double* s_val,
+                                     int32_t npair_max, const int32_t* pair_counts, const int32_t* pairs,
+                                     double* cov, int32_t* mask, int32_t* status, double* cross);
+int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream,
+                                         int32_t npair_max, const int32_t* pair_counts_host, const int32_t* pairs_host,
+                                         void* cov_dev, void* mask_dev, void* status_dev, void* cross_dev);
+int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
+                                     int32_t npair_max, const int32_t* pair_counts, const int32_t* pairs, int64_t* blocks_max, size_t* workspace_bytes);
 /* kernel time of the last covariance launch of this handle (HIP events on its stream; a resident launch is waited for), milliseconds */
 int loc_window_last_covariance_ms(loc_window* w, double* ms);
 

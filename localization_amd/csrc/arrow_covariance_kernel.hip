@@ -23,7 +23,7 @@
 //      sweep also sums the lane's column of B^T Y in registers.  A lane of another wave meanwhile runs the chain pass's selected
 //      inversion Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i for [A^-1]_ii;
 //   5. S = C - B^T Y, its Cholesky factor and inverse in LDS (lane = row / column);
-//   6. chain marginals, lane = chain pose; 7. the store (cov_store_window's rules).
+//   6. chain marginals, lane = chain pose; 7. the store (cov_store_window's rules); 8. joint calls only: the cross blocks, lane = pair.
 #include "cov_block_device.h"
 #include "window_kernel.h"
 
@@ -67,8 +67,8 @@ __host__ __device__ inline size_t arrow_cov_ws_doubles(const WindowCaps& c, int 
     return (size_t)c.nr_max * kAcRecG + 2 * (size_t)c.nv_max * 3 * kAcBS + ((size_t)c.nv_max * cap + 1) / 2;
 }
 
-template <int JAC>
-__global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const WindowArgs a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status) {
+template <int JAC, bool JOINT>
+__global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const WindowArgs a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int BS = kAcBS;
     const int tid = threadIdx.x;
     const long long inst = blockIdx.x;
@@ -515,14 +515,116 @@ __global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const Wind
     }
     for (int v = tid; v < nvm; v += kAcThreads) mask[(size_t)inst * nvm + v] = v < nv ? (shape_ok ? mk[v] : 0x38) : 0;
     if (tid == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+
+    // ---- 8. joint calls, lane = pair: the block (lo, hi) of H^-1 from S^-1 (C), Y (workspace), K_i (Ho) and Sigma_ii (Hd), transposed for (hi, lo) ----
+    //   border - border: the block of S^-1;   chain i - border: -Y_i S^-1;
+    //   chain - chain:   [A^-1]_ij + Y_i S^-1 Y_j^T,  [A^-1]_ij = (-K_i^T) .. (-K_{j-1}^T) [A^-1]_jj,  [A^-1]_jj = Sigma_jj - Y_j S^-1 Y_j^T
+    if (JOINT) {
+        const int npr = pp.counts[inst];
+        const int32_t* pr = pp.pairs + (size_t)inst * pp.npair_max * 2;
+        for (int p = tid; p < pp.npair_max; p += kAcThreads) {
+            double* o = pp.cross + ((size_t)inst * pp.npair_max + p) * 36;
+            const int pi = p < npr ? pr[2 * p] : -1, pj = p < npr ? pr[2 * p + 1] : -1;
+            if (pi < 0 || pi >= nv || pj < 0 || pj >= nv || !ok) {   // an unused slot: 0; a singular window: NaN
+                const double x = (p < npr && !ok) ? __builtin_nan("") : 0.0;
+                for (int k = 0; k < 36; ++k) o[k] = x;
+                continue;
+            }
+            const int lo = min(pi, pj), hi = max(pi, pj);
+            double X[3][3];   // Sigma_{lo,hi}
+            if (lo == hi) {
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        if (lo < nc) X[r][c] = (Hd[lo * 9 + r * 3 + c] + Hd[lo * 9 + c * 3 + r]) * 0.5;
+                        else { const int b = 3 * (lo - nc); X[r][c] = (C[(b + r) * BS + b + c] + C[(b + c) * BS + b + r]) * 0.5; }
+                    }
+            } else if (lo >= nc) {
+                const int bl = 3 * (lo - nc), bh = 3 * (hi - nc);
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) X[r][c] = C[(bl + r) * BS + bh + c];
+            } else if (hi >= nc) {
+                const double* Yl = Ym + (size_t)lo * 3 * BS;
+                const int bh = 3 * (hi - nc);
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) X[r][c] = 0.0;
+                for (int k = 0; k < D; ++k)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) X[r][c] = __builtin_fma(-Yl[r * BS + k], C[k * BS + bh + c], X[r][c]);
+            } else {
+                const double* Yl = Ym + (size_t)lo * 3 * BS;
+                const double* Yh = Ym + (size_t)hi * 3 * BS;
+                double hh[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, lh[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};   // Y_hi S^-1 Y_hi^T, Y_lo S^-1 Y_hi^T
+                for (int q2 = 0; q2 < D; ++q2) {
+                    double z[3] = {0, 0, 0};   // row q2 of S^-1 Y_hi^T
+                    for (int k = 0; k < D; ++k)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) z[c] = __builtin_fma(C[q2 * BS + k], Yh[c * BS + k], z[c]);
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            hh[r][c] = __builtin_fma(Yh[r * BS + q2], z[c], hh[r][c]);
+                            lh[r][c] = __builtin_fma(Yl[r * BS + q2], z[c], lh[r][c]);
+                        }
+                }
+                double G[3][3];
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) G[r][c] = (Hd[hi * 9 + r * 3 + c] + Hd[hi * 9 + c * 3 + r]) * 0.5 - hh[r][c];
+                for (int k = hi - 1; k >= lo; --k) {   // (hi < nc <= nv_max: bounded by the window)
+                    const double* K = Ho + k * 9;
+                    double T[3][3];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            double s2 = 0.0;
+#pragma unroll
+                            for (int t = 0; t < 3; ++t) s2 = __builtin_fma(K[t * 3 + r], G[t][c], s2);
+                            T[r][c] = -s2;
+                        }
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) G[r][c] = T[r][c];
+                }
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) X[r][c] = G[r][c] + lh[r][c];
+            }
+            const bool tr = pi != lo;   // the pair was asked for as (hi, lo)
+#pragma unroll
+            for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+                for (int cc = 0; cc < 6; ++cc) {
+                    double x = 0.0;
+                    if (rr < 3 && cc < 3 && !((mk[pi] >> rr) & 1) && !((mk[pj] >> cc) & 1)) x = tr ? X[cc][rr] : X[rr][cc];
+                    o[rr * 6 + cc] = x;
+                }
+        }
+    }
 }
 
-template <int JAC>
-hipError_t launch_arrow_cov_t(const WindowArgs& a, double* ws, int cap, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&arrow_covariance_kernel<JAC>>(160 * 1024);
+template <int JAC, bool JOINT>
+hipError_t launch_arrow_cov_j(const WindowArgs& a, double* ws, int cap, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<&arrow_covariance_kernel<JAC, JOINT>>(160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((arrow_covariance_kernel<JAC>), dim3((unsigned)a.B), dim3(kAcThreads), lds, stream, a, ws, cap, cov, mask, status);
+    hipLaunchKernelGGL((arrow_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(kAcThreads), lds, stream, a, ws, cap, cov, mask, status, pp);
     return hipGetLastError();
+}
+template <int JAC>
+hipError_t launch_arrow_cov_t(const WindowArgs& a, double* ws, int cap, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    return pp.cross ? launch_arrow_cov_j<JAC, true>(a, ws, cap, lds, cov, mask, status, pp, stream) : launch_arrow_cov_j<JAC, false>(a, ws, cap, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace
@@ -530,12 +632,12 @@ hipError_t launch_arrow_cov_t(const WindowArgs& a, double* ws, int cap, size_t l
 size_t window_arrow_covariance_lds_bytes(const WindowCaps& c) { return arrow_cov_layout(c.nv_max).bytes; }
 size_t window_arrow_covariance_workspace_doubles(const WindowCaps& c, int cap) { return arrow_cov_ws_doubles(c, cap); }
 
-hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
+hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     if (!ws || cap < 1) return hipErrorInvalidValue;
     const size_t lds = window_arrow_covariance_lds_bytes(a.caps);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    return a.jacobian ? launch_arrow_cov_t<1>(a, ws, cap, lds, cov, mask, status, stream) : launch_arrow_cov_t<0>(a, ws, cap, lds, cov, mask, status, stream);
+    return a.jacobian ? launch_arrow_cov_t<1>(a, ws, cap, lds, cov, mask, status, pp, stream) : launch_arrow_cov_t<0>(a, ws, cap, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace locamd

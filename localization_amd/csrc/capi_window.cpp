@@ -102,6 +102,14 @@ struct loc_window {
     bool cov_sched_valid = false;
     unsigned long long cov_sched_key = 0;
     int64_t cov_sched_n = 0;
+    // joint covariance calls (loc_window_joint_covariance_resident): the resident batch's counts as uploaded (the pair check needs every
+    // window's nv) and, once the envelope pass holds the batch, its pose-to-pose index tables (the pairs enlarge the envelope); the call's pair
+    // tables [counts | pairs] as a page-locked copy and as the device table the kernel reads, grown on demand
+    std::vector<int32_t> res_counts, res_ridx, res_sidx;
+    char *h_pairs = nullptr, *d_pairs = nullptr;
+    size_t pairs_cap = 0;
+    hipEvent_t pairs_copied = nullptr;   // the device table has the page-locked copy's content
+    bool pairs_inflight = false;
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -141,6 +149,9 @@ int loc_window_destroy(loc_window* w) {
     if (w->ev1) (void)hipEventDestroy(w->ev1);
     if (w->resident_done) (void)hipEventDestroy(w->resident_done);
     if (w->d_cov) (void)hipFree(w->d_cov);
+    if (w->h_pairs) (void)hipHostFree(w->h_pairs);
+    if (w->d_pairs) (void)hipFree(w->d_pairs);
+    if (w->pairs_copied) (void)hipEventDestroy(w->pairs_copied);
     if (w->cov_ev0) (void)hipEventDestroy(w->cov_ev0);
     if (w->cov_ev1) (void)hipEventDestroy(w->cov_ev1);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -477,11 +488,12 @@ static long long cov_switches(const loc_window* w) {
 }
 // 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is kCovEnvelope —
 //    envelope_covariance_kernel.hip in the caller's pose order; the batch's largest envelope goes to w->env_blocks[keyed ? 0 : 1].
-static int covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::WinAux* own, bool keyed, bool& need_upload) {
+//    pt: the pairs of a joint call count as edges of that envelope (none: the plain envelope).
+static int covariance_kind(loc_window* w, const locamd::HostBatch& b, const locamd::PairTables& pt, locamd::WinAux* own, bool keyed, bool& need_upload) {
     const int kind = structured_covariance_kind(w, b, own, keyed, need_upload);
     if (kind || w->has_off1 || !w->opt.cov_general) return kind;
     if (locamd::window_envelope_covariance_lds_bytes(w->caps) > 160 * 1024) return 0;
-    const long long blocks = locamd::envelope_blocks_max(w->caps, b);
+    const long long blocks = locamd::envelope_blocks_max_joint(w->caps, b, pt);
     if (blocks < 0) return 0;   // (cannot happen: the tables were validated)
     w->env_blocks[keyed ? 0 : 1] = blocks;
     return kCovEnvelope;
@@ -737,6 +749,7 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
             if (v1 < 0 && -v1 > max_anchor) max_anchor = -v1;
         }
     w->resident_min_anchors = max_anchor;
+    w->res_counts.assign(counts, counts + (size_t)n * 4);
     w->resident_topology = topology;
     // the block size of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
     // classified by the first loc_window_covariance_resident call (an upload costs nothing more for callers that never ask)
@@ -808,21 +821,35 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
 
 // the pass of a batch of covariance_kind's `kind`; which: 0 = loc_window_covariance_host's table set and workspace, 1 = the resident batch's
 // (a forest that loc_window_upload classified, kCovForest, walks the solve's schedule aux[1]; kCovForestOwn the covariance's own)
-static hipError_t launch_covariance(loc_window* w, int which, int kind, const locamd::WindowArgs& a, double* cov, int32_t* mask, int32_t* status, hipStream_t st) {
-    if (kind == kCovArrow) return locamd::launch_window_arrow_covariance(a, w->d_cov_ws[which], w->cov_list_cap[which], cov, mask, status, st);
-    if (kind == kCovEnvelope) return locamd::launch_window_envelope_covariance(a, w->d_env_ws[which], w->env_blocks[which], cov, mask, status, st);
-    if (kind == kCovForest) return locamd::launch_window_forest_covariance(a, w->aux[1].tsched, cov, mask, status, st);
-    if (kind == kCovForestOwn) return locamd::launch_window_forest_covariance(a, w->cov_aux[which].tsched, cov, mask, status, st);
-    return locamd::launch_window_covariance(a, kind == 3, cov, mask, status, st);
+// env_blocks: the envelope the workspace was sized for (a joint call's includes its pairs); pp: the pairs on the device, cross = nullptr for none
+static hipError_t launch_covariance(loc_window* w, int which, int kind, long long env_blocks, const locamd::WindowArgs& a, double* cov, int32_t* mask, int32_t* status,
+                                    const locamd::CovPairs& pp, hipStream_t st) {
+    if (kind == kCovArrow) return locamd::launch_window_arrow_covariance(a, w->d_cov_ws[which], w->cov_list_cap[which], cov, mask, status, pp, st);
+    if (kind == kCovEnvelope) return locamd::launch_window_envelope_covariance(a, w->d_env_ws[which], env_blocks, cov, mask, status, pp, st);
+    if (kind == kCovForest) return locamd::launch_window_forest_covariance(a, w->aux[1].tsched, cov, mask, status, pp, st);
+    if (kind == kCovForestOwn) return locamd::launch_window_forest_covariance(a, w->cov_aux[which].tsched, cov, mask, status, pp, st);
+    return locamd::launch_window_covariance(a, kind == 3, cov, mask, status, pp, st);
 }
-int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
-                               const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
-                               int32_t* status) {
+// the pair arguments of a joint call as given (npair_max = 0: none, the plain call): 0, or the error
+static int validate_pairs(int64_t n, const int32_t* counts, const locamd::PairTables& pt, const void* cross) {
+    if (pt.npair_max < 0 || (pt.npair_max > 0 && (!pt.counts || !pt.pairs || !cross))) return locamd_fail(LOC_ERR_INVALID, "joint covariance: pair arrays");
+    static const char* const kWhat[] = {nullptr, "joint covariance: a pair count outside [0, npair_max]", "joint covariance: a pair names a pose slot outside its window"};
+    if (const int bad = locamd::check_pairs(n, counts, pt)) return locamd_fail(LOC_ERR_INVALID, kWhat[bad]);
+    return LOC_OK;
+}
+// loc_window_covariance_host is the joint call without pairs (pt.npair_max = 0, cross = nullptr): one staging, classification and launch path
+int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                                     const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val,
+                                     int32_t npair_max, const int32_t* pair_counts, const int32_t* pairs,
+                                     double* cov, int32_t* mask, int32_t* status, double* cross) {
     if (!cov || !mask || !status) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
     const locamd::HostBatch b{n, poses, counts, r_val, p_val, s_val, r_idx, p_idx, s_idx};
     if (int rc = validate_instances(w, b)) return rc;
+    const locamd::PairTables pt{npair_max, pair_counts, pairs};
+    if (int rc = validate_pairs(n, counts, pt, cross)) return rc;
+    const bool joint = npair_max > 0;
     bool sched_upload = false;
-    const int kind = covariance_kind(w, b, &w->cov_aux[0], true, sched_upload);
+    const int kind = covariance_kind(w, b, pt, &w->cov_aux[0], true, sched_upload);
     if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host" LOC_COV_UNSUPPORTED);
     const locamd::WindowCaps& c = w->caps;
     LOC_HIP(hipSetDevice(w->device));
@@ -834,10 +861,16 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     }
     if (int rc = flush_anchors(w)) return rc;
     const size_t N = (size_t)n;
-    // one block: outputs [cov | mask | status], then the inputs [poses | counts | r_val | p_val | s_val | r_idx | p_idx | s_idx]
-    void* const out[3] = {cov, mask, status};
-    const size_t out_bytes[3] = {N * c.nv_max * 36 * sizeof(double), N * c.nv_max * sizeof(int32_t), N * sizeof(int32_t)};
-    const locamd::BlockLayout L = locamd::pack_block(c, N, out_bytes, 3, kPoses);
+    // one block: outputs [cov | mask | status], then the inputs [poses | counts | r_val | p_val | s_val | r_idx | p_idx | s_idx]; a joint call
+    // has [cross | pair counts | pairs] between them: a fourth output and two more inputs
+    void* const out[4] = {cov, mask, status, cross};
+    const void* const pair_in[2] = {pair_counts, pairs};
+    const size_t P = (size_t)npair_max;
+    const size_t pre_bytes[6] = {N * c.nv_max * 36 * sizeof(double), N * c.nv_max * sizeof(int32_t), N * sizeof(int32_t),
+                                 N * P * 36 * sizeof(double), N * sizeof(int32_t), N * P * 2 * sizeof(int32_t)};
+    const int n_out = joint ? 4 : 3;
+    const locamd::BlockLayout L = locamd::pack_block(c, N, pre_bytes, joint ? 6 : 3, kPoses);
+    const size_t in0 = joint ? L.pre[4] : L.tab[kPoses];   // the outputs end and the inputs begin here
     hipStream_t st = w->stream;
     char* d;
     const bool small = L.end <= kStageBytes;
@@ -845,24 +878,28 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
         if (!w->h_stage) LOC_HIP(hipHostMalloc((void**)&w->h_stage, kStageBytes, hipHostMallocDefault));
         if (!w->d_stage) LOC_HIP(hipMalloc((void**)&w->d_stage, kStageBytes));
         locamd::stage_tables(w->h_stage, L, c, b);
+        for (int k = 0; k < 2 && joint; ++k) std::memcpy(w->h_stage + L.pre[4 + k], pair_in[k], pre_bytes[4 + k]);
         d = w->d_stage;
-        LOC_HIP(hipMemcpyAsync(d + L.tab[kPoses], w->h_stage + L.tab[kPoses], L.end - L.tab[kPoses], hipMemcpyHostToDevice, st));
+        LOC_HIP(hipMemcpyAsync(d + in0, w->h_stage + in0, L.end - in0, hipMemcpyHostToDevice, st));
     } else {       // a device block of the covariance's own: the resident batch's arrays are not touched
         LOC_HIP(locamd::grow_buffers(w->cov_cap, L.end, {{w->d_cov, L.end}}));
         d = w->d_cov;
         LOC_HIP(copy_tables(c, N, locamd::tables_at(d, L).t, b.tables().t, hipMemcpyHostToDevice, &st));
+        for (int k = 0; k < 2 && joint; ++k) LOC_HIP(hipMemcpyAsync(d + L.pre[4 + k], pair_in[k], pre_bytes[4 + k], hipMemcpyHostToDevice, st));
     }
     const locamd::WindowArgs a = window_args(w, locamd::tables_at(d, L), n, nullptr, w->d_anchors, nullptr);
+    const locamd::CovPairs pp = joint ? locamd::CovPairs{(const int32_t*)(d + L.pre[4]), (const int32_t*)(d + L.pre[5]), (double*)(d + L.pre[3]), npair_max}
+                                      : locamd::CovPairs{nullptr, nullptr, nullptr, 0};
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, 0, kind, a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), st);
+    const hipError_t e = launch_covariance(w, 0, kind, w->env_blocks[0], a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), pp, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     if (small) {
-        LOC_HIP(hipMemcpyAsync(w->h_stage, d, L.tab[kPoses], hipMemcpyDeviceToHost, st));   // [cov | mask | status]
+        LOC_HIP(hipMemcpyAsync(w->h_stage, d, in0, hipMemcpyDeviceToHost, st));   // [cov | mask | status (| cross)]
         LOC_HIP(hipStreamSynchronize(st));
-        for (int k = 0; k < 3; ++k) std::memcpy(out[k], w->h_stage + L.pre[k], out_bytes[k]);
+        for (int k = 0; k < n_out; ++k) std::memcpy(out[k], w->h_stage + L.pre[k], pre_bytes[k]);
     } else {
-        for (int k = 0; k < 3; ++k) LOC_HIP(hipMemcpyAsync(out[k], d + L.pre[k], out_bytes[k], hipMemcpyDeviceToHost, st));
+        for (int k = 0; k < n_out; ++k) LOC_HIP(hipMemcpyAsync(out[k], d + L.pre[k], pre_bytes[k], hipMemcpyDeviceToHost, st));
         LOC_HIP(hipStreamSynchronize(st));
     }
     float ms = 0;
@@ -872,10 +909,21 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
     return LOC_OK;
 }
 
-int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev) {
+int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                               const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
+                               int32_t* status) {
+    return loc_window_joint_covariance_host(w, n, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val, 0, nullptr, nullptr, cov, mask, status, nullptr);
+}
+
+// loc_window_covariance_resident is the joint call without pairs, as on the host path
+int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_t npair_max, const int32_t* pair_counts_host, const int32_t* pairs_host,
+                                         void* cov_dev, void* mask_dev, void* status_dev, void* cross_dev) {
     if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
     if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
     if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
+    const locamd::PairTables pt{npair_max, pair_counts_host, pairs_host};
+    if (int rc = validate_pairs(w->n_resident, w->res_counts.data(), pt, cross_dev)) return rc;
+    const bool joint = npair_max > 0;
     LOC_HIP(hipSetDevice(w->device));
     // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
     // (an arrowhead batch likewise while option "arrow3" still admits it; the envelope pass while option "covariance_general" is 1)
@@ -903,16 +951,23 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
         LOC_HIP(copy_tables(c, N, dst, uploaded_tables(w).t, hipMemcpyDeviceToHost, nullptr));
         const locamd::HostBatch b{(int64_t)N, poses.data(), counts.data(), rval.data(), pval.data(), nullptr, ridx.data(), pidx.data(), sidx.data()};
         bool sched_upload = false;
-        const int kind = covariance_kind(w, b, &w->cov_aux[1], false, sched_upload);
+        const int kind = covariance_kind(w, b, locamd::PairTables{0, nullptr, nullptr}, &w->cov_aux[1], false, sched_upload);
         if (sched_upload) LOC_HIP(upload_tree_sched(w, w->cov_aux[1], w->stream, false));
         w->resident_cov = kind;
         w->env_switches = cov_switches(w);
+        if (kind == kCovEnvelope) { w->res_ridx.swap(ridx); w->res_sidx.swap(sidx); }   // (a joint call's pairs enlarge the envelope)
     }
     if (refused()) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
     const bool arrow = w->resident_cov == kCovArrow;
-    if (w->resident_cov == kCovEnvelope && w->env_ws_cap[1] < (size_t)w->n_resident * locamd::window_envelope_covariance_workspace_doubles(w->caps, w->env_blocks[1])) {
+    long long env_blocks = w->env_blocks[1];
+    if (w->resident_cov == kCovEnvelope && joint) {
+        const locamd::HostBatch eb{w->n_resident, nullptr, w->res_counts.data(), nullptr, nullptr, nullptr, w->res_ridx.data(), nullptr, w->res_sidx.data()};
+        env_blocks = locamd::envelope_blocks_max_joint(w->caps, eb, pt);
+        if (env_blocks < 0) return locamd_fail(LOC_ERR_INVALID, "joint covariance: pair tables");   // (cannot happen: validated above)
+    }
+    if (w->resident_cov == kCovEnvelope && w->env_ws_cap[1] < (size_t)w->n_resident * locamd::window_envelope_covariance_workspace_doubles(w->caps, env_blocks)) {
         if (int rc = wait_resident(w)) return rc;   // (as below)
-        LOC_HIP(grow_env_workspace(w, 1, w->n_resident, w->env_blocks[1]));
+        LOC_HIP(grow_env_workspace(w, 1, w->n_resident, env_blocks));
     }
     if (arrow && w->cov_ws_cap[1] < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, w->cov_list_cap[1])) {
         if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
@@ -920,10 +975,35 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     }
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    locamd::CovPairs pp{nullptr, nullptr, nullptr, 0};
+    const size_t N = (size_t)w->n_resident, cnt_bytes = (N * sizeof(int32_t) + 15) & ~(size_t)15, pair_bytes = N * (size_t)npair_max * 2 * sizeof(int32_t);
+    if (joint) {
+        // the caller's arrays are read here and never after the call returns: into the page-locked copy (once the previous call's copy has
+        // left it), from there to the device table in stream order below
+        if (w->pairs_cap < cnt_bytes + pair_bytes) {
+            if (int rc = wait_resident(w)) return rc;   // (an earlier joint launch may still read the table that is about to be replaced)
+            if (w->h_pairs) (void)hipHostFree(w->h_pairs);
+            if (w->d_pairs) (void)hipFree(w->d_pairs);
+            w->h_pairs = w->d_pairs = nullptr; w->pairs_cap = 0; w->pairs_inflight = false;
+            LOC_HIP(hipHostMalloc((void**)&w->h_pairs, cnt_bytes + pair_bytes, hipHostMallocDefault));
+            LOC_HIP(hipMalloc((void**)&w->d_pairs, cnt_bytes + pair_bytes));
+            w->pairs_cap = cnt_bytes + pair_bytes;
+        }
+        if (!w->pairs_copied) LOC_HIP(hipEventCreateWithFlags(&w->pairs_copied, hipEventDisableTiming));
+        if (w->pairs_inflight) { LOC_HIP(hipEventSynchronize(w->pairs_copied)); w->pairs_inflight = false; }
+        std::memcpy(w->h_pairs, pair_counts_host, N * sizeof(int32_t));
+        std::memcpy(w->h_pairs + cnt_bytes, pairs_host, pair_bytes);
+        pp = locamd::CovPairs{(const int32_t*)w->d_pairs, (const int32_t*)(w->d_pairs + cnt_bytes), (double*)cross_dev, npair_max};
+    }
     if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    if (joint) {   // (after that wait: an earlier joint launch on another stream has finished reading the table)
+        LOC_HIP(hipMemcpyAsync(w->d_pairs, w->h_pairs, cnt_bytes + pair_bytes, hipMemcpyHostToDevice, st));
+        LOC_HIP(hipEventRecord(w->pairs_copied, st));
+        w->pairs_inflight = true;
+    }
     const locamd::WindowArgs a = window_args(w, w->dev, w->n_resident, nullptr, w->d_anchors, nullptr);
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, 1, w->resident_cov, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, st);
+    const hipError_t e = launch_covariance(w, 1, w->resident_cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     // whatever overwrites the resident arrays next waits for this launch as well
@@ -933,16 +1013,26 @@ int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_de
     return LOC_OK;
 }
 
+int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev) {
+    return loc_window_joint_covariance_resident(w, hip_stream, 0, nullptr, nullptr, cov_dev, mask_dev, status_dev, nullptr);
+}
+
 int loc_window_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
                                int64_t* blocks_max, size_t* workspace_bytes) {
+    return loc_window_joint_covariance_plan(caps, n, counts, r_idx, s_idx, 0, nullptr, nullptr, blocks_max, workspace_bytes);
+}
+
+int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
+                                     int32_t npair_max, const int32_t* pair_counts, const int32_t* pairs, int64_t* blocks_max, size_t* workspace_bytes) {
     if (!caps || n <= 0 || !counts || !blocks_max || !workspace_bytes) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_plan arguments");
+    if (npair_max < 0 || (npair_max > 0 && (!pair_counts || !pairs))) return locamd_fail(LOC_ERR_INVALID, "loc_window_joint_covariance_plan: pair arrays");
     if (caps->nv_max <= 0 || caps->nv_max > 4096 || caps->nr_max < 0 || caps->np_max < 0 || caps->ns_max < 0)
         return locamd_fail(LOC_ERR_UNSUPPORTED, "window capacities (1 <= nv_max <= 4096)");
     if ((caps->nr_max && !r_idx) || (caps->ns_max && !s_idx)) return locamd_fail(LOC_ERR_INVALID, "missing edge arrays");
     const locamd::WindowCaps c = to_caps(caps);
     const locamd::HostBatch b{n, nullptr, counts, nullptr, nullptr, nullptr, r_idx, nullptr, s_idx};
-    const long long blocks = locamd::envelope_blocks_max(c, b);
-    if (blocks < 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_plan: counts exceed capacities, or an edge vertex index is out of range");
+    const long long blocks = locamd::envelope_blocks_max_joint(c, b, locamd::PairTables{npair_max, pair_counts, pairs});
+    if (blocks < 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_plan: counts exceed capacities, or an edge vertex index, a pair count or a pair's pose slot is out of range");
     *blocks_max = blocks;
     *workspace_bytes = (size_t)n * locamd::window_envelope_covariance_workspace_doubles(c, blocks) * sizeof(double);
     return LOC_OK;

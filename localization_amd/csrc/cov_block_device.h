@@ -7,6 +7,7 @@
 #pragma once
 #include "se3_edge_device.h"
 #include "cov_device.h"
+#include "window_kernel.h"
 
 #include <float.h>
 #include <math.h>
@@ -246,6 +247,81 @@ __device__ __forceinline__ void cov_store_window(const double* Hd, const int* mk
     }
     for (int v = lane; v < nvm; v += 64) mask[(size_t)inst * nvm + v] = v < nv ? mk[v] : 0;
     if (lane == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+}
+
+// ---- cross blocks (joint covariance calls) ----------------------------------------------------------------------------------------------
+// one step down a tree: Sigma_{v,x} = -K_v^T Sigma_{parent(v),x} (Kv = Ho[v]: K_v, rows: the parent; Kb: the running block, replaced)
+template <int D>
+__device__ __forceinline__ void cov_cross_step(const double* Kv, double* Kb, int lane, int r, int c, bool ent) {
+    double s = 0.0;
+    if (ent) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) s = __builtin_fma(Kv[k * D + r], Kb[k * D + c], s);
+    }
+    __syncthreads();
+    if (ent) Kb[lane] = -s;
+    __syncthreads();
+}
+
+// The cross blocks of window `inst` after the downward sweep of a wave-per-window pass (Hd: Sigma_v, Ho: K_v), lane = entry (r, c):
+//   Sigma_ij = M_i Sigma_aa M_j^T,  a = the lowest common ancestor of i and j,  M_i = the product of -K^T along the path i -> a
+// (the identity for i = a; no common ancestor: exact zeros).  One running D x D block in Kb: Sigma_aa, down to i, transposed, down to j.
+// parent(v): the parent's pose slot, -1 for a root (a chain: v + 1).  The pair is computed as (min, max) and transposed for the other
+// order; (i, i) is the symmetrised block cov_store_window writes.  Every walk is bounded by nv.  Uniform over the wave.
+template <int D, class Parent>
+__device__ __forceinline__ void cov_store_cross(const double* Hd, const double* Ho, double* Kb, const int* mk, int nv, bool ok, int lane, int r, int c,
+                                                bool ent, long long inst, const CovPairs& pp, Parent parent) {
+    constexpr int DD = D * D;
+    const int npr = pp.counts[inst];
+    const int32_t* pr = pp.pairs + (size_t)inst * pp.npair_max * 2;
+    double* out = pp.cross + (size_t)inst * pp.npair_max * 36;
+    for (int p = 0; p < pp.npair_max; ++p) {
+        const int pi = p < npr ? pr[2 * p] : -1, pj = p < npr ? pr[2 * p + 1] : -1;
+        if (pi < 0 || pi >= nv || pj < 0 || pj >= nv || !ok) {   // an unused slot: 0; a singular window: NaN
+            if (lane < 36) out[p * 36 + lane] = (p < npr && !ok) ? __builtin_nan("") : 0.0;
+            continue;
+        }
+        const int i = min(pi, pj), j = max(pi, pj);
+        int di = 0, dj = 0;   // depths
+        for (int v = parent(i); v >= 0 && di < nv; v = parent(v)) ++di;
+        for (int v = parent(j); v >= 0 && dj < nv; v = parent(v)) ++dj;
+        int a = i, b = j, hi = 0, hj = 0;   // the steps from i / j up to the common ancestor
+        for (; di - hi > dj - hj; ++hi) a = parent(a);
+        for (; dj - hj > di - hi; ++hj) b = parent(b);
+        for (int k = 0; k < nv && a != b && a >= 0 && b >= 0; ++k) { a = parent(a); b = parent(b); ++hi; ++hj; }
+        const bool joined = a >= 0 && a == b;
+        __syncthreads();
+        if (ent) Kb[lane] = joined ? (Hd[a * DD + r * D + c] + Hd[a * DD + c * D + r]) * 0.5 : 0.0;
+        __syncthreads();
+        if (joined) {
+            for (int s = hi - 1; s >= 0; --s) {
+                int v = i;
+                for (int k = 0; k < s; ++k) v = parent(v);
+                cov_cross_step<D>(Ho + v * DD, Kb, lane, r, c, ent);
+            }
+            if (hj > 0) {   // Sigma_ia -> Sigma_ai, then down to j: Sigma_ji
+                const double x = ent ? Kb[c * D + r] : 0.0;
+                __syncthreads();
+                if (ent) Kb[lane] = x;
+                __syncthreads();
+                for (int s = hj - 1; s >= 0; --s) {
+                    int v = j;
+                    for (int k = 0; k < s; ++k) v = parent(v);
+                    cov_cross_step<D>(Ho + v * DD, Kb, lane, r, c, ent);
+                }
+            }
+        }
+        // Kb: Sigma_ji when the second path was walked, Sigma_ij otherwise
+        if (lane < 36) {
+            const int rr = lane / 6, cc = lane % 6;
+            double x = 0.0;
+            if (rr < D && cc < D && !((mk[pi] >> rr) & 1) && !((mk[pj] >> cc) & 1)) {
+                const bool transposed = (hj == 0) != (pi == i);   // Kb's rows are not the requested pair's first pose
+                x = transposed ? Kb[cc * D + rr] : Kb[rr * D + cc];
+            }
+            out[p * 36 + lane] = x;
+        }
+    }
 }
 
 }  // namespace

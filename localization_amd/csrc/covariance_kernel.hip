@@ -56,8 +56,8 @@ __host__ __device__ inline CovLayout cov_layout(int nvl, int D, bool priors, boo
     return l;
 }
 
-template <int D, int JAC>
-__global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int nvl, bool priors, bool se3, double* cov, int32_t* mask, int32_t* status) {
+template <int D, int JAC, bool JOINT>
+__global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int nvl, bool priors, bool se3, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int DD = D * D;
     constexpr int RS = 1 + 2 * D;
     const int lane = threadIdx.x;
@@ -170,14 +170,21 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
     for (int i = 0; i < nv; ++i) cov_eliminate_block<D>(Hd, Ho, dg, Kb, i, i + 1 < nv, i + 1, lane, r, c, ent, ok);
     for (int i = nv - 2; i >= 0; --i) cov_back_substitute_block<D>(Hd, Ho, Kb, i, i + 1, lane, r, c, ent);
     cov_store_window<D>(Hd, mk, nv, nvm, ok, lane, inst, cov, mask, status);
+    // ---- joint calls: Sigma_ij = (-K_i^T) .. (-K_{j-1}^T) Sigma_jj for i < j (the chain is the forest with parent = next pose) ------------------
+    if (JOINT) cov_store_cross<D>(Hd, Ho, Kb, mk, nv, ok, lane, r, c, ent, inst, pp, [nv](int v) { return v + 1 < nv ? v + 1 : -1; });
 }
 
-template <int D, int JAC>
-hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC>>(160 * 1024);
+template <int D, int JAC, bool JOINT>
+hipError_t launch_cov_j(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC, JOINT>>(160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((covariance_kernel<D, JAC>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status);
+    hipLaunchKernelGGL((covariance_kernel<D, JAC, JOINT>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status, pp);
     return hipGetLastError();
+}
+template <int D, int JAC>
+hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    return pp.cross ? launch_cov_j<D, JAC, true>(a, nvl, priors, se3, lds, cov, mask, status, pp, stream)
+                    : launch_cov_j<D, JAC, false>(a, nvl, priors, se3, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace
@@ -186,16 +193,16 @@ size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3) {
     return cov_layout(c.nv_max, d3 ? 3 : 6, c.np_max > 0, !d3 && c.ns_max > 0).bytes;
 }
 
-hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
+hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     if (a.caps.nv_max > 64) return hipErrorInvalidValue;
     const bool priors = a.caps.np_max > 0, se3 = !d3 && a.caps.ns_max > 0;
     const size_t lds = window_covariance_lds_bytes(a.caps, d3);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (d3) return a.jacobian ? launch_cov_t<3, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream)
-                              : launch_cov_t<3, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream);
-    return a.jacobian ? launch_cov_t<6, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream)
-                      : launch_cov_t<6, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, stream);
+    if (d3) return a.jacobian ? launch_cov_t<3, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream)
+                              : launch_cov_t<3, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream);
+    return a.jacobian ? launch_cov_t<6, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream)
+                      : launch_cov_t<6, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace locamd

@@ -20,7 +20,7 @@
 //
 // Mapping: thread = (slot, entry) = (tid / 36, tid % 36): seven 6 x 6 blocks in flight, the last four threads of the workgroup only
 // linearise.
-//   * profile: first[] by integer LDS atomicMin over the edges, last[j] = max {k : first[k] <= j} (atomicMax + a running maximum), off[];
+//   * profile: first[] by integer LDS atomicMin over the edges (and, in a joint call, over the requested pairs), last[j] = max {k : first[k] <= j} (atomicMax + a running maximum), off[];
 //   * linearisation: thread = edge, the records of cov_block_device.h in one LDS region (256 ranges / 128 priors / 64 EdgeSE3 per pass);
 //   * assembly: the block ROW decides the owner (row % 7 = slot), every owner walks the chunk's records in edge order and adds its
 //     own — no floating-point atomics, every entry summed in edge order whatever the number of threads: the same bits on every run;
@@ -89,8 +89,8 @@ __device__ __forceinline__ int env_column_rows(int j, const int* first, const in
     return m;
 }
 
-template <int JAC>
-__global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(const WindowArgs a, double* ws, size_t ws_stride, int blocks_cap, double* cov, int32_t* mask, int32_t* status) {
+template <int JAC, bool JOINT>
+__global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(const WindowArgs a, double* ws, size_t ws_stride, int blocks_cap, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int D = 6, DD = 36, RS = 13, S = kEvSlots;
     const int tid = threadIdx.x;
     const long long inst = blockIdx.x;
@@ -127,6 +127,13 @@ __global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(cons
     for (int e = tid; e < ns; e += kEvThreads) {
         const int32_t* ix = a.s_idx + ((size_t)inst * cp.ns_max + e) * 4;
         atomicMin(&first[max(ix[0], ix[1])], min(ix[0], ix[1]));
+    }
+    if (JOINT) {   // a requested pair is one more edge (a structural zero): the selected inversion then leaves Sigma_ij in its block
+        const int npr = min(pp.counts[inst], pp.npair_max);
+        for (int p = tid; p < npr; p += kEvThreads) {
+            const int32_t* ix = pp.pairs + ((size_t)inst * pp.npair_max + p) * 2;
+            if (ix[0] >= 0 && ix[0] < nv && ix[1] >= 0 && ix[1] < nv) atomicMin(&first[max(ix[0], ix[1])], min(ix[0], ix[1]));
+        }
     }
     __syncthreads();
     for (int v = tid; v < nv; v += kEvThreads) atomicMax(&last[first[v]], v);
@@ -403,14 +410,39 @@ __global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(cons
     }
     for (int v = tid; v < nvm; v += kEvThreads) mask[(size_t)inst * nvm + v] = (v < nv && fits) ? mk[v] : 0;
     if (tid == 0) status[inst] = ok ? 0 : -6;   // LOC_OK / LOC_ERR_SINGULAR
+
+    // ---- joint calls: Sigma_ij from the block (max, min) of the envelope, thread = (pair, entry); (i, i) as the store above ----------------------
+    if (JOINT) {
+        const int npr = pp.counts[inst];
+        const int32_t* pr = pp.pairs + (size_t)inst * pp.npair_max * 2;
+        double* xo = pp.cross + (size_t)inst * pp.npair_max * 36;
+        for (int k = tid; k < pp.npair_max * 36; k += kEvThreads) {
+            const int p = k / 36, rr = (k % 36) / 6, cc = k % 6;
+            const int pi = p < npr ? pr[2 * p] : -1, pj = p < npr ? pr[2 * p + 1] : -1;
+            double x = 0.0;
+            if (pi >= 0 && pi < nv && pj >= 0 && pj < nv) {
+                if (!ok) x = __builtin_nan("");
+                else if (!((mk[pi] >> rr) & 1) && !((mk[pj] >> cc) & 1)) {
+                    if (pi == pj) { const double* sg = blk(pi, pi); x = (sg[rr * D + cc] + sg[cc * D + rr]) * 0.5; }
+                    else x = pi > pj ? blk(pi, pj)[rr * D + cc] : blk(pj, pi)[cc * D + rr];   // (rows of a stored block: the later pose)
+                }
+            }
+            xo[k] = x;
+        }
+    }
 }
 
-template <int JAC>
-hipError_t launch_env_cov_t(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&envelope_covariance_kernel<JAC>>(160 * 1024);
+template <int JAC, bool JOINT>
+hipError_t launch_env_cov_j(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<&envelope_covariance_kernel<JAC, JOINT>>(160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((envelope_covariance_kernel<JAC>), dim3((unsigned)a.B), dim3(kEvThreads), lds, stream, a, ws, ws_stride, blocks, cov, mask, status);
+    hipLaunchKernelGGL((envelope_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(kEvThreads), lds, stream, a, ws, ws_stride, blocks, cov, mask, status, pp);
     return hipGetLastError();
+}
+template <int JAC>
+hipError_t launch_env_cov_t(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    return pp.cross ? launch_env_cov_j<JAC, true>(a, ws, ws_stride, blocks, lds, cov, mask, status, pp, stream)
+                    : launch_env_cov_j<JAC, false>(a, ws, ws_stride, blocks, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace
@@ -421,14 +453,14 @@ size_t window_envelope_covariance_workspace_doubles(const WindowCaps& c, long lo
     return ((size_t)blocks + (size_t)c.nv_max) * 36 + (size_t)c.nv_max * 6;
 }
 
-hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
+hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     if (!ws || blocks < 0 || blocks > (1ll << 30)) return hipErrorInvalidValue;
     const size_t lds = window_envelope_covariance_lds_bytes(a.caps);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const size_t stride = window_envelope_covariance_workspace_doubles(a.caps, blocks);
-    return a.jacobian ? launch_env_cov_t<1>(a, ws, stride, (int)blocks, lds, cov, mask, status, stream)
-                      : launch_env_cov_t<0>(a, ws, stride, (int)blocks, lds, cov, mask, status, stream);
+    return a.jacobian ? launch_env_cov_t<1>(a, ws, stride, (int)blocks, lds, cov, mask, status, pp, stream)
+                      : launch_env_cov_t<0>(a, ws, stride, (int)blocks, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace locamd

@@ -53,8 +53,8 @@ __host__ __device__ inline ForestCovLayout forest_cov_layout(int nv, bool priors
     return l;
 }
 
-template <int JAC>
-__global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs a, const TreeSched ts, double* cov, int32_t* mask, int32_t* status) {
+template <int JAC, bool JOINT>
+__global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs a, const TreeSched ts, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int D = 6, DD = 36, RS = 13;
     const int lane = threadIdx.x;
     const long long inst = blockIdx.x;
@@ -160,14 +160,20 @@ __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs 
         if (p >= 0) cov_back_substitute_block<D>(Hd, Ho, Kb, v, p, lane, r, c, ent);
     }
     cov_store_window<D>(Hd, mk, nv, nvm, ok, lane, inst, cov, mask, status);
+    // ---- joint calls: the cross blocks through the lowest common ancestor, on the parent table in LDS ----------------------------------------
+    if (JOINT) cov_store_cross<D>(Hd, Ho, Kb, mk, nv, ok, lane, r, c, ent, inst, pp, [ps](int v) { return ps[v]; });
 }
 
-template <int JAC>
-hipError_t launch_forest_cov_t(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC>>(160 * 1024);
+template <int JAC, bool JOINT>
+hipError_t launch_forest_cov_j(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC, JOINT>>(160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((forest_covariance_kernel<JAC>), dim3((unsigned)a.B), dim3(64), lds, stream, a, ts, cov, mask, status);
+    hipLaunchKernelGGL((forest_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(64), lds, stream, a, ts, cov, mask, status, pp);
     return hipGetLastError();
+}
+template <int JAC>
+hipError_t launch_forest_cov_t(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    return pp.cross ? launch_forest_cov_j<JAC, true>(a, ts, lds, cov, mask, status, pp, stream) : launch_forest_cov_j<JAC, false>(a, ts, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace
@@ -176,13 +182,13 @@ size_t window_forest_covariance_lds_bytes(const TreeSched& ts) {
     return forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes;
 }
 
-hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, hipStream_t stream) {
+hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     // (the LDS blocks are indexed by pose slot and the tables by edge number: the schedule must be the batch's own)
     if (ts.nv < 2 || ts.nv > 64 || ts.nv > a.caps.nv_max || ts.nr > a.caps.nr_max || ts.np > a.caps.np_max || ts.ns > a.caps.ns_max) return hipErrorInvalidValue;
     const size_t lds = window_forest_covariance_lds_bytes(ts);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    return a.jacobian ? launch_forest_cov_t<1>(a, ts, lds, cov, mask, status, stream) : launch_forest_cov_t<0>(a, ts, lds, cov, mask, status, stream);
+    return a.jacobian ? launch_forest_cov_t<1>(a, ts, lds, cov, mask, status, pp, stream) : launch_forest_cov_t<0>(a, ts, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace locamd

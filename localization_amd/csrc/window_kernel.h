@@ -122,29 +122,40 @@ struct TreeSched {
                               //      consecutive columns); roots: nv - nroots, nv - nroots + 1, ...
     int nv, nr, np, ns, depth, nroots, nlev, max_se3_per_node, nu, max_r_per_node;
 };
+// The pose pairs of a joint covariance call (loc_window_joint_covariance_*), device arrays.  cross == nullptr: the plain call
+// (the passes' kernels without any pair code).  Otherwise every pass also writes cross[b][p] = [H^-1]_ij for the pairs p < counts[b] of
+// window b (6x6 row-major, rows: pose i; excluded rows / columns 0; NaN for a singular window) and 0 for the slots p >= counts[b].  The
+// host has checked every slot (window_structure.cpp: check_pairs).
+struct CovPairs {
+    const int32_t* counts;   // [B]
+    const int32_t* pairs;    // [B][npair_max][2]  pose slots i, j
+    double* cross;           // [B][npair_max][36]
+    int npair_max;
+};
+
 // marginal pose covariances of chain windows of <= 64 poses at a.poses (covariance_kernel.hip): one wave per window, 3x3 blocks for
 // translation-only batches (d3), 6x6 otherwise; cov [B][nv_max][36], mask [B][nv_max], status [B] (device arrays)
 size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3);
-hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream);
 
 // the same for forest windows of ONE shared topology of <= 64 poses (forest_covariance_kernel.hip): one wave per window on the solve
 // kernels' elimination schedule, always 6x6 blocks
 size_t window_forest_covariance_lds_bytes(const TreeSched& ts);
-hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream);
 
 // the same for translation-only arrowhead windows (arrow_covariance_kernel.hip: the windows arrow3_lm_kernel solves; border = the last slots
 // by build_arrow_aux's rule, recomputed on the device), one workgroup per window, 3x3 blocks.  ws: [B][window_arrow_covariance_workspace_doubles]
 // in HBM (edge records, B, Y = A^-1 B and a list of `cap` edges per pose); cap: the most edges and priors any pose in front of the border has
 size_t window_arrow_covariance_lds_bytes(const WindowCaps& c);
 size_t window_arrow_covariance_workspace_doubles(const WindowCaps& c, int cap);
-hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream);
 
 // the same for windows of any structure and length (envelope_covariance_kernel.hip: what the three passes above decline), one workgroup per
 // window, 6x6 blocks, block LDL^T and selected inversion on the envelope of the caller's pose order.  blocks: the batch's largest envelope
 // (window_structure.cpp: envelope_blocks_max); ws: [B][window_envelope_covariance_workspace_doubles] in HBM (the envelope, one column, diag(H))
 size_t window_envelope_covariance_lds_bytes(const WindowCaps& c);
 size_t window_envelope_covariance_workspace_doubles(const WindowCaps& c, long long blocks);
-hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, hipStream_t stream);
+hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream);
 
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);

@@ -55,6 +55,24 @@ int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b) {
     return first_bad.load();
 }
 
+// Host-side check of the pair tables of a joint covariance call: the kernels index LDS and the workspace with these slots
+int check_pairs(int64_t n, const int32_t* counts, const PairTables& pt) {
+    if (pt.npair_max <= 0) return 0;
+    std::atomic<int> first_bad{0};
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t i = lo; i < hi && first_bad.load(std::memory_order_relaxed) == 0; ++i) {
+            const int32_t nv = counts[i * 4], np = pt.counts[i];
+            int bad = np < 0 || np > pt.npair_max ? 1 : 0;
+            for (int p = 0; p < np && !bad; ++p) {
+                const int32_t* ix = pt.pairs + ((size_t)i * pt.npair_max + p) * 2;
+                if (ix[0] < 0 || ix[0] >= nv || ix[1] < 0 || ix[1] >= nv) bad = 2;
+            }
+            if (bad) { int zero = 0; first_bad.compare_exchange_strong(zero, bad); return; }
+        }
+    });
+    return first_bad.load();
+}
+
 // translation-only (the exact 3-DoF reduction, chain3_kernel.hip / arrow3_kernel.hip): no EdgeSE3, every lever arm zero, every
 // rotation the identity, priors with an identity measurement rotation and no rotation information
 bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b) {
@@ -162,7 +180,10 @@ unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const Host
 // The envelope (skyline) of every instance's block matrix in the caller's pose order, as envelope_covariance_kernel.hip lays it out: row i
 // holds the blocks (i, first[i]) .. (i, i).  Returns the largest block count of the batch, -1 when a count or an index is out of range
 // (loc_window_covariance_plan calls this on tables no handle has validated).
-long long envelope_blocks_max(const WindowCaps& c, const HostBatch& b) {
+long long envelope_blocks_max(const WindowCaps& c, const HostBatch& b) { return envelope_blocks_max_joint(c, b, PairTables{0, nullptr, nullptr}); }
+
+// Pairs count as edges: a pair count or a slot out of range is -1 as well.
+long long envelope_blocks_max_joint(const WindowCaps& c, const HostBatch& b, const PairTables& pt) {
     std::atomic<long long> most{0};
     std::atomic<bool> bad{false};
     parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int) {
@@ -188,6 +209,14 @@ long long envelope_blocks_max(const WindowCaps& c, const HostBatch& b) {
             for (int e = 0; e < ns; ++e) {
                 const int32_t* ix = b.s_idx + ((size_t)i * c.ns_max + e) * 4;
                 if (ix[1] < 0 || !join(ix[0], ix[1])) { bad.store(true); return; }
+            }
+            if (pt.npair_max > 0) {
+                const int32_t np = pt.counts[i];
+                if (np < 0 || np > pt.npair_max) { bad.store(true); return; }
+                for (int p = 0; p < np; ++p) {
+                    const int32_t* ix = pt.pairs + ((size_t)i * pt.npair_max + p) * 2;
+                    if (ix[1] < 0 || !join(ix[0], ix[1])) { bad.store(true); return; }
+                }
             }
             long long blocks = 0;
             for (int v = 0; v < nv; ++v) blocks += v - first[(size_t)v] + 1;

@@ -32,6 +32,13 @@ unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const Host
 // the largest number of envelope blocks any instance has (envelope_covariance_kernel.hip's profile: sum over the pose slots i of
 // i - first[i] + 1, first[i] = the smallest slot a pose-to-pose edge joins to i); reads counts, r_idx and s_idx alone; -1: an index out of range
 long long envelope_blocks_max(const WindowCaps& c, const HostBatch& b);
+// the pose pairs of a joint covariance call (loc_window_joint_covariance_*), host arrays: counts [n], pairs [n][npair_max][2] pose slots
+struct PairTables { int32_t npair_max; const int32_t* counts; const int32_t* pairs; };
+// 0, or the first check that failed: 1 a pair count outside [0, npair_max], 2 a pose slot outside [0, nv) of its window.  counts: the
+// batch's [n][4] table, already checked (check_instances)
+int check_pairs(int64_t n, const int32_t* counts, const PairTables& pt);
+// envelope_blocks_max with every requested pair taken as one more pose-to-pose edge (the envelope pass keeps Sigma_ij in the block it adds)
+long long envelope_blocks_max_joint(const WindowCaps& c, const HostBatch& b, const PairTables& pt);
 bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only = false);   // fills A.h_a* and A.arrow_*
 bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);                // fills A.h_tsched and A.tsched's sizes
 

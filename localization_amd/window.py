@@ -85,6 +85,33 @@ def covariance_plan(wb: WindowBatch):
     return blocks.value, nbytes.value
 
 
+def _pair_tables(B, pairs, pair_counts):
+    """(npair_max, pair_counts int32 [B], pairs int32 [B][npair_max][2]) as the joint covariance calls take them.  pairs: [B][npair_max][2],
+    or [npair_max][2] for every window alike; pair_counts None: every window has all npair_max pairs.  Nothing is checked here: the
+    library validates every count and slot."""
+    pairs = np.asarray(pairs, dtype=np.int32)
+    if pairs.ndim == 2:
+        pairs = np.broadcast_to(pairs, (B,) + pairs.shape)
+    assert pairs.ndim == 3 and pairs.shape[0] == B and pairs.shape[2] == 2
+    pairs = np.ascontiguousarray(pairs)
+    npm = pairs.shape[1]
+    pair_counts = np.full(B, npm, dtype=np.int32) if pair_counts is None else np.ascontiguousarray(pair_counts, dtype=np.int32).reshape(B)
+    return npm, pair_counts, pairs
+
+
+def joint_covariance_plan(wb: WindowBatch, pairs, pair_counts=None):
+    """covariance_plan(wb) for a joint call: the envelope pass keeps [H^-1]_ij of a requested pair in the block that pair adds to the envelope
+    (loc_window_joint_covariance_plan).  Without pairs: covariance_plan(wb)."""
+    ip = C.POINTER(C.c_int32)
+    caps = WindowCaps(*wb.caps, -1)
+    npm, pc, pr = _pair_tables(wb.B, pairs, pair_counts)
+    blocks, nbytes = C.c_int64(), C.c_size_t()
+    check(lib().loc_window_joint_covariance_plan(C.byref(caps), wb.B, wb.counts.ctypes.data_as(ip), wb.r_idx.ctypes.data_as(ip),
+                                                 wb.s_idx.ctypes.data_as(ip), npm, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip),
+                                                 C.byref(blocks), C.byref(nbytes)))
+    return blocks.value, nbytes.value
+
+
 class WindowSolver(_lib.Handle):
     _prefix = "loc_window"
 
@@ -182,6 +209,51 @@ class WindowSolver(_lib.Handle):
         """covariance_plan(wb) for this handle's capacities"""
         assert wb.caps == self.caps
         return covariance_plan(wb)
+
+    # ---- joint marginals: covariance() and the cross blocks [H^-1]_ij of requested pose pairs (loc_window_joint_covariance_*; DESIGN.md §2)
+    def joint_covariance(self, wb: WindowBatch, pairs, pair_counts=None, out=None):
+        """covariance(wb) and cross [B][npair_max][6][6]: cross[b][p] = [H^-1]_ij for pair p = (i, j) of window b (rows: pose i's
+        coordinates; excluded rows / columns 0; NaN for a singular window; slots p >= pair_counts[b] are 0).  pairs: int [B][npair_max][2]
+        pose slots, or [npair_max][2] for every window alike; pair_counts: [B], None = all of them.  Same coverage as covariance(); a pair
+        count or a slot out of range raises LOC_ERR_INVALID with nothing written.  Returns (cov, mask, status, cross)."""
+        assert wb.caps == self.caps and wb.B <= self.B
+        if getattr(wb, "r_off1", None) is not None:
+            raise _lib.LocalizationAmdError(-5, "covariance: windows with endpoint-1 lever arms are not supported")
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        npm, pc, pr = _pair_tables(wb.B, pairs, pair_counts)
+        if out is None:
+            out = (np.zeros((wb.B, self.caps[0], 6, 6)), np.zeros((wb.B, self.caps[0]), dtype=np.int32), np.zeros(wb.B, dtype=np.int32),
+                   np.zeros((wb.B, npm, 6, 6)))
+        cov, mask, status, cross = out   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
+        assert cov.dtype == np.float64 and cov.size >= wb.B * self.caps[0] * 36 and cov.flags["C_CONTIGUOUS"]
+        assert mask.dtype == np.int32 and mask.size >= wb.B * self.caps[0] and status.dtype == np.int32 and status.size >= wb.B
+        assert cross.dtype == np.float64 and cross.size >= wb.B * npm * 36 and cross.flags["C_CONTIGUOUS"]
+        check(self.L.loc_window_joint_covariance_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
+                                                      wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
+                                                      wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
+                                                      wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp),
+                                                      npm, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip),
+                                                      cov.ctypes.data_as(dp), mask.ctypes.data_as(ip), status.ctypes.data_as(ip), cross.ctypes.data_as(dp)))
+        return cov, mask, status, cross
+
+    def joint_covariance_resident(self, pairs, pair_counts, cov, mask, status, cross, stream=None):
+        """joint_covariance for the uploaded batch at its solved poses, asynchronous: pairs / pair_counts numpy arrays as above (read before
+        the call returns), cov / mask / status / cross torch device tensors (cross float64 [B][npair_max][6][6] or [..][36])."""
+        import torch
+        n = getattr(self, "_resident", 0)
+        npm, pc, pr = _pair_tables(n, pairs, pair_counts)
+        for t, dt, numel in ((cov, torch.float64, n * self.caps[0] * 36), (mask, torch.int32, n * self.caps[0]), (status, torch.int32, n),
+                             (cross, torch.float64, n * npm * 36)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= numel
+        ip = C.POINTER(C.c_int32)
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_joint_covariance_resident(self.h, st, npm, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip), C.c_void_p(cov.data_ptr()),
+                                                          C.c_void_p(mask.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(cross.data_ptr())))
+
+    def joint_covariance_plan(self, wb: WindowBatch, pairs, pair_counts=None):
+        """joint_covariance_plan(wb, pairs, pair_counts) for this handle's capacities"""
+        assert wb.caps == self.caps
+        return joint_covariance_plan(wb, pairs, pair_counts)
 
     def last_covariance_ms(self):
         ms = C.c_double()
