@@ -9,12 +9,14 @@
 #include <vector>
 
 #include "capi_host.h"
+#include "window_dispatch.h"
 #include "window_kernel.h"
 #include "window_structure.h"
 #include "window_tables.h"
 
 using locamd::kPoses;
 using locamd::kCounts;
+using locamd::CovKind;
 
 struct loc_window {
     int device = 0;
@@ -22,7 +24,7 @@ struct loc_window {
     locamd::WindowCaps caps{};
     int n_anchors = 0, anchors_cap = 0;
     int iterations = 10;
-    int jacobian = LOC_JAC_NUMERIC_G2O, natural_order = 0;   // default = the reference's configuration
+    int jacobian = LOC_JAC_NUMERIC_G2O;   // default = the reference's configuration (as is opt.natural_order = false)
     double* d_anchors = nullptr;
     std::vector<double> h_anchors;   // handles of <= 4 windows (a node's own): the table as last set; the device copy follows on demand
     bool anchors_dirty = false;
@@ -32,38 +34,37 @@ struct loc_window {
     double* d_poses_in = nullptr;   // resident mode: the uploaded initial estimates (every resident solve starts from them)
     double* d_chain_ws = nullptr;   // chain windows (one lane per window, chain_kernel.hip: chain_lm_kernel): its workspace
     double* d_chain3_ws = nullptr;  // translation-only chain windows (chain3_kernel.hip)
-    locamd::WinAux aux[2];   // [0]: loc_window_solve_host calls; [1]: the resident batch's from its upload on (a host-path solve in between must not disturb it)
+    // What belongs to ONE batch: slot[0] is the host path's (loc_window_solve_host, loc_window_covariance_host), slot[1] the resident batch's
+    // from its upload on (a host-path call in between must not disturb it).
+    struct BatchSlot {
+        locamd::WinAux aux;       // the solve's host-built tables.  The host path's topology cache and the resident solve rely on them: no covariance call writes here
+        // forest batches (forest_covariance_kernel.hip): the schedule the covariance pass builds itself — slot[0]'s is kept with the hash of
+        // the structure it was built for (cov_sched), slot[1]'s is for a resident batch no solve classified as a forest.
+        // arrowhead batches (arrow_covariance_kernel.hip): cov_aux takes build_arrow_aux's structure test (never aux: the solve's packed tables stay as they are)
+        locamd::WinAux cov_aux;
+        double* d_cov_ws = nullptr;   // the arrowhead pass's HBM workspace (records, B, Y, the poses' edge lists), allocated on first use and grown on demand
+        size_t cov_ws_cap = 0;        // doubles
+        int cov_list_cap = 0;         // list size the batch was classified with
+        // any other batch (envelope_covariance_kernel.hip, option "covariance_general"): the kernel's HBM workspace (the envelope of every window,
+        // one column, diag(H)), grown on demand; the batch's largest envelope in blocks
+        double* d_env_ws = nullptr;
+        size_t env_ws_cap = 0;        // doubles
+        long long env_blocks = 0;
+    } slot[2];
     double* d_tree_ws = nullptr;    // workspaces (used only while a launch runs)
     double* d_arrow_ws = nullptr;
-    int arrow_ws_nb = 0;            // border size d_arrow_ws was allocated for
-    double* d_roff1 = nullptr;      // optional lever arms of endpoint 1 (loc_window_set_endpoint1_offsets), [B][nr_max][3]
-    bool has_off1 = false;
+    size_t arrow_ws_nb = 0;         // border size d_arrow_ws was allocated for
+    double* d_roff1 = nullptr;      // optional lever arms of endpoint 1 (loc_window_set_endpoint1_offsets: opt.has_off1), [B][nr_max][3]
     int resident_topology = 0;      // LOC_WINDOW_KERNEL_* the uploaded batch qualifies for by its structure (the batch-size threshold is applied per solve)
-    long long chain_min = -1;       // smallest batch that takes a lane-per-window kernel (-1: the default / LOCAMD_CHAIN_MIN_BATCH)
     long long n_resident = 0;
     int resident_min_anchors = 0;   // anchors the resident batch references (loc_window_set_anchors may not shrink below it)
     bool resident_solved = false;   // a resident solve has run since the upload (loc_window_download has something to fetch)
     int last_kind = -1;             // LOC_WINDOW_KERNEL_* of the last launch
     hipEvent_t resident_done = nullptr;  // recorded after every resident launch on the stream it ran on: whatever touches the shared
     bool resident_inflight = false;      // device state waits for THIS (the caller's stream is not kept: it may be destroyed any time)
-    // kernel-selection switches: the environment is read ONCE, here at creation (loc_window_set_option changes them afterwards)
-    struct Opts {
-        long long env_chain_min = 12288;   // LOCAMD_CHAIN_MIN_BATCH, or the default
-        bool env_chain_min_set = false;
-        int arrow3 = -1;                   // LOCAMD_ARROW3: -1 default (windows of more than 64 poses), 0 never, 1 whenever the batch qualifies
-        int tree = -1;                     // LOCAMD_TREE: -1 default, 0 never, 2 the lane-per-window variant
-        bool wave3 = true, wave6 = true, chain3 = true, zero_copy = true, topology_cache = true;
-        bool cov_general = false;          // "covariance_general" 1: whatever the three structured covariance passes decline goes to envelope_covariance_kernel.hip
-        bool kernel_events = true;         // "kernel_events" 0: no HIP events around the launch of a zero-copy solve (loc_window_last_kernel_ms then reports launch-to-completion on the host clock)
-    } opt;
-    // structural verdict of the last host-path batch, keyed on a hash of (n, counts, index tables): a caller that replays one graph
-    // with new measurements (the node's window between two slides, a Monte-Carlo batch) skips the chain / forest / arrowhead tests
-    struct TopoCache {
-        bool valid = false;
-        unsigned long long key = 0;
-        int64_t n = 0;
-        bool chain = false, single_pairs = false, se3_pairs = false, tree_ok = false, tree_tried = false;
-    } topo_cache;
+    locamd::DispatchOpts opt;       // the kernel-selection switches (window_dispatch.h)
+    locamd::DispatchFits fits;      // what the capacities alone decide, from loc_window_create
+    locamd::TopoCache topo_cache;   // the host path's structural verdict
     double t_validate_ms = 0, t_topology_ms = 0, t_run_ms = 0;   // loc_window_last_host_timing
     bool t_cached = false;
     hipStream_t stream = nullptr;
@@ -79,29 +80,10 @@ struct loc_window {
     hipEvent_t cov_ev0 = nullptr, cov_ev1 = nullptr;
     bool cov_pending = false;       // the events of a resident covariance launch have not been read yet
     double cov_ms = 0.0;
-    int resident_cov = 0;           // 3 / 6: the resident chain batch's block size; kCovForest / kCovForestOwn: a forest batch on aux[1]'s /
-                                    // cov_aux[1]'s schedule; kCovArrow: an arrowhead batch; kCovEnvelope: none of these, taken by the envelope
-                                    // pass (option "covariance_general"); 0: not a covariance batch; -1: not classified yet
-    // forest batches (forest_covariance_kernel.hip): the schedules the covariance pass builds itself — [0] for loc_window_covariance_host
-    // (kept with the hash of the structure it was built for), [1] for a resident batch no solve classified as a forest.  Never aux[0] /
-    // aux[1]: the host path's topology cache and the resident solve rely on those.
-    // arrowhead batches (arrow_covariance_kernel.hip): cov_aux[.] takes build_arrow_aux's structure test (never aux[.]: the solve's packed
-    // tables stay as they are); the kernel's HBM workspace (records, B, Y, the poses' edge lists), one for the host path and one for the
-    // resident batch, allocated on first use and grown on demand
-    double* d_cov_ws[2] = {nullptr, nullptr};
-    size_t cov_ws_cap[2] = {0, 0};   // doubles
-    int cov_list_cap[2] = {0, 0};    // list size the batch was classified with
-    locamd::WinAux cov_aux[2];
-    // any other batch (envelope_covariance_kernel.hip, option "covariance_general"): the kernel's HBM workspace (the envelope of every window,
-    // one column, diag(H)), one for the host path and one for the resident batch, grown on demand; the batch's largest envelope in blocks
-    double* d_env_ws[2] = {nullptr, nullptr};
-    size_t env_ws_cap[2] = {0, 0};   // doubles
-    long long env_blocks[2] = {0, 0};
-    long long env_switches = 0;      // cov_switches() when the resident batch was handed to the envelope pass: a change of the switches the three
-                                     // structured tests read classifies it again
-    bool cov_sched_valid = false;
-    unsigned long long cov_sched_key = 0;
-    int64_t cov_sched_n = 0;
+    CovKind resident_cov = CovKind::None;   // the resident batch's pass; Unclassified: the first covariance call finds out
+    long long env_switches = 0;      // cov_switches() when the resident batch was classified: a change of the switches the three structured
+                                     // tests read classifies a batch the envelope pass holds again
+    locamd::SchedKey cov_sched;      // the structure slot[0].cov_aux's forest schedule was built (and uploaded) for
     // joint covariance calls (loc_window_joint_covariance_resident): the resident batch's counts as uploaded (the pair check needs every
     // window's nv) and, once the envelope pass holds the batch, its pose-to-pose index tables (the pairs enlarge the envelope); the call's pair
     // tables [counts | pairs] as a page-locked copy and as the device table the kernel reads, grown on demand
@@ -113,7 +95,6 @@ struct loc_window {
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
-static constexpr int kCovForest = 7, kCovForestOwn = 8, kCovArrow = 9, kCovEnvelope = 10;   // loc_window::resident_cov
 
 extern "C" {
 
@@ -132,15 +113,20 @@ size_t loc_window_lds_bytes(const loc_window_caps* caps) {
     return (in_lds <= 160 * 1024 - 512 && c.nv_max <= 64) ? in_lds : locamd::window_lds_bytes(c, true) + 36 * sizeof(double);  // large windows: index tables + exchange block; the rest in the HBM workspace
 }
 
+// every device buffer of one batch's slot
+static void release_slot(loc_window::BatchSlot& S) {
+    for (locamd::WinAux* A : {&S.aux, &S.cov_aux})
+        for (void* p : {(void*)A->d_tsched, (void*)A->d_ahdr, (void*)A->d_arslot, (void*)A->d_arec, (void*)A->d_aprec}) if (p) (void)hipFree(p);
+    if (S.d_cov_ws) (void)hipFree(S.d_cov_ws);
+    if (S.d_env_ws) (void)hipFree(S.d_env_ws);
+}
+
 int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
-    void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in,
-                    w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_tree_ws, w->d_arrow_ws,
-                    w->aux[0].d_tsched, w->aux[0].d_ahdr, w->aux[0].d_arslot, w->aux[0].d_arec, w->aux[0].d_aprec,
-                    w->aux[1].d_tsched, w->aux[1].d_ahdr, w->aux[1].d_arslot, w->aux[1].d_arec, w->aux[1].d_aprec,
-                    w->cov_aux[0].d_tsched, w->cov_aux[1].d_tsched, w->d_cov_ws[0], w->d_cov_ws[1], w->d_env_ws[0], w->d_env_ws[1]};
+    void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_tree_ws, w->d_arrow_ws};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
     w->timer.destroy();
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -176,6 +162,17 @@ int loc_window_create(loc_window** out, int32_t device, int64_t batch, const loc
     if (!w) return locamd_fail(LOC_ERR_INVALID, "out of host memory");
     w->device = device; w->B = batch; w->n_anchors = n_anchors; w->anchors_cap = n_anchors > 0 ? n_anchors : 1; w->iterations = maximum_iteration;
     w->caps = to_caps(caps);
+    {   // the kernels' LDS needs depend on the capacities alone
+        const locamd::WindowCaps& c = w->caps;
+        locamd::DispatchFits& f = w->fits;
+        f.nv_max = c.nv_max;
+        f.wave6 = c.nv_max <= 64 && locamd::window_wave6_lds_bytes(c) <= locamd::kWave6MaxLds;
+        f.wave6_se3 = c.nv_max <= 63 && c.ns_max <= 64 && locamd::window_wave6_lds_bytes(c, true) <= locamd::kWave6MaxLds;
+        f.wave3 = c.nv_max <= 64 && locamd::window_wave3_lds_bytes(c) <= 64 * 1024;
+        f.cov_chain = locamd::window_covariance_lds_bytes(c, false) <= 160 * 1024;
+        f.cov_arrow = locamd::window_arrow_covariance_lds_bytes(c) <= 160 * 1024;
+        f.cov_envelope = locamd::window_envelope_covariance_lds_bytes(c) <= 160 * 1024;
+    }
     // windows of more than 64 poses always keep their arrays in the HBM workspace (their structure tables alone fill the LDS)
     const bool global_a = locamd::window_lds_bytes(w->caps, false) > 160 * 1024 - 512 || w->caps.nv_max > 64;
     const size_t B = (size_t)batch;
@@ -196,7 +193,7 @@ int loc_window_create(loc_window** out, int32_t device, int64_t batch, const loc
     }
     if (batch <= 4 && n_anchors > 0) w->h_anchors.assign(anchors, anchors + (size_t)n_anchors * 3);
     {   // the A/B switches of the environment, read once
-        loc_window::Opts& o = w->opt;
+        locamd::DispatchOpts& o = w->opt;
         if (const char* v = getenv("LOCAMD_CHAIN_MIN_BATCH")) { o.env_chain_min = atoll(v); o.env_chain_min_set = true; }
         if (const char* v = getenv("LOCAMD_ARROW3")) o.arrow3 = v[0] == '1' ? 1 : 0;
         if (const char* v = getenv("LOCAMD_TREE")) o.tree = v[0] == '0' ? 0 : (v[0] == 'l' ? 2 : -1);
@@ -278,15 +275,8 @@ static int validate_instances(const loc_window* w, const locamd::HostBatch& b) {
     return LOC_OK;
 }
 
-// Large batches of CHAIN windows (every pose-to-pose edge — range or SE3 — joins consecutive poses; edges ordered by their
-// later pose and priors by pose — the order Localization::addRangeEdge / addImuEdge create them in) run one lane per window
-// (chain_lm_kernel; chain3_lm_kernel when the batch is translation-only).  Below the threshold a wave per window is faster (the
-// lane-per-window kernels take about as long for 1 000 windows as for 65 536); LOCAMD_CHAIN_MIN_BATCH in the environment moves it
-// (0 = never), loc_window_set_chain_threshold / option "chain_min_batch" the handle's.
-static long long effective_chain_min(const loc_window* w) { return w->chain_min >= 0 ? w->chain_min : w->opt.env_chain_min; }
-
-static hipError_t upload_arrow_aux(loc_window* w, int which, int64_t n, hipStream_t st) {
-    locamd::WinAux& A = w->aux[which];
+static hipError_t upload_arrow_aux(loc_window* w, loc_window::BatchSlot& S, int64_t n, hipStream_t st) {
+    locamd::WinAux& A = S.aux;
     const locamd::WindowCaps& c = w->caps;
     const size_t B = (size_t)w->B, N = (size_t)n;
     hipError_t e;
@@ -294,24 +284,15 @@ static hipError_t upload_arrow_aux(loc_window* w, int which, int64_t n, hipStrea
         if ((e = hipMalloc((void**)&A.d_ahdr, B * 8 * sizeof(int32_t))) != hipSuccess ||
             (e = hipMalloc((void**)&A.d_arslot, B * c.nv_max * sizeof(int32_t))) != hipSuccess) return e;
     }
-    if (A.arec_cap < A.h_arec.size()) {
-        if (A.d_arec) (void)hipFree(A.d_arec);
-        A.d_arec = nullptr; A.arec_cap = 0;
-        if ((e = hipMalloc((void**)&A.d_arec, A.h_arec.size() / N * B * sizeof(double))) != hipSuccess) return e;
-        A.arec_cap = A.h_arec.size() / N * B;
-    }
-    if (A.aprec_cap < A.h_aprec.size()) {
-        if (A.d_aprec) (void)hipFree(A.d_aprec);
-        A.d_aprec = nullptr; A.aprec_cap = 0;
-        if ((e = hipMalloc((void**)&A.d_aprec, A.h_aprec.size() / N * B * sizeof(double))) != hipSuccess) return e;
-        A.aprec_cap = A.h_aprec.size() / N * B;
-    }
-    if (!w->d_arrow_ws || w->arrow_ws_nb < A.arrow_nb_max) {
-        if (w->d_arrow_ws) (void)hipFree(w->d_arrow_ws);
-        w->d_arrow_ws = nullptr;
-        if ((e = hipMalloc((void**)&w->d_arrow_ws, B * locamd::window_arrow3_workspace_doubles(c, A.arrow_nb_max) * sizeof(double))) != hipSuccess) return e;
-        w->arrow_ws_nb = A.arrow_nb_max;
-    }
+    // a record table that this batch's records outgrow is replaced by one for B windows of this batch's records per window
+    auto grow_records = [&](double*& d, size_t& cap, size_t used) {
+        if (used <= cap) return hipSuccess;
+        cap = 0;
+        return locamd::grow_buffers(cap, used / N * B, {{d, used / N * B * sizeof(double)}});
+    };
+    if ((e = grow_records(A.d_arec, A.arec_cap, A.h_arec.size())) != hipSuccess || (e = grow_records(A.d_aprec, A.aprec_cap, A.h_aprec.size())) != hipSuccess ||
+        (e = locamd::grow_buffers(w->arrow_ws_nb, (size_t)A.arrow_nb_max,
+                                  {{w->d_arrow_ws, B * locamd::window_arrow3_workspace_doubles(c, A.arrow_nb_max) * sizeof(double)}})) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(A.d_ahdr, A.h_ahdr.data(), N * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess ||
         (e = hipMemcpyAsync(A.d_arslot, A.h_arslot.data(), N * c.nv_max * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess ||
         (e = hipMemcpyAsync(A.d_arec, A.h_arec.data(), A.h_arec.size() * sizeof(double), hipMemcpyHostToDevice, st)) != hipSuccess ||
@@ -322,191 +303,30 @@ static hipError_t upload_arrow_aux(loc_window* w, int which, int64_t n, hipStrea
 // solve: the schedule is for a solve kernel (tree_lm_kernel's workspace is allocated); the covariance pass needs the tables alone
 static hipError_t upload_tree_sched(loc_window* w, locamd::WinAux& A, hipStream_t st, bool solve = true) {
     hipError_t e;
-    if (A.tsched_cap < A.h_tsched.size()) {
-        if (A.d_tsched) (void)hipFree(A.d_tsched);
-        A.d_tsched = nullptr; A.tsched_cap = 0;
-        if ((e = hipMalloc((void**)&A.d_tsched, A.h_tsched.size() * sizeof(int32_t))) != hipSuccess) return e;
-        A.tsched_cap = A.h_tsched.size();
-    }
+    if ((e = locamd::grow_buffers(A.tsched_cap, A.h_tsched.size(), {{A.d_tsched, A.h_tsched.size() * sizeof(int32_t)}})) != hipSuccess) return e;
     if (solve && !w->d_tree_ws && (e = hipMalloc((void**)&w->d_tree_ws, locamd::window_tree_workspace_doubles(w->caps, w->B) * sizeof(double))) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(A.d_tsched, A.h_tsched.data(), A.h_tsched.size() * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    locamd::TreeSched& ts = A.tsched;
-    const int nv = ts.nv, nr = ts.nr, np = ts.np, ns = ts.ns;
-    const int32_t* p = A.d_tsched;
-    ts.node = p; p += nv; ts.par = p; p += nv;
-    ts.r_off = p; p += nv + 1; ts.r_list = p; p += nr;
-    ts.p_off = p; p += nv + 1; ts.p_list = p; p += np;
-    ts.s_off = p; p += nv + 1; ts.s_list = p; p += ns;
-    ts.r_idx = p; p += 2 * nr; ts.s_idx = p; p += 4 * ns;
-    ts.w_par = p; p += nv; ts.w_height = p; p += nv;
-    ts.w_koff = p; p += nv + 1; ts.w_klist = p; p += nv - ts.nroots;
-    ts.w_roff = p; p += nv + 1; ts.w_rlist = p; p += nr;
-    ts.w_poff = p; p += nv + 1; ts.w_plist = p; p += np;
-    ts.w_soff = p; p += nv + 1; ts.w_slist = p; p += ns;
-    ts.w_kleaf = p; p += nv;
-    ts.w_ulist = p; p += ts.nu;
-    ts.w_kpos = p;
+    locamd::bind_tree_sched(A.tsched, A.d_tsched);
     return hipSuccess;
 }
 
-static long long tree_min_batch(const loc_window* w) {
-    const long long mn = effective_chain_min(w);
-    if (mn <= 0) return 1ll << 62;     // (threshold 0 = "never a batch kernel")
-    return mn < 256 ? mn : 256;
-}
-
-// option "arrow3" admits the batch: 0 = never, 1 = whenever it qualifies; default: windows of more than 64 poses — below that the
-// wave-per-window kernel keeps everything in LDS and is the better choice
-static bool arrow3_wanted(const loc_window* w) { return w->opt.arrow3 >= 0 ? w->opt.arrow3 == 1 : w->caps.nv_max > 64; }
-
-// what the batch qualifies for BY ITS STRUCTURE: LOC_WINDOW_KERNEL_GENERAL, _CHAIN (block-tridiagonal, 6-DoF), _CHAIN3, _WAVE6, _WAVE6S,
-// _ARROW3 or _TREE.  which: the set of host-built tables w->aux[which] that ARROW3 (row order, packed edge records) / TREE (the
-// schedule) fill (0: a loc_window_solve_host call, 1: the resident batch).
-// Host-path calls (which == 0) keep the structural verdict of the previous batch in w->topo_cache: the same counts and index tables
-// (one 64-bit hash; a collision — 2^-64 per call — would hand a batch to a kernel built for another structure) skip the tests below.
-// What depends on the VALUES (translation_only: identity rotations, zero lever arms; arrow3's packed edge records) is looked at every time.
-static int batch_topology(loc_window* w, int which, const locamd::HostBatch& b) {
-    const locamd::WindowCaps& c = w->caps;
-    loc_window::TopoCache& tc = w->topo_cache;
-    const bool use_cache = which == 0 && w->opt.topology_cache;
-    unsigned long long key = 0;
-    bool hit = false;
-    if (use_cache) {
-        key = locamd::hash_structure(c, w->has_off1, b);
-        hit = tc.valid && tc.key == key && tc.n == b.n;
-    }
-    if (which == 0) w->t_cached = hit;
-    bool chain = true;
-    bool single_pairs = true;   // no EdgeSE3 anywhere and at most one range edge per pair of consecutive poses (wave6_lm_kernel's rank-1 couplings)
-    bool se3_pairs = false;     // EdgeSE3 factors, at most one per pair of consecutive poses, and at most one range edge per pair (wave6_lm_kernel<JAC, true>)
-    if (hit) { chain = tc.chain; single_pairs = tc.single_pairs; se3_pairs = tc.se3_pairs; }
-    if (!hit) locamd::chain_scan(c, b, true, chain, single_pairs, se3_pairs);
-    if (use_cache && !hit) { tc.valid = true; tc.key = key; tc.n = b.n; tc.chain = chain; tc.single_pairs = single_pairs; tc.se3_pairs = se3_pairs; tc.tree_tried = false; tc.tree_ok = false; }
-    if (chain) {
-        if (locamd::translation_only(c, w->n_anchors, b)) return LOC_WINDOW_KERNEL_CHAIN3;
-        if (single_pairs && c.nv_max <= 64 && locamd::window_wave6_lds_bytes(c) <= locamd::kWave6MaxLds) return LOC_WINDOW_KERNEL_WAVE6;
-        // cfg/uwb_twist.yaml's window: a twist EdgeSE3 per consecutive pair next to the ranges — the wave-per-window kernel with full coupling
-        // blocks.  (The same window was tried on tree_wave_kernel first — a chain is a forest, rooted at its centre it has 8 levels: 0.58 … 0.67 ms
-        // per solve against the general kernel's 0.62 ms, tools/dev/probe_tree_chain.py: no speculative trials, one or two busy lanes per level.)
-        if (se3_pairs && c.nv_max <= 63 && c.ns_max <= 64 && locamd::window_wave6_lds_bytes(c, true) <= locamd::kWave6MaxLds) return LOC_WINDOW_KERNEL_WAVE6S;   // (nv + 1 lanes: the middle pose twice)
-        return LOC_WINDOW_KERNEL_CHAIN;
-    }
-    if (arrow3_wanted(w) && locamd::translation_only(c, w->n_anchors, b) && locamd::build_arrow_aux(c, b, w->aux[which])) return LOC_WINDOW_KERNEL_ARROW3;
-    // (option "tree" = 0: never.  One wave per window, so any batch gains; the host-side comparison of the index tables is only worth
-    //  it from a few hundred windows on — or from the chain threshold when that was lowered, as the tests do)
-    if (w->opt.tree != 0 && b.n >= tree_min_batch(w)) {
-        if (hit && tc.tree_tried) {
-            if (tc.tree_ok) return LOC_WINDOW_KERNEL_TREE;   // (aux[0]'s schedule is still the one built for this structure)
-        } else {
-            const bool ok = locamd::build_tree_sched(c, w->has_off1, b, w->aux[which]);
-            if (use_cache) { tc.tree_tried = true; tc.tree_ok = ok; }
-            if (ok) return LOC_WINDOW_KERNEL_TREE;
-        }
-    }
-    return LOC_WINDOW_KERNEL_GENERAL;
-}
-// the kernel a batch of n windows with that structure takes NOW (threshold, ordering override, the handle's options)
-static int pick_kernel(const loc_window* w, int64_t n, int topology) {
-    const long long mn = effective_chain_min(w);
-    const bool default_rule = w->chain_min < 0 && !w->opt.env_chain_min_set;
-    if (w->has_off1) return LOC_WINDOW_KERNEL_GENERAL;   // (lever arms on endpoint 1: only the general kernel evaluates them)
-    if (mn <= 0 || w->natural_order) return LOC_WINDOW_KERNEL_GENERAL;   // threshold 0 = "never anything but the general kernel" (every structure)
-    if (topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) {   // (WAVE6S: the same rule for chains with EdgeSE3 factors)
-        // a 6-DoF chain batch that also qualifies for wave6_lm_kernel (one wave per window, rank-1 couplings).  Measured on twelve-pose
-        // cfg/uwb_imu.yaml windows: 1.15e7 windows/s at 4 096, 16 384 and 65 536 windows against chain_lm_kernel's 1.1e6 / 4.3e6 / 6.9e6 —
-        // so by default it takes every batch; an explicit threshold hands batches from that size on to the lane-per-window kernel.
-        // option "wave6" = 0: as before (the general kernel below the threshold, chain_lm_kernel from it on), for A/B runs.
-        const bool off = !w->opt.wave6;
-        if (n >= mn && (off || !default_rule)) return LOC_WINDOW_KERNEL_CHAIN;
-        return off ? LOC_WINDOW_KERNEL_GENERAL : topology;
-    }
-    if (topology == LOC_WINDOW_KERNEL_ARROW3) return LOC_WINDOW_KERNEL_ARROW3;   // (one workgroup per window: any batch size)
-    if (topology == LOC_WINDOW_KERNEL_TREE) return n < tree_min_batch(w) ? LOC_WINDOW_KERNEL_GENERAL : LOC_WINDOW_KERNEL_TREE;
-    if (topology == LOC_WINDOW_KERNEL_CHAIN3 && w->caps.nv_max <= 64 && locamd::window_wave3_lds_bytes(w->caps) <= 64 * 1024) {
-        // translation-only chains of <= 64 poses (the node's single window first of all): one wave per window with 3x3 blocks, rank-1
-        // couplings and speculative LM trials.  Measured on ten-pose windows: 0.056 ms for one window, 3.6e7 windows/s (numeric) /
-        // 4.0e7 (analytic) from ~8 000 windows on — level with chain3_lm_kernel at 65 536 windows, ahead of it everywhere else — so by
-        // default it takes every batch; an explicit threshold (loc_window_set_chain_threshold / LOCAMD_CHAIN_MIN_BATCH) hands batches
-        // from that size on to the lane-per-window kernel.  Options "wave3" / "chain3" = 0: no such kernel (A/B runs, tests).
-        if ((default_rule || n < mn) && w->opt.wave3 && w->opt.chain3) return LOC_WINDOW_KERNEL_WAVE3;
-    }
-    if (topology == LOC_WINDOW_KERNEL_CHAIN3 && default_rule && n >= 4096 && n < mn) {
-        // the translation-only kernel is worth it from ~4 096 windows on (it takes ~1 ms for any batch up to 16 384, the wave-per-window
-        // kernel 4.3e6 windows/s): e.g. one GPU's 8 192-window share of a 65 536-window job split over eight
-        if (w->opt.chain3) return LOC_WINDOW_KERNEL_CHAIN3;
-    }
-    if (topology == LOC_WINDOW_KERNEL_GENERAL || n < mn) return LOC_WINDOW_KERNEL_GENERAL;
-    if (topology == LOC_WINDOW_KERNEL_CHAIN3 && !w->opt.chain3) return LOC_WINDOW_KERNEL_CHAIN;   // the 6-DoF kernel on a translation-only batch (A/B runs, tests)
-    return topology;
-}
-// The block size the covariance pass computes a batch with (covariance_kernel.hip): 3 for translation-only batches, 6 otherwise; 0 = not
-// covered (LOC_ERR_UNSUPPORTED): lever arms on endpoint 1, or a batch none of the three tests below takes.  In this order:
-// 1. windows of <= 64 poses that are chains (in any edge order): 3 / 6;
-// 2. kCovArrow when the handle would solve the batch on arrow3_lm_kernel (batch_topology's rule: arrow3_wanted — by default windows of
-//    more than 64 poses only —, translation_only, build_arrow_aux's verdict) — arrow_covariance_kernel.hip; the structure test runs on `own`,
-//    a table set of the covariance's own, and the list size goes to w->cov_list_cap[keyed ? 0 : 1];
-// 3. windows of <= 64 poses: kCovForestOwn when the handle would solve the batch on a forest kernel (batch_topology's rule: option "tree",
-//    tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `own`, which the caller then sends
-//    to the device (need_upload).  keyed (the host path): the set is kept with the hash of the structure it was built for, and a batch of
-//    the same structure reuses it, device copy included.
-static int structured_covariance_kind(loc_window* w, const locamd::HostBatch& b, locamd::WinAux* own, bool keyed, bool& need_upload) {
-    const locamd::WindowCaps& c = w->caps;
-    need_upload = false;
-    if (w->has_off1) return 0;
-    const bool small = c.nv_max <= 64;
-    if (small) {
-        bool chain = false, single_pairs = false, se3_pairs = false;
-        locamd::chain_scan(c, b, false, chain, single_pairs, se3_pairs);
-        if (chain) {
-            if (locamd::window_covariance_lds_bytes(c, false) > 160 * 1024) return 0;
-            return locamd::translation_only(c, w->n_anchors, b) ? 3 : 6;
-        }
-    }
-    if (arrow3_wanted(w) && locamd::window_arrow_covariance_lds_bytes(c) <= 160 * 1024 && locamd::translation_only(c, w->n_anchors, b) &&
-        locamd::build_arrow_aux(c, b, *own, true)) {
-        w->cov_list_cap[keyed ? 0 : 1] = own->arrow_list_cap;
-        return kCovArrow;
-    }
-    if (!small) return 0;
-    if (w->opt.tree == 0 || b.n < tree_min_batch(w)) return 0;
-    unsigned long long key = 0;
-    if (keyed) {
-        key = locamd::hash_structure(c, w->has_off1, b);
-        if (w->cov_sched_valid && w->cov_sched_key == key && w->cov_sched_n == b.n) return kCovForestOwn;
-        w->cov_sched_valid = false;   // (valid again once the caller has uploaded the new tables)
-        w->cov_sched_key = key; w->cov_sched_n = b.n;
-    }
-    if (!locamd::build_tree_sched(c, w->has_off1, b, *own)) return 0;
-    need_upload = true;
-    return kCovForestOwn;
-}
-// the switches structured_covariance_kind reads besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold)
-static long long cov_switches(const loc_window* w) {
-    const long long mn = tree_min_batch(w);
-    return ((long long)(w->opt.arrow3 + 1) << 4 | (long long)(w->opt.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8);
-}
-// 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is kCovEnvelope —
-//    envelope_covariance_kernel.hip in the caller's pose order; the batch's largest envelope goes to w->env_blocks[keyed ? 0 : 1].
-//    pt: the pairs of a joint call count as edges of that envelope (none: the plain envelope).
-static int covariance_kind(loc_window* w, const locamd::HostBatch& b, const locamd::PairTables& pt, locamd::WinAux* own, bool keyed, bool& need_upload) {
-    const int kind = structured_covariance_kind(w, b, own, keyed, need_upload);
-    if (kind || w->has_off1 || !w->opt.cov_general) return kind;
-    if (locamd::window_envelope_covariance_lds_bytes(w->caps) > 160 * 1024) return 0;
-    const long long blocks = locamd::envelope_blocks_max_joint(w->caps, b, pt);
-    if (blocks < 0) return 0;   // (cannot happen: the tables were validated)
-    w->env_blocks[keyed ? 0 : 1] = blocks;
-    return kCovEnvelope;
-}
-// the envelope pass's workspace for n windows of at most `blocks` envelope blocks (which: 0 the host path's, 1 the resident batch's)
-static hipError_t grow_env_workspace(loc_window* w, int which, int64_t n, long long blocks) {
+// the envelope pass's workspace for n windows of at most `blocks` envelope blocks
+static hipError_t grow_env_workspace(loc_window* w, loc_window::BatchSlot& S, int64_t n, long long blocks) {
     const size_t need = (size_t)n * locamd::window_envelope_covariance_workspace_doubles(w->caps, blocks);
-    return locamd::grow_buffers(w->env_ws_cap[which], need, {{w->d_env_ws[which], need * sizeof(double)}});
+    return locamd::grow_buffers(S.env_ws_cap, need, {{S.d_env_ws, need * sizeof(double)}});
 }
-// the arrowhead pass's workspace for n windows with lists of `cap` entries (which: 0 the host path's, 1 the resident batch's)
-static hipError_t grow_cov_workspace(loc_window* w, int which, int64_t n, int cap) {
+// the arrowhead pass's workspace for n windows with lists of `cap` entries
+static hipError_t grow_cov_workspace(loc_window* w, loc_window::BatchSlot& S, int64_t n, int cap) {
     const size_t need = (size_t)n * locamd::window_arrow_covariance_workspace_doubles(w->caps, cap);
-    return locamd::grow_buffers(w->cov_ws_cap[which], need, {{w->d_cov_ws[which], need * sizeof(double)}});
+    return locamd::grow_buffers(S.cov_ws_cap, need, {{S.d_cov_ws, need * sizeof(double)}});
+}
+
+// the page-locked staging block of the small calls and its device twin
+static int ensure_stage(loc_window* w) {
+    if (!w->h_stage) LOC_HIP(hipHostMalloc((void**)&w->h_stage, kStageBytes, hipHostMallocDefault));
+    if (!w->d_stage) LOC_HIP(hipMalloc((void**)&w->d_stage, kStageBytes));
+    return LOC_OK;
 }
 
 // The kernels' arguments for n instances of the tables d.  poses_in: nullptr = d's own poses (solved in place; the resident solve starts
@@ -518,8 +338,8 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
     a.r_idx = (const int32_t*)d.t[locamd::kRIdx]; a.r_val = (const double*)d.t[locamd::kRVal];
     a.p_idx = (const int32_t*)d.t[locamd::kPIdx]; a.p_val = (const double*)d.t[locamd::kPVal];
     a.s_idx = (const int32_t*)d.t[locamd::kSIdx]; a.s_val = (const double*)d.t[locamd::kSVal];
-    a.anchors = anchors; a.result = result; a.r_off1 = result && w->has_off1 ? w->d_roff1 : nullptr; a.workspace = result ? w->d_workspace : nullptr;
-    a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->natural_order; a.caps = w->caps;
+    a.anchors = anchors; a.result = result; a.r_off1 = result && w->opt.has_off1 ? w->d_roff1 : nullptr; a.workspace = result ? w->d_workspace : nullptr;
+    a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->opt.natural_order; a.caps = w->caps;
     return a;
 }
 // the resident batch as uploaded: the initial estimates in the place of the optimised ones
@@ -527,8 +347,8 @@ static locamd::DeviceTables uploaded_tables(const loc_window* w) { locamd::Devic
 // the device arrays hold no resident batch any more (the resident calls return LOC_ERR_INVALID until the next loc_window_upload completes)
 static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_min_anchors = 0; }
 
-static hipError_t launch_any(loc_window* w, int which, const locamd::WindowArgs& a, hipStream_t st, int kind) {
-    locamd::WinAux& A = w->aux[which];
+static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const locamd::WindowArgs& a, hipStream_t st, int kind) {
+    locamd::WinAux& A = S.aux;
     w->last_kind = kind;
     if (kind == LOC_WINDOW_KERNEL_ARROW3) {
         locamd::ArrowAux x;
@@ -570,16 +390,16 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind) {
 
 int loc_window_set_chain_threshold(loc_window* w, int64_t min_batch) {
     if (!w) return locamd_fail(LOC_ERR_INVALID, "null");
-    w->chain_min = min_batch;
+    w->opt.chain_min = min_batch;
     return LOC_OK;
 }
 
 int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
     if (!w || !name) return locamd_fail(LOC_ERR_INVALID, "set_option");
     const std::string k(name);
-    loc_window::Opts& o = w->opt;
+    locamd::DispatchOpts& o = w->opt;
     auto flag = [&](bool& f) { if (value != 0 && value != 1) return locamd_fail(LOC_ERR_INVALID, "set_option: 0 or 1"); f = value == 1; return (int)LOC_OK; };
-    if (k == "chain_min_batch") { w->chain_min = value; return LOC_OK; }
+    if (k == "chain_min_batch") { o.chain_min = value; return LOC_OK; }
     if (k == "arrow3") { if (value < -1 || value > 1) return locamd_fail(LOC_ERR_INVALID, "set_option arrow3: -1, 0 or 1"); o.arrow3 = (int)value; w->topo_cache.valid = false; return LOC_OK; }
     if (k == "tree") { if (value != -1 && value != 0 && value != 2) return locamd_fail(LOC_ERR_INVALID, "set_option tree: -1, 0 or 2"); o.tree = (int)value; w->topo_cache.valid = false; return LOC_OK; }
     if (k == "wave3") return flag(o.wave3);
@@ -591,7 +411,7 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
         const bool before = o.cov_general;
         const int rc = flag(o.cov_general);
         // a resident batch the other value refused, or handed to the envelope pass, is classified again by the next covariance call
-        if (rc == LOC_OK && before != o.cov_general && w->n_resident > 0 && (w->resident_cov == 0 || w->resident_cov == kCovEnvelope)) w->resident_cov = -1;
+        if (rc == LOC_OK && before != o.cov_general && w->n_resident > 0 && (w->resident_cov == CovKind::None || w->resident_cov == CovKind::Envelope)) w->resident_cov = CovKind::Unclassified;
         return rc;
     }
     if (k == "topology_cache") { w->topo_cache.valid = false; return flag(o.topology_cache); }
@@ -606,7 +426,7 @@ int loc_window_last_host_timing(const loc_window* w, double* out) {
 
 int loc_window_set_endpoint1_offsets(loc_window* w, int64_t n, const double* off1) {
     if (!w || (off1 && (n <= 0 || n > w->B))) return locamd_fail(LOC_ERR_INVALID, "set_endpoint1_offsets");
-    if (!off1) { w->has_off1 = false; return LOC_OK; }   // (has_off1 is part of the structure hash: no cache entry survives a change of it)
+    if (!off1) { w->opt.has_off1 = false; return LOC_OK; }   // (has_off1 is part of the structure hash: no cache entry survives a change of it)
     if (w->caps.nr_max <= 0) return locamd_fail(LOC_ERR_INVALID, "set_endpoint1_offsets: no range edges in this solver");
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = wait_resident(w)) return rc;
@@ -616,7 +436,7 @@ int loc_window_set_endpoint1_offsets(loc_window* w, int64_t n, const double* off
     LOC_HIP(hipMemcpy(w->d_roff1, off1, (size_t)n * row, hipMemcpyHostToDevice));
     // rows [n, B): no lever arm (a call with fewer instances than an earlier one must not leave that one's behind)
     if (n < w->B) LOC_HIP(hipMemset((char*)w->d_roff1 + (size_t)n * row, 0, (size_t)(w->B - n) * row));
-    w->has_off1 = true;
+    w->opt.has_off1 = true;
     return LOC_OK;
 }
 
@@ -627,8 +447,15 @@ int loc_window_set_jacobian(loc_window* w, int32_t jacobian) {
 }
 int loc_window_set_ordering(loc_window* w, int32_t natural) {
     if (!w) return locamd_fail(LOC_ERR_INVALID, "null");
-    w->natural_order = natural != 0;
+    w->opt.natural_order = natural != 0;
     return LOC_OK;
+}
+
+// the kernel of a host-path batch: its structure (slot[0]'s tables, the topology cache), then the rules of the moment
+static int host_kernel(loc_window* w, const locamd::HostBatch& b) {
+    const locamd::Topology t = locamd::batch_topology(w->caps, w->opt, w->fits, w->n_anchors, b, w->slot[0].aux, &w->topo_cache);
+    w->t_cached = t.cached;
+    return locamd::pick_kernel(w->opt, w->fits, b.n, t.kind);
 }
 
 int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, double* poses, const int32_t* r_idx,
@@ -653,12 +480,11 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
     // then ~0.2 ms of host/PCIe overhead around the kernel instead of a dozen small pageable copies.
     const locamd::BlockLayout L = locamd::pack_block(c, N, out_bytes, 2, kCounts);
     if (L.end <= kStageBytes) {
-        if (!w->h_stage) LOC_HIP(hipHostMalloc((void**)&w->h_stage, kStageBytes, hipHostMallocDefault));
-        if (!w->d_stage) LOC_HIP(hipMalloc((void**)&w->d_stage, kStageBytes));
+        if (int rc = ensure_stage(w)) return rc;
         char* h = w->h_stage; char* d = w->d_stage;
         locamd::stage_tables(h, L, c, b);
         const auto t_topo = clk::now();
-        const int kind = pick_kernel(w, n, batch_topology(w, 0, b));
+        const int kind = host_kernel(w, b);
         w->t_topology_ms = ms_since(t_topo);
         const auto t_run = clk::now();
         // A handful of small windows on wave3_lm_kernel (the node's own solve): the kernel reads its few KB of input once and
@@ -667,8 +493,8 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
         const size_t anchor_bytes = (size_t)w->n_anchors * 3 * sizeof(double);
         // (tree_wave_kernel likewise reads its inputs once, in its prologue — unless a pose has priors or more than two range edges, which it
         //  fetches from memory on every sweep: such windows are copied to the device first)
-        const bool tree_once = kind == LOC_WINDOW_KERNEL_TREE && w->aux[0].tsched.np == 0 && w->aux[0].tsched.max_r_per_node <= 2 &&
-                               w->aux[0].tsched.max_se3_per_node <= 1 && w->opt.tree != 2;
+        const locamd::TreeSched& ts = w->slot[0].aux.tsched;
+        const bool tree_once = kind == LOC_WINDOW_KERNEL_TREE && ts.np == 0 && ts.max_r_per_node <= 2 && ts.max_se3_per_node <= 1 && w->opt.tree != 2;
         const bool zero_copy = (kind == LOC_WINDOW_KERNEL_WAVE3 || kind == LOC_WINDOW_KERNEL_WAVE6 || kind == LOC_WINDOW_KERNEL_WAVE6S || tree_once) && n <= 4 && w->B <= 4 && w->h_anchors.size() == (size_t)w->n_anchors * 3 &&
                                L.end + anchor_bytes <= kStageBytes && w->opt.zero_copy;
         if (zero_copy) {
@@ -682,10 +508,10 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
         // (the two event records around a ~50 us kernel are not free; option "kernel_events" = 0 drops them for the zero-copy solve)
         const bool events = w->opt.kernel_events || !zero_copy;
         if (events) LOC_HIP(hipEventRecord(w->ev0, st));
-        if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, 0, n, st));
-        if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->aux[0], st));
+        if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, w->slot[0], n, st));
+        if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->slot[0].aux, st));
         const auto t_launch = clk::now();
-        hipError_t e = launch_any(w, 0, a, st, kind);
+        hipError_t e = launch_any(w, w->slot[0], a, st, kind);
         if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
         if (events) LOC_HIP(hipEventRecord(w->ev1, st));
         if (!zero_copy) LOC_HIP(hipMemcpyAsync(h, d, L.tab[kCounts], hipMemcpyDeviceToHost, st));  // [poses | result]
@@ -702,15 +528,15 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
     // The large path stages its batch in the device arrays a resident batch lives in: that batch is gone from here on
     drop_resident(w);
     const auto t_topo = clk::now();
-    const int kind = pick_kernel(w, n, batch_topology(w, 0, b));
+    const int kind = host_kernel(w, b);
     w->t_topology_ms = ms_since(t_topo);
     const auto t_run = clk::now();
     LOC_HIP(copy_tables(c, N, w->dev.t, b.tables().t, hipMemcpyHostToDevice, &st));
     const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, w->d_result);
-    if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, 0, n, st));
-    if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->aux[0], st));
+    if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, w->slot[0], n, st));
+    if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->slot[0].aux, st));
     LOC_HIP(hipEventRecord(w->ev0, st));
-    hipError_t e = launch_any(w, 0, a, st, kind);
+    hipError_t e = launch_any(w, w->slot[0], a, st, kind);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
     LOC_HIP(hipEventRecord(w->ev1, st));
     LOC_HIP(hipMemcpyAsync(poses, w->dev.t[kPoses], out_bytes[0], hipMemcpyDeviceToHost, st));
@@ -736,12 +562,13 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     LOC_HIP(hipStreamSynchronize(w->stream));
     if (int rc = wait_resident(w)) return rc;
     // (a failing step below must not leave a half-described resident batch behind: nothing is resident until everything is)
-    drop_resident(w); w->resident_cov = 0;   // (and its covariance verdict with it)
+    drop_resident(w); w->resident_cov = CovKind::None;   // (and its covariance verdict with it)
     if (!w->d_poses_in) LOC_HIP(hipMalloc((void**)&w->d_poses_in, (size_t)w->B * locamd::table_bytes(c, kPoses)));
     LOC_HIP(copy_tables(c, (size_t)n, uploaded_tables(w).t, b.tables().t, hipMemcpyHostToDevice, nullptr));
-    const int topology = batch_topology(w, 1, b);
-    if (topology == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, 1, n, w->stream));
-    if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->aux[1], w->stream));
+    loc_window::BatchSlot& S = w->slot[1];
+    const int topology = locamd::batch_topology(c, w->opt, w->fits, w->n_anchors, b, S.aux, nullptr).kind;
+    if (topology == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, S, n, w->stream));
+    if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, S.aux, w->stream));
     int max_anchor = 0;   // anchors referenced: v1 = -1 - anchor
     for (int64_t i = 0; i < n; ++i)
         for (int e = 0; e < counts[i * 4 + 1]; ++e) {
@@ -751,20 +578,20 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     w->resident_min_anchors = max_anchor;
     w->res_counts.assign(counts, counts + (size_t)n * 4);
     w->resident_topology = topology;
-    // the block size of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
+    // the pass of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
     // classified by the first loc_window_covariance_resident call (an upload costs nothing more for callers that never ask)
-    if (topology == LOC_WINDOW_KERNEL_CHAIN3) w->resident_cov = 3;
-    else if (topology == LOC_WINDOW_KERNEL_CHAIN || topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) w->resident_cov = 6;
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3) w->resident_cov = CovKind::Chain3;
+    else if (topology == LOC_WINDOW_KERNEL_CHAIN || topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) w->resident_cov = CovKind::Chain6;
     else if (topology == LOC_WINDOW_KERNEL_TREE) {
-        // a forest the solve kernels take: the covariance pass walks the schedule just built and uploaded (aux[1]) — unless the batch is
+        // a forest the solve kernels take: the covariance pass walks the schedule just built and uploaded (S.aux) — unless the batch is
         // a chain in some edge order, which the chain pass serves as before
         bool chain = false, single_pairs = false, se3_pairs = false;
         locamd::chain_scan(c, b, false, chain, single_pairs, se3_pairs);
-        w->resident_cov = chain ? -1 : kCovForest;
+        w->resident_cov = chain ? CovKind::Unclassified : CovKind::Forest;
     } else if (topology == LOC_WINDOW_KERNEL_ARROW3) {   // (never a chain: build_arrow_aux wants a border)
-        w->resident_cov = kCovArrow;
-        w->cov_list_cap[1] = w->aux[1].arrow_list_cap;
-    } else w->resident_cov = -1;
+        w->resident_cov = CovKind::Arrow;
+        S.cov_list_cap = S.aux.arrow_list_cap;
+    } else w->resident_cov = CovKind::Unclassified;
     w->n_resident = n;
     return LOC_OK;
 }
@@ -778,7 +605,7 @@ int loc_window_solve_resident(loc_window* w, void* hip_stream) {
     LOC_HIP(w->timer.start(st));
     // (the batch-size threshold and the ordering override are looked at per solve: loc_window_set_chain_threshold /
     //  loc_window_set_ordering after the upload take effect)
-    hipError_t e = launch_any(w, 1, a, st, pick_kernel(w, w->n_resident, w->resident_topology));
+    hipError_t e = launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->n_resident, w->resident_topology));
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
     LOC_HIP(w->timer.stop(st));
     LOC_HIP(hipEventRecord(w->resident_done, st));
@@ -819,16 +646,16 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
                             "or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold), " \
                             "or option covariance_general must be 1 (any structure and length, in the caller's pose order); no endpoint-1 lever arms"
 
-// the pass of a batch of covariance_kind's `kind`; which: 0 = loc_window_covariance_host's table set and workspace, 1 = the resident batch's
-// (a forest that loc_window_upload classified, kCovForest, walks the solve's schedule aux[1]; kCovForestOwn the covariance's own)
+// the pass of a batch of covariance_kind's `kind`; S: the batch's table sets and workspaces (a forest that loc_window_upload classified,
+// Forest, walks the resident solve's schedule slot[1].aux; ForestOwn the covariance's own, S.cov_aux)
 // env_blocks: the envelope the workspace was sized for (a joint call's includes its pairs); pp: the pairs on the device, cross = nullptr for none
-static hipError_t launch_covariance(loc_window* w, int which, int kind, long long env_blocks, const locamd::WindowArgs& a, double* cov, int32_t* mask, int32_t* status,
-                                    const locamd::CovPairs& pp, hipStream_t st) {
-    if (kind == kCovArrow) return locamd::launch_window_arrow_covariance(a, w->d_cov_ws[which], w->cov_list_cap[which], cov, mask, status, pp, st);
-    if (kind == kCovEnvelope) return locamd::launch_window_envelope_covariance(a, w->d_env_ws[which], env_blocks, cov, mask, status, pp, st);
-    if (kind == kCovForest) return locamd::launch_window_forest_covariance(a, w->aux[1].tsched, cov, mask, status, pp, st);
-    if (kind == kCovForestOwn) return locamd::launch_window_forest_covariance(a, w->cov_aux[which].tsched, cov, mask, status, pp, st);
-    return locamd::launch_window_covariance(a, kind == 3, cov, mask, status, pp, st);
+static hipError_t launch_covariance(loc_window* w, loc_window::BatchSlot& S, CovKind kind, long long env_blocks, const locamd::WindowArgs& a, double* cov, int32_t* mask,
+                                    int32_t* status, const locamd::CovPairs& pp, hipStream_t st) {
+    if (kind == CovKind::Arrow) return locamd::launch_window_arrow_covariance(a, S.d_cov_ws, S.cov_list_cap, cov, mask, status, pp, st);
+    if (kind == CovKind::Envelope) return locamd::launch_window_envelope_covariance(a, S.d_env_ws, env_blocks, cov, mask, status, pp, st);
+    if (kind == CovKind::Forest) return locamd::launch_window_forest_covariance(a, w->slot[1].aux.tsched, cov, mask, status, pp, st);
+    if (kind == CovKind::ForestOwn) return locamd::launch_window_forest_covariance(a, S.cov_aux.tsched, cov, mask, status, pp, st);
+    return locamd::launch_window_covariance(a, kind == CovKind::Chain3, cov, mask, status, pp, st);
 }
 // the pair arguments of a joint call as given (npair_max = 0: none, the plain call): 0, or the error
 static int validate_pairs(int64_t n, const int32_t* counts, const locamd::PairTables& pt, const void* cross) {
@@ -848,16 +675,18 @@ int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* co
     const locamd::PairTables pt{npair_max, pair_counts, pairs};
     if (int rc = validate_pairs(n, counts, pt, cross)) return rc;
     const bool joint = npair_max > 0;
-    bool sched_upload = false;
-    const int kind = covariance_kind(w, b, pt, &w->cov_aux[0], true, sched_upload);
-    if (!kind) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host" LOC_COV_UNSUPPORTED);
     const locamd::WindowCaps& c = w->caps;
+    loc_window::BatchSlot& S = w->slot[0];
+    const locamd::CovVerdict v = locamd::covariance_kind(c, w->opt, w->fits, w->n_anchors, b, pt, S.cov_aux, &w->cov_sched);
+    const CovKind kind = v.kind;
+    if (kind == CovKind::None) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_host" LOC_COV_UNSUPPORTED);
+    S.cov_list_cap = v.list_cap; S.env_blocks = v.env_blocks;
     LOC_HIP(hipSetDevice(w->device));
-    if (kind == kCovArrow) LOC_HIP(grow_cov_workspace(w, 0, n, w->cov_list_cap[0]));
-    if (kind == kCovEnvelope) LOC_HIP(grow_env_workspace(w, 0, n, w->env_blocks[0]));
-    if (sched_upload) {
-        LOC_HIP(upload_tree_sched(w, w->cov_aux[0], w->stream, false));
-        w->cov_sched_valid = true;
+    if (kind == CovKind::Arrow) LOC_HIP(grow_cov_workspace(w, S, n, S.cov_list_cap));
+    if (kind == CovKind::Envelope) LOC_HIP(grow_env_workspace(w, S, n, S.env_blocks));
+    if (v.need_upload) {
+        LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false));
+        w->cov_sched.valid = true;
     }
     if (int rc = flush_anchors(w)) return rc;
     const size_t N = (size_t)n;
@@ -875,8 +704,7 @@ int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* co
     char* d;
     const bool small = L.end <= kStageBytes;
     if (small) {   // (the staging block of loc_window_solve_host: free between calls, never used by a resident launch)
-        if (!w->h_stage) LOC_HIP(hipHostMalloc((void**)&w->h_stage, kStageBytes, hipHostMallocDefault));
-        if (!w->d_stage) LOC_HIP(hipMalloc((void**)&w->d_stage, kStageBytes));
+        if (int rc = ensure_stage(w)) return rc;
         locamd::stage_tables(w->h_stage, L, c, b);
         for (int k = 0; k < 2 && joint; ++k) std::memcpy(w->h_stage + L.pre[4 + k], pair_in[k], pre_bytes[4 + k]);
         d = w->d_stage;
@@ -891,7 +719,7 @@ int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* co
     const locamd::CovPairs pp = joint ? locamd::CovPairs{(const int32_t*)(d + L.pre[4]), (const int32_t*)(d + L.pre[5]), (double*)(d + L.pre[3]), npair_max}
                                       : locamd::CovPairs{nullptr, nullptr, nullptr, 0};
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, 0, kind, w->env_blocks[0], a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), pp, st);
+    const hipError_t e = launch_covariance(w, S, kind, S.env_blocks, a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), pp, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     if (small) {
@@ -925,21 +753,9 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
     if (int rc = validate_pairs(w->n_resident, w->res_counts.data(), pt, cross_dev)) return rc;
     const bool joint = npair_max > 0;
     LOC_HIP(hipSetDevice(w->device));
-    // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
-    // (an arrowhead batch likewise while option "arrow3" still admits it; the envelope pass while option "covariance_general" is 1)
-    auto refused = [&] {
-        const bool forest = w->resident_cov == kCovForest || w->resident_cov == kCovForestOwn;
-        const bool arrow = w->resident_cov == kCovArrow, envelope = w->resident_cov == kCovEnvelope;
-        return w->has_off1 || (w->caps.nv_max > 64 && !arrow && !envelope) || w->resident_cov <= 0 || (forest && (w->n_resident < tree_min_batch(w) || w->opt.tree == 0)) ||
-               (arrow && (!arrow3_wanted(w) || locamd::window_arrow_covariance_lds_bytes(w->caps) > 160 * 1024)) || (envelope && !w->opt.cov_general);
-    };
-    // (option "covariance_general": a structured verdict the handle's switches no longer admit is no verdict — the batch is classified under
-    //  the switches as they are now, and lands on the envelope pass)
-    if (w->resident_cov > 0 && w->resident_cov != kCovEnvelope && w->opt.cov_general && !w->has_off1 && refused()) w->resident_cov = -1;
-    // (and the other way round: the envelope pass holds the batch only while the three structured tests would still decline it — they are
-    //  run again when a switch they read has changed, so that the resident batch takes the pass loc_window_covariance_host takes)
-    if (w->resident_cov == kCovEnvelope && w->env_switches != cov_switches(w)) w->resident_cov = -1;
-    if (w->resident_cov < 0 && !w->has_off1) {
+    loc_window::BatchSlot& S = w->slot[1];
+    if (locamd::cov_stale(w->opt, w->fits, w->n_resident, w->resident_cov, w->env_switches)) w->resident_cov = CovKind::Unclassified;
+    if (w->resident_cov == CovKind::Unclassified && !w->opt.has_off1) {
         // first call on an upload no solve kernel classified as a chain: the uploaded tables come back once and are scanned on the host
         if (int rc = wait_resident(w)) return rc;
         const locamd::WindowCaps& c = w->caps;
@@ -950,28 +766,28 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         void* const dst[locamd::kWindowTables] = {poses.data(), counts.data(), rval.data(), pval.data(), nullptr, ridx.data(), pidx.data(), sidx.data()};
         LOC_HIP(copy_tables(c, N, dst, uploaded_tables(w).t, hipMemcpyDeviceToHost, nullptr));
         const locamd::HostBatch b{(int64_t)N, poses.data(), counts.data(), rval.data(), pval.data(), nullptr, ridx.data(), pidx.data(), sidx.data()};
-        bool sched_upload = false;
-        const int kind = covariance_kind(w, b, locamd::PairTables{0, nullptr, nullptr}, &w->cov_aux[1], false, sched_upload);
-        if (sched_upload) LOC_HIP(upload_tree_sched(w, w->cov_aux[1], w->stream, false));
-        w->resident_cov = kind;
-        w->env_switches = cov_switches(w);
-        if (kind == kCovEnvelope) { w->res_ridx.swap(ridx); w->res_sidx.swap(sidx); }   // (a joint call's pairs enlarge the envelope)
+        const locamd::CovVerdict v = locamd::covariance_kind(c, w->opt, w->fits, w->n_anchors, b, locamd::PairTables{0, nullptr, nullptr}, S.cov_aux, nullptr);
+        if (v.need_upload) LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false));
+        w->resident_cov = v.kind;
+        S.cov_list_cap = v.list_cap; S.env_blocks = v.env_blocks;
+        w->env_switches = locamd::cov_switches(w->opt);
+        if (v.kind == CovKind::Envelope) { w->res_ridx.swap(ridx); w->res_sidx.swap(sidx); }   // (a joint call's pairs enlarge the envelope)
     }
-    if (refused()) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
-    const bool arrow = w->resident_cov == kCovArrow;
-    long long env_blocks = w->env_blocks[1];
-    if (w->resident_cov == kCovEnvelope && joint) {
+    if (!locamd::cov_admitted(w->opt, w->fits, w->n_resident, w->resident_cov)) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
+    const bool arrow = w->resident_cov == CovKind::Arrow, envelope = w->resident_cov == CovKind::Envelope;
+    long long env_blocks = S.env_blocks;
+    if (envelope && joint) {
         const locamd::HostBatch eb{w->n_resident, nullptr, w->res_counts.data(), nullptr, nullptr, nullptr, w->res_ridx.data(), nullptr, w->res_sidx.data()};
         env_blocks = locamd::envelope_blocks_max_joint(w->caps, eb, pt);
         if (env_blocks < 0) return locamd_fail(LOC_ERR_INVALID, "joint covariance: pair tables");   // (cannot happen: validated above)
     }
-    if (w->resident_cov == kCovEnvelope && w->env_ws_cap[1] < (size_t)w->n_resident * locamd::window_envelope_covariance_workspace_doubles(w->caps, env_blocks)) {
+    if (envelope && S.env_ws_cap < (size_t)w->n_resident * locamd::window_envelope_covariance_workspace_doubles(w->caps, env_blocks)) {
         if (int rc = wait_resident(w)) return rc;   // (as below)
-        LOC_HIP(grow_env_workspace(w, 1, w->n_resident, env_blocks));
+        LOC_HIP(grow_env_workspace(w, S, w->n_resident, env_blocks));
     }
-    if (arrow && w->cov_ws_cap[1] < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, w->cov_list_cap[1])) {
+    if (arrow && S.cov_ws_cap < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, S.cov_list_cap)) {
         if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
-        LOC_HIP(grow_cov_workspace(w, 1, w->n_resident, w->cov_list_cap[1]));
+        LOC_HIP(grow_cov_workspace(w, S, w->n_resident, S.cov_list_cap));
     }
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
@@ -983,11 +799,9 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         if (w->pairs_cap < cnt_bytes + pair_bytes) {
             if (int rc = wait_resident(w)) return rc;   // (an earlier joint launch may still read the table that is about to be replaced)
             if (w->h_pairs) (void)hipHostFree(w->h_pairs);
-            if (w->d_pairs) (void)hipFree(w->d_pairs);
-            w->h_pairs = w->d_pairs = nullptr; w->pairs_cap = 0; w->pairs_inflight = false;
+            w->h_pairs = nullptr; w->pairs_cap = 0; w->pairs_inflight = false;   // (capacity 0: grow_buffers replaces the device half with the host half, and a failure leaves none)
             LOC_HIP(hipHostMalloc((void**)&w->h_pairs, cnt_bytes + pair_bytes, hipHostMallocDefault));
-            LOC_HIP(hipMalloc((void**)&w->d_pairs, cnt_bytes + pair_bytes));
-            w->pairs_cap = cnt_bytes + pair_bytes;
+            LOC_HIP(locamd::grow_buffers(w->pairs_cap, cnt_bytes + pair_bytes, {{w->d_pairs, cnt_bytes + pair_bytes}}));
         }
         if (!w->pairs_copied) LOC_HIP(hipEventCreateWithFlags(&w->pairs_copied, hipEventDisableTiming));
         if (w->pairs_inflight) { LOC_HIP(hipEventSynchronize(w->pairs_copied)); w->pairs_inflight = false; }
@@ -1003,7 +817,7 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
     }
     const locamd::WindowArgs a = window_args(w, w->dev, w->n_resident, nullptr, w->d_anchors, nullptr);
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, 1, w->resident_cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st);
+    const hipError_t e = launch_covariance(w, S, w->resident_cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     // whatever overwrites the resident arrays next waits for this launch as well

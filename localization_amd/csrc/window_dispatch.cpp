@@ -1,0 +1,176 @@
+// The dispatch rules of the batched sliding-window solver (window_dispatch.h).  Host code only: no HIP call, no environment, no handle.
+#include "window_dispatch.h"
+
+#include "../../include/localization_amd.h"
+
+namespace locamd {
+
+// Large batches of CHAIN windows (every pose-to-pose edge — range or SE3 — joins consecutive poses; edges ordered by their
+// later pose and priors by pose — the order Localization::addRangeEdge / addImuEdge create them in) run one lane per window
+// (chain_lm_kernel; chain3_lm_kernel when the batch is translation-only).  Below the threshold a wave per window is faster (the
+// lane-per-window kernels take about as long for 1 000 windows as for 65 536); LOCAMD_CHAIN_MIN_BATCH in the environment moves it
+// (0 = never), loc_window_set_chain_threshold / option "chain_min_batch" the handle's.
+long long effective_chain_min(const DispatchOpts& o) { return o.chain_min >= 0 ? o.chain_min : o.env_chain_min; }
+
+long long tree_min_batch(const DispatchOpts& o) {
+    const long long mn = effective_chain_min(o);
+    if (mn <= 0) return 1ll << 62;     // (threshold 0 = "never a batch kernel")
+    return mn < 256 ? mn : 256;
+}
+
+// option "arrow3" admits the batch: 0 = never, 1 = whenever it qualifies; default: windows of more than 64 poses — below that the
+// wave-per-window kernel keeps everything in LDS and is the better choice
+bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f) { return o.arrow3 >= 0 ? o.arrow3 == 1 : f.nv_max > 64; }
+
+// what the batch qualifies for BY ITS STRUCTURE: LOC_WINDOW_KERNEL_GENERAL, _CHAIN (block-tridiagonal, 6-DoF), _CHAIN3, _WAVE6, _WAVE6S,
+// _ARROW3 or _TREE.  aux: the set of host-built tables that ARROW3 (row order, packed edge records) / TREE (the schedule) fill.
+// Host-path calls (tc != nullptr; the resident batch passes none) keep the structural verdict of the previous batch in *tc: the same counts
+// and index tables (one 64-bit hash; a collision — 2^-64 per call — would hand a batch to a kernel built for another structure) skip the tests below.
+// What depends on the VALUES (translation_only: identity rotations, zero lever arms; arrow3's packed edge records) is looked at every time.
+Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, WinAux& aux, TopoCache* tc) {
+    const bool use_cache = tc && o.topology_cache;
+    unsigned long long key = 0;
+    bool hit = false;
+    if (use_cache) {
+        key = hash_structure(c, o.has_off1, b);
+        hit = tc->valid && tc->key == key && tc->n == b.n;
+    }
+    bool chain = true;
+    bool single_pairs = true;   // no EdgeSE3 anywhere and at most one range edge per pair of consecutive poses (wave6_lm_kernel's rank-1 couplings)
+    bool se3_pairs = false;     // EdgeSE3 factors, at most one per pair of consecutive poses, and at most one range edge per pair (wave6_lm_kernel<JAC, true>)
+    if (hit) { chain = tc->chain; single_pairs = tc->single_pairs; se3_pairs = tc->se3_pairs; }
+    if (!hit) chain_scan(c, b, true, chain, single_pairs, se3_pairs);
+    if (use_cache && !hit) { tc->valid = true; tc->key = key; tc->n = b.n; tc->chain = chain; tc->single_pairs = single_pairs; tc->se3_pairs = se3_pairs; tc->tree_tried = false; tc->tree_ok = false; }
+    if (chain) {
+        if (translation_only(c, n_anchors, b)) return {LOC_WINDOW_KERNEL_CHAIN3, hit};
+        if (single_pairs && f.wave6) return {LOC_WINDOW_KERNEL_WAVE6, hit};
+        // cfg/uwb_twist.yaml's window: a twist EdgeSE3 per consecutive pair next to the ranges — the wave-per-window kernel with full coupling
+        // blocks.  (The same window was tried on tree_wave_kernel first — a chain is a forest, rooted at its centre it has 8 levels: 0.58 … 0.67 ms
+        // per solve against the general kernel's 0.62 ms, tools/dev/probe_tree_chain.py: no speculative trials, one or two busy lanes per level.)
+        if (se3_pairs && f.wave6_se3) return {LOC_WINDOW_KERNEL_WAVE6S, hit};   // (nv + 1 lanes: the middle pose twice)
+        return {LOC_WINDOW_KERNEL_CHAIN, hit};
+    }
+    if (arrow3_wanted(o, f) && translation_only(c, n_anchors, b) && build_arrow_aux(c, b, aux)) return {LOC_WINDOW_KERNEL_ARROW3, hit};
+    // (option "tree" = 0: never.  One wave per window, so any batch gains; the host-side comparison of the index tables is only worth
+    //  it from a few hundred windows on — or from the chain threshold when that was lowered, as the tests do)
+    if (o.tree != 0 && b.n >= tree_min_batch(o)) {
+        if (hit && tc->tree_tried) {
+            if (tc->tree_ok) return {LOC_WINDOW_KERNEL_TREE, hit};   // (aux's schedule is still the one built for this structure)
+        } else {
+            const bool ok = build_tree_sched(c, o.has_off1, b, aux);
+            if (use_cache) { tc->tree_tried = true; tc->tree_ok = ok; }
+            if (ok) return {LOC_WINDOW_KERNEL_TREE, hit};
+        }
+    }
+    return {LOC_WINDOW_KERNEL_GENERAL, hit};
+}
+
+int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology) {
+    const long long mn = effective_chain_min(o);
+    const bool default_rule = o.chain_min < 0 && !o.env_chain_min_set;
+    if (o.has_off1) return LOC_WINDOW_KERNEL_GENERAL;   // (lever arms on endpoint 1: only the general kernel evaluates them)
+    if (mn <= 0 || o.natural_order) return LOC_WINDOW_KERNEL_GENERAL;   // threshold 0 = "never anything but the general kernel" (every structure)
+    if (topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) {   // (WAVE6S: the same rule for chains with EdgeSE3 factors)
+        // a 6-DoF chain batch that also qualifies for wave6_lm_kernel (one wave per window, rank-1 couplings).  Measured on twelve-pose
+        // cfg/uwb_imu.yaml windows: 1.15e7 windows/s at 4 096, 16 384 and 65 536 windows against chain_lm_kernel's 1.1e6 / 4.3e6 / 6.9e6 —
+        // so by default it takes every batch; an explicit threshold hands batches from that size on to the lane-per-window kernel.
+        // option "wave6" = 0: as before (the general kernel below the threshold, chain_lm_kernel from it on), for A/B runs.
+        const bool off = !o.wave6;
+        if (n >= mn && (off || !default_rule)) return LOC_WINDOW_KERNEL_CHAIN;
+        return off ? LOC_WINDOW_KERNEL_GENERAL : topology;
+    }
+    if (topology == LOC_WINDOW_KERNEL_ARROW3) return LOC_WINDOW_KERNEL_ARROW3;   // (one workgroup per window: any batch size)
+    if (topology == LOC_WINDOW_KERNEL_TREE) return n < tree_min_batch(o) ? LOC_WINDOW_KERNEL_GENERAL : LOC_WINDOW_KERNEL_TREE;
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3 && f.wave3) {
+        // translation-only chains of <= 64 poses (the node's single window first of all): one wave per window with 3x3 blocks, rank-1
+        // couplings and speculative LM trials.  Measured on ten-pose windows: 0.056 ms for one window, 3.6e7 windows/s (numeric) /
+        // 4.0e7 (analytic) from ~8 000 windows on — level with chain3_lm_kernel at 65 536 windows, ahead of it everywhere else — so by
+        // default it takes every batch; an explicit threshold (loc_window_set_chain_threshold / LOCAMD_CHAIN_MIN_BATCH) hands batches
+        // from that size on to the lane-per-window kernel.  Options "wave3" / "chain3" = 0: no such kernel (A/B runs, tests).
+        if ((default_rule || n < mn) && o.wave3 && o.chain3) return LOC_WINDOW_KERNEL_WAVE3;
+    }
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3 && default_rule && n >= 4096 && n < mn) {
+        // the translation-only kernel is worth it from ~4 096 windows on (it takes ~1 ms for any batch up to 16 384, the wave-per-window
+        // kernel 4.3e6 windows/s): e.g. one GPU's 8 192-window share of a 65 536-window job split over eight
+        if (o.chain3) return LOC_WINDOW_KERNEL_CHAIN3;
+    }
+    if (topology == LOC_WINDOW_KERNEL_GENERAL || n < mn) return LOC_WINDOW_KERNEL_GENERAL;
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3 && !o.chain3) return LOC_WINDOW_KERNEL_CHAIN;   // the 6-DoF kernel on a translation-only batch (A/B runs, tests)
+    return topology;
+}
+
+// The pass a batch's covariances are computed by, structured passes only; CovKind::None = not covered: lever arms on endpoint 1, or a batch
+// none of the three tests below takes.  In this order:
+// 1. windows of <= 64 poses that are chains (in any edge order): Chain3 for translation-only batches, Chain6 otherwise (covariance_kernel.hip);
+// 2. Arrow when the handle would solve the batch on arrow3_lm_kernel (batch_topology's rule: arrow3_wanted — by default windows of
+//    more than 64 poses only —, translation_only, build_arrow_aux's verdict) — arrow_covariance_kernel.hip; the structure test runs on `own`,
+//    a table set of the covariance's own, and the list size goes to the verdict's list_cap;
+// 3. windows of <= 64 poses: ForestOwn when the handle would solve the batch on a forest kernel (batch_topology's rule: option "tree",
+//    tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `own`, which the caller then sends
+//    to the device (need_upload).  keyed (the host path): the set is kept with the hash of the structure it was built for, and a batch of
+//    the same structure reuses it, device copy included.
+static CovVerdict structured_covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b,
+                                             WinAux& own, SchedKey* keyed) {
+    const CovVerdict none{CovKind::None, false, 0, 0};
+    if (o.has_off1) return none;
+    const bool small = c.nv_max <= 64;
+    if (small) {
+        bool chain = false, single_pairs = false, se3_pairs = false;
+        chain_scan(c, b, false, chain, single_pairs, se3_pairs);
+        if (chain) {
+            if (!f.cov_chain) return none;
+            return {translation_only(c, n_anchors, b) ? CovKind::Chain3 : CovKind::Chain6, false, 0, 0};
+        }
+    }
+    if (arrow3_wanted(o, f) && f.cov_arrow && translation_only(c, n_anchors, b) && build_arrow_aux(c, b, own, true))
+        return {CovKind::Arrow, false, own.arrow_list_cap, 0};
+    if (!small) return none;
+    if (o.tree == 0 || b.n < tree_min_batch(o)) return none;
+    if (keyed) {
+        const unsigned long long key = hash_structure(c, o.has_off1, b);
+        if (keyed->valid && keyed->key == key && keyed->n == b.n) return {CovKind::ForestOwn, false, 0, 0};
+        keyed->valid = false;   // (valid again once the caller has uploaded the new tables)
+        keyed->key = key; keyed->n = b.n;
+    }
+    if (!build_tree_sched(c, o.has_off1, b, own)) return none;
+    return {CovKind::ForestOwn, true, 0, 0};
+}
+
+long long cov_switches(const DispatchOpts& o) {
+    const long long mn = tree_min_batch(o);
+    return ((long long)(o.arrow3 + 1) << 4 | (long long)(o.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8);
+}
+
+// 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is Envelope —
+//    envelope_covariance_kernel.hip in the caller's pose order; the batch's largest envelope goes to the verdict's env_blocks.
+//    pt: the pairs of a joint call count as edges of that envelope (none: the plain envelope).
+CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, const PairTables& pt,
+                           WinAux& own, SchedKey* keyed) {
+    const CovVerdict v = structured_covariance_kind(c, o, f, n_anchors, b, own, keyed);
+    if (v.kind != CovKind::None || o.has_off1 || !o.cov_general) return v;
+    if (!f.cov_envelope) return v;
+    const long long blocks = envelope_blocks_max_joint(c, b, pt);
+    if (blocks < 0) return v;   // (cannot happen: the tables were validated)
+    return {CovKind::Envelope, false, 0, blocks};
+}
+
+// (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
+// (an arrowhead batch likewise while option "arrow3" still admits it; the envelope pass while option "covariance_general" is 1)
+bool cov_admitted(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind) {
+    const bool forest = kind == CovKind::Forest || kind == CovKind::ForestOwn;
+    const bool arrow = kind == CovKind::Arrow, envelope = kind == CovKind::Envelope;
+    const bool refused = o.has_off1 || (f.nv_max > 64 && !arrow && !envelope) || kind == CovKind::Unclassified || kind == CovKind::None ||
+                         (forest && (n < tree_min_batch(o) || o.tree == 0)) || (arrow && (!arrow3_wanted(o, f) || !f.cov_arrow)) || (envelope && !o.cov_general);
+    return !refused;
+}
+
+bool cov_stale(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind, long long env_switches) {
+    // (the envelope pass holds the batch only while the three structured tests would still decline it — they are run again when a
+    //  switch they read has changed, so that the resident batch takes the pass loc_window_covariance_host takes)
+    if (kind == CovKind::Envelope) return env_switches != cov_switches(o);
+    // (option "covariance_general": a structured verdict the handle's switches no longer admit is no verdict — the batch is classified under
+    //  the switches as they are now, and lands on the envelope pass)
+    return kind != CovKind::Unclassified && kind != CovKind::None && o.cov_general && !o.has_off1 && !cov_admitted(o, f, n, kind);
+}
+
+}  // namespace locamd

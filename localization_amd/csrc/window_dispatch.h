@@ -1,0 +1,78 @@
+// Which solve kernel and which covariance pass a batch of windows takes: the rules, free of any handle and HIP state (window_dispatch.cpp
+// compiles with a plain host compiler, as window_structure.cpp does; tests/host/window_dispatch_driver.cpp runs the rules on the CPU).
+// capi_window.cpp keeps the switches and the capacity facts in its handle and asks here; a new kernel or covariance pass is registered
+// in pick_kernel / batch_topology or CovKind / covariance_kind / cov_admitted, and gets its launch in capi_window.cpp.
+#pragma once
+#include "window_structure.h"
+
+namespace locamd {
+
+// kernel-selection switches: the environment is read ONCE, by loc_window_create (loc_window_set_option and the setters change them afterwards)
+struct DispatchOpts {
+    long long env_chain_min = 12288;   // LOCAMD_CHAIN_MIN_BATCH, or the default
+    bool env_chain_min_set = false;
+    int arrow3 = -1;                   // LOCAMD_ARROW3: -1 default (windows of more than 64 poses), 0 never, 1 whenever the batch qualifies
+    int tree = -1;                     // LOCAMD_TREE: -1 default, 0 never, 2 the lane-per-window variant
+    bool wave3 = true, wave6 = true, chain3 = true, zero_copy = true, topology_cache = true;
+    bool cov_general = false;          // "covariance_general" 1: whatever the three structured covariance passes decline goes to envelope_covariance_kernel.hip
+    bool kernel_events = true;         // "kernel_events" 0: no HIP events around the launch of a zero-copy solve (loc_window_last_kernel_ms then reports launch-to-completion on the host clock)
+    long long chain_min = -1;          // smallest batch that takes a lane-per-window kernel (-1: the default / LOCAMD_CHAIN_MIN_BATCH)
+    bool natural_order = false;        // loc_window_set_ordering
+    bool has_off1 = false;             // lever arms of endpoint 1 are set (loc_window_set_endpoint1_offsets)
+};
+
+// what depends on the handle's capacities alone: the kernels' LDS needs against their limits, taken once by loc_window_create
+struct DispatchFits {
+    bool wave6 = false;          // nv_max <= 64 and wave6_lm_kernel's LDS
+    bool wave6_se3 = false;      // nv_max <= 63, ns_max <= 64 and wave6_lm_kernel<JAC, true>'s LDS
+    bool wave3 = false;          // nv_max <= 64 and wave3_lm_kernel's LDS
+    bool cov_chain = false, cov_arrow = false, cov_envelope = false;   // the chain (6x6) / arrowhead / envelope covariance pass within 160 KiB
+    int nv_max = 0;
+};
+
+// the covariance pass of a batch
+enum class CovKind : int {
+    Unclassified = -1,   // the first covariance call classifies the batch
+    None = 0,            // not covered (LOC_ERR_UNSUPPORTED)
+    Chain3, Chain6,      // covariance_kernel.hip with 3x3 (translation-only batches) / 6x6 blocks
+    Forest, ForestOwn,   // forest_covariance_kernel.hip on the solve's schedule / on the schedule the covariance pass built itself
+    Arrow,               // arrow_covariance_kernel.hip
+    Envelope             // envelope_covariance_kernel.hip (option "covariance_general")
+};
+
+long long effective_chain_min(const DispatchOpts& o);
+long long tree_min_batch(const DispatchOpts& o);
+bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f);
+// the switches the three structured covariance tests read besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold)
+long long cov_switches(const DispatchOpts& o);
+// the kernel a batch of n windows of that structure (batch_topology's verdict) takes NOW (threshold, ordering override, the options)
+int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology);
+// may the resident batch of n windows with verdict `kind` be served now
+bool cov_admitted(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind);
+// is that verdict out of date: the batch is classified again under the switches as they are now.  env_switches: cov_switches() when it was classified
+bool cov_stale(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind, long long env_switches);
+
+// structural verdict of the last host-path batch, keyed on a hash of (n, counts, index tables): a caller that replays one graph
+// with new measurements (the node's window between two slides, a Monte-Carlo batch) skips the chain / forest / arrowhead tests
+struct TopoCache {
+    bool valid = false;
+    unsigned long long key = 0;
+    int64_t n = 0;
+    bool chain = false, single_pairs = false, se3_pairs = false, tree_ok = false, tree_tried = false;
+};
+struct Topology { int kind; bool cached; };   // LOC_WINDOW_KERNEL_* by structure; the verdict came from the cache
+Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, WinAux& aux, TopoCache* tc);
+
+// the structure the host path's own forest schedule (its cov_aux) was built for, device copy included
+struct SchedKey {
+    bool valid = false;
+    unsigned long long key = 0;
+    int64_t n = 0;
+};
+// need_upload: `own` holds a new forest schedule for the caller to send to the device; list_cap: the arrowhead pass's list size;
+// env_blocks: the batch's largest envelope
+struct CovVerdict { CovKind kind; bool need_upload; int list_cap; long long env_blocks; };
+CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, const PairTables& pt,
+                           WinAux& own, SchedKey* keyed);
+
+}  // namespace locamd

@@ -378,7 +378,7 @@ bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool st
 // with different measurements in every instance): every instance has the same counts and index tables, and the pose-to-pose
 // edges form a forest.  Builds the elimination schedule tree_lm_kernel walks: nodes in post-order (children before their parent,
 // a node's children heavy subtree first so that the leaves of one parent are consecutive), per node its parent and its edges.
-// Layout of the int table: node[nv] par[nv] r_off[nv+1] r_list[nr] p_off[nv+1] p_list[np] s_off[nv+1] s_list[ns] r_idx[2 nr] s_idx[4 ns].
+// Layout of the int table: bind_tree_sched below, which walks it in the order the code from "std::vector<int32_t>& t = A.h_tsched" on emits it.
 bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
     const int nv = b.counts[0], nr = b.counts[1], np = b.counts[2], ns = b.counts[3];
     if (nv < 2 || nv > 64 || has_off1) return false;
@@ -528,6 +528,27 @@ bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, Wi
     for (int k = 0; k < nv; ++k) if ((int)re[(size_t)k].size() > A.tsched.max_r_per_node) A.tsched.max_r_per_node = (int)re[(size_t)k].size();
     A.tsched.nv = nv; A.tsched.nr = nr; A.tsched.np = np; A.tsched.ns = ns; A.tsched.depth = maxdepth + 1; A.tsched.nroots = nroots;
     return true;
+}
+
+// ts's pointers into a copy of the table build_tree_sched wrote (A.h_tsched, or its device copy) that starts at base; ts's sizes are those
+// build_tree_sched set.  The table's length: the int32s from base to the end of w_kpos.
+size_t bind_tree_sched(TreeSched& ts, const int32_t* base) {
+    const int nv = ts.nv, nr = ts.nr, np = ts.np, ns = ts.ns;
+    const int32_t* p = base;
+    ts.node = p; p += nv; ts.par = p; p += nv;
+    ts.r_off = p; p += nv + 1; ts.r_list = p; p += nr;
+    ts.p_off = p; p += nv + 1; ts.p_list = p; p += np;
+    ts.s_off = p; p += nv + 1; ts.s_list = p; p += ns;
+    ts.r_idx = p; p += 2 * nr; ts.s_idx = p; p += 4 * ns;
+    ts.w_par = p; p += nv; ts.w_height = p; p += nv;
+    ts.w_koff = p; p += nv + 1; ts.w_klist = p; p += nv - ts.nroots;
+    ts.w_roff = p; p += nv + 1; ts.w_rlist = p; p += nr;
+    ts.w_poff = p; p += nv + 1; ts.w_plist = p; p += np;
+    ts.w_soff = p; p += nv + 1; ts.w_slist = p; p += ns;
+    ts.w_kleaf = p; p += nv;
+    ts.w_ulist = p; p += ts.nu;
+    ts.w_kpos = p; p += nv;
+    return (size_t)(p - base);
 }
 
 }  // namespace locamd

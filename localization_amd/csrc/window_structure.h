@@ -41,5 +41,6 @@ int check_pairs(int64_t n, const int32_t* counts, const PairTables& pt);
 long long envelope_blocks_max_joint(const WindowCaps& c, const HostBatch& b, const PairTables& pt);
 bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only = false);   // fills A.h_a* and A.arrow_*
 bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);                // fills A.h_tsched and A.tsched's sizes
+size_t bind_tree_sched(TreeSched& ts, const int32_t* base);   // ts's pointers into a copy of that table at base; returns the table's length
 
 }  // namespace locamd

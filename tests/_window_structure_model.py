@@ -342,15 +342,19 @@ def is_forest(nv, pairs):
 
 
 def check_tree_sched(b, out):
-    """Walks h_tsched with upload_tree_sched's pointer steps (capi_window.cpp) and checks every list against instance 0's graph."""
+    """Walks h_tsched section by section, checks that bind_tree_sched (window_structure.cpp) puts TreeSched's pointers at those sections
+    and that the last one ends where the table ends, and checks every list against instance 0's graph."""
     sizes = [int(x) for x in out["tree_sizes"]]
     nv, nr, npr, ns, depth, nroots, nlev, max_s, nu, max_r = sizes
     assert [nv, nr, npr, ns] == b.counts[0].tolist()
     t = out["tsched"].tolist()
     at = [0]
 
+    starts = []
+
     def take(k):
         assert at[0] + k <= len(t), "the schedule is shorter than its pointer walk"
+        starts.append(at[0])
         at[0] += k
         return t[at[0] - k:at[0]]
     node, par = take(nv), take(nv)
@@ -365,6 +369,9 @@ def check_tree_sched(b, out):
     w_soff, w_slist = take(nv + 1), take(ns)
     w_kleaf, w_ulist, w_kpos = take(nv), take(nu), take(nv)
     assert at[0] == len(t), (at[0], len(t))
+    bind = [int(x) for x in out["tsched_bind"]]
+    assert len(starts) == 23 and bind[:-1] == starts, (bind, starts)      # TreeSched's pointers in its declaration order = the sections' order
+    assert bind[-1] == len(t) == starts[-1] + nv                          # the last section, w_kpos, ends at the end of the table
     redges = b.r_idx[0, :nr].tolist()
     sedges = [x[:2] for x in b.s_idx[0, :ns].tolist()]
     prior = b.p_idx[0, :npr].tolist()

@@ -11,6 +11,7 @@
 // <out>: a list of sections, each  char name[16], int32 type (0: int32, 1: double, 2: int64), int64 count, data.  Per batch: "batch"
 // {index, hw}, "check", "envelope"; when the counts fit the capacities "hash" {has_off1 as given, flipped}; and for a batch
 // check_instances accepts the rest (only a validated batch may reach those passes, capi_window.cpp: validate_instances comes first).
+// "tsched_bind": where bind_tree_sched puts TreeSched's 23 pointers in "tsched" (offsets in int32s), and the table length it returns.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -120,6 +121,16 @@ int main(int argc, char** argv) {
             if (ok) {
                 out.i32("tree_sizes", {t.nv, t.nr, t.np, t.ns, t.depth, t.nroots, t.nlev, t.max_se3_per_node, t.nu, t.max_r_per_node});
                 out.i32("tsched", A.h_tsched);
+                // bind_tree_sched on the host table: every pointer's offset from the base in TreeSched's order, then the length it reports
+                TreeSched bound = t;
+                const int32_t* base = A.h_tsched.data();
+                const int64_t len = (int64_t)bind_tree_sched(bound, base);
+                std::vector<int64_t> at;
+                for (const int32_t* p : {bound.node, bound.par, bound.r_off, bound.r_list, bound.p_off, bound.p_list, bound.s_off, bound.s_list, bound.r_idx, bound.s_idx,
+                                         bound.w_par, bound.w_height, bound.w_koff, bound.w_klist, bound.w_roff, bound.w_rlist, bound.w_poff, bound.w_plist, bound.w_soff,
+                                         bound.w_slist, bound.w_kleaf, bound.w_ulist, bound.w_kpos}) at.push_back((int64_t)(p - base));
+                at.push_back(len);
+                out.i64("tsched_bind", at);
             }
         }
         {
