@@ -228,6 +228,17 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms);
  * [n_instances][nr_max][3] (xyz per range edge; for a fixed endpoint 1 — identity rotation — the point is the anchor + o1), or
  * NULL to go back to none.  Batches with endpoint-1 lever arms are solved by the general kernel (LOC_WINDOW_KERNEL_GENERAL). */
 int loc_window_set_endpoint1_offsets(loc_window* w, int64_t n_instances, const double* off1_xyz);
+/* g2o's EdgeSE3Prior takes a full 6x6 information matrix (a pose source with a full covariance, the marginal prior of a dropped pose:
+ * loc_window_marginal_prior_host); p_val holds a diagonal.  This call supplies full matrices for the EdgeSE3Prior factors of every LATER
+ * solve / upload / covariance / marginal-prior call: pinfo = [n_instances][np_max][36], row-major, order (tx ty tz qx qy qz) as s_val's; row e
+ * REPLACES the diagonal p_val[b][e][12..17] (which is then not read).  NULL: back to the diagonals.  Everything is checked before anything
+ * changes: LOC_ERR_INVALID for n_instances <= 0 or beyond the handle's batch, for a solver without priors (np_max = 0) and for a matrix
+ * that is not exactly symmetric (W[i][j] != W[j][i]; every row of the n_instances * np_max is looked at, unused ones included).  While a
+ * table of n instances is set, a call with more than n instances is LOC_ERR_INVALID.  Priors stay non-robust: chi2 = e^T W e,
+ * H += J^T W J, b -= J^T W e.  Such a handle solves on the general kernel (LOC_WINDOW_KERNEL_GENERAL), and its covariances come from the
+ * envelope pass alone (option "covariance_general" = 1; LOC_ERR_UNSUPPORTED with nothing written otherwise).  The device table is
+ * allocated by the first call and freed with the handle. */
+int loc_window_set_prior_information(loc_window* w, int64_t n_instances, const double* pinfo);
 /* LOC_JAC_NUMERIC_G2O (default: the reference's configuration) or LOC_JAC_ANALYTIC (opt-in fast mode) for the EdgeSE3Range
  * factors of every later solve */
 int loc_window_set_jacobian(loc_window* w, int32_t jacobian);
@@ -355,9 +366,46 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
  *     same star packed key-first n (n + 1) / 2.  The envelopes live in a device workspace of the handle, allocated on first use and grown on
  *     demand (a failed allocation is LOC_ERR_HIP); loc_window_covariance_plan reports its size beforehand.
  *     Windows with endpoint-1 lever arms stay LOC_ERR_UNSUPPORTED under either value of the option.
+ *     A handle with full-information priors (loc_window_set_prior_information) is served by this pass ALONE, whatever its batch's structure:
+ *     items 1 to 3 read p_val's diagonal and decline it, so with the option at 0 its covariance calls are LOC_ERR_UNSUPPORTED.
  * Stateless: does not change the handle's resident batch, last kernel kind / ms, topology cache or options.  Synchronous.  Small calls (inputs
  * and outputs within the 4 MiB staging block) travel as loc_window_solve_host's small ones do; larger ones stage through a device block of
  * their own — unlike a large loc_window_solve_host they leave the resident batch intact. */
+/* The marginal prior of a dropped pose ("The marginal prior of a dropped pose"): what a sliding window keeps of its oldest pose
+ * instead of throwing away everything that pose's factors knew (the reference's robot.cpp:92-98).  TRANSLATION-ONLY batches.  For window b,
+ * d = drop[b], m = the one pose that pose-to-pose ranges join to d, x = poses: the factors with d as an endpoint (ranges to anchors, ranges
+ * between d and m — several allowed, either direction —, priors on d) are linearised at x by the covariance definition (rho' = 1 / (1 + chi2)
+ * on ranges, the handle's Jacobian mode, priors analytic and not robust, with their full matrix when loc_window_set_prior_information has set
+ * one — which makes the call recursive: the prior a slide produced is a removed factor of a later slide); d's exactly-zero-diagonal coordinates
+ * are excluded, H_dd is factored under both pivot tests of the covariance passes, and
+ *   Lambda = H_mm - H_md H_dd^-1 H_dm (symmetrised),  gamma = g_m - H_md H_dd^-1 g_d.
+ * Lambda is positive semi-definite and usually rank-deficient (one rank-1 smoothness link passes on one direction), so the pivot rule is not
+ * reused on it: of its symmetric eigen-decomposition the pairs with lambda_k > 1e-11 lambda_max are kept.  Same host layouts as
+ * loc_window_solve_host (poses is not written), the handle's anchors and Jacobian mode; stateless and synchronous, the resident batch is left alone.
+ *   drop   int32  [n]      the pose slot to marginalise out, in [0, nv_b)
+ *   slot   int32  [n]      the pose the prior sits on (m); -1: none
+ *   prior  double [n][48]  Z^-1 as R(9), t(3), then the information 6x6 row-major (top-left 3x3 = sum of the kept lambda_k v_k v_k^T, zeros
+ *                          elsewhere): an s_val row's layout = a p_val row's [0..11] followed by a loc_window_set_prior_information row.
+ *                          Z^-1 = (I, e0 - t_m), so that toVectorMQT(Z^-1 X_m) = e0 and EdgeSE3Prior(Z, information) on m has gradient gamma and
+ *                          Hessian Lambda at x: the removed factors' quadratic with d minimised out
+ *   grad   double [n][6]   gamma (rotation entries 0)
+ *   shift  double [n][6]   e0 = sum over the kept pairs of (v_k^T gamma / lambda_k) v_k: the minimum-norm solution of Lambda e0 = gamma
+ *   rank   int32  [n]      eigenpairs kept
+ *   status int32  [n]      LOC_OK or LOC_ERR_SINGULAR
+ * A failed pivot of H_dd (the removed factors do not determine d: e.g. one anchor range alone) is LOC_ERR_SINGULAR for that window with slot =
+ * m, information, grad and shift exact zeros, Z^-1 = X_m^-1 and rank 0 — zeros, not NaN, on purpose: the row is an input of the next solve,
+ * and a zero-information prior IS the reference's plain drop.  A dropped pose without a neighbour: slot -1, zeros, identity Z^-1, LOC_OK
+ * (whatever its own factors are).  Sums over edges run in edge order (ranges, then priors): the same bits on every run and for every position
+ * of a window in the batch.
+ * Checked on the host before anything is launched, nothing written on failure: LOC_ERR_INVALID for a drop slot outside [0, nv_b) (and for what
+ * loc_window_solve_host refuses); LOC_ERR_UNSUPPORTED when endpoint-1 lever arms are set, when the batch is not translation-only (no EdgeSE3,
+ * identity rotations, zero lever arms, priors with identity measurement rotation and no rotation information; with a full-matrix table: the
+ * rotation rows and columns of EVERY matrix of the table exactly 0), or when pose-to-pose edges join some window's dropped pose to more than one
+ * other pose (a marginal over several poses is not a unary prior; anchor self-calibration arrowheads are such windows).  6-DoF windows are out on
+ * purpose.  loc_window_last_covariance_ms reports the pass's kernel time. */
+int loc_window_marginal_prior_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                                   const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, const int32_t* drop,
+                                   int32_t* slot, double* prior, double* grad, double* shift, int32_t* rank, int32_t* status);
 int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses,
                                const int32_t* r_idx, const double* r_val, const int32_t* p_idx, const double* p_val,
                                const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask, int32_t* status);

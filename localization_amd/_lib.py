@@ -44,11 +44,11 @@ EXPORTED_SYMBOLS = [
     "loc_snapshot_solve_host_kmb", "loc_snapshot_solve_device_cov", "loc_snapshot_solve_host_kmb_cov", "loc_host_alloc", "loc_host_free",
     "loc_snapshot_timing_begin", "loc_snapshot_timing_end",
     "loc_window_create", "loc_window_destroy", "loc_window_set_anchors", "loc_window_lds_bytes", "loc_window_solve_host",
-    "loc_window_last_kernel_ms", "loc_window_set_endpoint1_offsets", "loc_window_set_jacobian", "loc_window_set_ordering", "loc_window_set_chain_threshold", "loc_window_last_kernel_kind", "loc_window_set_option", "loc_window_last_host_timing", "loc_window_upload",
+    "loc_window_last_kernel_ms", "loc_window_set_endpoint1_offsets", "loc_window_set_prior_information", "loc_window_set_jacobian", "loc_window_set_ordering", "loc_window_set_chain_threshold", "loc_window_last_kernel_kind", "loc_window_set_option", "loc_window_last_host_timing", "loc_window_upload",
     "loc_window_solve_resident", "loc_window_download", "loc_window_poses_device", "loc_window_result_device",
     "loc_window_timing_begin", "loc_window_timing_end",
     "loc_window_covariance_host", "loc_window_covariance_resident", "loc_window_last_covariance_ms", "loc_window_covariance_plan",
-    "loc_window_joint_covariance_host", "loc_window_joint_covariance_resident", "loc_window_joint_covariance_plan",
+    "loc_window_marginal_prior_host", "loc_window_joint_covariance_host", "loc_window_joint_covariance_resident", "loc_window_joint_covariance_plan",
     "loc_node_default_config", "loc_node_create", "loc_node_destroy", "loc_node_add_range", "loc_node_add_imu",
     "loc_node_add_pose", "loc_node_add_twist", "loc_node_add_lidar", "loc_node_add_rl_range", "loc_node_solve", "loc_node_get_path",
     "loc_node_number_measurements", "loc_node_last_timing", "loc_node_last_kernel_kind", "loc_node_flush_tail", "loc_node_set_deferred", "loc_node_solve_pending", "loc_nodes_solve_batch",
@@ -106,6 +106,7 @@ def lib():
     L.loc_window_last_kernel_ms.argtypes = [vp, dp]
     L.loc_window_set_jacobian.argtypes = [vp, C.c_int32]
     L.loc_window_set_endpoint1_offsets.argtypes = [vp, C.c_int64, dp]
+    L.loc_window_set_prior_information.argtypes = [vp, C.c_int64, dp]
     L.loc_window_set_ordering.argtypes = [vp, C.c_int32]
     L.loc_window_set_chain_threshold.argtypes = [vp, C.c_int64]
     L.loc_window_last_kernel_kind.argtypes = [vp, ip]
@@ -117,6 +118,7 @@ def lib():
     L.loc_window_timing_begin.argtypes = [vp, C.c_int32]
     L.loc_window_timing_end.argtypes = [vp, ip, dp, dp]
     L.loc_window_covariance_host.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp, dp, ip, ip]
+    L.loc_window_marginal_prior_host.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp, ip, ip, dp, dp, dp, ip, ip]
     L.loc_window_covariance_resident.argtypes = [vp, vp, vp, vp, vp]
     L.loc_window_last_covariance_ms.argtypes = [vp, dp]
     L.loc_window_covariance_plan.argtypes = [vp, C.c_int64, ip, ip, ip, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]

@@ -55,6 +55,9 @@ struct loc_window {
     double* d_arrow_ws = nullptr;
     size_t arrow_ws_nb = 0;         // border size d_arrow_ws was allocated for
     double* d_roff1 = nullptr;      // optional lever arms of endpoint 1 (loc_window_set_endpoint1_offsets: opt.has_off1), [B][nr_max][3]
+    double* d_pinfo = nullptr;      // optional full information matrices of the priors (loc_window_set_prior_information: opt.has_pinfo), [B][np_max][36]
+    long long n_pinfo = 0;          // instances the table describes: a call with more is refused
+    bool pinfo_translation = false; // no matrix of the table has rotation rows or columns (the marginal-prior pass's translation-only test)
     int resident_topology = 0;      // LOC_WINDOW_KERNEL_* the uploaded batch qualifies for by its structure (the batch-size threshold is applied per solve)
     long long n_resident = 0;
     int resident_min_anchors = 0;   // anchors the resident batch references (loc_window_set_anchors may not shrink below it)
@@ -124,7 +127,7 @@ static void release_slot(loc_window::BatchSlot& S) {
 int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
-    void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_tree_ws, w->d_arrow_ws};
+    void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
@@ -266,6 +269,7 @@ int loc_window_set_anchors(loc_window* w, int32_t n_anchors, const double* ancho
 static int validate_instances(const loc_window* w, const locamd::HostBatch& b) {
     if (!w || !b.counts || !b.poses) return locamd_fail(LOC_ERR_INVALID, "window solve arguments");
     if (b.n <= 0 || b.n > w->B) return locamd_fail(LOC_ERR_INVALID, "n_instances");
+    if (w->opt.has_pinfo && b.n > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "n_instances: more windows than loc_window_set_prior_information described");
     const locamd::WindowCaps& c = w->caps;
     if ((c.nr_max && (!b.r_idx || !b.r_val)) || (c.np_max && (!b.p_idx || !b.p_val)) || (c.ns_max && (!b.s_idx || !b.s_val)))
         return locamd_fail(LOC_ERR_INVALID, "missing edge arrays");
@@ -338,7 +342,7 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
     a.r_idx = (const int32_t*)d.t[locamd::kRIdx]; a.r_val = (const double*)d.t[locamd::kRVal];
     a.p_idx = (const int32_t*)d.t[locamd::kPIdx]; a.p_val = (const double*)d.t[locamd::kPVal];
     a.s_idx = (const int32_t*)d.t[locamd::kSIdx]; a.s_val = (const double*)d.t[locamd::kSVal];
-    a.anchors = anchors; a.result = result; a.r_off1 = result && w->opt.has_off1 ? w->d_roff1 : nullptr; a.workspace = result ? w->d_workspace : nullptr;
+    a.anchors = anchors; a.result = result; a.r_off1 = result && w->opt.has_off1 ? w->d_roff1 : nullptr; a.p_info = w->opt.has_pinfo ? w->d_pinfo : nullptr; a.workspace = result ? w->d_workspace : nullptr;
     a.n_anchors = w->n_anchors; a.B = (int)n; a.iterations = w->iterations; a.jacobian = w->jacobian; a.natural_order = w->opt.natural_order; a.caps = w->caps;
     return a;
 }
@@ -437,6 +441,31 @@ int loc_window_set_endpoint1_offsets(loc_window* w, int64_t n, const double* off
     // rows [n, B): no lever arm (a call with fewer instances than an earlier one must not leave that one's behind)
     if (n < w->B) LOC_HIP(hipMemset((char*)w->d_roff1 + (size_t)n * row, 0, (size_t)(w->B - n) * row));
     w->opt.has_off1 = true;
+    return LOC_OK;
+}
+
+int loc_window_set_prior_information(loc_window* w, int64_t n, const double* pinfo) {
+    if (!w) return locamd_fail(LOC_ERR_INVALID, "set_prior_information");
+    if (!pinfo) { w->opt.has_pinfo = false; w->n_pinfo = 0; return LOC_OK; }   // (has_pinfo is part of the structure hash, as has_off1 is)
+    if (n <= 0 || n > w->B) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: n_instances");
+    if (w->caps.np_max <= 0) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: no prior edges in this solver");
+    // everything is checked before anything changes: a matrix that is not exactly symmetric (a NaN entry included) leaves the handle as it was
+    const size_t rows = (size_t)n * w->caps.np_max;
+    for (size_t e = 0; e < rows; ++e) {
+        const double* W = pinfo + e * 36;
+        for (int i = 1; i < 6; ++i)
+            for (int j = 0; j < i; ++j)
+                if (!(W[i * 6 + j] == W[j * 6 + i])) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: an information matrix is not symmetric");
+    }
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = wait_resident(w)) return rc;
+    LOC_HIP(hipStreamSynchronize(w->stream));
+    const size_t row = (size_t)w->caps.np_max * 36 * sizeof(double);
+    if (!w->d_pinfo) LOC_HIP(hipMalloc((void**)&w->d_pinfo, (size_t)w->B * row));
+    LOC_HIP(hipMemcpy(w->d_pinfo, pinfo, (size_t)n * row, hipMemcpyHostToDevice));
+    w->opt.has_pinfo = true;
+    w->n_pinfo = n;
+    w->pinfo_translation = locamd::prior_information_translation_only(rows, pinfo);
     return LOC_OK;
 }
 
@@ -598,6 +627,7 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
 
 int loc_window_solve_resident(loc_window* w, void* hip_stream) {
     if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
@@ -644,7 +674,7 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
 // ---- marginal covariances (covariance_kernel.hip: chains; arrow_covariance_kernel.hip: arrowheads; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
 #define LOC_COV_UNSUPPORTED ": every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle solves on arrow3_lm_kernel (option arrow3), " \
                             "or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold), " \
-                            "or option covariance_general must be 1 (any structure and length, in the caller's pose order); no endpoint-1 lever arms"
+                            "or option covariance_general must be 1 (any structure and length, in the caller's pose order: the only pass for full-information priors); no endpoint-1 lever arms"
 
 // the pass of a batch of covariance_kind's `kind`; S: the batch's table sets and workspaces (a forest that loc_window_upload classified,
 // Forest, walks the resident solve's schedule slot[1].aux; ForestOwn the covariance's own, S.cov_aux)
@@ -737,6 +767,67 @@ int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* co
     return LOC_OK;
 }
 
+// ---- the marginal prior of a dropped pose (marginal_prior_kernel.hip) ------------------------------------------------------------
+// stateless and synchronous; staged like loc_window_covariance_host: small calls through the staging block, large ones through the
+// covariance's device block — the resident batch's arrays are not touched
+int loc_window_marginal_prior_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                                   const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, const int32_t* drop,
+                                   int32_t* slot, double* prior, double* grad, double* shift, int32_t* rank, int32_t* status) {
+    if (!drop || !slot || !prior || !grad || !shift || !rank || !status) return locamd_fail(LOC_ERR_INVALID, "marginal prior: drop and output arrays");
+    const locamd::HostBatch b{n, poses, counts, r_val, p_val, s_val, r_idx, p_idx, s_idx};
+    if (int rc = validate_instances(w, b)) return rc;
+    const locamd::WindowCaps& c = w->caps;
+    const int bad = locamd::check_marginal_drop(c, b, drop);
+    if (bad == 1) return locamd_fail(LOC_ERR_INVALID, "marginal prior: a drop slot outside its window");
+    if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: no endpoint-1 lever arms");
+    if (!locamd::translation_only(c, w->n_anchors, b, w->opt.has_pinfo) || (w->opt.has_pinfo && !w->pinfo_translation))
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: translation-only batches alone (no EdgeSE3, identity rotations, zero lever arms, priors without rotation information)");
+    if (bad == 2) return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: pose-to-pose edges join a dropped pose to more than one other pose");
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    const size_t N = (size_t)n;
+    // one block: outputs [slot | prior | grad | shift | rank | status], then the inputs [drop | poses | counts | ... | s_idx]
+    void* const out[6] = {slot, prior, grad, shift, rank, status};
+    const size_t pre_bytes[7] = {N * sizeof(int32_t), N * 48 * sizeof(double), N * 6 * sizeof(double), N * 6 * sizeof(double), N * sizeof(int32_t), N * sizeof(int32_t),
+                                 N * sizeof(int32_t)};
+    const locamd::BlockLayout L = locamd::pack_block(c, N, pre_bytes, 7, kPoses);
+    const size_t in0 = L.pre[6];   // the outputs end and the inputs begin here
+    hipStream_t st = w->stream;
+    char* d;
+    const bool small = L.end <= kStageBytes;
+    if (small) {
+        if (int rc = ensure_stage(w)) return rc;
+        locamd::stage_tables(w->h_stage, L, c, b);
+        std::memcpy(w->h_stage + L.pre[6], drop, pre_bytes[6]);
+        d = w->d_stage;
+        LOC_HIP(hipMemcpyAsync(d + in0, w->h_stage + in0, L.end - in0, hipMemcpyHostToDevice, st));
+    } else {
+        LOC_HIP(locamd::grow_buffers(w->cov_cap, L.end, {{w->d_cov, L.end}}));
+        d = w->d_cov;
+        LOC_HIP(copy_tables(c, N, locamd::tables_at(d, L).t, b.tables().t, hipMemcpyHostToDevice, &st));
+        LOC_HIP(hipMemcpyAsync(d + L.pre[6], drop, pre_bytes[6], hipMemcpyHostToDevice, st));
+    }
+    const locamd::WindowArgs a = window_args(w, locamd::tables_at(d, L), n, nullptr, w->d_anchors, nullptr);
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    const hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)(d + L.pre[6]), (int32_t*)(d + L.pre[0]), (double*)(d + L.pre[1]), (double*)(d + L.pre[2]),
+                                                              (double*)(d + L.pre[3]), (int32_t*)(d + L.pre[4]), (int32_t*)(d + L.pre[5]), st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    if (small) {
+        LOC_HIP(hipMemcpyAsync(w->h_stage, d, in0, hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipStreamSynchronize(st));
+        for (int k = 0; k < 6; ++k) std::memcpy(out[k], w->h_stage + L.pre[k], pre_bytes[k]);
+    } else {
+        for (int k = 0; k < 6; ++k) LOC_HIP(hipMemcpyAsync(out[k], d + L.pre[k], pre_bytes[k], hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipStreamSynchronize(st));
+    }
+    float ms = 0;
+    LOC_HIP(hipEventElapsedTime(&ms, w->cov_ev0, w->cov_ev1));
+    w->cov_ms = ms;
+    w->cov_pending = false;
+    return LOC_OK;
+}
+
 int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
                                const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, double* cov, int32_t* mask,
                                int32_t* status) {
@@ -749,6 +840,7 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
     if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
     if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
     if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
+    if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
     const locamd::PairTables pt{npair_max, pair_counts_host, pairs_host};
     if (int rc = validate_pairs(w->n_resident, w->res_counts.data(), pt, cross_dev)) return rc;
     const bool joint = npair_max > 0;

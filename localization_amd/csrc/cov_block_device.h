@@ -49,9 +49,28 @@ __device__ __forceinline__ void cov_prior_block(const double* val, const double*
         }
 }
 
+// the same with the prior's full information matrix W (6x6 row-major, symmetric: loc_window_set_prior_information) in the place of val's
+// diagonal — window_kernel.hip: evaluate_edges<.., PINFO>; the record's layout is the same
+__device__ __forceinline__ void cov_prior_block_full(const double* val, const double* W, const double* X, double* rec) {
+    double RE[9], q[4];
+    mat_mul(val, X, RE);
+    mat_to_quat(RE, q);
+    quat_normalize_sign(q);
+    double J[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) J[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
+    quat_right_jac(q, 1.0, J, 6);
+    prior_full_hessian(J, W, rec);
+}
+
 // one range edge (no lever arm on endpoint 1): rho' info, J0 (D columns of the pose carrying the lever arm), J1 (D columns of the other pose)
+// err_out: where the marginal-prior pass wants the edge's error as well (the covariance passes pass none)
 template <int D, int JAC>
-__device__ __forceinline__ void cov_range_rec(const double* X0, const double* X1, const double* p1, bool pose1, const double* val, double* rec) {
+__device__ __forceinline__ void cov_range_rec(const double* X0, const double* X1, const double* p1, bool pose1, const double* val, double* rec, double* err_out = nullptr) {
     const double meas = val[0], info = val[1];
     const double off[3] = {val[2], val[3], val[4]};
     double J0[6] = {0, 0, 0, 0, 0, 0}, J1[6] = {0, 0, 0, 0, 0, 0};
@@ -93,13 +112,14 @@ __device__ __forceinline__ void cov_range_rec(const double* X0, const double* X1
     }
     const double chi = err * (info * err);
     rec[0] = (1.0 / (1.0 + chi)) * info;   // rho' Omega
+    if (err_out) *err_out = err;
 #pragma unroll
     for (int k = 0; k < D; ++k) { rec[1 + k] = J0[k]; rec[1 + D + k] = J1[k]; }
 }
 
 // one range edge (v0, v1) of a window with poses P: endpoint 1 is pose v1, or the fixed anchor -1 - v1 (identity rotation); the record of cov_range_rec
 template <int D, int JAC>
-__device__ __forceinline__ void cov_range_edge(const double* P, const double* anchors, int v0, int v1, const double* val, double* rec) {
+__device__ __forceinline__ void cov_range_edge(const double* P, const double* anchors, int v0, int v1, const double* val, double* rec, double* err_out = nullptr) {
     double X0[12], X1[12], p1[3];
 #pragma unroll
     for (int k = 0; k < 12; ++k) X0[k] = P[v0 * 12 + k];
@@ -108,7 +128,7 @@ __device__ __forceinline__ void cov_range_edge(const double* P, const double* an
     for (int k = 0; k < 12; ++k) X1[k] = P[v1c * 12 + k];
     if (v1 >= 0) { p1[0] = X1[9]; p1[1] = X1[10]; p1[2] = X1[11]; }
     else { const double* an = anchors + (size_t)(-1 - v1) * 3; p1[0] = an[0]; p1[1] = an[1]; p1[2] = an[2]; }
-    cov_range_rec<D, JAC>(X0, X1, p1, v1 >= 0, val, rec);
+    cov_range_rec<D, JAC>(X0, X1, p1, v1 >= 0, val, rec, err_out);
 }
 
 // excluded coordinates of pose `v`'s assembled diagonal block: a diagonal entry exactly 0 (its row and column are 0 as well) is taken as

@@ -89,7 +89,9 @@ __device__ __forceinline__ int env_column_rows(int j, const int* first, const in
     return m;
 }
 
-template <int JAC, bool JOINT>
+// PINFO: the priors' information matrices are the full rows of a.p_info (loc_window_set_prior_information) — a twin of every variant, so that
+// the pass of every other handle is the machine code it was
+template <int JAC, bool JOINT, bool PINFO>
 __global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(const WindowArgs a, double* ws, size_t ws_stride, int blocks_cap, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int D = 6, DD = 36, RS = 13, S = kEvSlots;
     const int tid = threadIdx.x;
@@ -186,7 +188,8 @@ __global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(cons
             const int e = e0 + tid;
             if (tid < kEvPriorChunk && e < np) {
                 const int v = a.p_idx[(size_t)inst * cp.np_max + e];
-                cov_prior_block(a.p_val + ((size_t)inst * cp.np_max + e) * 18, P + v * 12, rec + tid * 21);
+                if (PINFO) cov_prior_block_full(a.p_val + ((size_t)inst * cp.np_max + e) * 18, a.p_info + ((size_t)inst * cp.np_max + e) * 36, P + v * 12, rec + tid * 21);
+                else cov_prior_block(a.p_val + ((size_t)inst * cp.np_max + e) * 18, P + v * 12, rec + tid * 21);
                 ei[tid] = v;
             }
             __syncthreads();
@@ -432,12 +435,17 @@ __global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(cons
     }
 }
 
+template <int JAC, bool JOINT, bool PINFO>
+hipError_t launch_env_cov_p(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<&envelope_covariance_kernel<JAC, JOINT, PINFO>>(160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((envelope_covariance_kernel<JAC, JOINT, PINFO>), dim3((unsigned)a.B), dim3(kEvThreads), lds, stream, a, ws, ws_stride, blocks, cov, mask, status, pp);
+    return hipGetLastError();
+}
 template <int JAC, bool JOINT>
 hipError_t launch_env_cov_j(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&envelope_covariance_kernel<JAC, JOINT>>(160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((envelope_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(kEvThreads), lds, stream, a, ws, ws_stride, blocks, cov, mask, status, pp);
-    return hipGetLastError();
+    return a.p_info ? launch_env_cov_p<JAC, JOINT, true>(a, ws, ws_stride, blocks, lds, cov, mask, status, pp, stream)
+                    : launch_env_cov_p<JAC, JOINT, false>(a, ws, ws_stride, blocks, lds, cov, mask, status, pp, stream);
 }
 template <int JAC>
 hipError_t launch_env_cov_t(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {

@@ -245,6 +245,30 @@ __device__ __forceinline__ double range_jac_numeric_t(const double* p0, const do
 }
 #pragma clang fp contract(fast)
 
+// J^T W J of an EdgeSE3Prior with a FULL information matrix W (6x6 row-major, symmetric: loc_window_set_prior_information), lower triangle
+// (21 entries, k = r (r + 1) / 2 + c).  J (6x6 row-major) = blockdiag(R_E, Q): J[i][r] is non-zero inside r's 3-block only, so entry (r, c)
+// sums J[i][r] W[i][k] J[k][c] over i in r's block and k in c's.  The one statement of that product: window_kernel.hip's
+// evaluate_edges<.., PINFO> and cov_block_device.h's cov_prior_block_full both call it.
+__device__ __forceinline__ void prior_full_hessian(const double* J, const double* W, double* rec) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        const int i0 = r < 3 ? 0 : 3;
+#pragma unroll
+        for (int cc = 0; cc <= r; ++cc) {
+            const int k0 = cc < 3 ? 0 : 3;
+            double h = 0.0;
+#pragma unroll
+            for (int i = i0; i < i0 + 3; ++i) {
+                double wj = 0.0;
+#pragma unroll
+                for (int k = k0; k < k0 + 3; ++k) wj += W[i * 6 + k] * J[k * 6 + cc];
+                h += J[i * 6 + r] * wj;
+            }
+            rec[r * (r + 1) / 2 + cc] = h;
+        }
+    }
+}
+
 // 1/sqrt(d) for a pivot d > 0: hardware seed (~2^-24) + one third-order step y (1 + e/2 + 3 e^2/8), e = 1 - d y^2: the error
 // term e^3 is far below an ulp; four dependent operations after the seed (the Goldschmidt pair + Newton used elsewhere: eight)
 __device__ __forceinline__ double pivot_rsqrt(double d) {

@@ -5,6 +5,10 @@
 
 namespace locamd {
 
+// what only the general kernel evaluates: lever arms on endpoint 1, full information matrices on the priors.  One flag of the structure
+// hash and of build_tree_sched: no cached verdict and no forest schedule survives a change of it.
+static bool general_only(const DispatchOpts& o) { return o.has_off1 || o.has_pinfo; }
+
 // Large batches of CHAIN windows (every pose-to-pose edge — range or SE3 — joins consecutive poses; edges ordered by their
 // later pose and priors by pose — the order Localization::addRangeEdge / addImuEdge create them in) run one lane per window
 // (chain_lm_kernel; chain3_lm_kernel when the batch is translation-only).  Below the threshold a wave per window is faster (the
@@ -32,7 +36,7 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
     unsigned long long key = 0;
     bool hit = false;
     if (use_cache) {
-        key = hash_structure(c, o.has_off1, b);
+        key = hash_structure(c, general_only(o), b);
         hit = tc->valid && tc->key == key && tc->n == b.n;
     }
     bool chain = true;
@@ -57,7 +61,7 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
         if (hit && tc->tree_tried) {
             if (tc->tree_ok) return {LOC_WINDOW_KERNEL_TREE, hit};   // (aux's schedule is still the one built for this structure)
         } else {
-            const bool ok = build_tree_sched(c, o.has_off1, b, aux);
+            const bool ok = build_tree_sched(c, general_only(o), b, aux);
             if (use_cache) { tc->tree_tried = true; tc->tree_ok = ok; }
             if (ok) return {LOC_WINDOW_KERNEL_TREE, hit};
         }
@@ -68,7 +72,7 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
 int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology) {
     const long long mn = effective_chain_min(o);
     const bool default_rule = o.chain_min < 0 && !o.env_chain_min_set;
-    if (o.has_off1) return LOC_WINDOW_KERNEL_GENERAL;   // (lever arms on endpoint 1: only the general kernel evaluates them)
+    if (general_only(o)) return LOC_WINDOW_KERNEL_GENERAL;   // (lever arms on endpoint 1, full-information priors: only the general kernel evaluates them)
     if (mn <= 0 || o.natural_order) return LOC_WINDOW_KERNEL_GENERAL;   // threshold 0 = "never anything but the general kernel" (every structure)
     if (topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) {   // (WAVE6S: the same rule for chains with EdgeSE3 factors)
         // a 6-DoF chain batch that also qualifies for wave6_lm_kernel (one wave per window, rank-1 couplings).  Measured on twelve-pose
@@ -112,7 +116,7 @@ int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int top
 static CovVerdict structured_covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b,
                                              WinAux& own, SchedKey* keyed) {
     const CovVerdict none{CovKind::None, false, 0, 0};
-    if (o.has_off1) return none;
+    if (general_only(o)) return none;   // (full-information priors: the three passes below read the diagonals alone — the envelope pass serves them)
     const bool small = c.nv_max <= 64;
     if (small) {
         bool chain = false, single_pairs = false, se3_pairs = false;
@@ -127,18 +131,18 @@ static CovVerdict structured_covariance_kind(const WindowCaps& c, const Dispatch
     if (!small) return none;
     if (o.tree == 0 || b.n < tree_min_batch(o)) return none;
     if (keyed) {
-        const unsigned long long key = hash_structure(c, o.has_off1, b);
+        const unsigned long long key = hash_structure(c, general_only(o), b);
         if (keyed->valid && keyed->key == key && keyed->n == b.n) return {CovKind::ForestOwn, false, 0, 0};
         keyed->valid = false;   // (valid again once the caller has uploaded the new tables)
         keyed->key = key; keyed->n = b.n;
     }
-    if (!build_tree_sched(c, o.has_off1, b, own)) return none;
+    if (!build_tree_sched(c, general_only(o), b, own)) return none;
     return {CovKind::ForestOwn, true, 0, 0};
 }
 
 long long cov_switches(const DispatchOpts& o) {
     const long long mn = tree_min_batch(o);
-    return ((long long)(o.arrow3 + 1) << 4 | (long long)(o.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8);
+    return (((long long)(o.arrow3 + 1) << 4 | (long long)(o.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8)) | (o.has_pinfo ? 1ll << 60 : 0);
 }
 
 // 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is Envelope —
@@ -159,7 +163,7 @@ CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const Dis
 bool cov_admitted(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind) {
     const bool forest = kind == CovKind::Forest || kind == CovKind::ForestOwn;
     const bool arrow = kind == CovKind::Arrow, envelope = kind == CovKind::Envelope;
-    const bool refused = o.has_off1 || (f.nv_max > 64 && !arrow && !envelope) || kind == CovKind::Unclassified || kind == CovKind::None ||
+    const bool refused = o.has_off1 || (o.has_pinfo && !envelope) || (f.nv_max > 64 && !arrow && !envelope) || kind == CovKind::Unclassified || kind == CovKind::None ||
                          (forest && (n < tree_min_batch(o) || o.tree == 0)) || (arrow && (!arrow3_wanted(o, f) || !f.cov_arrow)) || (envelope && !o.cov_general);
     return !refused;
 }

@@ -19,6 +19,7 @@ struct DispatchOpts {
     long long chain_min = -1;          // smallest batch that takes a lane-per-window kernel (-1: the default / LOCAMD_CHAIN_MIN_BATCH)
     bool natural_order = false;        // loc_window_set_ordering
     bool has_off1 = false;             // lever arms of endpoint 1 are set (loc_window_set_endpoint1_offsets)
+    bool has_pinfo = false;            // full information matrices of the priors are set (loc_window_set_prior_information)
 };
 
 // what depends on the handle's capacities alone: the kernels' LDS needs against their limits, taken once by loc_window_create
@@ -43,7 +44,7 @@ enum class CovKind : int {
 long long effective_chain_min(const DispatchOpts& o);
 long long tree_min_batch(const DispatchOpts& o);
 bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f);
-// the switches the three structured covariance tests read besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold)
+// the switches the three structured covariance tests read besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold, has_pinfo)
 long long cov_switches(const DispatchOpts& o);
 // the kernel a batch of n windows of that structure (batch_topology's verdict) takes NOW (threshold, ordering override, the options)
 int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology);

@@ -50,6 +50,7 @@ struct WindowArgs {
     const int32_t* r_idx; const double* r_val;
     const double* r_off1;   // optional [B][nr_max][3]: lever arm of endpoint 1 (types_edge_se3range.h:73 offset[1]); nullptr = none (general kernel only)
     const int32_t* p_idx; const double* p_val;
+    const double* p_info;   // optional [B][np_max][36]: full information matrix of every prior, row-major, in the place of p_val's diagonal; nullptr = none (general kernel, envelope covariance pass, marginal prior pass)
     const int32_t* s_idx; const double* s_val;
     const double* anchors;  // [n_anchors][3] fixed vertices (identity rotation), shared by all instances
     double* result;
@@ -156,6 +157,12 @@ hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int c
 size_t window_envelope_covariance_lds_bytes(const WindowCaps& c);
 size_t window_envelope_covariance_workspace_doubles(const WindowCaps& c, long long blocks);
 hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream);
+
+// the marginal prior a dropped pose leaves on its one neighbour, translation-only windows (marginal_prior_kernel.hip): one wave
+// per window at a.poses; drop [B] (checked on the host: window_structure.cpp, check_marginal_drop), slot [B], prior [B][48], grad / shift
+// [B][6], rank / status [B] (device arrays)
+hipError_t launch_window_marginal_prior(const WindowArgs& a, const int32_t* drop, int32_t* slot, double* prior, double* grad, double* shift, int32_t* rank, int32_t* status,
+                                        hipStream_t stream);
 
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);

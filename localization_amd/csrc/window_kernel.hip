@@ -143,7 +143,9 @@ __device__ __forceinline__ int blk_off(const Lds& L, int i, int K);
 // Evaluate every edge at the current poses: errors + chi sums always, Jacobian/weight records when FULL.
 // (FULL: the caller has zeroed H; an SE3 edge that is alone on its pair of poses — s_idx[4 e + 3] == 0, set once per solve —
 //  writes its off-diagonal block straight into H, the others leave it in their record for the ordered accumulation.)
-template <bool FULL, int JAC, bool SP, int NW>
+// PINFO: the priors' information matrices are the full 6x6 rows of a.p_info (loc_window_set_prior_information), read in place by the
+// prior's index e — the order the minimum-degree labels never touch — instead of the six diagonal entries of p_val.
+template <bool FULL, int JAC, bool SP, int NW, bool PINFO>
 __device__ __forceinline__ void evaluate_edges(const WindowArgs& a, const Lds& L, int inst, int lane, int nr, int np, int ns,
                                double& robust_chi, double& plain_chi) {
     (void)inst;
@@ -238,11 +240,46 @@ __device__ __forceinline__ void evaluate_edges(const WindowArgs& a, const Lds& L
         quat_normalize_sign(q);
         const double err[6] = {tE[0], tE[1], tE[2], q[1], q[2], q[3]};
         double chi = 0.0;
+        const double* Wf = PINFO ? a.p_info + ((size_t)inst * a.caps.np_max + e) * 36 : nullptr;
+        double We[6];   // PINFO: W e
+        if (PINFO) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) chi += err[i] * (val[12 + i] * err[i]);
+            for (int i = 0; i < 6; ++i) {
+                double r = 0.0;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) r += Wf[i * 6 + j] * err[j];
+                We[i] = r;
+                chi += err[i] * r;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) chi += err[i] * (val[12 + i] * err[i]);
+        }
         rsum += chi;  // not robust
         csum += chi;
-        if (FULL) {
+        if (FULL && PINFO) {
+            double* rec = L.prec + e * PREC;
+            double J[36];
+#pragma unroll
+            for (int i = 0; i < 36; ++i) J[i] = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
+            quat_right_jac(q, 1.0, J, 6);
+            // J = blockdiag(RE, Q) as below, W full (window_device.h: prior_full_hessian, shared with the envelope covariance pass); the
+            // record keeps the same 21 + 6 entries, so nothing after it knows the difference
+            prior_full_hessian(J, Wf, rec);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                const int i0 = r < 3 ? 0 : 3;
+                double bb = 0.0;
+#pragma unroll
+                for (int i = i0; i < i0 + 3; ++i) bb += J[i * 6 + r] * (-We[i]);
+                rec[21 + r] = bb;
+            }
+        }
+        if (FULL && !PINFO) {
             double* rec = L.prec + e * PREC;
             double J[36];
 #pragma unroll
@@ -2515,7 +2552,7 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
 // JAC: range-edge Jacobians analytic (0) or g2o's central differences (1).  SP: SPARSE path (nv_max <= 64) or SKYLINE.
 // (launch bounds: at least two waves per SIMD, i.e. at most 256 registers — a few rarely used values spill to scratch, which
 //  costs far less than the halved occupancy a 257th register would)
-template <bool GLOBAL_A, int JAC, bool SP, int W, int NW>
+template <bool GLOBAL_A, int JAC, bool SP, int W, int NW, bool PINFO>
 // (experiment kept as a switch: forcing 3 or 4 waves per SIMD for the workspace-mode SPARSE kernel — 168 / 128 registers, 204 /
 //  484 values spilled to scratch — made BASELINE config 5 slower, 19.7 -> 26.0 / 33.1 ms per 16 384 windows: the extra waves do
 //  not pay for the spill traffic)
@@ -2702,7 +2739,7 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
         //  BASELINE config 5 moved.)
         {
             LOCAMD_TIC();
-            evaluate_edges<true, JAC, SP, NW>(a, L, inst, lane, nr, np, ns, cur_chi, plain);  // computeActiveErrors + linearize
+            evaluate_edges<true, JAC, SP, NW, PINFO>(a, L, inst, lane, nr, np, ns, cur_chi, plain);  // computeActiveErrors + linearize
             last_plain = plain;
             __syncthreads();
             LOCAMD_TOC(1);
@@ -2756,7 +2793,7 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
             __syncthreads();
             ++trials;
             double temp_chi, plain2;
-            evaluate_edges<false, JAC, SP, NW>(a, L, inst, lane, nr, np, ns, temp_chi, plain2);
+            evaluate_edges<false, JAC, SP, NW, PINFO>(a, L, inst, lane, nr, np, ns, temp_chi, plain2);
             LOCAMD_TOC(6);
             last_plain = plain2;
             if (!ok2) temp_chi = DBL_MAX;
@@ -2808,15 +2845,18 @@ size_t window_workspace_doubles(const WindowCaps& c) { return window_instance_do
 constexpr int WIDE_WAVES = 8;   // waves per window of 65 .. 512 poses (two per SIMD)
 constexpr size_t WIDE_STATIC_LDS = 4096;   // >= the static LDS of the several-waves kernel (reduction scratch: 2.4 KB)
 
-template <bool GLOBAL_A, int JAC, bool SP, int W, int NW = 1>
+template <bool PINFO, bool GLOBAL_A, int JAC, bool SP, int W, int NW = 1>
 static hipError_t launch_window_t(const WindowArgs& a, size_t lds, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&window_lm_kernel<GLOBAL_A, JAC, SP, W, NW>>(160 * 1024 - (NW > 1 ? WIDE_STATIC_LDS : 512));  // static LDS on top
+    const hipError_t e = allow_dynamic_lds<&window_lm_kernel<GLOBAL_A, JAC, SP, W, NW, PINFO>>(160 * 1024 - (NW > 1 ? WIDE_STATIC_LDS : 512));  // static LDS on top
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((window_lm_kernel<GLOBAL_A, JAC, SP, W, NW>), dim3((unsigned)a.B), dim3(64 * NW), lds, stream, a);
+    hipLaunchKernelGGL((window_lm_kernel<GLOBAL_A, JAC, SP, W, NW, PINFO>), dim3((unsigned)a.B), dim3(64 * NW), lds, stream, a);
     return hipGetLastError();
 }
 
-hipError_t launch_window(const WindowArgs& a, hipStream_t stream) {
+// PINFO: the twin of every variant for handles with full-information priors (a.p_info) — a template twin, not a run-time branch, so that
+// the kernels of every other handle are the machine code they were
+template <bool PINFO>
+static hipError_t launch_window_p(const WindowArgs& a, hipStream_t stream) {
     if (a.B <= 0 || a.caps.bw_max < 0 || a.caps.bw_max >= a.caps.nv_max + (a.caps.nv_max == 1)) return hipErrorInvalidValue;
     const bool global_a = a.workspace != nullptr;
     const size_t lds = window_lds_bytes(a.caps, global_a);
@@ -2827,20 +2867,24 @@ hipError_t launch_window(const WindowArgs& a, hipStream_t stream) {
         // Their structure tables fill a CU's LDS, so one such window runs per CU: it gets the CU's four SIMDs (WIDE_WAVES
         // waves); LOCAMD_WINDOW_WAVES=1 in the environment keeps the one-wave kernel (for comparison).
         static const bool one_wave = [] { const char* v = getenv("LOCAMD_WINDOW_WAVES"); return v && v[0] == '1' && v[1] == 0; }();
-        if (one_wave || lds > 160 * 1024 - WIDE_STATIC_LDS) return a.jacobian ? launch_window_t<true, 1, true, 8>(a, lds, stream) : launch_window_t<true, 0, true, 8>(a, lds, stream);
-        return a.jacobian ? launch_window_t<true, 1, true, 8, WIDE_WAVES>(a, lds, stream) : launch_window_t<true, 0, true, 8, WIDE_WAVES>(a, lds, stream);
+        if (one_wave || lds > 160 * 1024 - WIDE_STATIC_LDS) return a.jacobian ? launch_window_t<PINFO, true, 1, true, 8>(a, lds, stream) : launch_window_t<PINFO, true, 0, true, 8>(a, lds, stream);
+        return a.jacobian ? launch_window_t<PINFO, true, 1, true, 8, WIDE_WAVES>(a, lds, stream) : launch_window_t<PINFO, true, 0, true, 8, WIDE_WAVES>(a, lds, stream);
     }
     const int sel = (global_a ? 4 : 0) | (a.jacobian ? 2 : 0) | (sp ? 1 : 0);
     switch (sel) {
-        case 0: return launch_window_t<false, 0, false, 1>(a, lds, stream);
-        case 1: return launch_window_t<false, 0, true, 1>(a, lds, stream);
-        case 2: return launch_window_t<false, 1, false, 1>(a, lds, stream);
-        case 3: return launch_window_t<false, 1, true, 1>(a, lds, stream);
-        case 4: return launch_window_t<true, 0, false, 1>(a, lds, stream);
-        case 5: return launch_window_t<true, 0, true, 1>(a, lds, stream);
-        case 6: return launch_window_t<true, 1, false, 1>(a, lds, stream);
-        default: return launch_window_t<true, 1, true, 1>(a, lds, stream);
+        case 0: return launch_window_t<PINFO, false, 0, false, 1>(a, lds, stream);
+        case 1: return launch_window_t<PINFO, false, 0, true, 1>(a, lds, stream);
+        case 2: return launch_window_t<PINFO, false, 1, false, 1>(a, lds, stream);
+        case 3: return launch_window_t<PINFO, false, 1, true, 1>(a, lds, stream);
+        case 4: return launch_window_t<PINFO, true, 0, false, 1>(a, lds, stream);
+        case 5: return launch_window_t<PINFO, true, 0, true, 1>(a, lds, stream);
+        case 6: return launch_window_t<PINFO, true, 1, false, 1>(a, lds, stream);
+        default: return launch_window_t<PINFO, true, 1, true, 1>(a, lds, stream);
     }
+}
+
+hipError_t launch_window(const WindowArgs& a, hipStream_t stream) {
+    return a.p_info ? launch_window_p<true>(a, stream) : launch_window_p<false>(a, stream);
 }
 
 

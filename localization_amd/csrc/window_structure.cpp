@@ -75,7 +75,7 @@ int check_pairs(int64_t n, const int32_t* counts, const PairTables& pt) {
 
 // translation-only (the exact 3-DoF reduction, chain3_kernel.hip / arrow3_kernel.hip): no EdgeSE3, every lever arm zero, every
 // rotation the identity, priors with an identity measurement rotation and no rotation information
-bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b) {
+bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b, bool skip_prior_diagonal) {
     static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     if (n_anchors > 500000) return false;   // (the packed endpoint word of chain3 holds 2^19 anchors)
     std::atomic<bool> all{true};
@@ -91,7 +91,7 @@ bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b) {
                 if (std::memcmp(b.poses + ((size_t)i * c.nv_max + p) * 12, I9, sizeof(I9)) != 0) return false;
             for (int e = 0; e < cn[2]; ++e) {
                 const double* v = b.p_val + ((size_t)i * c.np_max + e) * 18;
-                if (std::memcmp(v, I9, sizeof(I9)) != 0 || v[15] != 0.0 || v[16] != 0.0 || v[17] != 0.0) return false;
+                if (std::memcmp(v, I9, sizeof(I9)) != 0 || (!skip_prior_diagonal && (v[15] != 0.0 || v[16] != 0.0 || v[17] != 0.0))) return false;
             }
             return true;
         };
@@ -99,6 +99,46 @@ bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b) {
             if (!one(i)) { all.store(false); return; }
     });
     return all.load();
+}
+
+bool prior_information_translation_only(size_t n_rows, const double* pinfo) {
+    for (size_t e = 0; e < n_rows; ++e) {
+        const double* W = pinfo + e * 36;
+        for (int i = 0; i < 6; ++i)
+            for (int j = (i < 3 ? 3 : 0); j < 6; ++j)
+                if (W[i * 6 + j] != 0.0) return false;
+    }
+    return true;
+}
+
+// Host-side check of the drop slots of a marginal-prior call: the kernel indexes the pose table with them, and takes the one neighbour it finds
+int check_marginal_drop(const WindowCaps& c, const HostBatch& b, const int32_t* drop) {
+    for (int64_t i = 0; i < b.n; ++i)   // (every slot first: an invalid call is invalid whatever else is wrong with it)
+        if (drop[i] < 0 || drop[i] >= b.counts[i * 4]) return 1;
+    std::atomic<int> first_bad{0};
+    parallel_chunks(b.n, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t i = lo; i < hi && first_bad.load(std::memory_order_relaxed) == 0; ++i) {
+            const int32_t* cn = b.counts + i * 4;
+            const int32_t d = drop[i];
+            int bad = 0, m = -1;
+            for (int e = 0; e < cn[1] && !bad; ++e) {
+                const int32_t* ix = b.r_idx + ((size_t)i * c.nr_max + e) * 2;
+                if (ix[1] < 0 || (ix[0] != d && ix[1] != d)) continue;
+                const int other = ix[0] == d ? ix[1] : ix[0];
+                if (m >= 0 && other != m) bad = 2;
+                m = other;
+            }
+            for (int e = 0; e < cn[3] && !bad; ++e) {   // (a translation-only batch has none: the caller's scan comes first; counted all the same)
+                const int32_t* ix = b.s_idx + ((size_t)i * c.ns_max + e) * 4;
+                if (ix[0] != d && ix[1] != d) continue;
+                const int other = ix[0] == d ? ix[1] : ix[0];
+                if (m >= 0 && other != m) bad = 2;
+                m = other;
+            }
+            if (bad) { int zero = 0; first_bad.compare_exchange_strong(zero, bad); return; }
+        }
+    });
+    return first_bad.load();
 }
 
 // The chain scan: every pose-to-pose edge (range or SE3) of every window joins consecutive pose slots.  ordered: edges are also listed

@@ -26,7 +26,15 @@ struct WinAux {
 // 0, or the first check that failed: 1 counts exceed the capacities, 2 / 3 range edge (vertex index / poses further apart than bw_max),
 // 4 prior edge vertex index, 5 / 6 SE3 edge (as 2 / 3)
 int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b);
-bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b);
+// skip_prior_diagonal: the priors' information comes from a full-matrix table (loc_window_set_prior_information), p_val's diagonal is not read
+bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b, bool skip_prior_diagonal = false);
+// the full information matrices of n_rows priors ([n_rows][36]) carry no rotation information: rows and columns 3 .. 5 exactly 0
+bool prior_information_translation_only(size_t n_rows, const double* pinfo);
+// the drop slots of a marginal-prior call (loc_window_marginal_prior_host), drop [n]; the batch's tables are already checked
+// (check_instances).  0, or the first check that failed: 1 a drop slot outside [0, nv) of its window; 2 pose-to-pose ranges join some
+// window's dropped pose to more than one other pose (a marginal over several poses is not a unary prior: arrowheads are such windows) —
+// several ranges to the same pose, in either direction, are one neighbour
+int check_marginal_drop(const WindowCaps& c, const HostBatch& b, const int32_t* drop);
 void chain_scan(const WindowCaps& c, const HostBatch& b, bool ordered, bool& chain, bool& single_pairs, bool& se3_pairs);
 unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const HostBatch& b);
 // the largest number of envelope blocks any instance has (envelope_covariance_kernel.hip's profile: sum over the pose slots i of

@@ -28,11 +28,12 @@ struct HostBatch {
 // where a kernel finds the tables: eight base pointers the device can read (device arrays, or the page-locked staging block)
 struct DeviceTables { void* t[kWindowTables]; };
 
-// One block for n instances: up to six prefix pieces, then the tables from first_table on in WindowTable order, every piece 16-byte
+// One block for n instances: up to eight prefix pieces, then the tables from first_table on in WindowTable order, every piece 16-byte
 // aligned; offsets of the pieces and the block's size.  The covariance pass has [cov | mask | status] in front of all eight tables, a joint
-// call [cov | mask | status | cross | pair counts | pairs] (four outputs, then its two input tables).  The solve's prefix is
+// call [cov | mask | status | cross | pair counts | pairs] (four outputs, then its two input tables); the marginal-prior pass
+// [slot | prior | grad | shift | rank | status | drop] (six outputs, one input table).  The solve's prefix is
 // [poses | result], which come back as one copy, in front of the tables from kCounts on: tab[kPoses] = pre[0] = 0.
-struct BlockLayout { size_t pre[6], tab[kWindowTables], end; };
+struct BlockLayout { size_t pre[8], tab[kWindowTables], end; };
 inline BlockLayout pack_block(const WindowCaps& c, size_t n, const size_t* prefix_bytes, int n_prefix, int first_table) {
     auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
     BlockLayout L{};

@@ -33,6 +33,7 @@ class WindowBatch:
         self.s_val = np.zeros((self.B, max(ns_max, 1), 48))
         self.result = np.zeros((self.B, 8))
         self.r_off1 = None   # optional lever arms of endpoint 1, [B][nr_max][3] (loc_window_set_endpoint1_offsets); created by add_range(off1=...)
+        self.p_info = None   # optional full information matrices of the priors, [B][np_max][36] (loc_window_set_prior_information); created by add_prior(info=...)
 
     def add_pose(self, i, t, R=None):
         v = int(self.counts[i, 0])
@@ -53,12 +54,22 @@ class WindowBatch:
             self.r_off1[i, e] = off1
         self.counts[i, 1] = e + 1
 
-    def add_prior(self, i, v, t, R, info_diag):
+    def add_prior(self, i, v, t, R, info_diag=None, info=None):
+        """info_diag: the six diagonal entries; or info: the full symmetric 6x6 (the batch then carries p_info, in which every prior has a
+        row: the priors added with info_diag get diag(info_diag))"""
         e = int(self.counts[i, 2])
-        assert e < self.caps[2]
+        assert e < self.caps[2] and (info_diag is None) != (info is None)
         Ri, ti = _inv_iso(np.asarray(R, dtype=float), np.asarray(t, dtype=float))
         self.p_idx[i, e] = v
+        if info is not None:
+            info = np.asarray(info, dtype=float).reshape(6, 6)
+            info_diag = np.diag(info)
+            if self.p_info is None:   # the priors so far: their diagonals
+                self.p_info = np.zeros((self.B, max(self.caps[2], 1), 36))
+                self.p_info[:, :, ::7] = self.p_val[:, :, 12:]
         self.p_val[i, e, :9] = Ri.reshape(9); self.p_val[i, e, 9:12] = ti; self.p_val[i, e, 12:] = info_diag
+        if self.p_info is not None:
+            self.p_info[i, e] = (np.diag(np.asarray(info_diag, dtype=float)) if info is None else info).reshape(36)
         self.counts[i, 2] = e + 1
 
     def add_se3(self, i, vi, vj, t, R, info, robust=True):
@@ -138,9 +149,15 @@ class WindowSolver(_lib.Handle):
         off1 = getattr(wb, "r_off1", None)
         check(self.L.loc_window_set_endpoint1_offsets(self.h, wb.B, None if off1 is None else np.ascontiguousarray(off1).ctypes.data_as(dp)))
 
+    def _prior_information(self, wb):
+        dp = C.POINTER(C.c_double)
+        pinfo = getattr(wb, "p_info", None)
+        check(self.L.loc_window_set_prior_information(self.h, wb.B, None if pinfo is None else np.ascontiguousarray(pinfo, dtype=np.float64).ctypes.data_as(dp)))
+
     def solve(self, wb: WindowBatch):
         assert wb.caps == self.caps and wb.B <= self.B
         self._endpoint1(wb)
+        self._prior_information(wb)
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         for a in (wb.counts, wb.poses, wb.r_idx, wb.r_val, wb.p_idx, wb.p_val, wb.s_idx, wb.s_val, wb.result):
             assert a.flags["C_CONTIGUOUS"]
@@ -155,6 +172,7 @@ class WindowSolver(_lib.Handle):
     def upload(self, wb: WindowBatch):
         assert wb.caps == self.caps and wb.B <= self.B
         self._endpoint1(wb)
+        self._prior_information(wb)
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         check(self.L.loc_window_upload(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
                                        wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
@@ -177,10 +195,15 @@ class WindowSolver(_lib.Handle):
         "arrow3"; by default handles of more than 64 poses), and forest batches (one shared topology, <= 64 poses) whenever the handle
         would solve them on a forest kernel (option "tree", batch threshold); with set_option("covariance_general", 1) any other batch
         as well, on the envelope pass in the caller's pose order (covariance_plan reports its memory).  Returns (cov [B][nv_max][6][6],
-        mask [B][nv_max] — excluded coordinates, bits 0-5 = tx ty tz qx qy qz —, status [B]: 0 or LOC_ERR_SINGULAR, that window's blocks NaN)."""
+        mask [B][nv_max] — excluded coordinates, bits 0-5 = tx ty tz qx qy qz —, status [B]: 0 or LOC_ERR_SINGULAR, that window's blocks NaN).
+        The C call is stateless; THIS method first hands wb's prior table to the handle (_prior_information: wb.p_info, or none), as
+        solve() and upload() do, and so do joint_covariance() and marginal_prior().  The table belongs to the handle, not to a batch: after
+        upload(batch with p_info) a covariance(another batch without one) clears it, and the resident batch is from then on solved and
+        served with p_val's diagonals until a call with the table sets it again.  (The endpoint-1 lever arms are never touched here.)"""
         assert wb.caps == self.caps and wb.B <= self.B
         if getattr(wb, "r_off1", None) is not None:   # (refused here: the handle's endpoint-1 lever arms belong to its solves and stay as they are)
             raise _lib.LocalizationAmdError(-5, "covariance: windows with endpoint-1 lever arms are not supported")
+        self._prior_information(wb)
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         if out is None:
             out = (np.zeros((wb.B, self.caps[0], 6, 6)), np.zeros((wb.B, self.caps[0]), dtype=np.int32), np.zeros(wb.B, dtype=np.int32))
@@ -193,6 +216,32 @@ class WindowSolver(_lib.Handle):
                                                 wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp),
                                                 cov.ctypes.data_as(dp), mask.ctypes.data_as(ip), status.ctypes.data_as(ip)))
         return cov, mask, status
+
+    # ---- the marginal prior of a dropped pose (loc_window_marginal_prior_host)
+    def marginal_prior(self, wb: WindowBatch, drop, out=None):
+        """What dropping pose drop[b] of every (translation-only) window leaves on its one neighbour, at wb.poses: returns (slot [B] — the
+        neighbour, -1: none —, prior [B][48] — Z^-1 as R(9), t(3) and the 6x6 information: add_prior's row —, grad [B][6], shift [B][6],
+        rank [B], status [B]: 0 or LOC_ERR_SINGULAR, then a zero-information row = the plain drop).  drop: int [B], or one slot for all."""
+        assert wb.caps == self.caps and wb.B <= self.B
+        if getattr(wb, "r_off1", None) is not None:
+            raise _lib.LocalizationAmdError(-5, "marginal_prior: windows with endpoint-1 lever arms are not supported")
+        self._prior_information(wb)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        drop = np.ascontiguousarray(np.broadcast_to(np.asarray(drop, dtype=np.int32), (wb.B,)))
+        if out is None:
+            out = (np.zeros(wb.B, dtype=np.int32), np.zeros((wb.B, 48)), np.zeros((wb.B, 6)), np.zeros((wb.B, 6)), np.zeros(wb.B, dtype=np.int32),
+                   np.zeros(wb.B, dtype=np.int32))
+        slot, prior, grad, shift, rank, status = out   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
+        for x, dt, size in ((slot, np.int32, wb.B), (prior, np.float64, wb.B * 48), (grad, np.float64, wb.B * 6), (shift, np.float64, wb.B * 6),
+                            (rank, np.int32, wb.B), (status, np.int32, wb.B)):
+            assert x.dtype == dt and x.size >= size and x.flags["C_CONTIGUOUS"]
+        check(self.L.loc_window_marginal_prior_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
+                                                    wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
+                                                    wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
+                                                    wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp), drop.ctypes.data_as(ip),
+                                                    slot.ctypes.data_as(ip), prior.ctypes.data_as(dp), grad.ctypes.data_as(dp), shift.ctypes.data_as(dp),
+                                                    rank.ctypes.data_as(ip), status.ctypes.data_as(ip)))
+        return slot, prior, grad, shift, rank, status
 
     def covariance_resident(self, cov, mask, status, stream=None):
         """The same for the uploaded batch at its solved poses (after solve_resident), asynchronous, into torch device tensors: cov float64
@@ -219,6 +268,7 @@ class WindowSolver(_lib.Handle):
         assert wb.caps == self.caps and wb.B <= self.B
         if getattr(wb, "r_off1", None) is not None:
             raise _lib.LocalizationAmdError(-5, "covariance: windows with endpoint-1 lever arms are not supported")
+        self._prior_information(wb)
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         npm, pc, pr = _pair_tables(wb.B, pairs, pair_counts)
         if out is None:
@@ -276,7 +326,7 @@ class WindowSolver(_lib.Handle):
     def set_option(self, name, value):
         """loc_window_set_option: the kernel-selection switches of this handle ("chain_min_batch", "arrow3", "tree", "wave3", "wave6",
         "chain3", "zero_copy", "topology_cache", "kernel_events"; "covariance_general": 1 = covariance() / covariance_resident() also serve
-        the batches the chain, arrowhead and forest passes decline, default 0)"""
+        the batches the chain, arrowhead and forest passes decline — every batch with full-information priors among them —, default 0)"""
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
 
     def last_host_timing(self):
