@@ -236,7 +236,8 @@ int loc_window_set_endpoint1_offsets(loc_window* w, int64_t n_instances, const d
  * that is not exactly symmetric (W[i][j] != W[j][i]; every row of the n_instances * np_max is looked at, unused ones included).  While a
  * table of n instances is set, a call with more than n instances is LOC_ERR_INVALID.  Priors stay non-robust: chi2 = e^T W e,
  * H += J^T W J, b -= J^T W e.  Such a handle solves on the general kernel (LOC_WINDOW_KERNEL_GENERAL), and its covariances come from the
- * envelope pass alone (option "covariance_general" = 1; LOC_ERR_UNSUPPORTED with nothing written otherwise).  The device table is
+ * envelope pass alone (option "covariance_general" = 1; LOC_ERR_UNSUPPORTED with nothing written otherwise) — unless option
+ * "prior_information_structured" is 1 and the table is translation-only (see loc_window_set_option).  The device table is
  * allocated by the first call and freed with the handle. */
 int loc_window_set_prior_information(loc_window* w, int64_t n_instances, const double* pinfo);
 /* LOC_JAC_NUMERIC_G2O (default: the reference's configuration) or LOC_JAC_ANALYTIC (opt-in fast mode) for the EdgeSE3Range
@@ -305,6 +306,17 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *                      loc_window_last_kernel_ms then reports launch-to-completion on the host clock.  The node's own handle runs with 0.
  *   "covariance_general"  0 (default) / 1: loc_window_covariance_* also serve the batches their three structured passes decline (see there);
  *                      looked at per call; a resident batch classified under one value is classified again after a change
+ *   "prior_information_structured"  0 (default) / 1: a handle whose table of full information matrices (loc_window_set_prior_information) is
+ *                      TRANSLATION-ONLY — every matrix a dense 3x3 block on the translation, rotation rows and columns exactly 0: the rows
+ *                      loc_window_marginal_prior_host returns — keeps the wave-per-window 3x3 kernels for translation-only CHAIN batches of
+ *                      <= 64 poses: the solve runs on LOC_WINDOW_KERNEL_WAVE3 wherever a handle without a table would take it (options
+ *                      "wave3" / "chain3", the chain threshold, the ordering override), and loc_window_covariance_* take the chain 3x3 pass
+ *                      without "covariance_general".  While such a table is set p_val[12..17] is not read, by the structure test either.
+ *                      Everything else on the handle — a table with a rotation entry, endpoint-1 lever arms, a batch that is no
+ *                      translation-only chain, a batch the rules hand to another kernel — goes to the general kernel and the envelope pass
+ *                      as with 0.  0: every call does what it did without the option, bit for bit.  Looked at per call; a resident batch whose
+ *                      verdict was taken under a structured table solves on the general kernel once the table has gone, has got a rotation
+ *                      entry or the option is 0 (until the next upload), and its covariance pass is classified again.
  * LOC_ERR_INVALID for an unknown name or value. */
 int loc_window_set_option(loc_window* w, const char* name, int64_t value);
 /* Host-side cost of the last loc_window_solve_host call, milliseconds: [0] argument validation, [1] structure analysis (kernel

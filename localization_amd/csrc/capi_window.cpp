@@ -57,8 +57,8 @@ struct loc_window {
     double* d_roff1 = nullptr;      // optional lever arms of endpoint 1 (loc_window_set_endpoint1_offsets: opt.has_off1), [B][nr_max][3]
     double* d_pinfo = nullptr;      // optional full information matrices of the priors (loc_window_set_prior_information: opt.has_pinfo), [B][np_max][36]
     long long n_pinfo = 0;          // instances the table describes: a call with more is refused
-    bool pinfo_translation = false; // no matrix of the table has rotation rows or columns (the marginal-prior pass's translation-only test)
     int resident_topology = 0;      // LOC_WINDOW_KERNEL_* the uploaded batch qualifies for by its structure (the batch-size threshold is applied per solve)
+    bool resident_skip = false;     // ... a verdict taken with the priors' diagonals skipped (a structured table was set): it holds while structured_pinfo(opt) does
     long long n_resident = 0;
     int resident_min_anchors = 0;   // anchors the resident batch references (loc_window_set_anchors may not shrink below it)
     bool resident_solved = false;   // a resident solve has run since the upload (loc_window_download has something to fetch)
@@ -172,6 +172,7 @@ int loc_window_create(loc_window** out, int32_t device, int64_t batch, const loc
         f.wave6 = c.nv_max <= 64 && locamd::window_wave6_lds_bytes(c) <= locamd::kWave6MaxLds;
         f.wave6_se3 = c.nv_max <= 63 && c.ns_max <= 64 && locamd::window_wave6_lds_bytes(c, true) <= locamd::kWave6MaxLds;
         f.wave3 = c.nv_max <= 64 && locamd::window_wave3_lds_bytes(c) <= 64 * 1024;
+        f.wave3_pinfo = c.nv_max <= 64 && locamd::window_wave3_lds_bytes(c, true) <= 64 * 1024;
         f.cov_chain = locamd::window_covariance_lds_bytes(c, false) <= 160 * 1024;
         f.cov_arrow = locamd::window_arrow_covariance_lds_bytes(c) <= 160 * 1024;
         f.cov_envelope = locamd::window_envelope_covariance_lds_bytes(c) <= 160 * 1024;
@@ -349,7 +350,7 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
 // the resident batch as uploaded: the initial estimates in the place of the optimised ones
 static locamd::DeviceTables uploaded_tables(const loc_window* w) { locamd::DeviceTables d = w->dev; d.t[kPoses] = w->d_poses_in; return d; }
 // the device arrays hold no resident batch any more (the resident calls return LOC_ERR_INVALID until the next loc_window_upload completes)
-static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_min_anchors = 0; }
+static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_skip = false; w->resident_min_anchors = 0; }
 
 static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const locamd::WindowArgs& a, hipStream_t st, int kind) {
     locamd::WinAux& A = S.aux;
@@ -418,6 +419,13 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
         if (rc == LOC_OK && before != o.cov_general && w->n_resident > 0 && (w->resident_cov == CovKind::None || w->resident_cov == CovKind::Envelope)) w->resident_cov = CovKind::Unclassified;
         return rc;
     }
+    if (k == "prior_information_structured") {
+        const bool before = o.pinfo_structured;
+        const int rc = flag(o.pinfo_structured);
+        // a resident batch under a table is classified again by the next covariance call: the other value takes another pass (or none)
+        if (rc == LOC_OK && before != o.pinfo_structured && w->n_resident > 0 && o.has_pinfo) w->resident_cov = CovKind::Unclassified;
+        return rc;
+    }
     if (k == "topology_cache") { w->topo_cache.valid = false; return flag(o.topology_cache); }
     return locamd_fail(LOC_ERR_INVALID, "set_option: unknown option name");
 }
@@ -446,7 +454,10 @@ int loc_window_set_endpoint1_offsets(loc_window* w, int64_t n, const double* off
 
 int loc_window_set_prior_information(loc_window* w, int64_t n, const double* pinfo) {
     if (!w) return locamd_fail(LOC_ERR_INVALID, "set_prior_information");
-    if (!pinfo) { w->opt.has_pinfo = false; w->n_pinfo = 0; return LOC_OK; }   // (has_pinfo is part of the structure hash, as has_off1 is)
+    // (option "prior_information_structured": the resident batch's covariance verdict may rest on the table that goes or changes here — the
+    //  next covariance call classifies the batch again; its solve verdict is checked per solve, loc_window_solve_resident)
+    if (w->opt.pinfo_structured && w->n_resident > 0) w->resident_cov = CovKind::Unclassified;
+    if (!pinfo) { w->opt.has_pinfo = false; w->opt.pinfo_translation = false; w->n_pinfo = 0; return LOC_OK; }   // (has_pinfo is part of the structure hash, as has_off1 is)
     if (n <= 0 || n > w->B) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: n_instances");
     if (w->caps.np_max <= 0) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: no prior edges in this solver");
     // everything is checked before anything changes: a matrix that is not exactly symmetric (a NaN entry included) leaves the handle as it was
@@ -465,7 +476,7 @@ int loc_window_set_prior_information(loc_window* w, int64_t n, const double* pin
     LOC_HIP(hipMemcpy(w->d_pinfo, pinfo, (size_t)n * row, hipMemcpyHostToDevice));
     w->opt.has_pinfo = true;
     w->n_pinfo = n;
-    w->pinfo_translation = locamd::prior_information_translation_only(rows, pinfo);
+    w->opt.pinfo_translation = locamd::prior_information_translation_only(rows, pinfo);
     return LOC_OK;
 }
 
@@ -607,6 +618,7 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     w->resident_min_anchors = max_anchor;
     w->res_counts.assign(counts, counts + (size_t)n * 4);
     w->resident_topology = topology;
+    w->resident_skip = locamd::structured_pinfo(w->opt);
     // the pass of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
     // classified by the first loc_window_covariance_resident call (an upload costs nothing more for callers that never ask)
     if (topology == LOC_WINDOW_KERNEL_CHAIN3) w->resident_cov = CovKind::Chain3;
@@ -635,7 +647,11 @@ int loc_window_solve_resident(loc_window* w, void* hip_stream) {
     LOC_HIP(w->timer.start(st));
     // (the batch-size threshold and the ordering override are looked at per solve: loc_window_set_chain_threshold /
     //  loc_window_set_ordering after the upload take effect)
-    hipError_t e = launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->n_resident, w->resident_topology));
+    // (a verdict taken with the priors' diagonals skipped is worth nothing once the structured table has gone, has got rotation entries or the
+    //  option is off — the diagonals in p_val count again and may hold rotation information: such a batch takes the general kernel until the
+    //  next upload, never wave3_lm_kernel)
+    const int topology = w->resident_skip && !locamd::structured_pinfo(w->opt) ? (int)LOC_WINDOW_KERNEL_GENERAL : w->resident_topology;
+    hipError_t e = launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->n_resident, topology));
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
     LOC_HIP(w->timer.stop(st));
     LOC_HIP(hipEventRecord(w->resident_done, st));
@@ -780,7 +796,7 @@ int loc_window_marginal_prior_host(loc_window* w, int64_t n, const int32_t* coun
     const int bad = locamd::check_marginal_drop(c, b, drop);
     if (bad == 1) return locamd_fail(LOC_ERR_INVALID, "marginal prior: a drop slot outside its window");
     if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: no endpoint-1 lever arms");
-    if (!locamd::translation_only(c, w->n_anchors, b, w->opt.has_pinfo) || (w->opt.has_pinfo && !w->pinfo_translation))
+    if (!locamd::translation_only(c, w->n_anchors, b, w->opt.has_pinfo) || (w->opt.has_pinfo && !w->opt.pinfo_translation))
         return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: translation-only batches alone (no EdgeSE3, identity rotations, zero lever arms, priors without rotation information)");
     if (bad == 2) return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: pose-to-pose edges join a dropped pose to more than one other pose");
     LOC_HIP(hipSetDevice(w->device));

@@ -67,6 +67,29 @@ __device__ __forceinline__ void cov_prior_block_full(const double* val, const do
     prior_full_hessian(J, W, rec);
 }
 
+// the chain 3 x 3 pass under a structured table (covariance_kernel<3, .., true>): the prior's R_E^T W R_E with the dense 3 x 3 block W of
+// its table row (prior3_load / prior3_mul_add: window_device.h, shared with wave3_lm_kernel<JAC, true>), lower triangle into rec[0 .. 5] —
+// cov_prior_block's layout for r, c < 3.  (R_E is the identity in a translation-only batch: the block is W itself, as the diagonal
+// form's is diag(W).)
+__device__ __forceinline__ void cov_prior_block3(const double* val, const double* W36, const double* X, double* rec) {
+    double RE[9], w[6];
+    mat_mul(val, X, RE);
+    prior3_load(W36, w);
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) {
+        const double col[3] = {RE[cc], RE[3 + cc], RE[6 + cc]};
+        double t[3] = {0.0, 0.0, 0.0};
+        prior3_mul_add(w, col, t);   // W R_E[:, cc]
+#pragma unroll
+        for (int r = cc; r < 3; ++r) {
+            double h = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) h += RE[i * 3 + r] * t[i];
+            rec[r * (r + 1) / 2 + cc] = h;
+        }
+    }
+}
+
 // one range edge (no lever arm on endpoint 1): rho' info, J0 (D columns of the pose carrying the lever arm), J1 (D columns of the other pose)
 // err_out: where the marginal-prior pass wants the edge's error as well (the covariance passes pass none)
 template <int D, int JAC>

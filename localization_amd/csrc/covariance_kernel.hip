@@ -21,6 +21,8 @@
 //     lane factors S_i (Cholesky, pivots checked) in its registers and keeps entry (r, c) of S_i^-1 = L^-T L^-1 (cov_eliminate_block);
 //   * selected inversion, backwards: Sigma_{n-1} = S_{n-1}^-1, Sigma_i = S_i^-1 + K_i^T Sigma_{i+1} K_i (lane = entry; cov_back_substitute_block).
 // D = 3 for translation-only batches (capi_window.cpp: translation_only — 3x3 blocks, the rotation bits always set), D = 6 otherwise.
+// PINFO (D = 3 only): the priors' information is the dense 3 x 3 block of their row of a.p_info (a translation-only table, option
+// "prior_information_structured") in the place of p_val's diagonal; the exclusion rule and the pivot tests see whatever diagonal results.
 #include "cov_block_device.h"
 #include "window_kernel.h"
 
@@ -56,7 +58,7 @@ __host__ __device__ inline CovLayout cov_layout(int nvl, int D, bool priors, boo
     return l;
 }
 
-template <int D, int JAC, bool JOINT>
+template <int D, int JAC, bool JOINT, bool PINFO = false>
 __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int nvl, bool priors, bool se3, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int DD = D * D;
     constexpr int RS = 1 + 2 * D;
@@ -124,7 +126,8 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
         const int e = e0 + lane;
         if (e < np) {
             const int v = a.p_idx[(size_t)inst * cp.np_max + e];
-            cov_prior_block(a.p_val + ((size_t)inst * cp.np_max + e) * 18, P + v * 12, prec + lane * 21);
+            if (PINFO) cov_prior_block3(a.p_val + ((size_t)inst * cp.np_max + e) * 18, a.p_info + ((size_t)inst * cp.np_max + e) * 36, P + v * 12, prec + lane * 21);
+            else cov_prior_block(a.p_val + ((size_t)inst * cp.np_max + e) * 18, P + v * 12, prec + lane * 21);
             pi[lane] = v;
         }
         __syncthreads();
@@ -174,17 +177,17 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
     if (JOINT) cov_store_cross<D>(Hd, Ho, Kb, mk, nv, ok, lane, r, c, ent, inst, pp, [nv](int v) { return v + 1 < nv ? v + 1 : -1; });
 }
 
-template <int D, int JAC, bool JOINT>
+template <int D, int JAC, bool JOINT, bool PINFO = false>
 hipError_t launch_cov_j(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC, JOINT>>(160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC, JOINT, PINFO>>(160 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((covariance_kernel<D, JAC, JOINT>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status, pp);
+    hipLaunchKernelGGL((covariance_kernel<D, JAC, JOINT, PINFO>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status, pp);
     return hipGetLastError();
 }
-template <int D, int JAC>
+template <int D, int JAC, bool PINFO = false>
 hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    return pp.cross ? launch_cov_j<D, JAC, true>(a, nvl, priors, se3, lds, cov, mask, status, pp, stream)
-                    : launch_cov_j<D, JAC, false>(a, nvl, priors, se3, lds, cov, mask, status, pp, stream);
+    return pp.cross ? launch_cov_j<D, JAC, true, PINFO>(a, nvl, priors, se3, lds, cov, mask, status, pp, stream)
+                    : launch_cov_j<D, JAC, false, PINFO>(a, nvl, priors, se3, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace
@@ -199,6 +202,11 @@ hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, i
     const bool priors = a.caps.np_max > 0, se3 = !d3 && a.caps.ns_max > 0;
     const size_t lds = window_covariance_lds_bytes(a.caps, d3);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (a.p_info) {   // (the host admits a table here only where structured_pinfo holds: window_dispatch.cpp, cov_admitted — Chain3 alone)
+        if (!d3) return hipErrorInvalidValue;
+        return a.jacobian ? launch_cov_t<3, 1, true>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream)
+                          : launch_cov_t<3, 0, true>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream);
+    }
     if (d3) return a.jacobian ? launch_cov_t<3, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream)
                               : launch_cov_t<3, 0>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream);
     return a.jacobian ? launch_cov_t<6, 1>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream)

@@ -6,7 +6,10 @@
 // pose (:338-340), Cauchy kernels (:608-627) — solved by Localization::solve() = g2o Levenberg-Marquardt (:164-170), chi2() (:197).
 // The 3-DoF form is exact for these graphs (chain3_kernel.hip's header: identity antenna offsets, identity rotations, no rotation
 // information — every dropped term of the 6x6-block system is an exact zero); the host takes this kernel under the same
-// conditions as chain3_lm_kernel, for windows of <= 64 poses (capi_window.cpp: pick_kernel).
+// conditions as chain3_lm_kernel, for windows of <= 64 poses (capi_window.cpp: pick_kernel).  The twin <JAC, true> takes priors with a
+// dense 3 x 3 information block on the translation — the marginal prior a fixed-lag smoother carries (loc_window_set_prior_information
+// with a translation-only table and option "prior_information_structured"; window_dispatch.cpp: structured_pinfo): still exact, the
+// table's rotation rows and columns are zeros.
 //
 // MI355X mapping.  A single window is a latency problem: one wave issues one f64 instruction per 4 .. 8 cycles whatever its 64
 // lanes hold, so the general wave-per-window kernel's 6x6-block schedule (~9 k instructions per LM iteration on a ten-pose window,
@@ -53,11 +56,13 @@ struct W3Lds {
                     //                pose's own J (3), the other endpoint's J (3) when that is the previous pose (else 0)
     double* ev;     // [nr_max][2]    measurement, information
     double* fix;    // [nr_max][3]    the fixed endpoint of an anchor edge
-    double* pv;     // [np_max][6]    priors: Z^-1 t (3), information diagonal (3)
+    double* pv;     // [np_max][6]    priors: Z^-1 t (3), information diagonal (3); PINFO: [np_max][9], Z^-1 t (3), the lower triangle of the
+                    //                dense 3 x 3 information block on the translation (6: prior3_load)
     int* eidx;      // [nr_max][2]
     int* epos;      // [nr_max][2]    where the edge's two records go (endpoint 1 of an anchor edge: -1)
     int* pidx;      // [np_max]
 };
+template <bool PINFO>
 __device__ __forceinline__ W3Lds w3_carve(const WindowCaps& c) {
     W3Lds l;
     double* p = w3lds;
@@ -65,7 +70,7 @@ __device__ __forceinline__ W3Lds w3_carve(const WindowCaps& c) {
     l.rec = p; p += (size_t)c.nr_max * 16;
     l.ev = p; p += (size_t)c.nr_max * 2;
     l.fix = p; p += (size_t)c.nr_max * 3;
-    l.pv = p; p += (size_t)c.np_max * 6;
+    l.pv = p; p += (size_t)c.np_max * (PINFO ? 9 : 6);
     int* q = reinterpret_cast<int*>(p);
     l.eidx = q; q += (size_t)c.nr_max * 2;
     l.epos = q; q += (size_t)c.nr_max * 2;
@@ -154,19 +159,36 @@ __device__ __forceinline__ void w3_edge(const W3Lds& l, const double* T, const W
 
 // every edge and prior of the window at the translations of buffer `buf`: the robust and plain chi2 sums; FULL: the edges'
 // linearisation records as well
-template <bool FULL, int JAC>
+// one prior at the translations T: its chi2 (no robust kernel).  PINFO: e^T W e with the dense block (prior3_mul_add: the diagonal terms
+// first, so that a block without off-diagonal entries gives the bits of the diagonal form)
+template <bool PINFO>
+__device__ __forceinline__ double w3_prior_chi(const W3Lds& l, const double* T, int q) {
+    const double* s = T + l.pidx[q] * 3;
+    double chi = 0.0;
+    if (PINFO) {
+        const double* v = l.pv + (size_t)q * 9;
+        const double er[3] = {s[0] + v[0], s[1] + v[1], s[2] + v[2]};
+        double we[3] = {0.0, 0.0, 0.0};
+        prior3_mul_add(v + 3, er, we);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) chi += er[k] * we[k];
+    } else {
+        const double* v = l.pv + (size_t)q * 6;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const double er = s[k] + v[k]; chi += er * (v[3 + k] * er); }
+    }
+    return chi;
+}
+
+template <bool FULL, int JAC, bool PINFO>
 __device__ __forceinline__ void w3_edges(const W3Lds& l, const W3Edge& E0, int nvm, int nr, int np, int buf, int lane, double& robust_chi, double& plain_chi) {
     double rsum = 0.0, csum = 0.0;
     const double* T = l.T + (size_t)buf * nvm * 3;
     if (lane < nr) w3_edge<FULL, JAC>(l, T, E0, rsum, csum);
     for (int e = lane + 64; e < nr; e += 64) w3_edge<FULL, JAC>(l, T, w3_load_edge(l, e), rsum, csum);
-    // unary priors: e = t + Z^-1.t (identity rotations), diagonal information on the translation, no robust kernel
+    // unary priors: e = t + Z^-1.t (identity rotations), diagonal (PINFO: dense 3 x 3) information on the translation, no robust kernel
     for (int q = lane; q < np; q += 64) {
-        const double* s = T + l.pidx[q] * 3;
-        const double* v = l.pv + (size_t)q * 6;
-        double chi = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double er = s[k] + v[k]; chi += er * (v[3 + k] * er); }
+        const double chi = w3_prior_chi<PINFO>(l, T, q);
         rsum += chi;
         csum += chi;
     }
@@ -177,7 +199,7 @@ __device__ __forceinline__ void w3_edges(const W3Lds& l, const W3Edge& E0, int n
 // TWO trial states scored in one pass (windows of <= 32 edges and <= 32 priors): state A by lanes 0 .. 31, state B by lanes 32 .. 63, every
 // lane with the edge of its position in its half.  The sums are the DPP tree of wave_sum read where a half has been summed — lanes 31 and 63
 // after the row_bcast:15 step — which is bit for bit what the whole-wave sum of ONE state gives (its other rows add zeros).
-template <int JAC>
+template <int JAC, bool PINFO>
 __device__ __forceinline__ void w3_edges_dual(const W3Lds& l, const W3Edge& E0, int nvm, int nr, int np, int bufA, int bufB, int lane,
                                               double& chiA, double& plainA, double& chiB, double& plainB) {
     double rsum = 0.0, csum = 0.0;
@@ -185,11 +207,7 @@ __device__ __forceinline__ void w3_edges_dual(const W3Lds& l, const W3Edge& E0, 
     const double* T = l.T + (size_t)(lane < 32 ? bufA : bufB) * nvm * 3;
     if (el < nr) w3_edge<false, JAC>(l, T, E0, rsum, csum);
     if (el < np) {
-        const double* s = T + l.pidx[el] * 3;
-        const double* v = l.pv + (size_t)el * 6;
-        double chi = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double er = s[k] + v[k]; chi += er * (v[3 + k] * er); }
+        const double chi = w3_prior_chi<PINFO>(l, T, el);
         rsum += chi;
         csum += chi;
     }
@@ -202,12 +220,14 @@ __device__ __forceinline__ void w3_edges_dual(const W3Lds& l, const W3Edge& E0, 
     chiB = read_lane(rsum, 63); plainB = read_lane(csum, 63);
 }
 
-template <int JAC>
+// PINFO: the priors carry a dense 3 x 3 information block on the translation (a.p_info: loc_window_set_prior_information with a
+// translation-only table, option "prior_information_structured") in the place of p_val's diagonal — chi2 and the per-pose fold alone differ
+template <int JAC, bool PINFO>
 __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
     const int lane = threadIdx.x;
     const long long inst = blockIdx.x;
     const WindowCaps& cp = a.caps;
-    const W3Lds l = w3_carve(cp);
+    const W3Lds l = w3_carve<PINFO>(cp);
     const int nvm = cp.nv_max;
     const double* gin = a.poses_in + (size_t)inst * nvm * 12;
     double* gout = a.poses + (size_t)inst * nvm * 12;
@@ -253,8 +273,14 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
         const double* pval = a.p_val + (size_t)inst * cp.np_max * 18;
         for (int q = lane; q < np; q += 64) {
             l.pidx[q] = pidx[q];
+            if (PINFO) {   // (p_val's diagonal is not read under a table)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { l.pv[6 * q + k] = pval[18 * q + 9 + k]; l.pv[6 * q + 3 + k] = pval[18 * q + 12 + k]; }
+                for (int k = 0; k < 3; ++k) l.pv[9 * q + k] = pval[18 * q + 9 + k];
+                prior3_load(a.p_info + ((size_t)inst * cp.np_max + q) * 36, l.pv + 9 * q + 3);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { l.pv[6 * q + k] = pval[18 * q + 9 + k]; l.pv[6 * q + 3 + k] = pval[18 * q + 12 + k]; }
+            }
         }
     }
     wave_sync();
@@ -313,7 +339,7 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
     while (!done) {
         if (need_lin) {
             double plain;
-            w3_edges<true, JAC>(l, E0, nvm, nr, np, cur, lane, cur_chi, plain);
+            w3_edges<true, JAC, PINFO>(l, E0, nvm, nr, np, cur, lane, cur_chi, plain);
             last_plain = plain;
             wave_sync();
             W3_T(1);
@@ -356,10 +382,18 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
                 for (int k = lst + 3; k < k1; ++k) fold(k, l.rec + (size_t)k * 8);
                 for (int pq = 0; pq < np; ++pq) {
                     if (l.pidx[pq] != pp) continue;
-                    const double* v = l.pv + (size_t)pq * 6;
                     const double* s = l.T + ((size_t)cur * nvm + pp) * 3;
+                    if (PINFO) {   // H_pp += W, b_p -= W e
+                        const double* v = l.pv + (size_t)pq * 9;
+                        const double ner[3] = {-(s[0] + v[0]), -(s[1] + v[1]), -(s[2] + v[2])};
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) { const double er = s[k] + v[k]; D[k * (k + 1) / 2 + k] += v[3 + k]; b[k] += -v[3 + k] * er; }
+                        for (int k = 0; k < 6; ++k) D[k] += v[3 + k];
+                        prior3_mul_add(v + 3, ner, b);
+                    } else {
+                        const double* v = l.pv + (size_t)pq * 6;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) { const double er = s[k] + v[k]; D[k * (k + 1) / 2 + k] += v[3 + k]; b[k] += -v[3 + k] * er; }
+                    }
                 }
             }
             if (rank1) {
@@ -640,10 +674,10 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
                 if (!scored[g]) {
                     if (g < 3 && dual && g + 1 < G) {   // this trial and the next one in one pass
                         const int slot2 = cur + 2 + g - (cur + 2 + g >= NSLOT ? NSLOT : 0);
-                        w3_edges_dual<JAC>(l, E0, nvm, nr, np, slot, slot2, lane, tchi[g], tplain[g], tchi[g < 3 ? g + 1 : 3], tplain[g < 3 ? g + 1 : 3]);
+                        w3_edges_dual<JAC, PINFO>(l, E0, nvm, nr, np, slot, slot2, lane, tchi[g], tplain[g], tchi[g < 3 ? g + 1 : 3], tplain[g < 3 ? g + 1 : 3]);
                         scored[g < 3 ? g + 1 : 3] = true;
                     } else {
-                        w3_edges<false, JAC>(l, E0, nvm, nr, np, slot, lane, tchi[g], tplain[g]);
+                        w3_edges<false, JAC, PINFO>(l, E0, nvm, nr, np, slot, lane, tchi[g], tplain[g]);
                     }
                 }
                 double temp_chi = tchi[g];
@@ -701,18 +735,22 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
 
 }  // namespace
 
-size_t window_wave3_lds_bytes(const WindowCaps& c) {
-    const size_t doubles = (size_t)5 * c.nv_max * 3 + (size_t)c.nr_max * 21 + (size_t)c.np_max * 6;
+size_t window_wave3_lds_bytes(const WindowCaps& c, bool pinfo) {
+    const size_t doubles = (size_t)5 * c.nv_max * 3 + (size_t)c.nr_max * 21 + (size_t)c.np_max * (pinfo ? 9 : 6);
     const size_t ints = (size_t)c.nr_max * 4 + c.np_max;
     return doubles * sizeof(double) + ((ints + 1) & ~(size_t)1) * sizeof(int);
 }
 
 hipError_t launch_window_wave3(const WindowArgs& a, hipStream_t stream) {
     if (a.B <= 0 || a.caps.nv_max > 64 || a.caps.nv_max <= 0) return hipErrorInvalidValue;
-    const size_t lds = window_wave3_lds_bytes(a.caps);
+    const bool pinfo = a.p_info != nullptr;   // (the host hands over a table only where structured_pinfo holds: window_dispatch.cpp, pick_kernel)
+    const size_t lds = window_wave3_lds_bytes(a.caps, pinfo);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    if (a.jacobian) hipLaunchKernelGGL((wave3_lm_kernel<1>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((wave3_lm_kernel<0>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+    if (pinfo) {
+        if (a.jacobian) hipLaunchKernelGGL((wave3_lm_kernel<1, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((wave3_lm_kernel<0, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+    } else if (a.jacobian) hipLaunchKernelGGL((wave3_lm_kernel<1, false>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+    else hipLaunchKernelGGL((wave3_lm_kernel<0, false>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
     return hipGetLastError();
 }
 

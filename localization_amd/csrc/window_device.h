@@ -269,6 +269,27 @@ __device__ __forceinline__ void prior_full_hessian(const double* J, const double
     }
 }
 
+// A prior with a DENSE 3 x 3 information block W on the translation (the top-left block of a translation-only row of
+// loc_window_set_prior_information's table: the marginal prior of a dropped pose).  w: its lower triangle, k = r (r + 1) / 2 + c.
+__device__ __forceinline__ void prior3_load(const double* W36, double* w) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c <= r; ++c) w[r * (r + 1) / 2 + c] = W36[r * 6 + c];
+}
+// acc += W e.  The one statement of the 3 x 3 product: wave3_kernel.hip (chi2 = e^T (W e), b -= W e) and cov_block_device.h's
+// cov_prior_block3 both call it.  The diagonal terms come first and every off-diagonal term is added on its own: a W without
+// off-diagonal entries adds exact zeros to what the kernels for diagonal information compute.
+__device__ __forceinline__ void prior3_mul_add(const double* w, const double* e, double* acc) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] += w[k * (k + 1) / 2 + k] * e[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (j != k) acc[k] += w[k > j ? k * (k + 1) / 2 + j : j * (j + 1) / 2 + k] * e[j];
+}
+
 // 1/sqrt(d) for a pivot d > 0: hardware seed (~2^-24) + one third-order step y (1 + e/2 + 3 e^2/8), e = 1 - d y^2: the error
 // term e^3 is far below an ulp; four dependent operations after the seed (the Goldschmidt pair + Newton used elsewhere: eight)
 __device__ __forceinline__ double pivot_rsqrt(double d) {

@@ -8,6 +8,10 @@ namespace locamd {
 // what only the general kernel evaluates: lever arms on endpoint 1, full information matrices on the priors.  One flag of the structure
 // hash and of build_tree_sched: no cached verdict and no forest schedule survives a change of it.
 static bool general_only(const DispatchOpts& o) { return o.has_off1 || o.has_pinfo; }
+// ... unless the table is a dense 3 x 3 block on the translations and the handle asked for the 3 x 3 kernels: wave3_lm_kernel<JAC, true> and
+// covariance_kernel<3, .., true> take such a table on a translation-only chain (pick_kernel, structured_covariance_kind); chain3_lm_kernel,
+// arrow3_lm_kernel and every other pass do not
+bool structured_pinfo(const DispatchOpts& o) { return o.pinfo_structured && o.has_pinfo && o.pinfo_translation && !o.has_off1; }
 
 // Large batches of CHAIN windows (every pose-to-pose edge — range or SE3 — joins consecutive poses; edges ordered by their
 // later pose and priors by pose — the order Localization::addRangeEdge / addImuEdge create them in) run one lane per window
@@ -46,7 +50,9 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
     if (!hit) chain_scan(c, b, true, chain, single_pairs, se3_pairs);
     if (use_cache && !hit) { tc->valid = true; tc->key = key; tc->n = b.n; tc->chain = chain; tc->single_pairs = single_pairs; tc->se3_pairs = se3_pairs; tc->tree_tried = false; tc->tree_ok = false; }
     if (chain) {
-        if (translation_only(c, n_anchors, b)) return {LOC_WINDOW_KERNEL_CHAIN3, hit};
+        // (under a structured table the priors' diagonals are not read by any kernel, so not by the scan either: the verdict holds while
+        //  structured_pinfo does — pick_kernel asks again, and the resident batch remembers how its verdict was taken)
+        if (translation_only(c, n_anchors, b, structured_pinfo(o))) return {LOC_WINDOW_KERNEL_CHAIN3, hit};
         if (single_pairs && f.wave6) return {LOC_WINDOW_KERNEL_WAVE6, hit};
         // cfg/uwb_twist.yaml's window: a twist EdgeSE3 per consecutive pair next to the ranges — the wave-per-window kernel with full coupling
         // blocks.  (The same window was tried on tree_wave_kernel first — a chain is a forest, rooted at its centre it has 8 levels: 0.58 … 0.67 ms
@@ -69,10 +75,26 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
     return {LOC_WINDOW_KERNEL_GENERAL, hit};
 }
 
+static int pick_plain(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology);
+
 int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology) {
+    if (general_only(o)) {   // (lever arms on endpoint 1, full-information priors: only the general kernel evaluates them ...
+        // ... but for a structured table on a translation-only chain that the handle's other switches would hand to wave3_lm_kernel: its twin
+        // <JAC, true> takes it, when its larger prior records fit)
+        if (structured_pinfo(o) && topology == LOC_WINDOW_KERNEL_CHAIN3 && f.wave3_pinfo) {
+            DispatchFits g = f;
+            g.wave3 = true;
+            if (pick_plain(o, g, n, topology) == LOC_WINDOW_KERNEL_WAVE3) return LOC_WINDOW_KERNEL_WAVE3;
+        }
+        return LOC_WINDOW_KERNEL_GENERAL;
+    }
+    return pick_plain(o, f, n, topology);
+}
+
+// the rule for handles without lever arms on endpoint 1 and without a table of full information matrices
+static int pick_plain(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology) {
     const long long mn = effective_chain_min(o);
     const bool default_rule = o.chain_min < 0 && !o.env_chain_min_set;
-    if (general_only(o)) return LOC_WINDOW_KERNEL_GENERAL;   // (lever arms on endpoint 1, full-information priors: only the general kernel evaluates them)
     if (mn <= 0 || o.natural_order) return LOC_WINDOW_KERNEL_GENERAL;   // threshold 0 = "never anything but the general kernel" (every structure)
     if (topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) {   // (WAVE6S: the same rule for chains with EdgeSE3 factors)
         // a 6-DoF chain batch that also qualifies for wave6_lm_kernel (one wave per window, rank-1 couplings).  Measured on twelve-pose
@@ -116,16 +138,21 @@ int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int top
 static CovVerdict structured_covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b,
                                              WinAux& own, SchedKey* keyed) {
     const CovVerdict none{CovKind::None, false, 0, 0};
-    if (general_only(o)) return none;   // (full-information priors: the three passes below read the diagonals alone — the envelope pass serves them)
+    // (full-information priors: the three passes below read the diagonals alone — the envelope pass serves them; a structured table on a
+    //  translation-only chain alone is the chain pass's, covariance_kernel<3, .., true>)
+    const bool structured = structured_pinfo(o);
+    if (general_only(o) && !structured) return none;
     const bool small = c.nv_max <= 64;
     if (small) {
         bool chain = false, single_pairs = false, se3_pairs = false;
         chain_scan(c, b, false, chain, single_pairs, se3_pairs);
         if (chain) {
             if (!f.cov_chain) return none;
+            if (structured) return {translation_only(c, n_anchors, b, true) ? CovKind::Chain3 : CovKind::None, false, 0, 0};
             return {translation_only(c, n_anchors, b) ? CovKind::Chain3 : CovKind::Chain6, false, 0, 0};
         }
     }
+    if (structured) return none;
     if (arrow3_wanted(o, f) && f.cov_arrow && translation_only(c, n_anchors, b) && build_arrow_aux(c, b, own, true))
         return {CovKind::Arrow, false, own.arrow_list_cap, 0};
     if (!small) return none;
@@ -142,7 +169,8 @@ static CovVerdict structured_covariance_kind(const WindowCaps& c, const Dispatch
 
 long long cov_switches(const DispatchOpts& o) {
     const long long mn = tree_min_batch(o);
-    return (((long long)(o.arrow3 + 1) << 4 | (long long)(o.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8)) | (o.has_pinfo ? 1ll << 60 : 0);
+    return (((long long)(o.arrow3 + 1) << 4 | (long long)(o.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8)) | (o.has_pinfo ? 1ll << 60 : 0) |
+           (o.pinfo_structured ? 1ll << 59 : 0) | (o.has_pinfo && o.pinfo_translation ? 1ll << 58 : 0);
 }
 
 // 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is Envelope —
@@ -163,7 +191,7 @@ CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const Dis
 bool cov_admitted(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind) {
     const bool forest = kind == CovKind::Forest || kind == CovKind::ForestOwn;
     const bool arrow = kind == CovKind::Arrow, envelope = kind == CovKind::Envelope;
-    const bool refused = o.has_off1 || (o.has_pinfo && !envelope) || (f.nv_max > 64 && !arrow && !envelope) || kind == CovKind::Unclassified || kind == CovKind::None ||
+    const bool refused = o.has_off1 || (o.has_pinfo && !envelope && !(kind == CovKind::Chain3 && structured_pinfo(o))) || (f.nv_max > 64 && !arrow && !envelope) || kind == CovKind::Unclassified || kind == CovKind::None ||
                          (forest && (n < tree_min_batch(o) || o.tree == 0)) || (arrow && (!arrow3_wanted(o, f) || !f.cov_arrow)) || (envelope && !o.cov_general);
     return !refused;
 }

@@ -20,6 +20,9 @@ struct DispatchOpts {
     bool natural_order = false;        // loc_window_set_ordering
     bool has_off1 = false;             // lever arms of endpoint 1 are set (loc_window_set_endpoint1_offsets)
     bool has_pinfo = false;            // full information matrices of the priors are set (loc_window_set_prior_information)
+    bool pinfo_translation = false;    // ... and none of them has rotation rows or columns (prior_information_translation_only, taken once by the setter)
+    bool pinfo_structured = false;     // "prior_information_structured" 1: a translation-only table on a translation-only chain is served by
+                                       // wave3_lm_kernel<JAC, true> and the chain 3x3 covariance pass (structured_pinfo); 0: the general kernel, the envelope pass
 };
 
 // what depends on the handle's capacities alone: the kernels' LDS needs against their limits, taken once by loc_window_create
@@ -27,6 +30,7 @@ struct DispatchFits {
     bool wave6 = false;          // nv_max <= 64 and wave6_lm_kernel's LDS
     bool wave6_se3 = false;      // nv_max <= 63, ns_max <= 64 and wave6_lm_kernel<JAC, true>'s LDS
     bool wave3 = false;          // nv_max <= 64 and wave3_lm_kernel's LDS
+    bool wave3_pinfo = false;    // the same with the prior records of wave3_lm_kernel<JAC, true> (a dense 3x3 block per prior)
     bool cov_chain = false, cov_arrow = false, cov_envelope = false;   // the chain (6x6) / arrowhead / envelope covariance pass within 160 KiB
     int nv_max = 0;
 };
@@ -41,10 +45,14 @@ enum class CovKind : int {
     Envelope             // envelope_covariance_kernel.hip (option "covariance_general")
 };
 
+// the handle's table of full information matrices is one the 3 x 3 kernels take: option "prior_information_structured", a translation-only table,
+// no endpoint-1 lever arms.  While it holds, translation_only is asked with the prior diagonals skipped (p_val[12..17] is not read under a table)
+bool structured_pinfo(const DispatchOpts& o);
 long long effective_chain_min(const DispatchOpts& o);
 long long tree_min_batch(const DispatchOpts& o);
 bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f);
-// the switches the three structured covariance tests read besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold, has_pinfo)
+// the switches the three structured covariance tests read besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold, has_pinfo,
+// option "prior_information_structured", the table's translation-only verdict)
 long long cov_switches(const DispatchOpts& o);
 // the kernel a batch of n windows of that structure (batch_topology's verdict) takes NOW (threshold, ordering override, the options)
 int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology);

@@ -76,7 +76,8 @@ int window_chain3_lds_mode(const WindowCaps& c, long long B, int n_cus);   // bi
 hipError_t launch_window_chain3(const WindowArgs& a, double* ws, hipStream_t stream);
 
 // translation-only chain windows of <= 64 poses, one wave per window (wave3_kernel.hip): the node's own solve, small batches
-size_t window_wave3_lds_bytes(const WindowCaps& c);
+// pinfo: with the prior records of wave3_lm_kernel<JAC, true> (a.p_info set: a dense 3 x 3 information block per prior)
+size_t window_wave3_lds_bytes(const WindowCaps& c, bool pinfo = false);
 hipError_t launch_window_wave3(const WindowArgs& a, hipStream_t stream);
 
 // 6-DoF chain windows of <= 64 poses without EdgeSE3 factors and with at most one range edge per pair of consecutive poses, one wave

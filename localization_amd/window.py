@@ -326,7 +326,9 @@ class WindowSolver(_lib.Handle):
     def set_option(self, name, value):
         """loc_window_set_option: the kernel-selection switches of this handle ("chain_min_batch", "arrow3", "tree", "wave3", "wave6",
         "chain3", "zero_copy", "topology_cache", "kernel_events"; "covariance_general": 1 = covariance() / covariance_resident() also serve
-        the batches the chain, arrowhead and forest passes decline — every batch with full-information priors among them —, default 0)"""
+        the batches the chain, arrowhead and forest passes decline — every batch with full-information priors among them —, default 0;
+        "prior_information_structured": 1 = a translation-only p_info table (dense 3 x 3 blocks on the translations: marginal_prior()'s rows)
+        on translation-only chains of <= 64 poses is solved by wave3_lm_kernel and served by the chain 3 x 3 covariance pass, default 0)"""
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
 
     def last_host_timing(self):
