@@ -317,6 +317,8 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *                      as with 0.  0: every call does what it did without the option, bit for bit.  Looked at per call; a resident batch whose
  *                      verdict was taken under a structured table solves on the general kernel once the table has gone, has got a rotation
  *                      entry or the option is 0 (until the next upload), and its covariance pass is classified again.
+ *   "resident_slide"  0 (default) / 1: loc_window_upload keeps a host mirror of the batch's integer tables (counts, r_idx, p_idx), which
+ *                      loc_window_slide_resident needs; read at upload time.  0: an upload allocates and does exactly what it did without the option.
  * LOC_ERR_INVALID for an unknown name or value. */
 int loc_window_set_option(loc_window* w, const char* name, int64_t value);
 /* Host-side cost of the last loc_window_solve_host call, milliseconds: [0] argument validation, [1] structure analysis (kernel
@@ -468,8 +470,55 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream,
                                          void* cov_dev, void* mask_dev, void* status_dev, void* cross_dev);
 int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
                                      int32_t npair_max, const int32_t* pair_counts, const int32_t* pairs, int64_t* blocks_max, size_t* workspace_bytes);
-/* kernel time of the last covariance launch of this handle (HIP events on its stream; a resident launch is waited for), milliseconds */
+/* kernel time of the last covariance, marginal-prior or slide launch(es) of this handle (HIP events on its stream; a resident launch is
+ * waited for), milliseconds */
 int loc_window_last_covariance_ms(loc_window* w, double* ms);
+/* The resident fixed-lag slide ("The resident slide"): drop the oldest pose of every uploaded window, carry its marginal prior,
+ * append the newest pose and its factors — on the device, where the batch lives.  Needs loc_window_set_option(w, "resident_slide", 1) BEFORE
+ * loc_window_upload (the upload then keeps a host mirror of counts, r_idx and p_idx; with 0, the default, an upload does what it always did
+ * and this call is LOC_ERR_INVALID).  All inputs are HOST arrays; every output is a caller-owned DEVICE array and may be NULL.  Asynchronous
+ * on hip_stream (NULL = the handle's own stream): it waits for the last resident launch, the caller's arrays are copied to a page-locked
+ * block of the handle before the call returns (never read afterwards) and travel from there in stream order.
+ *   drop_oldest  int32  [n]                  non-zero: window b drops slot 0; 0: it only grows; NULL: every window drops
+ *   new_pose     double [n][12]              the appended pose, R(9) = identity, t(3)
+ *   nr_new_max, new_r_counts [n], new_r_idx [n][nr_new_max][2], new_r_val [n][nr_new_max][5]   the appended range rows (r_idx / r_val layouts)
+ *   np_new_max (may be 0), new_p_counts [n], new_p_val [n][np_new_max][18]                      the appended prior rows, all on the new pose
+ *   slot_dev int32 [n], prior_dev double [n][48], rank_dev int32 [n], status_dev int32 [n]      loc_window_marginal_prior_host's layouts
+ * Per window b, with x = loc_window_poses_device()'s content (the last resident solve's estimates):
+ *   1. drop_oldest[b] != 0: the marginal prior of slot 0 at x — marginal_prior_kernel itself, with the handle's Jacobian mode and table: the
+ *      bits loc_window_marginal_prior_host(.., drop = 0) returns for the same tables.  Slot 0 goes, with every range row that has it as an
+ *      endpoint and every prior row on it (and that row of the table); the other rows keep their order; moving slot indices decrease by 1
+ *      (anchor codes -1 - a stay); poses 1 .. nv - 1 move to 0 .. nv - 2.  If the marginal's slot >= 0 its row becomes prior row 0, on the new
+ *      slot 0, in front of the kept priors (a LOC_ERR_SINGULAR marginal's zero-information row included): p_val[0..11] = prior[0..11],
+ *      p_val[12..17] = the information's diagonal, table row = the information.
+ *   2. drop_oldest[b] == 0: nothing is removed (a window grows to its lag); outputs slot -1, 48 zeros, rank 0, LOC_OK.
+ *   3. new_pose[b] becomes the last slot s; then new_r_counts[b] range rows and new_p_counts[b] prior rows follow the kept ones.  Indices are
+ *      in the NEW numbering: v0 is s or s - 1, v1 is s, s - 1 or an anchor code; a pose-to-pose row joins s - 1 and s; rows are listed in the
+ *      order of their later pose (a row on s - 1 alone never after a row that names s).  The prior rows sit on s; their table row is
+ *      diag(p_val[12..17]).
+ *   4. the input estimates of the next resident solve AND loc_window_poses_device() become x's kept poses followed by new_pose; counts change
+ *      on the device and in the host's mirror.
+ *   5. a handle without a table of full information matrices gets one at its first slide ([batch][np_max][36]; every existing prior's row is
+ *      diag(p_val[12..17])) and from then on behaves as after loc_window_set_prior_information.
+ * After the call the handle is in the state loc_window_upload of the slid tables with that table set would leave: the kernel kind, the
+ * covariance pass, the anchors it references, the joint call's counts.  A resident solve, (joint) covariance or download after it sees the
+ * slid batch.  loc_window_last_covariance_ms reports the two launches (marginal pass + slide kernel).
+ * Everything is checked on the host before anything is launched or changed.  LOC_ERR_INVALID: option "resident_slide" was 0 at upload time;
+ * nothing uploaded; no resident solve since the upload; a table of full matrices that describes fewer windows than are resident; a new count
+ * outside [0, *_new_max]; a new index outside rule 3; a slid window beyond nv_max, nr_max or np_max (counted from the mirror); a window with
+ * nv = 0.  LOC_ERR_UNSUPPORTED: the resident batch's verdict is not LOC_WINDOW_KERNEL_CHAIN3 (an ordered translation-only chain, decided at
+ * upload; an ordered chain minus slot 0 plus a last slot joined to its predecessor alone is an ordered chain, so the verdict survives);
+ * endpoint-1 lever arms; a table with rotation entries; a new row that is not translation-only (a non-identity rotation, a non-zero lever
+ * arm, rotation information). */
+int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* drop_oldest, const double* new_pose,
+                              int32_t nr_new_max, const int32_t* new_r_counts, const int32_t* new_r_idx, const double* new_r_val,
+                              int32_t np_new_max, const int32_t* new_p_counts, const double* new_p_val,
+                              void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev);
+/* The resident batch as it stands (a checkpoint; host arrays in loc_window_upload's layouts, n = the resident batch's windows; any pointer may
+ * be NULL).  poses: the estimates the next resident solve starts from.  pinfo double [n][np_max][36]: the table of full information matrices;
+ * LOC_ERR_INVALID when the handle has none.  Synchronous (waits for the last resident launch). */
+int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
+                               int32_t* s_idx, double* s_val, double* pinfo);
 
 /* ================================================================================================
  * Node front-end — `class Localization` behind the ABI (one moving tag, its ring window, its anchors).

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <algorithm>
 #include <chrono>
 #include <new>
 #include <string>
@@ -95,6 +96,17 @@ struct loc_window {
     size_t pairs_cap = 0;
     hipEvent_t pairs_copied = nullptr;   // the device table has the page-locked copy's content
     bool pairs_inflight = false;
+    // the resident slide (loc_window_slide_resident): with option "resident_slide" loc_window_upload keeps the batch's index tables next to
+    // res_counts (the mirror the slide's admission counts from and slide_indices rewrites); the call's inputs [drop | counts | new rows] as a
+    // page-locked copy and as the device block the kernel reads, grown on demand, as the pair tables are; the marginal pass's drop table
+    // (zeros) and results for B windows
+    bool opt_slide = false, mirror_valid = false;
+    std::vector<int32_t> mir_ridx, mir_pidx;
+    char *h_slide = nullptr, *d_slide = nullptr;
+    size_t slide_cap = 0;
+    hipEvent_t slide_copied = nullptr;
+    bool slide_inflight = false;
+    char* d_slide_mp = nullptr;
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -141,6 +153,10 @@ int loc_window_destroy(loc_window* w) {
     if (w->h_pairs) (void)hipHostFree(w->h_pairs);
     if (w->d_pairs) (void)hipFree(w->d_pairs);
     if (w->pairs_copied) (void)hipEventDestroy(w->pairs_copied);
+    if (w->h_slide) (void)hipHostFree(w->h_slide);
+    if (w->d_slide) (void)hipFree(w->d_slide);
+    if (w->d_slide_mp) (void)hipFree(w->d_slide_mp);
+    if (w->slide_copied) (void)hipEventDestroy(w->slide_copied);
     if (w->cov_ev0) (void)hipEventDestroy(w->cov_ev0);
     if (w->cov_ev1) (void)hipEventDestroy(w->cov_ev1);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -350,7 +366,7 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
 // the resident batch as uploaded: the initial estimates in the place of the optimised ones
 static locamd::DeviceTables uploaded_tables(const loc_window* w) { locamd::DeviceTables d = w->dev; d.t[kPoses] = w->d_poses_in; return d; }
 // the device arrays hold no resident batch any more (the resident calls return LOC_ERR_INVALID until the next loc_window_upload completes)
-static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_skip = false; w->resident_min_anchors = 0; }
+static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_skip = false; w->resident_min_anchors = 0; w->mirror_valid = false; }
 
 static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const locamd::WindowArgs& a, hipStream_t st, int kind) {
     locamd::WinAux& A = S.aux;
@@ -426,6 +442,7 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
         if (rc == LOC_OK && before != o.pinfo_structured && w->n_resident > 0 && o.has_pinfo) w->resident_cov = CovKind::Unclassified;
         return rc;
     }
+    if (k == "resident_slide") return flag(w->opt_slide);   // (read by loc_window_upload: the batch resident now keeps what its upload decided)
     if (k == "topology_cache") { w->topo_cache.valid = false; return flag(o.topology_cache); }
     return locamd_fail(LOC_ERR_INVALID, "set_option: unknown option name");
 }
@@ -617,6 +634,13 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
         }
     w->resident_min_anchors = max_anchor;
     w->res_counts.assign(counts, counts + (size_t)n * 4);
+    if (w->opt_slide) {   // the mirror of loc_window_slide_resident
+        w->mir_ridx.assign((size_t)n * c.nr_max * 2, 0);
+        w->mir_pidx.assign((size_t)n * c.np_max, 0);
+        if (c.nr_max) std::memcpy(w->mir_ridx.data(), r_idx, w->mir_ridx.size() * sizeof(int32_t));
+        if (c.np_max) std::memcpy(w->mir_pidx.data(), p_idx, w->mir_pidx.size() * sizeof(int32_t));
+        w->mirror_valid = true;
+    }
     w->resident_topology = topology;
     w->resident_skip = locamd::structured_pinfo(w->opt);
     // the pass of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
@@ -957,6 +981,129 @@ int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, con
     if (blocks < 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_plan: counts exceed capacities, or an edge vertex index, a pair count or a pair's pose slot is out of range");
     *blocks_max = blocks;
     *workspace_bytes = (size_t)n * locamd::window_envelope_covariance_workspace_doubles(c, blocks) * sizeof(double);
+    return LOC_OK;
+}
+
+// ---- the resident slide (window_slide_kernel.hip; DESIGN.md §2, "The resident slide") ------------------------------------------------------------
+int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* drop_oldest, const double* new_pose,
+                              int32_t nr_new_max, const int32_t* new_r_counts, const int32_t* new_r_idx, const double* new_r_val,
+                              int32_t np_new_max, const int32_t* new_p_counts, const double* new_p_val,
+                              void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev) {
+    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->mirror_valid) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded");
+    if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: no resident solve has run since the upload");
+    if (!new_pose || nr_new_max < 0 || np_new_max < 0 || (nr_new_max > 0 && (!new_r_counts || !new_r_idx || !new_r_val)) ||
+        (np_new_max > 0 && (!new_p_counts || !new_p_val)))
+        return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: new pose and new row arrays");
+    if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
+    // (a verdict taken with the priors' diagonals skipped holds only while structured_pinfo does: loc_window_solve_resident's rule)
+    if (w->resident_topology != LOC_WINDOW_KERNEL_CHAIN3 || (w->resident_skip && !locamd::structured_pinfo(w->opt)))
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the resident batch is not an ordered translation-only chain batch");
+    if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
+    if (w->opt.has_pinfo && !w->opt.pinfo_translation) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the table of full information matrices has rotation entries");
+    const locamd::WindowCaps& c = w->caps;
+    const int64_t n = w->n_resident;
+    const size_t N = (size_t)n;
+    const locamd::SlideRows rows{drop_oldest, nr_new_max, new_r_counts, new_r_idx, np_new_max, new_p_counts};
+    static const char* const kWhat[] = {nullptr, "loc_window_slide_resident: a window without poses", "loc_window_slide_resident: a new count outside [0, *_new_max]",
+                                        "loc_window_slide_resident: a new range index (the new slot, the slot before it or an anchor; rows in the order of their later pose)",
+                                        "loc_window_slide_resident: the slid window exceeds nv_max", "loc_window_slide_resident: the slid window exceeds nr_max",
+                                        "loc_window_slide_resident: the slid window exceeds np_max"};
+    if (const int bad = locamd::slide_indices(c, w->n_anchors, n, w->res_counts.data(), w->mir_ridx.data(), w->mir_pidx.data(), rows, false).bad)
+        return locamd_fail(LOC_ERR_INVALID, kWhat[bad]);
+    if (!locamd::slide_rows_translation_only(n, rows, new_pose, new_r_val, new_p_val))
+        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: a new row is not translation-only (identity rotations, zero lever arms, no rotation information)");
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    // the staged inputs: [drop | new_r_counts | new_p_counts | new_r_idx | new_pose | new_r_val | new_p_val], 16-byte aligned pieces
+    const size_t nrn = (size_t)nr_new_max, npn = (size_t)np_new_max;
+    const size_t piece[7] = {N * sizeof(int32_t), N * sizeof(int32_t), N * sizeof(int32_t), N * nrn * 2 * sizeof(int32_t), N * 12 * sizeof(double),
+                             N * nrn * 5 * sizeof(double), N * npn * 18 * sizeof(double)};
+    size_t at[8] = {0};
+    for (int k = 0; k < 7; ++k) at[k + 1] = at[k] + ((piece[k] + 15) & ~(size_t)15);
+    if (w->slide_cap < at[7]) {
+        if (int rc = wait_resident(w)) return rc;   // (an earlier slide may still read the block that is about to be replaced)
+        if (w->h_slide) (void)hipHostFree(w->h_slide);
+        w->h_slide = nullptr; w->slide_cap = 0; w->slide_inflight = false;
+        LOC_HIP(hipHostMalloc((void**)&w->h_slide, at[7], hipHostMallocDefault));
+        LOC_HIP(locamd::grow_buffers(w->slide_cap, at[7], {{w->d_slide, at[7]}}));
+    }
+    // the marginal pass's block for B windows: [zeros | slot | rank | status | prior | grad | shift]
+    const size_t Bw = (size_t)w->B, mi = (Bw * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t mp_prior = 4 * mi, mp_grad = mp_prior + Bw * 48 * sizeof(double), mp_shift = mp_grad + Bw * 6 * sizeof(double), mp_end = mp_shift + Bw * 6 * sizeof(double);
+    const bool new_mp = !w->d_slide_mp;
+    if (new_mp) LOC_HIP(hipMalloc((void**)&w->d_slide_mp, mp_end));
+    const bool densify = !w->opt.has_pinfo && c.np_max > 0;
+    const size_t pinfo_bytes = Bw * c.np_max * 36 * sizeof(double);
+    if (densify) {
+        if (int rc = wait_resident(w)) return rc;   // (a launch under an earlier table may still read it)
+        if (!w->d_pinfo) LOC_HIP(hipMalloc((void**)&w->d_pinfo, pinfo_bytes));
+    }
+    if (!w->slide_copied) LOC_HIP(hipEventCreateWithFlags(&w->slide_copied, hipEventDisableTiming));
+    if (w->slide_inflight) { LOC_HIP(hipEventSynchronize(w->slide_copied)); w->slide_inflight = false; }
+    {   // the caller's arrays are read here and never after the call returns
+        char* h = w->h_slide;
+        int32_t* hd = (int32_t*)(h + at[0]);
+        if (drop_oldest) std::memcpy(hd, drop_oldest, piece[0]);
+        else for (size_t i = 0; i < N; ++i) hd[i] = 1;
+        const void* const src[7] = {nullptr, new_r_counts, new_p_counts, new_r_idx, new_pose, new_r_val, new_p_val};
+        for (int k = 1; k < 7; ++k)
+            if (piece[k] && src[k]) std::memcpy(h + at[k], src[k], piece[k]);
+    }
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    if (new_mp) LOC_HIP(hipMemsetAsync(w->d_slide_mp, 0, mi, st));                  // the marginal pass's drop table: slot 0 of every window
+    if (densify) LOC_HIP(hipMemsetAsync(w->d_pinfo, 0, pinfo_bytes, st));           // (rows beyond the counts: zeros, not what the allocation held)
+    LOC_HIP(hipMemcpyAsync(w->d_slide, w->h_slide, at[7], hipMemcpyHostToDevice, st));
+    LOC_HIP(hipEventRecord(w->slide_copied, st));
+    w->slide_inflight = true;
+    // launch 1: the marginal of slot 0 at the solved poses, marginal_prior_kernel itself (a handle without a table: p_val's diagonals, as
+    // loc_window_marginal_prior_host reads them); launch 2: the re-pack
+    const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, nullptr);
+    char* mp = w->d_slide_mp;
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)mp, (int32_t*)(mp + mi), (double*)(mp + mp_prior), (double*)(mp + mp_grad), (double*)(mp + mp_shift),
+                                                        (int32_t*)(mp + 2 * mi), (int32_t*)(mp + 3 * mi), st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
+    locamd::SlideArgs sa{};
+    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
+    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
+    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal]; sa.p_info = c.np_max > 0 ? w->d_pinfo : nullptr;
+    const char* d = w->d_slide;
+    sa.drop = (const int32_t*)(d + at[0]); sa.new_r_counts = (const int32_t*)(d + at[1]); sa.new_p_counts = (const int32_t*)(d + at[2]);
+    sa.new_r_idx = (const int32_t*)(d + at[3]); sa.new_pose = (const double*)(d + at[4]); sa.new_r_val = (const double*)(d + at[5]); sa.new_p_val = (const double*)(d + at[6]);
+    sa.m_slot = (const int32_t*)(mp + mi); sa.m_prior = (const double*)(mp + mp_prior); sa.m_rank = (const int32_t*)(mp + 2 * mi); sa.m_status = (const int32_t*)(mp + 3 * mi);
+    sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
+    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max; sa.B = (int)n; sa.caps = c;
+    e = locamd::launch_window_slide(sa, densify, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipEventRecord(w->resident_done, st));
+    w->resident_inflight = true;
+    w->cov_pending = true;
+    // the handle's state: what loc_window_upload of the slid tables, with the table set, would leave
+    const locamd::SlideVerdict v = locamd::slide_indices(c, w->n_anchors, n, w->res_counts.data(), w->mir_ridx.data(), w->mir_pidx.data(), rows, true);
+    w->resident_min_anchors = v.max_anchor;
+    if (densify) { w->opt.has_pinfo = true; w->opt.pinfo_translation = true; w->n_pinfo = n; }
+    w->resident_skip = locamd::structured_pinfo(w->opt);
+    w->resident_cov = CovKind::Chain3;   // (loc_window_upload's verdict for this topology; a call the switches do not admit classifies it again)
+    return LOC_OK;
+}
+
+int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
+                               int32_t* s_idx, double* s_val, double* pinfo) {
+    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (pinfo && !w->opt.has_pinfo) return locamd_fail(LOC_ERR_INVALID, "loc_window_download_tables: the handle has no table of full information matrices");
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = wait_resident(w)) return rc;
+    const locamd::WindowCaps& c = w->caps;
+    const size_t N = (size_t)w->n_resident;
+    void* dst[locamd::kWindowTables] = {nullptr};
+    dst[kPoses] = poses; dst[kCounts] = counts; dst[locamd::kRVal] = r_val; dst[locamd::kPVal] = p_val; dst[locamd::kSVal] = s_val;
+    dst[locamd::kRIdx] = r_idx; dst[locamd::kPIdx] = p_idx; dst[locamd::kSIdx] = s_idx;
+    LOC_HIP(copy_tables(c, N, dst, uploaded_tables(w).t, hipMemcpyDeviceToHost, nullptr));
+    const size_t n_info = std::min(N, (size_t)w->n_pinfo);
+    if (pinfo) LOC_HIP(hipMemcpy(pinfo, w->d_pinfo, n_info * c.np_max * 36 * sizeof(double), hipMemcpyDeviceToHost));
     return LOC_OK;
 }
 

@@ -165,6 +165,24 @@ hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, lo
 hipError_t launch_window_marginal_prior(const WindowArgs& a, const int32_t* drop, int32_t* slot, double* prior, double* grad, double* shift, int32_t* rank, int32_t* status,
                                         hipStream_t stream);
 
+// the resident slide's re-pack (window_slide_kernel.hip; DESIGN.md §2, "The resident slide"): one wave per window, in place on the resident
+// batch's tables, after launch_window_marginal_prior has left the marginal of slot 0 in m_*.  All device arrays; the host has admitted
+// every count and index (window_structure.cpp: slide_indices).
+struct SlideArgs {
+    int32_t* counts; double* poses; double* poses_in;   // [B][4]; the optimised estimates x (read, then re-packed); the next solve's input estimates
+    int32_t* r_idx; double* r_val; int32_t* p_idx; double* p_val; double* p_info;
+    const int32_t* drop;                                 // [B] != 0: the window drops slot 0
+    const double* new_pose;                              // [B][12]
+    const int32_t* new_r_counts; const int32_t* new_r_idx; const double* new_r_val;   // [B], [B][nr_new_max][2], [B][nr_new_max][5]
+    const int32_t* new_p_counts; const double* new_p_val;                             // [B], [B][np_new_max][18]
+    const int32_t* m_slot; const double* m_prior; const int32_t* m_rank; const int32_t* m_status;   // the marginal pass's results
+    int32_t* slot; double* prior; int32_t* rank; int32_t* status;                     // the caller's outputs, each may be nullptr
+    int nr_new_max, np_new_max, B;
+    WindowCaps caps;
+};
+// densify: p_info is a NEW table (the handle had none): every row but the carried one becomes diag(p_val[12..17])
+hipError_t launch_window_slide(const SlideArgs& s, bool densify, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

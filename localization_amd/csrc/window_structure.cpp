@@ -141,6 +141,103 @@ int check_marginal_drop(const WindowCaps& c, const HostBatch& b, const int32_t* 
     return first_bad.load();
 }
 
+// The resident slide's index rule on the host mirror (window_structure.h; window_slide_kernel.hip applies the same rule to the device tables)
+SlideVerdict slide_indices(const WindowCaps& c, int n_anchors, int64_t n, int32_t* counts, int32_t* r_idx, int32_t* p_idx, const SlideRows& s, bool apply) {
+    std::atomic<int> first_bad{0};
+    int max_part[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // one per thread's window range
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int t) {
+        int max_anchor = 0;
+        for (int64_t i = lo; i < hi && first_bad.load(std::memory_order_relaxed) == 0; ++i) {
+            int32_t* cn = counts + i * 4;
+            int32_t* ri = r_idx + (size_t)i * c.nr_max * 2;
+            int32_t* pi = p_idx + (size_t)i * c.np_max;
+            const int nv = cn[0], nr = cn[1], np = cn[2];
+            const bool drop = !s.drop || s.drop[i] != 0;
+            const int nrn = s.nr_new_max > 0 ? s.r_counts[i] : 0, npn = s.np_new_max > 0 ? s.p_counts[i] : 0;
+            const int32_t* nri = s.r_idx + (size_t)i * (s.nr_new_max > 0 ? s.nr_new_max : 0) * 2;
+            // what the drop leaves: the kept rows, and whether a pose-to-pose range joined slot 0 to another pose (the marginal's slot >= 0)
+            int r_kept = nr, p_kept = np, carried = 0;
+            if (drop) {
+                r_kept = 0; p_kept = 0;
+                for (int e = 0; e < nr; ++e) {
+                    const int32_t v0 = ri[e * 2], v1 = ri[e * 2 + 1];
+                    if (v0 != 0 && v1 != 0) ++r_kept;
+                    else if (v1 >= 0) carried = 1;
+                }
+                for (int e = 0; e < np; ++e) p_kept += pi[e] != 0;
+            }
+            const int nv2 = nv - (drop ? 1 : 0) + 1, sl = nv2 - 1;   // the slid window's poses, its new slot
+            if (!apply) {
+                int bad = 0;
+                if (nv <= 0) bad = 1;
+                else if (nrn < 0 || nrn > s.nr_new_max || npn < 0 || npn > s.np_new_max) bad = 2;
+                bool named = false;   // a row so far names the new slot
+                for (int e = 0; e < nrn && !bad; ++e) {
+                    const int32_t v0 = nri[e * 2], v1 = nri[e * 2 + 1];
+                    const bool ok0 = v0 == sl || (v0 == sl - 1 && v0 >= 0);
+                    const bool ok1 = v1 < 0 ? v1 >= -n_anchors : ((v1 == sl || v1 == sl - 1) && v1 != v0 && c.bw_max >= 1);
+                    const bool names = v0 == sl || v1 == sl;
+                    if (!ok0 || !ok1 || (named && !names)) bad = 3;
+                    named = named || names;
+                }
+                if (!bad && nv2 > c.nv_max) bad = 4;
+                if (!bad && r_kept + nrn > c.nr_max) bad = 5;
+                if (!bad && carried + p_kept + npn > c.np_max) bad = 6;
+                if (bad) { int zero = 0; first_bad.compare_exchange_strong(zero, bad); return; }
+                continue;
+            }
+            if (drop) {   // destinations never pass sources: in place
+                int k = 0;
+                for (int e = 0; e < nr; ++e) {
+                    const int32_t v0 = ri[e * 2], v1 = ri[e * 2 + 1];
+                    if (v0 == 0 || v1 == 0) continue;
+                    ri[k * 2] = v0 - 1; ri[k * 2 + 1] = v1 > 0 ? v1 - 1 : v1;
+                    ++k;
+                }
+                k = 0;
+                for (int e = 0; e < np; ++e)
+                    if (pi[e] != 0) pi[k++] = pi[e] - 1;
+                if (carried) {   // the one-row shift, from the top down
+                    for (int e = p_kept; e > 0; --e) pi[e] = pi[e - 1];
+                    pi[0] = 0;
+                }
+            }
+            for (int e = 0; e < nrn; ++e) { ri[(r_kept + e) * 2] = nri[e * 2]; ri[(r_kept + e) * 2 + 1] = nri[e * 2 + 1]; }
+            for (int e = 0; e < npn; ++e) pi[carried + p_kept + e] = sl;
+            cn[0] = nv2; cn[1] = r_kept + nrn; cn[2] = carried + p_kept + npn;
+            for (int e = 0; e < cn[1]; ++e)
+                if (ri[e * 2 + 1] < 0 && -ri[e * 2 + 1] > max_anchor) max_anchor = -ri[e * 2 + 1];
+        }
+        max_part[t] = max_anchor;
+    });
+    int max_anchor = 0;
+    for (int v : max_part) max_anchor = std::max(max_anchor, v);
+    return SlideVerdict{first_bad.load(), max_anchor};
+}
+
+bool slide_rows_translation_only(int64_t n, const SlideRows& s, const double* new_pose, const double* r_val, const double* p_val) {
+    static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::atomic<bool> all{true};
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
+        auto one = [&](int64_t i) {
+            if (std::memcmp(new_pose + (size_t)i * 12, I9, sizeof(I9)) != 0) return false;
+            const int nrn = s.nr_new_max > 0 ? s.r_counts[i] : 0, npn = s.np_new_max > 0 ? s.p_counts[i] : 0;
+            for (int e = 0; e < nrn && nrn <= s.nr_new_max; ++e) {
+                const double* v = r_val + ((size_t)i * s.nr_new_max + e) * 5;
+                if (v[2] != 0.0 || v[3] != 0.0 || v[4] != 0.0) return false;
+            }
+            for (int e = 0; e < npn && npn <= s.np_new_max; ++e) {
+                const double* v = p_val + ((size_t)i * s.np_new_max + e) * 18;
+                if (std::memcmp(v, I9, sizeof(I9)) != 0 || v[15] != 0.0 || v[16] != 0.0 || v[17] != 0.0) return false;
+            }
+            return true;
+        };
+        for (int64_t i = lo; i < hi && all.load(std::memory_order_relaxed); ++i)
+            if (!one(i)) { all.store(false); return; }
+    });
+    return all.load();
+}
+
 // The chain scan: every pose-to-pose edge (range or SE3) of every window joins consecutive pose slots.  ordered: edges are also listed
 // in the order of their later pose and priors in pose order (what the lane-per-window and wave-per-window solve kernels walk); the
 // covariance pass takes any order.  single_pairs / se3_pairs: batch_topology's pair counts (only meaningful for chain batches, where

@@ -35,6 +35,23 @@ bool prior_information_translation_only(size_t n_rows, const double* pinfo);
 // window's dropped pose to more than one other pose (a marginal over several poses is not a unary prior: arrowheads are such windows) —
 // several ranges to the same pose, in either direction, are one neighbour
 int check_marginal_drop(const WindowCaps& c, const HostBatch& b, const int32_t* drop);
+// The integer half of the resident slide (loc_window_slide_resident; DESIGN.md §2, "The resident slide") on the host's mirror of an ordered
+// translation-only chain batch: counts [n][4], r_idx [n][nr_max][2], p_idx [n][np_max].  Per window: drop[b] != 0 (drop == nullptr: every
+// window) removes slot 0, the range rows with it as an endpoint and the prior rows on it, renumbers the moving slots, and puts the carried
+// prior (row 0 on slot 0) in front of the kept priors iff a pose-to-pose range joined slot 0 to another pose; then the new slot s, r_counts[b]
+// rows of r_idx [n][nr_new_max][2] and p_counts[b] prior rows on s are appended.
+// apply == false: nothing is written.  bad = 0, or the first check that failed: 1 a window with nv = 0; 2 a new count outside [0, *_new_max];
+// 3 a new range index outside the rule (v0 in {s - 1, s}; v1 in {s - 1, s} or an anchor code of [0, n_anchors); v0 != v1; a pose-to-pose row
+// needs bw_max >= 1; no row on s - 1 alone after a row that names s); 4 / 5 / 6 the slid window exceeds nv_max / nr_max / np_max.
+// apply == true (after a call that returned bad = 0 for the same arguments): the mirror is rewritten in place; max_anchor = the largest
+// anchor code referenced afterwards, as -v1 (0: none).
+struct SlideRows { const int32_t* drop; int32_t nr_new_max; const int32_t* r_counts; const int32_t* r_idx; int32_t np_new_max; const int32_t* p_counts; };
+struct SlideVerdict { int bad; int max_anchor; };
+SlideVerdict slide_indices(const WindowCaps& c, int n_anchors, int64_t n, int32_t* counts, int32_t* r_idx, int32_t* p_idx, const SlideRows& s, bool apply);
+// the value half of that admission: every new row is translation-only — new_pose [n][12] with an identity rotation, r_val [n][nr_new_max][5]
+// without lever arm, p_val [n][np_new_max][18] with an identity measurement rotation and no rotation information.  Counts outside their
+// range read no row (slide_indices reports them).
+bool slide_rows_translation_only(int64_t n, const SlideRows& s, const double* new_pose, const double* r_val, const double* p_val);
 void chain_scan(const WindowCaps& c, const HostBatch& b, bool ordered, bool& chain, bool& single_pairs, bool& se3_pairs);
 unsigned long long hash_structure(const WindowCaps& c, bool has_off1, const HostBatch& b);
 // the largest number of envelope blocks any instance has (envelope_covariance_kernel.hip's profile: sum over the pose slots i of

@@ -254,6 +254,59 @@ class WindowSolver(_lib.Handle):
         check(self.L.loc_window_covariance_resident(self.h, st, C.c_void_p(cov.data_ptr()), C.c_void_p(mask.data_ptr()),
                                                     C.c_void_p(status.data_ptr())))
 
+    # ---- the resident fixed-lag slide (loc_window_slide_resident / loc_window_download_tables; DESIGN.md §2, "The resident slide")
+    def slide_resident(self, new_pose, new_ranges=None, new_priors=None, drop_oldest=None, out=None, stream=None):
+        """Slide every uploaded window on the device (after set_option("resident_slide", 1), upload() and solve_resident()): drop slot 0 and
+        carry its marginal prior, append new_pose [B][12] (R(9), t(3)) with its factors.  new_ranges: (counts int [B], r_idx int
+        [B][nr_new_max][2], r_val [B][nr_new_max][5]) in the NEW window's numbering; new_priors: (counts int [B], p_val [B][np_new_max][18]) on the
+        new pose, or None; drop_oldest: int [B] (0: that window only grows), None: every window drops.  out: (slot, prior, rank, status) torch
+        device tensors (int32 [B], float64 [B][48], int32 [B], int32 [B]), each may be None.  Asynchronous on stream (a torch stream; None: the
+        handle's own); the numpy inputs are read before the call returns.  Plumbing only: the library checks everything."""
+        n = getattr(self, "_resident", 0)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        keep = [np.ascontiguousarray(new_pose, dtype=np.float64).reshape(n, 12)]
+        drop = None
+        if drop_oldest is not None:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(drop_oldest, dtype=np.int32), (n,))))
+            drop = keep[-1].ctypes.data_as(ip)
+        nrn, r_args = 0, (None, None, None)
+        if new_ranges is not None:
+            rc, ri, rv = new_ranges
+            rc = np.ascontiguousarray(rc, dtype=np.int32).reshape(n)
+            ri = np.ascontiguousarray(ri, dtype=np.int32).reshape(n, -1, 2)
+            nrn = ri.shape[1]
+            rv = np.ascontiguousarray(rv, dtype=np.float64).reshape(n, nrn, 5)
+            keep += [rc, ri, rv]
+            r_args = (rc.ctypes.data_as(ip), ri.ctypes.data_as(ip), rv.ctypes.data_as(dp))
+        npn, p_args = 0, (None, None)
+        if new_priors is not None:
+            pc, pv = new_priors
+            pc = np.ascontiguousarray(pc, dtype=np.int32).reshape(n)
+            pv = np.ascontiguousarray(pv, dtype=np.float64).reshape(n, -1, 18)
+            npn = pv.shape[1]
+            keep += [pc, pv]
+            p_args = (pc.ctypes.data_as(ip), pv.ctypes.data_as(dp))
+        outs = []
+        for t, numel in zip(out if out is not None else (None,) * 4, (n, n * 48, n, n)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= numel)
+            outs.append(None if t is None else C.c_void_p(t.data_ptr()))
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_slide_resident(self.h, st, drop, keep[0].ctypes.data_as(dp), nrn, *r_args, npn, *p_args, *outs))
+
+    def download_batch(self):
+        """The resident batch as it stands, as a WindowBatch (loc_window_download_tables): counts, the estimates the next resident solve
+        starts from, every index and value table, and p_info when the handle has a table of full information matrices."""
+        n = getattr(self, "_resident", 0)
+        wb = WindowBatch(n, *self.caps)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        check(self.L.loc_window_download_tables(self.h, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp), wb.r_idx.ctypes.data_as(ip),
+                                                wb.r_val.ctypes.data_as(dp), wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
+                                                wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp), None))
+        pinfo = np.zeros((n, max(self.caps[2], 1), 36))
+        if self.L.loc_window_download_tables(self.h, None, None, None, None, None, None, None, None, pinfo.ctypes.data_as(dp)) == _lib.LOC_OK:
+            wb.p_info = pinfo   # (LOC_ERR_INVALID: the handle has no table)
+        return wb
+
     def covariance_plan(self, wb: WindowBatch):
         """covariance_plan(wb) for this handle's capacities"""
         assert wb.caps == self.caps
@@ -325,7 +378,8 @@ class WindowSolver(_lib.Handle):
 
     def set_option(self, name, value):
         """loc_window_set_option: the kernel-selection switches of this handle ("chain_min_batch", "arrow3", "tree", "wave3", "wave6",
-        "chain3", "zero_copy", "topology_cache", "kernel_events"; "covariance_general": 1 = covariance() / covariance_resident() also serve
+        "chain3", "zero_copy", "topology_cache", "kernel_events"; "resident_slide": 1 = upload() keeps what slide_resident() needs, default 0;
+        "covariance_general": 1 = covariance() / covariance_resident() also serve
         the batches the chain, arrowhead and forest passes decline — every batch with full-information priors among them —, default 0;
         "prior_information_structured": 1 = a translation-only p_info table (dense 3 x 3 blocks on the translations: marginal_prior()'s rows)
         on translation-only chains of <= 64 poses is solved by wave3_lm_kernel and served by the chain 3 x 3 covariance pass, default 0)"""
