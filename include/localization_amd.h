@@ -514,6 +514,44 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
                               int32_t nr_new_max, const int32_t* new_r_counts, const int32_t* new_r_idx, const double* new_r_val,
                               int32_t np_new_max, const int32_t* new_p_counts, const double* new_p_val,
                               void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev);
+/* loc_window_slide_resident with its per-window inputs in DEVICE arrays, and the admission of every window on the device.  Layouts and rules
+ * 1 to 5 are those of loc_window_slide_resident (above; DESIGN.md §2, "The resident slide").  drop_oldest_dev may be NULL: every window drops.
+ * Every output may be NULL; admit_dev int32 [n] gets one LOC_SLIDE_ADMIT_* code per window.
+ * How the inputs are read: the caller's arrays are device memory and the kernels read them directly, in stream order on hip_stream (NULL = the
+ * handle's own stream) — no page-locked copy, no hipMemcpy.  The caller keeps them alive and unchanged until the stream has passed the call,
+ * orders its own writes to them before the call (the handle's stream does not wait for any other), and they may not alias the handle's
+ * tables (loc_window_poses_device() among them) or the outputs.  The call makes no pass over per-window data on the host and does not
+ * synchronise; the exceptions are the one-time allocations loc_window_slide_resident also makes (the marginal pass's block at a handle's first
+ * slide; a new table of full information matrices, after waiting for the last resident launch).
+ * Checked on the host, with nothing launched or changed, exactly as by loc_window_slide_resident — LOC_ERR_INVALID: option "resident_slide"
+ * was 0 at upload time; nothing uploaded; no resident solve since the upload; a table of full matrices that describes fewer windows than are
+ * resident; a NULL new_pose_dev, a negative capacity or a NULL array under a positive one.  LOC_ERR_UNSUPPORTED: the resident batch's verdict is
+ * not LOC_WINDOW_KERNEL_CHAIN3; endpoint-1 lever arms; a table with rotation entries.
+ * Checked on the device, per window, by the wave that slides it: admit[b] = LOC_SLIDE_ADMIT_OK, or the first rule the window breaks.  THERE IS NO
+ * BATCH-WIDE REFUSAL BEFORE LAUNCH: a refused window is left exactly as it was (counts, every table row, poses, the next solve's input
+ * estimates) and reports slot -1, 48 zeros, rank 0 and status LOC_ERR_INVALID (codes 1 to 6) or LOC_ERR_UNSUPPORTED (code 7), while the other
+ * windows of the batch slide normally and report what loc_window_slide_resident reports.  A first slide that creates the table (rule 5)
+ * creates it for the refused windows as well: their rows become diag(p_val[12..17]).  Anchor codes are admitted against the anchor table's
+ * size at call time.  The verdict of a window does not depend on its position in the batch.
+ * Afterwards the handle is in the state loc_window_slide_resident leaves, except that its host mirror of counts, r_idx and p_idx is stale:
+ * the next call that needs it (loc_window_slide_resident, loc_window_joint_covariance_resident with pairs, loc_window_set_anchors) first waits
+ * for the resident work and fetches it.  loc_window_solve_resident, loc_window_covariance_resident, loc_window_download and
+ * loc_window_download_tables do not need it, so K cycles of (solve, slide) queue on a stream without a host round trip.
+ * loc_window_last_covariance_ms reports the two launches. */
+enum {
+    LOC_SLIDE_ADMIT_OK = 0,
+    LOC_SLIDE_ADMIT_NO_POSES = 1,         /* the window has nv = 0 */
+    LOC_SLIDE_ADMIT_COUNT = 2,            /* a new count outside [0, *_new_max] */
+    LOC_SLIDE_ADMIT_INDEX = 3,            /* a new range index outside rule 3 */
+    LOC_SLIDE_ADMIT_NV_MAX = 4,           /* the slid window exceeds nv_max */
+    LOC_SLIDE_ADMIT_NR_MAX = 5,           /* ... nr_max */
+    LOC_SLIDE_ADMIT_NP_MAX = 6,           /* ... np_max */
+    LOC_SLIDE_ADMIT_NOT_TRANSLATION = 7   /* a new row that is not translation-only: a non-identity rotation, a lever arm, rotation information */
+};
+int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
+                                  int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
+                                  int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
+                                  void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev, void* admit_dev);
 /* The resident batch as it stands (a checkpoint; host arrays in loc_window_upload's layouts, n = the resident batch's windows; any pointer may
  * be NULL).  poses: the estimates the next resident solve starts from.  pinfo double [n][np_max][36]: the table of full information matrices;
  * LOC_ERR_INVALID when the handle has none.  Synchronous (waits for the last resident launch). */

@@ -101,6 +101,7 @@ struct loc_window {
     // page-locked copy and as the device block the kernel reads, grown on demand, as the pair tables are; the marginal pass's drop table
     // (zeros) and results for B windows
     bool opt_slide = false, mirror_valid = false;
+    bool mirror_stale = false;   // loc_window_slide_resident_dev has slid the device tables since the mirror was written (refresh_mirror)
     std::vector<int32_t> mir_ridx, mir_pidx;
     char *h_slide = nullptr, *d_slide = nullptr;
     size_t slide_cap = 0;
@@ -246,6 +247,29 @@ static int wait_resident(loc_window* w) {
     return LOC_OK;
 }
 
+// After loc_window_slide_resident_dev the device holds the only copy of the slid counts and index tables.  Whoever reads the host's mirror
+// (res_counts, mir_ridx, mir_pidx, resident_min_anchors) asks here first: waits for the resident work, fetches counts, r_idx and p_idx,
+// recomputes the largest anchor referenced.  Nothing to do (and no wait) while the mirror is current.
+static int refresh_mirror(loc_window* w) {
+    if (!w->mirror_stale) return LOC_OK;
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = wait_resident(w)) return rc;
+    const locamd::WindowCaps& c = w->caps;
+    const size_t N = (size_t)w->n_resident;
+    LOC_HIP(hipMemcpy(w->res_counts.data(), w->dev.t[kCounts], N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (c.nr_max) LOC_HIP(hipMemcpy(w->mir_ridx.data(), w->dev.t[locamd::kRIdx], N * c.nr_max * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (c.np_max) LOC_HIP(hipMemcpy(w->mir_pidx.data(), w->dev.t[locamd::kPIdx], N * c.np_max * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int max_anchor = 0;   // (loc_window_upload's scan: v1 = -1 - anchor)
+    for (size_t i = 0; i < N; ++i)
+        for (int e = 0; e < w->res_counts[i * 4 + 1]; ++e) {
+            const int32_t v1 = w->mir_ridx[(i * c.nr_max + e) * 2 + 1];
+            if (v1 < 0 && -v1 > max_anchor) max_anchor = -v1;
+        }
+    w->resident_min_anchors = max_anchor;
+    w->mirror_stale = false;
+    return LOC_OK;
+}
+
 // the device copy of the anchor table
 static int upload_anchors(loc_window* w, int32_t n_anchors, const double* anchors) {
     LOC_HIP(hipSetDevice(w->device));
@@ -269,6 +293,7 @@ static int flush_anchors(loc_window* w) {
 
 int loc_window_set_anchors(loc_window* w, int32_t n_anchors, const double* anchors) {
     if (!w || n_anchors < 0 || (n_anchors > 0 && !anchors)) return locamd_fail(LOC_ERR_INVALID, "set_anchors");
+    if (int rc = refresh_mirror(w)) return rc;   // (a slide from device arrays may have introduced anchors the host has not seen)
     if (w->n_resident > 0 && n_anchors < w->resident_min_anchors)
         return locamd_fail(LOC_ERR_INVALID, "set_anchors: the resident batch references more anchors than the new table holds (upload again first)");
     if (w->B <= 4) {
@@ -366,7 +391,7 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
 // the resident batch as uploaded: the initial estimates in the place of the optimised ones
 static locamd::DeviceTables uploaded_tables(const loc_window* w) { locamd::DeviceTables d = w->dev; d.t[kPoses] = w->d_poses_in; return d; }
 // the device arrays hold no resident batch any more (the resident calls return LOC_ERR_INVALID until the next loc_window_upload completes)
-static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_skip = false; w->resident_min_anchors = 0; w->mirror_valid = false; }
+static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_skip = false; w->resident_min_anchors = 0; w->mirror_valid = false; w->mirror_stale = false; }
 
 static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const locamd::WindowArgs& a, hipStream_t st, int kind) {
     locamd::WinAux& A = S.aux;
@@ -882,6 +907,8 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
     if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
     if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
     const locamd::PairTables pt{npair_max, pair_counts_host, pairs_host};
+    if (npair_max > 0)   // (the pair check reads every window's nv; a call without pairs reads no count and does not wait)
+        if (int rc = refresh_mirror(w)) return rc;
     if (int rc = validate_pairs(w->n_resident, w->res_counts.data(), pt, cross_dev)) return rc;
     const bool joint = npair_max > 0;
     LOC_HIP(hipSetDevice(w->device));
@@ -985,22 +1012,74 @@ int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, con
 }
 
 // ---- the resident slide (window_slide_kernel.hip; DESIGN.md §2, "The resident slide") ------------------------------------------------------------
-int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* drop_oldest, const double* new_pose,
-                              int32_t nr_new_max, const int32_t* new_r_counts, const int32_t* new_r_idx, const double* new_r_val,
-                              int32_t np_new_max, const int32_t* new_p_counts, const double* new_p_val,
-                              void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev) {
+// what both entries check without looking at a window; nothing is launched or changed on a refusal
+static int slide_check_handle(const loc_window* w, bool arrays_ok) {
     if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
     if (!w->mirror_valid) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded");
     if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: no resident solve has run since the upload");
-    if (!new_pose || nr_new_max < 0 || np_new_max < 0 || (nr_new_max > 0 && (!new_r_counts || !new_r_idx || !new_r_val)) ||
-        (np_new_max > 0 && (!new_p_counts || !new_p_val)))
-        return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: new pose and new row arrays");
+    if (!arrays_ok) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: new pose and new row arrays");
     if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
     // (a verdict taken with the priors' diagonals skipped holds only while structured_pinfo does: loc_window_solve_resident's rule)
     if (w->resident_topology != LOC_WINDOW_KERNEL_CHAIN3 || (w->resident_skip && !locamd::structured_pinfo(w->opt)))
         return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the resident batch is not an ordered translation-only chain batch");
     if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
     if (w->opt.has_pinfo && !w->opt.pinfo_translation) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the table of full information matrices has rotation entries");
+    return LOC_OK;
+}
+// the one-time allocations of a slide: the marginal pass's block for B windows, [zeros | slot | rank | status | prior | grad | shift], and the
+// table a first slide creates (a launch under an earlier table may still read it: that one waits)
+struct SlideBlock { size_t mi, prior, grad, shift, end; bool fresh; };
+static int slide_allocate(loc_window* w, bool densify, SlideBlock& m) {
+    const size_t Bw = (size_t)w->B;
+    m.mi = (Bw * sizeof(int32_t) + 15) & ~(size_t)15;
+    m.prior = 4 * m.mi; m.grad = m.prior + Bw * 48 * sizeof(double); m.shift = m.grad + Bw * 6 * sizeof(double); m.end = m.shift + Bw * 6 * sizeof(double);
+    m.fresh = !w->d_slide_mp;
+    if (m.fresh) LOC_HIP(hipMalloc((void**)&w->d_slide_mp, m.end));
+    if (densify) {
+        if (int rc = wait_resident(w)) return rc;
+        if (!w->d_pinfo) LOC_HIP(hipMalloc((void**)&w->d_pinfo, Bw * w->caps.np_max * 36 * sizeof(double)));
+    }
+    return LOC_OK;
+}
+// launch 1: the marginal of slot 0 at the solved poses, marginal_prior_kernel itself (a handle without a table: p_val's diagonals, as
+// loc_window_marginal_prior_host reads them); launch 2: the re-pack — sa holds the call's inputs and outputs; admitting: the twin whose waves
+// admit their own windows.  Then the handle's state but the mirror: what loc_window_upload of the slid tables, with the table set, would leave
+static int slide_launches(loc_window* w, hipStream_t st, locamd::SlideArgs& sa, bool densify, const SlideBlock& m, bool admitting, int32_t* admit) {
+    const locamd::WindowCaps& c = w->caps;
+    const int64_t n = w->n_resident;
+    char* mp = w->d_slide_mp;
+    if (m.fresh) LOC_HIP(hipMemsetAsync(mp, 0, m.mi, st));                                                        // the marginal pass's drop table: slot 0 of every window
+    if (densify) LOC_HIP(hipMemsetAsync(w->d_pinfo, 0, (size_t)w->B * c.np_max * 36 * sizeof(double), st));     // (rows beyond the counts: zeros, not what the allocation held)
+    const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, nullptr);
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)mp, (int32_t*)(mp + m.mi), (double*)(mp + m.prior), (double*)(mp + m.grad), (double*)(mp + m.shift),
+                                                        (int32_t*)(mp + 2 * m.mi), (int32_t*)(mp + 3 * m.mi), st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
+    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
+    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
+    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal]; sa.p_info = c.np_max > 0 ? w->d_pinfo : nullptr;
+    sa.m_slot = (const int32_t*)(mp + m.mi); sa.m_prior = (const double*)(mp + m.prior); sa.m_rank = (const int32_t*)(mp + 2 * m.mi); sa.m_status = (const int32_t*)(mp + 3 * m.mi);
+    sa.B = (int)n; sa.caps = c;
+    e = admitting ? locamd::launch_window_slide_dev(sa, w->n_anchors, admit, densify, st) : locamd::launch_window_slide(sa, densify, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipEventRecord(w->resident_done, st));
+    w->resident_inflight = true;
+    w->cov_pending = true;
+    if (densify) { w->opt.has_pinfo = true; w->opt.pinfo_translation = true; w->n_pinfo = n; }
+    w->resident_skip = locamd::structured_pinfo(w->opt);
+    w->resident_cov = CovKind::Chain3;   // (loc_window_upload's verdict for this topology; a call the switches do not admit classifies it again)
+    return LOC_OK;
+}
+
+int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* drop_oldest, const double* new_pose,
+                              int32_t nr_new_max, const int32_t* new_r_counts, const int32_t* new_r_idx, const double* new_r_val,
+                              int32_t np_new_max, const int32_t* new_p_counts, const double* new_p_val,
+                              void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev) {
+    if (int rc = slide_check_handle(w, new_pose && nr_new_max >= 0 && np_new_max >= 0 && (nr_new_max == 0 || (new_r_counts && new_r_idx && new_r_val)) &&
+                                           (np_new_max == 0 || (new_p_counts && new_p_val))))
+        return rc;
+    if (int rc = refresh_mirror(w)) return rc;   // (the two entries may alternate on one handle)
     const locamd::WindowCaps& c = w->caps;
     const int64_t n = w->n_resident;
     const size_t N = (size_t)n;
@@ -1029,17 +1108,9 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
         LOC_HIP(hipHostMalloc((void**)&w->h_slide, at[7], hipHostMallocDefault));
         LOC_HIP(locamd::grow_buffers(w->slide_cap, at[7], {{w->d_slide, at[7]}}));
     }
-    // the marginal pass's block for B windows: [zeros | slot | rank | status | prior | grad | shift]
-    const size_t Bw = (size_t)w->B, mi = (Bw * sizeof(int32_t) + 15) & ~(size_t)15;
-    const size_t mp_prior = 4 * mi, mp_grad = mp_prior + Bw * 48 * sizeof(double), mp_shift = mp_grad + Bw * 6 * sizeof(double), mp_end = mp_shift + Bw * 6 * sizeof(double);
-    const bool new_mp = !w->d_slide_mp;
-    if (new_mp) LOC_HIP(hipMalloc((void**)&w->d_slide_mp, mp_end));
     const bool densify = !w->opt.has_pinfo && c.np_max > 0;
-    const size_t pinfo_bytes = Bw * c.np_max * 36 * sizeof(double);
-    if (densify) {
-        if (int rc = wait_resident(w)) return rc;   // (a launch under an earlier table may still read it)
-        if (!w->d_pinfo) LOC_HIP(hipMalloc((void**)&w->d_pinfo, pinfo_bytes));
-    }
+    SlideBlock m;
+    if (int rc = slide_allocate(w, densify, m)) return rc;
     if (!w->slide_copied) LOC_HIP(hipEventCreateWithFlags(&w->slide_copied, hipEventDisableTiming));
     if (w->slide_inflight) { LOC_HIP(hipEventSynchronize(w->slide_copied)); w->slide_inflight = false; }
     {   // the caller's arrays are read here and never after the call returns
@@ -1052,41 +1123,44 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
             if (piece[k] && src[k]) std::memcpy(h + at[k], src[k], piece[k]);
     }
     if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    if (new_mp) LOC_HIP(hipMemsetAsync(w->d_slide_mp, 0, mi, st));                  // the marginal pass's drop table: slot 0 of every window
-    if (densify) LOC_HIP(hipMemsetAsync(w->d_pinfo, 0, pinfo_bytes, st));           // (rows beyond the counts: zeros, not what the allocation held)
     LOC_HIP(hipMemcpyAsync(w->d_slide, w->h_slide, at[7], hipMemcpyHostToDevice, st));
     LOC_HIP(hipEventRecord(w->slide_copied, st));
     w->slide_inflight = true;
-    // launch 1: the marginal of slot 0 at the solved poses, marginal_prior_kernel itself (a handle without a table: p_val's diagonals, as
-    // loc_window_marginal_prior_host reads them); launch 2: the re-pack
-    const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, nullptr);
-    char* mp = w->d_slide_mp;
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)mp, (int32_t*)(mp + mi), (double*)(mp + mp_prior), (double*)(mp + mp_grad), (double*)(mp + mp_shift),
-                                                        (int32_t*)(mp + 2 * mi), (int32_t*)(mp + 3 * mi), st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
     locamd::SlideArgs sa{};
-    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
-    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
-    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal]; sa.p_info = c.np_max > 0 ? w->d_pinfo : nullptr;
     const char* d = w->d_slide;
     sa.drop = (const int32_t*)(d + at[0]); sa.new_r_counts = (const int32_t*)(d + at[1]); sa.new_p_counts = (const int32_t*)(d + at[2]);
     sa.new_r_idx = (const int32_t*)(d + at[3]); sa.new_pose = (const double*)(d + at[4]); sa.new_r_val = (const double*)(d + at[5]); sa.new_p_val = (const double*)(d + at[6]);
-    sa.m_slot = (const int32_t*)(mp + mi); sa.m_prior = (const double*)(mp + mp_prior); sa.m_rank = (const int32_t*)(mp + 2 * mi); sa.m_status = (const int32_t*)(mp + 3 * mi);
     sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
-    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max; sa.B = (int)n; sa.caps = c;
-    e = locamd::launch_window_slide(sa, densify, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    LOC_HIP(hipEventRecord(w->resident_done, st));
-    w->resident_inflight = true;
-    w->cov_pending = true;
-    // the handle's state: what loc_window_upload of the slid tables, with the table set, would leave
-    const locamd::SlideVerdict v = locamd::slide_indices(c, w->n_anchors, n, w->res_counts.data(), w->mir_ridx.data(), w->mir_pidx.data(), rows, true);
-    w->resident_min_anchors = v.max_anchor;
-    if (densify) { w->opt.has_pinfo = true; w->opt.pinfo_translation = true; w->n_pinfo = n; }
-    w->resident_skip = locamd::structured_pinfo(w->opt);
-    w->resident_cov = CovKind::Chain3;   // (loc_window_upload's verdict for this topology; a call the switches do not admit classifies it again)
+    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
+    if (int rc = slide_launches(w, st, sa, densify, m, false, nullptr)) return rc;
+    w->resident_min_anchors = locamd::slide_indices(c, w->n_anchors, n, w->res_counts.data(), w->mir_ridx.data(), w->mir_pidx.data(), rows, true).max_anchor;
+    return LOC_OK;
+}
+
+// the twin that takes the call's per-window inputs from DEVICE arrays: no pass over per-window data on the host, no copy, no synchronisation
+// (but the one-time allocations slide_allocate makes); each wave admits its own window (slide_admit.h) and the host's mirror goes stale
+int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
+                                  int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
+                                  int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
+                                  void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev, void* admit_dev) {
+    if (int rc = slide_check_handle(w, new_pose_dev && nr_new_max >= 0 && np_new_max >= 0 && (nr_new_max == 0 || (new_r_counts_dev && new_r_idx_dev && new_r_val_dev)) &&
+                                           (np_new_max == 0 || (new_p_counts_dev && new_p_val_dev))))
+        return rc;
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    const bool densify = !w->opt.has_pinfo && w->caps.np_max > 0;
+    SlideBlock m;
+    if (int rc = slide_allocate(w, densify, m)) return rc;
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    locamd::SlideArgs sa{};
+    sa.drop = (const int32_t*)drop_oldest_dev; sa.new_pose = (const double*)new_pose_dev;
+    sa.new_r_counts = (const int32_t*)new_r_counts_dev; sa.new_r_idx = (const int32_t*)new_r_idx_dev; sa.new_r_val = (const double*)new_r_val_dev;
+    sa.new_p_counts = (const int32_t*)new_p_counts_dev; sa.new_p_val = (const double*)new_p_val_dev;
+    sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
+    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
+    if (int rc = slide_launches(w, st, sa, densify, m, true, (int32_t*)admit_dev)) return rc;
+    w->mirror_stale = true;   // (refresh_mirror: the next reader of the mirror fetches it)
     return LOC_OK;
 }
 

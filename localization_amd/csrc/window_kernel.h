@@ -182,6 +182,11 @@ struct SlideArgs {
 };
 // densify: p_info is a NEW table (the handle had none): every row but the carried one becomes diag(p_val[12..17])
 hipError_t launch_window_slide(const SlideArgs& s, bool densify, hipStream_t stream);
+// the twin of loc_window_slide_resident_dev: the host has admitted NOTHING.  drop (may be nullptr: every window drops), new_pose and the new
+// rows are the caller's device arrays; each wave admits its own window against slide_admit.h's rule (new anchor codes against n_anchors),
+// writes admit[b] (may be nullptr) and either re-packs as above or reports slot -1, 48 zeros, rank 0, status LOC_ERR_INVALID (codes 1 .. 6) /
+// LOC_ERR_UNSUPPORTED (code 7) and leaves the window as it was (densify: its table rows become diag(p_val[12..17]) all the same)
+hipError_t launch_window_slide_dev(const SlideArgs& s, int n_anchors, int32_t* admit, bool densify, hipStream_t stream);
 
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);

@@ -1,7 +1,8 @@
 // gfx950 (MI355X / CDNA4): the resident fixed-lag slide (loc_window_slide_resident; DESIGN.md §2, "The resident slide"): drop slot 0 of every
 // uploaded window, put the marginal prior it leaves in front of the kept priors, append the newest pose and its factors — in the device
 // tables the batch lives in.  window_structure.cpp's slide_indices applies the same integer rule to the host's mirror and has admitted
-// every count and index before this runs.
+// every count and index before this runs — or, behind loc_window_slide_resident_dev, nobody has: the ARGS = SlideDevArgs twin reads the
+// caller's device arrays and each wave admits its own window first (slide_admit.h's rule), leaving a refused window untouched.
 //
 // Two launches.  The marginal of slot 0 is marginal_prior_kernel ITSELF (launch_window_marginal_prior with a drop table of zeros, into a
 // scratch block of the handle): the one statement of that arithmetic, so loc_window_marginal_prior_host and the slide return the same bits,
@@ -17,6 +18,9 @@
 // argument holds mirrored (a step stores to rows above the ones the later, lower steps load).
 // No atomics and no dependence on the window's position in the batch: the same bits wherever the window sits.  Plain vector loads and
 // stores only.
+#include <type_traits>
+
+#include "slide_admit.h"
 #include "window_device.h"
 
 namespace locamd {
@@ -61,15 +65,108 @@ __device__ __forceinline__ void slide_shift_up(double* t, int n, int lane) {
     }
 }
 
+// the twin's arguments: the re-pack's, and what the admission needs on top (all of s's input arrays are then the CALLER's device memory)
+struct SlideDevArgs : SlideArgs {
+    int n_anchors;    // the anchor table's size at call time: new anchor codes are admitted against it
+    int32_t* admit;   // [B] the admission code of every window, may be nullptr
+};
+
+// The admission of ONE window by its wave (loc_window_slide_resident_dev): slide_admit.h's rule, rows over lanes, "any row" as a ballot.  Every
+// lane returns the same code.  Reads the window's own index tables (valid by induction: the upload validated them and every slide either
+// admits a window or leaves it alone) and the caller's new rows — never a row beyond a count, and no row before both counts are in range.
+__device__ __forceinline__ int slide_admit_wave(const SlideArgs& s, int n_anchors, long long b, int lane, int nv, int nr, int np, bool drop, int nrn, int npn) {
+    const WindowCaps& cp = s.caps;
+    if (nv <= 0) return kSlideAdmitNoPoses;
+    if (nrn < 0 || nrn > s.nr_new_max || npn < 0 || npn > s.np_new_max) return kSlideAdmitCount;
+    const int sl = nv - (drop ? 1 : 0);   // the new slot
+    const u64 below = (1ull << lane) - 1;
+    bool named = false, bad = false;      // a row of an earlier step names the new slot; a row so far breaks rule 3
+    for (int e0 = 0; e0 < nrn; e0 += 64) {
+        const int e = e0 + lane;
+        const bool in = e < nrn;
+        int v0 = 0, v1 = 0;
+        if (in) { const int32_t* xi = s.new_r_idx + ((size_t)b * s.nr_new_max + e) * 2; v0 = xi[0]; v1 = xi[1]; }
+        const bool ok0 = v0 == sl || (v0 == sl - 1 && v0 >= 0);
+        const bool ok1 = v1 < 0 ? v1 >= -n_anchors : ((v1 == sl || v1 == sl - 1) && v1 != v0 && cp.bw_max >= 1);
+        const bool names = in && (v0 == sl || v1 == sl);
+        const u64 mn = __ballot(names);
+        const bool after = named || (mn & below) != 0;   // a row before this one names s: this one has to as well
+        bad = bad || __ballot(in && (!ok0 || !ok1 || (after && !names))) != 0;
+        named = named || mn != 0;
+    }
+    if (bad) return kSlideAdmitIndex;
+    // what the drop leaves: the kept rows, and whether a pose-to-pose range joined slot 0 to another pose (the marginal's slot >= 0)
+    int r_kept = nr, p_kept = np, carried = 0;
+    if (drop) {
+        r_kept = 0; p_kept = 0;
+        const int32_t* ri = s.r_idx + (size_t)b * cp.nr_max * 2;
+        const int32_t* pi = s.p_idx + (size_t)b * cp.np_max;
+        for (int e0 = 0; e0 < nr; e0 += 64) {
+            const int e = e0 + lane;
+            int v0 = 1, v1 = 1;
+            if (e < nr) { v0 = ri[e * 2]; v1 = ri[e * 2 + 1]; }
+            const bool gone = v0 == 0 || v1 == 0;
+            r_kept += __popcll(__ballot(e < nr && !gone));
+            if (__ballot(gone && v1 >= 0) != 0) carried = 1;
+        }
+        for (int e0 = 0; e0 < np; e0 += 64) {
+            const int e = e0 + lane;
+            p_kept += __popcll(__ballot(e < np && pi[e] != 0));
+        }
+    }
+    if (sl + 1 > cp.nv_max) return kSlideAdmitNvMax;
+    if (r_kept + nrn > cp.nr_max) return kSlideAdmitNrMax;
+    if (carried + p_kept + npn > cp.np_max) return kSlideAdmitNpMax;
+    // the value half: identity rotations by their bit pattern, no lever arm, no rotation information
+    bool other = false;
+    if (lane < 9) other = (u64)__double_as_longlong(s.new_pose[(size_t)b * 12 + lane]) != (lane % 4 == 0 ? 0x3FF0000000000000ull : 0ull);
+    for (int j = lane; j < nrn; j += 64) {
+        const double* v = s.new_r_val + ((size_t)b * s.nr_new_max + j) * 5;
+        other = other || v[2] != 0.0 || v[3] != 0.0 || v[4] != 0.0;
+    }
+    for (int j = lane; j < npn; j += 64) {
+        const double* v = s.new_p_val + ((size_t)b * s.np_new_max + j) * 18;
+        other = other || !slide_identity_bits(v) || v[15] != 0.0 || v[16] != 0.0 || v[17] != 0.0;
+    }
+    if (__ballot(other) != 0) return kSlideAdmitNotTranslation;
+    return kSlideAdmitOk;
+}
+
 // DENSIFY: the handle had no table of full information matrices so far — p_info is new, and every row it gets is diag(p_val[12..17]) but
-// the carried one
-template <bool DENSIFY>
-__global__ void __launch_bounds__(64) window_slide_kernel(const SlideArgs s) {
+// the carried one.  ARGS = SlideDevArgs (ADMIT, loc_window_slide_resident_dev): the host has admitted nothing — the wave first admits its window, then either
+// re-packs it exactly as below or writes the refusal's outputs and leaves every table row, pose and count as it was; s.drop may be nullptr
+// (every window drops).  Without ADMIT the host has admitted every window and the code is what it was before the parameter existed.
+template <bool DENSIFY, class ARGS>
+__global__ void __launch_bounds__(64) window_slide_kernel(const ARGS s) {
+    constexpr bool ADMIT = std::is_same<ARGS, SlideDevArgs>::value;
     const int lane = threadIdx.x;
     const long long b = blockIdx.x;
     const WindowCaps& cp = s.caps;
     const int nv = s.counts[b * 4], nr = s.counts[b * 4 + 1], np = s.counts[b * 4 + 2];
-    const bool drop = s.drop[b] != 0;
+    const bool drop = ADMIT ? (s.drop == nullptr || s.drop[b] != 0) : s.drop[b] != 0;
+    int nrn_in = 0, npn_in = 0;
+    if constexpr (ADMIT) {
+        nrn_in = s.nr_new_max > 0 ? s.new_r_counts[b] : 0; npn_in = s.np_new_max > 0 ? s.new_p_counts[b] : 0;
+        const int code = slide_admit_wave(s, s.n_anchors, b, lane, nv, nr, np, drop, nrn_in, npn_in);
+        if (lane == 0 && s.admit) s.admit[b] = code;
+        if (code != kSlideAdmitOk) {   // (the same code in every lane: the whole wave leaves)
+            if (s.prior && lane < 48) s.prior[(size_t)b * 48 + lane] = 0.0;
+            if (lane == 0) {
+                if (s.slot) s.slot[b] = -1;
+                if (s.rank) s.rank[b] = 0;
+                if (s.status) s.status[b] = code == kSlideAdmitNotTranslation ? -5 : -1;   // LOC_ERR_UNSUPPORTED / LOC_ERR_INVALID
+            }
+            if (DENSIFY) {   // the handle has a table from now on, for this window as well: its rows are the diagonals p_val holds
+                const double* pv = s.p_val + (size_t)b * cp.np_max * 18;
+                double* pw = s.p_info + (size_t)b * cp.np_max * 36;
+                for (int e = lane; e < np; e += 64) {
+#pragma unroll
+                    for (int k = 0; k < 36; ++k) pw[(size_t)e * 36 + k] = (k % 7 == 0) ? pv[(size_t)e * 18 + 12 + k / 7] : 0.0;
+                }
+            }
+            return;
+        }
+    }
     const int mslot = drop ? s.m_slot[b] : -1;     // the marginal's neighbour: slot 1 of an ordered chain, or none
     const int ins = mslot >= 0 ? 1 : 0;            // the carried prior takes row 0
     // lanes 0 .. 47: the marginal's row (a window that only grows reports zeros)
@@ -163,7 +260,7 @@ __global__ void __launch_bounds__(64) window_slide_kernel(const SlideArgs s) {
     }
 
     // ---- the new rows, last ----------------------------------------------------------------------------------------------------------------------
-    const int nrn = s.nr_new_max > 0 ? s.new_r_counts[b] : 0, npn = s.np_new_max > 0 ? s.new_p_counts[b] : 0;
+    const int nrn = ADMIT ? nrn_in : (s.nr_new_max > 0 ? s.new_r_counts[b] : 0), npn = ADMIT ? npn_in : (s.np_new_max > 0 ? s.new_p_counts[b] : 0);
     for (int j = lane; j < nrn; j += 64) {
         const int32_t* xi = s.new_r_idx + ((size_t)b * s.nr_new_max + j) * 2;
         const double* xv = s.new_r_val + ((size_t)b * s.nr_new_max + j) * 5;
@@ -199,8 +296,20 @@ __global__ void __launch_bounds__(64) window_slide_kernel(const SlideArgs s) {
 hipError_t launch_window_slide(const SlideArgs& s, bool densify, hipStream_t stream) {
     if (s.B <= 0) return hipSuccess;
     if (!s.counts || !s.poses || !s.poses_in || !s.drop || !s.new_pose || !s.m_slot || !s.m_prior || !s.m_rank || !s.m_status) return hipErrorInvalidValue;
-    if (densify) hipLaunchKernelGGL((window_slide_kernel<true>), dim3((unsigned)s.B), dim3(64), 0, stream, s);
-    else hipLaunchKernelGGL((window_slide_kernel<false>), dim3((unsigned)s.B), dim3(64), 0, stream, s);
+    if (densify) hipLaunchKernelGGL((window_slide_kernel<true, SlideArgs>), dim3((unsigned)s.B), dim3(64), 0, stream, s);
+    else hipLaunchKernelGGL((window_slide_kernel<false, SlideArgs>), dim3((unsigned)s.B), dim3(64), 0, stream, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_slide_dev(const SlideArgs& s, int n_anchors, int32_t* admit, bool densify, hipStream_t stream) {
+    if (s.B <= 0) return hipSuccess;
+    if (!s.counts || !s.poses || !s.poses_in || !s.new_pose || !s.m_slot || !s.m_prior || !s.m_rank || !s.m_status) return hipErrorInvalidValue;
+    if ((s.nr_new_max > 0 && (!s.new_r_counts || !s.new_r_idx || !s.new_r_val)) || (s.np_new_max > 0 && (!s.new_p_counts || !s.new_p_val))) return hipErrorInvalidValue;
+    if ((s.caps.nr_max > 0 && (!s.r_idx || !s.r_val)) || (s.caps.np_max > 0 && (!s.p_idx || !s.p_val || !s.p_info))) return hipErrorInvalidValue;
+    SlideDevArgs d;
+    static_cast<SlideArgs&>(d) = s; d.n_anchors = n_anchors; d.admit = admit;
+    if (densify) hipLaunchKernelGGL((window_slide_kernel<true, SlideDevArgs>), dim3((unsigned)s.B), dim3(64), 0, stream, d);
+    else hipLaunchKernelGGL((window_slide_kernel<false, SlideDevArgs>), dim3((unsigned)s.B), dim3(64), 0, stream, d);
     return hipGetLastError();
 }
 
