@@ -1,5 +1,5 @@
-// Host-side plumbing shared by the C ABI files (capi*.cpp, frontend.cpp): error reporting, grow-on-demand device buffers, the per-launch
-// HIP-event timer and the chunked three-stream pipeline of the snapshot and fusion solvers' host paths.  Never included by device code.
+// Host-side plumbing shared by the C ABI files (capi*.cpp, frontend.cpp): error reporting, grow-on-demand device buffers and staging pairs, the
+// per-launch HIP-event timer and the chunked three-stream pipeline of the snapshot and fusion solvers' host paths.  Never included by device code.
 #pragma once
 #include "../../include/localization_amd.h"
 
@@ -41,6 +41,43 @@ inline hipError_t grow_buffers(size_t& cap, size_t need, std::initializer_list<W
     cap = need;
     return hipSuccess;
 }
+
+// ---- a page-locked block and its device twin, grown on demand ------------------------------------------------------------------------------
+// How a call's small host arrays reach a kernel on the caller's stream: into the page-locked half before the call returns, from there to
+// the device half in stream order.
+struct StagingPair {
+    char *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+    hipEvent_t copied = nullptr;   // the device half has the page-locked half's content
+    bool inflight = false;
+
+    // Both halves for `bytes`; no-op while they fit.  The caller has waited for whatever may still read the device half.
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (h) (void)hipHostFree(h);
+        h = nullptr; cap = 0; inflight = false;   // (capacity 0: grow_buffers replaces the device half with the host half, and a failure leaves none)
+        if (hipError_t e = hipHostMalloc((void**)&h, bytes, hipHostMallocDefault); e != hipSuccess) return e;
+        return grow_buffers(cap, bytes, {{d, bytes}});
+    }
+    // the page-locked half, once the previous send() has left it
+    hipError_t host(char*& out) {
+        hipError_t e = copied ? hipSuccess : hipEventCreateWithFlags(&copied, hipEventDisableTiming);
+        if (e == hipSuccess && inflight && (e = hipEventSynchronize(copied)) == hipSuccess) inflight = false;
+        out = h;
+        return e;
+    }
+    // the first `bytes` of it to the device half, on st
+    hipError_t send(size_t bytes, hipStream_t st) {
+        hipError_t e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && (e = hipEventRecord(copied, st)) == hipSuccess) inflight = true;
+        return e;
+    }
+    void destroy() {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        if (copied) (void)hipEventDestroy(copied);
+    }
+};
 
 // ---- HIP-event timing of launches (loc_*_timing_begin / _end) -----------------------------------------------------------
 struct LaunchTimer {

@@ -19,6 +19,25 @@ using locamd::kPoses;
 using locamd::kCounts;
 using locamd::CovKind;
 
+// What the handle knows about the batch loc_window_upload left in the device arrays.  `Resident{}` is "none" (drop_resident): the resident
+// calls return LOC_ERR_INVALID until the next upload completes, and nothing reads another field while n is 0.
+struct Resident {
+    long long n = 0;
+    int topology = LOC_WINDOW_KERNEL_GENERAL;   // LOC_WINDOW_KERNEL_* the batch qualifies for by its structure (the batch-size threshold is applied per solve)
+    bool skip = false;              // ... a verdict taken with the priors' diagonals skipped (a structured table was set): it holds while structured_pinfo(opt) does
+    int min_anchors = 0;            // anchors the batch references (loc_window_set_anchors may not shrink below it)
+    bool solved = false;            // a resident solve has run since the upload (loc_window_download has something to fetch)
+    CovKind cov = CovKind::None;    // the batch's covariance pass; Unclassified: the first covariance call finds out
+    long long env_switches = 0;     // cov_switches() when it was classified: a change of the switches the structured tests read classifies an Envelope batch again
+    // joint covariance calls: the counts as uploaded (the pair check needs every window's nv) and, once the envelope pass holds the batch,
+    // its pose-to-pose index tables (the pairs enlarge the envelope)
+    std::vector<int32_t> counts, ridx, sidx;
+    // the resident slide: with option "resident_slide" the upload keeps the batch's index tables next to counts (the mirror the slide's
+    // admission counts from and slide_indices rewrites)
+    bool mirror_valid = false, mirror_stale = false;   // stale: loc_window_slide_resident_dev has slid the device tables since the mirror was written (refresh_mirror)
+    std::vector<int32_t> mir_ridx, mir_pidx;
+};
+
 struct loc_window {
     int device = 0;
     long long B = 0;
@@ -58,11 +77,7 @@ struct loc_window {
     double* d_roff1 = nullptr;      // optional lever arms of endpoint 1 (loc_window_set_endpoint1_offsets: opt.has_off1), [B][nr_max][3]
     double* d_pinfo = nullptr;      // optional full information matrices of the priors (loc_window_set_prior_information: opt.has_pinfo), [B][np_max][36]
     long long n_pinfo = 0;          // instances the table describes: a call with more is refused
-    int resident_topology = 0;      // LOC_WINDOW_KERNEL_* the uploaded batch qualifies for by its structure (the batch-size threshold is applied per solve)
-    bool resident_skip = false;     // ... a verdict taken with the priors' diagonals skipped (a structured table was set): it holds while structured_pinfo(opt) does
-    long long n_resident = 0;
-    int resident_min_anchors = 0;   // anchors the resident batch references (loc_window_set_anchors may not shrink below it)
-    bool resident_solved = false;   // a resident solve has run since the upload (loc_window_download has something to fetch)
+    Resident res;
     int last_kind = -1;             // LOC_WINDOW_KERNEL_* of the last launch
     hipEvent_t resident_done = nullptr;  // recorded after every resident launch on the stream it ran on: whatever touches the shared
     bool resident_inflight = false;      // device state waits for THIS (the caller's stream is not kept: it may be destroyed any time)
@@ -78,36 +93,18 @@ struct loc_window {
     // small calls (a node's single window): all inputs travel as one page-locked block, all outputs as another
     char *h_stage = nullptr, *d_stage = nullptr;
     // marginal covariances (loc_window_covariance_*): a device block of their own for batches beyond the staging block, HIP events of
-    // their own (the solve's last_kernel_ms stays as it is), the resident batch's verdict (set by loc_window_upload)
+    // their own (the solve's last_kernel_ms stays as it is)
     char* d_cov = nullptr;
     size_t cov_cap = 0;
     hipEvent_t cov_ev0 = nullptr, cov_ev1 = nullptr;
     bool cov_pending = false;       // the events of a resident covariance launch have not been read yet
     double cov_ms = 0.0;
-    CovKind resident_cov = CovKind::None;   // the resident batch's pass; Unclassified: the first covariance call finds out
-    long long env_switches = 0;      // cov_switches() when the resident batch was classified: a change of the switches the three structured
-                                     // tests read classifies a batch the envelope pass holds again
     locamd::SchedKey cov_sched;      // the structure slot[0].cov_aux's forest schedule was built (and uploaded) for
-    // joint covariance calls (loc_window_joint_covariance_resident): the resident batch's counts as uploaded (the pair check needs every
-    // window's nv) and, once the envelope pass holds the batch, its pose-to-pose index tables (the pairs enlarge the envelope); the call's pair
-    // tables [counts | pairs] as a page-locked copy and as the device table the kernel reads, grown on demand
-    std::vector<int32_t> res_counts, res_ridx, res_sidx;
-    char *h_pairs = nullptr, *d_pairs = nullptr;
-    size_t pairs_cap = 0;
-    hipEvent_t pairs_copied = nullptr;   // the device table has the page-locked copy's content
-    bool pairs_inflight = false;
-    // the resident slide (loc_window_slide_resident): with option "resident_slide" loc_window_upload keeps the batch's index tables next to
-    // res_counts (the mirror the slide's admission counts from and slide_indices rewrites); the call's inputs [drop | counts | new rows] as a
-    // page-locked copy and as the device block the kernel reads, grown on demand, as the pair tables are; the marginal pass's drop table
-    // (zeros) and results for B windows
-    bool opt_slide = false, mirror_valid = false;
-    bool mirror_stale = false;   // loc_window_slide_resident_dev has slid the device tables since the mirror was written (refresh_mirror)
-    std::vector<int32_t> mir_ridx, mir_pidx;
-    char *h_slide = nullptr, *d_slide = nullptr;
-    size_t slide_cap = 0;
-    hipEvent_t slide_copied = nullptr;
-    bool slide_inflight = false;
-    char* d_slide_mp = nullptr;
+    // the call's host arrays on their way to the caller's stream: a resident joint call's pair tables [counts | pairs], a host slide's
+    // inputs [drop | counts | new rows]
+    locamd::StagingPair pairs, slide;
+    bool opt_slide = false;         // option "resident_slide"
+    char* d_slide_mp = nullptr;     // a slide's marginal pass: its drop table (zeros) and results for B windows (slide_marginal_layout)
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -140,26 +137,14 @@ static void release_slot(loc_window::BatchSlot& S) {
 int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
-    void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws};
+    void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws,
+                    w->d_stage, w->d_cov, w->d_slide_mp};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
-    w->timer.destroy();
     if (w->h_stage) (void)hipHostFree(w->h_stage);
-    if (w->d_stage) (void)hipFree(w->d_stage);
-    if (w->ev0) (void)hipEventDestroy(w->ev0);
-    if (w->ev1) (void)hipEventDestroy(w->ev1);
-    if (w->resident_done) (void)hipEventDestroy(w->resident_done);
-    if (w->d_cov) (void)hipFree(w->d_cov);
-    if (w->h_pairs) (void)hipHostFree(w->h_pairs);
-    if (w->d_pairs) (void)hipFree(w->d_pairs);
-    if (w->pairs_copied) (void)hipEventDestroy(w->pairs_copied);
-    if (w->h_slide) (void)hipHostFree(w->h_slide);
-    if (w->d_slide) (void)hipFree(w->d_slide);
-    if (w->d_slide_mp) (void)hipFree(w->d_slide_mp);
-    if (w->slide_copied) (void)hipEventDestroy(w->slide_copied);
-    if (w->cov_ev0) (void)hipEventDestroy(w->cov_ev0);
-    if (w->cov_ev1) (void)hipEventDestroy(w->cov_ev1);
+    w->timer.destroy(); w->pairs.destroy(); w->slide.destroy();
+    for (hipEvent_t e : {w->ev0, w->ev1, w->resident_done, w->cov_ev0, w->cov_ev1}) if (e) (void)hipEventDestroy(e);
     if (w->stream) (void)hipStreamDestroy(w->stream);
     delete w;
     return LOC_OK;
@@ -248,25 +233,20 @@ static int wait_resident(loc_window* w) {
 }
 
 // After loc_window_slide_resident_dev the device holds the only copy of the slid counts and index tables.  Whoever reads the host's mirror
-// (res_counts, mir_ridx, mir_pidx, resident_min_anchors) asks here first: waits for the resident work, fetches counts, r_idx and p_idx,
+// (res.counts, res.mir_ridx, res.mir_pidx, res.min_anchors) asks here first: waits for the resident work, fetches counts, r_idx and p_idx,
 // recomputes the largest anchor referenced.  Nothing to do (and no wait) while the mirror is current.
 static int refresh_mirror(loc_window* w) {
-    if (!w->mirror_stale) return LOC_OK;
+    Resident& R = w->res;
+    if (!R.mirror_stale) return LOC_OK;
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = wait_resident(w)) return rc;
     const locamd::WindowCaps& c = w->caps;
-    const size_t N = (size_t)w->n_resident;
-    LOC_HIP(hipMemcpy(w->res_counts.data(), w->dev.t[kCounts], N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (c.nr_max) LOC_HIP(hipMemcpy(w->mir_ridx.data(), w->dev.t[locamd::kRIdx], N * c.nr_max * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (c.np_max) LOC_HIP(hipMemcpy(w->mir_pidx.data(), w->dev.t[locamd::kPIdx], N * c.np_max * sizeof(int32_t), hipMemcpyDeviceToHost));
-    int max_anchor = 0;   // (loc_window_upload's scan: v1 = -1 - anchor)
-    for (size_t i = 0; i < N; ++i)
-        for (int e = 0; e < w->res_counts[i * 4 + 1]; ++e) {
-            const int32_t v1 = w->mir_ridx[(i * c.nr_max + e) * 2 + 1];
-            if (v1 < 0 && -v1 > max_anchor) max_anchor = -v1;
-        }
-    w->resident_min_anchors = max_anchor;
-    w->mirror_stale = false;
+    const size_t N = (size_t)R.n;
+    LOC_HIP(hipMemcpy(R.counts.data(), w->dev.t[kCounts], N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (c.nr_max) LOC_HIP(hipMemcpy(R.mir_ridx.data(), w->dev.t[locamd::kRIdx], N * c.nr_max * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (c.np_max) LOC_HIP(hipMemcpy(R.mir_pidx.data(), w->dev.t[locamd::kPIdx], N * c.np_max * sizeof(int32_t), hipMemcpyDeviceToHost));
+    R.min_anchors = locamd::max_anchor_referenced(c, R.n, R.counts.data(), R.mir_ridx.data());
+    R.mirror_stale = false;
     return LOC_OK;
 }
 
@@ -294,7 +274,7 @@ static int flush_anchors(loc_window* w) {
 int loc_window_set_anchors(loc_window* w, int32_t n_anchors, const double* anchors) {
     if (!w || n_anchors < 0 || (n_anchors > 0 && !anchors)) return locamd_fail(LOC_ERR_INVALID, "set_anchors");
     if (int rc = refresh_mirror(w)) return rc;   // (a slide from device arrays may have introduced anchors the host has not seen)
-    if (w->n_resident > 0 && n_anchors < w->resident_min_anchors)
+    if (w->res.n > 0 && n_anchors < w->res.min_anchors)
         return locamd_fail(LOC_ERR_INVALID, "set_anchors: the resident batch references more anchors than the new table holds (upload again first)");
     if (w->B <= 4) {
         // a node's handle: its table changes with every message (the window slides), and its solve usually reads the table from the
@@ -391,7 +371,16 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
 // the resident batch as uploaded: the initial estimates in the place of the optimised ones
 static locamd::DeviceTables uploaded_tables(const loc_window* w) { locamd::DeviceTables d = w->dev; d.t[kPoses] = w->d_poses_in; return d; }
 // the device arrays hold no resident batch any more (the resident calls return LOC_ERR_INVALID until the next loc_window_upload completes)
-static void drop_resident(loc_window* w) { w->n_resident = 0; w->resident_solved = false; w->resident_topology = LOC_WINDOW_KERNEL_GENERAL; w->resident_skip = false; w->resident_min_anchors = 0; w->mirror_valid = false; w->mirror_stale = false; }
+static void drop_resident(loc_window* w) { w->res = Resident{}; }
+// a table of full information matrices has a row for every window of the resident batch
+static int check_pinfo_covers_resident(const loc_window* w) {
+    if (w->opt.has_pinfo && w->res.n > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
+    return LOC_OK;
+}
+// The resident batch's structural verdict as it holds NOW.  One taken with the priors' diagonals skipped is worth nothing once the structured
+// table has gone, has got rotation entries or the option is off — the diagonals in p_val count again and may hold rotation information: such a
+// batch takes the general kernel until the next upload, never wave3_lm_kernel, and does not slide
+static int resident_topology(const loc_window* w) { return w->res.skip && !locamd::structured_pinfo(w->opt) ? (int)LOC_WINDOW_KERNEL_GENERAL : w->res.topology; }
 
 static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const locamd::WindowArgs& a, hipStream_t st, int kind) {
     locamd::WinAux& A = S.aux;
@@ -457,14 +446,14 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
         const bool before = o.cov_general;
         const int rc = flag(o.cov_general);
         // a resident batch the other value refused, or handed to the envelope pass, is classified again by the next covariance call
-        if (rc == LOC_OK && before != o.cov_general && w->n_resident > 0 && (w->resident_cov == CovKind::None || w->resident_cov == CovKind::Envelope)) w->resident_cov = CovKind::Unclassified;
+        if (rc == LOC_OK && before != o.cov_general && w->res.n > 0 && (w->res.cov == CovKind::None || w->res.cov == CovKind::Envelope)) w->res.cov = CovKind::Unclassified;
         return rc;
     }
     if (k == "prior_information_structured") {
         const bool before = o.pinfo_structured;
         const int rc = flag(o.pinfo_structured);
         // a resident batch under a table is classified again by the next covariance call: the other value takes another pass (or none)
-        if (rc == LOC_OK && before != o.pinfo_structured && w->n_resident > 0 && o.has_pinfo) w->resident_cov = CovKind::Unclassified;
+        if (rc == LOC_OK && before != o.pinfo_structured && w->res.n > 0 && o.has_pinfo) w->res.cov = CovKind::Unclassified;
         return rc;
     }
     if (k == "resident_slide") return flag(w->opt_slide);   // (read by loc_window_upload: the batch resident now keeps what its upload decided)
@@ -498,7 +487,7 @@ int loc_window_set_prior_information(loc_window* w, int64_t n, const double* pin
     if (!w) return locamd_fail(LOC_ERR_INVALID, "set_prior_information");
     // (option "prior_information_structured": the resident batch's covariance verdict may rest on the table that goes or changes here — the
     //  next covariance call classifies the batch again; its solve verdict is checked per solve, loc_window_solve_resident)
-    if (w->opt.pinfo_structured && w->n_resident > 0) w->resident_cov = CovKind::Unclassified;
+    if (w->opt.pinfo_structured && w->res.n > 0) w->res.cov = CovKind::Unclassified;
     if (!pinfo) { w->opt.has_pinfo = false; w->opt.pinfo_translation = false; w->n_pinfo = 0; return LOC_OK; }   // (has_pinfo is part of the structure hash, as has_off1 is)
     if (n <= 0 || n > w->B) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: n_instances");
     if (w->caps.np_max <= 0) return locamd_fail(LOC_ERR_INVALID, "set_prior_information: no prior edges in this solver");
@@ -644,77 +633,68 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     LOC_HIP(hipStreamSynchronize(w->stream));
     if (int rc = wait_resident(w)) return rc;
     // (a failing step below must not leave a half-described resident batch behind: nothing is resident until everything is)
-    drop_resident(w); w->resident_cov = CovKind::None;   // (and its covariance verdict with it)
+    drop_resident(w);   // (and its covariance verdict with it)
+    Resident& R = w->res;
     if (!w->d_poses_in) LOC_HIP(hipMalloc((void**)&w->d_poses_in, (size_t)w->B * locamd::table_bytes(c, kPoses)));
     LOC_HIP(copy_tables(c, (size_t)n, uploaded_tables(w).t, b.tables().t, hipMemcpyHostToDevice, nullptr));
     loc_window::BatchSlot& S = w->slot[1];
     const int topology = locamd::batch_topology(c, w->opt, w->fits, w->n_anchors, b, S.aux, nullptr).kind;
     if (topology == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, S, n, w->stream));
     if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, S.aux, w->stream));
-    int max_anchor = 0;   // anchors referenced: v1 = -1 - anchor
-    for (int64_t i = 0; i < n; ++i)
-        for (int e = 0; e < counts[i * 4 + 1]; ++e) {
-            const int32_t v1 = r_idx[((size_t)i * c.nr_max + e) * 2 + 1];
-            if (v1 < 0 && -v1 > max_anchor) max_anchor = -v1;
-        }
-    w->resident_min_anchors = max_anchor;
-    w->res_counts.assign(counts, counts + (size_t)n * 4);
+    R.min_anchors = locamd::max_anchor_referenced(c, n, counts, r_idx);
+    R.counts.assign(counts, counts + (size_t)n * 4);
     if (w->opt_slide) {   // the mirror of loc_window_slide_resident
-        w->mir_ridx.assign((size_t)n * c.nr_max * 2, 0);
-        w->mir_pidx.assign((size_t)n * c.np_max, 0);
-        if (c.nr_max) std::memcpy(w->mir_ridx.data(), r_idx, w->mir_ridx.size() * sizeof(int32_t));
-        if (c.np_max) std::memcpy(w->mir_pidx.data(), p_idx, w->mir_pidx.size() * sizeof(int32_t));
-        w->mirror_valid = true;
+        R.mir_ridx.assign((size_t)n * c.nr_max * 2, 0);
+        R.mir_pidx.assign((size_t)n * c.np_max, 0);
+        if (c.nr_max) std::memcpy(R.mir_ridx.data(), r_idx, R.mir_ridx.size() * sizeof(int32_t));
+        if (c.np_max) std::memcpy(R.mir_pidx.data(), p_idx, R.mir_pidx.size() * sizeof(int32_t));
+        R.mirror_valid = true;
     }
-    w->resident_topology = topology;
-    w->resident_skip = locamd::structured_pinfo(w->opt);
+    R.topology = topology;
+    R.skip = locamd::structured_pinfo(w->opt);
     // the pass of loc_window_covariance_resident: ordered chain batches are known from the verdict above; any other batch is
     // classified by the first loc_window_covariance_resident call (an upload costs nothing more for callers that never ask)
-    if (topology == LOC_WINDOW_KERNEL_CHAIN3) w->resident_cov = CovKind::Chain3;
-    else if (topology == LOC_WINDOW_KERNEL_CHAIN || topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) w->resident_cov = CovKind::Chain6;
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3) R.cov = CovKind::Chain3;
+    else if (topology == LOC_WINDOW_KERNEL_CHAIN || topology == LOC_WINDOW_KERNEL_WAVE6 || topology == LOC_WINDOW_KERNEL_WAVE6S) R.cov = CovKind::Chain6;
     else if (topology == LOC_WINDOW_KERNEL_TREE) {
         // a forest the solve kernels take: the covariance pass walks the schedule just built and uploaded (S.aux) — unless the batch is
         // a chain in some edge order, which the chain pass serves as before
         bool chain = false, single_pairs = false, se3_pairs = false;
         locamd::chain_scan(c, b, false, chain, single_pairs, se3_pairs);
-        w->resident_cov = chain ? CovKind::Unclassified : CovKind::Forest;
+        R.cov = chain ? CovKind::Unclassified : CovKind::Forest;
     } else if (topology == LOC_WINDOW_KERNEL_ARROW3) {   // (never a chain: build_arrow_aux wants a border)
-        w->resident_cov = CovKind::Arrow;
+        R.cov = CovKind::Arrow;
         S.cov_list_cap = S.aux.arrow_list_cap;
-    } else w->resident_cov = CovKind::Unclassified;
-    w->n_resident = n;
+    } else R.cov = CovKind::Unclassified;
+    R.n = n;
     return LOC_OK;
 }
 
 int loc_window_solve_resident(loc_window* w, void* hip_stream) {
-    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (int rc = check_pinfo_covers_resident(w)) return rc;
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    const locamd::WindowArgs a = window_args(w, w->dev, w->n_resident, w->d_poses_in, w->d_anchors, w->d_result);
+    const locamd::WindowArgs a = window_args(w, w->dev, w->res.n, w->d_poses_in, w->d_anchors, w->d_result);
     LOC_HIP(w->timer.start(st));
     // (the batch-size threshold and the ordering override are looked at per solve: loc_window_set_chain_threshold /
     //  loc_window_set_ordering after the upload take effect)
-    // (a verdict taken with the priors' diagonals skipped is worth nothing once the structured table has gone, has got rotation entries or the
-    //  option is off — the diagonals in p_val count again and may hold rotation information: such a batch takes the general kernel until the
-    //  next upload, never wave3_lm_kernel)
-    const int topology = w->resident_skip && !locamd::structured_pinfo(w->opt) ? (int)LOC_WINDOW_KERNEL_GENERAL : w->resident_topology;
-    hipError_t e = launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->n_resident, topology));
+    hipError_t e = launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->res.n, resident_topology(w)));
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
     LOC_HIP(w->timer.stop(st));
     LOC_HIP(hipEventRecord(w->resident_done, st));
     w->resident_inflight = true;
-    w->resident_solved = true;
+    w->res.solved = true;
     return LOC_OK;
 }
 
 int loc_window_download(loc_window* w, double* poses, double* result) {
-    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_download: no resident solve has run since the upload");
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_download: no resident solve has run since the upload");
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = wait_resident(w)) return rc;
-    const size_t N = (size_t)w->n_resident;
+    const size_t N = (size_t)w->res.n;
     if (poses) LOC_HIP(hipMemcpy(poses, w->dev.t[kPoses], N * locamd::table_bytes(w->caps, kPoses), hipMemcpyDeviceToHost));
     if (result) LOC_HIP(hipMemcpy(result, w->d_result, N * kResultBytes, hipMemcpyDeviceToHost));
     return LOC_OK;
@@ -759,6 +739,54 @@ static int validate_pairs(int64_t n, const int32_t* counts, const locamd::PairTa
     if (const int bad = locamd::check_pairs(n, counts, pt)) return locamd_fail(LOC_ERR_INVALID, kWhat[bad]);
     return LOC_OK;
 }
+// The synchronous host calls beside the solve (joint covariance, marginal prior) as ONE pipeline.  L: the call's block — its output pieces,
+// then its extra input pieces, then all eight tables of b.  ins / outs: the caller's arrays and the prefix piece each travels in (a null
+// array: the call has no such piece).  Small calls go through the staging block of loc_window_solve_host (free between calls, never used by a
+// resident launch), large ones through a device block of the covariance's own: the resident batch's arrays are not touched.
+// launch(a, d, st): the kernel on the tables at device base d; cov_ev0 / cov_ev1 around it give loc_window_last_covariance_ms.
+extern "C++" {   // (a template cannot have C linkage)
+struct PieceIn { const void* p; int k; };
+struct PieceOut { void* p; int k; };
+template <class Launch>
+static int staged_call(loc_window* w, const locamd::BlockLayout& L, const locamd::HostBatch& b, std::initializer_list<PieceIn> ins, std::initializer_list<PieceOut> outs,
+                       const char* what, Launch&& launch) {
+    size_t in0 = L.tab[kPoses];   // the outputs end and the inputs begin here
+    for (const PieceIn& i : ins) if (i.p) in0 = std::min(in0, L.pre[i.k]);
+    hipStream_t st = w->stream;
+    char* d;
+    const bool small = L.end <= kStageBytes;
+    if (small) {
+        if (int rc = ensure_stage(w)) return rc;
+        locamd::stage_tables(w->h_stage, L, w->caps, b);
+        for (const PieceIn& i : ins) if (i.p) std::memcpy(w->h_stage + L.pre[i.k], i.p, L.len[i.k]);
+        d = w->d_stage;
+        LOC_HIP(hipMemcpyAsync(d + in0, w->h_stage + in0, L.end - in0, hipMemcpyHostToDevice, st));
+    } else {
+        LOC_HIP(locamd::grow_buffers(w->cov_cap, L.end, {{w->d_cov, L.end}}));
+        d = w->d_cov;
+        LOC_HIP(copy_tables(w->caps, (size_t)b.n, locamd::tables_at(d, L).t, b.tables().t, hipMemcpyHostToDevice, &st));
+        for (const PieceIn& i : ins) if (i.p) LOC_HIP(hipMemcpyAsync(d + L.pre[i.k], i.p, L.len[i.k], hipMemcpyHostToDevice, st));
+    }
+    const locamd::WindowArgs a = window_args(w, locamd::tables_at(d, L), b.n, nullptr, w->d_anchors, nullptr);
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    const hipError_t e = launch(a, d, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, what);
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    if (small) {
+        LOC_HIP(hipMemcpyAsync(w->h_stage, d, in0, hipMemcpyDeviceToHost, st));   // every output piece in one copy
+        LOC_HIP(hipStreamSynchronize(st));
+        for (const PieceOut& o : outs) if (o.p) std::memcpy(o.p, w->h_stage + L.pre[o.k], L.len[o.k]);
+    } else {
+        for (const PieceOut& o : outs) if (o.p) LOC_HIP(hipMemcpyAsync(o.p, d + L.pre[o.k], L.len[o.k], hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipStreamSynchronize(st));
+    }
+    float ms = 0;
+    LOC_HIP(hipEventElapsedTime(&ms, w->cov_ev0, w->cov_ev1));
+    w->cov_ms = ms;
+    w->cov_pending = false;
+    return LOC_OK;
+}
+}  // extern "C++"
 // loc_window_covariance_host is the joint call without pairs (pt.npair_max = 0, cross = nullptr): one staging, classification and launch path
 int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
                                      const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val,
@@ -784,57 +812,18 @@ int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* co
         w->cov_sched.valid = true;
     }
     if (int rc = flush_anchors(w)) return rc;
-    const size_t N = (size_t)n;
-    // one block: outputs [cov | mask | status], then the inputs [poses | counts | r_val | p_val | s_val | r_idx | p_idx | s_idx]; a joint call
-    // has [cross | pair counts | pairs] between them: a fourth output and two more inputs
-    void* const out[4] = {cov, mask, status, cross};
-    const void* const pair_in[2] = {pair_counts, pairs};
-    const size_t P = (size_t)npair_max;
-    const size_t pre_bytes[6] = {N * c.nv_max * 36 * sizeof(double), N * c.nv_max * sizeof(int32_t), N * sizeof(int32_t),
-                                 N * P * 36 * sizeof(double), N * sizeof(int32_t), N * P * 2 * sizeof(int32_t)};
-    const int n_out = joint ? 4 : 3;
-    const locamd::BlockLayout L = locamd::pack_block(c, N, pre_bytes, joint ? 6 : 3, kPoses);
-    const size_t in0 = joint ? L.pre[4] : L.tab[kPoses];   // the outputs end and the inputs begin here
-    hipStream_t st = w->stream;
-    char* d;
-    const bool small = L.end <= kStageBytes;
-    if (small) {   // (the staging block of loc_window_solve_host: free between calls, never used by a resident launch)
-        if (int rc = ensure_stage(w)) return rc;
-        locamd::stage_tables(w->h_stage, L, c, b);
-        for (int k = 0; k < 2 && joint; ++k) std::memcpy(w->h_stage + L.pre[4 + k], pair_in[k], pre_bytes[4 + k]);
-        d = w->d_stage;
-        LOC_HIP(hipMemcpyAsync(d + in0, w->h_stage + in0, L.end - in0, hipMemcpyHostToDevice, st));
-    } else {       // a device block of the covariance's own: the resident batch's arrays are not touched
-        LOC_HIP(locamd::grow_buffers(w->cov_cap, L.end, {{w->d_cov, L.end}}));
-        d = w->d_cov;
-        LOC_HIP(copy_tables(c, N, locamd::tables_at(d, L).t, b.tables().t, hipMemcpyHostToDevice, &st));
-        for (int k = 0; k < 2 && joint; ++k) LOC_HIP(hipMemcpyAsync(d + L.pre[4 + k], pair_in[k], pre_bytes[4 + k], hipMemcpyHostToDevice, st));
-    }
-    const locamd::WindowArgs a = window_args(w, locamd::tables_at(d, L), n, nullptr, w->d_anchors, nullptr);
-    const locamd::CovPairs pp = joint ? locamd::CovPairs{(const int32_t*)(d + L.pre[4]), (const int32_t*)(d + L.pre[5]), (double*)(d + L.pre[3]), npair_max}
-                                      : locamd::CovPairs{nullptr, nullptr, nullptr, 0};
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, S, kind, S.env_blocks, a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), pp, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    if (small) {
-        LOC_HIP(hipMemcpyAsync(w->h_stage, d, in0, hipMemcpyDeviceToHost, st));   // [cov | mask | status (| cross)]
-        LOC_HIP(hipStreamSynchronize(st));
-        for (int k = 0; k < n_out; ++k) std::memcpy(out[k], w->h_stage + L.pre[k], pre_bytes[k]);
-    } else {
-        for (int k = 0; k < n_out; ++k) LOC_HIP(hipMemcpyAsync(out[k], d + L.pre[k], pre_bytes[k], hipMemcpyDeviceToHost, st));
-        LOC_HIP(hipStreamSynchronize(st));
-    }
-    float ms = 0;
-    LOC_HIP(hipEventElapsedTime(&ms, w->cov_ev0, w->cov_ev1));
-    w->cov_ms = ms;
-    w->cov_pending = false;
-    return LOC_OK;
+    const locamd::BlockLayout L = locamd::covariance_layout(c, (size_t)n, (size_t)npair_max);
+    // (a plain call's block has no piece 3 .. 5, whatever the caller passed for them)
+    return staged_call(w, L, b, {{joint ? pair_counts : nullptr, 4}, {joint ? pairs : nullptr, 5}}, {{cov, 0}, {mask, 1}, {status, 2}, {joint ? cross : nullptr, 3}}, "launch_window_covariance",
+                       [&](const locamd::WindowArgs& a, char* d, hipStream_t st) {
+        const locamd::CovPairs pp = joint ? locamd::CovPairs{(const int32_t*)(d + L.pre[4]), (const int32_t*)(d + L.pre[5]), (double*)(d + L.pre[3]), npair_max}
+                                          : locamd::CovPairs{nullptr, nullptr, nullptr, 0};
+        return launch_covariance(w, S, kind, S.env_blocks, a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), pp, st);
+    });
 }
 
 // ---- the marginal prior of a dropped pose (marginal_prior_kernel.hip) ------------------------------------------------------------
-// stateless and synchronous; staged like loc_window_covariance_host: small calls through the staging block, large ones through the
-// covariance's device block — the resident batch's arrays are not touched
+// stateless and synchronous (staged_call: the resident batch's arrays are not touched)
 int loc_window_marginal_prior_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
                                    const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val, const int32_t* drop,
                                    int32_t* slot, double* prior, double* grad, double* shift, int32_t* rank, int32_t* status) {
@@ -850,47 +839,12 @@ int loc_window_marginal_prior_host(loc_window* w, int64_t n, const int32_t* coun
     if (bad == 2) return locamd_fail(LOC_ERR_UNSUPPORTED, "marginal prior: pose-to-pose edges join a dropped pose to more than one other pose");
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = flush_anchors(w)) return rc;
-    const size_t N = (size_t)n;
-    // one block: outputs [slot | prior | grad | shift | rank | status], then the inputs [drop | poses | counts | ... | s_idx]
-    void* const out[6] = {slot, prior, grad, shift, rank, status};
-    const size_t pre_bytes[7] = {N * sizeof(int32_t), N * 48 * sizeof(double), N * 6 * sizeof(double), N * 6 * sizeof(double), N * sizeof(int32_t), N * sizeof(int32_t),
-                                 N * sizeof(int32_t)};
-    const locamd::BlockLayout L = locamd::pack_block(c, N, pre_bytes, 7, kPoses);
-    const size_t in0 = L.pre[6];   // the outputs end and the inputs begin here
-    hipStream_t st = w->stream;
-    char* d;
-    const bool small = L.end <= kStageBytes;
-    if (small) {
-        if (int rc = ensure_stage(w)) return rc;
-        locamd::stage_tables(w->h_stage, L, c, b);
-        std::memcpy(w->h_stage + L.pre[6], drop, pre_bytes[6]);
-        d = w->d_stage;
-        LOC_HIP(hipMemcpyAsync(d + in0, w->h_stage + in0, L.end - in0, hipMemcpyHostToDevice, st));
-    } else {
-        LOC_HIP(locamd::grow_buffers(w->cov_cap, L.end, {{w->d_cov, L.end}}));
-        d = w->d_cov;
-        LOC_HIP(copy_tables(c, N, locamd::tables_at(d, L).t, b.tables().t, hipMemcpyHostToDevice, &st));
-        LOC_HIP(hipMemcpyAsync(d + L.pre[6], drop, pre_bytes[6], hipMemcpyHostToDevice, st));
-    }
-    const locamd::WindowArgs a = window_args(w, locamd::tables_at(d, L), n, nullptr, w->d_anchors, nullptr);
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)(d + L.pre[6]), (int32_t*)(d + L.pre[0]), (double*)(d + L.pre[1]), (double*)(d + L.pre[2]),
-                                                              (double*)(d + L.pre[3]), (int32_t*)(d + L.pre[4]), (int32_t*)(d + L.pre[5]), st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    if (small) {
-        LOC_HIP(hipMemcpyAsync(w->h_stage, d, in0, hipMemcpyDeviceToHost, st));
-        LOC_HIP(hipStreamSynchronize(st));
-        for (int k = 0; k < 6; ++k) std::memcpy(out[k], w->h_stage + L.pre[k], pre_bytes[k]);
-    } else {
-        for (int k = 0; k < 6; ++k) LOC_HIP(hipMemcpyAsync(out[k], d + L.pre[k], pre_bytes[k], hipMemcpyDeviceToHost, st));
-        LOC_HIP(hipStreamSynchronize(st));
-    }
-    float ms = 0;
-    LOC_HIP(hipEventElapsedTime(&ms, w->cov_ev0, w->cov_ev1));
-    w->cov_ms = ms;
-    w->cov_pending = false;
-    return LOC_OK;
+    const locamd::BlockLayout L = locamd::marginal_prior_layout(c, (size_t)n);
+    return staged_call(w, L, b, {{drop, 6}}, {{slot, 0}, {prior, 1}, {grad, 2}, {shift, 3}, {rank, 4}, {status, 5}}, "launch_window_marginal_prior",
+                       [&](const locamd::WindowArgs& a, char* d, hipStream_t st) {
+        return locamd::launch_window_marginal_prior(a, (const int32_t*)(d + L.pre[6]), (int32_t*)(d + L.pre[0]), (double*)(d + L.pre[1]), (double*)(d + L.pre[2]),
+                                                    (double*)(d + L.pre[3]), (int32_t*)(d + L.pre[4]), (int32_t*)(d + L.pre[5]), st);
+    });
 }
 
 int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
@@ -902,23 +856,24 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
 // loc_window_covariance_resident is the joint call without pairs, as on the host path
 int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_t npair_max, const int32_t* pair_counts_host, const int32_t* pairs_host,
                                          void* cov_dev, void* mask_dev, void* status_dev, void* cross_dev) {
-    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
     if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
-    if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
+    if (int rc = check_pinfo_covers_resident(w)) return rc;
+    Resident& R = w->res;
     const locamd::PairTables pt{npair_max, pair_counts_host, pairs_host};
     if (npair_max > 0)   // (the pair check reads every window's nv; a call without pairs reads no count and does not wait)
         if (int rc = refresh_mirror(w)) return rc;
-    if (int rc = validate_pairs(w->n_resident, w->res_counts.data(), pt, cross_dev)) return rc;
+    if (int rc = validate_pairs(R.n, R.counts.data(), pt, cross_dev)) return rc;
     const bool joint = npair_max > 0;
     LOC_HIP(hipSetDevice(w->device));
     loc_window::BatchSlot& S = w->slot[1];
-    if (locamd::cov_stale(w->opt, w->fits, w->n_resident, w->resident_cov, w->env_switches)) w->resident_cov = CovKind::Unclassified;
-    if (w->resident_cov == CovKind::Unclassified && !w->opt.has_off1) {
+    if (locamd::cov_stale(w->opt, w->fits, R.n, R.cov, R.env_switches)) R.cov = CovKind::Unclassified;
+    if (R.cov == CovKind::Unclassified && !w->opt.has_off1) {
         // first call on an upload no solve kernel classified as a chain: the uploaded tables come back once and are scanned on the host
         if (int rc = wait_resident(w)) return rc;
         const locamd::WindowCaps& c = w->caps;
-        const size_t N = (size_t)w->n_resident;
+        const size_t N = (size_t)R.n;
         auto len = [&](int t, size_t elem) { return N * locamd::table_bytes(c, t) / elem + 1; };
         std::vector<int32_t> counts(len(kCounts, 4)), ridx(len(locamd::kRIdx, 4)), pidx(len(locamd::kPIdx, 4)), sidx(len(locamd::kSIdx, 4));
         std::vector<double> poses(len(kPoses, 8)), rval(len(locamd::kRVal, 8)), pval(len(locamd::kPVal, 8));   // (no scan reads s_val: it stays on the device)
@@ -927,56 +882,48 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         const locamd::HostBatch b{(int64_t)N, poses.data(), counts.data(), rval.data(), pval.data(), nullptr, ridx.data(), pidx.data(), sidx.data()};
         const locamd::CovVerdict v = locamd::covariance_kind(c, w->opt, w->fits, w->n_anchors, b, locamd::PairTables{0, nullptr, nullptr}, S.cov_aux, nullptr);
         if (v.need_upload) LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false));
-        w->resident_cov = v.kind;
+        R.cov = v.kind;
         S.cov_list_cap = v.list_cap; S.env_blocks = v.env_blocks;
-        w->env_switches = locamd::cov_switches(w->opt);
-        if (v.kind == CovKind::Envelope) { w->res_ridx.swap(ridx); w->res_sidx.swap(sidx); }   // (a joint call's pairs enlarge the envelope)
+        R.env_switches = locamd::cov_switches(w->opt);
+        if (v.kind == CovKind::Envelope) { R.ridx.swap(ridx); R.sidx.swap(sidx); }   // (a joint call's pairs enlarge the envelope)
     }
-    if (!locamd::cov_admitted(w->opt, w->fits, w->n_resident, w->resident_cov)) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
-    const bool arrow = w->resident_cov == CovKind::Arrow, envelope = w->resident_cov == CovKind::Envelope;
+    if (!locamd::cov_admitted(w->opt, w->fits, R.n, R.cov)) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_covariance_resident" LOC_COV_UNSUPPORTED);
+    const bool arrow = R.cov == CovKind::Arrow, envelope = R.cov == CovKind::Envelope;
     long long env_blocks = S.env_blocks;
     if (envelope && joint) {
-        const locamd::HostBatch eb{w->n_resident, nullptr, w->res_counts.data(), nullptr, nullptr, nullptr, w->res_ridx.data(), nullptr, w->res_sidx.data()};
+        const locamd::HostBatch eb{R.n, nullptr, R.counts.data(), nullptr, nullptr, nullptr, R.ridx.data(), nullptr, R.sidx.data()};
         env_blocks = locamd::envelope_blocks_max_joint(w->caps, eb, pt);
         if (env_blocks < 0) return locamd_fail(LOC_ERR_INVALID, "joint covariance: pair tables");   // (cannot happen: validated above)
     }
-    if (envelope && S.env_ws_cap < (size_t)w->n_resident * locamd::window_envelope_covariance_workspace_doubles(w->caps, env_blocks)) {
+    if (envelope && S.env_ws_cap < (size_t)R.n * locamd::window_envelope_covariance_workspace_doubles(w->caps, env_blocks)) {
         if (int rc = wait_resident(w)) return rc;   // (as below)
-        LOC_HIP(grow_env_workspace(w, S, w->n_resident, env_blocks));
+        LOC_HIP(grow_env_workspace(w, S, R.n, env_blocks));
     }
-    if (arrow && S.cov_ws_cap < (size_t)w->n_resident * locamd::window_arrow_covariance_workspace_doubles(w->caps, S.cov_list_cap)) {
+    if (arrow && S.cov_ws_cap < (size_t)R.n * locamd::window_arrow_covariance_workspace_doubles(w->caps, S.cov_list_cap)) {
         if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
-        LOC_HIP(grow_cov_workspace(w, S, w->n_resident, S.cov_list_cap));
+        LOC_HIP(grow_cov_workspace(w, S, R.n, S.cov_list_cap));
     }
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
     locamd::CovPairs pp{nullptr, nullptr, nullptr, 0};
-    const size_t N = (size_t)w->n_resident, cnt_bytes = (N * sizeof(int32_t) + 15) & ~(size_t)15, pair_bytes = N * (size_t)npair_max * 2 * sizeof(int32_t);
+    const locamd::BlockLayout L = locamd::resident_pairs_layout((size_t)R.n, (size_t)npair_max);
     if (joint) {
         // the caller's arrays are read here and never after the call returns: into the page-locked copy (once the previous call's copy has
         // left it), from there to the device table in stream order below
-        if (w->pairs_cap < cnt_bytes + pair_bytes) {
+        if (L.end > w->pairs.cap)
             if (int rc = wait_resident(w)) return rc;   // (an earlier joint launch may still read the table that is about to be replaced)
-            if (w->h_pairs) (void)hipHostFree(w->h_pairs);
-            w->h_pairs = nullptr; w->pairs_cap = 0; w->pairs_inflight = false;   // (capacity 0: grow_buffers replaces the device half with the host half, and a failure leaves none)
-            LOC_HIP(hipHostMalloc((void**)&w->h_pairs, cnt_bytes + pair_bytes, hipHostMallocDefault));
-            LOC_HIP(locamd::grow_buffers(w->pairs_cap, cnt_bytes + pair_bytes, {{w->d_pairs, cnt_bytes + pair_bytes}}));
-        }
-        if (!w->pairs_copied) LOC_HIP(hipEventCreateWithFlags(&w->pairs_copied, hipEventDisableTiming));
-        if (w->pairs_inflight) { LOC_HIP(hipEventSynchronize(w->pairs_copied)); w->pairs_inflight = false; }
-        std::memcpy(w->h_pairs, pair_counts_host, N * sizeof(int32_t));
-        std::memcpy(w->h_pairs + cnt_bytes, pairs_host, pair_bytes);
-        pp = locamd::CovPairs{(const int32_t*)w->d_pairs, (const int32_t*)(w->d_pairs + cnt_bytes), (double*)cross_dev, npair_max};
+        LOC_HIP(w->pairs.reserve(L.end));
+        char* h;
+        LOC_HIP(w->pairs.host(h));
+        std::memcpy(h + L.pre[0], pair_counts_host, L.len[0]);
+        std::memcpy(h + L.pre[1], pairs_host, L.len[1]);
+        pp = locamd::CovPairs{(const int32_t*)(w->pairs.d + L.pre[0]), (const int32_t*)(w->pairs.d + L.pre[1]), (double*)cross_dev, npair_max};
     }
     if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    if (joint) {   // (after that wait: an earlier joint launch on another stream has finished reading the table)
-        LOC_HIP(hipMemcpyAsync(w->d_pairs, w->h_pairs, cnt_bytes + pair_bytes, hipMemcpyHostToDevice, st));
-        LOC_HIP(hipEventRecord(w->pairs_copied, st));
-        w->pairs_inflight = true;
-    }
-    const locamd::WindowArgs a = window_args(w, w->dev, w->n_resident, nullptr, w->d_anchors, nullptr);
+    if (joint) LOC_HIP(w->pairs.send(L.end, st));   // (after that wait: an earlier joint launch on another stream has finished reading the table)
+    const locamd::WindowArgs a = window_args(w, w->dev, R.n, nullptr, w->d_anchors, nullptr);
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, S, w->resident_cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st);
+    const hipError_t e = launch_covariance(w, S, R.cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
     LOC_HIP(hipEventRecord(w->cov_ev1, st));
     // whatever overwrites the resident arrays next waits for this launch as well
@@ -1014,51 +961,47 @@ int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, con
 // ---- the resident slide (window_slide_kernel.hip; DESIGN.md §2, "The resident slide") ------------------------------------------------------------
 // what both entries check without looking at a window; nothing is launched or changed on a refusal
 static int slide_check_handle(const loc_window* w, bool arrays_ok) {
-    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->mirror_valid) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded");
-    if (!w->resident_solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: no resident solve has run since the upload");
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->res.mirror_valid) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded");
+    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: no resident solve has run since the upload");
     if (!arrays_ok) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: new pose and new row arrays");
-    if (w->opt.has_pinfo && w->n_resident > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
-    // (a verdict taken with the priors' diagonals skipped holds only while structured_pinfo does: loc_window_solve_resident's rule)
-    if (w->resident_topology != LOC_WINDOW_KERNEL_CHAIN3 || (w->resident_skip && !locamd::structured_pinfo(w->opt)))
+    if (int rc = check_pinfo_covers_resident(w)) return rc;
+    if (resident_topology(w) != LOC_WINDOW_KERNEL_CHAIN3)
         return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the resident batch is not an ordered translation-only chain batch");
     if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
     if (w->opt.has_pinfo && !w->opt.pinfo_translation) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the table of full information matrices has rotation entries");
     return LOC_OK;
 }
-// the one-time allocations of a slide: the marginal pass's block for B windows, [zeros | slot | rank | status | prior | grad | shift], and the
-// table a first slide creates (a launch under an earlier table may still read it: that one waits)
-struct SlideBlock { size_t mi, prior, grad, shift, end; bool fresh; };
-static int slide_allocate(loc_window* w, bool densify, SlideBlock& m) {
-    const size_t Bw = (size_t)w->B;
-    m.mi = (Bw * sizeof(int32_t) + 15) & ~(size_t)15;
-    m.prior = 4 * m.mi; m.grad = m.prior + Bw * 48 * sizeof(double); m.shift = m.grad + Bw * 6 * sizeof(double); m.end = m.shift + Bw * 6 * sizeof(double);
-    m.fresh = !w->d_slide_mp;
-    if (m.fresh) LOC_HIP(hipMalloc((void**)&w->d_slide_mp, m.end));
+// the one-time allocations of a slide: the marginal pass's block for B windows (fresh: its drop table is not zeroed yet), and the table a first
+// slide creates (a launch under an earlier table may still read it: that one waits)
+static int slide_allocate(loc_window* w, bool densify, bool& fresh) {
+    fresh = !w->d_slide_mp;
+    if (fresh) LOC_HIP(hipMalloc((void**)&w->d_slide_mp, locamd::slide_marginal_layout((size_t)w->B).end));
     if (densify) {
         if (int rc = wait_resident(w)) return rc;
-        if (!w->d_pinfo) LOC_HIP(hipMalloc((void**)&w->d_pinfo, Bw * w->caps.np_max * 36 * sizeof(double)));
+        if (!w->d_pinfo) LOC_HIP(hipMalloc((void**)&w->d_pinfo, (size_t)w->B * w->caps.np_max * 36 * sizeof(double)));
     }
     return LOC_OK;
 }
 // launch 1: the marginal of slot 0 at the solved poses, marginal_prior_kernel itself (a handle without a table: p_val's diagonals, as
 // loc_window_marginal_prior_host reads them); launch 2: the re-pack — sa holds the call's inputs and outputs; admitting: the twin whose waves
 // admit their own windows.  Then the handle's state but the mirror: what loc_window_upload of the slid tables, with the table set, would leave
-static int slide_launches(loc_window* w, hipStream_t st, locamd::SlideArgs& sa, bool densify, const SlideBlock& m, bool admitting, int32_t* admit) {
+static int slide_launches(loc_window* w, hipStream_t st, locamd::SlideArgs& sa, bool densify, bool fresh, bool admitting, int32_t* admit) {
     const locamd::WindowCaps& c = w->caps;
-    const int64_t n = w->n_resident;
-    char* mp = w->d_slide_mp;
-    if (m.fresh) LOC_HIP(hipMemsetAsync(mp, 0, m.mi, st));                                                        // the marginal pass's drop table: slot 0 of every window
+    const int64_t n = w->res.n;
+    const locamd::BlockLayout M = locamd::slide_marginal_layout((size_t)w->B);
+    auto mp = [&](int piece) { return w->d_slide_mp + M.pre[piece]; };
+    if (fresh) LOC_HIP(hipMemsetAsync(mp(locamd::kMDrop), 0, M.pre[locamd::kMSlot], st));                         // the marginal pass's drop table: slot 0 of every window
     if (densify) LOC_HIP(hipMemsetAsync(w->d_pinfo, 0, (size_t)w->B * c.np_max * 36 * sizeof(double), st));     // (rows beyond the counts: zeros, not what the allocation held)
     const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, nullptr);
     LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)mp, (int32_t*)(mp + m.mi), (double*)(mp + m.prior), (double*)(mp + m.grad), (double*)(mp + m.shift),
-                                                        (int32_t*)(mp + 2 * m.mi), (int32_t*)(mp + 3 * m.mi), st);
+    hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)mp(locamd::kMDrop), (int32_t*)mp(locamd::kMSlot), (double*)mp(locamd::kMPrior), (double*)mp(locamd::kMGrad),
+                                                        (double*)mp(locamd::kMShift), (int32_t*)mp(locamd::kMRank), (int32_t*)mp(locamd::kMStatus), st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
     sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
     sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
     sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal]; sa.p_info = c.np_max > 0 ? w->d_pinfo : nullptr;
-    sa.m_slot = (const int32_t*)(mp + m.mi); sa.m_prior = (const double*)(mp + m.prior); sa.m_rank = (const int32_t*)(mp + 2 * m.mi); sa.m_status = (const int32_t*)(mp + 3 * m.mi);
+    sa.m_slot = (const int32_t*)mp(locamd::kMSlot); sa.m_prior = (const double*)mp(locamd::kMPrior); sa.m_rank = (const int32_t*)mp(locamd::kMRank); sa.m_status = (const int32_t*)mp(locamd::kMStatus);
     sa.B = (int)n; sa.caps = c;
     e = admitting ? locamd::launch_window_slide_dev(sa, w->n_anchors, admit, densify, st) : locamd::launch_window_slide(sa, densify, st);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide");
@@ -1067,8 +1010,8 @@ static int slide_launches(loc_window* w, hipStream_t st, locamd::SlideArgs& sa, 
     w->resident_inflight = true;
     w->cov_pending = true;
     if (densify) { w->opt.has_pinfo = true; w->opt.pinfo_translation = true; w->n_pinfo = n; }
-    w->resident_skip = locamd::structured_pinfo(w->opt);
-    w->resident_cov = CovKind::Chain3;   // (loc_window_upload's verdict for this topology; a call the switches do not admit classifies it again)
+    w->res.skip = locamd::structured_pinfo(w->opt);
+    w->res.cov = CovKind::Chain3;   // (loc_window_upload's verdict for this topology; a call the switches do not admit classifies it again)
     return LOC_OK;
 }
 
@@ -1081,59 +1024,48 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
         return rc;
     if (int rc = refresh_mirror(w)) return rc;   // (the two entries may alternate on one handle)
     const locamd::WindowCaps& c = w->caps;
-    const int64_t n = w->n_resident;
+    Resident& R = w->res;
+    const int64_t n = R.n;
     const size_t N = (size_t)n;
     const locamd::SlideRows rows{drop_oldest, nr_new_max, new_r_counts, new_r_idx, np_new_max, new_p_counts};
     static const char* const kWhat[] = {nullptr, "loc_window_slide_resident: a window without poses", "loc_window_slide_resident: a new count outside [0, *_new_max]",
                                         "loc_window_slide_resident: a new range index (the new slot, the slot before it or an anchor; rows in the order of their later pose)",
                                         "loc_window_slide_resident: the slid window exceeds nv_max", "loc_window_slide_resident: the slid window exceeds nr_max",
                                         "loc_window_slide_resident: the slid window exceeds np_max"};
-    if (const int bad = locamd::slide_indices(c, w->n_anchors, n, w->res_counts.data(), w->mir_ridx.data(), w->mir_pidx.data(), rows, false).bad)
+    if (const int bad = locamd::slide_indices(c, w->n_anchors, n, R.counts.data(), R.mir_ridx.data(), R.mir_pidx.data(), rows, false).bad)
         return locamd_fail(LOC_ERR_INVALID, kWhat[bad]);
     if (!locamd::slide_rows_translation_only(n, rows, new_pose, new_r_val, new_p_val))
         return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: a new row is not translation-only (identity rotations, zero lever arms, no rotation information)");
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    // the staged inputs: [drop | new_r_counts | new_p_counts | new_r_idx | new_pose | new_r_val | new_p_val], 16-byte aligned pieces
-    const size_t nrn = (size_t)nr_new_max, npn = (size_t)np_new_max;
-    const size_t piece[7] = {N * sizeof(int32_t), N * sizeof(int32_t), N * sizeof(int32_t), N * nrn * 2 * sizeof(int32_t), N * 12 * sizeof(double),
-                             N * nrn * 5 * sizeof(double), N * npn * 18 * sizeof(double)};
-    size_t at[8] = {0};
-    for (int k = 0; k < 7; ++k) at[k + 1] = at[k] + ((piece[k] + 15) & ~(size_t)15);
-    if (w->slide_cap < at[7]) {
+    const locamd::BlockLayout L = locamd::slide_inputs_layout(N, (size_t)nr_new_max, (size_t)np_new_max);
+    if (L.end > w->slide.cap)
         if (int rc = wait_resident(w)) return rc;   // (an earlier slide may still read the block that is about to be replaced)
-        if (w->h_slide) (void)hipHostFree(w->h_slide);
-        w->h_slide = nullptr; w->slide_cap = 0; w->slide_inflight = false;
-        LOC_HIP(hipHostMalloc((void**)&w->h_slide, at[7], hipHostMallocDefault));
-        LOC_HIP(locamd::grow_buffers(w->slide_cap, at[7], {{w->d_slide, at[7]}}));
-    }
+    LOC_HIP(w->slide.reserve(L.end));
     const bool densify = !w->opt.has_pinfo && c.np_max > 0;
-    SlideBlock m;
-    if (int rc = slide_allocate(w, densify, m)) return rc;
-    if (!w->slide_copied) LOC_HIP(hipEventCreateWithFlags(&w->slide_copied, hipEventDisableTiming));
-    if (w->slide_inflight) { LOC_HIP(hipEventSynchronize(w->slide_copied)); w->slide_inflight = false; }
+    bool fresh;
+    if (int rc = slide_allocate(w, densify, fresh)) return rc;
+    char* h;
+    LOC_HIP(w->slide.host(h));
     {   // the caller's arrays are read here and never after the call returns
-        char* h = w->h_slide;
-        int32_t* hd = (int32_t*)(h + at[0]);
-        if (drop_oldest) std::memcpy(hd, drop_oldest, piece[0]);
+        int32_t* hd = (int32_t*)(h + L.pre[0]);
+        if (drop_oldest) std::memcpy(hd, drop_oldest, L.len[0]);
         else for (size_t i = 0; i < N; ++i) hd[i] = 1;
         const void* const src[7] = {nullptr, new_r_counts, new_p_counts, new_r_idx, new_pose, new_r_val, new_p_val};
         for (int k = 1; k < 7; ++k)
-            if (piece[k] && src[k]) std::memcpy(h + at[k], src[k], piece[k]);
+            if (L.len[k] && src[k]) std::memcpy(h + L.pre[k], src[k], L.len[k]);
     }
     if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    LOC_HIP(hipMemcpyAsync(w->d_slide, w->h_slide, at[7], hipMemcpyHostToDevice, st));
-    LOC_HIP(hipEventRecord(w->slide_copied, st));
-    w->slide_inflight = true;
+    LOC_HIP(w->slide.send(L.end, st));
     locamd::SlideArgs sa{};
-    const char* d = w->d_slide;
-    sa.drop = (const int32_t*)(d + at[0]); sa.new_r_counts = (const int32_t*)(d + at[1]); sa.new_p_counts = (const int32_t*)(d + at[2]);
-    sa.new_r_idx = (const int32_t*)(d + at[3]); sa.new_pose = (const double*)(d + at[4]); sa.new_r_val = (const double*)(d + at[5]); sa.new_p_val = (const double*)(d + at[6]);
+    const char* d = w->slide.d;
+    sa.drop = (const int32_t*)(d + L.pre[0]); sa.new_r_counts = (const int32_t*)(d + L.pre[1]); sa.new_p_counts = (const int32_t*)(d + L.pre[2]);
+    sa.new_r_idx = (const int32_t*)(d + L.pre[3]); sa.new_pose = (const double*)(d + L.pre[4]); sa.new_r_val = (const double*)(d + L.pre[5]); sa.new_p_val = (const double*)(d + L.pre[6]);
     sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
     sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
-    if (int rc = slide_launches(w, st, sa, densify, m, false, nullptr)) return rc;
-    w->resident_min_anchors = locamd::slide_indices(c, w->n_anchors, n, w->res_counts.data(), w->mir_ridx.data(), w->mir_pidx.data(), rows, true).max_anchor;
+    if (int rc = slide_launches(w, st, sa, densify, fresh, false, nullptr)) return rc;
+    R.min_anchors = locamd::slide_indices(c, w->n_anchors, n, R.counts.data(), R.mir_ridx.data(), R.mir_pidx.data(), rows, true).max_anchor;
     return LOC_OK;
 }
 
@@ -1150,8 +1082,8 @@ int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* d
     if (int rc = flush_anchors(w)) return rc;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
     const bool densify = !w->opt.has_pinfo && w->caps.np_max > 0;
-    SlideBlock m;
-    if (int rc = slide_allocate(w, densify, m)) return rc;
+    bool fresh;
+    if (int rc = slide_allocate(w, densify, fresh)) return rc;
     if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
     locamd::SlideArgs sa{};
     sa.drop = (const int32_t*)drop_oldest_dev; sa.new_pose = (const double*)new_pose_dev;
@@ -1159,19 +1091,19 @@ int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* d
     sa.new_p_counts = (const int32_t*)new_p_counts_dev; sa.new_p_val = (const double*)new_p_val_dev;
     sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
     sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
-    if (int rc = slide_launches(w, st, sa, densify, m, true, (int32_t*)admit_dev)) return rc;
-    w->mirror_stale = true;   // (refresh_mirror: the next reader of the mirror fetches it)
+    if (int rc = slide_launches(w, st, sa, densify, fresh, true, (int32_t*)admit_dev)) return rc;
+    w->res.mirror_stale = true;   // (refresh_mirror: the next reader of the mirror fetches it)
     return LOC_OK;
 }
 
 int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
                                int32_t* s_idx, double* s_val, double* pinfo) {
-    if (!w || w->n_resident <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
     if (pinfo && !w->opt.has_pinfo) return locamd_fail(LOC_ERR_INVALID, "loc_window_download_tables: the handle has no table of full information matrices");
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = wait_resident(w)) return rc;
     const locamd::WindowCaps& c = w->caps;
-    const size_t N = (size_t)w->n_resident;
+    const size_t N = (size_t)w->res.n;
     void* dst[locamd::kWindowTables] = {nullptr};
     dst[kPoses] = poses; dst[kCounts] = counts; dst[locamd::kRVal] = r_val; dst[locamd::kPVal] = p_val; dst[locamd::kSVal] = s_val;
     dst[locamd::kRIdx] = r_idx; dst[locamd::kPIdx] = p_idx; dst[locamd::kSIdx] = s_idx;

@@ -55,6 +55,17 @@ int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b) {
     return first_bad.load();
 }
 
+// what loc_window_set_anchors may not shrink the anchor table below while the batch is resident
+int max_anchor_referenced(const WindowCaps& c, int64_t n, const int32_t* counts, const int32_t* r_idx) {
+    int max_anchor = 0;
+    for (int64_t i = 0; i < n; ++i)
+        for (int e = 0; e < counts[i * 4 + 1]; ++e) {
+            const int32_t v1 = r_idx[((size_t)i * c.nr_max + e) * 2 + 1];
+            if (v1 < 0 && -v1 > max_anchor) max_anchor = -v1;
+        }
+    return max_anchor;
+}
+
 // Host-side check of the pair tables of a joint covariance call: the kernels index LDS and the workspace with these slots
 int check_pairs(int64_t n, const int32_t* counts, const PairTables& pt) {
     if (pt.npair_max <= 0) return 0;

@@ -26,6 +26,9 @@ struct WinAux {
 // 0, or the first check that failed: 1 counts exceed the capacities, 2 / 3 range edge (vertex index / poses further apart than bw_max),
 // 4 prior edge vertex index, 5 / 6 SE3 edge (as 2 / 3)
 int check_instances(const WindowCaps& c, int n_anchors, const HostBatch& b);
+// the largest anchor the range rows of n checked instances reference, as -v1 (v1 = -1 - anchor; 0: none): counts [n][4], r_idx [n][nr_max][2],
+// rows beyond an instance's count are not read
+int max_anchor_referenced(const WindowCaps& c, int64_t n, const int32_t* counts, const int32_t* r_idx);
 // skip_prior_diagonal: the priors' information comes from a full-matrix table (loc_window_set_prior_information), p_val's diagonal is not read
 bool translation_only(const WindowCaps& c, int n_anchors, const HostBatch& b, bool skip_prior_diagonal = false);
 // the full information matrices of n_rows priors ([n_rows][36]) carry no rotation information: rows and columns 3 .. 5 exactly 0

@@ -29,17 +29,45 @@ struct HostBatch {
 struct DeviceTables { void* t[kWindowTables]; };
 
 // One block for n instances: up to eight prefix pieces, then the tables from first_table on in WindowTable order, every piece 16-byte
-// aligned; offsets of the pieces and the block's size.  The covariance pass has [cov | mask | status] in front of all eight tables, a joint
-// call [cov | mask | status | cross | pair counts | pairs] (four outputs, then its two input tables); the marginal-prior pass
-// [slot | prior | grad | shift | rank | status | drop] (six outputs, one input table).  The solve's prefix is
-// [poses | result], which come back as one copy, in front of the tables from kCounts on: tab[kPoses] = pre[0] = 0.
-struct BlockLayout { size_t pre[8], tab[kWindowTables], end; };
+// aligned; offsets of the pieces, their bytes as given and the block's size.  first_table = kWindowTables: prefix pieces alone.  The solve's
+// prefix is [poses | result], which come back as one copy, in front of the tables from kCounts on: tab[kPoses] = pre[0] = 0.
+struct BlockLayout { size_t pre[8], len[8], tab[kWindowTables], end; };
 inline BlockLayout pack_block(const WindowCaps& c, size_t n, const size_t* prefix_bytes, int n_prefix, int first_table) {
     auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
     BlockLayout L{};
-    for (int k = 0; k < n_prefix; ++k) { L.pre[k] = L.end; L.end += al(prefix_bytes[k]); }
+    for (int k = 0; k < n_prefix; ++k) { L.pre[k] = L.end; L.len[k] = prefix_bytes[k]; L.end += al(prefix_bytes[k]); }
     for (int t = first_table; t < kWindowTables; ++t) { L.tab[t] = L.end; L.end += al(n * table_bytes(c, t)); }
     return L;
+}
+// ---- every other block of capi_window.cpp, by name (tests/test_window_blocks_cpu.py holds each to the arithmetic it replaced) ----------------
+// a covariance call: the outputs [cov | mask | status], then all eight tables; a joint call (npair_max > 0) has
+// [cross | pair counts | pairs] between them: a fourth output and two more inputs
+inline BlockLayout covariance_layout(const WindowCaps& c, size_t n, size_t npair_max) {
+    const size_t nv = c.nv_max, P = npair_max;
+    const size_t pre[6] = {n * nv * 36 * sizeof(double), n * nv * sizeof(int32_t), n * sizeof(int32_t), n * P * 36 * sizeof(double), n * sizeof(int32_t), n * P * 2 * sizeof(int32_t)};
+    return pack_block(c, n, pre, P ? 6 : 3, kPoses);
+}
+// the marginal-prior pass: the outputs [slot | prior | grad | shift | rank | status], the input [drop], then all eight tables
+inline BlockLayout marginal_prior_layout(const WindowCaps& c, size_t n) {
+    const size_t pre[7] = {n * sizeof(int32_t), n * 48 * sizeof(double), n * 6 * sizeof(double), n * 6 * sizeof(double), n * sizeof(int32_t), n * sizeof(int32_t), n * sizeof(int32_t)};
+    return pack_block(c, n, pre, 7, kPoses);
+}
+// the pair tables of a resident joint call: [pair counts | pairs]
+inline BlockLayout resident_pairs_layout(size_t n, size_t npair_max) {
+    const size_t pre[2] = {n * sizeof(int32_t), n * npair_max * 2 * sizeof(int32_t)};
+    return pack_block(WindowCaps{}, n, pre, 2, kWindowTables);
+}
+// the staged inputs of a host slide: [drop | new_r_counts | new_p_counts | new_r_idx | new_pose | new_r_val | new_p_val]
+inline BlockLayout slide_inputs_layout(size_t n, size_t nr_new_max, size_t np_new_max) {
+    const size_t pre[7] = {n * sizeof(int32_t), n * sizeof(int32_t), n * sizeof(int32_t), n * nr_new_max * 2 * sizeof(int32_t), n * 12 * sizeof(double),
+                           n * nr_new_max * 5 * sizeof(double), n * np_new_max * 18 * sizeof(double)};
+    return pack_block(WindowCaps{}, n, pre, 7, kWindowTables);
+}
+// a slide's marginal pass, for the handle's B windows: [drop (zeros) | slot | rank | status | prior | grad | shift]
+enum SlideMarginalPiece { kMDrop, kMSlot, kMRank, kMStatus, kMPrior, kMGrad, kMShift };
+inline BlockLayout slide_marginal_layout(size_t B) {
+    const size_t pre[7] = {B * sizeof(int32_t), B * sizeof(int32_t), B * sizeof(int32_t), B * sizeof(int32_t), B * 48 * sizeof(double), B * 6 * sizeof(double), B * 6 * sizeof(double)};
+    return pack_block(WindowCaps{}, B, pre, 7, kWindowTables);
 }
 inline DeviceTables tables_at(char* base, const BlockLayout& L) {
     DeviceTables d;

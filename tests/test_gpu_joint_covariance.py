@@ -429,6 +429,42 @@ def test_resident_matches_host_bit_for_bit(gpu, name):
     a.close(); b.close()
 
 
+def test_resident_pair_table_grows_and_is_kept(gpu):
+    """One handle, three windows of four poses, resident joint calls with npair_max = 1, then 3 (the pair table grows), then 1 (the larger
+    table is kept): each has the bits of a fresh handle's only call."""
+    import torch
+    import localization_amd as la
+    from test_gpu_covariance import _observable_batch
+    from test_gpu_window_parity import ANCH
+    wb = _observable_batch(la, np.random.default_rng(733), 3, 4, False, False, translation_only=True)
+    B, T = wb.B, wb.caps[0]
+    per_window = {1: [[(0, 1)], [(1, 0)], [(3, 0)]], 3: [[(1, 0), (0, 0), (0, 1)], [(0, 3), (2, 1)], [(3, 3), (1, 2), (2, 0)]]}
+
+    def ready():
+        s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="numeric")
+        s.upload(G.copy_batch(la, wb)); s.solve_resident()
+        return s
+
+    def call(s, npm):
+        pairs, counts = _tables(wb, per_window[npm], npm=npm)
+        out = (torch.full((B, T, 36), 7.0, dtype=torch.float64, device=gpu), torch.full((B, T), 7, dtype=torch.int32, device=gpu),
+               torch.full((B,), 7, dtype=torch.int32, device=gpu), torch.full((B, npm, 36), 7.0, dtype=torch.float64, device=gpu))
+        torch.cuda.synchronize()
+        s.joint_covariance_resident(pairs, counts, *out)
+        torch.cuda.synchronize()
+        return tuple(t.cpu().numpy() for t in out)
+
+    one = ready()
+    got = [call(one, npm) for npm in (1, 3, 1)]
+    one.close()
+    for k, npm in enumerate((1, 3, 1)):
+        fresh = ready()
+        want = call(fresh, npm)
+        fresh.close()
+        assert not want[2].any() and np.isfinite(want[3]).all() and want[3][0, 0].any()
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(got[k], want)), (k, npm)
+
+
 # ---- refusals write nothing -----------------------------------------------------------------------------------------------------------------------
 def test_refusals_write_nothing(gpu):
     import torch

@@ -241,6 +241,62 @@ def test_a_small_host_solve_between_two_slides_leaves_the_chain_alone(gpu):
     assert final[1].result[:, :6].tobytes() == final[0].result[:, :6].tobytes()
 
 
+def _last_rows(ranges, keep):
+    """the last `keep` new rows of every window (tests/_slide_ref.new_rows: the anchor ranges, then the smoothness edge) under nr_new_max = keep"""
+    rc, ri, rv = ranges
+    B = len(rc)
+    counts = np.minimum(rc, keep).astype(np.int32)
+    r_idx, r_val = np.zeros((B, keep, 2), dtype=np.int32), np.zeros((B, keep, 5))
+    for b in range(B):
+        r_idx[b, :counts[b]] = ri[b, rc[b] - counts[b]:rc[b]]; r_val[b, :counts[b]] = rv[b, rc[b] - counts[b]:rc[b]]
+    return counts, r_idx, r_val
+
+
+def test_growing_input_blocks_and_alternating_entries(gpu):
+    """One handle, three windows of four poses: host slides with nr_new_max = 1, then 2 (the staged input block grows), a slide from device
+    arrays (the mirror goes stale), a host slide with seven row slots (the mirror is fetched, the block grows again).  After every slide the
+    tables are tests/_slide_ref.py's, bit for bit."""
+    import torch
+    import localization_amd as la
+    chains = [F.Chain(8600 + i, 9, 3 + i % 3) for i in range(3)]
+    wb = la.WindowBatch(3, *S.caps_for(4))
+    for i, ch in enumerate(chains):
+        F.add_chain_poses(wb, i, ch, 0, 4)
+    r, h = _solver(la, wb), _solver(la, wb, slide=None)
+    r.upload(wb)
+    g = _copy(la, wb)
+    dev = torch.device("cuda", 0)
+    for step, (keep, entry) in enumerate(((1, "host"), (2, "host"), (None, "device"), (None, "host"))):
+        what = f"step {step}: {entry} entry, nr_new_max {keep or F.NA_MAX + 2}"
+        r.solve_resident()
+        h.solve(g)
+        _same_solve(la, r, g, what)
+        pose, ranges = S.new_rows(chains, np.full(3, 4 + step), np.full(3, 3))
+        if keep is not None:
+            ranges = _last_rows(ranges, keep)
+        assert ranges[1].shape[1] == (keep or F.NA_MAX + 2)
+        out = _outs(3)
+        if entry == "host":
+            r.slide_resident(pose, ranges, None, None, out=out)
+        else:
+            t_in = [torch.from_numpy(a.copy()).to(dev) for a in (pose, *ranges)]
+            admit = torch.full((3,), -77, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            r.slide_resident_dev(t_in[0], tuple(t_in[1:]), None, None, out=(*out, admit))
+            torch.cuda.synchronize()
+            assert not admit.cpu().numpy().any()
+        slot, prior, _, _, rank, status = h.marginal_prior(g, 0)
+        got = _fetch(out)
+        for k, want in enumerate((slot, prior, rank, status)):
+            assert got[k].tobytes() == want.astype(got[k].dtype).tobytes(), (what, k, got[k], want)
+        g = S.slide_ref(la, g, slot, prior, pose, ranges, None, None)
+        S.assert_same_tables(r.download_batch(), g, what)
+    r.solve_resident()
+    h.solve(g)
+    _same_solve(la, r, g, "after the last slide")
+    r.close(); h.close()
+
+
 # ---- 5. refusals leave the batch and the outputs alone -------------------------------------------------------------------------------------------------
 def _refused(la, s, code, args, **kw):
     before = s.download_batch()
