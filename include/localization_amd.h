@@ -557,6 +557,47 @@ int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* d
  * LOC_ERR_INVALID when the handle has none.  Synchronous (waits for the last resident launch). */
 int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
                                int32_t* s_idx, double* s_val, double* pinfo);
+/* Edge audit and outlier removal ("Edge audit and outlier removal"): the block Localization::solve() keeps after
+ * optimizer.optimize() (localization.cpp:172-181) — with more than 100 active edges, every range edge whose chi2() exceeds 2.0 gets
+ * setLevel(1) and is left out of every later initializeOptimization().  Two things: the chi2 of every edge of every window, and that rule
+ * applied in place to the resident batch by the GPU.  Every structure, every handle state (endpoint-1 lever arms, a table of full
+ * information matrices): no dispatch, no LOC_ERR_UNSUPPORTED but the one below.
+ * Evaluated at x = the poses given (_host) or loc_window_poses_device()'s current content (_resident): a function of the returned estimate
+ * alone, not of g2o's "last evaluated state".  chi2 of a row is BaseEdge::chi2() = e^T Omega e, NOT robustified:
+ *   range    e = ||X0 o0 - p1|| - meas, p1 = X1 o1 / anchor + o1 with endpoint-1 lever arms set, X1.t / the anchor without; chi2 = e (info e).
+ *            One arithmetic form whatever loc_window_set_jacobian says (the plain-CPU operation order of the numeric solves): the bits do not
+ *            depend on the Jacobian mode.
+ *   prior    e = toVectorMQT(Z^-1 X), W = diag(p_val[12..17]), or the row of loc_window_set_prior_information's table when one is set
+ *   EdgeSE3  e = toVectorMQT(Z^-1 Xi^-1 Xj), Omega = the 6x6 of s_val; the robust flag does not enter
+ * Outputs (any may be NULL):
+ *   r_chi2 double [n][nr_max], p_chi2 double [n][np_max], s_chi2 double [n][ns_max]    slots at or beyond the window's count are written 0
+ *   total  double [n]   the sum over all rows of the window
+ *   active int32  [n]   (range rows with information != 0) + np + ns
+ * LEVEL 1 IS INFORMATION EXACTLY 0.0: such a range row adds exact zeros to chi2, H and b in every kernel.  So a caller's own zero-information
+ * range is at level 1: it is not counted in `active` and never flagged.  And result[b][0] of a later solve does not contain a removed row
+ * (g2o's OptimizableGraph::chi2() would keep its stale last value).
+ * loc_window_edge_chi2_host: host arrays in loc_window_solve_host's layouts (poses is not written), stateless and synchronous, the resident
+ * batch is left alone; LOC_ERR_INVALID for what loc_window_solve_host refuses.
+ * _resident calls: caller-owned DEVICE arrays, asynchronous on hip_stream (NULL = the handle's own stream), ordered after the last resident
+ * launch and before the next one; nothing is read on the host, nothing synchronises, the host mirror of a slide stays as it is.
+ * LOC_ERR_INVALID, with nothing launched or written: a NULL handle, nothing uploaded, no resident solve since the upload, a table of full
+ * matrices that describes fewer windows than are resident.
+ * loc_window_prune_resident (the reference: chi2_max = 2.0, min_edges = 100), per window at x:
+ *   if active[b] > min_edges, every range row with information != 0 and chi2 > chi2_max gets removed[b][e] = 1 and r_val[b][e][1] = 0.0
+ * Both comparisons are strict, as in the reference; a NaN chi2 compares false and stays in; the decision uses the active count from before any
+ * removal of this call.  Nothing else changes: no other entry of any table, no count, no pose, not the next solve's input estimates, none of
+ * the handle's verdicts (they read no range value).  removed int32 [n][nr_max]: 0 for rows not removed and for padding; n_removed int32 [n]:
+ * the rows removed; either may be NULL.  Also LOC_ERR_INVALID: chi2_max NaN or negative, min_edges < 0.  LOC_ERR_UNSUPPORTED: the resident
+ * batch's verdict is LOC_WINDOW_KERNEL_ARROW3 — that kernel solves from records packed at upload, which a store into r_val does not reach
+ * (every other solve kernel and covariance pass reads r_val at launch); loc_window_edge_chi2_resident serves such a batch normally.
+ * loc_window_last_covariance_ms reports the launch. */
+int loc_window_edge_chi2_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                              const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val,
+                              double* r_chi2, double* p_chi2, double* s_chi2, double* total, int32_t* active);
+int loc_window_edge_chi2_resident(loc_window* w, void* hip_stream, void* r_chi2_dev, void* p_chi2_dev, void* s_chi2_dev,
+                                  void* total_dev, void* active_dev);
+int loc_window_prune_resident(loc_window* w, void* hip_stream, double chi2_max, int32_t min_edges,
+                              void* removed_dev /* int32 [n][nr_max] */, void* n_removed_dev /* int32 [n] */);
 
 /* ================================================================================================
  * Node front-end — `class Localization` behind the ABI (one moving tag, its ring window, its anchors).

@@ -1096,6 +1096,67 @@ int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* d
     return LOC_OK;
 }
 
+// ---- the per-edge chi2 audit and the outlier-range removal (edge_audit_kernel.hip; DESIGN.md §2, "Edge audit and outlier removal") ----------------
+// stateless and synchronous (staged_call: the resident batch's arrays and the host path's cached verdict are not touched); every structure
+// and every handle state, so there is no dispatch and no UNSUPPORTED case
+int loc_window_edge_chi2_host(loc_window* w, int64_t n, const int32_t* counts, const double* poses, const int32_t* r_idx, const double* r_val,
+                              const int32_t* p_idx, const double* p_val, const int32_t* s_idx, const double* s_val,
+                              double* r_chi2, double* p_chi2, double* s_chi2, double* total, int32_t* active) {
+    const locamd::HostBatch b{n, poses, counts, r_val, p_val, s_val, r_idx, p_idx, s_idx};
+    if (int rc = validate_instances(w, b)) return rc;
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    const locamd::BlockLayout L = locamd::edge_audit_layout(w->caps, (size_t)n);
+    return staged_call(w, L, b, {}, {{r_chi2, 0}, {p_chi2, 1}, {s_chi2, 2}, {total, 3}, {active, 4}}, "launch_window_edge_audit",
+                       [&](const locamd::WindowArgs& a0, char* d, hipStream_t st) {
+        locamd::WindowArgs a = a0;
+        a.r_off1 = w->opt.has_off1 ? w->d_roff1 : nullptr;   // (window_args hands the lever arms of endpoint 1 to the solves alone)
+        const locamd::EdgeAudit x{(double*)(d + L.pre[0]), (double*)(d + L.pre[1]), (double*)(d + L.pre[2]), (double*)(d + L.pre[3]), (int32_t*)(d + L.pre[4]),
+                                  nullptr, 0.0, 0, nullptr, nullptr};
+        return locamd::launch_window_edge_audit(a, x, st);
+    });
+}
+
+// what the two resident entries share: the covariance call's refusals, then one launch in stream order after the last resident launch and
+// before the next one (loc_window_slide_resident_dev's way); nothing is read on the host, nothing synchronises, the mirror stays as it is
+static int resident_audit_launch(loc_window* w, void* hip_stream, const char* unsolved, bool prune, locamd::EdgeAudit x) {
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, unsolved);
+    if (int rc = check_pinfo_covers_resident(w)) return rc;
+    if (prune) {
+        if (!(x.chi2_max >= 0.0) || x.min_edges < 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_prune_resident: chi2_max must be a number >= 0 and min_edges >= 0");
+        // build_arrow_aux packed measurement and information into ArrowAux::rec at upload: a store into r_val would not reach that solve
+        // (every other solve kernel and covariance pass reads range values from r_val at launch)
+        if (resident_topology(w) == LOC_WINDOW_KERNEL_ARROW3)
+            return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_prune_resident: the resident batch is solved by arrow3_lm_kernel from records packed at upload");
+    }
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    locamd::WindowArgs a = window_args(w, w->dev, w->res.n, nullptr, w->d_anchors, nullptr);
+    a.r_off1 = w->opt.has_off1 ? w->d_roff1 : nullptr;
+    if (prune) x.prune_r_val = (double*)w->dev.t[locamd::kRVal];
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    const hipError_t e = locamd::launch_window_edge_audit(a, x, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_edge_audit");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipEventRecord(w->resident_done, st));   // whatever touches the resident arrays next waits for this launch as well
+    w->resident_inflight = true;
+    w->cov_pending = true;
+    return LOC_OK;
+}
+
+int loc_window_edge_chi2_resident(loc_window* w, void* hip_stream, void* r_chi2_dev, void* p_chi2_dev, void* s_chi2_dev, void* total_dev, void* active_dev) {
+    return resident_audit_launch(w, hip_stream, "loc_window_edge_chi2_resident: no resident solve has run since the upload", false,
+                                 locamd::EdgeAudit{(double*)r_chi2_dev, (double*)p_chi2_dev, (double*)s_chi2_dev, (double*)total_dev, (int32_t*)active_dev, nullptr, 0.0, 0, nullptr, nullptr});
+}
+
+int loc_window_prune_resident(loc_window* w, void* hip_stream, double chi2_max, int32_t min_edges, void* removed_dev, void* n_removed_dev) {
+    return resident_audit_launch(w, hip_stream, "loc_window_prune_resident: no resident solve has run since the upload", true,
+                                 locamd::EdgeAudit{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, chi2_max, min_edges, (int32_t*)removed_dev, (int32_t*)n_removed_dev});
+}
+
 int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
                                int32_t* s_idx, double* s_val, double* pinfo) {
     if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");

@@ -188,6 +188,19 @@ hipError_t launch_window_slide(const SlideArgs& s, bool densify, hipStream_t str
 // LOC_ERR_UNSUPPORTED (code 7) and leaves the window as it was (densify: its table rows become diag(p_val[12..17]) all the same)
 hipError_t launch_window_slide_dev(const SlideArgs& s, int n_anchors, int32_t* admit, bool densify, hipStream_t stream);
 
+// the per-edge chi2 audit and the outlier-range removal (edge_audit_kernel.hip; DESIGN.md §2, "Edge audit and outlier removal"): one wave per
+// window at a.poses, every structure; a.r_off1 / a.p_info as the handle has them.  All device arrays.
+struct EdgeAudit {
+    double *r_chi2, *p_chi2, *s_chi2;   // the audit's outputs, [B][nr_max] / [B][np_max] / [B][ns_max] (slots beyond a window's count: 0), each may be nullptr
+    double* total; int32_t* active;     // [B], each may be nullptr
+    // the removal (prune_r_val != nullptr: a.r_val itself, writable; the audit's outputs are then not written): a window with active > min_edges
+    // gets information 0.0 and removed = 1 on every range row with information != 0 and chi2 > chi2_max
+    double* prune_r_val;
+    double chi2_max; int min_edges;
+    int32_t *removed, *n_removed;       // [B][nr_max], [B], each may be nullptr
+};
+hipError_t launch_window_edge_audit(const WindowArgs& a, const EdgeAudit& x, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

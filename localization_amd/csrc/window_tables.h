@@ -52,6 +52,11 @@ inline BlockLayout marginal_prior_layout(const WindowCaps& c, size_t n) {
     const size_t pre[7] = {n * sizeof(int32_t), n * 48 * sizeof(double), n * 6 * sizeof(double), n * 6 * sizeof(double), n * sizeof(int32_t), n * sizeof(int32_t), n * sizeof(int32_t)};
     return pack_block(c, n, pre, 7, kPoses);
 }
+// the edge audit: the outputs [r_chi2 | p_chi2 | s_chi2 | total | active], then all eight tables
+inline BlockLayout edge_audit_layout(const WindowCaps& c, size_t n) {
+    const size_t pre[5] = {n * c.nr_max * sizeof(double), n * c.np_max * sizeof(double), n * c.ns_max * sizeof(double), n * sizeof(double), n * sizeof(int32_t)};
+    return pack_block(c, n, pre, 5, kPoses);
+}
 // the pair tables of a resident joint call: [pair counts | pairs]
 inline BlockLayout resident_pairs_layout(size_t n, size_t npair_max) {
     const size_t pre[2] = {n * sizeof(int32_t), n * npair_max * 2 * sizeof(int32_t)};

@@ -329,6 +329,52 @@ class WindowSolver(_lib.Handle):
             wb.p_info = pinfo   # (LOC_ERR_INVALID: the handle has no table)
         return wb
 
+    # ---- the per-edge chi2 audit and the reference's outlier-range removal (loc_window_edge_chi2_* / loc_window_prune_resident)
+    def edge_chi2(self, wb: WindowBatch, out=None):
+        """chi2 = e^T Omega e (not robustified) of every edge of every window at wb.poses, any structure: returns (r_chi2 [B][nr_max], p_chi2
+        [B][np_max], s_chi2 [B][ns_max] — slots beyond a window's count 0 —, total [B], active int32 [B] = range rows with information != 0
+        + priors + EdgeSE3).  out: the caller's five arrays, each may be None (that output is skipped).  Hands wb's endpoint-1 lever arms and
+        prior table to the handle first, as solve() does."""
+        assert wb.caps == self.caps and wb.B <= self.B
+        self._endpoint1(wb)
+        self._prior_information(wb)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if out is None:
+            out = (np.zeros((wb.B, max(self.caps[1], 1))), np.zeros((wb.B, max(self.caps[2], 1))), np.zeros((wb.B, max(self.caps[3], 1))),
+                   np.zeros(wb.B), np.zeros(wb.B, dtype=np.int32))
+        args = []
+        for x, dt, size in zip(out, (np.float64,) * 4 + (np.int32,), (wb.B * self.caps[1], wb.B * self.caps[2], wb.B * self.caps[3], wb.B, wb.B)):
+            assert x is None or (x.dtype == dt and x.size >= size and x.flags["C_CONTIGUOUS"])
+            args.append(None if x is None else x.ctypes.data_as(ip if dt == np.int32 else dp))
+        check(self.L.loc_window_edge_chi2_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
+                                               wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
+                                               wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
+                                               wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp), *args))
+        return tuple(out)
+
+    def edge_chi2_resident(self, r_chi2, p_chi2, s_chi2, total, active, stream=None):
+        """The same for the uploaded batch at its solved poses (after solve_resident), asynchronous, into torch device tensors (float64
+        [B][nr_max] / [B][np_max] / [B][ns_max] / [B], int32 [B]); each may be None.  stream: a torch stream (None: the handle's own)."""
+        n = getattr(self, "_resident", 0)
+        ptrs = []
+        for t, numel in zip((r_chi2, p_chi2, s_chi2, total, active), (n * self.caps[1], n * self.caps[2], n * self.caps[3], n, n)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= numel)
+            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_edge_chi2_resident(self.h, st, *ptrs))
+
+    def prune_resident(self, chi2_max=2.0, min_edges=100, removed=None, n_removed=None, stream=None):
+        """The reference's removal rule on the uploaded batch, in place on the device (after solve_resident): a window with more than min_edges
+        active edges gets information 0.0 on every range row with information != 0 and chi2 > chi2_max at the solved poses.  removed int32
+        [B][nr_max], n_removed int32 [B]: torch device tensors, each may be None.  Asynchronous on stream (None: the handle's own)."""
+        n = getattr(self, "_resident", 0)
+        ptrs = []
+        for t, numel in ((removed, n * self.caps[1]), (n_removed, n)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= numel)
+            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_prune_resident(self.h, st, float(chi2_max), int(min_edges), *ptrs))
+
     def covariance_plan(self, wb: WindowBatch):
         """covariance_plan(wb) for this handle's capacities"""
         assert wb.caps == self.caps
