@@ -46,6 +46,7 @@
 // B transposed to [border row][component][chain row] (coalesced for the thread-parallel phases, but the forward sweep's 39 lanes
 // then touch 39 cache lines per load: the sweep +20 %, the whole solve +7 %).
 #include "window_device.h"
+#include "window_layouts.h"
 #include "lm_damping.h"
 
 #include <float.h>
@@ -55,19 +56,8 @@
 
 namespace locamd {
 
-constexpr int ARROW_NW = 4;   // waves per instance = segments the chain is cut into at most
-
-// doubles of HBM workspace per instance: chain translations (two buffers) + the stale step, B rows, per-(row, border pose) shares
-static __host__ __device__ inline size_t window_arrow3_workspace_doubles_dev(const WindowCaps& c, int nb_max) {
-    return (size_t)c.nv_max * 9 + (size_t)c.nv_max * 3 * nb_max * 3 + (size_t)c.nv_max * nb_max * 9;
-}
-size_t window_arrow3_workspace_doubles(const WindowCaps& c, int nb_max) { return window_arrow3_workspace_doubles_dev(c, nb_max); }
-// doubles of LDS per instance
-static __host__ __device__ inline size_t arrow3_lds_doubles(int nv_max, int nb_max) {
-    const size_t D = 3 * (size_t)nb_max, D16 = 16 * ((D + 15) / 16);
-    return (size_t)nv_max * 28 + D * (D + 1) / 2 + (D + 1) * (D + 2) / 2 + 3 * D + ARROW_NW * D + ARROW_NW * 4 * D16 * 3 + 6 * (size_t)nb_max + 16 + 3 * (size_t)kArrowMaxAnchors;
-}
-size_t window_arrow3_lds_bytes(const WindowCaps& c, int nb_max) { return arrow3_lds_doubles(c.nv_max, nb_max) * sizeof(double); }
+size_t window_arrow3_workspace_doubles(const WindowCaps& c, int nb_max) { return arrow3_ws_layout(c, nb_max).doubles; }
+size_t window_arrow3_lds_bytes(const WindowCaps& c, int nb_max) { return arrow3_lds_layout(c.nv_max, nb_max).bytes; }
 
 namespace {
 
@@ -907,22 +897,24 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
         c.ppk0 |= (unsigned long long)(x.jpch[k] & 255) << (8 * k); c.ppk1 |= (unsigned long long)(x.jpch[8 + k] & 255) << (8 * k);
     }
     const int n = c.n, nb = c.nb, D = c.D;
-    {   // LDS carve-up (sized by the batch's capacities: arrow3_lds_doubles)
+    {
+        const Arrow3Lds y = arrow3_lds_layout(cp.nv_max, x.nb_max);
         double* q = ldsA;
-        c.PK = q; q += (size_t)cp.nv_max * 16; c.GZ = q; q += (size_t)cp.nv_max * 12;
-        c.C0 = q; q += (size_t)Dm * (Dm + 1) / 2; c.S = q; q += (size_t)(Dm + 1) * (Dm + 2) / 2;
-        c.bB = q; q += Dm; c.xB = q; q += Dm; c.xsB = q; q += Dm;
-        c.RA = q; q += (size_t)ARROW_NW * Dm;
-        c.FX = q; q += (size_t)ARROW_NW * 4 * D16m * 3;
-        c.TB = q; q += (size_t)6 * x.nb_max;
-        c.red = q; q += 16;
+        c.PK = q; q += y.PK.n; c.GZ = q; q += y.GZ.n;
+        c.C0 = q; q += y.C0.n; c.S = q; q += y.S.n;
+        c.bB = q; q += y.bB.n; c.xB = q; q += y.xB.n; c.xsB = q; q += y.xsB.n;
+        c.RA = q; q += y.RA.n;
+        c.FX = q; q += y.FX.n;
+        c.TB = q; q += y.TB.n;
+        c.red = q; q += y.red.n;
         c.AN = q;
     }
     {
-        double* w = x.ws + (size_t)inst * window_arrow3_workspace_doubles_dev(cp, x.nb_max);
-        c.TT = w; w += (size_t)cp.nv_max * 6;
-        c.XS = w; w += (size_t)cp.nv_max * 3;
-        c.BB = w; w += (size_t)cp.nv_max * 3 * x.nb_max * 3;
+        const Arrow3Ws y = arrow3_ws_layout(cp, x.nb_max);
+        double* w = x.ws + (size_t)inst * y.doubles;
+        c.TT = w; w += y.TT.n;
+        c.XS = w; w += y.XS.n;
+        c.BB = w; w += y.BB.n;
         c.CS = w;
         c.npad = (size_t)cp.nv_max;
     }
@@ -1015,7 +1007,7 @@ __global__ void __launch_bounds__(64 * ARROW_NW, 1) arrow3_lm_kernel(const Windo
 
 template <int JAC, int NTI>
 hipError_t launch_arrow3_t(const WindowArgs& a, const ArrowAux& x, size_t lds, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&arrow3_lm_kernel<JAC, NTI>>(160 * 1024 - 512);
+    const hipError_t e = allow_dynamic_lds<&arrow3_lm_kernel<JAC, NTI>>((int)kArrow3MaxLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((arrow3_lm_kernel<JAC, NTI>), dim3((unsigned)a.B), dim3(64 * ARROW_NW), lds, stream, a, x);
     return hipGetLastError();
@@ -1025,8 +1017,8 @@ hipError_t launch_arrow3_t(const WindowArgs& a, const ArrowAux& x, size_t lds, h
 
 hipError_t launch_window_arrow3(const WindowArgs& a, const ArrowAux& x, hipStream_t stream) {
     if (a.B <= 0 || !x.ws || x.nb_max < 1 || x.nb_max > 15 || x.jmax < 1 || x.jpmax < 1) return hipErrorInvalidValue;
-    const size_t lds = window_arrow3_lds_bytes(a.caps, x.nb_max);
-    if (lds > 160 * 1024 - 512) return hipErrorInvalidValue;
+    if (!arrow3_fits(a.caps, x.nb_max)) return hipErrorInvalidValue;
+    const size_t lds = arrow3_lds_layout(a.caps.nv_max, x.nb_max).bytes;
     const int nti = (3 * x.nb_max + 15) / 16;
     const int sel = (a.jacobian ? 3 : 0) + nti - 1;
     switch (sel) {

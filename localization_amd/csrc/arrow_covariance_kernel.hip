@@ -33,40 +33,6 @@ namespace {
 
 extern __shared__ double aclds[];
 
-constexpr int kAcThreads = 256;
-constexpr int kAcChunk = 256;     // edges linearised per pass (one per thread)
-constexpr int kAcBS = 36;         // row stride of B, Y, C: the widest border (12 slots)
-constexpr int kAcRec = 7;         // range record: rho' info, J0 (3), J1 (3)
-constexpr int kAcRecG = 8;        // its stride in the workspace
-
-// LDS layout of one window (offsets in doubles; the int tables follow the doubles)
-struct ArrowCovLayout {
-    int hd, ho, dg, cc, ig, rec, ints, ei, cnt, mk, flag;
-    size_t bytes;
-};
-__host__ __device__ inline ArrowCovLayout arrow_cov_layout(int nvm) {
-    ArrowCovLayout l;
-    int p = 0;
-    l.hd = p; p += nvm * 9;            // H_ii -> S_i^-1 -> [A^-1]_ii -> Sigma_i (chain poses)
-    l.ho = p; p += nvm * 9;            // H_{i+1,i} -> K_i
-    l.dg = p; p += nvm * 3;            // diag(H) of every coordinate, chain and border (the scale of the relative pivot test)
-    l.cc = p; p += kAcBS * kAcBS;      // C -> S -> its Cholesky factor (lower triangle) -> S^-1
-    l.ig = p; p += kAcBS;              // reciprocal diagonal of the factor
-    l.rec = p; p += kAcChunk * kAcRec; // the records of the current chunk; afterwards L^-1 (36 x 36)
-    l.ints = p;
-    int q = 0;
-    l.ei = q; q += 2 * kAcChunk;       // the chunk's pose slots
-    l.cnt = q; q += nvm;               // entries of a chain pose's list
-    l.mk = q; q += nvm;
-    l.flag = q; q += 2;                // border size; "no pivot failed"
-    l.bytes = (size_t)p * sizeof(double) + (size_t)q * sizeof(int);
-    return l;
-}
-
-__host__ __device__ inline size_t arrow_cov_ws_doubles(const WindowCaps& c, int cap) {
-    return (size_t)c.nr_max * kAcRecG + 2 * (size_t)c.nv_max * 3 * kAcBS + ((size_t)c.nv_max * cap + 1) / 2;
-}
-
 template <int JAC, bool JOINT>
 __global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const WindowArgs a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int BS = kAcBS;
@@ -617,7 +583,7 @@ __global__ void __launch_bounds__(kAcThreads) arrow_covariance_kernel(const Wind
 
 template <int JAC, bool JOINT>
 hipError_t launch_arrow_cov_j(const WindowArgs& a, double* ws, int cap, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&arrow_covariance_kernel<JAC, JOINT>>(160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&arrow_covariance_kernel<JAC, JOINT>>((int)kCovMaxLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((arrow_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(kAcThreads), lds, stream, a, ws, cap, cov, mask, status, pp);
     return hipGetLastError();
@@ -635,8 +601,8 @@ size_t window_arrow_covariance_workspace_doubles(const WindowCaps& c, int cap) {
 hipError_t launch_window_arrow_covariance(const WindowArgs& a, double* ws, int cap, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     if (!ws || cap < 1) return hipErrorInvalidValue;
-    const size_t lds = window_arrow_covariance_lds_bytes(a.caps);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!cov_arrow_fits(a.caps)) return hipErrorInvalidValue;
+    const size_t lds = arrow_cov_layout(a.caps.nv_max).bytes;
     return a.jacobian ? launch_arrow_cov_t<1>(a, ws, cap, lds, cov, mask, status, pp, stream) : launch_arrow_cov_t<0>(a, ws, cap, lds, cov, mask, status, pp, stream);
 }
 

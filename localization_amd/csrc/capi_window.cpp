@@ -12,6 +12,7 @@
 #include "capi_host.h"
 #include "window_dispatch.h"
 #include "window_kernel.h"
+#include "window_layouts.h"
 #include "window_structure.h"
 #include "window_tables.h"
 
@@ -122,8 +123,7 @@ size_t loc_window_lds_bytes(const loc_window_caps* caps) {
     if (!caps) return 0;
     if (caps->nv_max <= 0) return 0;
     locamd::WindowCaps c = to_caps(caps);
-    const size_t in_lds = locamd::window_lds_bytes(c, false);
-    return (in_lds <= 160 * 1024 - 512 && c.nv_max <= 64) ? in_lds : locamd::window_lds_bytes(c, true) + 36 * sizeof(double);  // large windows: index tables + exchange block; the rest in the HBM workspace
+    return locamd::window_arrays_in_lds(c) ? locamd::window_lds_bytes(c, false) : locamd::window_lds_bytes(c, true) + 36 * sizeof(double);  // large windows: index tables + exchange block; the rest in the HBM workspace
 }
 
 // every device buffer of one batch's slot
@@ -167,20 +167,8 @@ int loc_window_create(loc_window** out, int32_t device, int64_t batch, const loc
     if (!w) return locamd_fail(LOC_ERR_INVALID, "out of host memory");
     w->device = device; w->B = batch; w->n_anchors = n_anchors; w->anchors_cap = n_anchors > 0 ? n_anchors : 1; w->iterations = maximum_iteration;
     w->caps = to_caps(caps);
-    {   // the kernels' LDS needs depend on the capacities alone
-        const locamd::WindowCaps& c = w->caps;
-        locamd::DispatchFits& f = w->fits;
-        f.nv_max = c.nv_max;
-        f.wave6 = c.nv_max <= 64 && locamd::window_wave6_lds_bytes(c) <= locamd::kWave6MaxLds;
-        f.wave6_se3 = c.nv_max <= 63 && c.ns_max <= 64 && locamd::window_wave6_lds_bytes(c, true) <= locamd::kWave6MaxLds;
-        f.wave3 = c.nv_max <= 64 && locamd::window_wave3_lds_bytes(c) <= 64 * 1024;
-        f.wave3_pinfo = c.nv_max <= 64 && locamd::window_wave3_lds_bytes(c, true) <= 64 * 1024;
-        f.cov_chain = locamd::window_covariance_lds_bytes(c, false) <= 160 * 1024;
-        f.cov_arrow = locamd::window_arrow_covariance_lds_bytes(c) <= 160 * 1024;
-        f.cov_envelope = locamd::window_envelope_covariance_lds_bytes(c) <= 160 * 1024;
-    }
-    // windows of more than 64 poses always keep their arrays in the HBM workspace (their structure tables alone fill the LDS)
-    const bool global_a = locamd::window_lds_bytes(w->caps, false) > 160 * 1024 - 512 || w->caps.nv_max > 64;
+    w->fits = locamd::dispatch_fits(w->caps);
+    const bool global_a = !locamd::window_arrays_in_lds(w->caps);
     const size_t B = (size_t)batch;
     const size_t na = (size_t)(n_anchors > 0 ? n_anchors : 1);
     hipError_t e = hipSuccess;

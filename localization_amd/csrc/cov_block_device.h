@@ -7,16 +7,13 @@
 #pragma once
 #include "se3_edge_device.h"
 #include "cov_device.h"
-#include "window_kernel.h"
+#include "window_layouts.h"
 
 #include <float.h>
 #include <math.h>
 
 namespace locamd {
 namespace {
-
-constexpr int kCovChunk = 64;   // edges linearised per pass (one per lane)
-constexpr int kCovSRec = 21 + 21 + 36;   // EdgeSE3 record: H_ii, H_jj (lower triangles), the coupling block (rows: the later pose, column-major)
 
 #define LOCAMD_CV_TRI(r, c) ((r) >= (c) ? (r) * ((r) + 1) / 2 + (c) : (c) * ((c) + 1) / 2 + (r))
 

@@ -32,32 +32,6 @@ namespace {
 
 extern __shared__ double cvlds[];
 
-// LDS layout of one window (offsets in doubles; the int tables follow the doubles)
-struct CovLayout {
-    int hd, ho, kb, dg, rrec, prec, srec, ints, ri, pi, si, mk;
-    size_t bytes;
-};
-__host__ __device__ inline CovLayout cov_layout(int nvl, int D, bool priors, bool se3) {
-    CovLayout l;
-    const int DD = D * D;
-    int p = 0;
-    l.hd = p; p += nvl * DD;                   // H_ii -> S_i -> S_i^-1 -> Sigma_i
-    l.ho = p; p += nvl * DD;                   // H_{i+1,i} -> K_i
-    l.kb = p; p += DD;                         // K_i / T of the current step
-    l.dg = p; p += nvl * D;                    // diag(H) of every coordinate (the scale of the relative pivot test)
-    l.rrec = p; p += kCovChunk * (1 + 2 * D);  // range: rho' info, J0 (D), J1 (D)
-    l.prec = p; if (priors) p += kCovChunk * 21;
-    l.srec = p; if (se3) p += kCovChunk * kCovSRec;
-    l.ints = p;
-    int q = 0;
-    l.ri = q; q += 2 * kCovChunk;
-    l.pi = q; if (priors) q += kCovChunk;
-    l.si = q; if (se3) q += 2 * kCovChunk;
-    l.mk = q; q += nvl;
-    l.bytes = (size_t)p * sizeof(double) + (size_t)q * sizeof(int);
-    return l;
-}
-
 template <int D, int JAC, bool JOINT, bool PINFO = false>
 __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int nvl, bool priors, bool se3, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int DD = D * D;
@@ -179,7 +153,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(const WindowArgs a, int 
 
 template <int D, int JAC, bool JOINT, bool PINFO = false>
 hipError_t launch_cov_j(const WindowArgs& a, int nvl, bool priors, bool se3, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC, JOINT, PINFO>>(160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&covariance_kernel<D, JAC, JOINT, PINFO>>((int)kCovMaxLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((covariance_kernel<D, JAC, JOINT, PINFO>), dim3((unsigned)a.B), dim3(64), lds, stream, a, nvl, priors, se3, cov, mask, status, pp);
     return hipGetLastError();
@@ -192,16 +166,14 @@ hipError_t launch_cov_t(const WindowArgs& a, int nvl, bool priors, bool se3, siz
 
 }  // namespace
 
-size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3) {
-    return cov_layout(c.nv_max, d3 ? 3 : 6, c.np_max > 0, !d3 && c.ns_max > 0).bytes;
-}
+size_t window_covariance_lds_bytes(const WindowCaps& c, bool d3) { return cov_layout(c, d3).bytes; }
 
 hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     if (a.caps.nv_max > 64) return hipErrorInvalidValue;
     const bool priors = a.caps.np_max > 0, se3 = !d3 && a.caps.ns_max > 0;
-    const size_t lds = window_covariance_lds_bytes(a.caps, d3);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!cov_chain_fits(a.caps, d3)) return hipErrorInvalidValue;
+    const size_t lds = cov_layout(a.caps, d3).bytes;
     if (a.p_info) {   // (the host admits a table here only where structured_pinfo holds: window_dispatch.cpp, cov_admitted — Chain3 alone)
         if (!d3) return hipErrorInvalidValue;
         return a.jacobian ? launch_cov_t<3, 1, true>(a, a.caps.nv_max, priors, se3, lds, cov, mask, status, pp, stream)

@@ -40,35 +40,6 @@ namespace {
 
 extern __shared__ double evlds[];
 
-constexpr int kEvThreads = 256;
-constexpr int kEvSlots = kEvThreads / 36;          // 7 blocks in flight
-constexpr int kEvRangeChunk = 256, kEvPriorChunk = 128, kEvSe3Chunk = 64;   // edges linearised per pass
-constexpr int kEvRec = kEvSe3Chunk * kCovSRec;     // doubles of the record region (>= 256 * 13, 128 * 21)
-constexpr int kEvLdsRows = kEvRec / 72;            // a column of at most this many rows keeps its two copies (below) in the record region
-
-// LDS layout of one window (offsets in doubles; the int tables follow the doubles)
-struct EnvLayout {
-    int sinv, rec, ints, ei, wc, first, off, last, list, mk;
-    size_t bytes;
-};
-__host__ __device__ inline EnvLayout env_layout(int nvm) {
-    EnvLayout l;
-    int p = 0;
-    l.sinv = p; p += 36;       // S_j^-1 of the current column
-    l.rec = p; p += kEvRec;    // the records of the current chunk (one kind at a time)
-    l.ints = p;
-    int q = 0;
-    l.ei = q; q += 2 * kEvRangeChunk;   // the chunk's pose slots
-    l.wc = q; q += 4;                   // members found by each wave (the ordered compaction of struct(j))
-    l.first = q; q += nvm;
-    l.off = q; q += nvm + 1;            // first block of row i
-    l.last = q; q += nvm;               // the last row that reaches column j
-    l.list = q; q += nvm;               // struct(j), ascending
-    l.mk = q; q += nvm;
-    l.bytes = (size_t)p * sizeof(double) + (size_t)q * sizeof(int);
-    return l;
-}
-
 // struct(j) into list[] in ascending order; returns its size (the same value in every thread).  Barriers inside: call it uniformly.
 __device__ __forceinline__ int env_column_rows(int j, const int* first, const int* last, int* list, int* wc, int tid) {
     const int top = last[j];
@@ -437,7 +408,7 @@ __global__ void __launch_bounds__(kEvThreads, 2) envelope_covariance_kernel(cons
 
 template <int JAC, bool JOINT, bool PINFO>
 hipError_t launch_env_cov_p(const WindowArgs& a, double* ws, size_t ws_stride, int blocks, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&envelope_covariance_kernel<JAC, JOINT, PINFO>>(160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&envelope_covariance_kernel<JAC, JOINT, PINFO>>((int)kCovMaxLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((envelope_covariance_kernel<JAC, JOINT, PINFO>), dim3((unsigned)a.B), dim3(kEvThreads), lds, stream, a, ws, ws_stride, blocks, cov, mask, status, pp);
     return hipGetLastError();
@@ -464,8 +435,8 @@ size_t window_envelope_covariance_workspace_doubles(const WindowCaps& c, long lo
 hipError_t launch_window_envelope_covariance(const WindowArgs& a, double* ws, long long blocks, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     if (!ws || blocks < 0 || blocks > (1ll << 30)) return hipErrorInvalidValue;
-    const size_t lds = window_envelope_covariance_lds_bytes(a.caps);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!cov_envelope_fits(a.caps)) return hipErrorInvalidValue;
+    const size_t lds = env_layout(a.caps.nv_max).bytes;
     const size_t stride = window_envelope_covariance_workspace_doubles(a.caps, blocks);
     return a.jacobian ? launch_env_cov_t<1>(a, ws, stride, (int)blocks, lds, cov, mask, status, pp, stream)
                       : launch_env_cov_t<0>(a, ws, stride, (int)blocks, lds, cov, mask, status, pp, stream);

@@ -25,34 +25,6 @@ namespace {
 
 extern __shared__ double fclds[];
 
-constexpr int kFcSe3Chunk = 32;   // EdgeSE3 factors linearised per pass
-
-// LDS layout of one window (offsets in doubles; the int tables follow the doubles)
-struct ForestCovLayout {
-    int hd, ho, kb, dg, rec, ints, ei, mk, nd, ps;
-    size_t bytes;
-};
-__host__ __device__ inline ForestCovLayout forest_cov_layout(int nv, bool priors, bool se3) {
-    ForestCovLayout l;
-    int p = 0;
-    l.hd = p; p += nv * 36;   // H_vv -> S_v -> S_v^-1 -> Sigma_v
-    l.ho = p; p += nv * 36;   // H_{parent(v),v} -> K_v
-    l.kb = p; p += 36;        // the exchange block of the current step
-    l.dg = p; p += nv * 6;    // diag(H) of every coordinate (the scale of the relative pivot test)
-    int rec = kCovChunk * 13;                                        // range: rho' info, J0 (6), J1 (6)
-    if (priors && rec < kCovChunk * 21) rec = kCovChunk * 21;
-    if (se3 && rec < kFcSe3Chunk * kCovSRec) rec = kFcSe3Chunk * kCovSRec;
-    l.rec = p; p += rec;      // the records of the current chunk (one kind at a time)
-    l.ints = p;
-    int q = 0;
-    l.ei = q; q += 2 * kCovChunk;   // the chunk's pose slots
-    l.mk = q; q += nv;
-    l.nd = q; q += nv;              // pose slot of the k-th node of the schedule
-    l.ps = q; q += nv;              // parent slot of a pose slot (-1: root)
-    l.bytes = (size_t)p * sizeof(double) + (size_t)q * sizeof(int);
-    return l;
-}
-
 template <int JAC, bool JOINT>
 __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs a, const TreeSched ts, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int D = 6, DD = 36, RS = 13;
@@ -166,7 +138,7 @@ __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs 
 
 template <int JAC, bool JOINT>
 hipError_t launch_forest_cov_j(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC, JOINT>>(160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC, JOINT>>((int)kCovMaxLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((forest_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(64), lds, stream, a, ts, cov, mask, status, pp);
     return hipGetLastError();
@@ -178,16 +150,14 @@ hipError_t launch_forest_cov_t(const WindowArgs& a, const TreeSched& ts, size_t 
 
 }  // namespace
 
-size_t window_forest_covariance_lds_bytes(const TreeSched& ts) {
-    return forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes;
-}
+size_t window_forest_covariance_lds_bytes(const TreeSched& ts) { return forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes; }
 
 hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     // (the LDS blocks are indexed by pose slot and the tables by edge number: the schedule must be the batch's own)
     if (ts.nv < 2 || ts.nv > 64 || ts.nv > a.caps.nv_max || ts.nr > a.caps.nr_max || ts.np > a.caps.np_max || ts.ns > a.caps.ns_max) return hipErrorInvalidValue;
-    const size_t lds = window_forest_covariance_lds_bytes(ts);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!cov_forest_fits(ts.nv, ts.np > 0, ts.ns > 0)) return hipErrorInvalidValue;
+    const size_t lds = forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes;
     return a.jacobian ? launch_forest_cov_t<1>(a, ts, lds, cov, mask, status, pp, stream) : launch_forest_cov_t<0>(a, ts, lds, cov, mask, status, pp, stream);
 }
 

@@ -29,6 +29,7 @@
 //   * nothing but the poses and the per-edge records ever leaves registers; no barriers (one wave per workgroup), no HBM
 //     workspace, 6 KB of LDS for a ten-pose window; 168 registers: three waves per SIMD in batches (3.7e7 windows/s).
 #include "window_device.h"
+#include "window_layouts.h"
 #include "lm_damping.h"
 
 #include <float.h>
@@ -65,15 +66,16 @@ struct W3Lds {
 template <bool PINFO>
 __device__ __forceinline__ W3Lds w3_carve(const WindowCaps& c) {
     W3Lds l;
+    const W3Layout y = w3_layout(c, PINFO);
     double* p = w3lds;
-    l.T = p; p += 5 * c.nv_max * 3;
-    l.rec = p; p += (size_t)c.nr_max * 16;
-    l.ev = p; p += (size_t)c.nr_max * 2;
-    l.fix = p; p += (size_t)c.nr_max * 3;
-    l.pv = p; p += (size_t)c.np_max * (PINFO ? 9 : 6);
+    l.T = p; p += y.T.n;
+    l.rec = p; p += y.rec.n;
+    l.ev = p; p += y.ev.n;
+    l.fix = p; p += y.fix.n;
+    l.pv = p; p += y.pv.n;
     int* q = reinterpret_cast<int*>(p);
-    l.eidx = q; q += (size_t)c.nr_max * 2;
-    l.epos = q; q += (size_t)c.nr_max * 2;
+    l.eidx = q; q += y.eidx.n;
+    l.epos = q; q += y.epos.n;
     l.pidx = q;
     return l;
 }
@@ -735,17 +737,12 @@ __global__ void __launch_bounds__(64, 3) wave3_lm_kernel(const WindowArgs a) {
 
 }  // namespace
 
-size_t window_wave3_lds_bytes(const WindowCaps& c, bool pinfo) {
-    const size_t doubles = (size_t)5 * c.nv_max * 3 + (size_t)c.nr_max * 21 + (size_t)c.np_max * (pinfo ? 9 : 6);
-    const size_t ints = (size_t)c.nr_max * 4 + c.np_max;
-    return doubles * sizeof(double) + ((ints + 1) & ~(size_t)1) * sizeof(int);
-}
+size_t window_wave3_lds_bytes(const WindowCaps& c, bool pinfo) { return w3_layout(c, pinfo).bytes; }
 
 hipError_t launch_window_wave3(const WindowArgs& a, hipStream_t stream) {
-    if (a.B <= 0 || a.caps.nv_max > 64 || a.caps.nv_max <= 0) return hipErrorInvalidValue;
     const bool pinfo = a.p_info != nullptr;   // (the host hands over a table only where structured_pinfo holds: window_dispatch.cpp, pick_kernel)
-    const size_t lds = window_wave3_lds_bytes(a.caps, pinfo);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    if (a.B <= 0 || a.caps.nv_max <= 0 || !wave3_fits(a.caps, pinfo)) return hipErrorInvalidValue;
+    const size_t lds = w3_layout(a.caps, pinfo).bytes;
     if (pinfo) {
         if (a.jacobian) hipLaunchKernelGGL((wave3_lm_kernel<1, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
         else hipLaunchKernelGGL((wave3_lm_kernel<0, true>), dim3((unsigned)a.B), dim3(64), lds, stream, a);

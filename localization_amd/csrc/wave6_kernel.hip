@@ -28,6 +28,7 @@
 // pass), LM — is shared with the rank-1 kernel.  Measured: cfg/uwb_twist.yaml's 15-pose window 0.29 ms (window_lm_kernel 0.64), 0.32 ms
 // per range message through the node (the oracle: 0.34 ms), 4.5e6 windows/s in batches (chain_lm_kernel: 2.7e6).
 #include "se3_edge_device.h"
+#include "window_layouts.h"
 #include "lm_damping.h"
 
 #include <float.h>
@@ -117,10 +118,6 @@ __device__ __forceinline__ double w6_jac_numeric(const double* X0, const double*
 }
 #pragma clang fp contract(fast)
 
-constexpr int W6_NSLOT = 5;   // pose buffers in LDS: the state + up to four trial states
-constexpr int W6_REC = 14;    // per (edge, moving endpoint): w, -w e, the pose's own J (6), the other endpoint's J (6) when that is the previous pose
-constexpr int W6_PREC = 27;   // per prior: J^T W J (lower triangle, 21), -J^T W e (6)
-
 // LDS of one window (doubles first, then ints)
 struct W6Lds {
     double* pose;   // [5][nv_max][12] R (row-major), t
@@ -138,18 +135,19 @@ struct W6Lds {
 template <bool SE3>
 __device__ __forceinline__ W6Lds w6_carve(const WindowCaps& c) {
     W6Lds l;
+    const W6Layout y = w6_layout(c, SE3);
     double* p = w6lds;
-    l.pose = p; p += (size_t)W6_NSLOT * c.nv_max * 12;
-    l.rec = p; p += (size_t)c.nr_max * 2 * W6_REC;
-    l.prec = p; p += (size_t)c.np_max * W6_PREC;
-    l.ev = p; p += (size_t)c.nr_max * 5;
-    l.fix = p; p += (size_t)c.nr_max * 3;
-    l.pv = p; p += (size_t)c.np_max * 18;
-    l.sv = p; if (SE3) p += 48 * 64;
+    l.pose = p; p += y.pose.n;
+    l.rec = p; p += y.rec.n;
+    l.prec = p; p += y.prec.n;
+    l.ev = p; p += y.ev.n;
+    l.fix = p; p += y.fix.n;
+    l.pv = p; p += y.pv.n;
+    l.sv = p; p += y.sv.n;
     int* q = reinterpret_cast<int*>(p);
-    l.eidx = q; q += (size_t)c.nr_max * 2;
-    l.epos = q; q += (size_t)c.nr_max * 2;
-    l.pidx = q; q += c.np_max;
+    l.eidx = q; q += y.eidx.n;
+    l.epos = q; q += y.epos.n;
+    l.pidx = q; q += y.pidx.n;
     l.ppos = q;
     return l;
 }
@@ -1012,11 +1010,7 @@ __global__ void __launch_bounds__(64) wave6_lm_kernel(const WindowArgs a) {
 
 }  // namespace
 
-size_t window_wave6_lds_bytes(const WindowCaps& c, bool se3) {
-    const size_t doubles = (size_t)W6_NSLOT * c.nv_max * 12 + (size_t)c.nr_max * (2 * W6_REC + 5 + 3) + (size_t)c.np_max * (W6_PREC + 18) + (se3 ? 48 * 64 : 0);
-    const size_t ints = (size_t)c.nr_max * 4 + 2 * (size_t)c.np_max;
-    return doubles * sizeof(double) + ((ints + 1) & ~(size_t)1) * sizeof(int);
-}
+size_t window_wave6_lds_bytes(const WindowCaps& c, bool se3) { return w6_layout(c, se3).bytes; }
 
 namespace {
 template <int JAC, bool SE3>
@@ -1029,9 +1023,8 @@ hipError_t launch_wave6_t(const WindowArgs& a, size_t lds, hipStream_t stream) {
 }  // namespace
 
 hipError_t launch_window_wave6(const WindowArgs& a, bool se3, hipStream_t stream) {
-    if (a.B <= 0 || a.caps.nv_max > 64 || a.caps.nv_max <= 0 || (se3 && (a.caps.ns_max > 64 || a.caps.nv_max > 63))) return hipErrorInvalidValue;
-    const size_t lds = window_wave6_lds_bytes(a.caps, se3);
-    if (lds > kWave6MaxLds) return hipErrorInvalidValue;
+    if (a.B <= 0 || a.caps.nv_max <= 0 || !wave6_fits(a.caps, se3)) return hipErrorInvalidValue;
+    const size_t lds = w6_layout(a.caps, se3).bytes;
     if (se3) return a.jacobian ? launch_wave6_t<1, true>(a, lds, stream) : launch_wave6_t<0, true>(a, lds, stream);
     return a.jacobian ? launch_wave6_t<1, false>(a, lds, stream) : launch_wave6_t<0, false>(a, lds, stream);
 }

@@ -1,5 +1,6 @@
 // The dispatch rules of the batched sliding-window solver (window_dispatch.h).  Host code only: no HIP call, no environment, no handle.
 #include "window_dispatch.h"
+#include "window_layouts.h"
 
 #include "../../include/localization_amd.h"
 
@@ -24,6 +25,19 @@ long long tree_min_batch(const DispatchOpts& o) {
     const long long mn = effective_chain_min(o);
     if (mn <= 0) return 1ll << 62;     // (threshold 0 = "never a batch kernel")
     return mn < 256 ? mn : 256;
+}
+
+DispatchFits dispatch_fits(const WindowCaps& c) {
+    DispatchFits f;
+    f.nv_max = c.nv_max;
+    f.wave6 = wave6_fits(c, false);
+    f.wave6_se3 = wave6_fits(c, true);
+    f.wave3 = wave3_fits(c, false);
+    f.wave3_pinfo = wave3_fits(c, true);
+    f.cov_chain = cov_chain_fits(c, false);
+    f.cov_arrow = cov_arrow_fits(c);
+    f.cov_envelope = cov_envelope_fits(c);
+    return f;
 }
 
 // option "arrow3" admits the batch: 0 = never, 1 = whenever it qualifies; default: windows of more than 64 poses — below that the

@@ -25,7 +25,7 @@ struct DispatchOpts {
                                        // wave3_lm_kernel<JAC, true> and the chain 3x3 covariance pass (structured_pinfo); 0: the general kernel, the envelope pass
 };
 
-// what depends on the handle's capacities alone: the kernels' LDS needs against their limits, taken once by loc_window_create
+// what depends on the handle's capacities alone: the kernels' LDS needs against their limits (window_layouts.h), taken once by loc_window_create
 struct DispatchFits {
     bool wave6 = false;          // nv_max <= 64 and wave6_lm_kernel's LDS
     bool wave6_se3 = false;      // nv_max <= 63, ns_max <= 64 and wave6_lm_kernel<JAC, true>'s LDS
@@ -34,6 +34,7 @@ struct DispatchFits {
     bool cov_chain = false, cov_arrow = false, cov_envelope = false;   // the chain (6x6) / arrowhead / envelope covariance pass within 160 KiB
     int nv_max = 0;
 };
+DispatchFits dispatch_fits(const WindowCaps& c);
 
 // the covariance pass of a batch
 enum class CovKind : int {

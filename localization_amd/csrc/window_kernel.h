@@ -82,7 +82,6 @@ hipError_t launch_window_wave3(const WindowArgs& a, hipStream_t stream);
 
 // 6-DoF chain windows of <= 64 poses without EdgeSE3 factors and with at most one range edge per pair of consecutive poses, one wave
 // per window (wave6_kernel.hip): the node's own solve with IMU priors / lever arms, small batches
-constexpr size_t kWave6MaxLds = 128 * 1024;   // per window (one workgroup of one wave)
 size_t window_wave6_lds_bytes(const WindowCaps& c, bool se3 = false);   // se3: with the EdgeSE3 records of wave6_lm_kernel<JAC, true> (an EdgeSE3 per consecutive pair)
 hipError_t launch_window_wave6(const WindowArgs& a, bool se3, hipStream_t stream);
 

@@ -33,6 +33,7 @@
 //   * all LM control flow is uniform over the instance's threads (sums are DPP reductions, combined across the waves in wave
 //     order: every thread holds the same bits).
 #include "window_device.h"
+#include "window_layouts.h"
 #include "lm_damping.h"
 
 
@@ -40,12 +41,7 @@ namespace locamd {
 
 namespace {
 
-// Edge records written by the linearisation.  Unary and SE3 edges store their finished CONTRIBUTIONS to the normal equations
-// (the 6x6 products are formed once, by the lane that evaluated the edge, from values it holds in registers), so building H
-// and b is one load per (edge, entry); diagonal blocks as 21 lower-triangle entries k = r (r + 1) / 2 + c, r >= c.
-constexpr int RREC = 16;   // J0[6] J1[6] wr omega_r (+pad): rank-1, expanded on the fly
-constexpr int PREC = 28;   // H_vv[21] b_v[6] (+pad)
-constexpr int SREC = 90;   // H_ii[21] H_jj[21] H_(later,earlier)[36, column-major like the storage] b_i[6] b_j[6]
+// Edge records written by the linearisation: RREC, PREC, SREC doubles (window_layouts.h); inside an SREC record
 constexpr int S_HJJ = 21, S_OFF = 42, S_BI = 78, S_BJ = 84;
 
 
@@ -471,68 +467,38 @@ __device__ __forceinline__ void evaluate_edges(const WindowArgs& a, const Lds& L
 //     envelope, so storage and work are O(n band^2): a 500-pose chain (cfg/uwb_pose.yaml) is 3000 rows of ~12 entries;
 //   SPARSE  (nv_max <= 64): exactly the blocks of the factor's structure under the in-kernel elimination order (rowmask).
 // Capacity in both cases: the envelope bound of the caller's bw_max (the exact structure of the natural order lies inside
-// it; an elimination order that would need more falls back to the natural one).
-__host__ __device__ inline size_t sky_nnz_bound(int nv, int bw) {
-    size_t s = 0;
-    for (int v = 0; v < nv; ++v) s += 36 * ((size_t)(v < bw ? v : bw) + 1);
-    return s;
-}
-__host__ __device__ inline bool window_sparse_path(const WindowCaps& c) { return c.nv_max <= 512; }
-// Capacity of H / L in entries.  Windows of 65 .. 512 poses keep them in the HBM workspace, where room is cheap: they get the
-// envelope of a band of at least 3, so that a nested-dissection order of a long chain (one fill block per eliminated pose:
-// 3 n blocks where the natural order has 2 n) fits and the window factors in ~log2(n) levels instead of n (a 500-pose chain
-// of cfg/uwb_pose.yaml's length: 500 levels, 71 ms per solve with the caller's band of 1).
-__host__ __device__ inline size_t window_nnz_capacity(const WindowCaps& c) {
-    const int bw = (c.nv_max > 64 && c.nv_max <= 512 && c.bw_max < 3) ? (c.nv_max > 3 ? 3 : c.nv_max - 1) : c.bw_max;
-    return sky_nnz_bound(c.nv_max, bw);
-}
-__host__ __device__ inline int window_mask_words(const WindowCaps& c) { return c.nv_max <= 64 ? 1 : 8; }
+// it; an elimination order that would need more falls back to the natural one): window_layouts.h, window_nnz_capacity.
 
+// DEVICE SIDE ONLY.  window_lm_kernel keeps the pointer walk it has always had, and the sums that walk needs follow here: with the carve
+// taken from window_layouts.h's WindowLayout, six instantiations of this kernel (256 VGPRs, spilling already) needed 4 .. 60 bytes more
+// scratch per lane (profiles/kernel_layouts/kernel_resources.txt).  The host sizes every launch and allocation by WindowLayout;
+// tests/test_kernel_layouts_cpu.py holds WindowLayout to a recording of this walk, offset by offset and total by total — change both.
 // entries of the per-pose incidence lists: every edge once per moving endpoint
-__host__ __device__ inline size_t window_incidences(const WindowCaps& c) {
+__device__ inline size_t window_incidences(const WindowCaps& c) {
     return 2 * (size_t)c.nr_max + (size_t)c.np_max + 2 * (size_t)c.ns_max;
 }
-__host__ __device__ inline size_t ints_as_doubles(size_t n) { return (n + 1) / 2; }
+__device__ inline size_t ints_as_doubles(size_t n) { return (n + 1) / 2; }
 // the edge-index tables and incidence lists of one instance, in doubles; in HBM-workspace mode they move to LDS as well when
 // they are small (every gather starts with a look-up in them; from HBM that is a full memory round trip of pure latency)
-__host__ __device__ inline size_t window_index_doubles(const WindowCaps& c) {
+__device__ inline size_t window_index_doubles(const WindowCaps& c) {
     return ints_as_doubles(window_incidences(c)) + ints_as_doubles((size_t)c.nr_max + c.ns_max + 1) +
            ints_as_doubles(2 * (size_t)c.nr_max) + ints_as_doubles((size_t)c.np_max) + ints_as_doubles(4 * (size_t)c.ns_max);
 }
-constexpr size_t INDEX_TABLES_LDS_MAX = 16 * 1024;        // windows of <= 64 poses: keeps 8+ waves per CU
-constexpr size_t INDEX_TABLES_LDS_MAX_BIG = 72 * 1024;    // larger windows: their structure tables already limit the CU to 1-2 waves
-__host__ __device__ inline size_t window_table_bytes(const WindowCaps& c);
-__host__ __device__ inline bool window_index_in_lds(const WindowCaps& c) {
-    const size_t bytes = window_index_doubles(c) * 8;
-    if (c.nv_max <= 64) return bytes <= INDEX_TABLES_LDS_MAX;
-    return bytes <= INDEX_TABLES_LDS_MAX_BIG && bytes + window_table_bytes(c) + 1024 <= 160 * 1024 - 512;
-}
-
-// 8-word windows: the trailing clique of the elimination order (BASELINE config 4's ten unknown anchors; the last separator of
-// a nested dissection in general) is factored as ONE dense supernode of up to ROOT_MAX poses in LDS — when the LDS has room
-constexpr int ROOT_MAX = 10;
-__host__ __device__ inline size_t window_root_lds_doubles(const WindowCaps& c) {
-    if (!window_sparse_path(c) || window_mask_words(c) == 1) return 0;
-    const size_t need = (size_t)(6 * ROOT_MAX + 1) * (6 * ROOT_MAX);
-    const size_t used = (window_table_bytes(c) + 7) / 8 * 8 + (window_index_in_lds(c) ? window_index_doubles(c) * 8 : 0);
-    return used + need * 8 <= 160 * 1024 - 4096 ? need : 0;
-}
-
 // doubles of one instance's MAIN arrays (block-sparse pair, dense vectors, poses, edge records, incidence lists, a
 // writable copy of the edge index tables) — the layout the kernel carves, in LDS or in the HBM workspace
-__host__ __device__ inline size_t window_instance_doubles(const WindowCaps& c) {
+__device__ inline size_t window_instance_doubles(const WindowCaps& c) {
     const size_t n_max = 6 * (size_t)c.nv_max;
     return 2 * window_nnz_capacity(c) + 4 * n_max + 2 * (size_t)c.nv_max * 12 + (size_t)c.nr_max * RREC + (size_t)c.np_max * PREC +
            (size_t)c.ns_max * SREC + window_index_doubles(c);
 }
 // workspace mode only: the pushed updates and their per-parent sums (28 doubles per column each), and for 8-word windows the
 // off-diagonal task list
-__host__ __device__ inline size_t window_push_doubles(const WindowCaps& c) {
+__device__ inline size_t window_push_doubles(const WindowCaps& c) {
     if (!window_sparse_path(c)) return 0;
     return 56 * (size_t)c.nv_max + (window_mask_words(c) > 1 ? ints_as_doubles(window_nnz_capacity(c) / 36) : 0);
 }
 // bytes of the small index tables that always live in LDS
-__host__ __device__ inline size_t window_table_bytes(const WindowCaps& c) {
+__device__ inline size_t window_table_bytes(const WindowCaps& c) {
     const size_t nv = (size_t)c.nv_max;
     if (!window_sparse_path(c)) return (4 * nv + 2) * sizeof(int);  // fb, last, boff[nv + 1], ioff[nv + 1]
     const size_t nb_max = window_nnz_capacity(c) / 36;
@@ -547,13 +513,9 @@ __host__ __device__ inline size_t window_table_bytes(const WindowCaps& c) {
 // small windows: records of the pre-decoded factorisation schedule — first-level stage-A records (two per column, one per
 // off-diagonal block), continuation records for further earlier columns (capacity: one per block; a window that needs more
 // runs the generic look-ups), stage-B records (one per block), the hand-out counter
-__host__ __device__ inline size_t small_recA_capacity(const WindowCaps& c) {
+__device__ inline size_t small_recA_capacity(const WindowCaps& c) {
     const size_t nb_max = window_nnz_capacity(c) / 36;
     return (size_t)c.nv_max + 2 * nb_max;
-}
-__host__ __device__ inline size_t small_table_doubles(const WindowCaps& c) {
-    if (!window_sparse_path(c) || window_mask_words(c) != 1) return 0;
-    return 2 * small_recA_capacity(c) + window_nnz_capacity(c) / 36 + 2;
 }
 
 // offset of block (i, K), K <= i, in the storage of H / L
@@ -2835,19 +2797,14 @@ __global__ void __launch_bounds__(64 * NW, (GLOBAL_A && SP) ? LOCAMD_WS_WAVES : 
 
 }  // namespace
 
-size_t window_lds_bytes(const WindowCaps& c, bool global_a) {
-    // (+ the static 6x6 exchange block)
-    if (global_a) return (window_table_bytes(c) + 7) / 8 * 8 + (window_index_in_lds(c) ? window_index_doubles(c) * 8 : 0) + window_root_lds_doubles(c) * 8;
-    const size_t staged = (size_t)c.nr_max * 5 + (size_t)c.np_max * 18 + (size_t)c.ns_max * 48;
-    return (window_instance_doubles(c) + (window_table_bytes(c) + 7) / 8 + staged + small_table_doubles(c)) * sizeof(double);
-}
-size_t window_workspace_doubles(const WindowCaps& c) { return window_instance_doubles(c) + window_push_doubles(c); }
+// (+ the static 6x6 exchange block)
+size_t window_lds_bytes(const WindowCaps& c, bool global_a) { return window_layout(c, global_a).lds_bytes; }
+size_t window_workspace_doubles(const WindowCaps& c) { return window_layout(c, true).main_doubles; }
 constexpr int WIDE_WAVES = 8;   // waves per window of 65 .. 512 poses (two per SIMD)
-constexpr size_t WIDE_STATIC_LDS = 4096;   // >= the static LDS of the several-waves kernel (reduction scratch: 2.4 KB)
 
 template <bool PINFO, bool GLOBAL_A, int JAC, bool SP, int W, int NW = 1>
 static hipError_t launch_window_t(const WindowArgs& a, size_t lds, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&window_lm_kernel<GLOBAL_A, JAC, SP, W, NW, PINFO>>(160 * 1024 - (NW > 1 ? WIDE_STATIC_LDS : 512));  // static LDS on top
+    const hipError_t e = allow_dynamic_lds<&window_lm_kernel<GLOBAL_A, JAC, SP, W, NW, PINFO>>((int)(NW > 1 ? kWindowWideMaxLds : kWindowMaxLds));  // static LDS on top
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((window_lm_kernel<GLOBAL_A, JAC, SP, W, NW, PINFO>), dim3((unsigned)a.B), dim3(64 * NW), lds, stream, a);
     return hipGetLastError();
@@ -2859,15 +2816,15 @@ template <bool PINFO>
 static hipError_t launch_window_p(const WindowArgs& a, hipStream_t stream) {
     if (a.B <= 0 || a.caps.bw_max < 0 || a.caps.bw_max >= a.caps.nv_max + (a.caps.nv_max == 1)) return hipErrorInvalidValue;
     const bool global_a = a.workspace != nullptr;
-    const size_t lds = window_lds_bytes(a.caps, global_a);
-    if (lds > 160 * 1024 - 512) return hipErrorInvalidValue;
+    if (!window_fits(a.caps, global_a)) return hipErrorInvalidValue;
+    const size_t lds = window_layout(a.caps, global_a).lds_bytes;
     const bool sp = window_sparse_path(a.caps);
     if (sp && window_mask_words(a.caps) > 1) {   // 65 .. 512 poses: 8-word masks, always in the workspace
         if (!global_a) return hipErrorInvalidValue;
         // Their structure tables fill a CU's LDS, so one such window runs per CU: it gets the CU's four SIMDs (WIDE_WAVES
         // waves); LOCAMD_WINDOW_WAVES=1 in the environment keeps the one-wave kernel (for comparison).
         static const bool one_wave = [] { const char* v = getenv("LOCAMD_WINDOW_WAVES"); return v && v[0] == '1' && v[1] == 0; }();
-        if (one_wave || lds > 160 * 1024 - WIDE_STATIC_LDS) return a.jacobian ? launch_window_t<PINFO, true, 1, true, 8>(a, lds, stream) : launch_window_t<PINFO, true, 0, true, 8>(a, lds, stream);
+        if (one_wave || lds > kWindowWideMaxLds) return a.jacobian ? launch_window_t<PINFO, true, 1, true, 8>(a, lds, stream) : launch_window_t<PINFO, true, 0, true, 8>(a, lds, stream);
         return a.jacobian ? launch_window_t<PINFO, true, 1, true, 8, WIDE_WAVES>(a, lds, stream) : launch_window_t<PINFO, true, 0, true, 8, WIDE_WAVES>(a, lds, stream);
     }
     const int sel = (global_a ? 4 : 0) | (a.jacobian ? 2 : 0) | (sp ? 1 : 0);

@@ -1,5 +1,6 @@
 // Structure analysis of a batch of windows.  Host code only: no HIP runtime call in this file.
 #include "window_structure.h"
+#include "window_layouts.h"
 
 #include <cstring>
 #include <algorithm>
@@ -470,7 +471,7 @@ bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool st
         }
     }
     if (jmax > 64 || jpmax > 16 || nb_max > 15) return false;
-    if (window_arrow3_lds_bytes(c, nb_max) > 160 * 1024 - 512) return false;
+    if (!arrow3_fits(c, nb_max)) return false;
     A.arrow_list_cap = list_cap;
     if (structure_only) return true;
     // pass 2: the records

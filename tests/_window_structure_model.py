@@ -194,7 +194,7 @@ def envelope_blocks_max(b):
 # ---- arrowhead windows ----------------------------------------------------------------------------------------------------------
 
 def arrow3_lds_bytes(nv_max, nb_max):
-    """arrow3_kernel.hip: arrow3_lds_doubles (four waves, an anchor table of 256 entries), in bytes."""
+    """window_layouts.h: arrow3_lds_layout (four waves, an anchor table of 256 entries), in bytes."""
     D = 3 * nb_max
     D16 = 16 * ((D + 15) // 16)
     return 8 * (nv_max * 28 + D * (D + 1) // 2 + (D + 1) * (D + 2) // 2 + 3 * D + 4 * D + 4 * 4 * D16 * 3 + 6 * nb_max + 16 + 3 * ARROW_MAX_ANCHORS)

@@ -17,11 +17,6 @@
 
 #include "window_structure.h"
 
-namespace locamd {
-// the only symbol window_structure.cpp takes from a kernel file (build_arrow_aux's LDS test); neither pass under test calls it
-size_t window_arrow3_lds_bytes(const WindowCaps&, int) { return 0; }
-}  // namespace locamd
-
 template <class T>
 static bool read_vec(FILE* f, std::vector<T>& v, size_t count) {
     v.resize(count);

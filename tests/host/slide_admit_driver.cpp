@@ -20,11 +20,6 @@
 #include "slide_admit.h"
 #include "window_structure.h"
 
-namespace locamd {
-// (the only symbol window_structure.cpp takes from a kernel file; no pass run here calls it)
-size_t window_arrow3_lds_bytes(const WindowCaps&, int) { return 0; }
-}  // namespace locamd
-
 template <class T>
 static bool read_vec(FILE* f, std::vector<T>& v, size_t count) {
     v.resize(count);

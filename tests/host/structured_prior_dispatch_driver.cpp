@@ -23,11 +23,6 @@
 #include "../../include/localization_amd.h"
 #include "window_dispatch.h"
 
-namespace locamd {
-// window_structure.cpp's one symbol from a kernel file: no rule tested here may reach it (option "arrow3" is 0 throughout)
-size_t window_arrow3_lds_bytes(const WindowCaps&, int) { std::fprintf(stderr, "window_arrow3_lds_bytes: not in this driver\n"); std::abort(); }
-}  // namespace locamd
-
 using namespace locamd;
 
 static long long g_checks = 0;

@@ -21,11 +21,6 @@
 #include "window_structure.h"
 #include "window_tables.h"
 
-namespace locamd {
-// window_structure.cpp's one symbol from a kernel file (window_structure_driver.cpp has the formula): nothing tested here may reach it
-size_t window_arrow3_lds_bytes(const WindowCaps&, int) { std::fprintf(stderr, "window_arrow3_lds_bytes: not in this driver\n"); std::abort(); }
-}  // namespace locamd
-
 static void put(std::vector<int64_t>& res, const locamd::BlockLayout& L, int n_pre, bool tables) {
     for (int k = 0; k < n_pre; ++k) res.push_back((int64_t)L.pre[k]);
     for (int t = 0; t < locamd::kWindowTables && tables; ++t) res.push_back((int64_t)L.tab[t]);

@@ -17,11 +17,6 @@
 
 #include "window_dispatch.h"
 
-namespace locamd {
-// window_structure.cpp's one symbol from a kernel file (window_structure_driver.cpp has the formula): no rule tested here may reach it
-size_t window_arrow3_lds_bytes(const WindowCaps&, int) { std::fprintf(stderr, "window_arrow3_lds_bytes: not in this driver\n"); std::abort(); }
-}  // namespace locamd
-
 int main(int argc, char** argv) {
     using namespace locamd;
     if (argc != 3) { std::fprintf(stderr, "usage: %s <in> <out>\n", argv[0]); return 2; }

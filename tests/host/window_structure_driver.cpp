@@ -1,7 +1,7 @@
 // Stand-alone driver of localization_amd/csrc/window_structure.cpp for tests/test_window_structure_cpu.py: host code only, built with
 // plain g++ under AddressSanitizer + UBSan and under ThreadSanitizer.  It links against window_structure.cpp and nothing else of the product.
 //
-//   window_structure_driver --info                 prints "hw <std::thread::hardware_concurrency()>" and "lds <window_arrow3_lds_bytes({100, ..}, 7)>"
+//   window_structure_driver --info                 prints "hw <std::thread::hardware_concurrency()>" and "lds <arrow3_lds_layout(100, 7).bytes>"
 //   window_structure_driver <in> <out>             runs every pass of window_structure.h on each batch of <in>
 //
 // <in>: one or more batches back to back (several only to spare process starts: each batch is analysed on its own).  One batch =
@@ -19,17 +19,8 @@
 #include <thread>
 #include <vector>
 
+#include "window_layouts.h"
 #include "window_structure.h"
-
-namespace locamd {
-// arrow3_kernel.hip:66-69, arrow3_lds_doubles (ARROW_NW = 4 waves): the only symbol window_structure.cpp takes from a kernel file
-size_t window_arrow3_lds_bytes(const WindowCaps& c, int nb_max) {
-    const size_t NW = 4, D = 3 * (size_t)nb_max, D16 = 16 * ((D + 15) / 16);
-    const size_t doubles = (size_t)c.nv_max * 28 + D * (D + 1) / 2 + (D + 1) * (D + 2) / 2 + 3 * D + NW * D + NW * 4 * D16 * 3 + 6 * (size_t)nb_max + 16 +
-                           3 * (size_t)kArrowMaxAnchors;
-    return doubles * sizeof(double);
-}
-}  // namespace locamd
 
 namespace {
 
@@ -67,7 +58,7 @@ int main(int argc, char** argv) {
     const int hw = (int)std::thread::hardware_concurrency();
     if (argc == 2 && std::string(argv[1]) == "--info") {
         const WindowCaps c{100, 0, 0, 0, 0};
-        std::printf("hw %d\nlds %zu\n", hw, window_arrow3_lds_bytes(c, 7));
+        std::printf("hw %d\nlds %zu\n", hw, arrow3_lds_layout(c.nv_max, 7).bytes);
         return 0;
     }
     if (argc != 3) { std::fprintf(stderr, "usage: %s --info | <in> <out>\n", argv[0]); return 2; }

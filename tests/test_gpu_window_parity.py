@@ -801,3 +801,51 @@ def test_window_options_and_topology_cache(gpu):
     assert s2.last_kernel_kind() == "wave3_lm_kernel" and np.array_equal(small.poses, want.poses) and np.array_equal(r_with, r_without)
     assert 0.0 < ms_with < 5.0 and 0.0 < s2.last_kernel_ms() < 5.0
     s2.close()
+
+
+def _padded(la, wb, nv_max, nr_max, np_max, ns_max):
+    """the same windows under larger capacities"""
+    out = la.WindowBatch(wb.B, nv_max, nr_max, np_max, ns_max)
+    out.counts[:] = wb.counts
+    out.poses[:, :wb.caps[0]] = wb.poses
+    out.r_idx[:, :wb.caps[1]] = wb.r_idx[:, :wb.caps[1]]
+    out.r_val[:, :wb.caps[1]] = wb.r_val[:, :wb.caps[1]]
+    return out
+
+
+@pytest.mark.parametrize("caps,same_variant,kernel", [
+    # (nv_max, nr_max, np_max, ns_max, bw_max) of the padded batch and of a batch the SAME kernel variant takes on the other side of the branch
+    ((10, 900, 0, 0, 9), (10, 800, 0, 0, 9), "window_lm_kernel"),      # one-word masks, arrays in the workspace: the index tables (18 KB > 16 KB) stay there too / move to LDS
+    ((100, 4000, 0, 0, 9), (100, 20, 0, 0, 9), "window_lm_kernel"),    # eight-word masks: the index tables (80 KB > 72 KB) stay in the workspace / move to LDS
+    ((500, 20, 0, 0, 1), (500, 20, 0, 0, 3), "window_lm_kernel"),      # 65 .. 512 poses under bw_max < 3: the capacity of a band of 3 (the same layout); no room for the root supernode
+    ((10, 20, 1, 0, 1), (10, 20, 0, 0, 1), "wave3_lm_kernel"),         # wave3: an odd / even number of ints behind the doubles
+])
+def test_padded_capacities_take_the_other_layout_branch(gpu, caps, same_variant, kernel):
+    """Capacities, not counts, select a branch of a kernel's memory layout (window_layouts.h): the ten-pose chain batch of this file under
+    capacities padded across a boundary — against the oracle with the limits of test_window_matches_oracle, and bit for bit against the same
+    batch under capacities on the boundary's other side that the same kernel variant takes."""
+    import localization_amd as la
+    from _oracle_window import oracle_solve_instance
+    from oracle import oracle as O
+    B, T = 8, 10
+    base = _chain_batch(la, B, T, 21)
+    want = [oracle_solve_instance(base, i, ANCH, jac_mode=O.JAC_ANALYTIC) for i in range(B)]
+    poses = []
+    for nv_max, nr_max, np_max, ns_max, bw_max in (caps, same_variant):
+        wb = _padded(la, base, nv_max, nr_max, np_max, ns_max)
+        solver = la.WindowSolver(ANCH, B, nv_max, nr_max, np_max, ns_max, maximum_iteration=10, jacobian="analytic", bw_max=bw_max,
+                                 chain_threshold=0 if kernel == "window_lm_kernel" else None)
+        if kernel == "window_lm_kernel":
+            solver.set_option("arrow3", 0)
+        res = solver.solve(wb).copy()
+        assert solver.last_kernel_kind() == kernel
+        solver.close()
+        poses.append(wb.poses[:, :T].copy())
+        if (nv_max, nr_max, np_max, ns_max, bw_max) == caps:
+            for i in range(B):
+                d = np.abs(wb.poses[i, :T] - want[i][0])
+                chi = want[i][1]
+                assert d.max() < 1e-7, (i, d.max())
+                assert abs(res[i, 0] - chi) <= 1e-6 * max(1.0, abs(chi)), (i, res[i, 0], chi)
+            assert np.array_equal(wb.poses[:, T:], _padded(la, base, nv_max, nr_max, np_max, ns_max).poses[:, T:])   # the slots behind the window: untouched
+    assert np.array_equal(poses[0], poses[1])

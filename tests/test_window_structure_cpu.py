@@ -98,7 +98,7 @@ def run(drivers, tmp_path, batches, tsan=False):
 
 
 def test_lds_formula_is_the_kernels(drivers):
-    # arrow3_lds_doubles(100, 7) by hand: 2800 + 231 + 253 + 63 + 84 + 1536 + 42 + 16 + 768 = 5793 doubles
+    # arrow3_lds_layout(100, 7) (window_layouts.h) by hand: 2800 + 231 + 253 + 63 + 84 + 1536 + 42 + 16 + 768 = 5793 doubles
     assert drivers["lds"] == 46344 == M.arrow3_lds_bytes(100, 7)
 
 
