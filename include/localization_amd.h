@@ -542,16 +542,56 @@ enum {
     LOC_SLIDE_ADMIT_OK = 0,
     LOC_SLIDE_ADMIT_NO_POSES = 1,         /* the window has nv = 0 */
     LOC_SLIDE_ADMIT_COUNT = 2,            /* a new count outside [0, *_new_max] */
-    LOC_SLIDE_ADMIT_INDEX = 3,            /* a new range index outside rule 3 */
+    LOC_SLIDE_ADMIT_INDEX = 3,            /* a new range index outside rule 3 (loc_window_slide_plain_resident_dev: or a new EdgeSE3 row not on {s - 1, s}) */
     LOC_SLIDE_ADMIT_NV_MAX = 4,           /* the slid window exceeds nv_max */
     LOC_SLIDE_ADMIT_NR_MAX = 5,           /* ... nr_max */
     LOC_SLIDE_ADMIT_NP_MAX = 6,           /* ... np_max */
-    LOC_SLIDE_ADMIT_NOT_TRANSLATION = 7   /* a new row that is not translation-only: a non-identity rotation, a lever arm, rotation information */
+    LOC_SLIDE_ADMIT_NOT_TRANSLATION = 7,  /* a new row that is not translation-only: a non-identity rotation, a lever arm, rotation information */
+    LOC_SLIDE_ADMIT_NS_MAX = 8,           /* loc_window_slide_plain_resident_dev: the slid window exceeds ns_max */
+    LOC_SLIDE_ADMIT_PAIRS = 9             /* loc_window_slide_plain_resident_dev: the new rows break the pair rule of the resident verdict */
 };
 int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
                                   int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
                                   int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
                                   void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev, void* admit_dev);
+/* The resident slide for 6-DoF chain windows: the reference's PLAIN DROP ("The plain drop for 6-DoF chain windows").  What
+ * Robot::new_vertex does with its oldest pose (robot.cpp:92-98): the pose is thrown away with every factor on it and NOTHING is carried — no
+ * marginal pass, no inserted prior row, no table of full information matrices.  It serves the resident verdicts LOC_WINDOW_KERNEL_CHAIN,
+ * _WAVE6 and _WAVE6S (the ordered 6-DoF chain verdicts of loc_window_upload: IMU rotation priors, lever arms, EdgeSE3 factors between
+ * consecutive poses), which loc_window_slide_resident(_dev) refuse.  Needs option "resident_slide" = 1 at upload, like its siblings.
+ * Every per-window array is a DEVICE array in loc_window_slide_resident_dev's layouts and under its rules (read in stream order, kept alive
+ * and unchanged by the caller until the stream has passed the call, no aliasing of the handle's tables or the outputs); in addition
+ *   ns_new_max (may be 0), new_s_counts int32 [n], new_s_idx int32 [n][ns_new_max][4], new_s_val double [n][ns_new_max][48]
+ * the appended EdgeSE3 rows in the s_idx / s_val layouts.  New priors sit on the new slot: there is no index array for them.
+ * drop_oldest_dev may be NULL: every window drops.  status_dev int32 [n] and admit_dev int32 [n] may be NULL.  Asynchronous on hip_stream
+ * (NULL = the handle's own stream), ordered after the last resident launch; no pass over per-window data on the host, no copy, no
+ * synchronisation, no allocation.
+ * Per window b, with x = loc_window_poses_device()'s content:
+ *   1. drop_oldest[b] != 0: slot 0 goes, with every range row that has it as an endpoint, every prior row on it and every EdgeSE3 row that has
+ *      it as vi or vj; the kept rows keep their order; every moving slot index decreases by 1 (anchor codes -1 - a stay, s_idx[.][2..3]
+ *      travel as they are); poses 1 .. nv - 1 move to 0 .. nv - 2, all 12 doubles.
+ *   2. drop_oldest[b] == 0: nothing is removed.
+ *   3. new_pose[b] (any rotation) becomes the last slot s; the new range rows follow the kept ones under rule 3 of loc_window_slide_resident;
+ *      the new prior rows go on s; the new EdgeSE3 rows must have {vi, vj} = {s - 1, s} in either order, with s - 1 >= 0 and bw_max >= 1.
+ *      Lever arms, rotations and rotation information are allowed.
+ *   4. loc_window_poses_device() AND the input estimates of the next resident solve become the kept poses followed by new_pose; counts[b]
+ *      changes, [3] included.
+ * Checked on the host, with nothing launched or changed — LOC_ERR_INVALID as loc_window_slide_resident_dev; LOC_ERR_UNSUPPORTED: the resident
+ * verdict is LOC_WINDOW_KERNEL_CHAIN3 (loc_window_slide_resident / loc_window_slide_resident_dev slide such a batch) or any verdict that is
+ * not an ordered 6-DoF chain; endpoint-1 lever arms; a handle with a table of full information matrices.
+ * Checked on the device, per window, by the wave that slides it: admit[b] = LOC_SLIDE_ADMIT_OK or the first rule broken, in the order 1, 2
+ * (new_s_counts included), 3 (the EdgeSE3 index rule included), 4, 5, 6, 8, 9; code 7 is never produced.  LOC_SLIDE_ADMIT_PAIRS depends on the
+ * resident verdict — _WAVE6: any new EdgeSE3 row, or more than one new pose-to-pose range row; _WAVE6S: more than one new EdgeSE3 row, or
+ * more than one new pose-to-pose range row; _CHAIN: never.  A refused window is left exactly as it was and reports status LOC_ERR_INVALID
+ * (codes 1 to 6 and 8) or LOC_ERR_UNSUPPORTED (code 9); the other windows slide and report LOC_OK.
+ * Afterwards the handle keeps its verdict (an ordered chain minus slot 0 plus a last slot joined to its predecessor alone is an ordered
+ * chain, and code 9 keeps the pair rule), the covariance pass is the chain pass again, and the host mirror is stale exactly as after
+ * loc_window_slide_resident_dev.  loc_window_last_covariance_ms reports the launch. */
+int loc_window_slide_plain_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
+                                        int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
+                                        int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
+                                        int32_t ns_new_max, const void* new_s_counts_dev, const void* new_s_idx_dev, const void* new_s_val_dev,
+                                        void* status_dev, void* admit_dev);
 /* The resident batch as it stands (a checkpoint; host arrays in loc_window_upload's layouts, n = the resident batch's windows; any pointer may
  * be NULL).  poses: the estimates the next resident solve starts from.  pinfo double [n][np_max][36]: the table of full information matrices;
  * LOC_ERR_INVALID when the handle has none.  Synchronous (waits for the last resident launch). */

@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = [
     "loc_window_timing_begin", "loc_window_timing_end",
     "loc_window_covariance_host", "loc_window_covariance_resident", "loc_window_last_covariance_ms", "loc_window_covariance_plan",
     "loc_window_marginal_prior_host", "loc_window_joint_covariance_host", "loc_window_joint_covariance_resident", "loc_window_joint_covariance_plan",
-    "loc_window_slide_resident", "loc_window_slide_resident_dev", "loc_window_download_tables",
+    "loc_window_slide_resident", "loc_window_slide_resident_dev", "loc_window_slide_plain_resident_dev", "loc_window_download_tables",
     "loc_window_edge_chi2_host", "loc_window_edge_chi2_resident", "loc_window_prune_resident",
     "loc_node_default_config", "loc_node_create", "loc_node_destroy", "loc_node_add_range", "loc_node_add_imu",
     "loc_node_add_pose", "loc_node_add_twist", "loc_node_add_lidar", "loc_node_add_rl_range", "loc_node_solve", "loc_node_get_path",
@@ -130,6 +130,7 @@ def lib():
     L.loc_window_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     L.loc_window_slide_resident.argtypes = [vp, vp, ip, dp, C.c_int32, ip, ip, dp, C.c_int32, ip, dp, vp, vp, vp, vp]
     L.loc_window_slide_resident_dev.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.loc_window_slide_plain_resident_dev.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.loc_window_download_tables.argtypes = [vp, ip, dp, ip, dp, ip, dp, ip, dp, dp]
     L.loc_window_edge_chi2_host.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, dp, ip]
     L.loc_window_edge_chi2_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp]

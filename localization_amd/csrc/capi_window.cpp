@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "capi_host.h"
+#include "slide_plain_admit.h"
 #include "window_dispatch.h"
 #include "window_kernel.h"
 #include "window_layouts.h"
@@ -948,12 +949,25 @@ int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, con
 
 // ---- the resident slide (window_slide_kernel.hip; DESIGN.md §2, "The resident slide") ------------------------------------------------------------
 // what both entries check without looking at a window; nothing is launched or changed on a refusal
-static int slide_check_handle(const loc_window* w, bool arrays_ok) {
+// plain: loc_window_slide_plain_resident_dev — the same checks, but the verdict is one of the ordered 6-DoF chain verdicts and the handle has no
+// table of full information matrices at all
+static int slide_check_handle(const loc_window* w, bool arrays_ok, bool plain = false) {
     if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
     if (!w->res.mirror_valid) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded");
     if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: no resident solve has run since the upload");
     if (!arrays_ok) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: new pose and new row arrays");
     if (int rc = check_pinfo_covers_resident(w)) return rc;
+    if (plain) {
+        const int t = resident_topology(w);
+        if (t == LOC_WINDOW_KERNEL_CHAIN3)
+            return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_plain_resident_dev: the resident batch is an ordered translation-only chain batch: "
+                                                    "loc_window_slide_resident / loc_window_slide_resident_dev slide it");
+        if (t != LOC_WINDOW_KERNEL_CHAIN && t != LOC_WINDOW_KERNEL_WAVE6 && t != LOC_WINDOW_KERNEL_WAVE6S)
+            return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_plain_resident_dev: the resident batch is not an ordered 6-DoF chain batch");
+        if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
+        if (w->opt.has_pinfo) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_plain_resident_dev: the handle has a table of full information matrices");
+        return LOC_OK;
+    }
     if (resident_topology(w) != LOC_WINDOW_KERNEL_CHAIN3)
         return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the resident batch is not an ordered translation-only chain batch");
     if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
@@ -1081,6 +1095,49 @@ int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* d
     sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
     if (int rc = slide_launches(w, st, sa, densify, fresh, true, (int32_t*)admit_dev)) return rc;
     w->res.mirror_stale = true;   // (refresh_mirror: the next reader of the mirror fetches it)
+    return LOC_OK;
+}
+
+// the plain drop for the ordered 6-DoF chain verdicts (window_slide_plain_kernel.hip; DESIGN.md §2, "The plain drop for 6-DoF chain windows"): what
+// Robot::new_vertex does with its oldest pose (robot.cpp:92-98).  One launch, nothing carried, no table; device arrays, no host pass, no copy,
+// no synchronisation and no allocation; each wave admits its own window (slide_plain_admit.h) and the host's mirror goes stale
+int loc_window_slide_plain_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
+                                        int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
+                                        int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
+                                        int32_t ns_new_max, const void* new_s_counts_dev, const void* new_s_idx_dev, const void* new_s_val_dev,
+                                        void* status_dev, void* admit_dev) {
+    if (int rc = slide_check_handle(w, new_pose_dev && nr_new_max >= 0 && np_new_max >= 0 && ns_new_max >= 0 &&
+                                           (nr_new_max == 0 || (new_r_counts_dev && new_r_idx_dev && new_r_val_dev)) && (np_new_max == 0 || (new_p_counts_dev && new_p_val_dev)) &&
+                                           (ns_new_max == 0 || (new_s_counts_dev && new_s_idx_dev && new_s_val_dev)), true))
+        return rc;
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    const int topology = resident_topology(w);
+    locamd::SlidePlainArgs sa{};
+    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
+    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
+    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal];
+    sa.s_idx = (int32_t*)w->dev.t[locamd::kSIdx]; sa.s_val = (double*)w->dev.t[locamd::kSVal];
+    sa.drop = (const int32_t*)drop_oldest_dev; sa.new_pose = (const double*)new_pose_dev;
+    sa.new_r_counts = (const int32_t*)new_r_counts_dev; sa.new_r_idx = (const int32_t*)new_r_idx_dev; sa.new_r_val = (const double*)new_r_val_dev;
+    sa.new_p_counts = (const int32_t*)new_p_counts_dev; sa.new_p_val = (const double*)new_p_val_dev;
+    sa.new_s_counts = (const int32_t*)new_s_counts_dev; sa.new_s_idx = (const int32_t*)new_s_idx_dev; sa.new_s_val = (const double*)new_s_val_dev;
+    sa.status = (int32_t*)status_dev; sa.admit = (int32_t*)admit_dev;
+    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max; sa.ns_new_max = ns_new_max;
+    sa.n_anchors = w->n_anchors;
+    sa.pair_rule = topology == LOC_WINDOW_KERNEL_WAVE6 ? locamd::kSlidePairsWave6 : topology == LOC_WINDOW_KERNEL_WAVE6S ? locamd::kSlidePairsWave6S : locamd::kSlidePairsNone;
+    sa.B = (int)w->res.n; sa.caps = w->caps;
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    const hipError_t e = locamd::launch_window_slide_plain(sa, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide_plain");
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipEventRecord(w->resident_done, st));
+    w->resident_inflight = true;
+    w->cov_pending = true;
+    w->res.cov = CovKind::Chain6;     // (loc_window_upload's verdict for these topologies; a batch the envelope pass held is classified again)
+    w->res.mirror_stale = true;       // (refresh_mirror: the next reader of the mirror fetches it)
     return LOC_OK;
 }
 

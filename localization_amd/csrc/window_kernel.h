@@ -187,6 +187,28 @@ hipError_t launch_window_slide(const SlideArgs& s, bool densify, hipStream_t str
 // LOC_ERR_UNSUPPORTED (code 7) and leaves the window as it was (densify: its table rows become diag(p_val[12..17]) all the same)
 hipError_t launch_window_slide_dev(const SlideArgs& s, int n_anchors, int32_t* admit, bool densify, hipStream_t stream);
 
+// the resident plain-drop slide of 6-DoF chain windows (window_slide_plain_kernel.hip; DESIGN.md §2, "The plain drop for 6-DoF chain
+// windows"): one wave per window, in place on the resident batch's tables, one launch, nothing carried.  The host has admitted NOTHING: drop
+// (may be nullptr: every window drops), new_pose and the new rows are the caller's device arrays; each wave admits its own window against
+// slide_plain_admit.h's rule, writes admit[b] / status[b] (each may be nullptr: LOC_OK, LOC_ERR_INVALID for codes 1 .. 6 and 8,
+// LOC_ERR_UNSUPPORTED for code 9) and either re-packs the window or leaves it as it was.
+struct SlidePlainArgs {
+    int32_t* counts; double* poses; double* poses_in;   // [B][4]; the optimised estimates x (read, then re-packed); the next solve's input estimates
+    int32_t* r_idx; double* r_val; int32_t* p_idx; double* p_val; int32_t* s_idx; double* s_val;
+    const int32_t* drop;                                 // [B] != 0: the window drops slot 0
+    const double* new_pose;                              // [B][12]
+    const int32_t* new_r_counts; const int32_t* new_r_idx; const double* new_r_val;   // [B], [B][nr_new_max][2], [B][nr_new_max][5]
+    const int32_t* new_p_counts; const double* new_p_val;                             // [B], [B][np_new_max][18]
+    const int32_t* new_s_counts; const int32_t* new_s_idx; const double* new_s_val;   // [B], [B][ns_new_max][4], [B][ns_new_max][48]
+    int32_t* status; int32_t* admit;                                                  // [B], [B]
+    int nr_new_max, np_new_max, ns_new_max;
+    int n_anchors;    // the anchor table's size at call time: new anchor codes are admitted against it
+    int pair_rule;    // SlidePairRule (slide_plain_admit.h): the pair rule of the resident verdict
+    int B;
+    WindowCaps caps;
+};
+hipError_t launch_window_slide_plain(const SlidePlainArgs& s, hipStream_t stream);
+
 // the per-edge chi2 audit and the outlier-range removal (edge_audit_kernel.hip; DESIGN.md §2, "Edge audit and outlier removal"): one wave per
 // window at a.poses, every structure; a.r_off1 / a.p_info as the handle has them.  All device arrays.
 struct EdgeAudit {

@@ -315,6 +315,33 @@ class WindowSolver(_lib.Handle):
         st = None if stream is None else C.c_void_p(stream.cuda_stream)
         check(self.L.loc_window_slide_resident_dev(self.h, st, ptr(drop_oldest), ptr(new_pose), nrn, *r_args, npn, *p_args, *outs))
 
+    def slide_plain_resident_dev(self, new_pose, new_ranges, new_priors=None, new_se3=None, drop_oldest=None, out=None, stream=None):
+        """The plain drop for resident 6-DoF chain batches (loc_window_slide_plain_resident_dev): slot 0 goes with every factor on it, nothing
+        is carried, new_pose and its factors are appended.  Every per-window input is in device memory, as for slide_resident_dev(): new_pose
+        float64 [B][12] (any rotation); new_ranges (counts int32 [B], r_idx int32 [B][nr_new_max][2], r_val float64 [B][nr_new_max][5],
+        nr_new_max) or None; new_priors (counts int32 [B], p_val float64 [B][np_new_max][18], np_new_max) or None; new_se3 (counts int32 [B],
+        s_idx int32 [B][ns_new_max][4], s_val float64 [B][ns_new_max][48], ns_new_max) or None; drop_oldest int32 [B] or None (every window
+        drops).  The capacities may be left out for objects with a shape.  out: (status, admit), each a device pointer, an object with
+        data_ptr() or None.  Each wave admits its own window: admit[b] is 0 or the code of the rule window b breaks, and a refused window stays
+        as it was.  Asynchronous on stream (a torch stream; None: the handle's own), no host pass, no copy: the caller keeps the arrays alive
+        and unchanged until the stream has passed the call.  Plumbing only: the library checks everything."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        nrn, r_args = 0, (None, None, None)
+        if new_ranges is not None:
+            nrn = int(new_ranges[3]) if len(new_ranges) > 3 else int(new_ranges[1].shape[-2])
+            r_args = tuple(ptr(t) for t in new_ranges[:3])
+        npn, p_args = 0, (None, None)
+        if new_priors is not None:
+            npn = int(new_priors[2]) if len(new_priors) > 2 else int(new_priors[1].shape[-2])
+            p_args = tuple(ptr(t) for t in new_priors[:2])
+        nsn, s_args = 0, (None, None, None)
+        if new_se3 is not None:
+            nsn = int(new_se3[3]) if len(new_se3) > 3 else int(new_se3[1].shape[-2])
+            s_args = tuple(ptr(t) for t in new_se3[:3])
+        outs = [ptr(t) for t in (out if out is not None else (None,) * 2)]
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_slide_plain_resident_dev(self.h, st, ptr(drop_oldest), ptr(new_pose), nrn, *r_args, npn, *p_args, nsn, *s_args, *outs))
+
     def download_batch(self):
         """The resident batch as it stands, as a WindowBatch (loc_window_download_tables): counts, the estimates the next resident solve
         starts from, every index and value table, and p_info when the handle has a table of full information matrices."""

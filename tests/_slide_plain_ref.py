@@ -1,0 +1,302 @@
+"""Test helper: the rule of the resident plain-drop slide of 6-DoF chain windows (loc_window_slide_plain_resident_dev; DESIGN.md §2, "The plain
+drop for 6-DoF chain windows") stated in numpy on a WindowBatch — what tests/test_gpu_resident_slide_plain.py holds the device tables to, bit
+for bit.  Like tests/_slide_ref.py it moves rows and computes nothing.  It also holds the case table of that test and the refusals both it
+and tests/test_resident_slide_plain_cpu.py run.
+
+The windows are cut from 6-DoF streams in the reference's creation order (Stream): per pose its anchor ranges (with the antenna's lever arm),
+the zero-range smoothness edge to the pose before it, IMU rotation priors, optionally a lidar-style z prior and EdgeSE3 twist factors."""
+import numpy as np
+from scipy.spatial.transform import Rotation
+
+ANCH = np.array([[3, -3, 0.58], [3, 3, 1.97], [-3, 3, 0.54], [-3, -3, 1.76]], dtype=float)
+LEVER = np.array([0.1, 0.0, -0.05])
+RANGE_INFO = 1.0 / 0.055 ** 2
+SMOOTH_INFO = 1.0 / (5.0 * (1 / 32) / 3) ** 2
+IMU_INFO = np.array([0, 0, 0, 1, 1, 1.0]) / 4.592449e-06
+Z_INFO = np.array([0, 0, 1 / 0.05, 0, 0, 0.0])
+LOC_ERR_INVALID, LOC_ERR_UNSUPPORTED = -1, -5
+TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+
+
+def _inv_rows(R, t):
+    """Z^-1 as the tables hold it: R(9) row-major, t(3)"""
+    Ri = np.asarray(R).T
+    return np.concatenate([Ri.reshape(9), -Ri @ np.asarray(t)])
+
+
+class Stream:
+    """L poses of one robot and every factor of pose k, as rows in the tables' layouts for the window slot the pose takes"""
+
+    def __init__(self, seed, L, na=1, priors=1, se3=0, reverse=False, missing=()):
+        rng = np.random.default_rng(seed)
+        self.L, self.na, self.priors, self.se3, self.reverse, self.missing = L, na, priors, se3, reverse, tuple(missing)
+        self.truth_t = np.cumsum(rng.normal(0, 0.05, (L, 3)), axis=0) + np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.5, 1.5), 1.1])
+        self.truth_R = Rotation.from_rotvec(np.cumsum(rng.normal(0, 0.03, (L, 3)), axis=0) + rng.normal(0, 0.3, 3))
+        self.est_t = self.truth_t + rng.normal(0, 0.05, (L, 3))
+        self.est_R = (self.truth_R * Rotation.from_rotvec(rng.normal(0, 0.02, (L, 3)))).as_matrix()
+        self.which = np.array([rng.permutation(4)[:na] for _ in range(L)])
+        self.meas = np.array([[np.float32(np.linalg.norm(self.truth_t[k] + self.truth_R[k].apply(LEVER) - ANCH[a]) + rng.normal(0, 0.03)) for a in self.which[k]]
+                              for k in range(L)], dtype=float)
+        self.imu_R = (self.truth_R * Rotation.from_rotvec(rng.normal(0, 2e-3, (L, 3)))).as_matrix()
+        self.z = self.truth_t[:, 2] + rng.normal(0, 0.02, L)
+        self.twist = []   # [k][j]: (Zt, ZR, info) of the j-th EdgeSE3 between poses k - 1 and k
+        for k in range(L):
+            rows = []
+            for _ in range(se3 if k else 0):
+                Ra, Rb = self.truth_R[k - 1], self.truth_R[k]
+                Zt = Ra.inv().apply(self.truth_t[k] - self.truth_t[k - 1]) + rng.normal(0, 0.01, 3)
+                ZR = (Ra.inv() * Rb * Rotation.from_rotvec(rng.normal(0, 0.01, 3))).as_matrix()
+                A = rng.normal(size=(6, 6)); info = A @ A.T + 6 * np.eye(6); info *= 1e3 / np.trace(info)
+                rows.append((Zt, ZR, info))
+            self.twist.append(rows)
+
+    def pose(self, k):
+        return np.concatenate([self.est_R[k].reshape(9), self.est_t[k]])
+
+    def rows(self, k, s):
+        """(ranges [(idx2, val5)], priors [val18], se3 [(idx4, val48)]) of pose k as window slot s; s = 0: no factor to a pose before it"""
+        ranges = [((s, -1 - int(a)), (d, RANGE_INFO, *LEVER)) for a, d in zip(self.which[k], self.meas[k])]
+        if s > 0 and k not in self.missing:
+            ranges.append((((s, s - 1) if self.reverse else (s - 1, s)), (0.0, SMOOTH_INFO, 0.0, 0.0, 0.0)))
+        priors = []
+        if self.priors >= 1:
+            priors.append(np.concatenate([_inv_rows(self.imu_R[k], self.est_t[k]), IMU_INFO]))
+        if self.priors >= 2:   # addLidarEdge: information on z alone, measurement = the pose with another z
+            priors.append(np.concatenate([_inv_rows(self.est_R[k], [self.est_t[k, 0], self.est_t[k, 1], self.z[k]]), Z_INFO]))
+        se3 = []
+        if s > 0:
+            for j, (Zt, ZR, info) in enumerate(self.twist[k]):
+                fwd = (k + j) % 2 == 0   # every other one stored the other way round
+                Z = _inv_rows(ZR, Zt) if fwd else np.concatenate([np.asarray(ZR).reshape(9), Zt])   # (the reverse edge measures the inverse)
+                se3.append((((s - 1, s) if fwd else (s, s - 1)) + (int(k % 3 != 0), 0), np.concatenate([Z, info.reshape(36)])))
+        return ranges, priors, se3
+
+
+def _put(wb, i, ranges, priors, se3, slot):
+    nv, nr, npr, ns = (int(x) for x in wb.counts[i])
+    for ix, val in ranges:
+        wb.r_idx[i, nr] = ix; wb.r_val[i, nr] = val; nr += 1
+    for val in priors:
+        wb.p_idx[i, npr] = slot; wb.p_val[i, npr] = val; npr += 1
+    for ix, val in se3:
+        wb.s_idx[i, ns] = ix; wb.s_val[i, ns] = val; ns += 1
+    wb.counts[i, 1:] = (nr, npr, ns)
+
+
+def window_batch(la, streams, T, caps):
+    """the first T[i] poses of streams[i] as window i"""
+    wb = la.WindowBatch(len(streams), *caps)
+    for i, st in enumerate(streams):
+        for s in range(int(T[i])):
+            wb.poses[i, s] = st.pose(s)
+            wb.counts[i, 0] = s + 1
+            _put(wb, i, *st.rows(s, s), s)
+    return wb
+
+
+def new_rows(streams, consumed, slot):
+    """(new_pose [B][12], new_ranges, new_priors, new_se3) for pose consumed[i] of streams[i] appended as slot slot[i], every capacity the
+    largest any window needs (at least 1)"""
+    B = len(streams)
+    per = [st.rows(int(consumed[i]), int(slot[i])) for i, st in enumerate(streams)]
+    nrn, npn, nsn = (max(1, max(len(p[k]) for p in per)) for k in range(3))
+    pose = np.stack([st.pose(int(consumed[i])) for i, st in enumerate(streams)])
+    rc, ri, rv = np.zeros(B, dtype=np.int32), np.zeros((B, nrn, 2), dtype=np.int32), np.zeros((B, nrn, 5))
+    pc, pv = np.zeros(B, dtype=np.int32), np.zeros((B, npn, 18))
+    sc, si, sv = np.zeros(B, dtype=np.int32), np.zeros((B, nsn, 4), dtype=np.int32), np.zeros((B, nsn, 48))
+    for i, (ranges, priors, se3) in enumerate(per):
+        rc[i], pc[i], sc[i] = len(ranges), len(priors), len(se3)
+        for e, (ix, val) in enumerate(ranges):
+            ri[i, e] = ix; rv[i, e] = val
+        for e, val in enumerate(priors):
+            pv[i, e] = val
+        for e, (ix, val) in enumerate(se3):
+            si[i, e] = ix; sv[i, e] = val
+    return pose, (rc, ri, rv), (pc, pv), (sc, si, sv)
+
+
+def slide_plain_ref(la, wb, new_pose, new_ranges=None, new_priors=None, new_se3=None, drop_oldest=None, refused=()):
+    """The batch after the plain-drop slide of wb (poses: the solved estimates x).  new_ranges (counts [B], r_idx [B][n][2], r_val [B][n][5]),
+    new_se3 (counts [B], s_idx [B][n][4], s_val [B][n][48]) in the new numbering; new_priors (counts [B], p_val [B][n][18]) on the new slot;
+    drop_oldest [B] (None: every window drops).  refused: windows the call leaves as they are; every other window must be admissible
+    (asserted)."""
+    B = wb.B
+    nv_max, nr_max, np_max, ns_max = wb.caps
+    out = la.WindowBatch(B, *wb.caps)
+    new_pose = np.asarray(new_pose, dtype=float).reshape(B, 12)
+    for b in range(B):
+        if b in refused:
+            for name in TABLES:
+                getattr(out, name)[b] = getattr(wb, name)[b]
+            continue
+        nv, nr, npr, ns = (int(x) for x in wb.counts[b])
+        assert nv >= 1
+        drop = True if drop_oldest is None else bool(np.broadcast_to(drop_oldest, (B,))[b])
+        d = int(drop)
+        ranges = [(tuple(int(x) for x in wb.r_idx[b, e]), wb.r_val[b, e].copy()) for e in range(nr)]
+        priors = [(int(wb.p_idx[b, e]), wb.p_val[b, e].copy()) for e in range(npr)]
+        se3 = [(tuple(int(x) for x in wb.s_idx[b, e]), wb.s_val[b, e].copy()) for e in range(ns)]
+        if drop:
+            ranges = [((v0 - 1, v1 - 1 if v1 > 0 else v1), val) for (v0, v1), val in ranges if v0 != 0 and v1 != 0]
+            priors = [(v - 1, val) for v, val in priors if v != 0]
+            se3 = [((vi - 1, vj - 1, rb, pad), val) for (vi, vj, rb, pad), val in se3 if vi != 0 and vj != 0]
+        poses = wb.poses[b, d:nv]
+        s = len(poses)   # the new slot
+        if new_ranges is not None:
+            ranges += [(tuple(int(x) for x in new_ranges[1][b][e]), np.asarray(new_ranges[2][b][e], dtype=float).copy()) for e in range(int(new_ranges[0][b]))]
+        if new_priors is not None:
+            priors += [(s, np.asarray(new_priors[1][b][e], dtype=float).copy()) for e in range(int(new_priors[0][b]))]
+        if new_se3 is not None:
+            se3 += [(tuple(int(x) for x in new_se3[1][b][e]), np.asarray(new_se3[2][b][e], dtype=float).copy()) for e in range(int(new_se3[0][b]))]
+        assert s + 1 <= nv_max and len(ranges) <= nr_max and len(priors) <= np_max and len(se3) <= ns_max, (b, s, len(ranges), len(priors), len(se3))
+        out.counts[b] = (s + 1, len(ranges), len(priors), len(se3))
+        out.poses[b, :s] = poses
+        out.poses[b, s] = new_pose[b]
+        for e, (ix, val) in enumerate(ranges):
+            out.r_idx[b, e] = ix; out.r_val[b, e] = val
+        for e, (v, val) in enumerate(priors):
+            out.p_idx[b, e] = v; out.p_val[b, e] = val
+        for e, (ix, val) in enumerate(se3):
+            out.s_idx[b, e] = ix; out.s_val[b, e] = val
+    return out
+
+
+def assert_same_tables(got, ref, what="", windows=None):
+    """counts, poses and every index and value table of two batches, bitwise, on the used rows (rows beyond the counts are not compared)"""
+    ws = range(ref.B) if windows is None else windows
+    for b in ws:
+        assert got.counts[b].tolist() == ref.counts[b].tolist(), (what, b, got.counts[b], ref.counts[b])
+        nv, nr, npr, ns = (int(x) for x in ref.counts[b])
+        for name, n in (("poses", nv), ("r_idx", nr), ("r_val", nr), ("p_idx", npr), ("p_val", npr), ("s_idx", ns), ("s_val", ns)):
+            x, y = getattr(got, name)[b, :n], getattr(ref, name)[b, :n]
+            assert x.tobytes() == y.tobytes(), (what, name, b, x, y)
+
+
+def copy_batch(la, wb):
+    out = la.WindowBatch(wb.B, *wb.caps)
+    for name in TABLES:
+        getattr(out, name)[:] = getattr(wb, name)
+    return out
+
+
+# ---- the cases: name -> eight windows ------------------------------------------------------------------------------------------------------------------
+# T: the windows' lengths; na / priors / se3: anchor ranges and priors per pose, EdgeSE3 factors per consecutive pair; kernel: what the
+# resident solve runs on (None: not asserted).  The smallest shapes that reach a second compaction step ("long": 159 range, 80 prior and 78
+# EdgeSE3 rows), every verdict (WAVE6: imu, lidar, ragged; WAVE6S: twist; CHAIN: long) and every ragged branch.
+CASES = {
+    "imu": dict(T=[6] * 8, kernel="wave6_lm_kernel", reverse=(1, 4, 7), missing={2: (3, 7)}),   # cfg/uwb_imu.yaml: IMU priors, a lever arm
+    "lidar": dict(T=[6] * 8, priors=2),                                                        # cfg/uwb_imu_lidar.yaml: two priors per pose
+    "twist": dict(T=[6] * 8, se3=1, kernel="wave6_lm_kernel<SE3>"),                            # cfg/uwb_twist.yaml: an EdgeSE3 per pair next to the range
+    "ragged": dict(T=[1, 2, 4, 6, 1, 2, 4, 6], drop=[1, 0, 1, 1, 0, 1, 0, 1], nv_max=9),
+    "long": dict(T=[40] * 8, na=3, priors=2, se3=2, kernel="window_lm_kernel"),
+}
+SEED = {name: 9300 + 10 * k for k, name in enumerate(CASES)}
+SLIDES = 3
+
+
+def caps_of(nv_max, na, priors, se3, spare=(0, 0, 0)):
+    return nv_max, nv_max * na + (nv_max - 1) + spare[0], nv_max * priors + spare[1], (nv_max - 1) * se3 + spare[2]
+
+
+def case_batch(la, name, spare=(0, 0, 0)):
+    """(batch, streams, spec) of a case; spec["drop"]: drop_oldest of every slide (None: all), spec["consumed"]: stream poses used so far"""
+    spec = dict(CASES[name])
+    T = spec["T"]
+    na, priors, se3 = spec.get("na", 1), spec.get("priors", 1), spec.get("se3", 0)
+    streams = [Stream(SEED[name] + i, T[i] + SLIDES + 1, na, priors, se3, reverse=i in spec.get("reverse", ()), missing=spec.get("missing", {}).get(i, ()))
+               for i in range(8)]
+    wb = window_batch(la, streams, T, caps_of(spec.get("nv_max", max(T)), na, priors, se3, spare))
+    spec["consumed"] = np.array(T)
+    spec["drop"] = None if "drop" not in spec else np.array(spec["drop"], dtype=np.int32)
+    return wb, streams, spec
+
+
+def next_inputs(wb, streams, spec):
+    """(new_pose, new_ranges, new_priors, new_se3, drop_oldest) of the next slide of a case at batch wb (its counts), advancing spec["consumed"]"""
+    drop = spec["drop"]
+    nv = wb.counts[:, 0].astype(int)
+    slot = nv - (1 if drop is None else (drop != 0).astype(int))
+    pose, ranges, priors, se3 = new_rows(streams, spec["consumed"], slot)
+    spec["consumed"] = spec["consumed"] + 1
+    return pose, ranges, priors, se3, drop
+
+
+# ---- the refusals: one rule broken in window 1 alone ------------------------------------------------------------------------------------------------------
+# Two batches of eight full six-pose windows under tight capacities, one per pair rule: "imu" (verdict WAVE6; room for ONE EdgeSE3 row, which
+# no window has) and "twist" (verdict WAVE6S; room for one range row more than a window holds).  variant -> (case, the code window 1 reports)
+REFUSED = 1
+REFUSALS = {
+    "no_poses": ("imu", 1),           # window 1 was uploaded without poses
+    "count_r": ("imu", 2),            # new_r_counts = -1
+    "count_p": ("imu", 2),            # new_p_counts = np_new_max + 1
+    "count_s": ("twist", 2),          # new_s_counts = -1
+    "index_r": ("imu", 3),            # a range row on s - 2
+    "index_s": ("twist", 3),          # an EdgeSE3 row that joins s - 2 and s
+    "index_s_loop": ("twist", 3),     # an EdgeSE3 row from s to s
+    "nv_max": ("imu", 4),             # a full window that only grows
+    "nr_max": ("imu", 5),             # a second anchor range on the new pose
+    "np_max": ("imu", 6),             # a second prior on the new pose
+    "ns_max": ("twist", 8),           # a second EdgeSE3 on the new pair (code 8 comes before code 9)
+    "pairs_wave6": ("imu", 9),        # an EdgeSE3 row under the verdict WAVE6
+    "pairs_wave6s": ("twist", 9),     # a second pose-to-pose range row under the verdict WAVE6S
+}
+REFUSAL_SPARE = {"imu": (0, 0, 1), "twist": (1, 0, 0)}
+
+
+def status_of(codes):
+    codes = np.asarray(codes)
+    return np.where(codes == 0, 0, np.where(codes == 9, LOC_ERR_UNSUPPORTED, LOC_ERR_INVALID)).astype(np.int32)
+
+
+def refusal_batch(la, variant):
+    """(batch, streams, spec) a refusal variant uploads"""
+    case = REFUSALS[variant][0]
+    wb, streams, spec = case_batch(la, case, REFUSAL_SPARE[case])
+    if variant == "no_poses":
+        wb.counts[REFUSED] = 0
+    return wb, streams, spec
+
+
+def _grown(a, n):
+    """a [B][m][...] with room for n rows per window"""
+    if a.shape[1] >= n:
+        return a
+    out = np.zeros((a.shape[0], n) + a.shape[2:], dtype=a.dtype)
+    out[:, :a.shape[1]] = a
+    return out
+
+
+def refusing_inputs(wb, streams, spec, variant):
+    """(benign, refusing): the next slide's inputs as every window admits them (window 1 of "no_poses" apart), and the same with window 1
+    breaking the variant's rule.  Both have the same capacities."""
+    nv = wb.counts[:, 0].astype(int)
+    consumed = spec["consumed"].copy()
+    slot = np.maximum(nv - 1, 0)
+    pose, (rc, ri, rv), (pc, pv), (sc, si, sv) = new_rows(streams, consumed, slot)
+    ri, rv, pv, si, sv = _grown(ri, 3), _grown(rv, 3), _grown(pv, 2), _grown(si, 2), _grown(sv, 2)
+    drop = np.ones(8, dtype=np.int32)
+    benign = (pose, (rc, ri, rv), (pc, pv), (sc, si, sv), drop)
+    rc, ri, rv, pc, pv, sc, si, sv, drop = (a.copy() for a in (rc, ri, rv, pc, pv, sc, si, sv, drop))
+    w, s = REFUSED, int(slot[REFUSED])
+    if variant == "count_r": rc[w] = -1
+    elif variant == "count_p": pc[w] = pv.shape[1] + 1
+    elif variant == "count_s": sc[w] = -1
+    elif variant == "index_r": ri[w, 0] = (s - 2, -1)
+    elif variant == "index_s": si[w, 0, :2] = (s - 2, s)
+    elif variant == "index_s_loop": si[w, 0, :2] = (s, s)
+    elif variant == "nv_max":   # the rows of a window that keeps slot 0: they name slot nv
+        drop[w] = 0
+        ri[w, :int(rc[w])] += (ri[w, :int(rc[w])] >= 0)
+    elif variant == "nr_max":
+        ri[w, int(rc[w])] = (s, -1); rv[w, int(rc[w])] = (2.5, RANGE_INFO, *LEVER); rc[w] += 1
+    elif variant == "np_max":
+        pv[w, int(pc[w])] = pv[w, 0]; pc[w] += 1
+    elif variant == "ns_max":
+        si[w, int(sc[w])] = (s, s - 1, 0, 0); sv[w, int(sc[w])] = sv[w, 0]; sc[w] += 1
+    elif variant == "pairs_wave6":
+        si[w, 0] = (s - 1, s, 1, 0); sv[w, 0, [0, 4, 8]] = 1.0; sv[w, 0, 12::7] = 10.0; sc[w] = 1
+    elif variant == "pairs_wave6s":
+        ri[w, int(rc[w])] = (s, s - 1); rv[w, int(rc[w])] = (0.0, 0.5 * SMOOTH_INFO, 0, 0, 0); rc[w] += 1
+    else:
+        assert variant == "no_poses"
+    return benign, (pose, (rc, ri, rv), (pc, pv), (sc, si, sv), drop)
