@@ -592,6 +592,102 @@ int loc_window_slide_plain_resident_dev(loc_window* w, void* hip_stream, const v
                                         int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
                                         int32_t ns_new_max, const void* new_s_counts_dev, const void* new_s_idx_dev, const void* new_s_val_dev,
                                         void* status_dev, void* admit_dev);
+/* Rows from raw messages ("Rows from raw messages"): the step that turns ONE message per window into the window's newest pose
+ * and its factors, on the device — Localization::addRangeEdge (localization.cpp:297-376: the outlier gate :306-313, sigma^2 :318-319, the
+ * two-edge topology :327-340, the antenna lever arm :333-334), Robot::new_vertex (robot.cpp:75-110: the initial estimate :90, drop-oldest
+ * :92-98), addImuEdge (:499-535), addLidarEdge (:462-496) and addTwistEdge with twist2transform (:438-459, :560-605).  One launch
+ * (window_message_kernel.hip) writes exactly the arrays the two resident slides read, so (messages -> rows -> slide -> solve) queues on a
+ * stream with nothing but the messages crossing to the device.  The rule is stated once, for host and device, in
+ * localization_amd/csrc/message_rows.h.
+ * Configuration, per handle (loc_window_set_message_config): trajectory_length in [1, nv_max]; maximum_velocity (:319); distance_outlier (:78;
+ * <= 0 disables the gate); the antenna table antenna_xyz_host double [n_antenna][3] (:111-123; a message's `antenna` is 1-based, 0 = none),
+ * copied to the device by the call.  The call also allocates the handle's own block of the eleven output arrays at batch capacity: no later
+ * call allocates.  LOC_ERR_INVALID: a NULL handle or configuration, trajectory_length outside [1, nv_max], a maximum_velocity or
+ * distance_outlier that is not a number, n_antenna < 0, n_antenna > 0 without a table.  Synchronous (waits for the last resident launch).
+ * The message of window b, DEVICE arrays in one struct of pointers (n = the resident batch's windows):
+ *   kind         int32 [n]       bit set: LOC_MSG_RANGE 1, LOC_MSG_IMU 2, LOC_MSG_LIDAR 4, LOC_MSG_TWIST 8.  Legal: 0 (no message), RANGE with
+ *                                any subset of IMU / LIDAR, TWIST alone
+ *   dt           double [n]      the message stamp minus the newest pose's stamp (:316, :442).  The caller keeps the stamps: the handle has
+ *                                no per-window state for them
+ *   anchor, antenna int32 [n], distance, distance_err float [n]     the range message (responder = anchor table index)
+ *   imu          double [n][7]   q xyzw, then orientation_covariance[0], [4], [8]
+ *   lidar_z      double [n]      the lidar height
+ *   twist        double [n][42]  linear 3, angular 3, covariance 36 row-major
+ * kinds_mask names the bits that may occur: kind and dt are always required, every other array exactly when its bit is in the mask (it may
+ * be NULL otherwise and is then never read).
+ * The output of window b, in the slides' layouts at the capacities LOC_MSG_NR_NEW / _NP_NEW / _NS_NEW — with nv the window's count, x its
+ * newest solved pose (slot nv - 1 of loc_window_poses_device()), drop = (nv == trajectory_length) and s = nv - drop:
+ *   drop_oldest[b] = drop; new_pose[b] = x (robot.cpp:90)
+ *   RANGE  (the frame-id branch of :327 is always taken, as every cfg stream of the reference takes it)
+ *          row 0 (s, -1 - anchor): measurement (double)distance, information 1 / ((double)distance_err)^2, lever arm antenna_xyz[antenna - 1]
+ *          or zeros for antenna == 0; row 1 (s - 1, s): measurement 0, information 1 / (maximum_velocity dt / 3)^2, no lever arm — left out
+ *          when s == 0
+ *   IMU    first: new_pose's R = the quaternion's matrix (not normalised), t kept; one prior row Z^-1 = new_pose^-1, information
+ *          (0, 0, 0, 1/c0, 1/c4, 1/c8)
+ *   LIDAR  after IMU: new_pose.t[2] = lidar_z; one prior row Z^-1 = new_pose^-1, information (0, 0, 1/0.05, 0, 0, 0)
+ *   TWIST  no range or prior row; one EdgeSE3 row (s - 1, s, 1, 0), Z^-1 of setRPY(w dt) / v dt as the node forms it, information
+ *          (cov dt^2)^-1
+ *   gate   a RANGE message with distance_outlier > 0 and nv == trajectory_length (the window is at its lag: the batch's statement of
+ *          number_measurements > trajectory_length) is rejected when | ||x.t - anchor|| - (double)distance | > distance_outlier
+ * verdict[b], by the first test that decides: LOC_MSG_NONE (kind == 0); LOC_MSG_INVALID (nv <= 0 or nv > trajectory_length; an illegal kind
+ * or a bit outside kinds_mask; anchor outside the anchor table; antenna outside [0, n_antenna]; TWIST with s == 0); LOC_MSG_REJECTED (the
+ * gate); LOC_MSG_INVALID (an information value that must be finite and positive and is not: distance_err == 0, dt == 0 with a row 1, a zero
+ * or negative IMU covariance — STRICTER than the reference, which hands g2o an infinity); LOC_MSG_SINGULAR (the twist covariance times dt^2
+ * has no inverse); LOC_MSG_APPENDED.  For every verdict but APPENDED the three counts are written as -1 — both slides then refuse that
+ * window with LOC_SLIDE_ADMIT_COUNT and leave it exactly as it was — no row is written, and new_pose[b] is still x.  Rows at or beyond a
+ * count are left unwritten.  Everything is bit for bit what message_rows.h gives on the host, except the rotation of a TWIST row with a
+ * non-zero angular rate (sin and cos: DESIGN.md §3).
+ * loc_window_message_rows_dev: build only, into caller-owned DEVICE arrays (verdict may be NULL).  Asynchronous on hip_stream (NULL = the
+ * handle's own stream), ordered after the last resident launch; no host pass, no copy, no synchronisation, no allocation.  It serves every
+ * resident verdict (it reads only counts and poses) and needs no option.  LOC_ERR_INVALID, with nothing launched: a NULL handle, no
+ * configuration, nothing uploaded, no resident solve since the upload, kinds_mask with unknown bits, a NULL array under a mask bit (kind
+ * and dt always), a NULL output other than verdict.
+ * loc_window_push_messages_resident_dev: builds into the handle's own block, then calls the slide the resident verdict calls for on the
+ * same stream — LOC_WINDOW_KERNEL_CHAIN3: loc_window_slide_resident_dev (with its marginal carry); _CHAIN / _WAVE6 / _WAVE6S:
+ * loc_window_slide_plain_resident_dev.  Every host refusal of those slides is returned unchanged with NOTHING launched, the build included.
+ * verdict_dev int32 [n], status_dev int32 [n] and admit_dev int32 [n] may be NULL.  Read verdict FIRST: a window with LOC_MSG_NONE or
+ * _REJECTED shows admit code LOC_SLIDE_ADMIT_COUNT (and status LOC_ERR_INVALID), and that is not an error.  The slide's own per-window
+ * refusals appear in admit_dev as they do today: LOC_SLIDE_ADMIT_NOT_TRANSLATION for an IMU message or a lever arm on a translation-only
+ * batch, the capacities, the pair rule. */
+enum { LOC_MSG_RANGE = 1, LOC_MSG_IMU = 2, LOC_MSG_LIDAR = 4, LOC_MSG_TWIST = 8 };
+enum { LOC_MSG_NONE = 0, LOC_MSG_APPENDED = 1, LOC_MSG_REJECTED = 2, LOC_MSG_INVALID = 3, LOC_MSG_SINGULAR = 4 };
+#define LOC_MSG_NR_NEW 2
+#define LOC_MSG_NP_NEW 2
+#define LOC_MSG_NS_NEW 1
+typedef struct loc_window_message_config {
+    int32_t trajectory_length;
+    double maximum_velocity;
+    double distance_outlier;
+} loc_window_message_config;
+typedef struct loc_window_messages {
+    const void* kind;          /* int32 [n] */
+    const void* dt;            /* double [n] */
+    const void* anchor;        /* int32 [n] */
+    const void* antenna;       /* int32 [n] */
+    const void* distance;      /* float [n] */
+    const void* distance_err;  /* float [n] */
+    const void* imu;           /* double [n][7] */
+    const void* lidar_z;       /* double [n] */
+    const void* twist;         /* double [n][42] */
+} loc_window_messages;
+typedef struct loc_window_message_rows {
+    void* drop_oldest;         /* int32 [n] */
+    void* new_pose;            /* double [n][12] */
+    void* new_r_counts;        /* int32 [n] */
+    void* new_r_idx;           /* int32 [n][LOC_MSG_NR_NEW][2] */
+    void* new_r_val;           /* double [n][LOC_MSG_NR_NEW][5] */
+    void* new_p_counts;        /* int32 [n] */
+    void* new_p_val;           /* double [n][LOC_MSG_NP_NEW][18] */
+    void* new_s_counts;        /* int32 [n] */
+    void* new_s_idx;           /* int32 [n][LOC_MSG_NS_NEW][4] */
+    void* new_s_val;           /* double [n][LOC_MSG_NS_NEW][48] */
+    void* verdict;             /* int32 [n], may be NULL */
+} loc_window_message_rows;
+int loc_window_set_message_config(loc_window* w, const loc_window_message_config* cfg, int32_t n_antenna, const double* antenna_xyz_host);
+int loc_window_message_rows_dev(loc_window* w, void* hip_stream, int32_t kinds_mask, const loc_window_messages* msgs,
+                                const loc_window_message_rows* out);
+int loc_window_push_messages_resident_dev(loc_window* w, void* hip_stream, int32_t kinds_mask, const loc_window_messages* msgs,
+                                          void* verdict_dev, void* status_dev, void* admit_dev);
 /* The resident batch as it stands (a checkpoint; host arrays in loc_window_upload's layouts, n = the resident batch's windows; any pointer may
  * be NULL).  poses: the estimates the next resident solve starts from.  pinfo double [n][np_max][36]: the table of full information matrices;
  * LOC_ERR_INVALID when the handle has none.  Synchronous (waits for the last resident launch). */

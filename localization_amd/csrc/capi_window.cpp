@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "capi_host.h"
+#include "message_rows.h"
 #include "slide_plain_admit.h"
 #include "window_dispatch.h"
 #include "window_kernel.h"
@@ -107,6 +108,13 @@ struct loc_window {
     locamd::StagingPair pairs, slide;
     bool opt_slide = false;         // option "resident_slide"
     char* d_slide_mp = nullptr;     // a slide's marginal pass: its drop table (zeros) and results for B windows (slide_marginal_layout)
+    // rows from raw messages (loc_window_set_message_config): the configuration, the antenna table's device copy and the handle's own block of
+    // window_message_kernel's outputs for B windows (message_rows_layout), which loc_window_push_messages_resident_dev builds into
+    bool msg_set = false;
+    loc_window_message_config msg_cfg{};
+    int n_antenna = 0, antenna_cap = 0;
+    double* d_antenna = nullptr;
+    char* d_msg_rows = nullptr;
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -139,7 +147,7 @@ int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
     void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws,
-                    w->d_stage, w->d_cov, w->d_slide_mp};
+                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
@@ -1139,6 +1147,105 @@ int loc_window_slide_plain_resident_dev(loc_window* w, void* hip_stream, const v
     w->res.cov = CovKind::Chain6;     // (loc_window_upload's verdict for these topologies; a batch the envelope pass held is classified again)
     w->res.mirror_stale = true;       // (refresh_mirror: the next reader of the mirror fetches it)
     return LOC_OK;
+}
+
+// ---- rows from raw messages (window_message_kernel.hip, message_rows.h; DESIGN.md §2, "Rows from raw messages") ----------------------------------
+// Localization::addRangeEdge (localization.cpp:297-376), Robot::new_vertex (robot.cpp:75-110), addImuEdge (:499-535), addLidarEdge (:462-496) and
+// addTwistEdge (:438-459, :560-605) for a resident batch: the configuration those read (:72-78, :111-123), per handle
+int loc_window_set_message_config(loc_window* w, const loc_window_message_config* cfg, int32_t n_antenna, const double* antenna_xyz_host) {
+    if (!w || !cfg) return locamd_fail(LOC_ERR_INVALID, "loc_window_set_message_config: null");
+    if (cfg->trajectory_length < 1 || cfg->trajectory_length > w->caps.nv_max)
+        return locamd_fail(LOC_ERR_INVALID, "loc_window_set_message_config: trajectory_length must be in [1, nv_max]");
+    if (!(cfg->maximum_velocity == cfg->maximum_velocity) || !(cfg->distance_outlier == cfg->distance_outlier))
+        return locamd_fail(LOC_ERR_INVALID, "loc_window_set_message_config: maximum_velocity and distance_outlier must be numbers");
+    if (n_antenna < 0 || (n_antenna > 0 && !antenna_xyz_host)) return locamd_fail(LOC_ERR_INVALID, "loc_window_set_message_config: the antenna table");
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = wait_resident(w)) return rc;   // a resident launch may still be reading the table
+    if (n_antenna > w->antenna_cap) {
+        double* p = nullptr;
+        LOC_HIP(hipMalloc((void**)&p, (size_t)n_antenna * 3 * sizeof(double)));
+        if (w->d_antenna) (void)hipFree(w->d_antenna);
+        w->d_antenna = p;
+        w->antenna_cap = n_antenna;
+    }
+    if (n_antenna > 0) LOC_HIP(hipMemcpy(w->d_antenna, antenna_xyz_host, (size_t)n_antenna * 3 * sizeof(double), hipMemcpyHostToDevice));
+    if (!w->d_msg_rows) LOC_HIP(hipMalloc((void**)&w->d_msg_rows, locamd::message_rows_layout((size_t)w->B).end));
+    w->n_antenna = n_antenna;
+    w->msg_cfg = *cfg;
+    w->msg_set = true;
+    return LOC_OK;
+}
+// what both entries check without looking at a window; nothing is launched or changed on a refusal
+static int message_check_handle(const loc_window* w, int32_t kinds_mask, const loc_window_messages* m) {
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
+    if (!w->msg_set) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: loc_window_set_message_config has not been called");
+    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: no resident solve has run since the upload");
+    if ((kinds_mask & ~locamd::kMsgAllKinds) != 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: kinds_mask has unknown bits");
+    if (!m || !m->kind || !m->dt) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: kind and dt arrays");
+    if (((kinds_mask & LOC_MSG_RANGE) && (!m->anchor || !m->antenna || !m->distance || !m->distance_err)) || ((kinds_mask & LOC_MSG_IMU) && !m->imu) ||
+        ((kinds_mask & LOC_MSG_LIDAR) && !m->lidar_z) || ((kinds_mask & LOC_MSG_TWIST) && !m->twist))
+        return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: a NULL message array under a bit of kinds_mask");
+    return LOC_OK;
+}
+// the build launch, in stream order after the last resident launch; timed: with the covariance events around it
+static int message_launch(loc_window* w, hipStream_t st, int32_t kinds_mask, const loc_window_messages* m, const loc_window_message_rows& o, bool timed) {
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    locamd::MessageArgs a{};
+    a.counts = (const int32_t*)w->dev.t[kCounts]; a.poses = (const double*)w->dev.t[kPoses];
+    a.anchors = w->d_anchors; a.antenna_xyz = w->d_antenna; a.n_anchors = w->n_anchors; a.n_antenna = w->n_antenna;
+    a.trajectory_length = w->msg_cfg.trajectory_length; a.maximum_velocity = w->msg_cfg.maximum_velocity; a.distance_outlier = w->msg_cfg.distance_outlier;
+    a.kinds_mask = kinds_mask;
+    a.kind = (const int32_t*)m->kind; a.dt = (const double*)m->dt;
+    a.anchor = (const int32_t*)m->anchor; a.antenna = (const int32_t*)m->antenna; a.distance = (const float*)m->distance; a.distance_err = (const float*)m->distance_err;
+    a.imu = (const double*)m->imu; a.lidar_z = (const double*)m->lidar_z; a.twist = (const double*)m->twist;
+    a.drop_oldest = (int32_t*)o.drop_oldest; a.new_pose = (double*)o.new_pose;
+    a.new_r_counts = (int32_t*)o.new_r_counts; a.new_r_idx = (int32_t*)o.new_r_idx; a.new_r_val = (double*)o.new_r_val;
+    a.new_p_counts = (int32_t*)o.new_p_counts; a.new_p_val = (double*)o.new_p_val;
+    a.new_s_counts = (int32_t*)o.new_s_counts; a.new_s_idx = (int32_t*)o.new_s_idx; a.new_s_val = (double*)o.new_s_val;
+    a.verdict = (int32_t*)o.verdict;
+    a.B = (int)w->res.n; a.nv_max = w->caps.nv_max;
+    if (timed) LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    const hipError_t e = locamd::launch_window_message_rows(a, st);
+    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_message_rows");
+    if (timed) { LOC_HIP(hipEventRecord(w->cov_ev1, st)); w->cov_pending = true; }
+    LOC_HIP(hipEventRecord(w->resident_done, st));   // whatever touches the resident arrays next waits for this launch as well
+    w->resident_inflight = true;
+    return LOC_OK;
+}
+
+// build only (the rows of localization.cpp:297-376, :438-535 and :560-605 at robot.cpp:90's estimate), into the caller's device arrays: every resident verdict (only counts and poses are read); no host pass, no copy, no
+// synchronisation, no allocation
+int loc_window_message_rows_dev(loc_window* w, void* hip_stream, int32_t kinds_mask, const loc_window_messages* msgs, const loc_window_message_rows* out) {
+    if (int rc = message_check_handle(w, kinds_mask, msgs)) return rc;
+    if (!out || !out->drop_oldest || !out->new_pose || !out->new_r_counts || !out->new_r_idx || !out->new_r_val || !out->new_p_counts || !out->new_p_val ||
+        !out->new_s_counts || !out->new_s_idx || !out->new_s_val)
+        return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows_dev: a NULL output array (only verdict may be NULL)");
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    return message_launch(w, st, kinds_mask, msgs, *out, true);
+}
+
+// build into the handle's block, then the slide the resident verdict calls for (robot.cpp:92-98: drop-oldest), on the same stream.  Both slides' host refusals are taken
+// BEFORE the build (slide_check_handle is what they start with), so a refusal launches nothing
+int loc_window_push_messages_resident_dev(loc_window* w, void* hip_stream, int32_t kinds_mask, const loc_window_messages* msgs,
+                                          void* verdict_dev, void* status_dev, void* admit_dev) {
+    if (int rc = message_check_handle(w, kinds_mask, msgs)) return rc;
+    const bool plain = resident_topology(w) != LOC_WINDOW_KERNEL_CHAIN3;
+    if (int rc = slide_check_handle(w, true, plain)) return rc;
+    LOC_HIP(hipSetDevice(w->device));
+    if (int rc = flush_anchors(w)) return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    const locamd::MessageRowsLayout L = locamd::message_rows_layout((size_t)w->B);
+    auto at = [&](int piece) { return (void*)(w->d_msg_rows + L.off[piece]); };
+    const loc_window_message_rows o{at(locamd::kGDrop), at(locamd::kGPose), at(locamd::kGRCounts), at(locamd::kGRIdx), at(locamd::kGRVal), at(locamd::kGPCounts),
+                                    at(locamd::kGPVal), at(locamd::kGSCounts), at(locamd::kGSIdx), at(locamd::kGSVal), verdict_dev ? verdict_dev : at(locamd::kGVerdict)};
+    if (int rc = message_launch(w, st, kinds_mask, msgs, o, false)) return rc;
+    if (plain)
+        return loc_window_slide_plain_resident_dev(w, st, o.drop_oldest, o.new_pose, LOC_MSG_NR_NEW, o.new_r_counts, o.new_r_idx, o.new_r_val,
+                                                   LOC_MSG_NP_NEW, o.new_p_counts, o.new_p_val, LOC_MSG_NS_NEW, o.new_s_counts, o.new_s_idx, o.new_s_val, status_dev, admit_dev);
+    return loc_window_slide_resident_dev(w, st, o.drop_oldest, o.new_pose, LOC_MSG_NR_NEW, o.new_r_counts, o.new_r_idx, o.new_r_val,
+                                         LOC_MSG_NP_NEW, o.new_p_counts, o.new_p_val, nullptr, nullptr, nullptr, status_dev, admit_dev);
 }
 
 // ---- the per-edge chi2 audit and the outlier-range removal (edge_audit_kernel.hip; DESIGN.md §2, "Edge audit and outlier removal") ----------------

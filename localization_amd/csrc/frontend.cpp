@@ -17,30 +17,17 @@
 #include <vector>
 
 #include "capi_host.h"
+#include "message_rows.h"
 
 namespace {
 
-struct Iso { double R[9]; double t[3]; };
+// Iso, iso_identity, iso_inverse, quat_to_R, invert6 and twist_transform: message_rows.h (shared with window_message_kernel.hip)
+using locamd::Iso; using locamd::iso_identity; using locamd::iso_inverse; using locamd::quat_to_R; using locamd::invert6; using locamd::twist_transform;
 
-inline Iso iso_identity() { Iso x{}; x.R[0] = x.R[4] = x.R[8] = 1.0; return x; }
 inline void mul3(const double* A, const double* B, double* C) {
     double o[9];
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) o[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
     std::memcpy(C, o, sizeof(o));
-}
-inline Iso iso_inverse(const Iso& a) {
-    Iso o;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) o.R[i * 3 + j] = a.R[j * 3 + i];
-    for (int i = 0; i < 3; ++i) o.t[i] = -(o.R[i * 3] * a.t[0] + o.R[i * 3 + 1] * a.t[1] + o.R[i * 3 + 2] * a.t[2]);
-    return o;
-}
-// Eigen::Quaterniond(w,x,y,z).toRotationMatrix(), no normalisation (localization.cpp:509 relies on it)
-inline void quat_to_R(double w, double x, double y, double z, double* R) {
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
 // Eigen::Quaterniond(R) then tf::poseEigenToMsg's w >= 0 flip; out = (x, y, z, w)
 inline void R_to_quat_xyzw(const double* R, double* q) {
@@ -60,26 +47,6 @@ inline void R_to_quat_xyzw(const double* R, double* q) {
     }
     if (w < 0) { w = -w; x = -x; y = -y; z = -z; }
     q[0] = x; q[1] = y; q[2] = z; q[3] = w;
-}
-// MatrixXd::inverse() of a 6x6 (partial pivoting); false if singular
-bool invert6(const double* A, double* out) {
-    double M[6][12];
-    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) { M[i][j] = A[i * 6 + j]; M[i][6 + j] = i == j ? 1.0 : 0.0; }
-    for (int c = 0; c < 6; ++c) {
-        int p = c;
-        for (int r = c + 1; r < 6; ++r) if (std::fabs(M[r][c]) > std::fabs(M[p][c])) p = r;
-        if (M[p][c] == 0.0 || !std::isfinite(M[p][c])) return false;
-        if (p != c) for (int j = 0; j < 12; ++j) std::swap(M[c][j], M[p][j]);
-        const double d = M[c][c];
-        for (int j = 0; j < 12; ++j) M[c][j] /= d;
-        for (int r = 0; r < 6; ++r) {
-            if (r == c || M[r][c] == 0.0) continue;
-            const double f = M[r][c];
-            for (int j = 0; j < 12; ++j) M[r][j] -= f * M[c][j];
-        }
-    }
-    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) out[i * 6 + j] = M[i][6 + j];
-    return true;
 }
 
 struct Header { double stamp = 0.0; std::string frame_id; };
@@ -627,18 +594,7 @@ int loc_node_add_twist(loc_node* n, double stamp, const double* tw, const double
     const int last_vertex = r.last_vertex();
     Header h; h.stamp = stamp; h.frame_id = frame_id ? frame_id : "";
     const int nv = n->new_vertex(r, ST_TWIST, h);
-    // tf::Quaternion::setRPY(wx dt, wy dt, wz dt), then tf::Matrix3x3::setRotation (normalising by 2 / |q|^2)
-    const double hr = tw[3] * dt * 0.5, hp = tw[4] * dt * 0.5, hy = tw[5] * dt * 0.5;
-    const double cy = std::cos(hy), sy = std::sin(hy), cp = std::cos(hp), sp = std::sin(hp), cr = std::cos(hr), sr = std::sin(hr);
-    const double qx = sr * cp * cy - cr * sp * sy, qy = cr * sp * cy + sr * cp * sy, qz = cr * cp * sy - sr * sp * cy,
-                 qw = cr * cp * cy + sr * sp * sy;
-    const double s = 2.0 / (qx * qx + qy * qy + qz * qz + qw * qw);
-    const double xs = qx * s, ys = qy * s, zs = qz * s;
-    const double wx = qw * xs, wy = qw * ys, wz = qw * zs, xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
-    Iso z;
-    const double Rz[9] = {1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx, xz - wy, yz + wx, 1.0 - (xx + yy)};
-    std::memcpy(z.R, Rz, sizeof(Rz));
-    z.t[0] = tw[0] * dt; z.t[1] = tw[1] * dt; z.t[2] = tw[2] * dt;
+    const Iso z = twist_transform(tw, dt);   // twist2transform, :560-583
     Se3Edge e{};
     e.vi = last_vertex; e.vj = nv; e.robust = true;
     e.zinv = iso_inverse(z);

@@ -209,6 +209,28 @@ struct SlidePlainArgs {
 };
 hipError_t launch_window_slide_plain(const SlidePlainArgs& s, hipStream_t stream);
 
+// the newest pose and the factors of every resident window from one raw message per window (window_message_kernel.hip; DESIGN.md §2, "Rows
+// from raw messages"): one wave per window evaluates message_rows.h's rule at the window's count and newest solved pose and writes the
+// arrays the two slides above read, at the capacities kMsgNrNew / kMsgNpNew / kMsgNsNew.  All device arrays; a message array may be nullptr
+// when its bit is not in kinds_mask; verdict may be nullptr.
+struct MessageArgs {
+    const int32_t* counts; const double* poses;          // [B][4]; [B][nv_max][12] the optimised estimates
+    const double* anchors; const double* antenna_xyz;    // [n_anchors][3]; [n_antenna][3]
+    int n_anchors, n_antenna;
+    int trajectory_length; double maximum_velocity, distance_outlier;
+    int kinds_mask;
+    const int32_t* kind; const double* dt;                                                                   // [B], [B]
+    const int32_t* anchor; const int32_t* antenna; const float* distance; const float* distance_err;        // [B] each (RANGE)
+    const double* imu; const double* lidar_z; const double* twist;                                           // [B][7], [B], [B][42]
+    int32_t* drop_oldest; double* new_pose;                                                                  // [B], [B][12]
+    int32_t* new_r_counts; int32_t* new_r_idx; double* new_r_val;                                            // [B], [B][2][2], [B][2][5]
+    int32_t* new_p_counts; double* new_p_val;                                                                // [B], [B][2][18]
+    int32_t* new_s_counts; int32_t* new_s_idx; double* new_s_val;                                            // [B], [B][1][4], [B][1][48]
+    int32_t* verdict;                                                                                        // [B]
+    int B, nv_max;
+};
+hipError_t launch_window_message_rows(const MessageArgs& a, hipStream_t stream);
+
 // the per-edge chi2 audit and the outlier-range removal (edge_audit_kernel.hip; DESIGN.md §2, "Edge audit and outlier removal"): one wave per
 // window at a.poses, every structure; a.r_off1 / a.p_info as the handle has them.  All device arrays.
 struct EdgeAudit {

@@ -74,6 +74,17 @@ inline BlockLayout slide_marginal_layout(size_t B) {
     const size_t pre[7] = {B * sizeof(int32_t), B * sizeof(int32_t), B * sizeof(int32_t), B * sizeof(int32_t), B * 48 * sizeof(double), B * 6 * sizeof(double), B * 6 * sizeof(double)};
     return pack_block(WindowCaps{}, B, pre, 7, kWindowTables);
 }
+// the handle's own outputs of window_message_kernel for B windows (loc_window_push_messages_resident_dev builds here, the slide reads here):
+// the eleven arrays of loc_window_message_rows in its order, each 16-byte aligned
+enum MessageRowsPiece { kGDrop, kGPose, kGRCounts, kGRIdx, kGRVal, kGPCounts, kGPVal, kGSCounts, kGSIdx, kGSVal, kGVerdict, kMessageRowsPieces };
+struct MessageRowsLayout { size_t off[kMessageRowsPieces], end; };
+inline MessageRowsLayout message_rows_layout(size_t B) {
+    const size_t i4 = sizeof(int32_t), f8 = sizeof(double);
+    const size_t bytes[kMessageRowsPieces] = {B * i4, B * 12 * f8, B * i4, B * 2 * 2 * i4, B * 2 * 5 * f8, B * i4, B * 2 * 18 * f8, B * i4, B * 1 * 4 * i4, B * 1 * 48 * f8, B * i4};
+    MessageRowsLayout L{};
+    for (int k = 0; k < kMessageRowsPieces; ++k) { L.off[k] = L.end; L.end += (bytes[k] + 15) & ~(size_t)15; }
+    return L;
+}
 inline DeviceTables tables_at(char* base, const BlockLayout& L) {
     DeviceTables d;
     for (int t = 0; t < kWindowTables; ++t) d.t[t] = base + L.tab[t];

@@ -11,6 +11,10 @@ class WindowCaps(C.Structure):
     _fields_ = [("nv_max", C.c_int32), ("nr_max", C.c_int32), ("np_max", C.c_int32), ("ns_max", C.c_int32), ("bw_max", C.c_int32)]
 
 
+class MessageConfig(C.Structure):
+    _fields_ = [("trajectory_length", C.c_int32), ("maximum_velocity", C.c_double), ("distance_outlier", C.c_double)]
+
+
 def _inv_iso(R, t):
     Ri = R.T
     return Ri, -Ri @ t
@@ -341,6 +345,45 @@ class WindowSolver(_lib.Handle):
         outs = [ptr(t) for t in (out if out is not None else (None,) * 2)]
         st = None if stream is None else C.c_void_p(stream.cuda_stream)
         check(self.L.loc_window_slide_plain_resident_dev(self.h, st, ptr(drop_oldest), ptr(new_pose), nrn, *r_args, npn, *p_args, nsn, *s_args, *outs))
+
+    # ---- rows from raw messages (loc_window_set_message_config / _message_rows_dev / _push_messages_resident_dev)
+    MSG_RANGE, MSG_IMU, MSG_LIDAR, MSG_TWIST = 1, 2, 4, 8
+    MSG_NONE, MSG_APPENDED, MSG_REJECTED, MSG_INVALID, MSG_SINGULAR = 0, 1, 2, 3, 4
+    MSG_FIELDS = ("kind", "dt", "anchor", "antenna", "distance", "distance_err", "imu", "lidar_z", "twist")
+    MSG_ROWS = ("drop_oldest", "new_pose", "new_r_counts", "new_r_idx", "new_r_val", "new_p_counts", "new_p_val", "new_s_counts", "new_s_idx",
+                "new_s_val", "verdict")
+
+    def set_message_config(self, trajectory_length, maximum_velocity=1.0, distance_outlier=1.0, antenna_xyz=None):
+        """The configuration the message calls read (the reference's robot/trajectory_length, maximum_velocity, distance_outlier — <= 0: no
+        gate — and /uwb/antennaOffset as [n_antenna][3]); also allocates the handle's block of output arrays."""
+        cfg = MessageConfig(int(trajectory_length), float(maximum_velocity), float(distance_outlier))
+        ant = None if antenna_xyz is None else np.ascontiguousarray(antenna_xyz, dtype=np.float64).reshape(-1, 3)
+        check(self.L.loc_window_set_message_config(self.h, C.byref(cfg), 0 if ant is None else ant.shape[0],
+                                                   None if ant is None else ant.ctypes.data_as(C.POINTER(C.c_double))))
+
+    @staticmethod
+    def _ptr_struct(fields, values):
+        """a struct of len(fields) void pointers from a dict of device pointers (int) or objects with data_ptr(); a missing name is NULL"""
+        ptr = lambda t: None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        return (C.c_void_p * len(fields))(*[ptr(values.get(f)) for f in fields])
+
+    def message_rows_dev(self, kinds_mask, msgs, out, stream=None):
+        """Build only (loc_window_message_rows_dev): msgs a dict of the message arrays by MSG_FIELDS' names (kind int32 [B], dt float64 [B],
+        anchor / antenna int32 [B], distance / distance_err float32 [B], imu float64 [B][7], lidar_z float64 [B], twist float64 [B][42]), out
+        a dict of the eleven output arrays by MSG_ROWS' names ("verdict" may be missing); device pointers or objects with data_ptr().
+        Asynchronous on stream (a torch stream; None: the handle's own).  Plumbing only: the library checks everything."""
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        m, o = self._ptr_struct(self.MSG_FIELDS, msgs), self._ptr_struct(self.MSG_ROWS, out)
+        check(self.L.loc_window_message_rows_dev(self.h, st, int(kinds_mask), C.byref(m), C.byref(o)))
+
+    def push_messages_resident_dev(self, kinds_mask, msgs, verdict=None, status=None, admit=None, stream=None):
+        """Build into the handle's own block, then the slide the resident verdict calls for, on the same stream
+        (loc_window_push_messages_resident_dev).  msgs as for message_rows_dev(); verdict / status / admit int32 [B] device arrays or None.
+        Read verdict first: a window with MSG_NONE or MSG_REJECTED shows admit code 2, and that is not an error."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        m = self._ptr_struct(self.MSG_FIELDS, msgs)
+        check(self.L.loc_window_push_messages_resident_dev(self.h, st, int(kinds_mask), C.byref(m), ptr(verdict), ptr(status), ptr(admit)))
 
     def download_batch(self):
         """The resident batch as it stands, as a WindowBatch (loc_window_download_tables): counts, the estimates the next resident solve
