@@ -734,6 +734,42 @@ int loc_window_edge_chi2_resident(loc_window* w, void* hip_stream, void* r_chi2_
                                   void* total_dev, void* active_dev);
 int loc_window_prune_resident(loc_window* w, void* hip_stream, double chi2_max, int32_t min_edges,
                               void* removed_dev /* int32 [n][nr_max] */, void* n_removed_dev /* int32 [n] */);
+/* Publish and path records of a resident batch ("Publish and path records of a resident batch"): what the reference does with
+ * a window after every solve, on the device, in stream order, into the caller's DEVICE arrays.
+ *   loc_window_publish_resident   Localization::publish()     localization.cpp:195-226 — the gate optimizer.chi2() < minimum_optimize_error
+ *                                 (:199), Robot::current_pose() (robot.cpp:146-157), path->poses[trajectory_length / 2] (:220), tf::poseEigenToMsg
+ *   loc_window_path_resident      Robot::vertices2path()      robot.cpp:61-72 (first = 0, count = T); the destructor's tail path[T/2 .. T-1]
+ *                                 (localization.cpp:708-717: first = T / 2, count = T - T / 2 — loc_node_flush_tail's rows for one window)
+ * A record is 7 doubles: x, y, z, qx, qy, qz, qw — the position and Eigen::Quaterniond(R) with tf::poseEigenToMsg's w >= 0 flip: the node's
+ * 8-double rows without their stamp (stamps stay the caller's, as for the message entries).  The records are bitwise what the node forms from
+ * the same pose.
+ * With T = trajectory_length, a window holds the newest nv of the ring's T poses: path index i is window slot i - (T - nv), slot nv - 1 is path
+ * index T - 1.  The T - nv oldest ring vertices (the reference's never-measured initial vertices) are not in the window: they are reported as
+ * absent, not invented.  Per window b, with nv = counts[b][0] and chi2 = result[b][0] of loc_window_result_device() (what the node gates on):
+ *   flags     int32  [n]     bit 0: published = 1 <= nv and chi2 < minimum_optimize_error (strict; a NaN chi2 is never published, +inf publishes
+ *                            every other window); bit 1: the optimized pose, path index T / 2, is in the window (whatever the gate says)
+ *   realtime  double [n][7]  the newest pose, slot nv - 1; written ONLY with bit 0
+ *   optimized double [n][7]  path index T / 2; written ONLY with bits 0 and 1
+ *   chi2      double [n]     result[b][0], always written (a caller who gates differently needs no second array)
+ *   n_published int32 [1]    the windows with bit 0: zeroed on the stream before the launch, then summed by the kernel
+ * Rows of unpublished windows are left exactly as the caller had them (the reference returns before it forms a pose, :201-205).
+ * realtime, optimized, chi2 and n_published may each be NULL; flags may not.
+ *   path      double [n][count][7]   path index first + k at [b][k]; written ONLY where present; no gate (the reference has none there)
+ *   present   int32  [n][count]      1 where the window holds that path index, else 0
+ * A window with nv > trajectory_length is the caller's inconsistency: its flags are 0, its path rows are all absent, and no record of it is
+ * written (chi2[b] still is).
+ * Both calls: asynchronous on hip_stream (NULL = the handle's own stream), ordered after the last resident launch and before the next one;
+ * nothing is read on the host, nothing synchronises, the host mirror of a slide stays as it is (loc_window_edge_chi2_resident's contract).
+ * Only counts, poses and result are read: every structural verdict and every handle state is served, nothing of the batch is written.
+ * Publish AFTER the solve: between a slide and the next solve, slot nv - 1 holds the appended, unsolved pose and result the previous
+ * solve's chi2; that call is not refused.
+ * LOC_ERR_INVALID, with nothing launched or written: a NULL handle, nothing uploaded, no resident solve since the upload, trajectory_length
+ * < 1 or > nv_max, a NaN minimum_optimize_error, first < 0, count < 1 or first + count > trajectory_length, a NULL flags_dev, path_dev or
+ * present_dev.  loc_window_last_covariance_ms reports the launch. */
+int loc_window_publish_resident(loc_window* w, void* hip_stream, double minimum_optimize_error, int32_t trajectory_length,
+                                void* flags_dev, void* realtime_dev, void* optimized_dev, void* chi2_dev, void* n_published_dev);
+int loc_window_path_resident(loc_window* w, void* hip_stream, int32_t trajectory_length, int32_t first, int32_t count,
+                             void* path_dev, void* present_dev);
 
 /* ================================================================================================
  * Node front-end — `class Localization` behind the ABI (one moving tag, its ring window, its anchors).

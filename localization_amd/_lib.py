@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "loc_window_marginal_prior_host", "loc_window_joint_covariance_host", "loc_window_joint_covariance_resident", "loc_window_joint_covariance_plan",
     "loc_window_slide_resident", "loc_window_slide_resident_dev", "loc_window_slide_plain_resident_dev", "loc_window_download_tables",
     "loc_window_edge_chi2_host", "loc_window_edge_chi2_resident", "loc_window_prune_resident",
+    "loc_window_publish_resident", "loc_window_path_resident",
     "loc_window_set_message_config", "loc_window_message_rows_dev", "loc_window_push_messages_resident_dev",
     "loc_node_default_config", "loc_node_create", "loc_node_destroy", "loc_node_add_range", "loc_node_add_imu",
     "loc_node_add_pose", "loc_node_add_twist", "loc_node_add_lidar", "loc_node_add_rl_range", "loc_node_solve", "loc_node_get_path",
@@ -136,7 +137,9 @@ def lib():
     L.loc_window_edge_chi2_host.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, dp, ip]
     L.loc_window_edge_chi2_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.loc_window_prune_resident.argtypes = [vp, vp, C.c_double, C.c_int32, vp, vp]
-    L.loc_window_set_message_config.argtypes = [vp, vp, C.c_int32, dp]
+    L.loc_window_publish_resident.argtypes = [vp, vp, C.c_double, C.c_int32, vp, vp, vp, vp, vp]
+    L.loc_window_path_resident.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.loc_window_set_message_config.argtypes =[vp, vp, C.c_int32, dp]
     L.loc_window_message_rows_dev.argtypes = [vp, vp, C.c_int32, vp, vp]
     L.loc_window_push_messages_resident_dev.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
     L.loc_fusion_default_params.argtypes = [C.POINTER(FusionParams)]; L.loc_fusion_default_params.restype = None

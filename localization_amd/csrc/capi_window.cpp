@@ -1309,6 +1309,55 @@ int loc_window_prune_resident(loc_window* w, void* hip_stream, double chi2_max, 
                                  locamd::EdgeAudit{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, chi2_max, min_edges, (int32_t*)removed_dev, (int32_t*)n_removed_dev});
 }
 
+// ---- the publish step and the path of the resident batch (window_publish_kernel.hip; DESIGN.md §2, "Publish and path records of a resident
+// batch"): Localization::publish() (localization.cpp:195-226), Robot::vertices2path() (robot.cpp:61-72), the destructor's tail (:708-717) ----
+// what the two entries share: the refusals, then `launch` in stream order after the last resident launch and before the next one
+// (resident_audit_launch's way); nothing is read on the host, nothing synchronises, the mirror stays as it is.  Only counts, poses and
+// result are read: every structural verdict and every handle state, no anchors, no table of full matrices
+extern "C++" {   // (a template cannot have C linkage)
+template <class Launch>
+static int resident_records_launch(loc_window* w, void* hip_stream, const char* who, int32_t trajectory_length, const char* launch_name, Launch launch) {
+    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, (std::string(who) + ": nothing uploaded").c_str());
+    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, (std::string(who) + ": no resident solve has run since the upload").c_str());
+    if (trajectory_length < 1 || trajectory_length > w->caps.nv_max)
+        return locamd_fail(LOC_ERR_INVALID, (std::string(who) + ": trajectory_length must be in [1, nv_max]").c_str());
+    LOC_HIP(hipSetDevice(w->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    const hipError_t e = launch(st);
+    if (e != hipSuccess) return locamd_fail_hip(e, launch_name);
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipEventRecord(w->resident_done, st));   // the next resident launch writes what this one reads: it waits for it
+    w->resident_inflight = true;
+    w->cov_pending = true;
+    return LOC_OK;
+}
+}   // extern "C++"
+
+int loc_window_publish_resident(loc_window* w, void* hip_stream, double minimum_optimize_error, int32_t trajectory_length,
+                                void* flags_dev, void* realtime_dev, void* optimized_dev, void* chi2_dev, void* n_published_dev) {
+    if (minimum_optimize_error != minimum_optimize_error) return locamd_fail(LOC_ERR_INVALID, "loc_window_publish_resident: minimum_optimize_error is NaN");
+    if (!flags_dev) return locamd_fail(LOC_ERR_INVALID, "loc_window_publish_resident: flags_dev is NULL");
+    return resident_records_launch(w, hip_stream, "loc_window_publish_resident", trajectory_length, "launch_window_publish", [&](hipStream_t st) {
+        const locamd::PublishArgs a{(const int32_t*)w->dev.t[kCounts], (const double*)w->dev.t[kPoses], w->d_result, minimum_optimize_error, trajectory_length,
+                                    (int32_t*)flags_dev, (double*)realtime_dev, (double*)optimized_dev, (double*)chi2_dev, (int32_t*)n_published_dev,
+                                    w->res.n, w->caps.nv_max};
+        return locamd::launch_window_publish(a, st);
+    });
+}
+
+int loc_window_path_resident(loc_window* w, void* hip_stream, int32_t trajectory_length, int32_t first, int32_t count, void* path_dev, void* present_dev) {
+    if (!path_dev || !present_dev) return locamd_fail(LOC_ERR_INVALID, "loc_window_path_resident: path_dev or present_dev is NULL");
+    if (first < 0 || count < 1 || (int64_t)first + count > trajectory_length)
+        return locamd_fail(LOC_ERR_INVALID, "loc_window_path_resident: first >= 0, count >= 1 and first + count <= trajectory_length are required");
+    return resident_records_launch(w, hip_stream, "loc_window_path_resident", trajectory_length, "launch_window_path", [&](hipStream_t st) {
+        const locamd::PathArgs a{(const int32_t*)w->dev.t[kCounts], (const double*)w->dev.t[kPoses], trajectory_length, first, count,
+                                 (double*)path_dev, (int32_t*)present_dev, w->res.n, w->caps.nv_max};
+        return locamd::launch_window_path(a, st);
+    });
+}
+
 int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
                                int32_t* s_idx, double* s_val, double* pinfo) {
     if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");

@@ -18,6 +18,7 @@
 
 #include "capi_host.h"
 #include "message_rows.h"
+#include "pose_records.h"
 
 namespace {
 
@@ -29,25 +30,8 @@ inline void mul3(const double* A, const double* B, double* C) {
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) o[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
     std::memcpy(C, o, sizeof(o));
 }
-// Eigen::Quaterniond(R) then tf::poseEigenToMsg's w >= 0 flip; out = (x, y, z, w)
-inline void R_to_quat_xyzw(const double* R, double* q) {
-    double w, x, y, z, t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        t = std::sqrt(t + 1.0); w = 0.5 * t; t = 0.5 / t;
-        x = (R[7] - R[5]) * t; y = (R[2] - R[6]) * t; z = (R[3] - R[1]) * t;
-    } else if (R[0] >= R[4] && R[0] >= R[8]) {
-        t = std::sqrt(R[0] - R[4] - R[8] + 1.0); x = 0.5 * t; t = 0.5 / t;
-        w = (R[7] - R[5]) * t; y = (R[3] + R[1]) * t; z = (R[6] + R[2]) * t;
-    } else if (R[4] > R[0] && R[4] >= R[8]) {
-        t = std::sqrt(R[4] - R[8] - R[0] + 1.0); y = 0.5 * t; t = 0.5 / t;
-        w = (R[2] - R[6]) * t; z = (R[7] + R[5]) * t; x = (R[1] + R[3]) * t;
-    } else {
-        t = std::sqrt(R[8] - R[0] - R[4] + 1.0); z = 0.5 * t; t = 0.5 / t;
-        w = (R[3] - R[1]) * t; x = (R[2] + R[6]) * t; y = (R[5] + R[7]) * t;
-    }
-    if (w < 0) { w = -w; x = -x; y = -y; z = -z; }
-    q[0] = x; q[1] = y; q[2] = z; q[3] = w;
-}
+// R_to_quat_xyzw (Eigen::Quaterniond(R) then tf::poseEigenToMsg's w >= 0 flip) and publish_gate: pose_records.h (shared with window_publish_kernel.hip)
+using locamd::R_to_quat_xyzw; using locamd::publish_gate;
 
 struct Header { double stamp = 0.0; std::string frame_id; };
 
@@ -289,7 +273,7 @@ void fill_output(loc_node* n, const double* res, loc_node_output* out) {
     if (!out) return;
     out->solved = 1;
     out->chi2 = res[0];
-    out->published = res[0] < n->cfg.minimum_optimize_error ? 1 : 0;  // localization.cpp:199-205
+    out->published = publish_gate(res[0], n->cfg.minimum_optimize_error) ? 1 : 0;  // localization.cpp:199-205
     out->outer_iterations = (int32_t)res[3];
     out->lm_trials = (int32_t)res[4];
     RobotRing* r = n->robot(n->self_id);

@@ -244,6 +244,26 @@ struct EdgeAudit {
 };
 hipError_t launch_window_edge_audit(const WindowArgs& a, const EdgeAudit& x, hipStream_t stream);
 
+// the publish step and the path of a resident batch (window_publish_kernel.hip; DESIGN.md §2, "Publish and path records of a resident
+// batch"): one lane per record, pose_records.h's rule at `poses`; reads counts, poses and result alone.  All device arrays; the host has
+// checked 1 <= trajectory_length <= nv_max and 0 <= first, 1 <= count, first + count <= trajectory_length.
+struct PublishArgs {
+    const int32_t* counts; const double* poses; const double* result;   // [B][4]; [B][nv_max][12]; [B][8]
+    double minimum_optimize_error; int trajectory_length;
+    int32_t* flags;                      // [B]     bit 0: published, bit 1: the optimized pose is in the window
+    double *realtime, *optimized;        // [B][7]  written only with bit 0 / bits 0 and 1; each may be nullptr
+    double* chi2; int32_t* n_published;  // [B] always written; one count, zeroed on the stream by the launch; each may be nullptr
+    long long B; int nv_max;
+};
+hipError_t launch_window_publish(const PublishArgs& a, hipStream_t stream);
+struct PathArgs {
+    const int32_t* counts; const double* poses;   // [B][4]; [B][nv_max][12]
+    int trajectory_length, first, count;
+    double* path; int32_t* present;               // [B][count][7] written only where present; [B][count]
+    long long B; int nv_max;
+};
+hipError_t launch_window_path(const PathArgs& a, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

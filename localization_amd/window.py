@@ -445,6 +445,27 @@ class WindowSolver(_lib.Handle):
         st = None if stream is None else C.c_void_p(stream.cuda_stream)
         check(self.L.loc_window_prune_resident(self.h, st, float(chi2_max), int(min_edges), *ptrs))
 
+    # ---- publish and path records of the resident batch (loc_window_publish_resident / loc_window_path_resident)
+    def publish_resident(self, minimum_optimize_error, trajectory_length, flags, realtime=None, optimized=None, chi2=None, n_published=None, stream=None):
+        """The reference's publish step for the uploaded batch (after solve_resident), on the device: flags int32 [B] (bit 0: chi2 <
+        minimum_optimize_error and the window has a pose; bit 1: path index trajectory_length // 2 is in the window), realtime / optimized
+        float64 [B][7] (x, y, z, qx, qy, qz, qw; written only with bit 0 / bits 0 and 1), chi2 float64 [B], n_published int32 [1].  Device
+        pointers or objects with data_ptr(); all but flags may be None.  Asynchronous on stream (a torch stream; None: the handle's own).
+        Plumbing only: the library checks everything."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_publish_resident(self.h, st, float(minimum_optimize_error), int(trajectory_length), ptr(flags), ptr(realtime),
+                                                 ptr(optimized), ptr(chi2), ptr(n_published)))
+
+    def path_resident(self, trajectory_length, path, present, first=0, count=None, stream=None):
+        """Path indices first .. first + count - 1 (count None: up to trajectory_length - 1) of every window of the uploaded batch: path float64
+        [B][count][7], written only where present int32 [B][count] is 1.  first = 0: vertices2path; first = trajectory_length // 2: the tail
+        the reference flushes at exit.  Device pointers or objects with data_ptr().  Asynchronous on stream; plumbing only."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        count = int(trajectory_length) - int(first) if count is None else int(count)
+        check(self.L.loc_window_path_resident(self.h, st, int(trajectory_length), int(first), count, ptr(path), ptr(present)))
+
     def covariance_plan(self, wb: WindowBatch):
         """covariance_plan(wb) for this handle's capacities"""
         assert wb.caps == self.caps
