@@ -6,9 +6,13 @@ namespace locamd {
 namespace {
 
 // ---- f64 reciprocal / sqrt from the hardware seeds + FMA refinement ------------------------------------
-// Accuracies measured on MI355X with tools/math_probe.hip (profiles/r01_math_probe.txt); operands here are ranges,
-// 1 + chi and pivots: normal, positive, so no div_scale / div_fixup range handling is needed.
-// v_rcp_f64 seed (4.6e-8) + two Newton steps: 1.1e-16 relative (as good as an IEEE divide).
+// Accuracies first measured on MI355X in round 1 (profiles/r01_math_probe.txt); the standing check of every bound stated here is
+// tests/test_gpu_device_primitives.py, which evaluates these very functions on the device (tools/primitives_probe.hip) against 50-digit
+// references at random arguments, at powers of two and their neighbours and on both sides of powers of four
+// (profiles/device_primitives/measured.txt).  Operands here are ranges, 1 + chi and pivots: normal, positive, so no div_scale /
+// div_fixup range handling is needed.
+// v_rcp_f64 seed (4.6e-8) + two Newton steps: 1.111e-16 relative — half an ulp, 2^-53, which a correctly rounded divide also reaches
+// next to a power of two; as good as an IEEE divide.
 __device__ __forceinline__ double fast_rcp(double d) {
     double r = __builtin_amdgcn_rcp(d);
     double e = __builtin_fma(-d, r, 1.0);
@@ -24,8 +28,8 @@ __device__ __forceinline__ double fast_rcp_1nr(double d) {
     r = __builtin_fma(r, e, r);
     return r;
 }
-// n = sqrt(x) to 1.1e-16 relative (identical error bound to the builtin sqrt: v_rsq_f64 seed, one Goldschmidt step, one
-// residual correction) and inv = 1/sqrt(x) to 4.2e-15 (only scales the unit vector of the Jacobian).
+// n = sqrt(x) to 1.111e-16 relative (half an ulp, 2^-53: identical error bound to the builtin sqrt: v_rsq_f64 seed, one Goldschmidt
+// step, one residual correction) and inv = 1/sqrt(x) to 4.2e-15 (only scales the unit vector of the Jacobian).
 __device__ __forceinline__ void sqrt_and_rsqrt(double x, double& n, double& inv) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
@@ -123,7 +127,7 @@ __device__ __forceinline__ double sqrt_ieee_near_c(double x, double s0, double h
     return __builtin_fma(d, h, s);
 }
 
-// n = sqrt(x) to 4.1e-15 relative (the Goldschmidt step without the residual correction; profiles/r01_math_probe.txt) and
+// n = sqrt(x) to 4.1e-15 relative (the Goldschmidt step without the residual correction) and
 // inv = 1/sqrt(x) to 4.2e-15:
 // the range norm of the analytic kernels, where 1e-14 m is five orders below anything the estimate resolves; two
 // instructions per range fewer than sqrt_and_rsqrt.
@@ -140,7 +144,7 @@ __device__ __forceinline__ void sqrt_and_rsqrt_fast(double x, double& n, double&
 // log(x) for x >= 1 (what the robust cost needs: 1 + chi, and products of such) — the kernel of fdlibm's e_log.c without the
 // argument classes that cannot occur: x = 2^k (1 + f) with sqrt(1/2) < 1 + f < sqrt(2), s = f / (2 + f),
 // log(1 + f) = f - hfsq + s (hfsq + R(s^2)), R a degree-7 minimax polynomial: < 1 ulp (checked against long-double log over
-// [1, 1e300], 7e6 samples: max 0.84 ulp).  About 40 instructions; the general-purpose library log is about 110, and it was a
+// [1, 1e300], 7e6 samples: max 0.84 ulp — profiles/r02_log_probe.txt; the standing check is tests/test_gpu_device_primitives.py).  About 40 instructions; the general-purpose library log is about 110, and it was a
 // fifth of every LM pass of the snapshot kernel.  inf and NaN pass through.
 // log(x 2^k0): the same kernel for a value kept as (x, k0) — a running product whose exponent was taken out on the way so that it
 // cannot overflow (x 2^k0 >= 1 as for fast_log_ge1)

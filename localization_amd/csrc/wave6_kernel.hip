@@ -49,37 +49,6 @@ extern __shared__ double w6lds[];
 #define W6_T(k) do {} while (0)
 #endif
 
-// Eigen::Quaternion(Matrix3) — q = (w, x, y, z); the square root and its reciprocal from one v_rsq_f64 seed (device_math.h:
-// sqrt_and_rsqrt, 1e-16 / 4e-15 relative: the prior's error and Jacobian carry them at that level)
-__device__ __forceinline__ void w6_mat_to_quat(const double* R, double* q) {
-    double qw, qx, qy, qz, n, inv;
-    const double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        sqrt_and_rsqrt(t + 1.0, n, inv);
-        qw = 0.5 * n; inv *= 0.5;
-        qx = (R[7] - R[5]) * inv; qy = (R[2] - R[6]) * inv; qz = (R[3] - R[1]) * inv;
-    } else if (R[0] >= R[4] && R[0] >= R[8]) {
-        sqrt_and_rsqrt(R[0] - R[4] - R[8] + 1.0, n, inv);
-        qx = 0.5 * n; inv *= 0.5;
-        qw = (R[7] - R[5]) * inv; qy = (R[3] + R[1]) * inv; qz = (R[6] + R[2]) * inv;
-    } else if (R[4] > R[0] && R[4] >= R[8]) {
-        sqrt_and_rsqrt(R[4] - R[8] - R[0] + 1.0, n, inv);
-        qy = 0.5 * n; inv *= 0.5;
-        qw = (R[2] - R[6]) * inv; qz = (R[7] + R[5]) * inv; qx = (R[1] + R[3]) * inv;
-    } else {
-        sqrt_and_rsqrt(R[8] - R[0] - R[4] + 1.0, n, inv);
-        qz = 0.5 * n; inv *= 0.5;
-        qw = (R[3] - R[1]) * inv; qx = (R[2] + R[6]) * inv; qy = (R[5] + R[7]) * inv;
-    }
-    q[0] = qw; q[1] = qx; q[2] = qy; q[3] = qz;
-}
-// g2o internal::normalize: unit norm, w >= 0
-__device__ __forceinline__ void w6_quat_normalize_sign(double* q) {
-    double n, s;
-    sqrt_and_rsqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3], n, s);
-    if (q[0] < 0) s = -s;
-    q[0] *= s; q[1] *= s; q[2] *= s; q[3] *= s;
-}
 #pragma clang fp contract(off)
 // the squared distance of range_error_plain (numeric_jacobian.h), same operation order: |(R off + t) - q1|^2
 __device__ __forceinline__ double w6_range_sq_plain(const double* R, const double* t, const double* off, const double* q1) {
@@ -279,8 +248,8 @@ __device__ __forceinline__ void w6_prior(const W6Lds& l, const double* P, int q,
     mat_mul(val, X, RE);
     mat_vec(val, X + 9, tE);
     tE[0] += val[9]; tE[1] += val[10]; tE[2] += val[11];
-    w6_mat_to_quat(RE, qq);
-    w6_quat_normalize_sign(qq);
+    mat_to_quat_rsq(RE, qq);
+    quat_normalize_sign_rsq(qq);
     const double err[6] = {tE[0], tE[1], tE[2], qq[1], qq[2], qq[3]};
     double chi = 0.0;
 #pragma unroll

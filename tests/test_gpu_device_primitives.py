@@ -1,0 +1,353 @@
+"""The device functions every 6-DoF kernel shares, each against a 50-digit reference of its definition (tests/_primitives_ref.py) at
+the inputs where it can go wrong: Eigen's matrix -> quaternion conversion in all four branches, at the branch boundaries and at the
+ties; g2o's normalize at w < 0, -0, +0; the EdgeSE3 terms with the inverse measurement, the relative rotation and the error rotation
+each in each branch; the prior blocks; the f64 reciprocal / square root / log sequences of device_math.h at their header's own bounds;
+the DPP reductions in every lane.  tools/primitives_probe.hip evaluates on the device, one process per call; the comparison is here.
+
+Tolerances.  Math primitives: the bounds device_math.h states (MATH_BOUNDS).  Reductions: identical bits in every lane, exact on
+integer inputs, otherwise 64 NW 2^-53 sum|v| from math.fsum.  Quaternion / SE3 / prior functions: the plain float64 evaluation of the
+same definitions on the same rows is measured against the reference, per output, as max |x - ref| over the row's largest |ref|; the
+device may be 4 times as far (FMA contraction and summation order differ), with a floor of 8 * 2^-53.  The *_rsq forms carry
+sqrt_and_rsqrt's stated 4.2e-15 on top of that floor.  Every figure is printed (profiles/device_primitives/measured.txt)."""
+import math
+import os
+import shutil
+import subprocess
+import tempfile
+
+import mpmath
+import numpy as np
+import pytest
+
+import _primitives_ref as P
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 2.0 ** -53
+FLOOR = 8 * EPS
+
+# device_math.h's stated relative bounds.  (It used to state half an ulp as "1.1e-16": 2^-53 is 1.1102e-16, and a correctly rounded
+# result reaches it next to a power of two — so do fast_rcp and sqrt_and_rsqrt, at 1.1102230246251573e-16 and ...564e-16 — so the header
+# now says 1.111e-16.)  pivot_rsqrt (window_device.h) stated no number: 1.67e-16 measured on these inputs, times 2, capped at 2^-52.
+MATH_BOUNDS = {"fast_rcp": (1.111e-16,), "fast_rcp_1nr": (2.2e-15,), "sqrt_and_rsqrt": (1.111e-16, 4.2e-15),
+               "sqrt_and_rsqrt_fast": (4.1e-15, 4.2e-15), "pivot_rsqrt": (2.0 ** -52,)}
+
+
+def _exe():
+    exe = os.path.join(ROOT, "tools", "primitives_probe.bin")
+    if not os.path.exists(exe):   # (__graft_entry__.build() compiles it; the binary travels with the snapshot)
+        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-I", os.path.join(ROOT, "localization_amd", "csrc"),
+                               os.path.join(ROOT, "tools", "primitives_probe.hip"), "-o", exe])
+    return exe
+
+
+def _probe(op, rows, width_out):
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        rows.tofile(fin)
+        out = subprocess.run([_exe(), op, fin, fout], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, (op, out.returncode, out.stderr)
+        got = np.fromfile(fout, dtype=np.float64)
+    assert got.size == rows.shape[0] * width_out, (op, got.size, rows.shape, width_out)
+    return got.reshape(rows.shape[0], width_out)
+
+
+def _rel_distance(got, ref):
+    """max |got - ref| over the row's largest |ref| (the difference at 50 digits)"""
+    with mpmath.workdps(P.DPS):
+        scale = max(abs(r) for r in ref)
+        return float(max(abs(mpmath.mpf(float(g)) - r) for g, r in zip(got, ref)) / scale) if scale > 0 else float(max(abs(float(g)) for g in got))
+
+
+def _hold(name, dev, f64, refs, extra=0.0, both_signs=()):
+    """device rows against references under the measured-float64 rule; both_signs: rows compared as +-q"""
+    def dist(got, ref, k):
+        d = _rel_distance(got, ref)
+        return min(d, _rel_distance([-x for x in got], ref)) if k in both_signs else d
+    d64 = max(dist(f, r, k) for k, (f, r) in enumerate(zip(f64, refs)))
+    ddev = [dist(g, r, k) for k, (g, r) in enumerate(zip(dev, refs))]
+    tol = max(4 * d64, FLOOR) + extra
+    worst = int(np.argmax(ddev))
+    print(f"measured: {name:34s} float64 {d64:.3e}  device {max(ddev):.3e}  tolerance {tol:.3e}  rows {len(refs)}")
+    assert np.all(np.isfinite(dev)), name
+    assert max(ddev) <= tol, (name, worst, ddev[worst], tol)
+
+
+# ---- f64 reciprocal / square root sequences -----------------------------------------------------------------------------------------------
+def _math_arguments():
+    rng = np.random.default_rng(1)
+    x = [2.0 ** rng.uniform(-20, 20, 4096)]
+    p2 = 2.0 ** np.arange(-20, 21)                      # exact powers of two (odd and even exponents: both parities of the seed)
+    x += [p2, np.nextafter(p2, 0), np.nextafter(p2, np.inf)]
+    p4 = 4.0 ** np.arange(-10, 11)                      # just below / above a power of four, a few ulps out
+    for k in (2, 3, 17):
+        x += [p4 * (1 - k * 2.0 ** -53), p4 * (1 + k * 2.0 ** -52)]
+    return np.concatenate(x)
+
+
+@pytest.mark.parametrize("op", sorted(MATH_BOUNDS))
+def test_reciprocal_and_root_sequences_hold_their_stated_bounds(gpu, op):
+    x = _math_arguments()
+    got = _probe(op, x[:, None], len(MATH_BOUNDS[op]))
+    with mpmath.workdps(P.DPS):
+        for col, bound in enumerate(MATH_BOUNDS[op]):
+            def ref(v):
+                v = mpmath.mpf(float(v))
+                if op.startswith("fast_rcp"):
+                    return 1 / v
+                return mpmath.sqrt(v) if (col == 0 and op != "pivot_rsqrt") else 1 / mpmath.sqrt(v)
+            rel = [float(abs(mpmath.mpf(float(g)) - ref(v)) / ref(v)) for g, v in zip(got[:, col], x)]
+            k = int(np.argmax(rel))
+            print(f"measured: {op:22s} output {col}  max relative error {max(rel):.4e} at x = {x[k]!r}  stated bound {bound:.3e}")
+            assert max(rel) <= bound, (op, col, max(rel), x[k])
+
+
+# ---- log ------------------------------------------------------------------------------------------------------------------------------------
+def _ulps(got, ref):
+    with mpmath.workdps(P.DPS):
+        return float(abs(mpmath.mpf(float(got)) - ref) / mpmath.mpf(float(np.spacing(abs(float(ref))))))
+
+
+def test_fast_log_is_within_one_ulp(gpu):
+    rng = np.random.default_rng(2)
+    half = math.sqrt(0.5)
+    edge = np.array([np.nextafter(half, 0), half, np.nextafter(half, 1)])
+    x = np.concatenate([rng.uniform(1, 2, 1024), 2.0 ** rng.uniform(0, 40, 1536), 2.0 ** rng.uniform(0, 1000, 1536),
+                        np.ldexp(edge, 1), np.ldexp(edge, 7), np.ldexp(edge, 1000), np.nextafter(1.0, 2) * np.ones(1),
+                        2.0 ** np.arange(1, 1024, 31), [np.finfo(np.float64).max]])
+    got = _probe("fast_log_ge1", x[:, None], 1)[:, 0]
+    with mpmath.workdps(P.DPS):
+        u = [_ulps(g, mpmath.log(mpmath.mpf(float(v)))) for g, v in zip(got, x)]
+    k = int(np.argmax(u))
+    print(f"measured: fast_log_ge1           max {max(u):.4f} ulp at x = {x[k]!r}  ({len(x)} arguments)")
+    assert max(u) < 1.0, (max(u), x[k])
+    special = _probe("fast_log_ge1", np.array([[1.0], [np.inf], [np.nan]]), 1)[:, 0]
+    assert special[0] == 0.0 and not np.signbit(special[0])
+    assert special[1] == np.inf and np.isnan(special[2])
+
+
+def test_fast_log_scaled_takes_the_exponent_along(gpu):
+    rng = np.random.default_rng(3)
+    e = rng.integers(-30, 31, 2048)
+    m = rng.uniform(1, 2, 2048)
+    k0 = np.array([rng.integers(max(0, -ee), 900) for ee in e]) * 1.0      # x 2^k0 >= 1
+    x = np.ldexp(m, e)
+    half = math.sqrt(0.5)
+    x = np.concatenate([x, [np.nextafter(half, 0), np.nextafter(half, 1), 0.5, 2.0 ** -30]])
+    k0 = np.concatenate([k0, [1.0, 1.0, 1.0, 30.0]])
+    got = _probe("fast_log_ge1_scaled", np.stack([x, k0], axis=1), 1)[:, 0]
+    assert got[-2] == 0.0 and got[-1] == 0.0                            # x 2^k0 = 1: exactly 0
+    with mpmath.workdps(P.DPS):
+        u = [_ulps(g, mpmath.log(mpmath.mpf(float(v))) + int(k) * mpmath.log(2)) for g, v, k in zip(got[:-2], x[:-2], k0[:-2])]
+    print(f"measured: fast_log_ge1_scaled    max {max(u):.4f} ulp  ({len(u)} arguments)")
+    assert max(u) < 1.0, max(u)
+
+
+# ---- reductions -----------------------------------------------------------------------------------------------------------------------------
+BOUNDARY_LANES = (0, 15, 16, 31, 32, 47, 48, 63)
+
+
+def _reduction_rows(n, rng):
+    """rows of n lanes: random, integer-valued (the sum is exact), one non-zero lane at every DPP row boundary and wave boundary"""
+    rows = [rng.normal(0, 1, n) * 10.0 ** rng.uniform(-6, 6, n) for _ in range(8)]
+    ints = [rng.integers(-1000, 1001, n).astype(np.float64) for _ in range(8)]
+    single = []
+    for w in range(n // 64):
+        for l in BOUNDARY_LANES:
+            r = np.zeros(n)
+            r[64 * w + l] = 3.0 + w + l
+            single.append(r)
+    return np.array(rows), np.array(ints + single)
+
+
+@pytest.mark.parametrize("nw", [0, 1, 2, 4, 8])   # 0: the wave forms on their own
+def test_reductions_give_every_lane_the_same_exact_bits(gpu, nw):
+    rng = np.random.default_rng(4 + nw)
+    n = 64 * max(nw, 1)
+    inexact, exact = _reduction_rows(n, rng)
+    rows = np.concatenate([inexact, exact])
+    sum_op, max_op = ("wave_sum", "wave_max") if nw == 0 else (f"block_sum_{nw}", f"block_max_{nw}")
+    s = _probe(sum_op, rows, n)
+    assert np.array_equal(s.view(np.uint64), np.repeat(s[:, :1], n, axis=1).view(np.uint64)), "lanes differ"
+    for k, r in enumerate(rows):
+        want = math.fsum(r)
+        if k >= len(inexact):
+            assert s[k, 0] == want, (sum_op, k, s[k, 0], want)
+        else:
+            assert abs(s[k, 0] - want) <= n * EPS * math.fsum(np.abs(r)), (sum_op, k, s[k, 0], want)
+    m = _probe(max_op, np.abs(rows), n)
+    assert np.array_equal(m, np.repeat(np.abs(rows).max(axis=1)[:, None], n, axis=1)), max_op
+    if nw == 0:
+        prev, nxt = _probe("lane_from_prev", rows, 64), _probe("lane_from_next", rows, 64)
+        assert np.array_equal(prev[:, 1:], rows[:, :-1]) and not prev[:, 0].any()      # lane 0 has no neighbour: 0
+        assert np.array_equal(nxt[:, :-1], rows[:, 1:]) and not nxt[:, 63].any()
+    else:
+        flags = np.concatenate([np.zeros((1, n)), exact[8:]])                          # nobody; one thread at each boundary
+        a = _probe(f"block_any_{nw}", flags, n)
+        assert not a[0].any() and np.all(a[1:] == 1.0)
+
+
+# ---- quaternion algebra ---------------------------------------------------------------------------------------------------------------------
+def _rotations():
+    """rows (9) and the set of rows at a branch boundary or a tie (compared as rotations, +-q)"""
+    rng = np.random.default_rng(5)
+    rows, loose = [], set()
+
+    def add(R, boundary=False):
+        if boundary:
+            loose.add(len(rows))
+        rows.append(np.asarray(R, dtype=np.float64).ravel())
+
+    for _ in range(3000):                                # random axes, angles up to 180 degrees: all four branches
+        a = rng.normal(size=3)
+        add(P.rotvec(a / np.linalg.norm(a) * rng.uniform(0, math.pi)))
+    for k in range(3):                                   # beyond 120 degrees about axes led by x, y, z
+        for ang in (121, 150, 175, 179.9999):
+            for _ in range(8):
+                add(P.rotvec(P.near_axis(rng, k) * math.radians(ang)))
+    third = 2 * math.pi / 3
+    for a in list(P.AXES.values()) + [P.near_axis(rng, k) for k in range(3)]:   # trace = +-tiny
+        for d in (-1e-9, 0.0, 1e-9):
+            add(P.rotvec(a * (third + d)), True)
+    add(np.eye(3))
+    add(np.diag([1.0, -1, -1]), True); add(np.diag([-1.0, 1, -1]), True); add(np.diag([-1.0, -1, 1]), True)
+    add(np.full((3, 3), 2.0 / 3) - np.eye(3), True)      # half turn about (1,1,1)/sqrt 3: three equal diagonal entries, trace -1
+    add([[0, 1, 0], [1, 0, 0], [0, 0, -1]], True)        # half turns about (1,1,0), (1,0,1), (0,1,1): two equal and largest
+    add([[0, 0, 1], [0, -1, 0], [1, 0, 0]], True)
+    add([[-1, 0, 0], [0, 0, 1], [0, 1, 0]], True)
+    s = math.sqrt(0.5)
+    for n in ((s, s, 0), (s, 0, s), (0, s, s)):          # 150 degrees about the same axes: equal and largest again, w != 0
+        R = P.rotvec(np.array(n) * math.radians(150))
+        i, j = [k for k in range(3) if n[k] != 0]
+        assert R[i, i] == R[j, j] and R[i, i] > R[3 - i - j, 3 - i - j] and np.trace(R) <= 0
+        add(R, True)
+    rows = np.array(rows)
+    assert set(P.branch_of(r) for r in rows) == {0, 1, 2, 3}
+    return rows, loose
+
+
+@pytest.mark.parametrize("op,extra", [("mat_to_quat", 0.0), ("mat_to_quat_rsq", 4.2e-15)])
+def test_matrix_to_quaternion_in_every_branch(gpu, op, extra):
+    rows, loose = _rotations()
+    dev = _probe(op, rows, 4)
+    refs = [P.with_mp(P.mat_to_quat, P._mat(P.MP, r)) for r in rows]
+    f64 = [P.mat_to_quat(P.F64, P._mat(P.F64, r)) for r in rows]
+    for b in range(4):   # per branch, so that a quiet branch cannot hide behind a noisy one
+        sel = [k for k, r in enumerate(rows) if P.branch_of(r) == b]
+        _hold(f"{op} branch {b}", dev[sel], [f64[k] for k in sel], [refs[k] for k in sel], extra,
+              both_signs={n for n, k in enumerate(sel) if k in loose})
+
+
+def _quaternions(rng, n):
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1)[:, None]
+    d = 1 / math.sqrt(3.0)
+    return np.concatenate([q, [[0, 1.0, 0, 0], [0, 0, 1.0, 0], [0, 0, 0, 1.0], [0, d, d, d], [1.0, 0, 0, 0]]])
+
+
+@pytest.mark.parametrize("op,extra", [("quat_normalize_sign", 0.0), ("quat_normalize_sign_rsq", 4.2e-15)])
+def test_quaternion_normalisation_and_its_sign(gpu, op, extra):
+    rng = np.random.default_rng(6)
+    q = _quaternions(rng, 2048) * 10.0 ** rng.uniform(-3, 3, (2053, 1))     # non-unit
+    q[:512, 0] = -np.abs(q[:512, 0])
+    q[512:1024, 0] = np.abs(q[512:1024, 0])
+    q[1024:1040, 0] = -0.0
+    q[1040:1056, 0] = 0.0
+    plain = op == "quat_normalize_sign"
+    dev = _probe(op, q, 5 if plain else 4)
+    refs, f64 = [], []
+    for r in q:
+        qr, sg = P.with_mp(P.quat_normalize_sign, [mpmath.mpf(float(x)) for x in r])
+        qf, _ = P.quat_normalize_sign(P.F64, [float(x) for x in r])
+        refs.append(qr); f64.append(qf)
+        assert sg == (-1 if r[0] < 0 else 1)
+    _hold(op, dev[:, :4], f64, refs, extra)
+    assert np.all(dev[:, 0] >= 0)
+    if plain:   # the sign applied: -1 for w < 0 only (-0.0 is not below 0)
+        assert np.array_equal(dev[:, 4], np.where(q[:, 0] < 0, -1.0, 1.0))
+
+
+def test_quaternion_product_matrix_and_right_jacobian(gpu):
+    rng = np.random.default_rng(7)
+    a, b = _quaternions(rng, 2048), _quaternions(rng, 2048)[::-1]
+    mp = lambda r: [mpmath.mpf(float(x)) for x in r]
+    fl = lambda r: [float(x) for x in r]
+    flat = lambda M: [x for row in M for x in row]
+    _hold("quat_mul", _probe("quat_mul", np.concatenate([a, b], axis=1), 4),
+          [P.quat_mul(P.F64, fl(x), fl(y)) for x, y in zip(a, b)], [P.with_mp(P.quat_mul, mp(x), mp(y)) for x, y in zip(a, b)])
+    _hold("quat_to_mat", _probe("quat_to_mat", a, 9),
+          [flat(P.quat_to_mat(P.F64, fl(x))) for x in a], [flat(P.with_mp(P.quat_to_mat, mp(x))) for x in a])
+    sgn = np.where(np.arange(len(a)) % 2, -1.0, 1.0)
+    _hold("quat_right_jac", _probe("quat_right_jac", np.concatenate([a, sgn[:, None]], axis=1), 9),
+          [flat(P.quat_right_jac(P.F64, fl(x), s)) for x, s in zip(a, sgn)],
+          [flat(P.with_mp(P.quat_right_jac, mp(x), int(s))) for x, s in zip(a, sgn)])
+
+
+# ---- EdgeSE3 terms --------------------------------------------------------------------------------------------------------------------------
+_SE3 = {}
+
+
+def _se3_cases():
+    """rows [N, 74] (every base row under the four (robust, j_is_later) pairs), their 50-digit outputs and the float64 evaluation's:
+    computed once, shared by the four instantiations"""
+    if not _SE3:
+        base, branches = P.se3_base_rows()
+        for conv in range(3):   # the inverse measurement, Xi^T Xj and the error rotation: each in each branch
+            assert set(branches[:, conv]) == {0, 1, 2, 3}, (conv, set(branches[:, conv]))
+        rows, refs, f64 = [], [], []
+        for b in base:
+            lin = P.se3_row_linearization(b)
+            for robust in (0.0, 1.0):
+                for later in (0.0, 1.0):
+                    r = np.concatenate([b, [robust, later]])
+                    rows.append(r)
+                    refs.append(P.se3_row_reference(r, lin))
+                    f64.append(P.se3_row_float64(r))
+        _SE3.update(rows=np.array(rows), refs=refs, f64=f64)
+    return _SE3["rows"], _SE3["refs"], _SE3["f64"]
+
+
+@pytest.mark.parametrize("vs", [1, 64])
+@pytest.mark.parametrize("full", [True, False])
+def test_edge_se3_terms_with_every_conversion_in_every_branch(gpu, full, vs):
+    rows, refs, f64 = _se3_cases()
+    op = f"se3_{'full' if full else 'chi'}_vs{vs}"
+    dev = _probe(op, rows, 92)
+    for name, sl in P.SE3_SLICES.items():
+        if not full and name not in ("chi", "rterm"):
+            assert not dev[:, sl].any()
+            continue
+        _hold(f"{op} {name}", dev[:, sl], [f[sl] for f in f64], [r[sl] for r in refs])
+
+
+# ---- prior blocks ---------------------------------------------------------------------------------------------------------------------------
+def test_prior_blocks_with_the_error_rotation_in_every_branch(gpu):
+    rng = np.random.default_rng(8)
+    base, branches = P.prior_base_rows()
+    assert set(branches) == {0, 1, 2, 3}
+    n = len(base)
+    Zi, X = base[:, :12], base[:, 12:]
+    Wd = 10.0 ** rng.uniform(0, 4, (n, 6))
+    Wf = np.array([P.spd6(rng).ravel() for _ in range(n)])
+    v18 = np.concatenate([Zi, Wd], axis=1)
+    _hold("cov_prior_block", _probe("cov_prior_block", np.concatenate([v18, X], axis=1), 21),
+          [P.prior_block_float64(v, x) for v, x in zip(v18, X)], [P.prior_block_reference(v, x) for v, x in zip(v18, X)])
+    full_rows = np.concatenate([Zi, Wf, X], axis=1)
+    _hold("cov_prior_block_full", _probe("cov_prior_block_full", full_rows, 21),
+          [P.prior_block_full_float64(z, w, x) for z, w, x in zip(Zi, Wf, X)],
+          [P.prior_block_full_reference(z, w, x) for z, w, x in zip(Zi, Wf, X)])
+    _hold("cov_prior_block3", _probe("cov_prior_block3", full_rows, 6),
+          [P.prior_block3(P.F64, z, w, x) for z, w, x in zip(Zi, Wf, X)], [P.with_mp(P.prior_block3, z, w, x) for z, w, x in zip(Zi, Wf, X)])
+    J = np.zeros((n, 6, 6))                                            # block-diagonal Jacobians, as the prior's are
+    J[:, :3, :3] = rng.normal(size=(n, 3, 3)); J[:, 3:, 3:] = rng.normal(size=(n, 3, 3))
+    J = J.reshape(n, 36)
+    _hold("prior_full_hessian", _probe("prior_full_hessian", np.concatenate([J, Wf], axis=1), 21),
+          [P.prior_full_hessian(P.F64, j, w) for j, w in zip(J, Wf)], [P.with_mp(P.prior_full_hessian, j, w) for j, w in zip(J, Wf)])
+    w6 = np.array([[W.reshape(6, 6)[r, c] for r in range(3) for c in range(r + 1)] for W in Wf])
+    w6[::4, [1, 3, 4]] = 0.0                                           # a diagonal W: the off-diagonal terms add exact zeros
+    e, acc = rng.normal(size=(n, 3)), rng.normal(size=(n, 3)) * 100
+    _hold("prior3_mul_add", _probe("prior3_mul_add", np.concatenate([w6, e, acc], axis=1), 3),
+          [P.prior3_mul_add(P.F64, w, x, a) for w, x, a in zip(w6, e, acc)], [P.with_mp(P.prior3_mul_add, w, x, a) for w, x, a in zip(w6, e, acc)])

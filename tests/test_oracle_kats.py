@@ -142,6 +142,44 @@ def test_se3_edge_and_prior_jacobians_match_finite_differences():
         assert np.allclose(Jp, _fd_jac(g2, (5,), 5), atol=1e-7)
 
 
+def test_se3_edge_and_prior_linearisation_in_every_quaternion_branch():
+    """Eigen::Quaternion(Matrix3) has four branches (trace > 0, and one per largest diagonal entry); the test above draws rotations that
+    keep every conversion in the first.  Here the oracle's error and analytic Jacobians are held to the 50-digit reference of
+    tests/_primitives_ref.py (the definitions; Jacobians by central differences at step 1e-20) with the inverse measurement, the
+    relative rotation Xi^T Xj and the error rotation each in each branch, and the prior's error rotation at 121, 150 and 175 degrees
+    about axes led by x, y, z and about the diagonal.  Bounds: float64 roundings of a few dozen operations on translations of a few
+    metres (errors, 1e-13) and on Jacobian entries up to ~20 (1e-12)."""
+    import _primitives_ref as P
+    base, branches = P.se3_base_rows()
+    for conv in range(3):
+        assert set(branches[:, conv]) == {0, 1, 2, 3}
+    for row in base:
+        Ri, ti, Rj, tj = row[0:9].reshape(3, 3), row[9:12], row[12:21].reshape(3, 3), row[21:24]
+        Rz, tz, W = row[24:33].reshape(3, 3), row[33:36], row[36:72].reshape(6, 6)
+        g = O.Graph()
+        g.add_vertex(0, ti, Ri); g.add_vertex(1, tj, Rj)
+        g.add_se3_edge(0, 1, -(Rz.T @ tz), Rz.T, W)          # the measurement: the inverse of the record's (Rz, tz)
+        err, J0, J1 = g.linearize(0, O.JAC_ANALYTIC)
+        e, R0, R1 = P.se3_row_linearization(row)
+        assert P.to_f64_err(err, e).max() < 1e-13
+        for J, Rf in ((J0, R0), (J1, R1)):
+            assert max(P.to_f64_err(J[r], Rf[r]).max() for r in range(6)) < 1e-12
+    rows, pb = P.prior_base_rows()
+    assert set(pb) == {0, 1, 2, 3}
+    for row in rows:
+        Rz, tz, R, t = row[0:9].reshape(3, 3), row[9:12], row[12:21].reshape(3, 3), row[21:24]
+        g = O.Graph()
+        g.add_vertex(5, t, R)
+        g.add_prior_edge(5, -(Rz.T @ tz), Rz.T, np.eye(6))
+        err, J, _ = g.linearize(0, O.JAC_ANALYTIC)
+        with P.mpmath.workdps(P.DPS):
+            Xm, Zm = P._pose(P.MP, row[12:]), P._pose(P.MP, row[:12])
+            e = P.prior_error(P.MP, Xm[0], Xm[1], Zm[0], Zm[1])
+            Jr = P.prior_jacobian_central(Xm[0], Xm[1], Zm[0], Zm[1])
+        assert P.to_f64_err(err, e).max() < 1e-13
+        assert max(P.to_f64_err(J[r], Jr[r]).max() for r in range(6)) < 1e-12
+
+
 def test_lm_lambda_schedule_hand_computed():
     # One tag at (2,0,0), one fixed anchor at the origin, range 1, Omega 1, no robust kernel  (SURVEY A.6):
     #   e = -1, J = (-1,0,0), H = diag(1,0,0,0,0,0), b = (-1,0,..), lambda0 = 1e-5 * max diag = 1e-5
