@@ -369,15 +369,64 @@ static locamd::WindowArgs window_args(const loc_window* w, const locamd::DeviceT
 static locamd::DeviceTables uploaded_tables(const loc_window* w) { locamd::DeviceTables d = w->dev; d.t[kPoses] = w->d_poses_in; return d; }
 // the device arrays hold no resident batch any more (the resident calls return LOC_ERR_INVALID until the next loc_window_upload completes)
 static void drop_resident(loc_window* w) { w->res = Resident{}; }
-// a table of full information matrices has a row for every window of the resident batch
-static int check_pinfo_covers_resident(const loc_window* w) {
-    if (w->opt.has_pinfo && w->res.n > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "the resident batch has more windows than loc_window_set_prior_information described");
-    return LOC_OK;
-}
 // The resident batch's structural verdict as it holds NOW.  One taken with the priors' diagonals skipped is worth nothing once the structured
 // table has gone, has got rotation entries or the option is off — the diagonals in p_val count again and may hold rotation information: such a
 // batch takes the general kernel until the next upload, never wave3_lm_kernel, and does not slide
 static int resident_topology(const loc_window* w) { return w->res.skip && !locamd::structured_pinfo(w->opt) ? (int)LOC_WINDOW_KERNEL_GENERAL : w->res.topology; }
+
+// What a resident entry refuses without looking at a window: the rule and its words are window_dispatch.cpp's resident_refusal.  The entry's own
+// argument checks travel as arg_failed (0, or the first of them that fails, counted from 1): the rule knows their place between the state
+// checks, and their words.  Nothing is launched or changed on a refusal
+static int resident_gate(const loc_window* w, locamd::ResidentEntry e, int arg_failed = 0) {
+    locamd::ResidentFacts f;
+    if (w) {
+        f.handle = true; f.resident = w->res.n > 0; f.mirror_valid = w->res.mirror_valid; f.solved = w->res.solved;
+        f.pinfo_short = w->opt.has_pinfo && w->res.n > w->n_pinfo; f.topology = resident_topology(w);
+        f.has_off1 = w->opt.has_off1; f.has_pinfo = w->opt.has_pinfo; f.pinfo_translation = w->opt.pinfo_translation; f.msg_set = w->msg_set;
+    }
+    const locamd::Refusal r = locamd::resident_refusal(e, f, arg_failed);
+    return r.code == LOC_OK ? (int)LOC_OK : locamd_fail(r.code, r.text);
+}
+
+// ---- the launch bracket of the resident entries: the whole stream-ordering contract of the resident batch -------------------------------------
+// First half: the device, the anchor table's device copy where the launch reads it (flush), the stream of the call.
+static int resident_stream(loc_window* w, void* hip_stream, bool flush, hipStream_t& st) {
+    LOC_HIP(hipSetDevice(w->device));
+    if (flush)
+        if (int rc = flush_anchors(w)) return rc;
+    st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    return LOC_OK;
+}
+// Second half: st waits for the last resident launch (it may have run on another stream), `staged` queues what the launch reads (outside the
+// timing), `launch` runs between the timing's two records, and resident_done is recorded for whatever touches the resident arrays next —
+// the next resident launch on any stream, wait_resident on the host.  Both callables return a LOC_* code.
+enum class Timing { None, Solve, Covariance };   // none; loc_window_timing_*'s pair; cov_ev0 / cov_ev1 for loc_window_last_covariance_ms
+extern "C++" {   // (a template cannot have C linkage)
+template <class Staged, class Launch>
+static int resident_bracket(loc_window* w, hipStream_t st, Timing timing, Staged&& staged, Launch&& launch) {
+    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));
+    if (int rc = staged(st)) return rc;
+    if (timing == Timing::Solve) LOC_HIP(w->timer.start(st));
+    if (timing == Timing::Covariance) LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    if (int rc = launch(st)) return rc;
+    if (timing == Timing::Solve) LOC_HIP(w->timer.stop(st));
+    if (timing == Timing::Covariance) LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipEventRecord(w->resident_done, st));
+    w->resident_inflight = true;
+    if (timing == Timing::Covariance) w->cov_pending = true;
+    return LOC_OK;
+}
+static int nothing_staged(hipStream_t) { return LOC_OK; }
+// both halves, for an entry with no work of its own in between
+template <class Launch>
+static int resident_launch(loc_window* w, void* hip_stream, Timing timing, bool flush, Launch&& launch) {
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, flush, st)) return rc;
+    return resident_bracket(w, st, timing, nothing_staged, launch);
+}
+}   // extern "C++"
+// a launcher's hipError_t as a LOC_* code
+static int launched(hipError_t e, const char* what) { return e == hipSuccess ? (int)LOC_OK : locamd_fail_hip(e, what); }
 
 static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const locamd::WindowArgs& a, hipStream_t st, int kind) {
     locamd::WinAux& A = S.aux;
@@ -668,27 +717,19 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
 }
 
 int loc_window_solve_resident(loc_window* w, void* hip_stream) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (int rc = check_pinfo_covers_resident(w)) return rc;
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    const locamd::WindowArgs a = window_args(w, w->dev, w->res.n, w->d_poses_in, w->d_anchors, w->d_result);
-    LOC_HIP(w->timer.start(st));
-    // (the batch-size threshold and the ordering override are looked at per solve: loc_window_set_chain_threshold /
-    //  loc_window_set_ordering after the upload take effect)
-    hipError_t e = launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->res.n, resident_topology(w)));
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
-    LOC_HIP(w->timer.stop(st));
-    LOC_HIP(hipEventRecord(w->resident_done, st));
-    w->resident_inflight = true;
-    w->res.solved = true;
-    return LOC_OK;
+    if (int rc = resident_gate(w, locamd::ResidentEntry::Solve)) return rc;
+    const int rc = resident_launch(w, hip_stream, Timing::Solve, true, [&](hipStream_t st) {
+        const locamd::WindowArgs a = window_args(w, w->dev, w->res.n, w->d_poses_in, w->d_anchors, w->d_result);
+        // (the batch-size threshold and the ordering override are looked at per solve: loc_window_set_chain_threshold /
+        //  loc_window_set_ordering after the upload take effect)
+        return launched(launch_any(w, w->slot[1], a, st, locamd::pick_kernel(w->opt, w->fits, w->res.n, resident_topology(w))), "launch_window");
+    });
+    if (rc == LOC_OK) w->res.solved = true;
+    return rc;
 }
 
 int loc_window_download(loc_window* w, double* poses, double* result) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_download: no resident solve has run since the upload");
+    if (int rc = resident_gate(w, locamd::ResidentEntry::Download)) return rc;
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = wait_resident(w)) return rc;
     const size_t N = (size_t)w->res.n;
@@ -853,10 +894,7 @@ int loc_window_covariance_host(loc_window* w, int64_t n, const int32_t* counts, 
 // loc_window_covariance_resident is the joint call without pairs, as on the host path
 int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_t npair_max, const int32_t* pair_counts_host, const int32_t* pairs_host,
                                          void* cov_dev, void* mask_dev, void* status_dev, void* cross_dev) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_covariance_resident: no resident solve has run since the upload");
-    if (!cov_dev || !mask_dev || !status_dev) return locamd_fail(LOC_ERR_INVALID, "covariance output arrays");
-    if (int rc = check_pinfo_covers_resident(w)) return rc;
+    if (int rc = resident_gate(w, locamd::ResidentEntry::Covariance, !cov_dev || !mask_dev || !status_dev ? 1 : 0)) return rc;
     Resident& R = w->res;
     const locamd::PairTables pt{npair_max, pair_counts_host, pairs_host};
     if (npair_max > 0)   // (the pair check reads every window's nv; a call without pairs reads no count and does not wait)
@@ -900,8 +938,8 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         if (int rc = wait_resident(w)) return rc;   // (an earlier covariance launch may still use the workspace that is about to be replaced)
         LOC_HIP(grow_cov_workspace(w, S, R.n, S.cov_list_cap));
     }
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, true, st)) return rc;
     locamd::CovPairs pp{nullptr, nullptr, nullptr, 0};
     const locamd::BlockLayout L = locamd::resident_pairs_layout((size_t)R.n, (size_t)npair_max);
     if (joint) {
@@ -916,18 +954,13 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         std::memcpy(h + L.pre[1], pairs_host, L.len[1]);
         pp = locamd::CovPairs{(const int32_t*)(w->pairs.d + L.pre[0]), (const int32_t*)(w->pairs.d + L.pre[1]), (double*)cross_dev, npair_max};
     }
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    if (joint) LOC_HIP(w->pairs.send(L.end, st));   // (after that wait: an earlier joint launch on another stream has finished reading the table)
-    const locamd::WindowArgs a = window_args(w, w->dev, R.n, nullptr, w->d_anchors, nullptr);
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch_covariance(w, S, R.cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_covariance");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    // whatever overwrites the resident arrays next waits for this launch as well
-    LOC_HIP(hipEventRecord(w->resident_done, st));
-    w->resident_inflight = true;
-    w->cov_pending = true;
-    return LOC_OK;
+    return resident_bracket(w, st, Timing::Covariance, [&](hipStream_t st) {
+        if (joint) LOC_HIP(w->pairs.send(L.end, st));   // (after the bracket's wait: an earlier joint launch on another stream has finished reading the table)
+        return (int)LOC_OK;
+    }, [&](hipStream_t st) {
+        const locamd::WindowArgs a = window_args(w, w->dev, R.n, nullptr, w->d_anchors, nullptr);
+        return launched(launch_covariance(w, S, R.cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st), "launch_window_covariance");
+    });
 }
 
 int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev) {
@@ -956,32 +989,33 @@ int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, con
 }
 
 // ---- the resident slide (window_slide_kernel.hip; DESIGN.md §2, "The resident slide") ------------------------------------------------------------
-// what both entries check without looking at a window; nothing is launched or changed on a refusal
-// plain: loc_window_slide_plain_resident_dev — the same checks, but the verdict is one of the ordered 6-DoF chain verdicts and the handle has no
-// table of full information matrices at all
-static int slide_check_handle(const loc_window* w, bool arrays_ok, bool plain = false) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->res.mirror_valid) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded");
-    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: no resident solve has run since the upload");
-    if (!arrays_ok) return locamd_fail(LOC_ERR_INVALID, "loc_window_slide_resident: new pose and new row arrays");
-    if (int rc = check_pinfo_covers_resident(w)) return rc;
-    if (plain) {
-        const int t = resident_topology(w);
-        if (t == LOC_WINDOW_KERNEL_CHAIN3)
-            return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_plain_resident_dev: the resident batch is an ordered translation-only chain batch: "
-                                                    "loc_window_slide_resident / loc_window_slide_resident_dev slide it");
-        if (t != LOC_WINDOW_KERNEL_CHAIN && t != LOC_WINDOW_KERNEL_WAVE6 && t != LOC_WINDOW_KERNEL_WAVE6S)
-            return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_plain_resident_dev: the resident batch is not an ordered 6-DoF chain batch");
-        if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
-        if (w->opt.has_pinfo) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_plain_resident_dev: the handle has a table of full information matrices");
-        return LOC_OK;
-    }
-    if (resident_topology(w) != LOC_WINDOW_KERNEL_CHAIN3)
-        return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the resident batch is not an ordered translation-only chain batch");
-    if (w->opt.has_off1) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: no endpoint-1 lever arms");
-    if (w->opt.has_pinfo && !w->opt.pinfo_translation) return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: the table of full information matrices has rotation entries");
-    return LOC_OK;
+// A slide's new pose and new rows as one block of pointers (the public loc_window_message_rows: host arrays for loc_window_slide_resident,
+// device arrays for the other two; verdict is not used) and the capacities they were written for
+struct NewRows { loc_window_message_rows p; int32_t nr, np, ns; };
+static NewRows new_rows(const void* drop, const void* pose, int32_t nr, const void* rc, const void* ri, const void* rv, int32_t np, const void* pc, const void* pv,
+                        int32_t ns = 0, const void* sc = nullptr, const void* si = nullptr, const void* sv = nullptr) {
+    auto m = [](const void* q) { return const_cast<void*>(q); };   // (the block is the build's OUTPUT type; a slide only reads through it)
+    return {{m(drop), m(pose), m(rc), m(ri), m(rv), m(pc), m(pv), m(sc), m(si), m(sv), nullptr}, nr, np, ns};
 }
+// the slides' argument check: the new pose and the new row arrays are all there for the capacities given
+static int new_rows_missing(const NewRows& r) {
+    const loc_window_message_rows& p = r.p;
+    return p.new_pose && r.nr >= 0 && r.np >= 0 && r.ns >= 0 && (r.nr == 0 || (p.new_r_counts && p.new_r_idx && p.new_r_val)) && (r.np == 0 || (p.new_p_counts && p.new_p_val)) &&
+           (r.ns == 0 || (p.new_s_counts && p.new_s_idx && p.new_s_val)) ? 0 : 1;
+}
+// the resident batch's tables and the call's new rows in a slide's argument block (SlideArgs, SlidePlainArgs)
+extern "C++" {   // (a template cannot have C linkage)
+template <class Args>
+static void slide_tables_and_rows(const loc_window* w, const NewRows& r, Args& sa) {
+    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
+    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
+    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal];
+    sa.drop = (const int32_t*)r.p.drop_oldest; sa.new_pose = (const double*)r.p.new_pose;
+    sa.new_r_counts = (const int32_t*)r.p.new_r_counts; sa.new_r_idx = (const int32_t*)r.p.new_r_idx; sa.new_r_val = (const double*)r.p.new_r_val;
+    sa.new_p_counts = (const int32_t*)r.p.new_p_counts; sa.new_p_val = (const double*)r.p.new_p_val;
+    sa.nr_new_max = r.nr; sa.np_new_max = r.np; sa.B = (int)w->res.n; sa.caps = w->caps;
+}
+}   // extern "C++"
 // the one-time allocations of a slide: the marginal pass's block for B windows (fresh: its drop table is not zeroed yet), and the table a first
 // slide creates (a launch under an earlier table may still read it: that one waits)
 static int slide_allocate(loc_window* w, bool densify, bool& fresh) {
@@ -995,30 +1029,31 @@ static int slide_allocate(loc_window* w, bool densify, bool& fresh) {
 }
 // launch 1: the marginal of slot 0 at the solved poses, marginal_prior_kernel itself (a handle without a table: p_val's diagonals, as
 // loc_window_marginal_prior_host reads them); launch 2: the re-pack — sa holds the call's inputs and outputs; admitting: the twin whose waves
-// admit their own windows.  Then the handle's state but the mirror: what loc_window_upload of the slid tables, with the table set, would leave
-static int slide_launches(loc_window* w, hipStream_t st, locamd::SlideArgs& sa, bool densify, bool fresh, bool admitting, int32_t* admit) {
+// admit their own windows.  Then the handle's state but the mirror: what loc_window_upload of the slid tables, with the table set, would leave.
+// rows: where the kernel reads them (the caller's device arrays, or the staging block's device half: send_bytes of it travel first); out: the
+// caller's {slot, prior, rank, status}
+static int slide_launches(loc_window* w, hipStream_t st, const NewRows& rows, size_t send_bytes, void* const out[4], bool densify, bool fresh, bool admitting, int32_t* admit) {
     const locamd::WindowCaps& c = w->caps;
     const int64_t n = w->res.n;
     const locamd::BlockLayout M = locamd::slide_marginal_layout((size_t)w->B);
     auto mp = [&](int piece) { return w->d_slide_mp + M.pre[piece]; };
-    if (fresh) LOC_HIP(hipMemsetAsync(mp(locamd::kMDrop), 0, M.pre[locamd::kMSlot], st));                         // the marginal pass's drop table: slot 0 of every window
-    if (densify) LOC_HIP(hipMemsetAsync(w->d_pinfo, 0, (size_t)w->B * c.np_max * 36 * sizeof(double), st));     // (rows beyond the counts: zeros, not what the allocation held)
-    const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, nullptr);
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    hipError_t e = locamd::launch_window_marginal_prior(a, (const int32_t*)mp(locamd::kMDrop), (int32_t*)mp(locamd::kMSlot), (double*)mp(locamd::kMPrior), (double*)mp(locamd::kMGrad),
-                                                        (double*)mp(locamd::kMShift), (int32_t*)mp(locamd::kMRank), (int32_t*)mp(locamd::kMStatus), st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_marginal_prior");
-    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
-    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
-    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal]; sa.p_info = c.np_max > 0 ? w->d_pinfo : nullptr;
+    locamd::SlideArgs sa{};
+    slide_tables_and_rows(w, rows, sa);
+    sa.p_info = c.np_max > 0 ? w->d_pinfo : nullptr;
     sa.m_slot = (const int32_t*)mp(locamd::kMSlot); sa.m_prior = (const double*)mp(locamd::kMPrior); sa.m_rank = (const int32_t*)mp(locamd::kMRank); sa.m_status = (const int32_t*)mp(locamd::kMStatus);
-    sa.B = (int)n; sa.caps = c;
-    e = admitting ? locamd::launch_window_slide_dev(sa, w->n_anchors, admit, densify, st) : locamd::launch_window_slide(sa, densify, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    LOC_HIP(hipEventRecord(w->resident_done, st));
-    w->resident_inflight = true;
-    w->cov_pending = true;
+    sa.slot = (int32_t*)out[0]; sa.prior = (double*)out[1]; sa.rank = (int32_t*)out[2]; sa.status = (int32_t*)out[3];
+    const int rc = resident_bracket(w, st, Timing::Covariance, [&](hipStream_t st) {
+        if (send_bytes) LOC_HIP(w->slide.send(send_bytes, st));
+        if (fresh) LOC_HIP(hipMemsetAsync(mp(locamd::kMDrop), 0, M.pre[locamd::kMSlot], st));                         // the marginal pass's drop table: slot 0 of every window
+        if (densify) LOC_HIP(hipMemsetAsync(w->d_pinfo, 0, (size_t)w->B * c.np_max * 36 * sizeof(double), st));     // (rows beyond the counts: zeros, not what the allocation held)
+        return (int)LOC_OK;
+    }, [&](hipStream_t st) {
+        const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, nullptr);
+        if (int rc = launched(locamd::launch_window_marginal_prior(a, (const int32_t*)mp(locamd::kMDrop), (int32_t*)mp(locamd::kMSlot), (double*)mp(locamd::kMPrior), (double*)mp(locamd::kMGrad),
+                                                                   (double*)mp(locamd::kMShift), (int32_t*)mp(locamd::kMRank), (int32_t*)mp(locamd::kMStatus), st), "launch_window_marginal_prior")) return rc;
+        return launched(admitting ? locamd::launch_window_slide_dev(sa, w->n_anchors, admit, densify, st) : locamd::launch_window_slide(sa, densify, st), "launch_window_slide");
+    });
+    if (rc) return rc;
     if (densify) { w->opt.has_pinfo = true; w->opt.pinfo_translation = true; w->n_pinfo = n; }
     w->res.skip = locamd::structured_pinfo(w->opt);
     w->res.cov = CovKind::Chain3;   // (loc_window_upload's verdict for this topology; a call the switches do not admit classifies it again)
@@ -1029,9 +1064,8 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
                               int32_t nr_new_max, const int32_t* new_r_counts, const int32_t* new_r_idx, const double* new_r_val,
                               int32_t np_new_max, const int32_t* new_p_counts, const double* new_p_val,
                               void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev) {
-    if (int rc = slide_check_handle(w, new_pose && nr_new_max >= 0 && np_new_max >= 0 && (nr_new_max == 0 || (new_r_counts && new_r_idx && new_r_val)) &&
-                                           (np_new_max == 0 || (new_p_counts && new_p_val))))
-        return rc;
+    const NewRows given = new_rows(drop_oldest, new_pose, nr_new_max, new_r_counts, new_r_idx, new_r_val, np_new_max, new_p_counts, new_p_val);
+    if (int rc = resident_gate(w, locamd::ResidentEntry::SlideHost, new_rows_missing(given))) return rc;
     if (int rc = refresh_mirror(w)) return rc;   // (the two entries may alternate on one handle)
     const locamd::WindowCaps& c = w->caps;
     Resident& R = w->res;
@@ -1046,9 +1080,8 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
         return locamd_fail(LOC_ERR_INVALID, kWhat[bad]);
     if (!locamd::slide_rows_translation_only(n, rows, new_pose, new_r_val, new_p_val))
         return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_slide_resident: a new row is not translation-only (identity rotations, zero lever arms, no rotation information)");
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, true, st)) return rc;
     const locamd::BlockLayout L = locamd::slide_inputs_layout(N, (size_t)nr_new_max, (size_t)np_new_max);
     if (L.end > w->slide.cap)
         if (int rc = wait_resident(w)) return rc;   // (an earlier slide may still read the block that is about to be replaced)
@@ -1066,87 +1099,66 @@ int loc_window_slide_resident(loc_window* w, void* hip_stream, const int32_t* dr
         for (int k = 1; k < 7; ++k)
             if (L.len[k] && src[k]) std::memcpy(h + L.pre[k], src[k], L.len[k]);
     }
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    LOC_HIP(w->slide.send(L.end, st));
-    locamd::SlideArgs sa{};
     const char* d = w->slide.d;
-    sa.drop = (const int32_t*)(d + L.pre[0]); sa.new_r_counts = (const int32_t*)(d + L.pre[1]); sa.new_p_counts = (const int32_t*)(d + L.pre[2]);
-    sa.new_r_idx = (const int32_t*)(d + L.pre[3]); sa.new_pose = (const double*)(d + L.pre[4]); sa.new_r_val = (const double*)(d + L.pre[5]); sa.new_p_val = (const double*)(d + L.pre[6]);
-    sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
-    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
-    if (int rc = slide_launches(w, st, sa, densify, fresh, false, nullptr)) return rc;
+    const NewRows staged = new_rows(d + L.pre[0], d + L.pre[4], nr_new_max, d + L.pre[1], d + L.pre[3], d + L.pre[5], np_new_max, d + L.pre[2], d + L.pre[6]);
+    void* const out[4] = {slot_dev, prior_dev, rank_dev, status_dev};
+    if (int rc = slide_launches(w, st, staged, L.end, out, densify, fresh, false, nullptr)) return rc;
     R.min_anchors = locamd::slide_indices(c, w->n_anchors, n, R.counts.data(), R.mir_ridx.data(), R.mir_pidx.data(), rows, true).max_anchor;
     return LOC_OK;
 }
 
 // the twin that takes the call's per-window inputs from DEVICE arrays: no pass over per-window data on the host, no copy, no synchronisation
-// (but the one-time allocations slide_allocate makes); each wave admits its own window (slide_admit.h) and the host's mirror goes stale
+// (but the one-time allocations slide_allocate makes); each wave admits its own window (slide_admit.h) and the host's mirror goes stale.  First
+// its internal form, past the gate, on a stream resident_stream chose: loc_window_push_messages_resident_dev enters here
+static int slide_carry_dev(loc_window* w, hipStream_t st, const NewRows& rows, void* const out[4], void* admit_dev) {
+    const bool densify = !w->opt.has_pinfo && w->caps.np_max > 0;
+    bool fresh;
+    if (int rc = slide_allocate(w, densify, fresh)) return rc;
+    if (int rc = slide_launches(w, st, rows, 0, out, densify, fresh, true, (int32_t*)admit_dev)) return rc;
+    w->res.mirror_stale = true;   // (refresh_mirror: the next reader of the mirror fetches it)
+    return LOC_OK;
+}
 int loc_window_slide_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
                                   int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
                                   int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
                                   void* slot_dev, void* prior_dev, void* rank_dev, void* status_dev, void* admit_dev) {
-    if (int rc = slide_check_handle(w, new_pose_dev && nr_new_max >= 0 && np_new_max >= 0 && (nr_new_max == 0 || (new_r_counts_dev && new_r_idx_dev && new_r_val_dev)) &&
-                                           (np_new_max == 0 || (new_p_counts_dev && new_p_val_dev))))
-        return rc;
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    const bool densify = !w->opt.has_pinfo && w->caps.np_max > 0;
-    bool fresh;
-    if (int rc = slide_allocate(w, densify, fresh)) return rc;
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    locamd::SlideArgs sa{};
-    sa.drop = (const int32_t*)drop_oldest_dev; sa.new_pose = (const double*)new_pose_dev;
-    sa.new_r_counts = (const int32_t*)new_r_counts_dev; sa.new_r_idx = (const int32_t*)new_r_idx_dev; sa.new_r_val = (const double*)new_r_val_dev;
-    sa.new_p_counts = (const int32_t*)new_p_counts_dev; sa.new_p_val = (const double*)new_p_val_dev;
-    sa.slot = (int32_t*)slot_dev; sa.prior = (double*)prior_dev; sa.rank = (int32_t*)rank_dev; sa.status = (int32_t*)status_dev;
-    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max;
-    if (int rc = slide_launches(w, st, sa, densify, fresh, true, (int32_t*)admit_dev)) return rc;
-    w->res.mirror_stale = true;   // (refresh_mirror: the next reader of the mirror fetches it)
-    return LOC_OK;
+    const NewRows rows = new_rows(drop_oldest_dev, new_pose_dev, nr_new_max, new_r_counts_dev, new_r_idx_dev, new_r_val_dev, np_new_max, new_p_counts_dev, new_p_val_dev);
+    if (int rc = resident_gate(w, locamd::ResidentEntry::SlideDev, new_rows_missing(rows))) return rc;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, true, st)) return rc;
+    void* const out[4] = {slot_dev, prior_dev, rank_dev, status_dev};
+    return slide_carry_dev(w, st, rows, out, admit_dev);
 }
 
 // the plain drop for the ordered 6-DoF chain verdicts (window_slide_plain_kernel.hip; DESIGN.md §2, "The plain drop for 6-DoF chain windows"): what
 // Robot::new_vertex does with its oldest pose (robot.cpp:92-98).  One launch, nothing carried, no table; device arrays, no host pass, no copy,
-// no synchronisation and no allocation; each wave admits its own window (slide_plain_admit.h) and the host's mirror goes stale
+// no synchronisation and no allocation; each wave admits its own window (slide_plain_admit.h) and the host's mirror goes stale.  First the
+// internal form, as slide_carry_dev
+static int slide_plain_dev(loc_window* w, hipStream_t st, const NewRows& rows, void* status_dev, void* admit_dev) {
+    const int topology = resident_topology(w);
+    locamd::SlidePlainArgs sa{};
+    slide_tables_and_rows(w, rows, sa);
+    sa.s_idx = (int32_t*)w->dev.t[locamd::kSIdx]; sa.s_val = (double*)w->dev.t[locamd::kSVal];
+    sa.new_s_counts = (const int32_t*)rows.p.new_s_counts; sa.new_s_idx = (const int32_t*)rows.p.new_s_idx; sa.new_s_val = (const double*)rows.p.new_s_val;
+    sa.status = (int32_t*)status_dev; sa.admit = (int32_t*)admit_dev; sa.ns_new_max = rows.ns; sa.n_anchors = w->n_anchors;
+    sa.pair_rule = topology == LOC_WINDOW_KERNEL_WAVE6 ? locamd::kSlidePairsWave6 : topology == LOC_WINDOW_KERNEL_WAVE6S ? locamd::kSlidePairsWave6S : locamd::kSlidePairsNone;
+    if (int rc = resident_bracket(w, st, Timing::Covariance, nothing_staged, [&](hipStream_t st) { return launched(locamd::launch_window_slide_plain(sa, st), "launch_window_slide_plain"); }))
+        return rc;
+    w->res.cov = CovKind::Chain6;     // (loc_window_upload's verdict for these topologies; a batch the envelope pass held is classified again)
+    w->res.mirror_stale = true;       // (refresh_mirror: the next reader of the mirror fetches it)
+    return LOC_OK;
+}
 int loc_window_slide_plain_resident_dev(loc_window* w, void* hip_stream, const void* drop_oldest_dev, const void* new_pose_dev,
                                         int32_t nr_new_max, const void* new_r_counts_dev, const void* new_r_idx_dev, const void* new_r_val_dev,
                                         int32_t np_new_max, const void* new_p_counts_dev, const void* new_p_val_dev,
                                         int32_t ns_new_max, const void* new_s_counts_dev, const void* new_s_idx_dev, const void* new_s_val_dev,
                                         void* status_dev, void* admit_dev) {
-    if (int rc = slide_check_handle(w, new_pose_dev && nr_new_max >= 0 && np_new_max >= 0 && ns_new_max >= 0 &&
-                                           (nr_new_max == 0 || (new_r_counts_dev && new_r_idx_dev && new_r_val_dev)) && (np_new_max == 0 || (new_p_counts_dev && new_p_val_dev)) &&
-                                           (ns_new_max == 0 || (new_s_counts_dev && new_s_idx_dev && new_s_val_dev)), true))
-        return rc;
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    const int topology = resident_topology(w);
-    locamd::SlidePlainArgs sa{};
-    sa.counts = (int32_t*)w->dev.t[kCounts]; sa.poses = (double*)w->dev.t[kPoses]; sa.poses_in = w->d_poses_in;
-    sa.r_idx = (int32_t*)w->dev.t[locamd::kRIdx]; sa.r_val = (double*)w->dev.t[locamd::kRVal];
-    sa.p_idx = (int32_t*)w->dev.t[locamd::kPIdx]; sa.p_val = (double*)w->dev.t[locamd::kPVal];
-    sa.s_idx = (int32_t*)w->dev.t[locamd::kSIdx]; sa.s_val = (double*)w->dev.t[locamd::kSVal];
-    sa.drop = (const int32_t*)drop_oldest_dev; sa.new_pose = (const double*)new_pose_dev;
-    sa.new_r_counts = (const int32_t*)new_r_counts_dev; sa.new_r_idx = (const int32_t*)new_r_idx_dev; sa.new_r_val = (const double*)new_r_val_dev;
-    sa.new_p_counts = (const int32_t*)new_p_counts_dev; sa.new_p_val = (const double*)new_p_val_dev;
-    sa.new_s_counts = (const int32_t*)new_s_counts_dev; sa.new_s_idx = (const int32_t*)new_s_idx_dev; sa.new_s_val = (const double*)new_s_val_dev;
-    sa.status = (int32_t*)status_dev; sa.admit = (int32_t*)admit_dev;
-    sa.nr_new_max = nr_new_max; sa.np_new_max = np_new_max; sa.ns_new_max = ns_new_max;
-    sa.n_anchors = w->n_anchors;
-    sa.pair_rule = topology == LOC_WINDOW_KERNEL_WAVE6 ? locamd::kSlidePairsWave6 : topology == LOC_WINDOW_KERNEL_WAVE6S ? locamd::kSlidePairsWave6S : locamd::kSlidePairsNone;
-    sa.B = (int)w->res.n; sa.caps = w->caps;
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = locamd::launch_window_slide_plain(sa, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_slide_plain");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    LOC_HIP(hipEventRecord(w->resident_done, st));
-    w->resident_inflight = true;
-    w->cov_pending = true;
-    w->res.cov = CovKind::Chain6;     // (loc_window_upload's verdict for these topologies; a batch the envelope pass held is classified again)
-    w->res.mirror_stale = true;       // (refresh_mirror: the next reader of the mirror fetches it)
-    return LOC_OK;
+    const NewRows rows = new_rows(drop_oldest_dev, new_pose_dev, nr_new_max, new_r_counts_dev, new_r_idx_dev, new_r_val_dev, np_new_max, new_p_counts_dev, new_p_val_dev,
+                                  ns_new_max, new_s_counts_dev, new_s_idx_dev, new_s_val_dev);
+    if (int rc = resident_gate(w, locamd::ResidentEntry::SlidePlain, new_rows_missing(rows))) return rc;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, true, st)) return rc;
+    return slide_plain_dev(w, st, rows, status_dev, admit_dev);
 }
 
 // ---- rows from raw messages (window_message_kernel.hip, message_rows.h; DESIGN.md §2, "Rows from raw messages") ----------------------------------
@@ -1175,21 +1187,17 @@ int loc_window_set_message_config(loc_window* w, const loc_window_message_config
     w->msg_set = true;
     return LOC_OK;
 }
-// what both entries check without looking at a window; nothing is launched or changed on a refusal
-static int message_check_handle(const loc_window* w, int32_t kinds_mask, const loc_window_messages* m) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->msg_set) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: loc_window_set_message_config has not been called");
-    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: no resident solve has run since the upload");
-    if ((kinds_mask & ~locamd::kMsgAllKinds) != 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: kinds_mask has unknown bits");
-    if (!m || !m->kind || !m->dt) return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: kind and dt arrays");
+// the argument checks both entries share, in their order (loc_window_message_rows_dev has a fourth: its output arrays)
+static int message_args_failed(int32_t kinds_mask, const loc_window_messages* m) {
+    if ((kinds_mask & ~locamd::kMsgAllKinds) != 0) return 1;
+    if (!m || !m->kind || !m->dt) return 2;
     if (((kinds_mask & LOC_MSG_RANGE) && (!m->anchor || !m->antenna || !m->distance || !m->distance_err)) || ((kinds_mask & LOC_MSG_IMU) && !m->imu) ||
         ((kinds_mask & LOC_MSG_LIDAR) && !m->lidar_z) || ((kinds_mask & LOC_MSG_TWIST) && !m->twist))
-        return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows: a NULL message array under a bit of kinds_mask");
-    return LOC_OK;
+        return 3;
+    return 0;
 }
-// the build launch, in stream order after the last resident launch; timed: with the covariance events around it
-static int message_launch(loc_window* w, hipStream_t st, int32_t kinds_mask, const loc_window_messages* m, const loc_window_message_rows& o, bool timed) {
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
+// the build launch, in its bracket; timing: the covariance events around it, or none
+static int message_launch(loc_window* w, hipStream_t st, int32_t kinds_mask, const loc_window_messages* m, const loc_window_message_rows& o, Timing timing) {
     locamd::MessageArgs a{};
     a.counts = (const int32_t*)w->dev.t[kCounts]; a.poses = (const double*)w->dev.t[kPoses];
     a.anchors = w->d_anchors; a.antenna_xyz = w->d_antenna; a.n_anchors = w->n_anchors; a.n_antenna = w->n_antenna;
@@ -1204,48 +1212,37 @@ static int message_launch(loc_window* w, hipStream_t st, int32_t kinds_mask, con
     a.new_s_counts = (int32_t*)o.new_s_counts; a.new_s_idx = (int32_t*)o.new_s_idx; a.new_s_val = (double*)o.new_s_val;
     a.verdict = (int32_t*)o.verdict;
     a.B = (int)w->res.n; a.nv_max = w->caps.nv_max;
-    if (timed) LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = locamd::launch_window_message_rows(a, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_message_rows");
-    if (timed) { LOC_HIP(hipEventRecord(w->cov_ev1, st)); w->cov_pending = true; }
-    LOC_HIP(hipEventRecord(w->resident_done, st));   // whatever touches the resident arrays next waits for this launch as well
-    w->resident_inflight = true;
-    return LOC_OK;
+    return resident_bracket(w, st, timing, nothing_staged, [&](hipStream_t st) { return launched(locamd::launch_window_message_rows(a, st), "launch_window_message_rows"); });
 }
 
 // build only (the rows of localization.cpp:297-376, :438-535 and :560-605 at robot.cpp:90's estimate), into the caller's device arrays: every resident verdict (only counts and poses are read); no host pass, no copy, no
 // synchronisation, no allocation
 int loc_window_message_rows_dev(loc_window* w, void* hip_stream, int32_t kinds_mask, const loc_window_messages* msgs, const loc_window_message_rows* out) {
-    if (int rc = message_check_handle(w, kinds_mask, msgs)) return rc;
-    if (!out || !out->drop_oldest || !out->new_pose || !out->new_r_counts || !out->new_r_idx || !out->new_r_val || !out->new_p_counts || !out->new_p_val ||
-        !out->new_s_counts || !out->new_s_idx || !out->new_s_val)
-        return locamd_fail(LOC_ERR_INVALID, "loc_window_message_rows_dev: a NULL output array (only verdict may be NULL)");
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    return message_launch(w, st, kinds_mask, msgs, *out, true);
+    int bad = message_args_failed(kinds_mask, msgs);
+    if (!bad && (!out || !out->drop_oldest || !out->new_pose || !out->new_r_counts || !out->new_r_idx || !out->new_r_val || !out->new_p_counts || !out->new_p_val ||
+                 !out->new_s_counts || !out->new_s_idx || !out->new_s_val))
+        bad = 4;
+    if (int rc = resident_gate(w, locamd::ResidentEntry::MessageRows, bad)) return rc;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, true, st)) return rc;
+    return message_launch(w, st, kinds_mask, msgs, *out, Timing::Covariance);
 }
 
-// build into the handle's block, then the slide the resident verdict calls for (robot.cpp:92-98: drop-oldest), on the same stream.  Both slides' host refusals are taken
-// BEFORE the build (slide_check_handle is what they start with), so a refusal launches nothing
+// build into the handle's block (untimed), then the slide the resident verdict calls for (robot.cpp:92-98: drop-oldest) in a bracket of its own on
+// the same stream.  Both slides' host refusals are the rule's, taken BEFORE the build, so a refusal launches nothing
 int loc_window_push_messages_resident_dev(loc_window* w, void* hip_stream, int32_t kinds_mask, const loc_window_messages* msgs,
                                           void* verdict_dev, void* status_dev, void* admit_dev) {
-    if (int rc = message_check_handle(w, kinds_mask, msgs)) return rc;
-    const bool plain = resident_topology(w) != LOC_WINDOW_KERNEL_CHAIN3;
-    if (int rc = slide_check_handle(w, true, plain)) return rc;
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    if (int rc = resident_gate(w, locamd::ResidentEntry::PushMessages, message_args_failed(kinds_mask, msgs))) return rc;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, true, st)) return rc;
     const locamd::MessageRowsLayout L = locamd::message_rows_layout((size_t)w->B);
     auto at = [&](int piece) { return (void*)(w->d_msg_rows + L.off[piece]); };
     const loc_window_message_rows o{at(locamd::kGDrop), at(locamd::kGPose), at(locamd::kGRCounts), at(locamd::kGRIdx), at(locamd::kGRVal), at(locamd::kGPCounts),
                                     at(locamd::kGPVal), at(locamd::kGSCounts), at(locamd::kGSIdx), at(locamd::kGSVal), verdict_dev ? verdict_dev : at(locamd::kGVerdict)};
-    if (int rc = message_launch(w, st, kinds_mask, msgs, o, false)) return rc;
-    if (plain)
-        return loc_window_slide_plain_resident_dev(w, st, o.drop_oldest, o.new_pose, LOC_MSG_NR_NEW, o.new_r_counts, o.new_r_idx, o.new_r_val,
-                                                   LOC_MSG_NP_NEW, o.new_p_counts, o.new_p_val, LOC_MSG_NS_NEW, o.new_s_counts, o.new_s_idx, o.new_s_val, status_dev, admit_dev);
-    return loc_window_slide_resident_dev(w, st, o.drop_oldest, o.new_pose, LOC_MSG_NR_NEW, o.new_r_counts, o.new_r_idx, o.new_r_val,
-                                         LOC_MSG_NP_NEW, o.new_p_counts, o.new_p_val, nullptr, nullptr, nullptr, status_dev, admit_dev);
+    if (int rc = message_launch(w, st, kinds_mask, msgs, o, Timing::None)) return rc;
+    if (resident_topology(w) != LOC_WINDOW_KERNEL_CHAIN3) return slide_plain_dev(w, st, NewRows{o, LOC_MSG_NR_NEW, LOC_MSG_NP_NEW, LOC_MSG_NS_NEW}, status_dev, admit_dev);
+    void* const out[4] = {nullptr, nullptr, nullptr, status_dev};
+    return slide_carry_dev(w, st, NewRows{o, LOC_MSG_NR_NEW, LOC_MSG_NP_NEW, 0}, out, admit_dev);
 }
 
 // ---- the per-edge chi2 audit and the outlier-range removal (edge_audit_kernel.hip; DESIGN.md §2, "Edge audit and outlier removal") ----------------
@@ -1269,99 +1266,58 @@ int loc_window_edge_chi2_host(loc_window* w, int64_t n, const int32_t* counts, c
     });
 }
 
-// what the two resident entries share: the covariance call's refusals, then one launch in stream order after the last resident launch and
-// before the next one (loc_window_slide_resident_dev's way); nothing is read on the host, nothing synchronises, the mirror stays as it is
-static int resident_audit_launch(loc_window* w, void* hip_stream, const char* unsolved, bool prune, locamd::EdgeAudit x) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, unsolved);
-    if (int rc = check_pinfo_covers_resident(w)) return rc;
-    if (prune) {
-        if (!(x.chi2_max >= 0.0) || x.min_edges < 0) return locamd_fail(LOC_ERR_INVALID, "loc_window_prune_resident: chi2_max must be a number >= 0 and min_edges >= 0");
-        // build_arrow_aux packed measurement and information into ArrowAux::rec at upload: a store into r_val would not reach that solve
-        // (every other solve kernel and covariance pass reads range values from r_val at launch)
-        if (resident_topology(w) == LOC_WINDOW_KERNEL_ARROW3)
-            return locamd_fail(LOC_ERR_UNSUPPORTED, "loc_window_prune_resident: the resident batch is solved by arrow3_lm_kernel from records packed at upload");
-    }
-    LOC_HIP(hipSetDevice(w->device));
-    if (int rc = flush_anchors(w)) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    locamd::WindowArgs a = window_args(w, w->dev, w->res.n, nullptr, w->d_anchors, nullptr);
-    a.r_off1 = w->opt.has_off1 ? w->d_roff1 : nullptr;
-    if (prune) x.prune_r_val = (double*)w->dev.t[locamd::kRVal];
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = locamd::launch_window_edge_audit(a, x, st);
-    if (e != hipSuccess) return locamd_fail_hip(e, "launch_window_edge_audit");
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    LOC_HIP(hipEventRecord(w->resident_done, st));   // whatever touches the resident arrays next waits for this launch as well
-    w->resident_inflight = true;
-    w->cov_pending = true;
-    return LOC_OK;
+// the two resident entries' launch, in the bracket (resident_launch); nothing is read on the host, nothing synchronises, the mirror stays as it is
+static int resident_audit_launch(loc_window* w, void* hip_stream, const locamd::EdgeAudit& x) {
+    return resident_launch(w, hip_stream, Timing::Covariance, true, [&](hipStream_t st) {
+        locamd::WindowArgs a = window_args(w, w->dev, w->res.n, nullptr, w->d_anchors, nullptr);
+        a.r_off1 = w->opt.has_off1 ? w->d_roff1 : nullptr;
+        return launched(locamd::launch_window_edge_audit(a, x, st), "launch_window_edge_audit");
+    });
 }
 
 int loc_window_edge_chi2_resident(loc_window* w, void* hip_stream, void* r_chi2_dev, void* p_chi2_dev, void* s_chi2_dev, void* total_dev, void* active_dev) {
-    return resident_audit_launch(w, hip_stream, "loc_window_edge_chi2_resident: no resident solve has run since the upload", false,
-                                 locamd::EdgeAudit{(double*)r_chi2_dev, (double*)p_chi2_dev, (double*)s_chi2_dev, (double*)total_dev, (int32_t*)active_dev, nullptr, 0.0, 0, nullptr, nullptr});
+    if (int rc = resident_gate(w, locamd::ResidentEntry::EdgeChi2)) return rc;
+    return resident_audit_launch(w, hip_stream, locamd::EdgeAudit{(double*)r_chi2_dev, (double*)p_chi2_dev, (double*)s_chi2_dev, (double*)total_dev, (int32_t*)active_dev, nullptr, 0.0, 0, nullptr, nullptr});
 }
 
 int loc_window_prune_resident(loc_window* w, void* hip_stream, double chi2_max, int32_t min_edges, void* removed_dev, void* n_removed_dev) {
-    return resident_audit_launch(w, hip_stream, "loc_window_prune_resident: no resident solve has run since the upload", true,
-                                 locamd::EdgeAudit{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, chi2_max, min_edges, (int32_t*)removed_dev, (int32_t*)n_removed_dev});
+    if (int rc = resident_gate(w, locamd::ResidentEntry::Prune, !(chi2_max >= 0.0) || min_edges < 0 ? 1 : 0)) return rc;
+    return resident_audit_launch(w, hip_stream, locamd::EdgeAudit{nullptr, nullptr, nullptr, nullptr, nullptr, (double*)w->dev.t[locamd::kRVal], chi2_max, min_edges,
+                                                                  (int32_t*)removed_dev, (int32_t*)n_removed_dev});
 }
 
 // ---- the publish step and the path of the resident batch (window_publish_kernel.hip; DESIGN.md §2, "Publish and path records of a resident
 // batch"): Localization::publish() (localization.cpp:195-226), Robot::vertices2path() (robot.cpp:61-72), the destructor's tail (:708-717) ----
-// what the two entries share: the refusals, then `launch` in stream order after the last resident launch and before the next one
-// (resident_audit_launch's way); nothing is read on the host, nothing synchronises, the mirror stays as it is.  Only counts, poses and
-// result are read: every structural verdict and every handle state, no anchors, no table of full matrices
-extern "C++" {   // (a template cannot have C linkage)
-template <class Launch>
-static int resident_records_launch(loc_window* w, void* hip_stream, const char* who, int32_t trajectory_length, const char* launch_name, Launch launch) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, (std::string(who) + ": nothing uploaded").c_str());
-    if (!w->res.solved) return locamd_fail(LOC_ERR_INVALID, (std::string(who) + ": no resident solve has run since the upload").c_str());
-    if (trajectory_length < 1 || trajectory_length > w->caps.nv_max)
-        return locamd_fail(LOC_ERR_INVALID, (std::string(who) + ": trajectory_length must be in [1, nv_max]").c_str());
-    LOC_HIP(hipSetDevice(w->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    if (w->resident_inflight) LOC_HIP(hipStreamWaitEvent(st, w->resident_done, 0));   // (the solve may have run on another stream)
-    LOC_HIP(hipEventRecord(w->cov_ev0, st));
-    const hipError_t e = launch(st);
-    if (e != hipSuccess) return locamd_fail_hip(e, launch_name);
-    LOC_HIP(hipEventRecord(w->cov_ev1, st));
-    LOC_HIP(hipEventRecord(w->resident_done, st));   // the next resident launch writes what this one reads: it waits for it
-    w->resident_inflight = true;
-    w->cov_pending = true;
-    return LOC_OK;
-}
-}   // extern "C++"
+// Both entries: their argument checks in the rule's order, then one launch in the bracket WITHOUT the anchor table's flush (resident_launch).
+// Nothing is read on the host, nothing synchronises, the mirror stays as it is.  Only counts, poses and result are read: every structural
+// verdict and every handle state, no anchors, no table of full matrices
+static bool trajectory_length_bad(const loc_window* w, int32_t trajectory_length) { return w && (trajectory_length < 1 || trajectory_length > w->caps.nv_max); }
 
 int loc_window_publish_resident(loc_window* w, void* hip_stream, double minimum_optimize_error, int32_t trajectory_length,
                                 void* flags_dev, void* realtime_dev, void* optimized_dev, void* chi2_dev, void* n_published_dev) {
-    if (minimum_optimize_error != minimum_optimize_error) return locamd_fail(LOC_ERR_INVALID, "loc_window_publish_resident: minimum_optimize_error is NaN");
-    if (!flags_dev) return locamd_fail(LOC_ERR_INVALID, "loc_window_publish_resident: flags_dev is NULL");
-    return resident_records_launch(w, hip_stream, "loc_window_publish_resident", trajectory_length, "launch_window_publish", [&](hipStream_t st) {
+    const int bad = minimum_optimize_error != minimum_optimize_error ? 1 : !flags_dev ? 2 : trajectory_length_bad(w, trajectory_length) ? 3 : 0;
+    if (int rc = resident_gate(w, locamd::ResidentEntry::Publish, bad)) return rc;
+    return resident_launch(w, hip_stream, Timing::Covariance, false, [&](hipStream_t st) {
         const locamd::PublishArgs a{(const int32_t*)w->dev.t[kCounts], (const double*)w->dev.t[kPoses], w->d_result, minimum_optimize_error, trajectory_length,
                                     (int32_t*)flags_dev, (double*)realtime_dev, (double*)optimized_dev, (double*)chi2_dev, (int32_t*)n_published_dev,
                                     w->res.n, w->caps.nv_max};
-        return locamd::launch_window_publish(a, st);
+        return launched(locamd::launch_window_publish(a, st), "launch_window_publish");
     });
 }
 
 int loc_window_path_resident(loc_window* w, void* hip_stream, int32_t trajectory_length, int32_t first, int32_t count, void* path_dev, void* present_dev) {
-    if (!path_dev || !present_dev) return locamd_fail(LOC_ERR_INVALID, "loc_window_path_resident: path_dev or present_dev is NULL");
-    if (first < 0 || count < 1 || (int64_t)first + count > trajectory_length)
-        return locamd_fail(LOC_ERR_INVALID, "loc_window_path_resident: first >= 0, count >= 1 and first + count <= trajectory_length are required");
-    return resident_records_launch(w, hip_stream, "loc_window_path_resident", trajectory_length, "launch_window_path", [&](hipStream_t st) {
+    const int bad = !path_dev || !present_dev ? 1 : first < 0 || count < 1 || (int64_t)first + count > trajectory_length ? 2 : trajectory_length_bad(w, trajectory_length) ? 3 : 0;
+    if (int rc = resident_gate(w, locamd::ResidentEntry::Path, bad)) return rc;
+    return resident_launch(w, hip_stream, Timing::Covariance, false, [&](hipStream_t st) {
         const locamd::PathArgs a{(const int32_t*)w->dev.t[kCounts], (const double*)w->dev.t[kPoses], trajectory_length, first, count,
                                  (double*)path_dev, (int32_t*)present_dev, w->res.n, w->caps.nv_max};
-        return locamd::launch_window_path(a, st);
+        return launched(locamd::launch_window_path(a, st), "launch_window_path");
     });
 }
 
 int loc_window_download_tables(loc_window* w, int32_t* counts, double* poses, int32_t* r_idx, double* r_val, int32_t* p_idx, double* p_val,
                                int32_t* s_idx, double* s_val, double* pinfo) {
-    if (!w || w->res.n <= 0) return locamd_fail(LOC_ERR_INVALID, "nothing uploaded");
-    if (pinfo && !w->opt.has_pinfo) return locamd_fail(LOC_ERR_INVALID, "loc_window_download_tables: the handle has no table of full information matrices");
+    if (int rc = resident_gate(w, locamd::ResidentEntry::DownloadTables, w && pinfo && !w->opt.has_pinfo ? 1 : 0)) return rc;
     LOC_HIP(hipSetDevice(w->device));
     if (int rc = wait_resident(w)) return rc;
     const locamd::WindowCaps& c = w->caps;

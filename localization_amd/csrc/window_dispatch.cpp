@@ -219,4 +219,71 @@ bool cov_stale(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind 
     return kind != CovKind::Unclassified && kind != CovKind::None && o.cov_general && !o.has_off1 && !cov_admitted(o, f, n, kind);
 }
 
+// ---- the resident entries' refusals ("What every resident entry refuses") --------------------------------------------------------
+#define LOC_UNSOLVED(who) who ": no resident solve has run since the upload"
+#define LOC_SLIDE_ROWS "loc_window_slide_resident: new pose and new row arrays"
+#define LOC_MESSAGE_ARGS "loc_window_message_rows: kinds_mask has unknown bits", "loc_window_message_rows: kind and dt arrays", "loc_window_message_rows: a NULL message array under a bit of kinds_mask"
+enum RefusalText { kNothing, kNothingPublish, kNothingPath, kMirror, kMsgSet, kPinfoShort, kSlideVerdict, kSlideOff1, kSlidePinfoRotation, kPlainChain3, kPlainVerdict, kPlainPinfo, kPruneArrow3,
+                   kUnsolved /* + entry */, kRefusalTexts = kUnsolved + kResidentEntries };
+static const char* const kRefusalText[kRefusalTexts] = {
+    "nothing uploaded", "loc_window_publish_resident: nothing uploaded", "loc_window_path_resident: nothing uploaded",
+    "loc_window_slide_resident: option \"resident_slide\" was 0 when the batch was uploaded", "loc_window_message_rows: loc_window_set_message_config has not been called",
+    "the resident batch has more windows than loc_window_set_prior_information described",
+    "loc_window_slide_resident: the resident batch is not an ordered translation-only chain batch", "loc_window_slide_resident: no endpoint-1 lever arms",
+    "loc_window_slide_resident: the table of full information matrices has rotation entries",
+    "loc_window_slide_plain_resident_dev: the resident batch is an ordered translation-only chain batch: loc_window_slide_resident / loc_window_slide_resident_dev slide it",
+    "loc_window_slide_plain_resident_dev: the resident batch is not an ordered 6-DoF chain batch", "loc_window_slide_plain_resident_dev: the handle has a table of full information matrices",
+    "loc_window_prune_resident: the resident batch is solved by arrow3_lm_kernel from records packed at upload",
+    nullptr, LOC_UNSOLVED("loc_window_download"), LOC_UNSOLVED("loc_window_covariance_resident"), LOC_UNSOLVED("loc_window_slide_resident"), LOC_UNSOLVED("loc_window_slide_resident"),
+    LOC_UNSOLVED("loc_window_slide_resident"), LOC_UNSOLVED("loc_window_message_rows"), LOC_UNSOLVED("loc_window_message_rows"), LOC_UNSOLVED("loc_window_edge_chi2_resident"),
+    LOC_UNSOLVED("loc_window_prune_resident"), LOC_UNSOLVED("loc_window_publish_resident"), LOC_UNSOLVED("loc_window_path_resident"), nullptr};
+// the words of the entries' own argument checks (the checks stay with the entries), in the order each entry takes them
+static const char* const kArgumentText[kResidentEntries][4] = {
+    {}, {}, {"covariance output arrays"}, {LOC_SLIDE_ROWS}, {LOC_SLIDE_ROWS}, {LOC_SLIDE_ROWS},
+    {LOC_MESSAGE_ARGS, "loc_window_message_rows_dev: a NULL output array (only verdict may be NULL)"}, {LOC_MESSAGE_ARGS}, {},
+    {"loc_window_prune_resident: chi2_max must be a number >= 0 and min_edges >= 0"},
+    {"loc_window_publish_resident: minimum_optimize_error is NaN", "loc_window_publish_resident: flags_dev is NULL", "loc_window_publish_resident: trajectory_length must be in [1, nv_max]"},
+    {"loc_window_path_resident: path_dev or present_dev is NULL", "loc_window_path_resident: first >= 0, count >= 1 and first + count <= trajectory_length are required",
+     "loc_window_path_resident: trajectory_length must be in [1, nv_max]"},
+    {"loc_window_download_tables: the handle has no table of full information matrices"}};
+
+// The order, for every entry: [publish, path: their first two argument checks] — handle and batch — [the slides: the mirror] [the message
+// entries: the configuration] — solved (but the solve and the tables' download) — the argument checks that are left (prune's comes later) —
+// [push: the mirror] — the table covers the batch (but the downloads, the build, publish and path) — [prune: its argument check, then the
+// verdict] — [the slides and push: the verdict, the lever arms, the table, as the carrying or the plain slide wants them]
+Refusal resident_refusal(ResidentEntry e, const ResidentFacts& f, int arg_failed) {
+    using E = ResidentEntry;
+    auto no = [](int code, int text) { return Refusal{code, kRefusalText[text]}; };
+    const Refusal go{LOC_OK, nullptr}, argument{LOC_ERR_INVALID, arg_failed >= 1 && arg_failed <= 4 ? kArgumentText[(int)e][arg_failed - 1] : nullptr};
+    if (!argument.text) arg_failed = 0;   // (the entry has no such check)
+    const bool records = e == E::Publish || e == E::Path, slide = e == E::SlideHost || e == E::SlideDev || e == E::SlidePlain;
+    if (records && (arg_failed == 1 || arg_failed == 2)) return argument;
+    if (!f.handle || !f.resident) return no(LOC_ERR_INVALID, e == E::Publish ? kNothingPublish : e == E::Path ? kNothingPath : kNothing);
+    if (slide && !f.mirror_valid) return no(LOC_ERR_INVALID, kMirror);
+    if ((e == E::MessageRows || e == E::PushMessages) && !f.msg_set) return no(LOC_ERR_INVALID, kMsgSet);
+    if (e != E::Solve && e != E::DownloadTables && !f.solved) return no(LOC_ERR_INVALID, kUnsolved + (int)e);
+    if (arg_failed && e != E::Prune) return argument;
+    if (e == E::PushMessages && !f.mirror_valid) return no(LOC_ERR_INVALID, kMirror);
+    if (e == E::Download || e == E::DownloadTables || e == E::MessageRows || records) return go;
+    if (f.pinfo_short) return no(LOC_ERR_INVALID, kPinfoShort);
+    if (e == E::Prune) {
+        if (arg_failed) return argument;
+        // build_arrow_aux packed measurement and information into ArrowAux::rec at upload: a store into r_val would not reach that solve
+        // (every other solve kernel and covariance pass reads range values from r_val at launch)
+        return f.topology == LOC_WINDOW_KERNEL_ARROW3 ? no(LOC_ERR_UNSUPPORTED, kPruneArrow3) : go;
+    }
+    if (!slide && e != E::PushMessages) return go;
+    const int t = f.topology;
+    if (e == E::SlidePlain || (e == E::PushMessages && t != LOC_WINDOW_KERNEL_CHAIN3)) {
+        // the plain drop: one of the ordered 6-DoF chain verdicts, and no table of full information matrices at all
+        if (t == LOC_WINDOW_KERNEL_CHAIN3) return no(LOC_ERR_UNSUPPORTED, kPlainChain3);
+        if (t != LOC_WINDOW_KERNEL_CHAIN && t != LOC_WINDOW_KERNEL_WAVE6 && t != LOC_WINDOW_KERNEL_WAVE6S) return no(LOC_ERR_UNSUPPORTED, kPlainVerdict);
+        if (f.has_off1) return no(LOC_ERR_UNSUPPORTED, kSlideOff1);
+        return f.has_pinfo ? no(LOC_ERR_UNSUPPORTED, kPlainPinfo) : go;
+    }
+    if (t != LOC_WINDOW_KERNEL_CHAIN3) return no(LOC_ERR_UNSUPPORTED, kSlideVerdict);
+    if (f.has_off1) return no(LOC_ERR_UNSUPPORTED, kSlideOff1);
+    return f.has_pinfo && !f.pinfo_translation ? no(LOC_ERR_UNSUPPORTED, kSlidePinfoRotation) : go;
+}
+
 }  // namespace locamd

@@ -1,7 +1,9 @@
 // Which solve kernel and which covariance pass a batch of windows takes: the rules, free of any handle and HIP state (window_dispatch.cpp
 // compiles with a plain host compiler, as window_structure.cpp does; tests/host/window_dispatch_driver.cpp runs the rules on the CPU).
 // capi_window.cpp keeps the switches and the capacity facts in its handle and asks here; a new kernel or covariance pass is registered
-// in pick_kernel / batch_topology or CovKind / covariance_kind / cov_admitted, and gets its launch in capi_window.cpp.
+// in pick_kernel / batch_topology or CovKind / covariance_kind / cov_admitted, and gets its launch in capi_window.cpp.  What a resident entry
+// refuses by the handle's state alone, in which order and with which words, is resident_refusal: a new resident entry is registered in
+// ResidentEntry and gets its line there.
 #pragma once
 #include "window_structure.h"
 
@@ -84,5 +86,17 @@ struct SchedKey {
 struct CovVerdict { CovKind kind; bool need_upload; int list_cap; long long env_blocks; };
 CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, const PairTables& pt,
                            WinAux& own, SchedKey* keyed);
+
+// ---- what every resident entry refuses by the handle's state, in which order and with which words ------------------------------------------
+enum class ResidentEntry : int { Solve, Download, Covariance, SlideHost, SlideDev, SlidePlain, MessageRows, PushMessages, EdgeChi2, Prune, Publish, Path, DownloadTables };
+constexpr int kResidentEntries = 13;
+// the facts of the handle, as plain values: a handle was given at all; loc_window_upload has left a batch; ... under option "resident_slide"; a
+// resident solve has run since the upload; the table of full information matrices describes fewer windows than the batch has; the structural
+// verdict as it holds now (LOC_WINDOW_KERNEL_*); the three table and lever-arm switches; loc_window_set_message_config has been called
+struct ResidentFacts { bool handle = false, resident = false, mirror_valid = false, solved = false, pinfo_short = false; int topology = 0; bool has_off1 = false, has_pinfo = false, pinfo_translation = false, msg_set = false; };
+struct Refusal { int code; const char* text; };   // LOC_OK and nullptr: go on; else the LOC_ERR_* and the words of the FIRST refusal
+// arg_failed: 0, or k when the k-th of the entry's own argument checks (NULL arrays, kinds_mask, chi2_max, trajectory_length ..., counted in
+// the order the entry takes them) is the first of them to fail: the rule knows where each sits between the state checks, and its words
+Refusal resident_refusal(ResidentEntry e, const ResidentFacts& f, int arg_failed);
 
 }  // namespace locamd

@@ -11,7 +11,16 @@ tree_min_batch, arrow3_wanted, cov_switches, the refused() lambda of loc_window_
 that reset resident_cov to -1, bodies verbatim, behind a stand-in struct with the fields they read (the two *_lds_bytes calls answered by
 the grid's "fits" columns); it read the same input file and wrote the same output as the driver.  The file holds that output and, as a
 guard against a grid that drifts from the recording, the grids' axes.  A covariance verdict travels as CovKind's value; the scratch
-program mapped it to the integers the parent kept in loc_window::resident_cov (-1, 0, 3, 6, 7, 8, 9, 10)."""
+program mapped it to the integers the parent kept in loc_window::resident_cov (-1, 0, 3, 6, 7, 8, 9, 10).
+
+Rule set 3, what a resident entry refuses by the handle's state (resident_refusal), is held in the same way to tests/golden/window_refusal_table.npz:
+a recording of commit 7061161, where every resident entry of capi_window.cpp spelled its refusals out.  The scratch program held that commit's
+slide_check_handle, message_check_handle, check_pinfo_covers_resident and the heads of loc_window_solve_resident, loc_window_download,
+loc_window_joint_covariance_resident, resident_audit_launch, resident_records_launch (with its two callers' argument checks in front),
+loc_window_push_messages_resident_dev and loc_window_download_tables, bodies verbatim, behind a stand-in struct with the fields they read
+(resident_topology answered by the grid's topology column, the condition of an entry's k-th argument check by "arg_failed == k"); it wrote the
+return code and the text handed to locamd_fail for every row.  The grid is the full product of the axes below but for the rows no handle can be
+in (pinfo_short without has_pinfo) and the argument checks an entry does not have; topology takes every LOC_WINDOW_KERNEL_* value."""
 import itertools
 import os
 import shutil
@@ -23,6 +32,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "localization_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "window_dispatch_table.npz")
+GOLDEN_REFUSAL = os.path.join(ROOT, "tests", "golden", "window_refusal_table.npz")
 FLAGS = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 # rule set 1: LOC_WINDOW_KERNEL_* (include/localization_amd.h) and the switches pick_kernel reads.  LOCAMD_CHAIN_MIN_BATCH, where set, is 4 096
@@ -43,6 +53,15 @@ COV_AXES = {
     "has_off1": [0, 1], "nv_max": [64, 65], "n": [255, 256], "tree": [-1, 0], "arrow3": [-1, 0, 1], "cov_general": [0, 1], "arrow_fits": [0, 1],
 }
 COV_RESULTS = ("cov_admitted", "cov_stale", "cov_stale_switches_changed", "cov_switches", "arrow3_wanted")
+# rule set 3: ResidentEntry Solve .. DownloadTables, the facts of the handle and which of the entry's own argument checks fails first (0: none)
+REFUSAL_AXES = {
+    "entry": list(range(13)),
+    "handle": [0, 1], "resident": [0, 1], "mirror_valid": [0, 1], "solved": [0, 1], "pinfo_short": [0, 1],
+    "topology": list(range(9)),
+    "has_off1": [0, 1], "has_pinfo": [0, 1], "pinfo_translation": [0, 1], "msg_set": [0, 1],
+    "arg_failed": [0, 1, 2, 3, 4],
+}
+REFUSAL_ARGUMENT_CHECKS = [0, 0, 1, 1, 1, 1, 4, 3, 0, 1, 3, 3, 1]   # per entry
 
 
 def solve_rows():
@@ -53,6 +72,26 @@ def solve_rows():
 
 def cov_rows():
     return np.array(list(itertools.product(*COV_AXES.values())), dtype=np.int64)
+
+
+def refusal_rows():
+    rows = np.array(list(itertools.product(*REFUSAL_AXES.values())), dtype=np.int64)
+    keep = (rows[:, 11] <= np.array(REFUSAL_ARGUMENT_CHECKS)[rows[:, 0]]) & ~((rows[:, 5] == 1) & (rows[:, 8] == 0))
+    return rows[keep]
+
+
+def write_refusal_table(path):
+    rows = refusal_rows()
+    with open(path, "wb") as f:
+        np.array([3, rows.shape[0], rows.shape[1]], dtype=np.int64).tofile(f)
+        np.ascontiguousarray(rows).tofile(f)
+
+
+def read_refusals(out_path, texts_path):
+    with open(texts_path, "rb") as f:
+        texts = f.read().decode("utf-8").split("\n")
+    assert texts[-1] == ""
+    return np.fromfile(out_path, dtype=np.int64), texts[:-1]
 
 
 def write_tables(path):
@@ -88,7 +127,10 @@ def tables(tmp_path_factory):
     r = subprocess.run([str(d / "driver"), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-4000:])
     solve, cov = read_results(d / "out.bin")
-    return {"solve": solve, "cov": cov, "golden": np.load(GOLDEN)}
+    write_refusal_table(d / "in3.bin")
+    r = subprocess.run([str(d / "driver"), str(d / "in3.bin"), str(d / "out3.bin"), str(d / "texts3.txt")], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-4000:])
+    return {"solve": solve, "cov": cov, "golden": np.load(GOLDEN), "refusal": read_refusals(d / "out3.bin", d / "texts3.txt"), "refusal_golden": np.load(GOLDEN_REFUSAL)}
 
 
 def assert_same(got, want, rows, names, columns):
@@ -116,3 +158,26 @@ def test_solve_kernel_table(tables):
 
 def test_resident_covariance_table(tables):
     assert_same(tables["cov"], tables["golden"]["cov"], cov_rows(), COV_RESULTS, list(COV_AXES))
+
+
+def test_the_refusal_recording_is_of_this_grid(tables):
+    g = tables["refusal_golden"]
+    for name, values in REFUSAL_AXES.items():
+        assert g["axis_" + name].tolist() == values, name
+    assert g["argument_checks"].tolist() == REFUSAL_ARGUMENT_CHECKS
+    rows = refusal_rows()
+    assert len(rows) == (13 + sum(REFUSAL_ARGUMENT_CHECKS)) * 2 ** 9 * 9 * 3 // 4 and g["code"].shape == g["text"].shape == (len(rows),)
+    # every code the entries return and every text of the parent is in the recording; "go on" has no text
+    assert sorted(set(g["code"].tolist())) == [-5, -1, 0] and set(g["text"].tolist()) == set(range(len(g["texts"])))
+    assert ((g["code"] == 0) == (g["texts"][g["text"]] == "")).all()
+
+
+def test_resident_refusal_table(tables):
+    g = tables["refusal_golden"]
+    code, texts = tables["refusal"]
+    rows = refusal_rows()
+    want = g["texts"][g["text"]].tolist()
+    assert len(code) == len(texts) == len(rows)
+    bad = [i for i in range(len(rows)) if code[i] != g["code"][i] or texts[i] != want[i]]
+    assert not bad, (f"{len(bad)} of {len(rows)} rows differ; the first: " + ", ".join(f"{k}={v}" for k, v in zip(REFUSAL_AXES, rows[bad[0]].tolist())) +
+                     f" gives {code[bad[0]]} {texts[bad[0]]!r} (recorded {g['code'][bad[0]]} {want[bad[0]]!r})")
