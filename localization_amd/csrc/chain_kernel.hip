@@ -245,6 +245,7 @@ __device__ __forceinline__ void chain_sweep(const WindowArgs& a, double* slab, l
             for (int k = 0; k < 12; ++k) Zi[k] = CP(q, 1 + k);
 #pragma unroll
             for (int k = 0; k < 6; ++k) Wd[k] = CP(q, 13 + k);
+            // (kept written out — must equal se3_edge_device.h: prior_terms / prior_diag_chi / prior_diag_products: DESIGN.md §4)
             double RE[9], tE[3], qq[4];
             mat_mul(Zi, Xc, RE);
             mat_vec(Zi, Xc + 9, tE);

@@ -17,50 +17,18 @@ namespace {
 
 #define LOCAMD_CV_TRI(r, c) ((r) >= (c) ? (r) * ((r) + 1) / 2 + (c) : (c) * ((c) + 1) / 2 + (r))
 
-// one unary EdgeSE3Prior at X: its J^T W J (lower triangle, 21) — window_kernel.hip: evaluate_edges, unary priors
+// one unary EdgeSE3Prior at X: its J^T W J (lower triangle, 21) — se3_edge_device.h: prior_terms, prior_diag_hessian
 __device__ __forceinline__ void cov_prior_block(const double* val, const double* X, double* rec) {
-    double RE[9], tE[3], q[4];
-    mat_mul(val, X, RE);
-    mat_vec(val, X + 9, tE);
-    mat_to_quat(RE, q);
-    quat_normalize_sign(q);
-    double J[36];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) J[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
-    quat_right_jac(q, 1.0, J, 6);
-    const double* W = val + 12;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int cc = 0; cc <= r; ++cc) {
-            double h = 0.0;
-            if ((r < 3) == (cc < 3)) {
-#pragma unroll
-                for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) h += J[i * 6 + r] * W[i] * J[i * 6 + cc];
-            }
-            rec[r * (r + 1) / 2 + cc] = h;
-        }
+    double err[6], J[36];
+    prior_terms<true>(val, X, err, J);
+    prior_diag_hessian(J, val + 12, rec);
 }
 
 // the same with the prior's full information matrix W (6x6 row-major, symmetric: loc_window_set_prior_information) in the place of val's
-// diagonal — window_kernel.hip: evaluate_edges<.., PINFO>; the record's layout is the same
+// diagonal — window_device.h: prior_full_hessian, as window_kernel.hip's evaluate_edges<.., PINFO>; the record's layout is the same
 __device__ __forceinline__ void cov_prior_block_full(const double* val, const double* W, const double* X, double* rec) {
-    double RE[9], q[4];
-    mat_mul(val, X, RE);
-    mat_to_quat(RE, q);
-    quat_normalize_sign(q);
-    double J[36];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) J[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
-    quat_right_jac(q, 1.0, J, 6);
+    double err[6], J[36];
+    prior_terms<true>(val, X, err, J);
     prior_full_hessian(J, W, rec);
 }
 

@@ -25,7 +25,7 @@ namespace {
 
 constexpr int kAuditChunk = 64;   // rows per pass (one per lane)
 
-// e = toVectorMQT(Z^-1 X) of a unary EdgeSE3Prior: the operations of evaluate_edges' prior branch (window_kernel.hip), val = Z^-1 as R(9), t(3)
+// e = toVectorMQT(Z^-1 X) of a unary EdgeSE3Prior: the operations of se3_edge_device.h's prior_terms, val = Z^-1 as R(9), t(3)
 __device__ __forceinline__ void audit_prior_error(const double* val, const double* X, double* err) {
     double RE[9], tE[3], q[4];
     mat_mul(val, X, RE);

@@ -240,43 +240,16 @@ __device__ __forceinline__ void tree_sweep(const WindowArgs& a, const TreeSched&
             for (int k = 0; k < 12; ++k) Zi[k] = TP(qi, k);
 #pragma unroll
             for (int k = 0; k < 6; ++k) Wd[k] = TP(qi, 12 + k);
-            double RE[9], tE[3], qq[4];
-            mat_mul(Zi, Xc, RE);
-            mat_vec(Zi, Xc + 9, tE);
-            tE[0] += Zi[9]; tE[1] += Zi[10]; tE[2] += Zi[11];
-            mat_to_quat(RE, qq);
-            quat_normalize_sign(qq);
-            const double err[6] = {tE[0], tE[1], tE[2], qq[1], qq[2], qq[3]};
-            double chi = 0.0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) chi += err[i] * (Wd[i] * err[i]);
+            double err[6], J[36];
+            prior_terms<FULL>(Zi, Xc, err, J);
+            const double chi = prior_diag_chi(Wd, err);
             rsum += chi;
             csum += chi;
             if (FULL) {
-                double J[36];
+                double h[27];
+                prior_diag_products(J, Wd, err, h);
 #pragma unroll
-                for (int i = 0; i < 36; ++i) J[i] = 0.0;
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
-                quat_right_jac(qq, 1.0, J, 6);
-#pragma unroll
-                for (int r = 0; r < 6; ++r) {
-#pragma unroll
-                    for (int cc = 0; cc <= r; ++cc) {
-                        double h = 0.0;
-                        if ((r < 3) == (cc < 3)) {
-#pragma unroll
-                            for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) h += J[i * 6 + r] * Wd[i] * J[i * 6 + cc];
-                        }
-                        D[r * (r + 1) / 2 + cc] += h;
-                    }
-                    double bb = 0.0;
-#pragma unroll
-                    for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) bb += J[i * 6 + r] * (-Wd[i] * err[i]);
-                    D[21 + r] += bb;
-                }
+                for (int k = 0; k < 27; ++k) D[k] += h[k];
             }
         }
         if (FULL) {

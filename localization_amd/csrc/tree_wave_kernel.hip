@@ -233,6 +233,7 @@ __device__ __forceinline__ void wave_node_edges(const WindowArgs& a, const TreeS
         for (int k = 0; k < 12; ++k) Zi[k] = pv[k];
 #pragma unroll
         for (int k = 0; k < 6; ++k) Wd[k] = pv[12 + k];
+        // (kept written out — must equal se3_edge_device.h: prior_terms / prior_diag_chi / prior_diag_products: DESIGN.md §4)
         double RE[9], tE[3], qq[4];
         mat_mul(Zi, Xc, RE);
         mat_vec(Zi, Xc + 9, tE);

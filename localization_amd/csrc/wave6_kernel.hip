@@ -234,7 +234,7 @@ __device__ __forceinline__ void w6_edge(const W6Lds& l, const double* P, const W
     }
 }
 
-// one EdgeSE3Prior (window_kernel.hip: evaluate_edges, unary priors): e = toVectorMQT(Z^-1 X), diagonal information, not robust
+// one EdgeSE3Prior (se3_edge_device.h: prior_terms states it for the other kernels; this one has its own arithmetic on purpose): e = toVectorMQT(Z^-1 X), diagonal information, not robust
 template <bool FULL>
 __device__ __forceinline__ void w6_prior(const W6Lds& l, const double* P, int q, double& rsum, double& csum) {
     const int v = l.pidx[q];

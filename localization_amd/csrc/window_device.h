@@ -279,8 +279,9 @@ __device__ __forceinline__ double range_jac_numeric_t(const double* p0, const do
 
 // J^T W J of an EdgeSE3Prior with a FULL information matrix W (6x6 row-major, symmetric: loc_window_set_prior_information), lower triangle
 // (21 entries, k = r (r + 1) / 2 + c).  J (6x6 row-major) = blockdiag(R_E, Q): J[i][r] is non-zero inside r's 3-block only, so entry (r, c)
-// sums J[i][r] W[i][k] J[k][c] over i in r's block and k in c's.  The one statement of that product: window_kernel.hip's
-// evaluate_edges<.., PINFO> and cov_block_device.h's cov_prior_block_full both call it.
+// sums J[i][r] W[i][k] J[k][c] over i in r's block and k in c's.  The one statement of that product (J: se3_edge_device.h's prior_terms;
+// the diagonal-W form: prior_diag_hessian there): window_kernel.hip's evaluate_edges<.., PINFO> and cov_block_device.h's
+// cov_prior_block_full both call it.
 __device__ __forceinline__ void prior_full_hessian(const double* J, const double* W, double* rec) {
 #pragma unroll
     for (int r = 0; r < 6; ++r) {

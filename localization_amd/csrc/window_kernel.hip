@@ -32,7 +32,7 @@
 //   * small windows keep everything in LDS, larger ones in a per-instance slice of an HBM workspace (index tables in LDS);
 //   * all LM control flow is uniform over the instance's threads (sums are DPP reductions, combined across the waves in wave
 //     order: every thread holds the same bits).
-#include "window_device.h"
+#include "se3_edge_device.h"
 #include "window_layouts.h"
 #include "lm_damping.h"
 
@@ -228,13 +228,8 @@ __device__ __forceinline__ void evaluate_edges(const WindowArgs& a, const Lds& L
         const int v = L.p_idx[e];
         const double* val = L.p_val + e * 18;
         const double* X = L.pose + v * 12;
-        double RE[9], tE[3], q[4];
-        mat_mul(val, X, RE);
-        mat_vec(val, X + 9, tE);
-        tE[0] += val[9]; tE[1] += val[10]; tE[2] += val[11];
-        mat_to_quat(RE, q);
-        quat_normalize_sign(q);
-        const double err[6] = {tE[0], tE[1], tE[2], q[1], q[2], q[3]};
+        double err[6], J[36];   // J = blockdiag(RE, Q)
+        prior_terms<FULL>(val, X, err, J);
         double chi = 0.0;
         const double* Wf = PINFO ? a.p_info + ((size_t)inst * a.caps.np_max + e) * 36 : nullptr;
         double We[6];   // PINFO: W e
@@ -247,24 +242,13 @@ __device__ __forceinline__ void evaluate_edges(const WindowArgs& a, const Lds& L
                 We[i] = r;
                 chi += err[i] * r;
             }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) chi += err[i] * (val[12 + i] * err[i]);
-        }
+        } else chi = prior_diag_chi(val + 12, err);
         rsum += chi;  // not robust
         csum += chi;
         if (FULL && PINFO) {
+            // W full (window_device.h: prior_full_hessian, shared with the envelope covariance pass); the record keeps the same 21 + 6
+            // entries as the diagonal form's, so nothing after it knows the difference
             double* rec = L.prec + e * PREC;
-            double J[36];
-#pragma unroll
-            for (int i = 0; i < 36; ++i) J[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
-            quat_right_jac(q, 1.0, J, 6);
-            // J = blockdiag(RE, Q) as below, W full (window_device.h: prior_full_hessian, shared with the envelope covariance pass); the
-            // record keeps the same 21 + 6 entries, so nothing after it knows the difference
             prior_full_hessian(J, Wf, rec);
 #pragma unroll
             for (int r = 0; r < 6; ++r) {
@@ -275,38 +259,10 @@ __device__ __forceinline__ void evaluate_edges(const WindowArgs& a, const Lds& L
                 rec[21 + r] = bb;
             }
         }
-        if (FULL && !PINFO) {
-            double* rec = L.prec + e * PREC;
-            double J[36];
-#pragma unroll
-            for (int i = 0; i < 36; ++i) J[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) J[i * 6 + j] = RE[i * 3 + j];
-            quat_right_jac(q, 1.0, J, 6);
-            const double* W = val + 12;
-            // J = blockdiag(RE, Q): row i of the Jacobian touches columns of its own 3-block only, so entry (r, cc) of
-            // J^T W J is non-zero only inside a diagonal 3-block (IEEE arithmetic cannot drop 0 * x by itself)
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-#pragma unroll
-                for (int cc = 0; cc <= r; ++cc) {
-                    double h = 0.0;
-                    if ((r < 3) == (cc < 3)) {
-#pragma unroll
-                        for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) h += J[i * 6 + r] * W[i] * J[i * 6 + cc];
-                    }
-                    rec[r * (r + 1) / 2 + cc] = h;
-                }
-                double bb = 0.0;
-#pragma unroll
-                for (int i = (r < 3 ? 0 : 3); i < (r < 3 ? 3 : 6); ++i) bb += J[i * 6 + r] * (-W[i] * err[i]);
-                rec[21 + r] = bb;
-            }
-        }
+        if (FULL && !PINFO) prior_diag_products(J, val + 12, err, L.prec + e * PREC);
     }
     // ---- binary SE3 edges ---------------------------------------------------------------------------------------
+    // (kept written out — must equal se3_edge_device.h: chain_se3_terms, statement for statement: DESIGN.md §4)
     for (int e = lane; e < ns; e += NT) {
         const int32_t* idx = L.s_idx + e * 4;
         const double* val = L.s_val + e * 48;

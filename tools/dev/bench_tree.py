@@ -9,6 +9,7 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 wb, graphs, anchors, T = bw.build_pose64(B, np.random.default_rng(7), n_graphs=0)
 for jac in ("analytic", "numeric"):
     s = la.WindowSolver(anchors, B, *wb.caps, maximum_iteration=10, bw_max=8, jacobian=jac)
+    if len(sys.argv) > 2: s.set_option("tree", int(sys.argv[2]))   # 2: tree_lm_kernel
     s.upload(wb)
     s.solve_resident()
     s.timing_begin(3)
