@@ -337,6 +337,28 @@ int loc_window_last_host_timing(const loc_window* w, double* validate_topology_r
 int loc_window_upload(loc_window* w, int64_t n_instances, const int32_t* counts, const double* poses,
                       const int32_t* r_idx, const double* r_val, const int32_t* p_idx, const double* p_val,
                       const int32_t* s_idx, const double* s_val);
+/* loc_window_upload from DEVICE arrays ("Upload from device arrays"): the layouts are loc_window_upload's, every array is a device
+ * array at the handle's capacities, alive and unchanged until the call returns, and none aliases the handle's own arrays (loc_window_poses_device
+ * ...).  Nothing of the batch passes through host memory: one HIP pass on hip_stream (NULL = the handle's own) admits every window — the shape
+ * check loc_window_upload runs on CPU threads, the same checks in the same order — and scans the structure of the chain family; the host reads
+ * back one small record.  admit_dev: int32 [n] or NULL; window b's code: 0 admitted, 1 counts exceed capacities, 2 / 3 range edge (vertex index /
+ * poses further apart than bw_max), 4 prior edge vertex index, 5 / 6 SE3 edge (as 2 / 3); written for every window, admitted batch or not.
+ * A batch with a refused window is LOC_ERR_INVALID (loc_last_error: loc_window_upload's words for the code of the LOWEST refused window, and
+ * that window's index): nothing is copied, and the previous resident batch stays exactly as it was and still solves.  An admitted batch is
+ * copied device-to-device, and the handle is in the state loc_window_upload of the same arrays would have left — every resident entry works
+ * unchanged — with one difference: only the chain family's verdicts (LOC_WINDOW_KERNEL_CHAIN3 / _WAVE3, _WAVE6, _WAVE6S, _CHAIN) are taken on the
+ * device.  A forest- or arrowhead-shaped batch (whose schedule / packed records loc_window_upload builds on the host) solves on the general
+ * kernel, correctly; its covariances are classified by the first covariance call as for any upload.
+ * Synchronisation: hip_stream is synchronised ONCE for the record (work the caller queued on it before the call — a kernel that writes the
+ * arrays — is seen), and an admitted batch waits for the previous batch's resident work and for its own copies: like loc_window_upload the call
+ * returns when the arrays are free again.  The host copies of the integer tables (the counts, and the mirror of option "resident_slide") are
+ * fetched from the device by the first entry that reads them.
+ * Timing: the pass's two launches are bracketed by the events loc_window_last_covariance_ms reads, as the slides' launches are.  After the
+ * call — a REFUSED one included — loc_window_last_covariance_ms reports the admit pass, no longer the previous batch's last covariance or
+ * slide launch: read that figure before calling. */
+int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n_instances, const void* counts_dev, const void* poses_dev,
+                          const void* r_idx_dev, const void* r_val_dev, const void* p_idx_dev, const void* p_val_dev,
+                          const void* s_idx_dev, const void* s_val_dev, void* admit_dev);
 int loc_window_solve_resident(loc_window* w, void* hip_stream);
 int loc_window_download(loc_window* w, double* poses, double* result);
 void* loc_window_poses_device(loc_window* w);   /* double [B][nv_max][12] */

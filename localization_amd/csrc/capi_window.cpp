@@ -12,6 +12,7 @@
 #include "capi_host.h"
 #include "message_rows.h"
 #include "slide_plain_admit.h"
+#include "window_admit.h"
 #include "window_dispatch.h"
 #include "window_kernel.h"
 #include "window_layouts.h"
@@ -115,6 +116,9 @@ struct loc_window {
     int n_antenna = 0, antenna_cap = 0;
     double* d_antenna = nullptr;
     char* d_msg_rows = nullptr;
+    // loc_window_upload_dev: the admit pass's device block [flags u64 [B] | kAdmitMaxWaves partial records | the record] and the record's page-locked copy
+    char* d_admit = nullptr;
+    locamd::WindowAdmitRecord* h_admit_record = nullptr;
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -147,11 +151,12 @@ int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
     void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws,
-                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows};
+                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows, w->d_admit};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
+    if (w->h_admit_record) (void)hipHostFree(w->h_admit_record);
     w->timer.destroy(); w->pairs.destroy(); w->slide.destroy();
     for (hipEvent_t e : {w->ev0, w->ev1, w->resident_done, w->cov_ev0, w->cov_ev1}) if (e) (void)hipEventDestroy(e);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -229,9 +234,11 @@ static int wait_resident(loc_window* w) {
     return LOC_OK;
 }
 
-// After loc_window_slide_resident_dev the device holds the only copy of the slid counts and index tables.  Whoever reads the host's mirror
-// (res.counts, res.mir_ridx, res.mir_pidx, res.min_anchors) asks here first: waits for the resident work, fetches counts, r_idx and p_idx,
-// recomputes the largest anchor referenced.  Nothing to do (and no wait) while the mirror is current.
+// After loc_window_slide_resident_dev — and after loc_window_upload_dev, which copies no integer table to the host — the device holds the only
+// copy of the counts and index tables.  Whoever reads the host's copies (res.counts, res.mir_ridx, res.mir_pidx, res.min_anchors) asks here
+// first: waits for the resident work, fetches counts and, where the batch has a mirror (option "resident_slide" at its upload), r_idx and p_idx,
+// and recomputes the largest anchor referenced from them.  A batch without a mirror fetches counts alone: only loc_window_upload_dev leaves such
+// a batch stale, and its min_anchors came from the admit pass's record.  Nothing to do (and no wait) while the copies are current.
 static int refresh_mirror(loc_window* w) {
     Resident& R = w->res;
     if (!R.mirror_stale) return LOC_OK;
@@ -240,9 +247,11 @@ static int refresh_mirror(loc_window* w) {
     const locamd::WindowCaps& c = w->caps;
     const size_t N = (size_t)R.n;
     LOC_HIP(hipMemcpy(R.counts.data(), w->dev.t[kCounts], N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (c.nr_max) LOC_HIP(hipMemcpy(R.mir_ridx.data(), w->dev.t[locamd::kRIdx], N * c.nr_max * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (c.np_max) LOC_HIP(hipMemcpy(R.mir_pidx.data(), w->dev.t[locamd::kPIdx], N * c.np_max * sizeof(int32_t), hipMemcpyDeviceToHost));
-    R.min_anchors = locamd::max_anchor_referenced(c, R.n, R.counts.data(), R.mir_ridx.data());
+    if (R.mirror_valid) {
+        if (c.nr_max) LOC_HIP(hipMemcpy(R.mir_ridx.data(), w->dev.t[locamd::kRIdx], N * c.nr_max * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (c.np_max) LOC_HIP(hipMemcpy(R.mir_pidx.data(), w->dev.t[locamd::kPIdx], N * c.np_max * sizeof(int32_t), hipMemcpyDeviceToHost));
+        R.min_anchors = locamd::max_anchor_referenced(c, R.n, R.counts.data(), R.mir_ridx.data());
+    }
     R.mirror_stale = false;
     return LOC_OK;
 }
@@ -284,17 +293,23 @@ int loc_window_set_anchors(loc_window* w, int32_t n_anchors, const double* ancho
     return upload_anchors(w, n_anchors, anchors);
 }
 
-// host-side shape check: a bad index would fault the GPU
-static int validate_instances(const loc_window* w, const locamd::HostBatch& b) {
+// the checks of a batch's arguments that read no table (b's pointers are looked at, never followed: host or device arrays alike)
+static int validate_arguments(const loc_window* w, const locamd::HostBatch& b) {
     if (!w || !b.counts || !b.poses) return locamd_fail(LOC_ERR_INVALID, "window solve arguments");
     if (b.n <= 0 || b.n > w->B) return locamd_fail(LOC_ERR_INVALID, "n_instances");
     if (w->opt.has_pinfo && b.n > w->n_pinfo) return locamd_fail(LOC_ERR_INVALID, "n_instances: more windows than loc_window_set_prior_information described");
     const locamd::WindowCaps& c = w->caps;
     if ((c.nr_max && (!b.r_idx || !b.r_val)) || (c.np_max && (!b.p_idx || !b.p_val)) || (c.ns_max && (!b.s_idx || !b.s_val)))
         return locamd_fail(LOC_ERR_INVALID, "missing edge arrays");
-    static const char* const kWhat[] = {nullptr, "counts exceed capacities", "range edge vertex index", "range edge couples poses further apart than bw_max",
-                                        "prior edge vertex index", "SE3 edge vertex index", "SE3 edge couples poses further apart than bw_max"};
-    if (const int bad = locamd::check_instances(c, w->n_anchors, b)) return locamd_fail(LOC_ERR_INVALID, kWhat[bad]);
+    return LOC_OK;
+}
+// the words of check_instances' / window_admit.h's codes
+static const char* const kInstanceCheck[] = {nullptr, "counts exceed capacities", "range edge vertex index", "range edge couples poses further apart than bw_max",
+                                             "prior edge vertex index", "SE3 edge vertex index", "SE3 edge couples poses further apart than bw_max"};
+// host-side shape check: a bad index would fault the GPU
+static int validate_instances(const loc_window* w, const locamd::HostBatch& b) {
+    if (int rc = validate_arguments(w, b)) return rc;
+    if (const int bad = locamd::check_instances(w->caps, w->n_anchors, b)) return locamd_fail(LOC_ERR_INVALID, kInstanceCheck[bad]);
     return LOC_OK;
 }
 
@@ -712,6 +727,69 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
         R.cov = CovKind::Arrow;
         S.cov_list_cap = S.aux.arrow_list_cap;
     } else R.cov = CovKind::Unclassified;
+    R.n = n;
+    return LOC_OK;
+}
+
+// The same from the caller's DEVICE arrays ("Upload from device arrays"): window_admit_kernel.hip admits every window and scans
+// the chain family's structure on hip_stream, the host reads back one record (the call's ONE synchronisation of that stream), and an admitted
+// batch is copied device-to-device.  A refused batch copies nothing and leaves the previous resident batch as it was.  The host copies of the
+// integer tables are not made: they are sized and marked stale (refresh_mirror).
+int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void* counts_dev, const void* poses_dev, const void* r_idx_dev, const void* r_val_dev,
+                          const void* p_idx_dev, const void* p_val_dev, const void* s_idx_dev, const void* s_val_dev, void* admit_dev) {
+    const locamd::HostBatch b{n, (const double*)poses_dev, (const int32_t*)counts_dev, (const double*)r_val_dev, (const double*)p_val_dev, (const double*)s_val_dev,
+                              (const int32_t*)r_idx_dev, (const int32_t*)p_idx_dev, (const int32_t*)s_idx_dev};
+    if (int rc = validate_arguments(w, b)) return rc;
+    const locamd::WindowCaps& c = w->caps;
+    hipStream_t st;
+    if (int rc = resident_stream(w, hip_stream, false, st)) return rc;
+    const size_t B = (size_t)w->B;
+    // the admit block: flags [B] | kAdmitMaxWaves partial records | the record (every part a multiple of 8 bytes)
+    const size_t at_partial = B * sizeof(uint64_t), at_record = at_partial + (size_t)locamd::kAdmitMaxWaves * sizeof(locamd::WindowAdmitRecord);
+    if (!w->d_admit) LOC_HIP(hipMalloc((void**)&w->d_admit, at_record + sizeof(locamd::WindowAdmitRecord)));
+    if (!w->h_admit_record) LOC_HIP(hipHostMalloc((void**)&w->h_admit_record, sizeof(locamd::WindowAdmitRecord), hipHostMallocDefault));
+    locamd::WindowAdmitArgs a{};
+    a.counts = b.counts; a.poses = b.poses; a.r_idx = b.r_idx; a.r_val = b.r_val; a.p_idx = b.p_idx; a.p_val = b.p_val; a.s_idx = b.s_idx;
+    a.admit = (int32_t*)admit_dev; a.flags = (uint64_t*)w->d_admit;
+    a.partial = (locamd::WindowAdmitRecord*)(w->d_admit + at_partial); a.record = (locamd::WindowAdmitRecord*)(w->d_admit + at_record);
+    a.n_anchors = w->n_anchors; a.B = n; a.caps = c;
+    // (the pass reads the caller's arrays and writes the handle's admit block alone: no resident array, so it does not wait for resident work)
+    // (between cov_ev0 and cov_ev1, as the slides' launches are: loc_window_last_covariance_ms reports the pass's two launches)
+    LOC_HIP(hipEventRecord(w->cov_ev0, st));
+    LOC_HIP(locamd::launch_window_admit(a, st));
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    w->cov_pending = true;
+    LOC_HIP(hipMemcpyAsync(w->h_admit_record, a.record, sizeof(locamd::WindowAdmitRecord), hipMemcpyDeviceToHost, st));
+    LOC_HIP(hipStreamSynchronize(st));
+    const locamd::WindowAdmitRecord rec = *w->h_admit_record;
+    if (rec.first_bad != locamd::kWinNoneRefused) {
+        const int code = rec.code >= 1 && rec.code <= 6 ? rec.code : 1;
+        char text[160];
+        std::snprintf(text, sizeof(text), "%s (window %lld)", kInstanceCheck[code], rec.first_bad);
+        return locamd_fail(LOC_ERR_INVALID, text);
+    }
+    // as loc_window_upload from here: a resident launch of the previous batch may still read what the copies below overwrite
+    LOC_HIP(hipStreamSynchronize(w->stream));
+    if (int rc = wait_resident(w)) return rc;
+    drop_resident(w);
+    Resident& R = w->res;
+    if (!w->d_poses_in) LOC_HIP(hipMalloc((void**)&w->d_poses_in, B * locamd::table_bytes(c, kPoses)));
+    LOC_HIP(copy_tables(c, (size_t)n, uploaded_tables(w).t, b.tables().t, hipMemcpyDeviceToDevice, &st));
+    LOC_HIP(hipStreamSynchronize(st));   // (the call returns synchronously, like loc_window_upload: the caller's arrays are free again)
+    const int topology = locamd::topology_from_flags(w->opt, w->fits, locamd::window_batch_flags(rec));
+    R.min_anchors = rec.max_anchor;
+    R.counts.assign((size_t)n * 4, 0);
+    if (w->opt_slide) {
+        R.mir_ridx.assign((size_t)n * c.nr_max * 2, 0);
+        R.mir_pidx.assign((size_t)n * c.np_max, 0);
+        R.mirror_valid = true;
+    }
+    R.mirror_stale = true;   // (refresh_mirror: the first reader of counts or the mirror fetches them)
+    R.topology = topology;
+    R.skip = locamd::structured_pinfo(w->opt);
+    if (topology == LOC_WINDOW_KERNEL_CHAIN3) R.cov = CovKind::Chain3;
+    else if (topology == LOC_WINDOW_KERNEL_GENERAL) R.cov = CovKind::Unclassified;
+    else R.cov = CovKind::Chain6;
     R.n = n;
     return LOC_OK;
 }

@@ -89,6 +89,15 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
     return {LOC_WINDOW_KERNEL_GENERAL, hit};
 }
 
+// batch_topology's chain block on the flags of a batch no host pass has seen (window_dispatch.h); nothing else is decided here
+int topology_from_flags(const DispatchOpts& o, const DispatchFits& f, const WindowBatchFlags& b) {
+    if (!b.chain) return LOC_WINDOW_KERNEL_GENERAL;
+    if (structured_pinfo(o) ? b.translation_only_skip : b.translation_only) return LOC_WINDOW_KERNEL_CHAIN3;
+    if (b.single_pairs && f.wave6) return LOC_WINDOW_KERNEL_WAVE6;
+    if (b.se3_pairs && f.wave6_se3) return LOC_WINDOW_KERNEL_WAVE6S;
+    return LOC_WINDOW_KERNEL_CHAIN;
+}
+
 static int pick_plain(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology);
 
 int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology) {

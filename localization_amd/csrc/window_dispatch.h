@@ -5,6 +5,7 @@
 // refuses by the handle's state alone, in which order and with which words, is resident_refusal: a new resident entry is registered in
 // ResidentEntry and gets its line there.
 #pragma once
+#include "window_admit.h"
 #include "window_structure.h"
 
 namespace locamd {
@@ -74,6 +75,12 @@ struct TopoCache {
 };
 struct Topology { int kind; bool cached; };   // LOC_WINDOW_KERNEL_* by structure; the verdict came from the cache
 Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, WinAux& aux, TopoCache* tc);
+// The chain family of that verdict from a batch's reduced flags (window_admit.h: what window_admit_kernel.hip leaves of a batch uploaded from
+// device arrays, loc_window_upload_dev): batch_topology's `if (chain)` block restated — LOC_WINDOW_KERNEL_CHAIN3 (structured_pinfo(o) chooses
+// which of the two translation-only flags is read), _WAVE6, _WAVE6S, _CHAIN.  Every other batch is _GENERAL: the forest and arrowhead verdicts
+// are OUT OF SCOPE here — their schedule and packed records are built on the host from host tables — so a forest- or arrowhead-shaped batch
+// uploaded from device arrays solves on the general kernel, correctly; loc_window_upload serves a caller who wants those kernels.
+int topology_from_flags(const DispatchOpts& o, const DispatchFits& f, const WindowBatchFlags& b);
 
 // the structure the host path's own forest schedule (its cov_aux) was built for, device copy included
 struct SchedKey {

@@ -264,6 +264,24 @@ struct PathArgs {
 };
 hipError_t launch_window_path(const PathArgs& a, hipStream_t stream);
 
+// the admission and the chain-family structure scan of a batch in the caller's DEVICE arrays (window_admit_kernel.hip; DESIGN.md §2, "Upload
+// from device arrays"): one wave per window applies window_admit.h's rule and writes admit[b] (may be nullptr) and flags[b]; each wave leaves
+// one partial record and a second launch of one wave merges them into *record.  All device arrays at the capacities `caps`; the host has
+// checked NOTHING of their contents.  partial: kAdmitMaxWaves records.  s_val is not read and not passed.
+struct WindowAdmitRecord;   // window_admit.h
+constexpr int kAdmitMaxWaves = 8192;
+struct WindowAdmitArgs {
+    const int32_t* counts; const double* poses;
+    const int32_t* r_idx; const double* r_val; const int32_t* p_idx; const double* p_val; const int32_t* s_idx;
+    int32_t* admit; uint64_t* flags;                      // [B] window_admit's code; [B] window_structure_flags' word (0 for a refused window)
+    WindowAdmitRecord* partial; WindowAdmitRecord* record;
+    int n_anchors;
+    long long B;
+    WindowCaps caps;
+};
+int window_admit_waves(long long B);   // the waves launch_window_admit starts for B windows (= the partial records it writes)
+hipError_t launch_window_admit(const WindowAdmitArgs& a, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

@@ -184,6 +184,21 @@ class WindowSolver(_lib.Handle):
                                        wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp)))
         self._resident = wb.B
 
+    def upload_dev(self, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val, n=None, admit=None, stream=None):
+        """upload() from device memory (loc_window_upload_dev): the eight tables in upload()'s layouts at the handle's capacities — counts int32
+        [n][4], poses float64 [n][nv_max][12], r_idx int32 [n][nr_max][2], r_val float64 [n][nr_max][5], p_idx int32 [n][np_max], p_val float64
+        [n][np_max][18], s_idx int32 [n][ns_max][4], s_val float64 [n][ns_max][48] — each a device pointer, an object with data_ptr() or None (a
+        table under a capacity of 0).  n: the windows (None: counts.shape[0]).  admit: int32 [n] on the device or None; window b's code (0
+        admitted, 1 .. 6 the check it fails).  Every window is admitted and the chain family's structure scanned by a HIP pass on stream (a torch
+        stream; None: the handle's own); a batch with a refused window raises (LOC_ERR_INVALID; the error names the check and the lowest refused
+        window) and leaves the previous resident batch as it was.  Returns when the arrays are free again, like upload().  The handle's tables of
+        endpoint-1 lever arms / full information matrices stay as they are.  Plumbing only: the library checks everything."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        n = int(counts.shape[0]) if n is None else int(n)
+        st = None if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self.L.loc_window_upload_dev(self.h, st, n, *(ptr(t) for t in (counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val)), ptr(admit)))
+        self._resident = n
+
     def solve_resident(self, stream=None):
         check(self.L.loc_window_solve_resident(self.h, stream))
 
