@@ -31,9 +31,13 @@
 //     block column after the other;
 //   * small windows keep everything in LDS, larger ones in a per-instance slice of an HBM workspace (index tables in LDS);
 //   * all LM control flow is uniform over the instance's threads (sums are DPP reductions, combined across the waves in wave
-//     order: every thread holds the same bits).
+//     order: every thread holds the same bits);
+//   * 6x6 block steps (the Cholesky factor of a diagonal block, row solves against it, its store, block products) are stated in
+//     window_block_device.h with their rounding order and pivot rule: the SKYLINE sweep and the root supernode take theirs from
+//     there; the level-by-level routines call four of them and still write the rest out.
 #include "se3_edge_device.h"
 #include "window_layouts.h"
+#include "window_block_device.h"
 #include "lm_damping.h"
 
 
@@ -1403,14 +1407,7 @@ __device__ __forceinline__ bool factor_and_solve(const Lds& L, int lane, int n, 
                     double li[6];
 #pragma unroll
                     for (int k = 0; k < 6; ++k) li[k] = ri[roff + rs * (6 * K + k)];
-                    const double* rj = L.Ls + jb + 36 * K;  // the 6x6 block (rows c0.., columns 6K..) is contiguous: [k][c]
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        double acc = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 6; ++k) acc = __builtin_fma(li[k], rj[6 * k + c], acc);
-                        S[c] -= acc;
-                    }
+                    wb_row_block_sub(li, L.Ls + jb + 36 * K, S);  // the 6x6 block (rows c0.., columns 6K..) is contiguous: [k][c]
                 }
             }
             if (base == 0) {
@@ -1421,50 +1418,17 @@ __device__ __forceinline__ bool factor_and_solve(const Lds& L, int lane, int n, 
                 }
                 __syncthreads();
                 bool ok = true;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    double dj = L.blk[j * 6 + j];
-#pragma unroll
-                    for (int k = 0; k < j; ++k) dj = __builtin_fma(-G[j][k], G[j][k], dj);
-                    ok = ok && (dj > 0.0) && (dj < DBL_MAX);
-                    double g, igj;
-                    sqrt_and_rsqrt(fmax(dj, 1e-300), g, igj);
-                    igj = __builtin_fma(igj, __builtin_fma(-g, igj, 1.0), igj);  // one Newton step: 1/g to ~1e-16
-                    G[j][j] = g;
-                    ig[j] = igj;
-#pragma unroll
-                    for (int i2 = j + 1; i2 < 6; ++i2) {
-                        double v = L.blk[i2 * 6 + j];
-#pragma unroll
-                        for (int k = 0; k < j; ++k) v = __builtin_fma(-G[i2][k], G[j][k], v);
-                        G[i2][j] = v * ig[j];
-                    }
-                }
+                wb_chol_left([&](int r, int c) { return L.blk[r * 6 + c]; }, G, ig, ok);
                 if (!ok) return false;  // uniform: every lane factored the same block
             }
             // (c) finish the rows
             if (part && (is_rhs || idx >= 6)) {
-                double x[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    double v = S[c];
-#pragma unroll
-                    for (int k = 0; k < c; ++k) v = __builtin_fma(-x[k], G[c][k], v);
-                    x[c] = v * ig[c];
-                }
+                wb_forward_row(S, G, ig);
                 double* dst = is_rhs ? L.yrow : L.Ls;
 #pragma unroll
-                for (int c = 0; c < 6; ++c) dst[roff + rs * (c0 + c)] = x[c];
+                for (int c = 0; c < 6; ++c) dst[roff + rs * (c0 + c)] = S[c];
             } else if (base == 0 && idx < 6) {
-                // (static indices only: a runtime row index would push G into scratch memory)
-#pragma unroll
-                for (int rr = 0; rr < 6; ++rr) {
-                    if (idx == rr) {
-#pragma unroll
-                        for (int c = 0; c < rr; ++c) L.Ls[roff + 6 * (c0 + c)] = G[rr][c];
-                        L.diagL[row] = ig[rr];  // the INVERSE pivot: back-substitution multiplies
-                    }
-                }
+                wb_store_factor_row(idx, G, ig, L.Ls + roff + 6 * c0, 6, L.diagL + row);
             }
         }
         __syncthreads();
@@ -1478,28 +1442,14 @@ __device__ __forceinline__ bool factor_and_solve(const Lds& L, int lane, int n, 
         double yj[6], x[6], G[6][6], igd[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) yj[c] = L.yrow[c0 + c];
-#pragma unroll
-        for (int rr = 0; rr < 6; ++rr) {
-            igd[rr] = L.diagL[c0 + rr];
-#pragma unroll
-            for (int c = 0; c < rr; ++c) G[rr][c] = L.Ls[jb + 6 * (c0 + c) + rr];
-        }
-#pragma unroll
-        for (int rr = 5; rr >= 0; --rr) {
-            double v = yj[rr];
-#pragma unroll
-            for (int s2 = rr + 1; s2 < 6; ++s2) v = __builtin_fma(-G[s2][rr], x[s2], v);
-            x[rr] = v * igd[rr];
-        }
+        wb_load_factor(L.Ls + jb + 6 * c0, L.diagL + c0, G, igd);
+        wb_back_solve_gather(yj, G, igd, x);
         if (lane < 6) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) if (lane == c) L.x[c0 + c] = x[c];
         }
         for (int k = fJ6 + lane; k < c0; k += 64) {
-            double acc = L.yrow[k];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) acc = __builtin_fma(-L.Ls[jb + 6 * k + c], x[c], acc);
-            L.yrow[k] = acc;
+            L.yrow[k] = wb_dot_fms(L.Ls + jb + 6 * k, x, L.yrow[k]);
         }
         __syncthreads();
     }
@@ -1631,29 +1581,14 @@ __device__ __forceinline__ bool root_factor_and_solve(const Lds& L, int tid, int
         for (int c = 0; c < 6; ++c)
 #pragma unroll
             for (int r = c; r < 6; ++r) A[r][c] = S[(j0 + r) * n + j0 + c];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const double g = pivot_rsqrt(A[j][j]);
-            ig[j] = g;
-#pragma unroll
-            for (int i2 = j + 1; i2 < 6; ++i2) A[i2][j] *= g;
-#pragma unroll
-            for (int i2 = j + 1; i2 < 6; ++i2)
-#pragma unroll
-                for (int c = j + 1; c <= i2; ++c) A[i2][c] = __builtin_fma(-A[i2][j], A[c][j], A[i2][c]);
-        }
-        ok = ok && (((ig[0] + ig[1]) + (ig[2] + ig[3])) + (ig[4] + ig[5]) < DBL_MAX);   // (a pivot <= 0 or not finite: NaN / inf)
+        wb_chol_right(A, ig);
+        ok = ok && wb_inverse_pivots_finite(ig);
         const int i = j0 + 6 + tid;   // rows below the block, the right-hand side last
         if (i <= n) {
             double sv[6];
 #pragma unroll
             for (int c = 0; c < 6; ++c) sv[c] = S[i * n + j0 + c];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                sv[c] *= ig[c];
-#pragma unroll
-                for (int c2 = c + 1; c2 < 6; ++c2) sv[c2] = __builtin_fma(-sv[c], A[c2][c], sv[c2]);
-            }
+            wb_forward_row_scatter(sv, A, ig);
 #pragma unroll
             for (int c = 0; c < 6; ++c) S[i * n + j0 + c] = sv[c];
         }
@@ -1669,10 +1604,7 @@ __device__ __forceinline__ bool root_factor_and_solve(const Lds& L, int tid, int
         const int c = j0 + 6 + (tid & 63);
         for (int i2 = j0 + 6 + (tid >> 6); i2 <= n; i2 += NW) {
             if (c <= i2 && c < n) {
-                double acc = S[i2 * n + c];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) acc = __builtin_fma(-S[i2 * n + j0 + k], S[c * n + j0 + k], acc);
-                S[i2 * n + c] = acc;
+                S[i2 * n + c] = wb_dot_fms(S + i2 * n + j0, S + c * n + j0, S[i2 * n + c]);
             }
         }
         __syncthreads();
@@ -1762,14 +1694,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         G[r][r] += lambda;
                         y[r] = L.b[6 * J + r];
                     }
-                    if (GLOBAL_A && has_pushed_child<W>(L, J)) {
-#pragma unroll
-                        for (int r = 0; r < 6; ++r) {
-#pragma unroll
-                            for (int c = 0; c <= r; ++c) G[r][c] -= L.As[28 * J + r * (r + 1) / 2 + c];
-                            y[r] -= L.As[28 * J + 21 + r];
-                        }
-                    }
+                    if (GLOBAL_A && has_pushed_child<W>(L, J)) wb_sub_update(G, y, L.As + 28 * J);
                     LOCAMD_SUB(0);
                     int kb = -1;
                     for (int w = 0; w < W; ++w) {
@@ -1779,16 +1704,10 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                             m &= m - 1;
                             ++kb;
                             if (pushed<W>(L, K)) {
-                                if (!GLOBAL_A) {
-#pragma unroll
-                                    for (int r = 0; r < 6; ++r) {
-#pragma unroll
-                                        for (int c = 0; c <= r; ++c) G[r][c] -= L.Us[28 * K + r * (r + 1) / 2 + c];
-                                        y[r] -= L.Us[28 * K + 21 + r];
-                                    }
-                                }
+                                if (!GLOBAL_A) wb_sub_update(G, y, L.Us + 28 * K);
                                 continue;
                             }
+                            // (the lower triangle of B B^T and B y_K, then wb_sub_update's subtraction, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
                             const double* blk = L.Ls + rowJ + 36 * kb;
                             double bl[36], yk[6];
 #pragma unroll
@@ -1812,6 +1731,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         }
                     }
                     LOCAMD_SUB(1);
+                    // (wb_chol_left in place and wb_forward_row on y, with the factor's stores between them, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
 #pragma unroll
                     for (int j = 0; j < 6; ++j) {
                         double dj = G[j][j];
@@ -1862,6 +1782,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                             m &= m - 1;
                             const double* bki = L.Ls + rowi + 36 * row_rank<W>(L, i, K);
                             const double* bkj = L.Ls + rowJ + 36 * row_rank<W>(L, J, K);
+                            // (block times block^T, FMA'd into S: not in window_block_device.h yet)
                             for (int k = 0; k < 6; ++k) {
                                 double li[6], lj[6];
 #pragma unroll
@@ -1873,6 +1794,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                             }
                         }
                         }
+                        // (wb_forward_row for each of the block's six rows, written out; below it the pushed update B B^T, B y — DESIGN.md §2)
 #pragma unroll
                         for (int r = 0; r < 6; ++r) {
 #pragma unroll
@@ -1967,6 +1889,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                     for (int k = 0; k < 6; ++k) li[k] = blk[6 * k + r];
 #pragma unroll
                     for (int q = 0; q < 36; ++q) bj[q] = W > 1 ? blk[q] : 0.0;   // (one-word windows: the products read in place, as measured best there)
+                    // (wb_row_block_sub, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
 #pragma unroll
                     for (int c = 0; c < 6; ++c) {
                         double acc = 0.0;
@@ -2031,6 +1954,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         for (int k = 0; k < 6; ++k) li[k] = bki[6 * k + r];
 #pragma unroll
                         for (int q = 0; q < 36; ++q) bj[q] = W > 1 ? bkj[q] : 0.0;
+                        // (wb_row_block_sub, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
 #pragma unroll
                         for (int c = 0; c < 6; ++c) {
                             double acc = 0.0;
@@ -2071,6 +1995,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         for (int k = 0; k < 6; ++k) li[k] = L.yrow[6 * K + k];
 #pragma unroll
                         for (int q = 0; q < 36; ++q) bj[q] = W > 1 ? bkj[q] : 0.0;
+                        // (wb_row_block_sub, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
 #pragma unroll
                         for (int c = 0; c < 6; ++c) {
                             double acc = 0.0;
@@ -2082,6 +2007,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                     }
                 }
                 // G_J from the raw diagonal block: entry (p, q), p >= q, at dJ + 6 p + q
+                // (wb_chol_left from memory, wb_store_factor_row, wb_forward_row, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
                 double G[6][6], ig[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
@@ -2170,6 +2096,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                     double xi[6];
 #pragma unroll
                     for (int r = 0; r < 6; ++r) xi[r] = L.x[6 * i + r];
+                    // (block^T times vector, summed then subtracted: not in window_block_device.h yet)
 #pragma unroll
                     for (int c = 0; c < 6; ++c) {
                         double acc = 0.0;
@@ -2181,6 +2108,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                 }
                 LOCAMD_SUB3(1);
                 double xs[6];
+                // (wb_back_solve_gather with G and the inverse pivots read in place, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
 #pragma unroll
                 for (int rr = 5; rr >= 0; --rr) {
                     double v = t[rr];
@@ -2340,8 +2268,7 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
                         double av[6], bv[6];
 #pragma unroll
                         for (int k = 0; k < 6; ++k) { av[k] = ap[k * ast]; bv[k] = bp[6 * k]; }
-#pragma unroll
-                        for (int k = 0; k < 6; ++k) out = __builtin_fma(-av[k], bv[k], out);
+                        out = wb_dot_fms(av, bv, out);
                         const int next = rec.ctl >> 8;
                         if (next == 0) break;
                         rec = L.recA[next];
@@ -2381,6 +2308,7 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
                     for (int q = 0; q < 6; ++q) A[q][q] += lambda;
 #pragma unroll
                     for (int j = 0; j < 6; ++j) {
+                        // (wb_chol_right, wb_forward_row_scatter and wb_inverse_pivots_finite, written out: window_block_device.h states the steps, this site does not call them yet — DESIGN.md §2)
                         // (a pivot <= 0 or not finite turns its reciprocal square root into NaN / inf, which the sum below catches)
                         const double g = pivot_rsqrt(A[j][j]);
                         ig[j] = g;
@@ -2425,12 +2353,7 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
             double t[6], G[6][6], ig[6];
 #pragma unroll
             for (int c = 0; c < 6; ++c) t[c] = L.yrow[6 * J + c];
-#pragma unroll
-            for (int c = 0; c < 5; ++c)
-#pragma unroll
-                for (int rr = c + 1; rr < 6; ++rr) G[rr][c] = L.Ls[dJ + 6 * c + rr];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) ig[c] = L.diagL[6 * J + c];
+            wb_load_factor(L.Ls + dJ, L.diagL + 6 * J, G, ig);
             u64 m = plan.colmask;
             bool first = true;
             while (m) {
@@ -2444,18 +2367,14 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
                 for (int q = 0; q < 36; ++q) bv[q] = bk[q];
 #pragma unroll
                 for (int r = 0; r < 6; ++r) xi[r] = L.x[6 * i + r];
+                // (block^T times vector, FMA'd into t: not in window_block_device.h yet)
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
 #pragma unroll
                     for (int c = 0; c < 6; ++c) t[c] = __builtin_fma(-bv[6 * c + r], xi[r], t[c]);
             }
             double xs[6];
-#pragma unroll
-            for (int rr = 5; rr >= 0; --rr) {
-                xs[rr] = t[rr] * ig[rr];
-#pragma unroll
-                for (int q = 0; q < rr; ++q) t[q] = __builtin_fma(-G[rr][q], xs[rr], t[q]);
-            }
+            wb_back_solve_scatter(t, G, ig, xs);
 #pragma unroll
             for (int c = 0; c < 6; ++c) L.x[6 * J + c] = xs[c];
         }

@@ -453,3 +453,115 @@ def prior_base_rows(seed=12):
                 rows.append(np.concatenate([Rz.ravel(), tz, R.ravel(), t]))
                 branches.append(branch_of((Rz @ R).ravel()))
     return np.array(rows), np.array(branches)
+
+
+# ---- the 6x6 block steps of the general window kernel (window_block_device.h) ---------------------------------------------------------------
+# Matrices are 6x6 lists of lists over the number type.
+def mat6(C, rows36):
+    """a 6x6 list of lists from 36 row-major numbers"""
+    return [[C.num(rows36[6 * i + j]) for j in range(6)] for i in range(6)]
+
+
+def chol6(C, A):
+    """The Cholesky factor of the symmetric 6x6 A (its lower triangle is read): G lower with G G^T = A, column by column, and the inverse
+    pivots ig_j = 1 / G_jj"""
+    G = [[C.num(0)] * 6 for _ in range(6)]
+    ig = [None] * 6
+    for j in range(6):
+        d = A[j][j] - sum(G[j][k] * G[j][k] for k in range(j))
+        G[j][j] = C.sqrt(d)
+        ig[j] = 1 / G[j][j]
+        for i in range(j + 1, 6):
+            G[i][j] = (A[i][j] - sum(G[i][k] * G[j][k] for k in range(j))) / G[j][j]
+    return G, ig
+
+
+def chol6_pivots(A36):
+    """the exact (50-digit) pivots d_j = A_jj - sum_k G_jk^2 of the float64 matrix A36 (36 row-major), up to and including the first one
+    that is not positive and finite"""
+    with mpmath.workdps(DPS):
+        A = [[mpmath.mpf(float(A36[6 * i + j])) for j in range(6)] for i in range(6)]
+        G = [[mpmath.mpf(0)] * 6 for _ in range(6)]
+        out = []
+        for j in range(6):
+            d = A[j][j] - sum(G[j][k] * G[j][k] for k in range(j))
+            out.append(d)
+            if not (d > 0 and mpmath.isfinite(d)):
+                break
+            G[j][j] = mpmath.sqrt(d)
+            for i in range(j + 1, 6):
+                G[i][j] = (A[i][j] - sum(G[i][k] * G[j][k] for k in range(j))) / G[j][j]
+        return out
+
+
+def forward_row(C, G, ig, s):
+    """x G^T = s with the factor's inverse pivots given: x_c = (s_c - sum_{k<c} x_k G_ck) ig_c"""
+    x = []
+    for c in range(6):
+        x.append((s[c] - sum(x[k] * G[c][k] for k in range(c))) * ig[c])
+    return x
+
+
+def back_solve(C, G, ig, t):
+    """G^T x = t: x_r = (t_r - sum_{s>r} G_sr x_s) ig_r"""
+    x = [None] * 6
+    for r in range(5, -1, -1):
+        x[r] = (t[r] - sum(G[s][r] * x[s] for s in range(r + 1, 6))) * ig[r]
+    return x
+
+
+def dot_sub(C, a, b, out):
+    return out - sum(x * y for x, y in zip(a, b))
+
+
+def chol_spd_cases(seed=21):
+    """[(class, A 36 row-major)]: J^T J + lambda I with the singular values of J from 1 down to 1e-8, so that the condition number is about
+    1 / lambda (classes 'cond 1e0' .. 'cond 1e12'; lambda I alone: 'cond 1'), and diagonal matrices spanning 1e-12 .. 1e12"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for e in (0, 2, 4, 6, 8, 10, 12):
+        for _ in range(5):
+            U, _ = np.linalg.qr(rng.normal(size=(6, 6)))
+            V, _ = np.linalg.qr(rng.normal(size=(6, 6)))
+            J = U @ np.diag(10.0 ** np.linspace(0, -8, 6)) @ V.T
+            A = J.T @ J + 10.0 ** -e * np.eye(6)
+            out.append((f"cond 1e{e}", ((A + A.T) / 2).ravel()))
+    for lam in (1.0, 1e-3, 7.0):
+        out.append(("cond 1", (lam * np.eye(6)).ravel()))
+    span = 10.0 ** np.array([-12.0, -7, -2, 3, 8, 12])
+    for _ in range(4):
+        out.append(("diagonal", np.diag(rng.permutation(span)).ravel()))
+    return out
+
+
+CHOL_FAIL_KINDS = ("negative", "zero", "inf", "nan")
+
+
+def chol_failing_cases(seed=22):
+    """[(A 36 row-major, position, kind, the same with the pivot put right)]: A = L D L^T with L unit lower triangular with small integer
+    entries and D powers of four, so that A is exact in float64 and its exact pivots ARE the entries of D; the pivot at `position` (0, 3,
+    5) is -4 (negative), 0 (zero), or the diagonal entry itself is +inf / NaN (then so is the pivot).  Every other pivot is at least 1/4."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for p in (0, 3, 5):
+        for kind in CHOL_FAIL_KINDS:
+            for _ in range(2):
+                Lm = np.tril(rng.integers(-2, 3, (6, 6)).astype(np.float64), -1) + np.eye(6)
+                D = 4.0 ** rng.integers(-1, 3, 6)
+                good = Lm @ np.diag(D) @ Lm.T
+                D[p] = {"negative": -4.0, "zero": 0.0}.get(kind, D[p])
+                A = Lm @ np.diag(D) @ Lm.T
+                if kind in ("inf", "nan"):
+                    A[p, p] = np.inf if kind == "inf" else np.nan
+                out.append((A.ravel(), p, kind, good.ravel()))
+    return out
+
+
+def solve_operands(seed=23, n=48):
+    """(random, integer) operand sets for the row solves: G (36 row-major, strict lower triangle used), ig (6), s (6).  The integer set —
+    integer G and s, inverse pivots powers of two — solves exactly in float64"""
+    rng = np.random.default_rng(seed)
+    rnd = np.concatenate([np.tril(rng.normal(size=(n, 6, 6)), -1).reshape(n, 36), rng.uniform(0.5, 2.0, (n, 6)), rng.normal(size=(n, 6)) * 3], axis=1)
+    ints = np.concatenate([np.tril(rng.integers(-3, 4, (n, 6, 6)), -1).reshape(n, 36), 2.0 ** rng.integers(-2, 2, (n, 6)), rng.integers(-8, 9, (n, 6))],
+                          axis=1).astype(np.float64)
+    return rnd, ints

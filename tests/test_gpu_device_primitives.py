@@ -351,3 +351,122 @@ def test_prior_blocks_with_the_error_rotation_in_every_branch(gpu):
     e, acc = rng.normal(size=(n, 3)), rng.normal(size=(n, 3)) * 100
     _hold("prior3_mul_add", _probe("prior3_mul_add", np.concatenate([w6, e, acc], axis=1), 3),
           [P.prior3_mul_add(P.F64, w, x, a) for w, x, a in zip(w6, e, acc)], [P.with_mp(P.prior3_mul_add, w, x, a) for w, x, a in zip(w6, e, acc)])
+
+
+# ---- the 6x6 block steps of the general window kernel (window_block_device.h) -----------------------------------------------------------------
+LOWER = [6 * r + c for r in range(6) for c in range(r)]          # the strict lower triangle of a row-major 6x6
+_flat = lambda M: [x for row in M for x in row]
+_mp = lambda v: [mpmath.mpf(float(x)) for x in v]
+_fl = lambda v: [float(x) for x in v]
+
+
+def _both(f, *args):
+    """f over float64 and at 50 digits; args: flat float64 vectors, 36 long = a row-major matrix"""
+    def conv(C, to):
+        return [P.mat6(C, to(a)) if len(a) == 36 else to(a) for a in args]
+    return f(P.F64, *conv(P.F64, _fl)), P.with_mp(f, *conv(P.MP, _mp))
+
+
+@pytest.mark.parametrize("op", ["wb_chol_left", "wb_chol_right"])
+def test_block_cholesky_by_condition_class(gpu, op):
+    cases = P.chol_spd_cases()
+    A = np.array([a for _, a in cases])
+    dev = _probe(op, A, 43)
+    assert np.all(dev[:, 42] == 1.0), (op, np.flatnonzero(dev[:, 42] != 1.0))
+    if op == "wb_chol_left":   # the register source, in place, is the same function: the same bits
+        assert np.array_equal(_probe("wb_chol_left_in_place", A, 43).view(np.uint64), dev.view(np.uint64))
+    pairs = [_both(P.chol6, a) for a in A]
+    for cls in sorted({c for c, _ in cases}):   # per class, so that the well-conditioned blocks cannot hide behind the others
+        sel = [k for k, (c, _) in enumerate(cases) if c == cls]
+        for name, cols, pick in (("G", LOWER, lambda Gi: [_flat(Gi[0])[q] for q in LOWER]), ("ig", list(range(36, 42)), lambda Gi: Gi[1])):
+            if name == "G" and cls in ("cond 1", "diagonal"):
+                assert not dev[sel][:, LOWER].any()            # nothing below the diagonal of a diagonal matrix
+                continue
+            _hold(f"{op} {cls} {name}", dev[sel][:, cols], [pick(pairs[k][0]) for k in sel], [pick(pairs[k][1]) for k in sel])
+
+
+def test_block_cholesky_flags_every_bad_pivot(gpu):
+    cases = P.chol_failing_cases()
+    A = np.array([a for a, _, _, _ in cases])
+    for op in ("wb_chol_left", "wb_chol_left_in_place", "wb_chol_right"):
+        ok = _probe(op, A, 43)[:, 42]
+        assert not ok.any(), (op, [(p, kind) for (_, p, kind, _), o in zip(cases, ok) if o])
+    # the same L D L^T with that one pivot put right factors: the flag is the pivot's doing
+    good = np.array([g for _, _, _, g in cases])
+    for op in ("wb_chol_left", "wb_chol_right"):
+        assert np.all(_probe(op, good, 43)[:, 42] == 1.0), op
+    # a positive pivot below 1e-300 is factored as 1e-300 by the left-looking form, and is no failure
+    tiny = np.array([np.diag([1.0] * p + [d] + [1.0] * (5 - p)).ravel() for p in (0, 3, 5) for d in (1e-305, 1e-310, 5e-324)])
+    out = _probe("wb_chol_left", tiny, 43)
+    assert np.all(out[:, 42] == 1.0)
+    for row, p in zip(out, [p for p in (0, 3, 5) for _ in range(3)]):
+        assert abs(row[7 * p] / 1e-150 - 1) < 4 * EPS and abs(row[36 + p] / 1e150 - 1) < 4 * EPS, (p, row[7 * p], row[36 + p])
+
+
+@pytest.mark.parametrize("op,ref", [("wb_forward_row", P.forward_row), ("wb_forward_row_scatter", P.forward_row),
+                                    ("wb_back_solve_gather", P.back_solve), ("wb_back_solve_scatter", P.back_solve)])
+def test_block_row_solves(gpu, op, ref):
+    rnd, ints = P.solve_operands()
+    dev = _probe(op, rnd, 6)
+    pairs = [_both(ref, r[:36], r[36:42], r[42:]) for r in rnd]
+    _hold(op, dev, [p[0] for p in pairs], [p[1] for p in pairs])
+    exact = np.array([ref(P.F64, P.mat6(P.F64, r[:36]), _fl(r[36:42]), _fl(r[42:])) for r in ints])
+    assert np.array_equal(_probe(op, ints, 6), exact), op      # integer operands: exact
+    if op == "wb_forward_row_scatter":                          # the same FMAs in the same order per entry: the gather form's bits
+        assert np.array_equal(dev.view(np.uint64), _probe("wb_forward_row", rnd, 6).view(np.uint64))
+
+
+def test_block_factor_row_store_and_load(gpu):
+    rnd, _ = P.solve_operands()
+    G = rnd[:, :36].reshape(-1, 6, 6)
+    want = np.zeros((len(rnd), 42))
+    for r in range(6):
+        for c in range(r):
+            want[:, 6 * c + r] = G[:, r, c]                     # column-major, strictly below the diagonal; everything else untouched
+    want[:, 36:] = rnd[:, 36:42]
+    rows = np.zeros_like(want)
+    for r in range(6):                                          # one lane per row: each call writes its row only
+        part = _probe("wb_store_factor_row", np.concatenate([rnd[:, :42], np.full((len(rnd), 1), float(r))], axis=1), 42)
+        assert np.array_equal(part != 0, np.isin(np.arange(42), [6 * c + r for c in range(r)] + [36 + r])[None, :] & (want != 0)), r
+        rows += part
+    assert np.array_equal(rows, want)
+    back = _probe("wb_load_factor", np.concatenate([rnd[:, :42], np.zeros((len(rnd), 1))], axis=1), 42)
+    assert np.array_equal(back[:, LOWER], rnd[:, LOWER]) and np.array_equal(back[:, 36:], rnd[:, 36:42])
+    assert not np.delete(back[:, :36], LOWER, axis=1).any()   # nothing on or above the diagonal is loaded
+
+
+def test_block_products(gpu):
+    rng = np.random.default_rng(25)
+    n = 48
+    def operands(*widths):
+        return (np.concatenate([rng.normal(size=(n, w)) for w in widths], axis=1),
+                np.concatenate([rng.integers(-9, 10, (n, w)) for w in widths], axis=1).astype(np.float64))
+    T = lambda v: [v[6 * c + r] for r in range(6) for c in range(6)]   # column-major 36 -> row-major 36
+    # name, input widths, outputs, the definition over (C, operands...) with every block given row-major
+    table = [
+        ("wb_dot_fms", (6, 6, 1), 1, lambda C, a, b, o: [P.dot_sub(C, a, b, o[0])], ()),
+        ("wb_row_block_sub", (6, 36, 6), 6, lambda C, li, B, S: [P.dot_sub(C, li, B[c], S[c]) for c in range(6)], (1,)),
+    ]
+    for op, widths, no, f, blocks in table:
+        rnd, ints = operands(*widths)
+        def split(row):
+            parts, at = [], 0
+            for k, w in enumerate(widths):
+                v = row[at:at + w]
+                parts.append(T(v) if k in blocks else v)       # the device's blocks are column-major
+                at += w
+            return parts
+        dev = _probe(op, rnd, no)
+        pairs = [_both(f, *split(r)) for r in rnd]
+        _hold(op, dev, [p[0] for p in pairs], [p[1] for p in pairs])
+        exact = np.array([_both(f, *split(r))[0] for r in ints])
+        assert np.array_equal(_probe(op, ints, no), exact), op
+    # a packed update taken off a diagonal block and its right-hand side: one subtraction per entry, exact to the last bit in float64
+    rows = rng.normal(size=(n, 69))
+    got = _probe("wb_sub_update", rows, 42)
+    want = np.zeros((n, 42))
+    for r in range(6):
+        for c in range(r + 1):
+            want[:, 6 * r + c] = rows[:, 6 * r + c] - rows[:, 42 + r * (r + 1) // 2 + c]
+        want[:, 36 + r] = rows[:, 36 + r] - rows[:, 42 + 21 + r]
+    assert np.array_equal(got, want)

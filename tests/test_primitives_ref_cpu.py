@@ -78,3 +78,49 @@ def test_rodrigues_helper_and_exact_half_turns():
         assert np.allclose(R @ R.T, np.eye(3), atol=1e-15) and abs(np.trace(R) - (1 + 2 * math.cos(math.radians(150)))) < 1e-15
         H = P.half_turn(a)
         assert np.allclose(H @ H, np.eye(3), atol=1e-15) and np.allclose(H @ a, a, atol=1e-15)
+
+
+def test_cholesky_cases_fail_where_they_say_and_by_a_margin_no_rounding_can_close():
+    """the matrices behind the exact comparison of the block Cholesky's ok flag (tests/test_gpu_device_primitives.py): at 50 digits every
+    pivot before the named position is at least 1/4, the named pivot is -4 (at most -1e-3 of the diagonal entry), exactly 0, +inf or NaN, and
+    the repaired matrix has every pivot at least 1/4"""
+    seen = set()
+    for A, p, kind, good in P.chol_failing_cases():
+        seen.add((p, kind))
+        d = P.chol6_pivots(A)
+        assert len(d) == p + 1 and all(x >= 0.25 for x in d[:p]), (p, kind, d)
+        if kind == "negative":
+            assert d[p] == -4 and d[p] <= -1e-3 * abs(A[7 * p]), (p, d[p], A[7 * p])
+        elif kind == "zero":
+            assert d[p] == 0
+        else:
+            assert (d[p] == mpmath.inf) if kind == "inf" else mpmath.isnan(d[p])
+        dg = P.chol6_pivots(good)
+        assert len(dg) == 6 and all(x >= 0.25 for x in dg), (p, kind, dg)
+    assert seen == {(p, k) for p in (0, 3, 5) for k in P.CHOL_FAIL_KINDS}
+
+
+def test_positive_definite_cases_span_the_condition_numbers_and_keep_their_pivots_clear_of_rounding():
+    conds = {}
+    for cls, A in P.chol_spd_cases():
+        d = P.chol6_pivots(A)
+        assert len(d) == 6 and all(x > 1e-13 * abs(A[7 * j]) for j, x in enumerate(d)), (cls, d)   # (rounding moves a pivot by ~1e-15 of it)
+        conds.setdefault(cls, []).append(np.linalg.cond(A.reshape(6, 6)))
+    assert max(conds["cond 1"]) == 1.0 and min(conds["cond 1e12"]) > 1e11 and max(conds["cond 1e0"]) < 3
+    assert all(c == 1e24 or abs(c / 1e24 - 1) < 1e-9 for c in conds["diagonal"])
+
+
+def test_block_step_references_agree_between_float64_and_50_digits():
+    rnd, ints = P.solve_operands()
+    for row in list(rnd[:8]) + list(ints[:8]):
+        G, ig, s = row[:36], [float(x) for x in row[36:42]], [float(x) for x in row[42:]]
+        for f in (P.forward_row, P.back_solve):
+            a = f(P.F64, P.mat6(P.F64, G), ig, s)
+            with mpmath.workdps(P.DPS):
+                b = f(P.MP, P.mat6(P.MP, [float(x) for x in G]), [mpmath.mpf(x) for x in ig], [mpmath.mpf(x) for x in s])
+            assert P.to_f64_err(a, b).max() <= 1e-12 * max(abs(float(x)) for x in b)
+    for cls, A in P.chol_spd_cases()[::6]:
+        G, ig = P.chol6(P.F64, P.mat6(P.F64, A))
+        recon = np.array(G) @ np.array(G).T
+        assert np.abs(np.tril(recon - A.reshape(6, 6))).max() <= 1e-14 * np.abs(A).max(), cls
+        assert np.allclose(np.array(ig) * np.diag(np.array(G)), 1.0, rtol=1e-15)

@@ -1,5 +1,5 @@
 // A plain evaluator of the device functions the 6-DoF kernels share (device_math.h, window_device.h, se3_edge_device.h,
-// cov_block_device.h): no reference and no comparison in here — tests/test_gpu_device_primitives.py holds both.
+// cov_block_device.h, window_block_device.h): no reference and no comparison in here — tests/test_gpu_device_primitives.py holds both.
 //   hipcc --offload-arch=gfx950 -O3 -I localization_amd/csrc tools/primitives_probe.hip -o tools/primitives_probe.bin
 //   tools/primitives_probe.bin <op> <in.bin> <out.bin>
 // in.bin: raw float64 rows of the op's input width; out.bin: raw float64 rows of its output width, one per input row.  The row
@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "cov_block_device.h"
+#include "window_block_device.h"
 using namespace locamd;
 
 #define HIP_OK(call)                                                                                         \
@@ -85,6 +86,106 @@ struct OpSqrtAndRsqrtFast { static constexpr int NI = 1, NO = 2; __device__ stat
 struct OpPivotRsqrt { static constexpr int NI = 1, NO = 1; __device__ static void run(const double* in, double* out) { out[0] = pivot_rsqrt(in[0]); } };
 struct OpFastLogGe1 { static constexpr int NI = 1, NO = 1; __device__ static void run(const double* in, double* out) { out[0] = fast_log_ge1(in[0]); } };
 struct OpFastLogGe1Scaled { static constexpr int NI = 2, NO = 1; __device__ static void run(const double* in, double* out) { out[0] = fast_log_ge1_scaled(in[0], (int)in[1]); } };
+
+// ---- window_block_device.h: the 6x6 block steps of window_lm_kernel's factorisations ---------------------------------------------------------
+// A matrix is 36 doubles ROW-major (its lower triangle is read); a factor is G (36, row-major, strict lower triangle) then ig (6); the
+// blocks the products take are COLUMN-major, as the kernel stores them; a packed update is 27 doubles.
+__device__ static void wbp_factor_in(const double* in, double (&G)[6][6], double (&ig)[6]) {
+    for (int r = 0; r < 6; ++r) {
+        for (int c = 0; c < 6; ++c) G[r][c] = in[6 * r + c];
+        ig[r] = in[36 + r];
+    }
+}
+// out: the lower triangle of G (row-major 36, the rest 0), ig (6), ok
+__device__ static void wbp_factor_out(const double (&G)[6][6], const double (&ig)[6], bool ok, double* out) {
+    for (int r = 0; r < 6; ++r) {
+        for (int c = 0; c < 6; ++c) out[6 * r + c] = c <= r ? G[r][c] : 0.0;
+        out[36 + r] = ig[r];
+    }
+    out[42] = ok ? 1.0 : 0.0;
+}
+template <bool IN_PLACE>
+struct OpCholLeft {
+    static constexpr int NI = 36, NO = 43;
+    __device__ static void run(const double* in, double* out) {
+        double G[6][6], ig[6];
+        bool ok = true;
+        if (IN_PLACE) {
+            for (int r = 0; r < 6; ++r)
+                for (int c = 0; c <= r; ++c) G[r][c] = in[6 * r + c];
+            wb_chol_left([&](int r, int c) { return G[r][c]; }, G, ig, ok);
+        } else wb_chol_left([&](int r, int c) { return in[6 * r + c]; }, G, ig, ok);
+        wbp_factor_out(G, ig, ok, out);
+    }
+};
+struct OpCholRight {   // (the diagonal of the output keeps the pivots)
+    static constexpr int NI = 36, NO = 43;
+    __device__ static void run(const double* in, double* out) {
+        double A[6][6], ig[6];
+        for (int r = 0; r < 6; ++r)
+            for (int c = 0; c <= r; ++c) A[r][c] = in[6 * r + c];
+        wb_chol_right(A, ig);
+        wbp_factor_out(A, ig, wb_inverse_pivots_finite(ig), out);
+    }
+};
+template <int FORM>   // G, ig, s -> x.  0: wb_forward_row, 1: wb_forward_row_scatter, 2: wb_back_solve_gather, 3: wb_back_solve_scatter
+struct OpRowSolve {
+    static constexpr int NI = 48, NO = 6;
+    __device__ static void run(const double* in, double* out) {
+        double G[6][6], ig[6], s[6], x[6];
+        wbp_factor_in(in, G, ig);
+        for (int c = 0; c < 6; ++c) s[c] = x[c] = in[42 + c];
+        if (FORM == 0) wb_forward_row(x, G, ig);
+        else if (FORM == 1) wb_forward_row_scatter(x, G, ig);
+        else if (FORM == 2) wb_back_solve_gather(s, G, ig, x);
+        else wb_back_solve_scatter(s, G, ig, x);
+        for (int c = 0; c < 6; ++c) out[c] = x[c];
+    }
+};
+template <bool LOAD>   // G, ig, row -> the block in memory (column-major 36, untouched entries 0) and its inverse pivots (6) after wb_store_factor_row
+struct OpStoreFactorRow {   // of that row (a run-time index); LOAD: wb_load_factor of a block that holds G and ig, back as G (row-major) and ig
+    static constexpr int NI = 43, NO = 42;
+    __device__ static void run(const double* in, double* out) {
+        double G[6][6], ig[6], mem[42];
+        wbp_factor_in(in, G, ig);
+        for (int k = 0; k < 42; ++k) mem[k] = 0.0;
+        const int r = (int)in[42];
+        if (!LOAD) wb_store_factor_row(r, G, ig, mem + r, 6, mem + 36 + r);
+        else {
+            double Gd[36], G2[6][6], ig2[6];
+            for (int a = 0; a < 6; ++a)
+                for (int b = 0; b < 6; ++b) { Gd[6 * b + a] = G[a][b]; G2[a][b] = 0.0; }
+            wb_load_factor(Gd, ig, G2, ig2);
+            for (int a = 0; a < 6; ++a) {
+                for (int b = 0; b < 6; ++b) mem[6 * a + b] = G2[a][b];
+                mem[36 + a] = ig2[a];
+            }
+        }
+        for (int k = 0; k < 42; ++k) out[k] = mem[k];
+    }
+};
+struct OpDotFms { static constexpr int NI = 13, NO = 1; __device__ static void run(const double* in, double* out) { out[0] = wb_dot_fms(in, in + 6, in[12]); } };
+struct OpRowBlockSub {   // li, B, S -> S - li B^T
+    static constexpr int NI = 48, NO = 6;
+    __device__ static void run(const double* in, double* out) {
+        double li[6], S[6];
+        for (int k = 0; k < 6; ++k) { li[k] = in[k]; S[k] = in[42 + k]; }
+        wb_row_block_sub(li, in + 6, S);
+        for (int k = 0; k < 6; ++k) out[k] = S[k];
+    }
+};
+struct OpSubUpdate {   // G (row-major, lower), y, U -> G - U (row-major, lower, the rest 0), y - u
+    static constexpr int NI = 69, NO = 42;
+    __device__ static void run(const double* in, double* out) {
+        double G[6][6], y[6];
+        wbp_factor_in(in, G, y);
+        wb_sub_update(G, y, in + 42);
+        for (int r = 0; r < 6; ++r) {
+            for (int c = 0; c < 6; ++c) out[6 * r + c] = c <= r ? G[r][c] : 0.0;
+            out[36 + r] = y[r];
+        }
+    }
+};
 
 template <class Op>
 __global__ void rows_kernel(const double* __restrict__ in, double* __restrict__ out, long long n) {
@@ -174,6 +275,11 @@ static const Entry kOps[] = {
     ROWS("fast_rcp", OpFastRcp), ROWS("fast_rcp_1nr", OpFastRcp1nr), ROWS("sqrt_and_rsqrt", OpSqrtAndRsqrt),
     ROWS("sqrt_and_rsqrt_fast", OpSqrtAndRsqrtFast), ROWS("pivot_rsqrt", OpPivotRsqrt),
     ROWS("fast_log_ge1", OpFastLogGe1), ROWS("fast_log_ge1_scaled", OpFastLogGe1Scaled),
+    ROWS("wb_chol_left", OpCholLeft<false>), ROWS("wb_chol_left_in_place", OpCholLeft<true>), ROWS("wb_chol_right", OpCholRight),
+    ROWS("wb_forward_row", OpRowSolve<0>), ROWS("wb_forward_row_scatter", OpRowSolve<1>),
+    ROWS("wb_back_solve_gather", OpRowSolve<2>), ROWS("wb_back_solve_scatter", OpRowSolve<3>),
+    ROWS("wb_store_factor_row", OpStoreFactorRow<false>), ROWS("wb_load_factor", OpStoreFactorRow<true>),
+    ROWS("wb_dot_fms", OpDotFms), ROWS("wb_row_block_sub", OpRowBlockSub), ROWS("wb_sub_update", OpSubUpdate),
     {"wave_sum", 64, 64, launch_wave<WvSum>}, {"wave_max", 64, 64, launch_wave<WvMax>},
     {"lane_from_prev", 64, 64, launch_wave<WvPrev>}, {"lane_from_next", 64, 64, launch_wave<WvNext>},
     BLOCKS("block_sum", 0), BLOCKS("block_max", 1), BLOCKS("block_any", 2),
