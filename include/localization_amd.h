@@ -319,6 +319,9 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *                      entry or the option is 0 (until the next upload), and its covariance pass is classified again.
  *   "resident_slide"  0 (default) / 1: loc_window_upload keeps a host mirror of the batch's integer tables (counts, r_idx, p_idx), which
  *                      loc_window_slide_resident needs; read at upload time.  0: an upload allocates and does exactly what it did without the option.
+ *   "upload_dev_structures"  0 (default) / 1: loc_window_upload_dev also takes the ARROWHEAD and FOREST verdicts on the device (see there), so
+ *                      that such a batch runs on LOC_WINDOW_KERNEL_ARROW3 / _TREE and their covariance passes exactly as after loc_window_upload
+ *                      of the same arrays; read at upload time.  0: loc_window_upload_dev does exactly what it did without the option.
  * LOC_ERR_INVALID for an unknown name or value. */
 int loc_window_set_option(loc_window* w, const char* name, int64_t value);
 /* Host-side cost of the last loc_window_solve_host call, milliseconds: [0] argument validation, [1] structure analysis (kernel
@@ -349,11 +352,22 @@ int loc_window_upload(loc_window* w, int64_t n_instances, const int32_t* counts,
  * unchanged — with one difference: only the chain family's verdicts (LOC_WINDOW_KERNEL_CHAIN3 / _WAVE3, _WAVE6, _WAVE6S, _CHAIN) are taken on the
  * device.  A forest- or arrowhead-shaped batch (whose schedule / packed records loc_window_upload builds on the host) solves on the general
  * kernel, correctly; its covariances are classified by the first covariance call as for any upload.
+ * Option "upload_dev_structures" = 1 removes that difference: a batch that is no chain then takes the two tests loc_window_upload runs next,
+ * in its order and under its conditions (options "arrow3" / "tree", the forest threshold, translation-only values, no endpoint-1 lever arms
+ * or full information matrices for a forest), on the device.  One further launch pair on hip_stream decides both and the host reads back one
+ * more record.  An arrowhead batch gets its row order and packed records from a third launch (nothing is packed on the host); for a forest
+ * batch — every window's counts and used index rows equal window 0's — the host fetches window 0's counts and index rows, ONE window's, and
+ * builds the schedule from them.  Kernel, covariance pass and solve bits are loc_window_upload's; so are the resident entries' answers
+ * (loc_window_prune_resident refuses an ARROW3 batch).  hip_stream is then synchronised once or twice more.  Still on the host only: the
+ * topology cache (every upload is analysed), loc_window_set_endpoint1_offsets / _set_prior_information (host arrays), and forest batches
+ * whose windows differ in topology (the general kernel, as after loc_window_upload).
  * Synchronisation: hip_stream is synchronised ONCE for the record (work the caller queued on it before the call — a kernel that writes the
  * arrays — is seen), and an admitted batch waits for the previous batch's resident work and for its own copies: like loc_window_upload the call
  * returns when the arrays are free again.  The host copies of the integer tables (the counts, and the mirror of option "resident_slide") are
  * fetched from the device by the first entry that reads them.
- * Timing: the pass's two launches are bracketed by the events loc_window_last_covariance_ms reads, as the slides' launches are.  After the
+ * Timing: the pass's two launches are bracketed by the events loc_window_last_covariance_ms reads, as the slides' launches are (when option
+ * "upload_dev_structures" adds launches the closing event is recorded again behind the last of them: the figure then spans admission, the
+ * device-to-device copy and the structure / pack launches).  After the
  * call — a REFUSED one included — loc_window_last_covariance_ms reports the admit pass, no longer the previous batch's last covariance or
  * slide launch: read that figure before calling. */
 int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n_instances, const void* counts_dev, const void* poses_dev,

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "arrow_pack.h"
 #include "capi_host.h"
 #include "message_rows.h"
 #include "slide_plain_admit.h"
@@ -119,6 +120,9 @@ struct loc_window {
     // loc_window_upload_dev: the admit pass's device block [flags u64 [B] | kAdmitMaxWaves partial records | the record] and the record's page-locked copy
     char* d_admit = nullptr;
     locamd::WindowAdmitRecord* h_admit_record = nullptr;
+    // ... under option "upload_dev_structures": the structure pass's device block [kStructMaxWaves partial records | the record] and the record's page-locked copy
+    char* d_struct = nullptr;
+    locamd::WindowStructRecord* h_struct_record = nullptr;
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -151,8 +155,9 @@ int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
     void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws,
-                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows, w->d_admit};
+                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows, w->d_admit, w->d_struct};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (w->h_struct_record) (void)hipHostFree(w->h_struct_record);
     for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -313,24 +318,33 @@ static int validate_instances(const loc_window* w, const locamd::HostBatch& b) {
     return LOC_OK;
 }
 
-static hipError_t upload_arrow_aux(loc_window* w, loc_window::BatchSlot& S, int64_t n, hipStream_t st) {
-    locamd::WinAux& A = S.aux;
-    const locamd::WindowCaps& c = w->caps;
+// the device tables of arrow3_lm_kernel for B windows: hdr and rslot
+static hipError_t reserve_arrow_rows(loc_window* w, locamd::WinAux& A) {
+    if (A.d_ahdr) return hipSuccess;
+    const hipError_t e = hipMalloc((void**)&A.d_ahdr, (size_t)w->B * 8 * sizeof(int32_t));
+    return e != hipSuccess ? e : hipMalloc((void**)&A.d_arslot, (size_t)w->B * w->caps.nv_max * sizeof(int32_t));
+}
+// ... the record tables for n windows of rec_used / prec_used doubles in all, and the kernel's workspace for a border of A.arrow_nb_max
+static hipError_t reserve_arrow_records(loc_window* w, locamd::WinAux& A, int64_t n, size_t rec_used, size_t prec_used) {
     const size_t B = (size_t)w->B, N = (size_t)n;
-    hipError_t e;
-    if (!A.d_ahdr) {
-        if ((e = hipMalloc((void**)&A.d_ahdr, B * 8 * sizeof(int32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&A.d_arslot, B * c.nv_max * sizeof(int32_t))) != hipSuccess) return e;
-    }
     // a record table that this batch's records outgrow is replaced by one for B windows of this batch's records per window
     auto grow_records = [&](double*& d, size_t& cap, size_t used) {
         if (used <= cap) return hipSuccess;
         cap = 0;
         return locamd::grow_buffers(cap, used / N * B, {{d, used / N * B * sizeof(double)}});
     };
-    if ((e = grow_records(A.d_arec, A.arec_cap, A.h_arec.size())) != hipSuccess || (e = grow_records(A.d_aprec, A.aprec_cap, A.h_aprec.size())) != hipSuccess ||
-        (e = locamd::grow_buffers(w->arrow_ws_nb, (size_t)A.arrow_nb_max,
-                                  {{w->d_arrow_ws, B * locamd::window_arrow3_workspace_doubles(c, A.arrow_nb_max) * sizeof(double)}})) != hipSuccess) return e;
+    hipError_t e;
+    if ((e = grow_records(A.d_arec, A.arec_cap, rec_used)) != hipSuccess || (e = grow_records(A.d_aprec, A.aprec_cap, prec_used)) != hipSuccess) return e;
+    return locamd::grow_buffers(w->arrow_ws_nb, (size_t)A.arrow_nb_max,
+                                {{w->d_arrow_ws, B * locamd::window_arrow3_workspace_doubles(w->caps, A.arrow_nb_max) * sizeof(double)}});
+}
+
+static hipError_t upload_arrow_aux(loc_window* w, loc_window::BatchSlot& S, int64_t n, hipStream_t st) {
+    locamd::WinAux& A = S.aux;
+    const locamd::WindowCaps& c = w->caps;
+    const size_t N = (size_t)n;
+    hipError_t e;
+    if ((e = reserve_arrow_rows(w, A)) != hipSuccess || (e = reserve_arrow_records(w, A, n, A.h_arec.size(), A.h_aprec.size())) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(A.d_ahdr, A.h_ahdr.data(), N * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess ||
         (e = hipMemcpyAsync(A.d_arslot, A.h_arslot.data(), N * c.nv_max * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess ||
         (e = hipMemcpyAsync(A.d_arec, A.h_arec.data(), A.h_arec.size() * sizeof(double), hipMemcpyHostToDevice, st)) != hipSuccess ||
@@ -519,6 +533,7 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
     }
     if (k == "resident_slide") return flag(w->opt_slide);   // (read by loc_window_upload: the batch resident now keeps what its upload decided)
     if (k == "topology_cache") { w->topo_cache.valid = false; return flag(o.topology_cache); }
+    if (k == "upload_dev_structures") return flag(o.upload_dev_structures);   // (read by loc_window_upload_dev: the batch resident now keeps what its upload decided)
     return locamd_fail(LOC_ERR_INVALID, "set_option: unknown option name");
 }
 
@@ -731,10 +746,79 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     return LOC_OK;
 }
 
+// Option "upload_dev_structures": batch_topology's two tests behind its chain block — the arrowhead, then the forest, each under its
+// conditions — for an admitted batch that is no chain and already lies in the handle's device arrays (window_structure_kernel.hip; DESIGN.md
+// §2, "Upload from device arrays").  One launch pair answers both tests and the host reads back ONE record; an arrowhead batch is packed by a
+// further launch at the sizes of that record, a forest batch sends window 0's counts and index rows (one window, not the batch) to
+// build_tree_sched.  topology / cov: what loc_window_upload of the same arrays leaves in Resident — untouched when neither test takes the
+// batch.  slot[1].aux is written here alone, after the previous batch was dropped.  The launches end the call's cov_ev0 / cov_ev1 bracket:
+// cov_ev1 is recorded again behind them, so loc_window_last_covariance_ms spans admission, copy and these launches.
+static int dev_structures(loc_window* w, int64_t n, const locamd::WindowBatchFlags& flags, hipStream_t st, int& topology, CovKind& cov) {
+    const locamd::WindowCaps& c = w->caps;
+    const locamd::DispatchOpts& o = w->opt;
+    loc_window::BatchSlot& S = w->slot[1];
+    locamd::WinAux& A = S.aux;
+    // (arrow3_fits grows with the border: a handle that fails it for a border of one row fails it for every batch)
+    const bool arrow = locamd::arrow3_wanted(o, w->fits) && flags.translation_only && locamd::arrow3_fits(c, 1);
+    const bool forest = o.tree != 0 && n >= locamd::tree_min_batch(o) && !locamd::general_only(o);   // (build_tree_sched refuses under general_only)
+    if (!arrow && !forest) return LOC_OK;
+    const size_t at_record = (size_t)locamd::kStructMaxWaves * sizeof(locamd::WindowStructRecord);
+    if (!w->d_struct) LOC_HIP(hipMalloc((void**)&w->d_struct, at_record + sizeof(locamd::WindowStructRecord)));
+    if (!w->h_struct_record) LOC_HIP(hipHostMalloc((void**)&w->h_struct_record, sizeof(locamd::WindowStructRecord), hipHostMallocDefault));
+    if (arrow) LOC_HIP(reserve_arrow_rows(w, A));
+    const locamd::DeviceTables& d = w->dev;
+    locamd::WindowStructArgs a{};
+    a.counts = (const int32_t*)d.t[kCounts]; a.r_idx = (const int32_t*)d.t[locamd::kRIdx]; a.p_idx = (const int32_t*)d.t[locamd::kPIdx]; a.s_idx = (const int32_t*)d.t[locamd::kSIdx];
+    a.hdr = A.d_ahdr; a.rslot = A.d_arslot;
+    a.partial = (locamd::WindowStructRecord*)w->d_struct; a.record = (locamd::WindowStructRecord*)(w->d_struct + at_record);
+    a.arrow = arrow; a.forest = forest; a.B = n; a.caps = c;
+    LOC_HIP(locamd::launch_window_structure(a, st));
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipMemcpyAsync(w->h_struct_record, a.record, sizeof(locamd::WindowStructRecord), hipMemcpyDeviceToHost, st));
+    LOC_HIP(hipStreamSynchronize(st));
+    const locamd::WindowStructRecord rec = *w->h_struct_record;
+    const locamd::ArrowMaxima& m = rec.arrow;
+    if (arrow && (rec.and_bits & locamd::kStructArrow) != 0 && !locamd::arrow_batch_refused(m) && locamd::arrow3_fits(c, m.nb_max)) {
+        const int nchunk = (c.nv_max + 63) / 64;
+        A.arrow_nb_max = m.nb_max; A.arrow_jmax = m.jmax; A.arrow_jpmax = m.jpmax; A.arrow_list_cap = m.list_cap;
+        for (int k = 0; k < 16; ++k) { A.arrow_jch[k] = m.jch[k]; A.arrow_jpch[k] = m.jpch[k]; }
+        LOC_HIP(reserve_arrow_records(w, A, n, (size_t)n * locamd::arrow_rec_doubles(nchunk, m.jmax), (size_t)n * locamd::arrow_prec_doubles(nchunk, m.jpmax)));
+        locamd::ArrowPackArgs p{};
+        p.counts = a.counts; p.r_idx = a.r_idx; p.r_val = (const double*)d.t[locamd::kRVal]; p.p_idx = a.p_idx; p.p_val = (const double*)d.t[locamd::kPVal];
+        p.hdr = A.d_ahdr; p.rec = A.d_arec; p.prec = A.d_aprec; p.jmax = m.jmax; p.jpmax = m.jpmax; p.nchunk = nchunk; p.B = n; p.caps = c;
+        LOC_HIP(locamd::launch_window_arrow_pack(p, st));
+        LOC_HIP(hipEventRecord(w->cov_ev1, st));
+        LOC_HIP(hipStreamSynchronize(st));
+        topology = LOC_WINDOW_KERNEL_ARROW3;
+        cov = CovKind::Arrow;
+        S.cov_list_cap = m.list_cap;
+        return LOC_OK;
+    }
+    if (forest && (rec.and_bits & locamd::kStructEqual0) != 0) {
+        // every window equals window 0: everything else build_tree_sched reads is window 0's integer tables
+        int32_t cn[4];
+        LOC_HIP(hipMemcpy(cn, d.t[kCounts], sizeof(cn), hipMemcpyDeviceToHost));
+        std::vector<int32_t> ridx((size_t)cn[1] * 2), pidx((size_t)cn[2]), sidx((size_t)cn[3] * 4);
+        if (!ridx.empty()) LOC_HIP(hipMemcpy(ridx.data(), d.t[locamd::kRIdx], ridx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!pidx.empty()) LOC_HIP(hipMemcpy(pidx.data(), d.t[locamd::kPIdx], pidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!sidx.empty()) LOC_HIP(hipMemcpy(sidx.data(), d.t[locamd::kSIdx], sidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        const locamd::HostBatch one{1, nullptr, cn, nullptr, nullptr, nullptr, ridx.data(), pidx.data(), sidx.data()};
+        if (locamd::build_tree_sched(c, locamd::general_only(o), one, A)) {
+            LOC_HIP(upload_tree_sched(w, A, w->stream));
+            bool chain = false, single_pairs = false, se3_pairs = false;
+            locamd::chain_scan(c, one, false, chain, single_pairs, se3_pairs);   // (the batch's: every window has window 0's rows)
+            topology = LOC_WINDOW_KERNEL_TREE;
+            cov = chain ? CovKind::Unclassified : CovKind::Forest;
+        }
+    }
+    return LOC_OK;
+}
+
 // The same from the caller's DEVICE arrays ("Upload from device arrays"): window_admit_kernel.hip admits every window and scans
 // the chain family's structure on hip_stream, the host reads back one record (the call's ONE synchronisation of that stream), and an admitted
 // batch is copied device-to-device.  A refused batch copies nothing and leaves the previous resident batch as it was.  The host copies of the
-// integer tables are not made: they are sized and marked stale (refresh_mirror).
+// integer tables are not made: they are sized and marked stale (refresh_mirror).  Option "upload_dev_structures": a batch that is no chain
+// goes on to dev_structures above.
 int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void* counts_dev, const void* poses_dev, const void* r_idx_dev, const void* r_val_dev,
                           const void* p_idx_dev, const void* p_val_dev, const void* s_idx_dev, const void* s_val_dev, void* admit_dev) {
     const locamd::HostBatch b{n, (const double*)poses_dev, (const int32_t*)counts_dev, (const double*)r_val_dev, (const double*)p_val_dev, (const double*)s_val_dev,
@@ -776,7 +860,11 @@ int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void
     if (!w->d_poses_in) LOC_HIP(hipMalloc((void**)&w->d_poses_in, B * locamd::table_bytes(c, kPoses)));
     LOC_HIP(copy_tables(c, (size_t)n, uploaded_tables(w).t, b.tables().t, hipMemcpyDeviceToDevice, &st));
     LOC_HIP(hipStreamSynchronize(st));   // (the call returns synchronously, like loc_window_upload: the caller's arrays are free again)
-    const int topology = locamd::topology_from_flags(w->opt, w->fits, locamd::window_batch_flags(rec));
+    const locamd::WindowBatchFlags flags = locamd::window_batch_flags(rec);
+    int topology = locamd::topology_from_flags(w->opt, w->fits, flags);
+    CovKind cov = topology == LOC_WINDOW_KERNEL_CHAIN3 ? CovKind::Chain3 : topology == LOC_WINDOW_KERNEL_GENERAL ? CovKind::Unclassified : CovKind::Chain6;
+    if (w->opt.upload_dev_structures && !flags.chain)
+        if (int rc = dev_structures(w, n, flags, st, topology, cov)) return rc;
     R.min_anchors = rec.max_anchor;
     R.counts.assign((size_t)n * 4, 0);
     if (w->opt_slide) {
@@ -787,9 +875,7 @@ int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void
     R.mirror_stale = true;   // (refresh_mirror: the first reader of counts or the mirror fetches them)
     R.topology = topology;
     R.skip = locamd::structured_pinfo(w->opt);
-    if (topology == LOC_WINDOW_KERNEL_CHAIN3) R.cov = CovKind::Chain3;
-    else if (topology == LOC_WINDOW_KERNEL_GENERAL) R.cov = CovKind::Unclassified;
-    else R.cov = CovKind::Chain6;
+    R.cov = cov;
     R.n = n;
     return LOC_OK;
 }

@@ -8,7 +8,7 @@ namespace locamd {
 
 // what only the general kernel evaluates: lever arms on endpoint 1, full information matrices on the priors.  One flag of the structure
 // hash and of build_tree_sched: no cached verdict and no forest schedule survives a change of it.
-static bool general_only(const DispatchOpts& o) { return o.has_off1 || o.has_pinfo; }
+bool general_only(const DispatchOpts& o) { return o.has_off1 || o.has_pinfo; }
 // ... unless the table is a dense 3 x 3 block on the translations and the handle asked for the 3 x 3 kernels: wave3_lm_kernel<JAC, true> and
 // covariance_kernel<3, .., true> take such a table on a translation-only chain (pick_kernel, structured_covariance_kind); chain3_lm_kernel,
 // arrow3_lm_kernel and every other pass do not

@@ -26,6 +26,8 @@ struct DispatchOpts {
     bool pinfo_translation = false;    // ... and none of them has rotation rows or columns (prior_information_translation_only, taken once by the setter)
     bool pinfo_structured = false;     // "prior_information_structured" 1: a translation-only table on a translation-only chain is served by
                                        // wave3_lm_kernel<JAC, true> and the chain 3x3 covariance pass (structured_pinfo); 0: the general kernel, the envelope pass
+    bool upload_dev_structures = false; // "upload_dev_structures" 1: loc_window_upload_dev takes batch_topology's arrowhead and forest tests on the device
+                                       // (window_structure_kernel.hip) for a batch that is no chain; 0: such a batch is LOC_WINDOW_KERNEL_GENERAL
 };
 
 // what depends on the handle's capacities alone: the kernels' LDS needs against their limits (window_layouts.h), taken once by loc_window_create
@@ -77,10 +79,13 @@ struct Topology { int kind; bool cached; };   // LOC_WINDOW_KERNEL_* by structur
 Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, WinAux& aux, TopoCache* tc);
 // The chain family of that verdict from a batch's reduced flags (window_admit.h: what window_admit_kernel.hip leaves of a batch uploaded from
 // device arrays, loc_window_upload_dev): batch_topology's `if (chain)` block restated — LOC_WINDOW_KERNEL_CHAIN3 (structured_pinfo(o) chooses
-// which of the two translation-only flags is read), _WAVE6, _WAVE6S, _CHAIN.  Every other batch is _GENERAL: the forest and arrowhead verdicts
-// are OUT OF SCOPE here — their schedule and packed records are built on the host from host tables — so a forest- or arrowhead-shaped batch
-// uploaded from device arrays solves on the general kernel, correctly; loc_window_upload serves a caller who wants those kernels.
+// which of the two translation-only flags is read), _WAVE6, _WAVE6S, _CHAIN.  Every other batch is _GENERAL here: the arrowhead and forest
+// verdicts are taken by loc_window_upload_dev itself under option "upload_dev_structures" (capi_window.cpp: dev_structures — the two tests
+// that follow the chain block in batch_topology, in its order and under its conditions, on the device); without the option a forest- or
+// arrowhead-shaped batch uploaded from device arrays solves on the general kernel, correctly.
 int topology_from_flags(const DispatchOpts& o, const DispatchFits& f, const WindowBatchFlags& b);
+// what only the general kernel evaluates (lever arms on endpoint 1, full information matrices): build_tree_sched's has_off1 argument
+bool general_only(const DispatchOpts& o);
 
 // the structure the host path's own forest schedule (its cov_aux) was built for, device copy included
 struct SchedKey {

@@ -282,6 +282,32 @@ struct WindowAdmitArgs {
 int window_admit_waves(long long B);   // the waves launch_window_admit starts for B windows (= the partial records it writes)
 hipError_t launch_window_admit(const WindowAdmitArgs& a, hipStream_t stream);
 
+// the forest and arrowhead verdicts of an ADMITTED batch in device arrays, and arrow3_lm_kernel's tables (window_structure_kernel.hip; DESIGN.md
+// §2, "Upload from device arrays"; option "upload_dev_structures"): arrow_pack.h's rule, one wave per window.  launch_window_structure writes
+// hdr / rslot of every window (arrow != 0) and one partial record per wave, a one-wave launch merges them into *record; launch_window_arrow_pack
+// writes rec / prec, the fill included, at the sizes the host took from that record.  All device arrays at the capacities `caps`.
+struct WindowStructRecord;   // arrow_pack.h
+constexpr int kStructMaxWaves = 2048;
+struct WindowStructArgs {
+    const int32_t* counts; const int32_t* r_idx; const int32_t* p_idx; const int32_t* s_idx;
+    int32_t* hdr; int32_t* rslot;                         // [B][8], [B][nv_max]: ArrowAux's (arrow != 0)
+    WindowStructRecord* partial; WindowStructRecord* record;   // kStructMaxWaves records; the batch's
+    int arrow, forest;                                    // which of the two verdicts is wanted (the other bit of the record is 0)
+    long long B;
+    WindowCaps caps;
+};
+struct ArrowPackArgs {
+    const int32_t* counts; const int32_t* r_idx; const double* r_val; const int32_t* p_idx; const double* p_val;
+    const int32_t* hdr;                                   // [B][8] as launch_window_structure wrote it
+    double* rec; double* prec;                            // [B][nchunk][jmax][64][3], [B][nchunk][jpmax][64][7]
+    int jmax, jpmax, nchunk;
+    long long B;
+    WindowCaps caps;
+};
+size_t window_structure_lds_bytes(const WindowCaps& c);   // launch_window_structure's, arrow != 0 (four waves' row counters)
+hipError_t launch_window_structure(const WindowStructArgs& a, hipStream_t stream);
+hipError_t launch_window_arrow_pack(const ArrowPackArgs& a, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

@@ -1,6 +1,7 @@
 // Structure analysis of a batch of windows.  Host code only: no HIP runtime call in this file.
 #include "window_structure.h"
 #include "window_layouts.h"
+#include "arrow_pack.h"
 
 #include <cstring>
 #include <algorithm>
@@ -387,139 +388,32 @@ long long envelope_blocks_max_joint(const WindowCaps& c, const HostBatch& b, con
 // and priors are packed as records [chunk of 64 rows][slot][lane].
 // A.arrow_list_cap: the most edges and priors any pose in front of the nb0 border slots has (arrow_covariance_kernel.hip's list size).
 // structure_only: the test alone, for the covariance pass — A is a table set of the covariance's own and nothing is packed.
+// The rule for one window — structure, owners, refusals, records — is arrow_pack.h's; this is the loop over the batch and its batch-level refusals.
 bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only) {
-    const int NW = 4;
+    static_assert(kArrowPackAnchors == kArrowMaxAnchors && kArrowSegments == ARROW_NW, "arrow_pack.h states arrow3_lm_kernel's limits");
     const int nchunk = (c.nv_max + 63) / 64;
     A.h_ahdr.assign((size_t)b.n * 8, 0);
     A.h_arslot.assign((size_t)b.n * c.nv_max, 0);
-    std::vector<int32_t> cls, nedge, nprior, pairs;
-    std::vector<int> seps;
-    // pass 1: structure, record counts
-    int nb_max = 0, jmax = 1, jpmax = 1, list_cap = 1;
-    int jch[16], jpch[16];
-    for (int k = 0; k < 16; ++k) { jch[k] = 1; jpch[k] = 1; }
-    for (int64_t i = 0; i < b.n; ++i) {
-        const int32_t* cn = b.counts + i * 4;
-        const int nv = cn[0], nr = cn[1], np = cn[2];
-        const int32_t* ri = b.r_idx + (size_t)i * c.nr_max * 2;
-        int nb0 = 0;
-        for (int e = 0; e < nr; ++e) {
-            const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
-            if (v1 < 0) {
-                if (-1 - v1 >= kArrowMaxAnchors) return false;   // (the kernel keeps the anchor table in LDS)
-                continue;
-            }
-            const int hi = v0 > v1 ? v0 : v1, lo = v0 > v1 ? v1 : v0;
-            if (hi - lo != 1 && nv - hi > nb0) nb0 = nv - hi;
-        }
-        if (nb0 < 1 || nb0 > 12 || nv - nb0 < 2) return false;
-        const int n0 = nv - nb0;
-        int nseg = n0 / 24;
-        if (nseg > NW) nseg = NW;
-        if (nseg < 1) nseg = 1;
-        const int nb = nb0 + nseg - 1, nc = n0 - (nseg - 1);
-        cls.assign((size_t)nv, 0);
-        seps.clear();
-        for (int k = 1; k < nseg; ++k) seps.push_back((int)((long long)k * n0 / nseg));
-        int32_t* hdr = A.h_ahdr.data() + (size_t)i * 8;
-        int32_t* rslot = A.h_arslot.data() + (size_t)i * c.nv_max;
-        hdr[0] = nb; hdr[1] = nseg; hdr[2] = nc; hdr[3] = 0;
-        int q = 0, si = 0;
-        for (int v = 0; v < n0; ++v) {
-            if (si < (int)seps.size() && v == seps[si]) { cls[v] = -1 - si; rslot[nc + si] = v; ++si; hdr[3 + si] = q; continue; }
-            cls[v] = q; rslot[q] = v; ++q;
-        }
-        for (int s2 = nseg; s2 <= NW; ++s2) hdr[3 + s2] = nc;   // (segments nseg .. NW-1 are empty)
-        for (int v = n0; v < nv; ++v) { const int bs = (nseg - 1) + (v - n0); cls[v] = -1 - bs; rslot[nc + bs] = v; }
-        // owners
-        nedge.assign((size_t)nv, 0); nprior.assign((size_t)nv, 0); pairs.assign((size_t)nc + 1, 0);
-        for (int e = 0; e < nr; ++e) {
-            const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
-            int row;
-            if (v1 < 0) row = cls[v0] >= 0 ? cls[v0] : nc + (-1 - cls[v0]);
-            else {
-                const int c0 = cls[v0], c1 = cls[v1];
-                if (c0 >= 0 && c1 >= 0) {
-                    if (c0 - c1 != 1 && c1 - c0 != 1) return false;   // (cannot happen: non-consecutive edges end in the border)
-                    row = c0 > c1 ? c0 : c1;
-                    if (++pairs[row] > 1) return false;                // one edge per consecutive chain pair
-                } else if (c0 >= 0) row = c0;
-                else if (c1 >= 0) row = c1;
-                else row = nc + ((-1 - c0) > (-1 - c1) ? (-1 - c0) : (-1 - c1));
-            }
-            if (++nedge[row] > jmax) jmax = nedge[row];
-            if (row / 64 < 16 && nedge[row] > jch[row / 64]) jch[row / 64] = nedge[row];
-        }
-        const int32_t* pi = b.p_idx + (size_t)i * c.np_max;
-        for (int e = 0; e < np; ++e) {
-            const int cv = cls[pi[e]], row = cv >= 0 ? cv : nc + (-1 - cv);
-            if (++nprior[row] > jpmax) jpmax = nprior[row];
-            if (row / 64 < 16 && nprior[row] > jpch[row / 64]) jpch[row / 64] = nprior[row];
-        }
-        if (nb > nb_max) nb_max = nb;
-        {
-            std::vector<int32_t>& deg = nedge;   // (its row counts are not needed any more)
-            deg.assign((size_t)nv, 0);
-            for (int e = 0; e < nr; ++e) {
-                const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
-                if (structure_only && v1 == v0) return false;   // (pass 2's test: a range from a border pose to itself)
-                ++deg[v0];
-                if (v1 >= 0) ++deg[v1];
-            }
-            for (int e = 0; e < np; ++e) ++deg[pi[e]];
-            for (int v = 0; v < n0; ++v) if (deg[v] > list_cap) list_cap = deg[v];
-        }
-    }
-    if (jmax > 64 || jpmax > 16 || nb_max > 15) return false;
-    if (!arrow3_fits(c, nb_max)) return false;
-    A.arrow_list_cap = list_cap;
+    std::vector<int32_t> work((size_t)3 * c.nv_max);
+    // pass 1 (arrow_pack.h, (a)): structure, record counts
+    ArrowMaxima m = arrow_maxima_empty();
+    for (int64_t i = 0; i < b.n; ++i)
+        if (arrow_window_structure(b.counts + i * 4, b.r_idx + (size_t)i * c.nr_max * 2, b.p_idx + (size_t)i * c.np_max, A.h_ahdr.data() + (size_t)i * 8,
+                                   A.h_arslot.data() + (size_t)i * c.nv_max, work.data(), m) != kArrowOk) return false;
+    if (arrow_batch_refused(m)) return false;
+    if (!arrow3_fits(c, m.nb_max)) return false;
+    A.arrow_list_cap = m.list_cap;
     if (structure_only) return true;
-    // pass 2: the records
-    const size_t rec_per = (size_t)nchunk * jmax * 64 * 3, prec_per = (size_t)nchunk * jpmax * 64 * 7;
-    A.h_arec.assign((size_t)b.n * rec_per, -1.0);
-    A.h_aprec.assign((size_t)b.n * prec_per, 0.0);
-    for (int64_t i = 0; i < b.n; ++i) {
-        const int32_t* cn = b.counts + i * 4;
-        const int nv = cn[0], nr = cn[1], np = cn[2];
-        const int32_t* ri = b.r_idx + (size_t)i * c.nr_max * 2;
-        const double* rv = b.r_val + (size_t)i * c.nr_max * 5;
-        const int32_t* hdr = A.h_ahdr.data() + (size_t)i * 8;
-        const int32_t* rslot = A.h_arslot.data() + (size_t)i * c.nv_max;
-        const int nb = hdr[0], nc = hdr[2];
-        cls.assign((size_t)nv, 0);
-        for (int r = 0; r < nc + nb; ++r) cls[rslot[r]] = r < nc ? r : -1 - (r - nc);
-        nedge.assign((size_t)nv, 0); nprior.assign((size_t)nv, 0);
-        double* rec = A.h_arec.data() + (size_t)i * rec_per;
-        for (int e = 0; e < nr; ++e) {
-            const int v0 = ri[2 * e], v1 = ri[2 * e + 1];
-            int row, kind, idx, own0;
-            if (v1 < 0) { row = cls[v0] >= 0 ? cls[v0] : nc + (-1 - cls[v0]); kind = 0; idx = -1 - v1; own0 = 1; }
-            else {
-                const int c0 = cls[v0], c1 = cls[v1];
-                if (c0 >= 0 && c1 >= 0) { row = c0 > c1 ? c0 : c1; kind = 1; idx = 0; own0 = c0 > c1; }
-                else if (c0 >= 0) { row = c0; kind = 2; idx = -1 - c1; own0 = 1; }
-                else if (c1 >= 0) { row = c1; kind = 2; idx = -1 - c0; own0 = 0; }
-                else {
-                    const int b0 = -1 - c0, b1 = -1 - c1;
-                    if (b0 == b1) return false;
-                    row = nc + (b0 > b1 ? b0 : b1); kind = 2; idx = b0 > b1 ? b1 : b0; own0 = b0 > b1;
-                }
-            }
-            double* q = rec + (((size_t)(row / 64) * jmax + nedge[row]++) * 64 + row % 64) * 3;
-            q[0] = (double)((idx << 3) | (kind << 1) | own0); q[1] = rv[5 * e]; q[2] = rv[5 * e + 1];
-        }
-        const int32_t* pi = b.p_idx + (size_t)i * c.np_max;
-        const double* pv = b.p_val + (size_t)i * c.np_max * 18;
-        double* prec = A.h_aprec.data() + (size_t)i * prec_per;
-        for (int e = 0; e < np; ++e) {
-            const int cv = cls[pi[e]], row = cv >= 0 ? cv : nc + (-1 - cv);
-            double* q = prec + (((size_t)(row / 64) * jpmax + nprior[row]++) * 64 + row % 64) * 7;
-            q[0] = 1.0;
-            for (int k = 0; k < 3; ++k) { q[1 + k] = pv[18 * e + 9 + k]; q[4 + k] = pv[18 * e + 12 + k]; }
-        }
-    }
-    A.arrow_nb_max = nb_max; A.arrow_jmax = jmax; A.arrow_jpmax = jpmax;
-    for (int k = 0; k < 16; ++k) { A.arrow_jch[k] = jch[k]; A.arrow_jpch[k] = jpch[k]; }
+    // pass 2 (arrow_pack.h, (b)): the records
+    const size_t rec_per = arrow_rec_doubles(nchunk, m.jmax), prec_per = arrow_prec_doubles(nchunk, m.jpmax);
+    A.h_arec.resize((size_t)b.n * rec_per);
+    A.h_aprec.resize((size_t)b.n * prec_per);
+    for (int64_t i = 0; i < b.n; ++i)
+        arrow_window_pack(b.counts + i * 4, A.h_ahdr.data() + (size_t)i * 8, b.r_idx + (size_t)i * c.nr_max * 2, b.r_val + (size_t)i * c.nr_max * 5,
+                          b.p_idx + (size_t)i * c.np_max, b.p_val + (size_t)i * c.np_max * 18, nchunk, m.jmax, m.jpmax, A.h_arec.data() + (size_t)i * rec_per,
+                          A.h_aprec.data() + (size_t)i * prec_per, work.data());
+    A.arrow_nb_max = m.nb_max; A.arrow_jmax = m.jmax; A.arrow_jpmax = m.jpmax;
+    for (int k = 0; k < 16; ++k) { A.arrow_jch[k] = m.jch[k]; A.arrow_jpch[k] = m.jpch[k]; }
     return true;
 }
 

@@ -190,7 +190,7 @@ class WindowSolver(_lib.Handle):
         [n][np_max][18], s_idx int32 [n][ns_max][4], s_val float64 [n][ns_max][48] — each a device pointer, an object with data_ptr() or None (a
         table under a capacity of 0).  n: the windows (None: counts.shape[0]).  admit: int32 [n] on the device or None; window b's code (0
         admitted, 1 .. 6 the check it fails).  Every window is admitted and the chain family's structure scanned by a HIP pass on stream (a torch
-        stream; None: the handle's own); a batch with a refused window raises (LOC_ERR_INVALID; the error names the check and the lowest refused
+        stream; None: the handle's own; set_option("upload_dev_structures", 1): the arrowhead and forest verdicts as well); a batch with a refused window raises (LOC_ERR_INVALID; the error names the check and the lowest refused
         window) and leaves the previous resident batch as it was.  Returns when the arrays are free again, like upload().  The handle's tables of
         endpoint-1 lever arms / full information matrices stay as they are.  Plumbing only: the library checks everything."""
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
@@ -556,7 +556,10 @@ class WindowSolver(_lib.Handle):
         "covariance_general": 1 = covariance() / covariance_resident() also serve
         the batches the chain, arrowhead and forest passes decline — every batch with full-information priors among them —, default 0;
         "prior_information_structured": 1 = a translation-only p_info table (dense 3 x 3 blocks on the translations: marginal_prior()'s rows)
-        on translation-only chains of <= 64 poses is solved by wave3_lm_kernel and served by the chain 3 x 3 covariance pass, default 0)"""
+        on translation-only chains of <= 64 poses is solved by wave3_lm_kernel and served by the chain 3 x 3 covariance pass, default 0;
+        "upload_dev_structures": 1 = upload_dev() also takes the arrowhead and forest verdicts on the device, so that such a batch runs on
+        arrow3_lm_kernel / tree_wave_kernel and its covariance passes exactly as after upload() of the same arrays; default 0: a batch
+        uploaded from device arrays that is no chain solves on the general kernel)"""
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
 
     def last_host_timing(self):
