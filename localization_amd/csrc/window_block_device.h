@@ -1,10 +1,24 @@
 // 6x6 block steps of window_lm_kernel's factorisations (window_kernel.hip), each stated once with its definition, its rounding order and
 // what it does at a pivot that is not positive or not finite: the Cholesky factor G of a diagonal block (G G^T = the block, lower), row
-// solves against it, the factor's way to and from memory, three products.  Callers: factor_and_solve (the SKYLINE sweep) and
+// solves against it, the factor's way to and from memory, seven products.  Callers: factor_and_solve (the SKYLINE sweep) and
 // root_factor_and_solve (the dense root supernode) take every block step they have from here; factor_and_solve_sparse and
-// factor_and_solve_small call wb_sub_update, wb_dot_fms, wb_load_factor and wb_back_solve_scatter and still write their other steps out
-// (DESIGN.md §2 says which, and what is known about them).  The SCHEDULE stays with the callers — who factors which block, from which
-// memory, between which barriers; in here is only what a lane does to the numbers in its registers.
+// factor_and_solve_small call wb_sub_update, wb_dot_fms, wb_load_factor and wb_back_solve_scatter.  Their other steps are DELIBERATE
+// COPIES of functions in here, kept in window_kernel.hip because the kernel sits at 256 VGPRs and spills, and each of them, made a call,
+// moved an instantiation's scratch size or spill counts, or its time beyond the parent's own spread:
+//   column mode     wb_chol_left in place with its stores and wb_forward_row: uwb_twist numeric 42.21 .. 42.30 ms against a limit of 42.06;
+//                   wb_outer_lower (both sinks), wb_block_blockT_fms, the six wb_forward_row of a block: scratch bytes or SGPR spills;
+//   row mode        wb_row_block_sub (three sites): scratch bytes of one instantiation, 204 -> 252;  wb_chol_left from memory,
+//                   wb_store_factor_row, wb_forward_row: selfcal 13.62 .. 13.80 ms against 13.55 with G loaded first, SGPR spills of eleven
+//                   instantiations with the memory source handed over;
+//   back-substitution  wb_blockT_vec_sub and wb_back_solve_gather: pose64 + 0.27 ms with G loaded first, 18.47 .. 18.49 ms against a limit of
+//                   18.28 with the factor read in place through callables;
+//   small schedule  wb_chol_right, wb_forward_row_scatter, wb_inverse_pivots_finite, wb_blockT_vec_fms: uwb_imu numeric 26.93 .. 26.99 ms
+//                   against a limit of 26.92.
+// Every copy says so where it stands, DESIGN.md §2 has the table, and tests/test_gpu_window_block_bits.py holds the kernel to the bits it
+// had before the first step moved in here: a copy that drifts shows there as a changed digest (a function in here that drifts from its
+// copy does not: whoever changes one that has a copy carries the change over, as before).  The SCHEDULE stays
+// with the callers — who factors which block, from which memory, between which barriers; in here is only what a lane does to the numbers
+// in its registers.
 // Conventions: G[r][c], r > c, is the factor's strict lower triangle; ig[j] = 1 / G_jj, the INVERSE pivot (every solve multiplies); a block
 // in memory is column-major, entry (r, c) at 6 c + r; a packed update is 27 doubles: the lower triangle at wb_tri(r, c), then 6 of the
 // right-hand side (the callers keep one per column, 28 apart).  Every loop is unrolled and every index is static: nothing in here sends a
@@ -100,15 +114,20 @@ __device__ __forceinline__ void wb_forward_row_scatter(double (&s)[6], const dou
     }
 }
 // Back-solve G^T x = t, GATHER form: x_r = (t_r - sum_{s>r} G_sr x_s) ig_r, rows 5 .. 0, every term FMA'd into t_r, s ASCENDING, then one
-// product.
-__device__ __forceinline__ void wb_back_solve_gather(const double (&t)[6], const double (&G)[6][6], const double (&ig)[6], double (&x)[6]) {
+// product.  fac(s, r) = G_sr and piv(r) = ig_r: any callables, so that a caller whose factor lies in memory reads each entry where it is used.
+template <class Fac, class Piv>
+__device__ __forceinline__ void wb_back_solve_gather(const double (&t)[6], Fac fac, Piv piv, double (&x)[6]) {
 #pragma unroll
     for (int rr = 5; rr >= 0; --rr) {
         double v = t[rr];
 #pragma unroll
-        for (int s2 = rr + 1; s2 < 6; ++s2) v = __builtin_fma(-G[s2][rr], x[s2], v);
-        x[rr] = v * ig[rr];
+        for (int s2 = rr + 1; s2 < 6; ++s2) v = __builtin_fma(-fac(s2, rr), x[s2], v);
+        x[rr] = v * piv(rr);
     }
+}
+// the factor in registers
+__device__ __forceinline__ void wb_back_solve_gather(const double (&t)[6], const double (&G)[6][6], const double (&ig)[6], double (&x)[6]) {
+    wb_back_solve_gather(t, [&](int s2, int rr) { return G[s2][rr]; }, [&](int rr) { return ig[rr]; }, x);
 }
 // Back-solve G^T x = t, SCATTER form: x_r = t_r ig_r is taken out of the rows above it at once, so row q sees its terms with s DESCENDING:
 // other bits than the gather form's, which is why both exist.  t is used up.
@@ -173,6 +192,57 @@ __device__ __forceinline__ void wb_sub_update(double (&G)[6][6], double (&y)[6],
         for (int c = 0; c <= r; ++c) G[r][c] -= U[wb_tri(r, c)];
         y[r] -= U[21 + r];
     }
+}
+// the lower triangle of B B^T and B y, B = a block L_iK (entry (r, k) at 6 k + r), y = y_K: 27 sums, each an FMA chain from 0 with k
+// ascending — what a column owes its parent.  A finished sum goes to put(r, c, sum), c <= r, or to put_rhs(r, sum): the caller subtracts it
+// once from its diagonal block and right-hand side ("_sub" rounding), or stores it as a packed update for wb_sub_update to subtract later —
+// the same 27 numbers either way.
+template <class Put, class PutRhs>
+__device__ __forceinline__ void wb_outer_lower(const double (&B)[36], const double (&y)[6], Put put, PutRhs put_rhs) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+        for (int c = 0; c <= r; ++c) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc = __builtin_fma(B[6 * k + r], B[6 * k + c], acc);
+            put(r, c, acc);
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc = __builtin_fma(B[6 * k + r], y[k], acc);
+        put_rhs(r, acc);
+    }
+}
+// block times block^T, "_fms": S(r, c) -= sum_k Li(r, k) Lj(c, k), every term FMA'd into S, k ascending; all three column-major.  Li and Lj
+// are read from memory a column at a time (the k loop indexes memory only and is left to the compiler).
+__device__ __forceinline__ void wb_block_blockT_fms(const double* Li, const double* Lj, double (&S)[36]) {
+    for (int k = 0; k < 6; ++k) {
+        double li[6], lj[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) { li[r] = Li[6 * k + r]; lj[r] = Lj[6 * k + r]; }
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+#pragma unroll
+            for (int r = 0; r < 6; ++r) S[6 * c + r] = __builtin_fma(-li[r], lj[c], S[6 * c + r]);
+    }
+}
+// block^T times vector, "_sub": t_c -= sum_r B(r, c) x_r, the sum an FMA chain from 0 with r ascending, subtracted once
+__device__ __forceinline__ void wb_blockT_vec_sub(const double* B, const double (&x)[6], double (&t)[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        double acc = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) acc = __builtin_fma(B[6 * c + r], x[r], acc);
+        t[c] -= acc;
+    }
+}
+// block^T times vector, "_fms": every term FMA'd into t_c, r ascending (other bits than wb_blockT_vec_sub's)
+__device__ __forceinline__ void wb_blockT_vec_fms(const double* B, const double (&x)[6], double (&t)[6]) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) t[c] = __builtin_fma(-B[6 * c + r], x[r], t[c]);
 }
 }  // namespace
 }  // namespace locamd

@@ -34,7 +34,9 @@
 //     order: every thread holds the same bits);
 //   * 6x6 block steps (the Cholesky factor of a diagonal block, row solves against it, its store, block products) are stated in
 //     window_block_device.h with their rounding order and pivot rule: the SKYLINE sweep and the root supernode take theirs from
-//     there; the level-by-level routines call four of them and still write the rest out.
+//     there; the level-by-level routines call four of them and keep the rest written out as deliberate copies: each was tried
+//     as a call and moved the kernel's registers or its time, and its comment says by how much;
+//     tests/test_gpu_window_block_bits.py holds the kernel to the bits it had before the first step was shared.
 #include "se3_edge_device.h"
 #include "window_layouts.h"
 #include "window_block_device.h"
@@ -1707,7 +1709,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                                 if (!GLOBAL_A) wb_sub_update(G, y, L.Us + 28 * K);
                                 continue;
                             }
-                            // (the lower triangle of B B^T and B y_K, then wb_sub_update's subtraction, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                            // (wb_outer_lower with a subtracting sink, written out: as that call the SGPR spill counts of two eight-word instantiations moved, 412 -> 410 and 455 -> 453; as a 27-entry array handed to wb_sub_update the scratch size of six — DESIGN.md §2)
                             const double* blk = L.Ls + rowJ + 36 * kb;
                             double bl[36], yk[6];
 #pragma unroll
@@ -1731,7 +1733,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         }
                     }
                     LOCAMD_SUB(1);
-                    // (wb_chol_left in place and wb_forward_row on y, with the factor's stores between them, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                    // (wb_chol_left in place and wb_forward_row on y, with the factor's stores between them, written out: as calls every register row stayed, and uwb_twist in numeric mode ran in 42.21 .. 42.30 ms against a limit of 42.06 — DESIGN.md §2)
 #pragma unroll
                     for (int j = 0; j < 6; ++j) {
                         double dj = G[j][j];
@@ -1782,7 +1784,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                             m &= m - 1;
                             const double* bki = L.Ls + rowi + 36 * row_rank<W>(L, i, K);
                             const double* bkj = L.Ls + rowJ + 36 * row_rank<W>(L, J, K);
-                            // (block times block^T, FMA'd into S: not in window_block_device.h yet)
+                            // (wb_block_blockT_fms, written out: as a call the scratch size of six eight-word instantiations moved, 300 -> 292 bytes in the first — DESIGN.md §2)
                             for (int k = 0; k < 6; ++k) {
                                 double li[6], lj[6];
 #pragma unroll
@@ -1794,7 +1796,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                             }
                         }
                         }
-                        // (wb_forward_row for each of the block's six rows, written out; below it the pushed update B B^T, B y — DESIGN.md §2)
+                        // (wb_forward_row for each of the block's six rows and, below it, wb_outer_lower with a storing sink, written out: as calls the scratch size of the same six instantiations moved — DESIGN.md §2)
 #pragma unroll
                         for (int r = 0; r < 6; ++r) {
 #pragma unroll
@@ -1889,7 +1891,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                     for (int k = 0; k < 6; ++k) li[k] = blk[6 * k + r];
 #pragma unroll
                     for (int q = 0; q < 36; ++q) bj[q] = W > 1 ? blk[q] : 0.0;   // (one-word windows: the products read in place, as measured best there)
-                    // (wb_row_block_sub, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                    // (wb_row_block_sub, written out: with the three sites as calls the scratch size of one eight-word instantiation moved, 204 -> 252 bytes — DESIGN.md §2)
 #pragma unroll
                     for (int c = 0; c < 6; ++c) {
                         double acc = 0.0;
@@ -1954,7 +1956,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         for (int k = 0; k < 6; ++k) li[k] = bki[6 * k + r];
 #pragma unroll
                         for (int q = 0; q < 36; ++q) bj[q] = W > 1 ? bkj[q] : 0.0;
-                        // (wb_row_block_sub, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                        // (wb_row_block_sub, written out: with the three sites as calls the scratch size of one eight-word instantiation moved, 204 -> 252 bytes — DESIGN.md §2)
 #pragma unroll
                         for (int c = 0; c < 6; ++c) {
                             double acc = 0.0;
@@ -1995,7 +1997,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                         for (int k = 0; k < 6; ++k) li[k] = L.yrow[6 * K + k];
 #pragma unroll
                         for (int q = 0; q < 36; ++q) bj[q] = W > 1 ? bkj[q] : 0.0;
-                        // (wb_row_block_sub, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                        // (wb_row_block_sub, written out: with the three sites as calls the scratch size of one eight-word instantiation moved, 204 -> 252 bytes — DESIGN.md §2)
 #pragma unroll
                         for (int c = 0; c < 6; ++c) {
                             double acc = 0.0;
@@ -2007,7 +2009,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                     }
                 }
                 // G_J from the raw diagonal block: entry (p, q), p >= q, at dJ + 6 p + q
-                // (wb_chol_left from memory, wb_store_factor_row, wb_forward_row, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                // (wb_chol_left from memory, wb_store_factor_row, wb_forward_row, written out: as calls with G loaded first selfcal ran in 13.62 .. 13.80 ms against a limit of 13.55; with the memory source handed to wb_chol_left the SGPR spill counts of eleven instantiations moved — DESIGN.md §2)
                 double G[6][6], ig[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
@@ -2096,7 +2098,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                     double xi[6];
 #pragma unroll
                     for (int r = 0; r < 6; ++r) xi[r] = L.x[6 * i + r];
-                    // (block^T times vector, summed then subtracted: not in window_block_device.h yet)
+                    // (wb_blockT_vec_sub, written out with the back-solve below it)
 #pragma unroll
                     for (int c = 0; c < 6; ++c) {
                         double acc = 0.0;
@@ -2108,7 +2110,7 @@ __device__ __forceinline__ bool factor_and_solve_sparse(const Lds& L, int lane, 
                 }
                 LOCAMD_SUB3(1);
                 double xs[6];
-                // (wb_back_solve_gather with G and the inverse pivots read in place, written out: window_block_device.h states the step, this site does not call it yet — DESIGN.md §2)
+                // (wb_back_solve_gather, written out: as calls with G loaded first this and the product above cost pose64 0.27 ms of 17.8; with the factor and the inverse pivots read in place through callables every register row stayed and pose64 ran in 18.47 .. 18.49 ms against a limit of 18.28 — DESIGN.md §2)
 #pragma unroll
                 for (int rr = 5; rr >= 0; --rr) {
                     double v = t[rr];
@@ -2308,7 +2310,7 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
                     for (int q = 0; q < 6; ++q) A[q][q] += lambda;
 #pragma unroll
                     for (int j = 0; j < 6; ++j) {
-                        // (wb_chol_right, wb_forward_row_scatter and wb_inverse_pivots_finite, written out: window_block_device.h states the steps, this site does not call them yet — DESIGN.md §2)
+                        // (wb_chol_right, wb_forward_row_scatter and wb_inverse_pivots_finite, written out: as calls every register row stayed, and uwb_imu in numeric mode ran in 26.93 .. 26.99 ms against a limit of 26.92, as it had on its own before — DESIGN.md §2)
                         // (a pivot <= 0 or not finite turns its reciprocal square root into NaN / inf, which the sum below catches)
                         const double g = pivot_rsqrt(A[j][j]);
                         ig[j] = g;
@@ -2367,7 +2369,7 @@ __device__ __forceinline__ bool factor_and_solve_small(const Lds& L, int lane, i
                 for (int q = 0; q < 36; ++q) bv[q] = bk[q];
 #pragma unroll
                 for (int r = 0; r < 6; ++r) xi[r] = L.x[6 * i + r];
-                // (block^T times vector, FMA'd into t: not in window_block_device.h yet)
+                // (wb_blockT_vec_fms, written out with stage B above)
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
 #pragma unroll

@@ -414,6 +414,8 @@ def test_block_row_solves(gpu, op, ref):
     assert np.array_equal(_probe(op, ints, 6), exact), op      # integer operands: exact
     if op == "wb_forward_row_scatter":                          # the same FMAs in the same order per entry: the gather form's bits
         assert np.array_equal(dev.view(np.uint64), _probe("wb_forward_row", rnd, 6).view(np.uint64))
+    if op == "wb_back_solve_gather":                            # factor and inverse pivots through callables: the register form's bits
+        assert np.array_equal(dev.view(np.uint64), _probe("wb_back_solve_gather_in_place", rnd, 6).view(np.uint64))
 
 
 def test_block_factor_row_store_and_load(gpu):
@@ -430,7 +432,7 @@ def test_block_factor_row_store_and_load(gpu):
         assert np.array_equal(part != 0, np.isin(np.arange(42), [6 * c + r for c in range(r)] + [36 + r])[None, :] & (want != 0)), r
         rows += part
     assert np.array_equal(rows, want)
-    back = _probe("wb_load_factor", np.concatenate([rnd[:, :42], np.zeros((len(rnd), 1))], axis=1), 42)
+    back =_probe("wb_load_factor", np.concatenate([rnd[:, :42], np.zeros((len(rnd), 1))], axis=1), 42)
     assert np.array_equal(back[:, LOWER], rnd[:, LOWER]) and np.array_equal(back[:, 36:], rnd[:, 36:42])
     assert not np.delete(back[:, :36], LOWER, axis=1).any()   # nothing on or above the diagonal is loaded
 
@@ -446,7 +448,17 @@ def test_block_products(gpu):
     table = [
         ("wb_dot_fms", (6, 6, 1), 1, lambda C, a, b, o: [P.dot_sub(C, a, b, o[0])], ()),
         ("wb_row_block_sub", (6, 36, 6), 6, lambda C, li, B, S: [P.dot_sub(C, li, B[c], S[c]) for c in range(6)], (1,)),
+        # the lower triangle of B B^T and B y_K taken off (G, y) — G row-major, as the probe takes it; the output's upper triangle is 0
+        ("wb_outer_lower_sub", (36, 6, 36, 6), 42, lambda C, B, yk, G, y: [P.dot_sub(C, B[r], B[c], G[r][c]) if c <= r else C.num(0) for r in range(6) for c in range(6)]
+                                                                         + [P.dot_sub(C, B[r], yk, y[r]) for r in range(6)], (0,)),
+        ("wb_outer_lower_packed", (36, 6), 27, lambda C, B, yk: [-P.dot_sub(C, B[r], B[c], C.num(0)) for r in range(6) for c in range(r + 1)]
+                                                               + [-P.dot_sub(C, B[r], yk, C.num(0)) for r in range(6)], (0,)),
+        # S - Li Lj^T, all three column-major (the definition's output in that order too)
+        ("wb_block_blockT_fms", (36, 36, 36), 36, lambda C, Li, Lj, S: [P.dot_sub(C, Li[r], Lj[c], S[r][c]) for c in range(6) for r in range(6)], (0, 1, 2)),
+        ("wb_blockT_vec_sub", (36, 6, 6), 6, lambda C, B, x, t: [P.dot_sub(C, [B[r][c] for r in range(6)], x, t[c]) for c in range(6)], (0,)),
+        ("wb_blockT_vec_fms", (36, 6, 6), 6, lambda C, B, x, t: [P.dot_sub(C, [B[r][c] for r in range(6)], x, t[c]) for c in range(6)], (0,)),
     ]
+    kept = {}
     for op, widths, no, f, blocks in table:
         rnd, ints = operands(*widths)
         def split(row):
@@ -461,6 +473,12 @@ def test_block_products(gpu):
         _hold(op, dev, [p[0] for p in pairs], [p[1] for p in pairs])
         exact = np.array([_both(f, *split(r))[0] for r in ints])
         assert np.array_equal(_probe(op, ints, no), exact), op
+        kept[op] = (rnd, dev)
+    # the packed form's 27 sums are the subtract form's: taken off zero targets they come back negated, bit for bit
+    rnd, packed = kept["wb_outer_lower_packed"]
+    off_zero = _probe("wb_outer_lower_sub", np.concatenate([rnd, np.zeros((n, 42))], axis=1), 42)
+    tri = [6 * r + c for r in range(6) for c in range(r + 1)] + list(range(36, 42))
+    assert np.array_equal(off_zero[:, tri], -packed) and not np.delete(off_zero, tri, axis=1).any()
     # a packed update taken off a diagonal block and its right-hand side: one subtraction per entry, exact to the last bit in float64
     rows = rng.normal(size=(n, 69))
     got = _probe("wb_sub_update", rows, 42)

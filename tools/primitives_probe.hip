@@ -128,8 +128,8 @@ struct OpCholRight {   // (the diagonal of the output keeps the pivots)
         wbp_factor_out(A, ig, wb_inverse_pivots_finite(ig), out);
     }
 };
-template <int FORM>   // G, ig, s -> x.  0: wb_forward_row, 1: wb_forward_row_scatter, 2: wb_back_solve_gather, 3: wb_back_solve_scatter
-struct OpRowSolve {
+template <int FORM>   // G, ig, s -> x.  0: wb_forward_row, 1: wb_forward_row_scatter, 2: wb_back_solve_gather, 3: wb_back_solve_scatter,
+struct OpRowSolve {   // 4: wb_back_solve_gather with the factor and the inverse pivots read where they lie (callable sources)
     static constexpr int NI = 48, NO = 6;
     __device__ static void run(const double* in, double* out) {
         double G[6][6], ig[6], s[6], x[6];
@@ -138,6 +138,7 @@ struct OpRowSolve {
         if (FORM == 0) wb_forward_row(x, G, ig);
         else if (FORM == 1) wb_forward_row_scatter(x, G, ig);
         else if (FORM == 2) wb_back_solve_gather(s, G, ig, x);
+        else if (FORM == 4) wb_back_solve_gather(s, [&](int s2, int rr) { return in[6 * s2 + rr]; }, [&](int rr) { return in[36 + rr]; }, x);
         else wb_back_solve_scatter(s, G, ig, x);
         for (int c = 0; c < 6; ++c) out[c] = x[c];
     }
@@ -162,6 +163,45 @@ struct OpStoreFactorRow {   // of that row (a run-time index); LOAD: wb_load_fac
             }
         }
         for (int k = 0; k < 42; ++k) out[k] = mem[k];
+    }
+};
+template <bool PACKED>   // B (column-major), y_K, then (!PACKED) G (row-major, lower), y -> G - lower(B B^T) (row-major, the rest 0), y - B y_K;
+struct OpOuterLower {    // PACKED: -> the 27 sums as a packed update
+    static constexpr int NI = PACKED ? 42 : 84, NO = PACKED ? 27 : 42;
+    __device__ static void run(const double* in, double* out) {
+        double B[36], yk[6];
+        for (int k = 0; k < 36; ++k) B[k] = in[k];
+        for (int k = 0; k < 6; ++k) yk[k] = in[36 + k];
+        if (PACKED) wb_outer_lower(B, yk, [&](int r, int c, double v) { out[wb_tri(r, c)] = v; }, [&](int r, double v) { out[21 + r] = v; });
+        else {
+            double G[6][6], y[6];
+            wbp_factor_in(in + 42, G, y);
+            wb_outer_lower(B, yk, [&](int r, int c, double v) { G[r][c] -= v; }, [&](int r, double v) { y[r] -= v; });
+            for (int r = 0; r < 6; ++r) {
+                for (int c = 0; c < 6; ++c) out[6 * r + c] = c <= r ? G[r][c] : 0.0;
+                out[36 + r] = y[r];
+            }
+        }
+    }
+};
+struct OpBlockBlockTFms {   // Li, Lj, S (all column-major) -> S - Li Lj^T
+    static constexpr int NI = 108, NO = 36;
+    __device__ static void run(const double* in, double* out) {
+        double S[36];
+        for (int k = 0; k < 36; ++k) S[k] = in[72 + k];
+        wb_block_blockT_fms(in, in + 36, S);
+        for (int k = 0; k < 36; ++k) out[k] = S[k];
+    }
+};
+template <bool FMS>   // B (column-major), x, t -> t - B^T x: wb_blockT_vec_sub / wb_blockT_vec_fms
+struct OpBlockTVec {
+    static constexpr int NI = 48, NO = 6;
+    __device__ static void run(const double* in, double* out) {
+        double x[6], t[6];
+        for (int k = 0; k < 6; ++k) { x[k] = in[36 + k]; t[k] = in[42 + k]; }
+        if (FMS) wb_blockT_vec_fms(in, x, t);
+        else wb_blockT_vec_sub(in, x, t);
+        for (int k = 0; k < 6; ++k) out[k] = t[k];
     }
 };
 struct OpDotFms { static constexpr int NI = 13, NO = 1; __device__ static void run(const double* in, double* out) { out[0] = wb_dot_fms(in, in + 6, in[12]); } };
@@ -277,9 +317,11 @@ static const Entry kOps[] = {
     ROWS("fast_log_ge1", OpFastLogGe1), ROWS("fast_log_ge1_scaled", OpFastLogGe1Scaled),
     ROWS("wb_chol_left", OpCholLeft<false>), ROWS("wb_chol_left_in_place", OpCholLeft<true>), ROWS("wb_chol_right", OpCholRight),
     ROWS("wb_forward_row", OpRowSolve<0>), ROWS("wb_forward_row_scatter", OpRowSolve<1>),
-    ROWS("wb_back_solve_gather", OpRowSolve<2>), ROWS("wb_back_solve_scatter", OpRowSolve<3>),
+    ROWS("wb_back_solve_gather", OpRowSolve<2>), ROWS("wb_back_solve_scatter", OpRowSolve<3>), ROWS("wb_back_solve_gather_in_place", OpRowSolve<4>),
     ROWS("wb_store_factor_row", OpStoreFactorRow<false>), ROWS("wb_load_factor", OpStoreFactorRow<true>),
     ROWS("wb_dot_fms", OpDotFms), ROWS("wb_row_block_sub", OpRowBlockSub), ROWS("wb_sub_update", OpSubUpdate),
+    ROWS("wb_outer_lower_sub", OpOuterLower<false>), ROWS("wb_outer_lower_packed", OpOuterLower<true>),
+    ROWS("wb_block_blockT_fms", OpBlockBlockTFms), ROWS("wb_blockT_vec_sub", OpBlockTVec<false>), ROWS("wb_blockT_vec_fms", OpBlockTVec<true>),
     {"wave_sum", 64, 64, launch_wave<WvSum>}, {"wave_max", 64, 64, launch_wave<WvMax>},
     {"lane_from_prev", 64, 64, launch_wave<WvPrev>}, {"lane_from_next", 64, 64, launch_wave<WvNext>},
     BLOCKS("block_sum", 0), BLOCKS("block_max", 1), BLOCKS("block_any", 2),
