@@ -292,7 +292,9 @@ enum { LOC_WINDOW_KERNEL_NONE = -1, LOC_WINDOW_KERNEL_GENERAL = 0, LOC_WINDOW_KE
        LOC_WINDOW_KERNEL_TREE_LANE = 5 /* reported only: the lane-per-window variant of TREE ran */,
        LOC_WINDOW_KERNEL_WAVE3 = 6 /* translation-only chains of <= 64 poses: one wave per window (wave3_lm_kernel) */,
        LOC_WINDOW_KERNEL_WAVE6 = 7 /* 6-DoF chains of <= 64 poses (no EdgeSE3, one range edge per consecutive pair): wave6_lm_kernel */,
-       LOC_WINDOW_KERNEL_WAVE6S = 8 /* the same with EdgeSE3 factors between consecutive poses (cfg/uwb_twist.yaml), at most one per pair: wave6_lm_kernel<.., SE3> */ };
+       LOC_WINDOW_KERNEL_WAVE6S = 8 /* the same with EdgeSE3 factors between consecutive poses (cfg/uwb_twist.yaml), at most one per pair: wave6_lm_kernel<.., SE3> */,
+       LOC_WINDOW_KERNEL_TREE_GROUPS = 9 /* option "forest_groups": forest windows of DIFFERING topologies, one wave per window on the schedule of the
+                                            window's group (tree_wave_kernel<JAC, TreeGroups>); TREE's batch threshold */ };
 int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
 /* Kernel-selection switches of ONE handle.  They are read from the environment ONCE, when the handle is created (LOCAMD_CHAIN_MIN_BATCH,
  * LOCAMD_ARROW3, LOCAMD_TREE, LOCAMD_WAVE3, LOCAMD_WAVE6, LOCAMD_CHAIN3, LOCAMD_NO_ZERO_COPY: A/B runs and tests), never at solve
@@ -319,6 +321,19 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *                      entry or the option is 0 (until the next upload), and its covariance pass is classified again.
  *   "resident_slide"  0 (default) / 1: loc_window_upload keeps a host mirror of the batch's integer tables (counts, r_idx, p_idx), which
  *                      loc_window_slide_resident needs; read at upload time.  0: an upload allocates and does exactly what it did without the option.
+ *   "forest_groups"   0 (default) / 1: a batch of FOREST windows of <= 64 poses whose topologies differ — key-frame windows cut from different
+ *                      robots or at different phases of the key cadence (Localization::addPoseEdge, localization.cpp:254-290): other parents,
+ *                      other lengths, other anchors — is grouped by topology (the four counts and the used index rows; anchor numbers and
+ *                      robust flags do not count) and solved on LOC_WINDOW_KERNEL_TREE_GROUPS with one schedule per group, by
+ *                      loc_window_solve_host and by loc_window_upload + loc_window_solve_resident.  Looked at only after the one-topology test
+ *                      has declined the batch: a batch of one topology takes LOC_WINDOW_KERNEL_TREE as without the option, bit for bit.  The
+ *                      batch stays on the general kernel when any window has fewer than 2 poses, a cycle, or two EdgeSE3 factors on one pair of
+ *                      poses; under option "tree" = 0 or 2; below TREE's batch threshold; with endpoint-1 lever arms or a table of full
+ *                      information matrices; on a handle with nv_max > 64.  loc_window_upload_dev does not group (such a batch solves on the
+ *                      general kernel), and covariances of such a batch are served as without the option (the envelope pass under
+ *                      "covariance_general", else LOC_ERR_UNSUPPORTED).  Measured at 16 384 x 64 poses: the solve 3.5 ... 4.8 times faster than on
+ *                      the general kernel for 1 ... 16 384 groups; the upload 3 ... 7 ms slower up to 256 groups and 46 ms slower (102 MB of
+ *                      schedule tables) with a topology per window — there the option pays from the fourth resident solve on (README).
  *   "upload_dev_structures"  0 (default) / 1: loc_window_upload_dev also takes the ARROWHEAD and FOREST verdicts on the device (see there), so
  *                      that such a batch runs on LOC_WINDOW_KERNEL_ARROW3 / _TREE and their covariance passes exactly as after loc_window_upload
  *                      of the same arrays; read at upload time.  0: loc_window_upload_dev does exactly what it did without the option.
@@ -328,6 +343,10 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value);
  * choice: hash of the index tables, chain / forest / arrowhead tests, host-built schedules), [2] staging + launch + copy back +
  * synchronise, [3] 1.0 when the structural verdict came from the handle's cache, else 0.0 */
 int loc_window_last_host_timing(const loc_window* w, double* validate_topology_run_cached);
+/* Option "forest_groups": what the handle's LAST structural verdict — of a loc_window_solve_host call or of an upload, whichever came last —
+ * found: the number of topology groups and the size in bytes of the block sent to the device (headers, window -> group map, the groups'
+ * schedule tables).  0 and 0 when that batch is not on the grouped path. */
+int loc_window_forest_groups(const loc_window* w, int32_t* n_groups, int64_t* table_bytes);
 /* Device-resident operation: upload n instances once (same host layouts as loc_window_solve_host), then run
  * loc_window_solve_resident any number of times — each launch starts from the uploaded estimates, is asynchronous on
  * hip_stream (NULL = the handle's own stream) and leaves poses / result on the device — and fetch them with

@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = [
     "loc_snapshot_solve_host_kmb", "loc_snapshot_solve_device_cov", "loc_snapshot_solve_host_kmb_cov", "loc_host_alloc", "loc_host_free",
     "loc_snapshot_timing_begin", "loc_snapshot_timing_end",
     "loc_window_create", "loc_window_destroy", "loc_window_set_anchors", "loc_window_lds_bytes", "loc_window_solve_host",
-    "loc_window_last_kernel_ms", "loc_window_set_endpoint1_offsets", "loc_window_set_prior_information", "loc_window_set_jacobian", "loc_window_set_ordering", "loc_window_set_chain_threshold", "loc_window_last_kernel_kind", "loc_window_set_option", "loc_window_last_host_timing", "loc_window_upload", "loc_window_upload_dev",
+    "loc_window_last_kernel_ms", "loc_window_set_endpoint1_offsets", "loc_window_set_prior_information", "loc_window_set_jacobian", "loc_window_set_ordering", "loc_window_set_chain_threshold", "loc_window_last_kernel_kind", "loc_window_set_option", "loc_window_last_host_timing", "loc_window_forest_groups", "loc_window_upload", "loc_window_upload_dev",
     "loc_window_solve_resident", "loc_window_download", "loc_window_poses_device", "loc_window_result_device",
     "loc_window_timing_begin", "loc_window_timing_end",
     "loc_window_covariance_host", "loc_window_covariance_resident", "loc_window_last_covariance_ms", "loc_window_covariance_plan",
@@ -114,6 +114,7 @@ def lib():
     L.loc_window_set_ordering.argtypes = [vp, C.c_int32]
     L.loc_window_set_chain_threshold.argtypes = [vp, C.c_int64]
     L.loc_window_last_kernel_kind.argtypes = [vp, ip]
+    L.loc_window_forest_groups.argtypes = [vp, ip, C.POINTER(C.c_int64)]
     L.loc_window_upload.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp]
     L.loc_window_upload_dev.argtypes = [vp, vp, C.c_int64] + [vp] * 9
     L.loc_window_solve_resident.argtypes = [vp, vp]

@@ -90,6 +90,8 @@ struct loc_window {
     locamd::DispatchFits fits;      // what the capacities alone decide, from loc_window_create
     locamd::TopoCache topo_cache;   // the host path's structural verdict
     double t_validate_ms = 0, t_topology_ms = 0, t_run_ms = 0;   // loc_window_last_host_timing
+    int32_t last_groups = 0;        // loc_window_forest_groups: what the last structural verdict (host path or upload) found
+    int64_t last_groups_bytes = 0;
     bool t_cached = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -146,7 +148,7 @@ size_t loc_window_lds_bytes(const loc_window_caps* caps) {
 // every device buffer of one batch's slot
 static void release_slot(loc_window::BatchSlot& S) {
     for (locamd::WinAux* A : {&S.aux, &S.cov_aux})
-        for (void* p : {(void*)A->d_tsched, (void*)A->d_ahdr, (void*)A->d_arslot, (void*)A->d_arec, (void*)A->d_aprec}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)A->d_tsched, (void*)A->d_groups, (void*)A->d_ahdr, (void*)A->d_arslot, (void*)A->d_arec, (void*)A->d_aprec}) if (p) (void)hipFree(p);
     if (S.d_cov_ws) (void)hipFree(S.d_cov_ws);
     if (S.d_env_ws) (void)hipFree(S.d_env_ws);
 }
@@ -353,8 +355,15 @@ static hipError_t upload_arrow_aux(loc_window* w, loc_window::BatchSlot& S, int6
 }
 
 // solve: the schedule is for a solve kernel (tree_lm_kernel's workspace is allocated); the covariance pass needs the tables alone
-static hipError_t upload_tree_sched(loc_window* w, locamd::WinAux& A, hipStream_t st, bool solve = true) {
+// groups: the batch is on the grouped path (LOC_WINDOW_KERNEL_TREE_GROUPS) — the block [hdr | sched_of | pad | tables] of build_tree_groups
+// goes instead, into a buffer of its own (the one-topology table of the same slot stays as it is)
+static hipError_t upload_tree_sched(loc_window* w, locamd::WinAux& A, hipStream_t st, bool solve = true, bool groups = false) {
     hipError_t e;
+    if (groups) {
+        if ((e = locamd::grow_buffers(A.groups_cap, A.h_groups.size(), {{A.d_groups, A.h_groups.size() * sizeof(int32_t)}})) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(A.d_groups, A.h_groups.data(), A.h_groups.size() * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        return hipStreamSynchronize(st);
+    }
     if ((e = locamd::grow_buffers(A.tsched_cap, A.h_tsched.size(), {{A.d_tsched, A.h_tsched.size() * sizeof(int32_t)}})) != hipSuccess) return e;
     if (solve && !w->d_tree_ws && (e = hipMalloc((void**)&w->d_tree_ws, locamd::window_tree_workspace_doubles(w->caps, w->B) * sizeof(double))) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(A.d_tsched, A.h_tsched.data(), A.h_tsched.size() * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
@@ -474,6 +483,11 @@ static hipError_t launch_any(loc_window* w, loc_window::BatchSlot& S, const loca
         }
         return locamd::launch_window_tree_wave(a, A.tsched, st);
     }
+    if (kind == LOC_WINDOW_KERNEL_TREE_GROUPS) {
+        if (A.n_groups <= 0 || !A.d_groups) return hipErrorInvalidValue;
+        const locamd::TreeGroups g{A.d_groups, A.d_groups + A.groups_of_at, A.d_groups + A.groups_tab_at, A.n_groups};
+        return locamd::launch_window_tree_wave_groups(a, g, A.h_groups.data(), st);
+    }
     if (kind == LOC_WINDOW_KERNEL_CHAIN3) {
         if (!w->d_chain3_ws) {
             hipError_t e = hipMalloc((void**)&w->d_chain3_ws, locamd::window_chain3_workspace_doubles(w->caps, w->B) * sizeof(double));
@@ -512,6 +526,7 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
     if (k == "chain_min_batch") { o.chain_min = value; return LOC_OK; }
     if (k == "arrow3") { if (value < -1 || value > 1) return locamd_fail(LOC_ERR_INVALID, "set_option arrow3: -1, 0 or 1"); o.arrow3 = (int)value; w->topo_cache.valid = false; return LOC_OK; }
     if (k == "tree") { if (value != -1 && value != 0 && value != 2) return locamd_fail(LOC_ERR_INVALID, "set_option tree: -1, 0 or 2"); o.tree = (int)value; w->topo_cache.valid = false; return LOC_OK; }
+    if (k == "forest_groups") { w->topo_cache.valid = false; return flag(o.forest_groups); }   // (read by the structure test: loc_window_solve_host, loc_window_upload)
     if (k == "wave3") return flag(o.wave3);
     if (k == "wave6") return flag(o.wave6);
     if (k == "chain3") return flag(o.chain3);
@@ -540,6 +555,12 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
 int loc_window_last_host_timing(const loc_window* w, double* out) {
     if (!w || !out) return locamd_fail(LOC_ERR_INVALID, "null");
     out[0] = w->t_validate_ms; out[1] = w->t_topology_ms; out[2] = w->t_run_ms; out[3] = w->t_cached ? 1.0 : 0.0;
+    return LOC_OK;
+}
+
+int loc_window_forest_groups(const loc_window* w, int32_t* n_groups, int64_t* table_bytes) {
+    if (!w || !n_groups || !table_bytes) return locamd_fail(LOC_ERR_INVALID, "null");
+    *n_groups = w->last_groups; *table_bytes = w->last_groups_bytes;
     return LOC_OK;
 }
 
@@ -598,10 +619,18 @@ int loc_window_set_ordering(loc_window* w, int32_t natural) {
     return LOC_OK;
 }
 
+// loc_window_forest_groups: a structural verdict's groups (none unless it is the grouped path's)
+static void note_groups(loc_window* w, const locamd::WinAux& A, int topology) {
+    const bool on = topology == LOC_WINDOW_KERNEL_TREE_GROUPS;
+    w->last_groups = on ? A.n_groups : 0;
+    w->last_groups_bytes = on ? (int64_t)(A.h_groups.size() * sizeof(int32_t)) : 0;
+}
+
 // the kernel of a host-path batch: its structure (slot[0]'s tables, the topology cache), then the rules of the moment
 static int host_kernel(loc_window* w, const locamd::HostBatch& b) {
     const locamd::Topology t = locamd::batch_topology(w->caps, w->opt, w->fits, w->n_anchors, b, w->slot[0].aux, &w->topo_cache);
     w->t_cached = t.cached;
+    note_groups(w, w->slot[0].aux, t.kind);
     return locamd::pick_kernel(w->opt, w->fits, b.n, t.kind);
 }
 
@@ -657,6 +686,7 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
         if (events) LOC_HIP(hipEventRecord(w->ev0, st));
         if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, w->slot[0], n, st));
         if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->slot[0].aux, st));
+        if (kind == LOC_WINDOW_KERNEL_TREE_GROUPS) LOC_HIP(upload_tree_sched(w, w->slot[0].aux, st, true, true));
         const auto t_launch = clk::now();
         hipError_t e = launch_any(w, w->slot[0], a, st, kind);
         if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
@@ -682,6 +712,7 @@ int loc_window_solve_host(loc_window* w, int64_t n, const int32_t* counts, doubl
     const locamd::WindowArgs a = window_args(w, w->dev, n, nullptr, w->d_anchors, w->d_result);
     if (kind == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, w->slot[0], n, st));
     if (kind == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, w->slot[0].aux, st));
+    if (kind == LOC_WINDOW_KERNEL_TREE_GROUPS) LOC_HIP(upload_tree_sched(w, w->slot[0].aux, st, true, true));
     LOC_HIP(hipEventRecord(w->ev0, st));
     hipError_t e = launch_any(w, w->slot[0], a, st, kind);
     if (e != hipSuccess) return locamd_fail_hip(e, "launch_window");
@@ -717,6 +748,9 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     const int topology = locamd::batch_topology(c, w->opt, w->fits, w->n_anchors, b, S.aux, nullptr).kind;
     if (topology == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, S, n, w->stream));
     if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, S.aux, w->stream));
+    // (the grouped forest: its covariance pass is classified by the first covariance call, as any batch the structured passes may decline)
+    if (topology == LOC_WINDOW_KERNEL_TREE_GROUPS) LOC_HIP(upload_tree_sched(w, S.aux, w->stream, true, true));
+    note_groups(w, S.aux, topology);
     R.min_anchors = locamd::max_anchor_referenced(c, n, counts, r_idx);
     R.counts.assign(counts, counts + (size_t)n * 4);
     if (w->opt_slide) {   // the mirror of loc_window_slide_resident
@@ -873,6 +907,7 @@ int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void
         R.mirror_valid = true;
     }
     R.mirror_stale = true;   // (refresh_mirror: the first reader of counts or the mirror fetches them)
+    note_groups(w, w->slot[1].aux, topology);   // (never the grouped path: a mixed forest batch in device arrays solves on the general kernel)
     R.topology = topology;
     R.skip = locamd::structured_pinfo(w->opt);
     R.cov = cov;

@@ -4,6 +4,9 @@
 // (Localization::solve, localization.cpp:164-170).  The same residuals and the same LM as every other window
 // kernel here; the elimination schedule (parent, height, children and edge lists per pose slot) is built once per batch by the host
 // (capi_window.cpp: build_tree_sched) and shared by every window.
+// Windows of DIFFERING topologies — cut from different robots, or at different phases of the key cadence of localization.cpp:254-290 — run the
+// same kernel with one schedule per group of windows of one topology (option "forest_groups"; SCHED = TreeGroups, wave_sched below;
+// instantiated in tree_wave_groups_kernel.hip).
 //
 // tree_lm_kernel (tree_kernel.hip) walks a window's 64 nodes one after the other in one lane.  Here the 64 nodes are the 64 lanes:
 //   * linearisation and trial scoring: every lane evaluates ITS node's edges (its EdgeSE3 to the parent, its ranges, its priors);
@@ -30,6 +33,7 @@
 // (correct, slower) generic loops over the tables in memory.
 #include "se3_edge_device.h"
 #include "lm_damping.h"
+#include "window_layouts.h"
 
 namespace locamd {
 namespace {
@@ -275,8 +279,26 @@ __device__ __forceinline__ void wave_node_edges(const WindowArgs& a, const TreeS
     }
 }
 
-template <int JAC>
-__global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, const TreeSched ts) {
+// The schedule of the wave's window.  SCHED = TreeSched: the one schedule of the batch, whose r_idx / s_idx sections are every window's rows.
+// SCHED = TreeGroups (option "forest_groups"): windows of differing topologies, cut from different robots or at different phases of the key
+// cadence of Localization::addPoseEdge (localization.cpp:254-290) — the wave reads its window's group and that group's header (wave-uniform
+// loads through blockIdx.x), binds the schedule's pointers from the group's table with the host's own function (tree_sched_bind), and points
+// r_idx / s_idx at the window's OWN rows: a group's windows share parents, heights and edge lists, not anchor numbers or robust flags, and
+// every index look-up of the kernel — the prologue's, the generic loops', the anchor number, the robust flag — goes through these two
+// pointers.  nv, nu, nlev, nroots are then per-wave values; lanes >= nv idle as before.
+__device__ __forceinline__ const TreeSched& wave_sched(const TreeSched& ts, const WindowArgs&, long long) { return ts; }
+__device__ __forceinline__ TreeSched wave_sched(const TreeGroups& g, const WindowArgs& a, long long inst) {
+    const int32_t* h = g.hdr + (size_t)g.sched_of[inst] * kTreeGroupHdr;
+    TreeSched ts;
+    tree_group_sizes(ts, h);
+    tree_sched_bind(ts, g.tables + h[10]);
+    ts.r_idx = a.r_idx + (size_t)inst * a.caps.nr_max * 2;
+    ts.s_idx = a.s_idx + (size_t)inst * a.caps.ns_max * 4;
+    return ts;
+}
+
+template <int JAC, class SCHED>
+__global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, const SCHED sched) {
     __shared__ double sv_lds[48 * 64];    // [entry][lane]: the EdgeSE3 record of the lane's node (Z^-1 as R t, information 6x6)
     __shared__ double dep[27 * DS + 8];   // [entry][column], row stride DS (+ 8: sum_children reads eight columns at a time): what a node hands to its parent (linearisation share / Schur update);
                                           // between those uses: rows 0 .. 11 the poses (for the children), rows 12 .. 17 x (back-substitution)
@@ -286,6 +308,7 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
     const int lane = threadIdx.x;
     const long long inst = blockIdx.x;
     const WindowCaps& c = a.caps;
+    const TreeSched& ts = wave_sched(sched, a, inst);
     const int nv = ts.nv;
     const bool node = lane < nv;
     // ---- prologue: everything a sweep needs, once -------------------------------------------------------------------------------------
@@ -683,11 +706,28 @@ __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, co
 
 }  // namespace
 
+// (one instantiation family per translation unit: tree_wave_groups_kernel.hip includes this file for SCHED = TreeGroups — with both families in one
+//  module the register assignment of the TreeSched kernels changes, and those keep their machine code)
+#ifndef LOCAMD_TREE_WAVE_GROUPS
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream) {
-    if (a.B <= 0 || ts.nv <= 0 || ts.nv > 64 || ts.nlev <= 0 || ts.nu < 0 || ts.nu > 64) return hipErrorInvalidValue;
-    if (a.jacobian) hipLaunchKernelGGL((tree_wave_kernel<1>), dim3((unsigned)a.B), dim3(64), 0, stream, a, ts);
-    else hipLaunchKernelGGL((tree_wave_kernel<0>), dim3((unsigned)a.B), dim3(64), 0, stream, a, ts);
+    if (a.B <= 0 || !tree_wave_sizes_ok(ts)) return hipErrorInvalidValue;
+    if (a.jacobian) hipLaunchKernelGGL((tree_wave_kernel<1, TreeSched>), dim3((unsigned)a.B), dim3(64), 0, stream, a, ts);
+    else hipLaunchKernelGGL((tree_wave_kernel<0, TreeSched>), dim3((unsigned)a.B), dim3(64), 0, stream, a, ts);
     return hipGetLastError();
 }
+#else
+hipError_t launch_window_tree_wave_groups(const WindowArgs& a, const TreeGroups& g, const int32_t* host_hdr, hipStream_t stream) {
+    if (a.B <= 0 || g.n_groups <= 0 || !host_hdr || !g.hdr || !g.sched_of || !g.tables) return hipErrorInvalidValue;
+    for (int k = 0; k < g.n_groups; ++k) {   // every group's sizes, on the host's copy of the headers
+        TreeSched ts{};
+        tree_group_sizes(ts, host_hdr + (size_t)k * kTreeGroupHdr);
+        if (!tree_wave_sizes_ok(ts) || ts.nr < 0 || ts.nr > a.caps.nr_max || ts.np < 0 || ts.np > a.caps.np_max || ts.ns < 0 || ts.ns > a.caps.ns_max ||
+            ts.max_se3_per_node > 1 || ts.nroots <= 0 || ts.nroots > ts.nv || host_hdr[(size_t)k * kTreeGroupHdr + 10] < 0) return hipErrorInvalidValue;
+    }
+    if (a.jacobian) hipLaunchKernelGGL((tree_wave_kernel<1, TreeGroups>), dim3((unsigned)a.B), dim3(64), 0, stream, a, g);
+    else hipLaunchKernelGGL((tree_wave_kernel<0, TreeGroups>), dim3((unsigned)a.B), dim3(64), 0, stream, a, g);
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace locamd

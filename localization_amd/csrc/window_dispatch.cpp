@@ -45,7 +45,7 @@ DispatchFits dispatch_fits(const WindowCaps& c) {
 bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f) { return o.arrow3 >= 0 ? o.arrow3 == 1 : f.nv_max > 64; }
 
 // what the batch qualifies for BY ITS STRUCTURE: LOC_WINDOW_KERNEL_GENERAL, _CHAIN (block-tridiagonal, 6-DoF), _CHAIN3, _WAVE6, _WAVE6S,
-// _ARROW3 or _TREE.  aux: the set of host-built tables that ARROW3 (row order, packed edge records) / TREE (the schedule) fill.
+// _ARROW3, _TREE or _TREE_GROUPS.  aux: the set of host-built tables that ARROW3 (row order, packed edge records) / TREE (the schedule) fill.
 // Host-path calls (tc != nullptr; the resident batch passes none) keep the structural verdict of the previous batch in *tc: the same counts
 // and index tables (one 64-bit hash; a collision — 2^-64 per call — would hand a batch to a kernel built for another structure) skip the tests below.
 // What depends on the VALUES (translation_only: identity rotations, zero lever arms; arrow3's packed edge records) is looked at every time.
@@ -62,7 +62,7 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
     bool se3_pairs = false;     // EdgeSE3 factors, at most one per pair of consecutive poses, and at most one range edge per pair (wave6_lm_kernel<JAC, true>)
     if (hit) { chain = tc->chain; single_pairs = tc->single_pairs; se3_pairs = tc->se3_pairs; }
     if (!hit) chain_scan(c, b, true, chain, single_pairs, se3_pairs);
-    if (use_cache && !hit) { tc->valid = true; tc->key = key; tc->n = b.n; tc->chain = chain; tc->single_pairs = single_pairs; tc->se3_pairs = se3_pairs; tc->tree_tried = false; tc->tree_ok = false; }
+    if (use_cache && !hit) { tc->valid = true; tc->key = key; tc->n = b.n; tc->chain = chain; tc->single_pairs = single_pairs; tc->se3_pairs = se3_pairs; tc->tree_tried = false; tc->tree_ok = false; tc->groups_tried = false; tc->groups_ok = false; }
     if (chain) {
         // (under a structured table the priors' diagonals are not read by any kernel, so not by the scan either: the verdict holds while
         //  structured_pinfo does — pick_kernel asks again, and the resident batch remembers how its verdict was taken)
@@ -84,6 +84,18 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
             const bool ok = build_tree_sched(c, general_only(o), b, aux);
             if (use_cache) { tc->tree_tried = true; tc->tree_ok = ok; }
             if (ok) return {LOC_WINDOW_KERNEL_TREE, hit};
+        }
+        // option "forest_groups": forest windows of differing topologies, only after build_tree_sched has declined the batch — a one-topology batch
+        // takes the path above.  Never under option "tree" = 2 (tree_lm_kernel has no per-window-schedule twin) or on a handle of longer windows.
+        // On a hit aux's groups and tables are still those built for this structure (hash_structure covers the full index tables).
+        if (o.forest_groups && o.tree != 2 && c.nv_max <= 64) {
+            if (hit && tc->groups_tried) {
+                if (tc->groups_ok) return {LOC_WINDOW_KERNEL_TREE_GROUPS, hit};
+            } else {
+                const bool ok = build_tree_groups(c, general_only(o), b, aux);
+                if (use_cache) { tc->groups_tried = true; tc->groups_ok = ok; }
+                if (ok) return {LOC_WINDOW_KERNEL_TREE_GROUPS, hit};
+            }
         }
     }
     return {LOC_WINDOW_KERNEL_GENERAL, hit};
@@ -130,6 +142,8 @@ static int pick_plain(const DispatchOpts& o, const DispatchFits& f, int64_t n, i
     }
     if (topology == LOC_WINDOW_KERNEL_ARROW3) return LOC_WINDOW_KERNEL_ARROW3;   // (one workgroup per window: any batch size)
     if (topology == LOC_WINDOW_KERNEL_TREE) return n < tree_min_batch(o) ? LOC_WINDOW_KERNEL_GENERAL : LOC_WINDOW_KERNEL_TREE;
+    // (the grouped forest: TREE's threshold; a verdict taken under switches that have changed since — a resident batch's — falls to the general kernel)
+    if (topology == LOC_WINDOW_KERNEL_TREE_GROUPS) return n < tree_min_batch(o) || !o.forest_groups || o.tree == 0 || o.tree == 2 ? LOC_WINDOW_KERNEL_GENERAL : LOC_WINDOW_KERNEL_TREE_GROUPS;
     if (topology == LOC_WINDOW_KERNEL_CHAIN3 && f.wave3) {
         // translation-only chains of <= 64 poses (the node's single window first of all): one wave per window with 3x3 blocks, rank-1
         // couplings and speculative LM trials.  Measured on ten-pose windows: 0.056 ms for one window, 3.6e7 windows/s (numeric) /

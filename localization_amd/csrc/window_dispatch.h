@@ -26,6 +26,8 @@ struct DispatchOpts {
     bool pinfo_translation = false;    // ... and none of them has rotation rows or columns (prior_information_translation_only, taken once by the setter)
     bool pinfo_structured = false;     // "prior_information_structured" 1: a translation-only table on a translation-only chain is served by
                                        // wave3_lm_kernel<JAC, true> and the chain 3x3 covariance pass (structured_pinfo); 0: the general kernel, the envelope pass
+    bool forest_groups = false;        // "forest_groups" 1: a batch of forest windows whose topologies DIFFER (build_tree_sched declines it) is grouped by topology
+                                       // (build_tree_groups) and solved by tree_wave_kernel<JAC, TreeGroups>; 0: such a batch is LOC_WINDOW_KERNEL_GENERAL
     bool upload_dev_structures = false; // "upload_dev_structures" 1: loc_window_upload_dev takes batch_topology's arrowhead and forest tests on the device
                                        // (window_structure_kernel.hip) for a batch that is no chain; 0: such a batch is LOC_WINDOW_KERNEL_GENERAL
 };
@@ -74,6 +76,7 @@ struct TopoCache {
     unsigned long long key = 0;
     int64_t n = 0;
     bool chain = false, single_pairs = false, se3_pairs = false, tree_ok = false, tree_tried = false;
+    bool groups_ok = false, groups_tried = false;   // build_tree_groups' verdict (option "forest_groups"): a refusal is remembered as well
 };
 struct Topology { int kind; bool cached; };   // LOC_WINDOW_KERNEL_* by structure; the verdict came from the cache
 Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, WinAux& aux, TopoCache* tc);

@@ -112,7 +112,7 @@ struct TreeSched {
     const int32_t* r_list;  // [nr]   edge numbers in schedule order (the kernel copies the values into its workspace in this order)
     const int32_t* p_off; const int32_t* p_list;   // priors of the node
     const int32_t* s_off; const int32_t* s_list;   // EdgeSE3 factors between the node and its parent
-    const int32_t* r_idx;   // [nr][2], [ns][4]: the index tables of instance 0 (= of every instance)
+    const int32_t* r_idx;   // [nr][2], [ns][4]: the index tables of instance 0 (= of every instance); tree_wave_kernel<JAC, TreeGroups> points its wave's copy at the window's own rows
     const int32_t* s_idx;
     // the same structure by POSE SLOT, for tree_wave_kernel (one wave per window, lane = pose): parent slot (-1: root), height above
     // the leaves, children (w_klist[w_koff[v] .. w_koff[v+1])), and the edges of the pose (unary ones, and those to its parent)
@@ -122,6 +122,19 @@ struct TreeSched {
     const int32_t* w_kpos;    // [nv] a pose's position in w_klist (= the LDS column its hand-over to the parent uses: a node's children are
                               //      consecutive columns); roots: nv - nroots, nv - nroots + 1, ...
     int nv, nr, np, ns, depth, nroots, nlev, max_se3_per_node, nu, max_r_per_node;
+};
+// Forest windows of DIFFERING topologies (option "forest_groups"; window_structure.cpp: build_tree_groups): one schedule per group of windows
+// of one topology, one device block [hdr | sched_of | pad | tables].  hdr: kTreeGroupHdr int32 per group — TreeSched's ten sizes in their
+// declaration order, the offset of the group's table in `tables` (int32s, a multiple of 4), the table's length.  A group's table is
+// build_tree_sched's, bound by tree_sched_bind (window_layouts.h) on the host and in the kernel alike; its r_idx / s_idx sections hold the
+// group's FIRST window's rows — the twin kernel reads every window's own rows (anchor numbers and robust flags are not part of a topology).
+constexpr int kTreeGroupHdr = 12;
+constexpr int32_t kTreeGroupPoison = INT32_MIN;   // the padding between sched_of and the tables, and behind every table up to a multiple of 4
+struct TreeGroups {
+    const int32_t* hdr;        // [n_groups][kTreeGroupHdr]
+    const int32_t* sched_of;   // [B] window -> group
+    const int32_t* tables;     // the groups' tables, concatenated
+    int n_groups;
 };
 // The pose pairs of a joint covariance call (loc_window_joint_covariance_*), device arrays.  cross == nullptr: the plain call
 // (the passes' kernels without any pair code).  Otherwise every pass also writes cross[b][p] = [H^-1]_ij for the pairs p < counts[b] of
@@ -311,5 +324,8 @@ hipError_t launch_window_arrow_pack(const ArrowPackArgs& a, hipStream_t stream);
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);
+// the per-window-schedule twin (tree_wave_kernel.hip: tree_wave_groups_kernel).  host_hdr: the host's copy of g.hdr — every group's sizes are
+// held to launch_window_tree_wave's bounds (and one EdgeSE3 per node) BEFORE the launch; hipErrorInvalidValue otherwise, and for B <= 0
+hipError_t launch_window_tree_wave_groups(const WindowArgs& a, const TreeGroups& g, const int32_t* host_hdr, hipStream_t stream);
 
 }  // namespace locamd

@@ -433,4 +433,32 @@ LOCAMD_HD inline size_t arrow_cov_ws_doubles(const WindowCaps& c, int cap) {
 }
 LOCAMD_HD inline bool cov_arrow_fits(const WindowCaps& c) { return arrow_cov_layout(c.nv_max).bytes <= kCovMaxLds; }
 
+// The forest kernels' schedule table (window_structure.cpp: build_tree_sched emits it in this order): ts's pointers into a copy of the table
+// that starts at base; ts's ten sizes are set.  Returns the table's length in int32s (base to the end of w_kpos).  The host binds the one
+// shared table with it (bind_tree_sched), tree_wave_groups_kernel the table of its window's group.
+LOCAMD_HD inline size_t tree_sched_bind(TreeSched& ts, const int32_t* base) {
+    const int nv = ts.nv, nr = ts.nr, np = ts.np, ns = ts.ns;
+    const int32_t* p = base;
+    ts.node = p; p += nv; ts.par = p; p += nv;
+    ts.r_off = p; p += nv + 1; ts.r_list = p; p += nr;
+    ts.p_off = p; p += nv + 1; ts.p_list = p; p += np;
+    ts.s_off = p; p += nv + 1; ts.s_list = p; p += ns;
+    ts.r_idx = p; p += 2 * nr; ts.s_idx = p; p += 4 * ns;
+    ts.w_par = p; p += nv; ts.w_height = p; p += nv;
+    ts.w_koff = p; p += nv + 1; ts.w_klist = p; p += nv - ts.nroots;
+    ts.w_roff = p; p += nv + 1; ts.w_rlist = p; p += nr;
+    ts.w_poff = p; p += nv + 1; ts.w_plist = p; p += np;
+    ts.w_soff = p; p += nv + 1; ts.w_slist = p; p += ns;
+    ts.w_kleaf = p; p += nv;
+    ts.w_ulist = p; p += ts.nu;
+    ts.w_kpos = p; p += nv;
+    return (size_t)(p - base);
+}
+// a group's header of a TreeGroups block (window_kernel.h): the ten sizes in TreeSched's order; slot 10: the table's offset, slot 11: its length
+LOCAMD_HD inline void tree_group_sizes(TreeSched& ts, const int32_t* h) {
+    ts.nv = h[0]; ts.nr = h[1]; ts.np = h[2]; ts.ns = h[3]; ts.depth = h[4]; ts.nroots = h[5]; ts.nlev = h[6]; ts.max_se3_per_node = h[7]; ts.nu = h[8]; ts.max_r_per_node = h[9];
+}
+// what both launchers of tree_wave_kernel.hip hold a schedule's sizes to (lane = pose: 64 lanes, 64 LDS columns)
+LOCAMD_HD inline bool tree_wave_sizes_ok(const TreeSched& ts) { return ts.nv > 0 && ts.nv <= 64 && ts.nlev > 0 && ts.nu >= 0 && ts.nu <= 64; }
+
 }  // namespace locamd

@@ -417,20 +417,11 @@ bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool st
     return true;
 }
 
-// FOREST windows of ONE shared topology (BASELINE config 5: the key-frame star of addPoseEdge, localization.cpp:254-290, replayed
-// with different measurements in every instance): every instance has the same counts and index tables, and the pose-to-pose
-// edges form a forest.  Builds the elimination schedule tree_lm_kernel walks: nodes in post-order (children before their parent,
-// a node's children heavy subtree first so that the leaves of one parent are consecutive), per node its parent and its edges.
-// Layout of the int table: bind_tree_sched below, which walks it in the order the code from "std::vector<int32_t>& t = A.h_tsched" on emits it.
-bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
-    const int nv = b.counts[0], nr = b.counts[1], np = b.counts[2], ns = b.counts[3];
-    if (nv < 2 || nv > 64 || has_off1) return false;
-    for (int64_t i = 1; i < b.n; ++i) {   // one topology
-        if (std::memcmp(b.counts + i * 4, b.counts, 4 * sizeof(int32_t)) != 0) return false;
-        if (nr && std::memcmp(b.r_idx + (size_t)i * c.nr_max * 2, b.r_idx, (size_t)nr * 2 * sizeof(int32_t)) != 0) return false;
-        if (np && std::memcmp(b.p_idx + (size_t)i * c.np_max, b.p_idx, (size_t)np * sizeof(int32_t)) != 0) return false;
-        if (ns && std::memcmp(b.s_idx + (size_t)i * c.ns_max * 4, b.s_idx, (size_t)ns * 4 * sizeof(int32_t)) != 0) return false;
-    }
+// One topology's schedule: everything build_tree_sched does behind its "one topology" loop — the forest test, centres, post-order, by-slot
+// lists — on ONE window's counts and used index rows.  t receives the table (cleared first), ts the ten sizes.  false: nv outside [2, 64], or a cycle.
+static bool tree_sched_one(const int32_t* counts, const int32_t* r_idx, const int32_t* p_idx, const int32_t* s_idx, std::vector<int32_t>& t, TreeSched& ts) {
+    const int nv = counts[0], nr = counts[1], np = counts[2], ns = counts[3];
+    if (nv < 2 || nv > 64) return false;
     // adjacency (pairs joined by at least one edge); a forest has no cycle: union-find on the distinct pairs
     std::vector<int> uf((size_t)nv);
     for (int v = 0; v < nv; ++v) uf[(size_t)v] = v;
@@ -444,8 +435,8 @@ bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, Wi
         adj[(size_t)u].push_back(v); adj[(size_t)v].push_back(u);
         return true;
     };
-    for (int e = 0; e < nr; ++e) if (b.r_idx[2 * e + 1] >= 0 && !join(b.r_idx[2 * e], b.r_idx[2 * e + 1])) return false;
-    for (int e = 0; e < ns; ++e) if (!join(b.s_idx[4 * e], b.s_idx[4 * e + 1])) return false;
+    for (int e = 0; e < nr; ++e) if (r_idx[2 * e + 1] >= 0 && !join(r_idx[2 * e], r_idx[2 * e + 1])) return false;
+    for (int e = 0; e < ns; ++e) if (!join(s_idx[4 * e], s_idx[4 * e + 1])) return false;
     // root of every component = its CENTRE (the middle of a longest path: two breadth-first searches), so that the elimination by
     // height takes half as many steps as from an end (config 5's chain of eight keys: 6 levels instead of 9); parents towards the
     // root; subtree sizes; post-order, heavy child first
@@ -505,16 +496,15 @@ bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, Wi
     // edges by node: a unary edge belongs to its pose; an edge between a node and its parent to the node (the child)
     std::vector<std::vector<int>> re((size_t)nv), pe((size_t)nv), se((size_t)nv);
     for (int e = 0; e < nr; ++e) {
-        const int v0 = b.r_idx[2 * e], v1 = b.r_idx[2 * e + 1];
+        const int v0 = r_idx[2 * e], v1 = r_idx[2 * e + 1];
         if (v1 < 0) re[(size_t)pos[(size_t)v0]].push_back(e);
         else re[(size_t)pos[(size_t)(parent[(size_t)v0] == v1 ? v0 : v1)]].push_back(e);
     }
-    for (int e = 0; e < np; ++e) pe[(size_t)pos[(size_t)b.p_idx[e]]].push_back(e);
+    for (int e = 0; e < np; ++e) pe[(size_t)pos[(size_t)p_idx[e]]].push_back(e);
     for (int e = 0; e < ns; ++e) {
-        const int vi = b.s_idx[4 * e], vj = b.s_idx[4 * e + 1];
+        const int vi = s_idx[4 * e], vj = s_idx[4 * e + 1];
         se[(size_t)pos[(size_t)(parent[(size_t)vi] == vj ? vi : vj)]].push_back(e);
     }
-    std::vector<int32_t>& t = A.h_tsched;
     t.clear();
     for (int k = 0; k < nv; ++k) t.push_back(order[(size_t)k]);
     for (int k = 0; k < nv; ++k) { const int p = parent[(size_t)order[(size_t)k]]; t.push_back(p < 0 ? -1 : pos[(size_t)p]); }
@@ -525,8 +515,8 @@ bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, Wi
         for (int k = 0; k < nv; ++k) for (int e : L[(size_t)k]) t.push_back(e);
     };
     lists(re); lists(pe); lists(se);
-    for (int i = 0; i < 2 * nr; ++i) t.push_back(b.r_idx[i]);
-    for (int i = 0; i < 4 * ns; ++i) t.push_back(b.s_idx[i]);
+    for (int i = 0; i < 2 * nr; ++i) t.push_back(r_idx[i]);
+    for (int i = 0; i < 4 * ns; ++i) t.push_back(s_idx[i]);
     // by pose slot (tree_wave_kernel): parent, height, children, edges
     std::vector<int> height((size_t)nv, 0);
     int hmax = 0;
@@ -556,7 +546,7 @@ bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, Wi
     int nu = 0;
     for (int h = hmax; h >= 1; --h)
         for (int v = 0; v < nv; ++v) if (height[(size_t)v] == h) { t.push_back(v); ++nu; }
-    A.tsched.nu = nu;
+    ts.nu = nu;
     {   // a pose's position in the children list just emitted (by_slot(kids_lf)): parents in slot order, a parent's leaf children first
         std::vector<int> kpos((size_t)nv, -1);
         int at = 0;
@@ -564,34 +554,144 @@ bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, Wi
         for (int v = 0; v < nv; ++v) if (kpos[(size_t)v] < 0) kpos[(size_t)v] = at++;   // roots
         for (int v = 0; v < nv; ++v) t.push_back(kpos[(size_t)v]);
     }
-    A.tsched.nlev = hmax + 1;
-    A.tsched.max_se3_per_node = 0;
-    A.tsched.max_r_per_node = 0;
-    for (int k = 0; k < nv; ++k) if ((int)se[(size_t)k].size() > A.tsched.max_se3_per_node) A.tsched.max_se3_per_node = (int)se[(size_t)k].size();
-    for (int k = 0; k < nv; ++k) if ((int)re[(size_t)k].size() > A.tsched.max_r_per_node) A.tsched.max_r_per_node = (int)re[(size_t)k].size();
-    A.tsched.nv = nv; A.tsched.nr = nr; A.tsched.np = np; A.tsched.ns = ns; A.tsched.depth = maxdepth + 1; A.tsched.nroots = nroots;
+    ts.nlev = hmax + 1;
+    ts.max_se3_per_node = 0;
+    ts.max_r_per_node = 0;
+    for (int k = 0; k < nv; ++k) if ((int)se[(size_t)k].size() > ts.max_se3_per_node) ts.max_se3_per_node = (int)se[(size_t)k].size();
+    for (int k = 0; k < nv; ++k) if ((int)re[(size_t)k].size() > ts.max_r_per_node) ts.max_r_per_node = (int)re[(size_t)k].size();
+    ts.nv = nv; ts.nr = nr; ts.np = np; ts.ns = ns; ts.depth = maxdepth + 1; ts.nroots = nroots;
     return true;
+}
+
+// FOREST windows of ONE shared topology (BASELINE config 5: the key-frame star of addPoseEdge, localization.cpp:254-290, replayed
+// with different measurements in every instance): every instance has the same counts and index tables, and the pose-to-pose
+// edges form a forest.  Builds the elimination schedule tree_lm_kernel walks: nodes in post-order (children before their parent,
+// a node's children heavy subtree first so that the leaves of one parent are consecutive), per node its parent and its edges.
+// Layout of the int table: tree_sched_bind (window_layouts.h), which walks it in the order tree_sched_one above emits it from "t.clear()" on.
+bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
+    const int nv = b.counts[0], nr = b.counts[1], np = b.counts[2], ns = b.counts[3];
+    if (nv < 2 || nv > 64 || has_off1) return false;
+    for (int64_t i = 1; i < b.n; ++i) {   // one topology
+        if (std::memcmp(b.counts + i * 4, b.counts, 4 * sizeof(int32_t)) != 0) return false;
+        if (nr && std::memcmp(b.r_idx + (size_t)i * c.nr_max * 2, b.r_idx, (size_t)nr * 2 * sizeof(int32_t)) != 0) return false;
+        if (np && std::memcmp(b.p_idx + (size_t)i * c.np_max, b.p_idx, (size_t)np * sizeof(int32_t)) != 0) return false;
+        if (ns && std::memcmp(b.s_idx + (size_t)i * c.ns_max * 4, b.s_idx, (size_t)ns * 4 * sizeof(int32_t)) != 0) return false;
+    }
+    return tree_sched_one(b.counts, b.r_idx, b.p_idx, b.s_idx, A.h_tsched, A.tsched);   // (the one-group case of build_tree_groups below)
 }
 
 // ts's pointers into a copy of the table build_tree_sched wrote (A.h_tsched, or its device copy) that starts at base; ts's sizes are those
 // build_tree_sched set.  The table's length: the int32s from base to the end of w_kpos.
-size_t bind_tree_sched(TreeSched& ts, const int32_t* base) {
-    const int nv = ts.nv, nr = ts.nr, np = ts.np, ns = ts.ns;
-    const int32_t* p = base;
-    ts.node = p; p += nv; ts.par = p; p += nv;
-    ts.r_off = p; p += nv + 1; ts.r_list = p; p += nr;
-    ts.p_off = p; p += nv + 1; ts.p_list = p; p += np;
-    ts.s_off = p; p += nv + 1; ts.s_list = p; p += ns;
-    ts.r_idx = p; p += 2 * nr; ts.s_idx = p; p += 4 * ns;
-    ts.w_par = p; p += nv; ts.w_height = p; p += nv;
-    ts.w_koff = p; p += nv + 1; ts.w_klist = p; p += nv - ts.nroots;
-    ts.w_roff = p; p += nv + 1; ts.w_rlist = p; p += nr;
-    ts.w_poff = p; p += nv + 1; ts.w_plist = p; p += np;
-    ts.w_soff = p; p += nv + 1; ts.w_slist = p; p += ns;
-    ts.w_kleaf = p; p += nv;
-    ts.w_ulist = p; p += ts.nu;
-    ts.w_kpos = p; p += nv;
-    return (size_t)(p - base);
+size_t bind_tree_sched(TreeSched& ts, const int32_t* base) { return tree_sched_bind(ts, base); }   // (window_layouts.h: the one statement)
+
+// ---- forest windows of DIFFERING topologies (option "forest_groups"; DESIGN.md §2, "Forest groups") -------------------------------------------
+// Key-frame windows cut from different robots, or at different phases of one robot's key cadence (Localization::addPoseEdge,
+// localization.cpp:254-290), have different parents and lengths and range different anchors.  A window's TOPOLOGY KEY: its four counts, its
+// used r_idx rows with every fixed endpoint (v1 < 0) collapsed to -1, its used p_idx rows, columns 0 - 1 of its used s_idx rows.  Anchor
+// numbers and robust flags are not part of it: tree_wave_groups_kernel reads them from the window's own rows.
+static void topology_key(const WindowCaps& c, const HostBatch& b, int64_t i, std::vector<int32_t>& k) {
+    const int32_t* cn = b.counts + i * 4;
+    k.assign(cn, cn + 4);
+    const int32_t* r = b.r_idx + (size_t)i * c.nr_max * 2;
+    for (int e = 0; e < cn[1]; ++e) { k.push_back(r[2 * e]); k.push_back(r[2 * e + 1] < 0 ? -1 : r[2 * e + 1]); }
+    const int32_t* p = b.p_idx + (size_t)i * c.np_max;
+    k.insert(k.end(), p, p + cn[2]);
+    const int32_t* s = b.s_idx + (size_t)i * c.ns_max * 4;
+    for (int e = 0; e < cn[3]; ++e) { k.push_back(s[4 * e]); k.push_back(s[4 * e + 1]); }
+}
+
+// Groups the windows by topology key (ids in order of first appearance; a hash finds the candidates, a memcmp of the keys decides), runs
+// every group's first window through tree_sched_one and writes A.h_groups = [hdr | sched_of | pad | tables] (window_kernel.h: TreeGroups).
+// The batch is refused as a whole — false, A.n_groups = 0 — when any window has nv outside [2, 64], any group has a cycle or more than one
+// EdgeSE3 on a node's edge to its parent (tree_lm_kernel, which takes those, has no twin), under has_off1, or when the handle's nv_max > 64.
+bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
+    A.n_groups = 0;
+    A.h_groups.clear();
+    const int64_t n = b.n;
+    if (has_off1 || c.nv_max > 64 || n <= 0) return false;
+    // pass 1, split over the windows: a 64-bit FNV-1a of every key
+    std::vector<uint64_t> hash((size_t)n);
+    std::atomic<bool> bad{false};
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
+        std::vector<int32_t> k;
+        for (int64_t i = lo; i < hi && !bad.load(std::memory_order_relaxed); ++i) {
+            const int32_t nv = b.counts[i * 4];
+            if (nv < 2 || nv > 64) { bad.store(true); return; }
+            topology_key(c, b, i, k);
+            uint64_t h = 1469598103934665603ull;
+            for (int32_t x : k) { h ^= (uint32_t)x; h *= 1099511628211ull; }
+            hash[(size_t)i] = h;
+        }
+    });
+    if (bad.load()) return false;
+    // pass 2, in window order: a window joins the first group of its hash whose representative's key equals its own
+    std::vector<int32_t> of((size_t)n), k;
+    std::vector<int64_t> rep;                    // a group's first window
+    std::vector<std::vector<int32_t>> rep_key;   // ... and its key
+    {
+        std::vector<std::pair<uint64_t, int64_t>> order((size_t)n);
+        for (int64_t i = 0; i < n; ++i) order[(size_t)i] = {hash[(size_t)i], i};
+        std::sort(order.begin(), order.end());   // (equal hashes in window order: a group's representative is its first window)
+        std::vector<int32_t> local((size_t)n, -1);   // per window: index of its group among the groups found in hash order
+        std::vector<int64_t> lrep;
+        std::vector<std::vector<int32_t>> lkey;
+        for (size_t a0 = 0; a0 < order.size();) {
+            size_t a1 = a0;
+            while (a1 < order.size() && order[a1].first == order[a0].first) ++a1;
+            const size_t g0 = lrep.size();
+            for (size_t q = a0; q < a1; ++q) {
+                const int64_t i = order[q].second;
+                topology_key(c, b, i, k);
+                size_t g = g0;
+                for (; g < lrep.size(); ++g)
+                    if (lkey[g].size() == k.size() && std::memcmp(lkey[g].data(), k.data(), k.size() * sizeof(int32_t)) == 0) break;
+                if (g == lrep.size()) { lrep.push_back(i); lkey.push_back(k); }
+                local[(size_t)i] = (int32_t)g;
+            }
+            a0 = a1;
+        }
+        // group ids in order of first appearance
+        std::vector<int32_t> id(lrep.size(), -1);
+        for (int64_t i = 0; i < n; ++i) {
+            int32_t& g = id[(size_t)local[(size_t)i]];
+            if (g < 0) { g = (int32_t)rep.size(); rep.push_back(i); }
+            of[(size_t)i] = g;
+        }
+    }
+    const int64_t G = (int64_t)rep.size();
+    // every group's schedule, split over the groups
+    std::vector<std::vector<int32_t>> tab((size_t)G);
+    std::vector<TreeSched> sizes((size_t)G);
+    parallel_chunks(G, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t g = lo; g < hi && !bad.load(std::memory_order_relaxed); ++g) {
+            const int64_t i = rep[(size_t)g];
+            TreeSched& ts = sizes[(size_t)g];
+            ts = TreeSched{};
+            if (!tree_sched_one(b.counts + i * 4, b.r_idx + (size_t)i * c.nr_max * 2, b.p_idx + (size_t)i * c.np_max, b.s_idx + (size_t)i * c.ns_max * 4, tab[(size_t)g], ts) ||
+                ts.max_se3_per_node > 1 || !tree_wave_sizes_ok(ts)) { bad.store(true); return; }
+        }
+    });
+    if (bad.load()) return false;
+    // [hdr | sched_of | pad | tables]: every table starts at a multiple of 4 int32s; the slots no table owns are poisoned
+    std::vector<int32_t>& t = A.h_groups;
+    const size_t of_at = (size_t)G * kTreeGroupHdr, tab_at = (of_at + (size_t)n + 3) / 4 * 4;
+    size_t total = 0;
+    for (const auto& x : tab) total += (x.size() + 3) / 4 * 4;
+    if (total > (size_t)INT32_MAX) return false;   // (a header holds its table's offset as an int32)
+    t.assign(tab_at + total, kTreeGroupPoison);
+    std::memcpy(t.data() + of_at, of.data(), (size_t)n * sizeof(int32_t));
+    size_t at = 0;
+    for (int64_t g = 0; g < G; ++g) {
+        const TreeSched& ts = sizes[(size_t)g];
+        const int32_t h[kTreeGroupHdr] = {ts.nv, ts.nr, ts.np, ts.ns, ts.depth, ts.nroots, ts.nlev, ts.max_se3_per_node, ts.nu, ts.max_r_per_node, (int32_t)at, (int32_t)tab[(size_t)g].size()};
+        std::memcpy(t.data() + (size_t)g * kTreeGroupHdr, h, sizeof(h));
+        std::memcpy(t.data() + tab_at + at, tab[(size_t)g].data(), tab[(size_t)g].size() * sizeof(int32_t));
+        at += (tab[(size_t)g].size() + 3) / 4 * 4;
+    }
+    A.n_groups = (int)G;
+    A.groups_of_at = of_at;
+    A.groups_tab_at = tab_at;
+    return true;
 }
 
 }  // namespace locamd

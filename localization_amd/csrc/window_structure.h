@@ -14,6 +14,12 @@ struct WinAux {
     size_t tsched_cap = 0;
     std::vector<int32_t> h_tsched;
     TreeSched tsched{};
+    // option "forest_groups" (build_tree_groups): the block [hdr | sched_of | pad | tables] of window_kernel.h's TreeGroups, its device copy,
+    // the number of groups (0: the batch is not on the grouped path) and where sched_of and the tables start (int32s)
+    std::vector<int32_t> h_groups;
+    int32_t* d_groups = nullptr;
+    size_t groups_cap = 0, groups_of_at = 0, groups_tab_at = 0;
+    int n_groups = 0;
     int32_t *d_ahdr = nullptr, *d_arslot = nullptr;
     double *d_arec = nullptr, *d_aprec = nullptr;
     size_t arec_cap = 0, aprec_cap = 0;   // doubles allocated
@@ -70,5 +76,8 @@ long long envelope_blocks_max_joint(const WindowCaps& c, const HostBatch& b, con
 bool build_arrow_aux(const WindowCaps& c, const HostBatch& b, WinAux& A, bool structure_only = false);   // fills A.h_a* and A.arrow_*
 bool build_tree_sched(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);                // fills A.h_tsched and A.tsched's sizes
 size_t bind_tree_sched(TreeSched& ts, const int32_t* base);   // ts's pointers into a copy of that table at base; returns the table's length
+// Forest windows of DIFFERING topologies: groups by topology key (counts, index rows without anchor numbers and robust flags), one
+// build_tree_sched table per group; fills A.h_groups, A.n_groups, A.groups_*_at.  false: the batch stays with the general kernel
+bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);
 
 }  // namespace locamd

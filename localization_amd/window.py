@@ -537,7 +537,8 @@ class WindowSolver(_lib.Handle):
         check(self.L.loc_window_last_covariance_ms(self.h, C.byref(ms)))
         return ms.value
 
-    KERNEL_KINDS = {-1: "none", 0: "window_lm_kernel", 1: "chain_lm_kernel", 2: "chain3_lm_kernel", 3: "arrow3_lm_kernel", 4: "tree_wave_kernel", 5: "tree_lm_kernel", 6: "wave3_lm_kernel", 7: "wave6_lm_kernel", 8: "wave6_lm_kernel<SE3>"}
+    KERNEL_KINDS = {-1: "none", 0: "window_lm_kernel", 1: "chain_lm_kernel", 2: "chain3_lm_kernel", 3: "arrow3_lm_kernel", 4: "tree_wave_kernel", 5: "tree_lm_kernel", 6: "wave3_lm_kernel", 7: "wave6_lm_kernel", 8: "wave6_lm_kernel<SE3>",
+                    9: "tree_wave_kernel<groups>"}
 
     def last_kernel_kind(self):
         """name of the kernel the last solve ran (loc_window_last_kernel_kind)"""
@@ -559,8 +560,19 @@ class WindowSolver(_lib.Handle):
         on translation-only chains of <= 64 poses is solved by wave3_lm_kernel and served by the chain 3 x 3 covariance pass, default 0;
         "upload_dev_structures": 1 = upload_dev() also takes the arrowhead and forest verdicts on the device, so that such a batch runs on
         arrow3_lm_kernel / tree_wave_kernel and its covariance passes exactly as after upload() of the same arrays; default 0: a batch
-        uploaded from device arrays that is no chain solves on the general kernel)"""
+        uploaded from device arrays that is no chain solves on the general kernel;
+        "forest_groups": 1 = a batch of forest windows of <= 64 poses whose topologies differ (other parents, lengths, anchors: key-frame windows
+        of different robots or phases) is grouped by topology and solved by tree_wave_kernel<groups> with one schedule per group, from solve()
+        and from upload() + solve_resident(); a one-topology batch keeps tree_wave_kernel; upload_dev() does not group and covariances of a
+        mixed batch are served as without the option; default 0: such a batch solves on the general kernel)"""
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
+
+    def forest_groups(self):
+        """(number of topology groups, bytes of schedule tables sent to the device) of the handle's last structural verdict — solve() or
+        upload(), whichever came last; (0, 0) when that batch is not on the grouped path (option "forest_groups")"""
+        n, nbytes = C.c_int32(), C.c_int64()
+        check(self.L.loc_window_forest_groups(self.h, C.byref(n), C.byref(nbytes)))
+        return int(n.value), int(nbytes.value)
 
     def last_host_timing(self):
         """(validate ms, structure analysis ms, staging + launch + copy back ms, verdict came from the cache) of the last solve()"""
