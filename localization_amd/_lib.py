@@ -114,7 +114,8 @@ def lib():
     L.loc_window_set_ordering.argtypes = [vp, C.c_int32]
     L.loc_window_set_chain_threshold.argtypes = [vp, C.c_int64]
     L.loc_window_last_kernel_kind.argtypes = [vp, ip]
-    L.loc_window_forest_groups.argtypes = [vp, ip, C.POINTER(C.c_int64)]
+    L.loc_window_last_host_timing.argtypes = [vp, dp]
+    L.loc_window_forest_groups.argtypes =[vp, ip, C.POINTER(C.c_int64)]
     L.loc_window_upload.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp]
     L.loc_window_upload_dev.argtypes = [vp, vp, C.c_int64] + [vp] * 9
     L.loc_window_solve_resident.argtypes = [vp, vp]

@@ -15,29 +15,107 @@ class MessageConfig(C.Structure):
     _fields_ = [("trajectory_length", C.c_int32), ("maximum_velocity", C.c_double), ("distance_outlier", C.c_double)]
 
 
+_IP, _DP = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+_I32, _F64 = np.dtype(np.int32), np.dtype(np.float64)
+
+
 def _inv_iso(R, t):
     Ri = R.T
     return Ri, -Ri @ t
 
 
+def _dev(t):
+    """device pointer argument from None, an int or an object with data_ptr()"""
+    return C.c_void_p(None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+
+def _stream(stream):
+    """stream argument from None (the handle's own) or a torch stream"""
+    return None if stream is None else C.c_void_p(stream.cuda_stream)
+
+
+def _new_rows(rows, n):
+    """(capacity, *n device pointers) of a new_ranges / new_priors / new_se3 tuple of n arrays and, optionally, their capacity (left out: the
+    second array's rows per window); None: capacity 0 and n NULLs"""
+    if rows is None:
+        return (0,) + (None,) * n
+    return (int(rows[n]) if len(rows) > n else int(rows[1].shape[-2]),) + tuple(_dev(t) for t in rows[:n])
+
+
+def _host_out(x, dtype, size, optional=False):
+    """pointer argument of a host output array: of this dtype, C-contiguous, at least size elements; None only where optional.  (C.cast
+    is the cheaper half of ndarray.ctypes.data_as; the pointer does not keep x alive, the caller does.)"""
+    if x is None and optional:
+        return None
+    assert x.dtype == dtype and x.size >= size and x.flags.c_contiguous
+    return C.cast(x.ctypes.data, _IP if dtype == _I32 else _DP)
+
+
+def _dev_out(t, numel, dtype=None, optional=False):
+    """pointer argument of a torch output tensor: on the device, contiguous, at least numel elements, of dtype where one is given"""
+    if t is None and optional:
+        return None
+    assert t.is_cuda and t.is_contiguous() and t.numel() >= numel and (dtype is None or t.dtype == dtype)
+    return C.c_void_p(t.data_ptr())
+
+
 class WindowBatch:
     """Host-side arrays of B instances in the ABI's layout; fill with add_* then hand to WindowSolver.solve."""
+    TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")   # in the C ABI's argument order
 
     def __init__(self, batch, nv_max, nr_max, np_max, ns_max):
         self.B = int(batch)
         self.caps = (int(nv_max), int(nr_max), int(np_max), int(ns_max))
-        self.counts = np.zeros((self.B, 4), dtype=np.int32)
-        self.poses = np.zeros((self.B, nv_max, 12))
+        self._layout_of = None
+        for name, dtype, shape, _ in self._layout():
+            setattr(self, name, np.zeros(shape, dtype=dtype))
         self.poses[:, :, 0] = self.poses[:, :, 4] = self.poses[:, :, 8] = 1.0
-        self.r_idx = np.zeros((self.B, max(nr_max, 1), 2), dtype=np.int32)
-        self.r_val = np.zeros((self.B, max(nr_max, 1), 5))
-        self.p_idx = np.zeros((self.B, max(np_max, 1)), dtype=np.int32)
-        self.p_val = np.zeros((self.B, max(np_max, 1), 18))
-        self.s_idx = np.zeros((self.B, max(ns_max, 1), 4), dtype=np.int32)
-        self.s_val = np.zeros((self.B, max(ns_max, 1), 48))
         self.result = np.zeros((self.B, 8))
         self.r_off1 = None   # optional lever arms of endpoint 1, [B][nr_max][3] (loc_window_set_endpoint1_offsets); created by add_range(off1=...)
         self.p_info = None   # optional full information matrices of the priors, [B][np_max][36] (loc_window_set_prior_information); created by add_prior(info=...)
+
+    def _layout(self):
+        """(name, dtype, shape, pointer type) of the eight tables, in TABLES order, for this batch's B and capacities (kept until they change)"""
+        if self._layout_of != (self.B, self.caps):
+            B, (nv, nr, npr, ns) = self.B, self.caps
+            nr, npr, ns = max(nr, 1), max(npr, 1), max(ns, 1)
+            rows = ((4,), (nv, 12), (nr, 2), (nr, 5), (npr,), (npr, 18), (ns, 4), (ns, 48))
+            self._layout_rows = tuple((name, _F64, (B,) + row, _DP) if k % 2 else (name, _I32, (B,) + row, _IP) for k, (name, row) in enumerate(zip(self.TABLES, rows)))
+            self._layout_of = (self.B, self.caps)
+        return self._layout_rows
+
+    def _pointers(self):
+        """The eight tables as the library takes them: ctypes pointers in TABLES order.  The library sees neither dtypes nor strides, so
+        every table is first held to _layout() and to C-contiguity.  The pointers are good for as long as the batch holds these arrays."""
+        out = []
+        for name, dtype, shape, pointer in self._layout():
+            a = getattr(self, name)
+            if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == shape and a.flags.c_contiguous):
+                what = (f"is a {type(a).__name__}, not a numpy array" if not isinstance(a, np.ndarray) else f"has dtype {a.dtype}, not {dtype}" if a.dtype != dtype
+                        else f"has shape {a.shape}, not {shape}" if a.shape != shape else "is not C-contiguous")
+                raise ValueError(f"WindowBatch.{name} {what}")
+            out.append(C.cast(a.ctypes.data, pointer))
+        return out
+
+    def take(self, rows):
+        """A new batch of len(rows) windows at the same capacities, window k a copy of this batch's window rows[k]: the eight tables, result,
+        and p_info / r_off1 where the batch has them.  Every array is freshly allocated."""
+        rows = np.asarray(rows, dtype=np.intp).reshape(-1)
+        out = WindowBatch(len(rows), *self.caps)
+        for name in self.TABLES + ("result", "p_info", "r_off1"):
+            src = getattr(self, name)
+            if src is not None:
+                dst = np.empty((len(rows),) + src.shape[1:], dtype=src.dtype)
+                dst[...] = src[rows]
+                setattr(out, name, dst)
+        return out
+
+    def copy(self):
+        return self.take(np.arange(self.B))
+
+    def tile(self, B):
+        """B windows: this batch's windows repeated in order (or its first B)"""
+        return self.take(np.arange(B) % self.B)
 
     def add_pose(self, i, t, R=None):
         v = int(self.counts[i, 0])
@@ -92,11 +170,10 @@ class WindowBatch:
 def covariance_plan(wb: WindowBatch):
     """(blocks_max, workspace_bytes) of loc_window_covariance_plan: the largest envelope of wb's windows in 6x6 blocks, in their pose
     order, and the device workspace the envelope pass (option "covariance_general") allocates for the batch.  Host only: no device."""
-    ip = C.POINTER(C.c_int32)
     caps = WindowCaps(*wb.caps, -1)
+    counts, _, r_idx, _, _, _, s_idx, _ = wb._pointers()
     blocks, nbytes = C.c_int64(), C.c_size_t()
-    check(lib().loc_window_covariance_plan(C.byref(caps), wb.B, wb.counts.ctypes.data_as(ip), wb.r_idx.ctypes.data_as(ip),
-                                           wb.s_idx.ctypes.data_as(ip), C.byref(blocks), C.byref(nbytes)))
+    check(lib().loc_window_covariance_plan(C.byref(caps), wb.B, counts, r_idx, s_idx, C.byref(blocks), C.byref(nbytes)))
     return blocks.value, nbytes.value
 
 
@@ -117,12 +194,11 @@ def _pair_tables(B, pairs, pair_counts):
 def joint_covariance_plan(wb: WindowBatch, pairs, pair_counts=None):
     """covariance_plan(wb) for a joint call: the envelope pass keeps [H^-1]_ij of a requested pair in the block that pair adds to the envelope
     (loc_window_joint_covariance_plan).  Without pairs: covariance_plan(wb)."""
-    ip = C.POINTER(C.c_int32)
     caps = WindowCaps(*wb.caps, -1)
+    counts, _, r_idx, _, _, _, s_idx, _ = wb._pointers()
     npm, pc, pr = _pair_tables(wb.B, pairs, pair_counts)
     blocks, nbytes = C.c_int64(), C.c_size_t()
-    check(lib().loc_window_joint_covariance_plan(C.byref(caps), wb.B, wb.counts.ctypes.data_as(ip), wb.r_idx.ctypes.data_as(ip),
-                                                 wb.s_idx.ctypes.data_as(ip), npm, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip),
+    check(lib().loc_window_joint_covariance_plan(C.byref(caps), wb.B, counts, r_idx, s_idx, npm, pc.ctypes.data_as(_IP), pr.ctypes.data_as(_IP),
                                                  C.byref(blocks), C.byref(nbytes)))
     return blocks.value, nbytes.value
 
@@ -141,6 +217,7 @@ class WindowSolver(_lib.Handle):
         check(L.loc_window_create(C.byref(h), device, int(batch), C.byref(caps), anchors.shape[0],
                                   anchors.ctypes.data_as(C.POINTER(C.c_double)), int(maximum_iteration)))
         self.h, self.L, self.B = h, L, int(batch)
+        self._resident = 0   # windows of the resident batch (upload / upload_dev)
         self.caps = (nv_max, nr_max, np_max, ns_max)
         self.lds_bytes = L.loc_window_lds_bytes(C.byref(caps))
         check(L.loc_window_set_jacobian(h, _lib.JAC_NUMERIC_G2O if jacobian in ("numeric", _lib.JAC_NUMERIC_G2O) else _lib.JAC_ANALYTIC))
@@ -149,39 +226,31 @@ class WindowSolver(_lib.Handle):
             check(L.loc_window_set_chain_threshold(h, int(chain_threshold)))
 
     def _endpoint1(self, wb):
-        dp = C.POINTER(C.c_double)
-        off1 = getattr(wb, "r_off1", None)
-        check(self.L.loc_window_set_endpoint1_offsets(self.h, wb.B, None if off1 is None else np.ascontiguousarray(off1).ctypes.data_as(dp)))
+        check(self.L.loc_window_set_endpoint1_offsets(self.h, wb.B, None if wb.r_off1 is None else np.ascontiguousarray(wb.r_off1).ctypes.data_as(_DP)))
 
     def _prior_information(self, wb):
-        dp = C.POINTER(C.c_double)
-        pinfo = getattr(wb, "p_info", None)
-        check(self.L.loc_window_set_prior_information(self.h, wb.B, None if pinfo is None else np.ascontiguousarray(pinfo, dtype=np.float64).ctypes.data_as(dp)))
+        check(self.L.loc_window_set_prior_information(self.h, wb.B, None if wb.p_info is None else np.ascontiguousarray(wb.p_info, dtype=np.float64).ctypes.data_as(_DP)))
+
+    def _tables(self, wb, refuse_off1=None):
+        """wb's eight table pointers (checked before any library call), after its prior table and its endpoint-1 lever arms are handed to
+        the handle.  refuse_off1: the name of a call that does not serve lever arms; it refuses them and leaves the handle's as they are."""
+        assert wb.caps == self.caps and wb.B <= self.B
+        tables = wb._pointers()
+        if refuse_off1 is None:
+            self._endpoint1(wb)
+        elif wb.r_off1 is not None:   # (the handle's endpoint-1 lever arms belong to its solves and stay as they are)
+            raise _lib.LocalizationAmdError(-5, f"{refuse_off1}: windows with endpoint-1 lever arms are not supported")
+        self._prior_information(wb)
+        return tables
 
     def solve(self, wb: WindowBatch):
-        assert wb.caps == self.caps and wb.B <= self.B
-        self._endpoint1(wb)
-        self._prior_information(wb)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        for a in (wb.counts, wb.poses, wb.r_idx, wb.r_val, wb.p_idx, wb.p_val, wb.s_idx, wb.s_val, wb.result):
-            assert a.flags["C_CONTIGUOUS"]
-        check(self.L.loc_window_solve_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
-                                           wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
-                                           wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                           wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp),
-                                           wb.result.ctypes.data_as(dp)))
+        tables = self._tables(wb)
+        check(self.L.loc_window_solve_host(self.h, wb.B, *tables, _host_out(wb.result, _F64, wb.B * 8)))
         return wb.result
 
     # ---- device-resident operation: upload once, solve any number of times from the uploaded estimates, download
     def upload(self, wb: WindowBatch):
-        assert wb.caps == self.caps and wb.B <= self.B
-        self._endpoint1(wb)
-        self._prior_information(wb)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        check(self.L.loc_window_upload(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
-                                       wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
-                                       wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                       wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp)))
+        check(self.L.loc_window_upload(self.h, wb.B, *self._tables(wb)))
         self._resident = wb.B
 
     def upload_dev(self, counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val, n=None, admit=None, stream=None):
@@ -193,19 +262,24 @@ class WindowSolver(_lib.Handle):
         stream; None: the handle's own; set_option("upload_dev_structures", 1): the arrowhead and forest verdicts as well); a batch with a refused window raises (LOC_ERR_INVALID; the error names the check and the lowest refused
         window) and leaves the previous resident batch as it was.  Returns when the arrays are free again, like upload().  The handle's tables of
         endpoint-1 lever arms / full information matrices stay as they are.  Plumbing only: the library checks everything."""
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         n = int(counts.shape[0]) if n is None else int(n)
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_upload_dev(self.h, st, n, *(ptr(t) for t in (counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val)), ptr(admit)))
+        check(self.L.loc_window_upload_dev(self.h, _stream(stream), n, *(_dev(t) for t in (counts, poses, r_idx, r_val, p_idx, p_val, s_idx, s_val)), _dev(admit)))
         self._resident = n
 
     def solve_resident(self, stream=None):
         check(self.L.loc_window_solve_resident(self.h, stream))
 
     def download(self, wb: WindowBatch):
-        dp = C.POINTER(C.c_double)
-        check(self.L.loc_window_download(self.h, wb.poses.ctypes.data_as(dp), wb.result.ctypes.data_as(dp)))
+        check(self.L.loc_window_download(self.h, wb.poses.ctypes.data_as(_DP), wb.result.ctypes.data_as(_DP)))
         return wb.result
+
+    def _covariance_out(self, B, out, npm=None):
+        """(cov, mask, status[, cross]) of a covariance call on B windows, the caller's or fresh, and their pointer arguments"""
+        nv = self.caps[0]
+        if out is None:
+            out = (np.zeros((B, nv, 6, 6)), np.zeros((B, nv), dtype=np.int32), np.zeros(B, dtype=np.int32)) + (() if npm is None else (np.zeros((B, npm, 6, 6)),))
+        sizes = ((_F64, B * nv * 36), (_I32, B * nv), (_I32, B)) + (() if npm is None else ((_F64, B * npm * 36),))
+        return tuple(out), [_host_out(x, dt, size) for x, (dt, size) in zip(out, sizes, strict=True)]
 
     # ---- marginal pose covariances at the given (solved) estimates (loc_window_covariance_*; DESIGN.md §2)
     def covariance(self, wb: WindowBatch, out=None):
@@ -219,59 +293,34 @@ class WindowSolver(_lib.Handle):
         solve() and upload() do, and so do joint_covariance() and marginal_prior().  The table belongs to the handle, not to a batch: after
         upload(batch with p_info) a covariance(another batch without one) clears it, and the resident batch is from then on solved and
         served with p_val's diagonals until a call with the table sets it again.  (The endpoint-1 lever arms are never touched here.)"""
-        assert wb.caps == self.caps and wb.B <= self.B
-        if getattr(wb, "r_off1", None) is not None:   # (refused here: the handle's endpoint-1 lever arms belong to its solves and stay as they are)
-            raise _lib.LocalizationAmdError(-5, "covariance: windows with endpoint-1 lever arms are not supported")
-        self._prior_information(wb)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        if out is None:
-            out = (np.zeros((wb.B, self.caps[0], 6, 6)), np.zeros((wb.B, self.caps[0]), dtype=np.int32), np.zeros(wb.B, dtype=np.int32))
-        cov, mask, status = out   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
-        assert cov.dtype == np.float64 and cov.size >= wb.B * self.caps[0] * 36 and cov.flags["C_CONTIGUOUS"]
-        assert mask.dtype == np.int32 and mask.size >= wb.B * self.caps[0] and status.dtype == np.int32 and status.size >= wb.B
-        check(self.L.loc_window_covariance_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
-                                                wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
-                                                wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                                wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp),
-                                                cov.ctypes.data_as(dp), mask.ctypes.data_as(ip), status.ctypes.data_as(ip)))
-        return cov, mask, status
+        tables = self._tables(wb, refuse_off1="covariance")
+        out, args = self._covariance_out(wb.B, out)   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
+        check(self.L.loc_window_covariance_host(self.h, wb.B, *tables, *args))
+        return out
 
     # ---- the marginal prior of a dropped pose (loc_window_marginal_prior_host; DESIGN.md §2)
     def marginal_prior(self, wb: WindowBatch, drop, out=None):
         """What dropping pose drop[b] of every (translation-only) window leaves on its one neighbour, at wb.poses: returns (slot [B] — the
         neighbour, -1: none —, prior [B][48] — Z^-1 as R(9), t(3) and the 6x6 information: add_prior's row —, grad [B][6], shift [B][6],
         rank [B], status [B]: 0 or LOC_ERR_SINGULAR, then a zero-information row = the plain drop).  drop: int [B], or one slot for all."""
-        assert wb.caps == self.caps and wb.B <= self.B
-        if getattr(wb, "r_off1", None) is not None:
-            raise _lib.LocalizationAmdError(-5, "marginal_prior: windows with endpoint-1 lever arms are not supported")
-        self._prior_information(wb)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        tables = self._tables(wb, refuse_off1="marginal_prior")
         drop = np.ascontiguousarray(np.broadcast_to(np.asarray(drop, dtype=np.int32), (wb.B,)))
         if out is None:
             out = (np.zeros(wb.B, dtype=np.int32), np.zeros((wb.B, 48)), np.zeros((wb.B, 6)), np.zeros((wb.B, 6)), np.zeros(wb.B, dtype=np.int32),
                    np.zeros(wb.B, dtype=np.int32))
         slot, prior, grad, shift, rank, status = out   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
-        for x, dt, size in ((slot, np.int32, wb.B), (prior, np.float64, wb.B * 48), (grad, np.float64, wb.B * 6), (shift, np.float64, wb.B * 6),
-                            (rank, np.int32, wb.B), (status, np.int32, wb.B)):
-            assert x.dtype == dt and x.size >= size and x.flags["C_CONTIGUOUS"]
-        check(self.L.loc_window_marginal_prior_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
-                                                    wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
-                                                    wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                                    wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp), drop.ctypes.data_as(ip),
-                                                    slot.ctypes.data_as(ip), prior.ctypes.data_as(dp), grad.ctypes.data_as(dp), shift.ctypes.data_as(dp),
-                                                    rank.ctypes.data_as(ip), status.ctypes.data_as(ip)))
+        args = [_host_out(x, dt, wb.B * width) for x, dt, width in ((slot, _I32, 1), (prior, _F64, 48), (grad, _F64, 6), (shift, _F64, 6), (rank, _I32, 1),
+                                                                    (status, _I32, 1))]
+        check(self.L.loc_window_marginal_prior_host(self.h, wb.B, *tables, drop.ctypes.data_as(_IP), *args))
         return slot, prior, grad, shift, rank, status
 
     def covariance_resident(self, cov, mask, status, stream=None):
         """The same for the uploaded batch at its solved poses (after solve_resident), asynchronous, into torch device tensors: cov float64
         [B][nv_max][6][6] (or [..][36]), mask int32 [B][nv_max], status int32 [B].  stream: a torch stream (None: the handle's own stream)."""
         import torch
-        n = getattr(self, "_resident", 0)
-        for t, dt, numel in ((cov, torch.float64, n * self.caps[0] * 36), (mask, torch.int32, n * self.caps[0]), (status, torch.int32, n)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= numel
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_covariance_resident(self.h, st, C.c_void_p(cov.data_ptr()), C.c_void_p(mask.data_ptr()),
-                                                    C.c_void_p(status.data_ptr())))
+        n = self._resident
+        args = [_dev_out(t, numel, dt) for t, dt, numel in ((cov, torch.float64, n * self.caps[0] * 36), (mask, torch.int32, n * self.caps[0]), (status, torch.int32, n))]
+        check(self.L.loc_window_covariance_resident(self.h, _stream(stream), *args))
 
     # ---- the resident fixed-lag slide (loc_window_slide_resident / loc_window_download_tables; DESIGN.md §2, "The resident slide")
     def slide_resident(self, new_pose, new_ranges=None, new_priors=None, drop_oldest=None, out=None, stream=None):
@@ -281,36 +330,23 @@ class WindowSolver(_lib.Handle):
         new pose, or None; drop_oldest: int [B] (0: that window only grows), None: every window drops.  out: (slot, prior, rank, status) torch
         device tensors (int32 [B], float64 [B][48], int32 [B], int32 [B]), each may be None.  Asynchronous on stream (a torch stream; None: the
         handle's own); the numpy inputs are read before the call returns.  Plumbing only: the library checks everything."""
-        n = getattr(self, "_resident", 0)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        keep = [np.ascontiguousarray(new_pose, dtype=np.float64).reshape(n, 12)]
-        drop = None
-        if drop_oldest is not None:
-            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(drop_oldest, dtype=np.int32), (n,))))
-            drop = keep[-1].ctypes.data_as(ip)
-        nrn, r_args = 0, (None, None, None)
-        if new_ranges is not None:
-            rc, ri, rv = new_ranges
-            rc = np.ascontiguousarray(rc, dtype=np.int32).reshape(n)
-            ri = np.ascontiguousarray(ri, dtype=np.int32).reshape(n, -1, 2)
-            nrn = ri.shape[1]
-            rv = np.ascontiguousarray(rv, dtype=np.float64).reshape(n, nrn, 5)
-            keep += [rc, ri, rv]
-            r_args = (rc.ctypes.data_as(ip), ri.ctypes.data_as(ip), rv.ctypes.data_as(dp))
-        npn, p_args = 0, (None, None)
+        n = self._resident
+        pose = np.ascontiguousarray(new_pose, dtype=np.float64).reshape(n, 12)
+        drop = None if drop_oldest is None else np.ascontiguousarray(np.broadcast_to(np.asarray(drop_oldest, dtype=np.int32), (n,)))
+        r_args = (0, None, None, None)
+        if new_ranges is not None:   # (the arrays converted here stay alive until the call has read them)
+            rc = np.ascontiguousarray(new_ranges[0], dtype=np.int32).reshape(n)
+            ri = np.ascontiguousarray(new_ranges[1], dtype=np.int32).reshape(n, -1, 2)
+            rv = np.ascontiguousarray(new_ranges[2], dtype=np.float64).reshape(n, ri.shape[1], 5)
+            r_args = (ri.shape[1], rc.ctypes.data_as(_IP), ri.ctypes.data_as(_IP), rv.ctypes.data_as(_DP))
+        p_args = (0, None, None)
         if new_priors is not None:
-            pc, pv = new_priors
-            pc = np.ascontiguousarray(pc, dtype=np.int32).reshape(n)
-            pv = np.ascontiguousarray(pv, dtype=np.float64).reshape(n, -1, 18)
-            npn = pv.shape[1]
-            keep += [pc, pv]
-            p_args = (pc.ctypes.data_as(ip), pv.ctypes.data_as(dp))
-        outs = []
-        for t, numel in zip(out if out is not None else (None,) * 4, (n, n * 48, n, n)):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= numel)
-            outs.append(None if t is None else C.c_void_p(t.data_ptr()))
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_slide_resident(self.h, st, drop, keep[0].ctypes.data_as(dp), nrn, *r_args, npn, *p_args, *outs))
+            pc = np.ascontiguousarray(new_priors[0], dtype=np.int32).reshape(n)
+            pv = np.ascontiguousarray(new_priors[1], dtype=np.float64).reshape(n, -1, 18)
+            p_args = (pv.shape[1], pc.ctypes.data_as(_IP), pv.ctypes.data_as(_DP))
+        outs = [_dev_out(t, numel, optional=True) for t, numel in zip(out if out is not None else (None,) * 4, (n, n * 48, n, n))]
+        check(self.L.loc_window_slide_resident(self.h, _stream(stream), None if drop is None else drop.ctypes.data_as(_IP), pose.ctypes.data_as(_DP),
+                                               *r_args, *p_args, *outs))
 
     def slide_resident_dev(self, new_pose, new_ranges, new_priors=None, drop_oldest=None, out=None, stream=None):
         """slide_resident() with every per-window input in device memory (loc_window_slide_resident_dev): device pointers (int) or objects
@@ -321,18 +357,9 @@ class WindowSolver(_lib.Handle):
         code of the rule window b breaks, and a refused window stays as it was.  Asynchronous on stream (a torch stream; None: the handle's own),
         no host pass, no copy: the caller keeps the arrays alive and unchanged until the stream has passed the call, and orders its own writes to
         them before it.  Plumbing only: the library checks everything."""
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        nrn, r_args = 0, (None, None, None)
-        if new_ranges is not None:
-            nrn = int(new_ranges[3]) if len(new_ranges) > 3 else int(new_ranges[1].shape[-2])
-            r_args = tuple(ptr(t) for t in new_ranges[:3])
-        npn, p_args = 0, (None, None)
-        if new_priors is not None:
-            npn = int(new_priors[2]) if len(new_priors) > 2 else int(new_priors[1].shape[-2])
-            p_args = tuple(ptr(t) for t in new_priors[:2])
-        outs = [ptr(t) for t in (out if out is not None else (None,) * 5)]
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_slide_resident_dev(self.h, st, ptr(drop_oldest), ptr(new_pose), nrn, *r_args, npn, *p_args, *outs))
+        outs = [_dev(t) for t in (out if out is not None else (None,) * 5)]
+        check(self.L.loc_window_slide_resident_dev(self.h, _stream(stream), _dev(drop_oldest), _dev(new_pose), *_new_rows(new_ranges, 3),
+                                                   *_new_rows(new_priors, 2), *outs))
 
     def slide_plain_resident_dev(self, new_pose, new_ranges, new_priors=None, new_se3=None, drop_oldest=None, out=None, stream=None):
         """The plain drop for resident 6-DoF chain batches (loc_window_slide_plain_resident_dev): slot 0 goes with every factor on it, nothing
@@ -344,22 +371,9 @@ class WindowSolver(_lib.Handle):
         data_ptr() or None.  Each wave admits its own window: admit[b] is 0 or the code of the rule window b breaks, and a refused window stays
         as it was.  Asynchronous on stream (a torch stream; None: the handle's own), no host pass, no copy: the caller keeps the arrays alive
         and unchanged until the stream has passed the call.  Plumbing only: the library checks everything."""
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        nrn, r_args = 0, (None, None, None)
-        if new_ranges is not None:
-            nrn = int(new_ranges[3]) if len(new_ranges) > 3 else int(new_ranges[1].shape[-2])
-            r_args = tuple(ptr(t) for t in new_ranges[:3])
-        npn, p_args = 0, (None, None)
-        if new_priors is not None:
-            npn = int(new_priors[2]) if len(new_priors) > 2 else int(new_priors[1].shape[-2])
-            p_args = tuple(ptr(t) for t in new_priors[:2])
-        nsn, s_args = 0, (None, None, None)
-        if new_se3 is not None:
-            nsn = int(new_se3[3]) if len(new_se3) > 3 else int(new_se3[1].shape[-2])
-            s_args = tuple(ptr(t) for t in new_se3[:3])
-        outs = [ptr(t) for t in (out if out is not None else (None,) * 2)]
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_slide_plain_resident_dev(self.h, st, ptr(drop_oldest), ptr(new_pose), nrn, *r_args, npn, *p_args, nsn, *s_args, *outs))
+        outs = [_dev(t) for t in (out if out is not None else (None,) * 2)]
+        check(self.L.loc_window_slide_plain_resident_dev(self.h, _stream(stream), _dev(drop_oldest), _dev(new_pose), *_new_rows(new_ranges, 3),
+                                                         *_new_rows(new_priors, 2), *_new_rows(new_se3, 3), *outs))
 
     # ---- rows from raw messages (loc_window_set_message_config / _message_rows_dev / _push_messages_resident_dev; DESIGN.md §2)
     MSG_RANGE, MSG_IMU, MSG_LIDAR, MSG_TWIST = 1, 2, 4, 8
@@ -373,44 +387,35 @@ class WindowSolver(_lib.Handle):
         gate — and /uwb/antennaOffset as [n_antenna][3]); also allocates the handle's block of output arrays."""
         cfg = MessageConfig(int(trajectory_length), float(maximum_velocity), float(distance_outlier))
         ant = None if antenna_xyz is None else np.ascontiguousarray(antenna_xyz, dtype=np.float64).reshape(-1, 3)
-        check(self.L.loc_window_set_message_config(self.h, C.byref(cfg), 0 if ant is None else ant.shape[0],
-                                                   None if ant is None else ant.ctypes.data_as(C.POINTER(C.c_double))))
+        check(self.L.loc_window_set_message_config(self.h, C.byref(cfg), 0 if ant is None else ant.shape[0], None if ant is None else ant.ctypes.data_as(_DP)))
 
     @staticmethod
     def _ptr_struct(fields, values):
         """a struct of len(fields) void pointers from a dict of device pointers (int) or objects with data_ptr(); a missing name is NULL"""
-        ptr = lambda t: None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        return (C.c_void_p * len(fields))(*[ptr(values.get(f)) for f in fields])
+        return (C.c_void_p * len(fields))(*[_dev(values.get(f)).value for f in fields])
 
     def message_rows_dev(self, kinds_mask, msgs, out, stream=None):
         """Build only (loc_window_message_rows_dev): msgs a dict of the message arrays by MSG_FIELDS' names (kind int32 [B], dt float64 [B],
         anchor / antenna int32 [B], distance / distance_err float32 [B], imu float64 [B][7], lidar_z float64 [B], twist float64 [B][42]), out
         a dict of the eleven output arrays by MSG_ROWS' names ("verdict" may be missing); device pointers or objects with data_ptr().
         Asynchronous on stream (a torch stream; None: the handle's own).  Plumbing only: the library checks everything."""
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
         m, o = self._ptr_struct(self.MSG_FIELDS, msgs), self._ptr_struct(self.MSG_ROWS, out)
-        check(self.L.loc_window_message_rows_dev(self.h, st, int(kinds_mask), C.byref(m), C.byref(o)))
+        check(self.L.loc_window_message_rows_dev(self.h, _stream(stream), int(kinds_mask), C.byref(m), C.byref(o)))
 
     def push_messages_resident_dev(self, kinds_mask, msgs, verdict=None, status=None, admit=None, stream=None):
         """Build into the handle's own block, then the slide the resident verdict calls for, on the same stream
         (loc_window_push_messages_resident_dev).  msgs as for message_rows_dev(); verdict / status / admit int32 [B] device arrays or None.
         Read verdict first: a window with MSG_NONE or MSG_REJECTED shows admit code 2, and that is not an error."""
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
         m = self._ptr_struct(self.MSG_FIELDS, msgs)
-        check(self.L.loc_window_push_messages_resident_dev(self.h, st, int(kinds_mask), C.byref(m), ptr(verdict), ptr(status), ptr(admit)))
+        check(self.L.loc_window_push_messages_resident_dev(self.h, _stream(stream), int(kinds_mask), C.byref(m), _dev(verdict), _dev(status), _dev(admit)))
 
     def download_batch(self):
         """The resident batch as it stands, as a WindowBatch (loc_window_download_tables): counts, the estimates the next resident solve
         starts from, every index and value table, and p_info when the handle has a table of full information matrices."""
-        n = getattr(self, "_resident", 0)
-        wb = WindowBatch(n, *self.caps)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        check(self.L.loc_window_download_tables(self.h, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp), wb.r_idx.ctypes.data_as(ip),
-                                                wb.r_val.ctypes.data_as(dp), wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                                wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp), None))
-        pinfo = np.zeros((n, max(self.caps[2], 1), 36))
-        if self.L.loc_window_download_tables(self.h, None, None, None, None, None, None, None, None, pinfo.ctypes.data_as(dp)) == _lib.LOC_OK:
+        wb = WindowBatch(self._resident, *self.caps)
+        check(self.L.loc_window_download_tables(self.h, *wb._pointers(), None))
+        pinfo = np.zeros((wb.B, max(self.caps[2], 1), 36))
+        if self.L.loc_window_download_tables(self.h, None, None, None, None, None, None, None, None, pinfo.ctypes.data_as(_DP)) == _lib.LOC_OK:
             wb.p_info = pinfo   # (LOC_ERR_INVALID: the handle has no table)
         return wb
 
@@ -420,45 +425,28 @@ class WindowSolver(_lib.Handle):
         [B][np_max], s_chi2 [B][ns_max] — slots beyond a window's count 0 —, total [B], active int32 [B] = range rows with information != 0
         + priors + EdgeSE3).  out: the caller's five arrays, each may be None (that output is skipped).  Hands wb's endpoint-1 lever arms and
         prior table to the handle first, as solve() does."""
-        assert wb.caps == self.caps and wb.B <= self.B
-        self._endpoint1(wb)
-        self._prior_information(wb)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        tables = self._tables(wb)
         if out is None:
             out = (np.zeros((wb.B, max(self.caps[1], 1))), np.zeros((wb.B, max(self.caps[2], 1))), np.zeros((wb.B, max(self.caps[3], 1))),
                    np.zeros(wb.B), np.zeros(wb.B, dtype=np.int32))
-        args = []
-        for x, dt, size in zip(out, (np.float64,) * 4 + (np.int32,), (wb.B * self.caps[1], wb.B * self.caps[2], wb.B * self.caps[3], wb.B, wb.B)):
-            assert x is None or (x.dtype == dt and x.size >= size and x.flags["C_CONTIGUOUS"])
-            args.append(None if x is None else x.ctypes.data_as(ip if dt == np.int32 else dp))
-        check(self.L.loc_window_edge_chi2_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
-                                               wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
-                                               wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                               wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp), *args))
+        args = [_host_out(x, dt, wb.B * width, optional=True) for x, dt, width in zip(out, (_F64,) * 4 + (_I32,), self.caps[1:] + (1, 1), strict=True)]
+        check(self.L.loc_window_edge_chi2_host(self.h, wb.B, *tables, *args))
         return tuple(out)
 
     def edge_chi2_resident(self, r_chi2, p_chi2, s_chi2, total, active, stream=None):
         """The same for the uploaded batch at its solved poses (after solve_resident), asynchronous, into torch device tensors (float64
         [B][nr_max] / [B][np_max] / [B][ns_max] / [B], int32 [B]); each may be None.  stream: a torch stream (None: the handle's own)."""
-        n = getattr(self, "_resident", 0)
-        ptrs = []
-        for t, numel in zip((r_chi2, p_chi2, s_chi2, total, active), (n * self.caps[1], n * self.caps[2], n * self.caps[3], n, n)):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= numel)
-            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_edge_chi2_resident(self.h, st, *ptrs))
+        n = self._resident
+        args = [_dev_out(t, n * width, optional=True) for t, width in zip((r_chi2, p_chi2, s_chi2, total, active), self.caps[1:] + (1, 1))]
+        check(self.L.loc_window_edge_chi2_resident(self.h, _stream(stream), *args))
 
     def prune_resident(self, chi2_max=2.0, min_edges=100, removed=None, n_removed=None, stream=None):
         """The reference's removal rule on the uploaded batch, in place on the device (after solve_resident): a window with more than min_edges
         active edges gets information 0.0 on every range row with information != 0 and chi2 > chi2_max at the solved poses.  removed int32
         [B][nr_max], n_removed int32 [B]: torch device tensors, each may be None.  Asynchronous on stream (None: the handle's own)."""
-        n = getattr(self, "_resident", 0)
-        ptrs = []
-        for t, numel in ((removed, n * self.caps[1]), (n_removed, n)):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= numel)
-            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_prune_resident(self.h, st, float(chi2_max), int(min_edges), *ptrs))
+        n = self._resident
+        args = [_dev_out(t, numel, optional=True) for t, numel in ((removed, n * self.caps[1]), (n_removed, n))]
+        check(self.L.loc_window_prune_resident(self.h, _stream(stream), float(chi2_max), int(min_edges), *args))
 
     # ---- publish and path records of the resident batch (loc_window_publish_resident / loc_window_path_resident; DESIGN.md §2)
     def publish_resident(self, minimum_optimize_error, trajectory_length, flags, realtime=None, optimized=None, chi2=None, n_published=None, stream=None):
@@ -467,19 +455,15 @@ class WindowSolver(_lib.Handle):
         float64 [B][7] (x, y, z, qx, qy, qz, qw; written only with bit 0 / bits 0 and 1), chi2 float64 [B], n_published int32 [1].  Device
         pointers or objects with data_ptr(); all but flags may be None.  Asynchronous on stream (a torch stream; None: the handle's own).
         Plumbing only: the library checks everything."""
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_publish_resident(self.h, st, float(minimum_optimize_error), int(trajectory_length), ptr(flags), ptr(realtime),
-                                                 ptr(optimized), ptr(chi2), ptr(n_published)))
+        check(self.L.loc_window_publish_resident(self.h, _stream(stream), float(minimum_optimize_error), int(trajectory_length), _dev(flags), _dev(realtime),
+                                                 _dev(optimized), _dev(chi2), _dev(n_published)))
 
     def path_resident(self, trajectory_length, path, present, first=0, count=None, stream=None):
         """Path indices first .. first + count - 1 (count None: up to trajectory_length - 1) of every window of the uploaded batch: path float64
         [B][count][7], written only where present int32 [B][count] is 1.  first = 0: vertices2path; first = trajectory_length // 2: the tail
         the reference flushes at exit.  Device pointers or objects with data_ptr().  Asynchronous on stream; plumbing only."""
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
         count = int(trajectory_length) - int(first) if count is None else int(count)
-        check(self.L.loc_window_path_resident(self.h, st, int(trajectory_length), int(first), count, ptr(path), ptr(present)))
+        check(self.L.loc_window_path_resident(self.h, _stream(stream), int(trajectory_length), int(first), count, _dev(path), _dev(present)))
 
     def covariance_plan(self, wb: WindowBatch):
         """covariance_plan(wb) for this handle's capacities"""
@@ -492,40 +476,21 @@ class WindowSolver(_lib.Handle):
         coordinates; excluded rows / columns 0; NaN for a singular window; slots p >= pair_counts[b] are 0).  pairs: int [B][npair_max][2]
         pose slots, or [npair_max][2] for every window alike; pair_counts: [B], None = all of them.  Same coverage as covariance(); a pair
         count or a slot out of range raises LOC_ERR_INVALID with nothing written.  Returns (cov, mask, status, cross)."""
-        assert wb.caps == self.caps and wb.B <= self.B
-        if getattr(wb, "r_off1", None) is not None:
-            raise _lib.LocalizationAmdError(-5, "covariance: windows with endpoint-1 lever arms are not supported")
-        self._prior_information(wb)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        tables = self._tables(wb, refuse_off1="covariance")
         npm, pc, pr = _pair_tables(wb.B, pairs, pair_counts)
-        if out is None:
-            out = (np.zeros((wb.B, self.caps[0], 6, 6)), np.zeros((wb.B, self.caps[0]), dtype=np.int32), np.zeros(wb.B, dtype=np.int32),
-                   np.zeros((wb.B, npm, 6, 6)))
-        cov, mask, status, cross = out   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
-        assert cov.dtype == np.float64 and cov.size >= wb.B * self.caps[0] * 36 and cov.flags["C_CONTIGUOUS"]
-        assert mask.dtype == np.int32 and mask.size >= wb.B * self.caps[0] and status.dtype == np.int32 and status.size >= wb.B
-        assert cross.dtype == np.float64 and cross.size >= wb.B * npm * 36 and cross.flags["C_CONTIGUOUS"]
-        check(self.L.loc_window_joint_covariance_host(self.h, wb.B, wb.counts.ctypes.data_as(ip), wb.poses.ctypes.data_as(dp),
-                                                      wb.r_idx.ctypes.data_as(ip), wb.r_val.ctypes.data_as(dp),
-                                                      wb.p_idx.ctypes.data_as(ip), wb.p_val.ctypes.data_as(dp),
-                                                      wb.s_idx.ctypes.data_as(ip), wb.s_val.ctypes.data_as(dp),
-                                                      npm, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip),
-                                                      cov.ctypes.data_as(dp), mask.ctypes.data_as(ip), status.ctypes.data_as(ip), cross.ctypes.data_as(dp)))
-        return cov, mask, status, cross
+        out, args = self._covariance_out(wb.B, out, npm)   # (out: caller's arrays of these shapes and dtypes; left untouched when the call fails)
+        check(self.L.loc_window_joint_covariance_host(self.h, wb.B, *tables, npm, pc.ctypes.data_as(_IP), pr.ctypes.data_as(_IP), *args))
+        return out
 
     def joint_covariance_resident(self, pairs, pair_counts, cov, mask, status, cross, stream=None):
         """joint_covariance for the uploaded batch at its solved poses, asynchronous: pairs / pair_counts numpy arrays as above (read before
         the call returns), cov / mask / status / cross torch device tensors (cross float64 [B][npair_max][6][6] or [..][36])."""
         import torch
-        n = getattr(self, "_resident", 0)
+        n = self._resident
         npm, pc, pr = _pair_tables(n, pairs, pair_counts)
-        for t, dt, numel in ((cov, torch.float64, n * self.caps[0] * 36), (mask, torch.int32, n * self.caps[0]), (status, torch.int32, n),
-                             (cross, torch.float64, n * npm * 36)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= numel
-        ip = C.POINTER(C.c_int32)
-        st = None if stream is None else C.c_void_p(stream.cuda_stream)
-        check(self.L.loc_window_joint_covariance_resident(self.h, st, npm, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip), C.c_void_p(cov.data_ptr()),
-                                                          C.c_void_p(mask.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(cross.data_ptr())))
+        args = [_dev_out(t, numel, dt) for t, dt, numel in ((cov, torch.float64, n * self.caps[0] * 36), (mask, torch.int32, n * self.caps[0]), (status, torch.int32, n),
+                                                            (cross, torch.float64, n * npm * 36))]
+        check(self.L.loc_window_joint_covariance_resident(self.h, _stream(stream), npm, pc.ctypes.data_as(_IP), pr.ctypes.data_as(_IP), *args))
 
     def joint_covariance_plan(self, wb: WindowBatch, pairs, pair_counts=None):
         """joint_covariance_plan(wb, pairs, pair_counts) for this handle's capacities"""

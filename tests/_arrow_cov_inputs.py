@@ -13,13 +13,6 @@ SURVEYED = np.vstack([FIXED, [[4.0, 4.0, 3.0], [-4.0, -4.0, 0.2]]])
 MIN_NODES = 4
 
 
-def copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
-
-
 def arrow_cov_batch(la, rng, B, T, A, rich):
     """B hypotheses of up to T tag poses and up to A unknown anchors.  rich: ragged trajectory lengths and border sizes inside the batch, a
     missing smoothness link, ranges stored border-first, doubled (pose, anchor) ranges, missed ranges, ranges between unknown anchors, ranges

@@ -86,14 +86,14 @@ def margin(wb, r_chi2, chi2_max):
 
 def with_rows_zeroed(la, wb, removed):
     """a copy of wb whose flagged range rows have information 0.0 (what the prune leaves on the device)"""
-    out = copy_batch(la, wb)
+    out = wb.copy()
     out.r_val[:, :, 1] = np.where(removed[:, :out.r_val.shape[1]] != 0, 0.0, out.r_val[:, :, 1])
     return out
 
 
 def with_rows_deleted(la, wb, removed):
     """a copy of wb without the flagged range rows (the reference's level 1 as the oracle can express it: the edge is not in the graph)"""
-    out = copy_batch(la, wb)
+    out = wb.copy()
     for i in range(wb.B):
         nr = int(wb.counts[i, 1])
         keep = [e for e in range(nr) if not removed[i, e]]
@@ -102,13 +102,4 @@ def with_rows_deleted(la, wb, removed):
         if out.r_off1 is not None:
             out.r_off1[i] = 0.0; out.r_off1[i, :len(keep)] = wb.r_off1[i, keep]
         out.counts[i, 1] = len(keep)
-    return out
-
-
-def copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val", "result"):
-        getattr(out, name)[:] = getattr(wb, name)
-    out.p_info = None if getattr(wb, "p_info", None) is None else wb.p_info.copy()
-    out.r_off1 = None if getattr(wb, "r_off1", None) is None else wb.r_off1.copy()
     return out

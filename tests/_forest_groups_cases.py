@@ -93,12 +93,3 @@ def mixed_batch(la, topos, of, seed, vary=True):
     for b in range(len(of)):
         fill_window(wb, b, topos[of[b]], rng, shift=(b // len(topos)) % 4 if vary else 0, flip_robust=vary and b % 3 == 1)
     return wb
-
-
-def copy_batch(la, wb, rows=None):
-    """a copy of wb, or of its windows `rows` as a batch of their own"""
-    rows = np.arange(wb.B) if rows is None else np.asarray(rows)
-    out = la.WindowBatch(len(rows), *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)[rows]
-    return out

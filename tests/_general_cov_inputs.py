@@ -14,13 +14,6 @@ IMU_INFO = np.array([0, 0, 0, 1, 1, 1.0]) / 4.592449e-06
 SMOOTH_INFO = 1.0 / (5.0 * (1 / 32) / 3) ** 2
 
 
-def copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
-
-
 def _trajectory(rng, T, six_dof=True):
     tt = np.cumsum(rng.normal(0, 0.05, (T, 3)), axis=0) + np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.5, 1.5), 1.1])
     if six_dof:

@@ -9,7 +9,7 @@ import functools
 import numpy as np
 from scipy.spatial.transform import Rotation
 
-from _general_cov_inputs import ANCH, IMU_INFO, LEVER, _anchor_ranges, _se3, _trajectory, copy_batch, fill_arrowhead6, window_pairs
+from _general_cov_inputs import ANCH, IMU_INFO, LEVER, _anchor_ranges, _se3, _trajectory, fill_arrowhead6, window_pairs
 
 
 # ---- pair builders: lists of (slot, slot) ---------------------------------------------------------------------------------------------
@@ -215,7 +215,7 @@ def _built(name):
 def build_batch(name):
     """a fresh copy of batch `name` (the same bits every time)"""
     import localization_amd as la
-    return copy_batch(la, _built(name))
+    return _built(name).copy()
 
 
 def batch_perms(name):

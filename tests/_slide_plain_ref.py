@@ -8,6 +8,8 @@ the zero-range smoothness edge to the pose before it, IMU rotation priors, optio
 import numpy as np
 from scipy.spatial.transform import Rotation
 
+from localization_amd.window import WindowBatch
+
 ANCH = np.array([[3, -3, 0.58], [3, 3, 1.97], [-3, 3, 0.54], [-3, -3, 1.76]], dtype=float)
 LEVER = np.array([0.1, 0.0, -0.05])
 RANGE_INFO = 1.0 / 0.055 ** 2
@@ -15,7 +17,7 @@ SMOOTH_INFO = 1.0 / (5.0 * (1 / 32) / 3) ** 2
 IMU_INFO = np.array([0, 0, 0, 1, 1, 1.0]) / 4.592449e-06
 Z_INFO = np.array([0, 0, 1 / 0.05, 0, 0, 0.0])
 LOC_ERR_INVALID, LOC_ERR_UNSUPPORTED = -1, -5
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+TABLES = WindowBatch.TABLES
 
 
 def _inv_rows(R, t):
@@ -170,13 +172,6 @@ def assert_same_tables(got, ref, what="", windows=None):
         for name, n in (("poses", nv), ("r_idx", nr), ("r_val", nr), ("p_idx", npr), ("p_val", npr), ("s_idx", ns), ("s_val", ns)):
             x, y = getattr(got, name)[b, :n], getattr(ref, name)[b, :n]
             assert x.tobytes() == y.tobytes(), (what, name, b, x, y)
-
-
-def copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in TABLES:
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
 
 
 # ---- the cases: name -> eight windows ------------------------------------------------------------------------------------------------------------------

@@ -97,14 +97,6 @@ def case_batch(la, name):
     return wb
 
 
-def copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    out.p_info = None if wb.p_info is None else wb.p_info.copy()
-    return out
-
-
 def diagonal_batch(la):
     """ten-pose chains with DIAGONAL priors alone and no table: a lidar z prior on pose 0, a position prior on pose 3"""
     wb = la.WindowBatch(8, *caps(10, 2))

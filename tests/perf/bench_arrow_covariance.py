@@ -28,10 +28,7 @@ def main():
     import bench_window as bw
     B, nd = args.batch, 32
     small, _, anchors, nv = bw.build_selfcal(nd, np.random.default_rng(21))
-    wb = la.WindowBatch(B, *small.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(small, name)
-        getattr(wb, name)[:] = np.resize(src, (B,) + src.shape[1:])
+    wb = small.tile(B)
     cov = torch.empty((B, nv, 36), dtype=torch.float64, device="cuda")
     mask = torch.empty((B, nv), dtype=torch.int32, device="cuda")
     status = torch.empty((B,), dtype=torch.int32, device="cuda")

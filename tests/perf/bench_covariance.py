@@ -18,16 +18,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def _tile(la, wb, B):
-    """B windows: the distinct windows of wb repeated"""
-    out = la.WindowBatch(B, *wb.caps)
-    reps = -(-B // wb.B)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(wb, name)
-        getattr(out, name)[:] = np.concatenate([src] * reps)[:B]
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=65536)
@@ -44,7 +34,7 @@ def main():
               "uwb_imu_T12": lambda: _observable_batch(la, rng, 1024, 12, True, True),
               "uwb_twist_T15": lambda: _twist_batch(la, rng, 1024, 15, True)}
     for name, make in shapes.items():
-        wb = _tile(la, make(), args.batch)
+        wb = make().tile(args.batch)
         B = wb.B
         s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="numeric")
         s.upload(wb)

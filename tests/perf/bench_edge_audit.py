@@ -24,14 +24,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
 
-def _tile(la, wb, B):
-    out = la.WindowBatch(B, *wb.caps)
-    pick = np.arange(B) % wb.B
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)[pick]
-    return out
-
-
 def _stats(v):
     return {"median": round(float(np.median(v)), 4), "min": round(float(np.min(v)), 4), "max": round(float(np.max(v)), 4)}
 
@@ -57,8 +49,8 @@ def main():
     import _fixed_lag as F
     import _general_cov_inputs as G
     dev = torch.device("cuda", 0)
-    shapes = (("chains", lambda: _tile(la, F.first_window(la, [F.Chain(9950 + i, 10, 4) for i in range(8)], 10), args.chains), F.ANCH, {}),
-              ("keyframes", lambda: _tile(la, G.keyframe_batch(la, 9960, 4, 500, 10), args.keyframes), G.ANCH, {"chain_min_batch": 1}))
+    shapes = (("chains", lambda: F.first_window(la, [F.Chain(9950 + i, 10, 4) for i in range(8)], 10).tile(args.chains), F.ANCH, {}),
+              ("keyframes", lambda: G.keyframe_batch(la, 9960, 4, 500, 10).tile(args.keyframes), G.ANCH, {"chain_min_batch": 1}))
     for name, build, anchors, opts in shapes:
         wb = build()
         B = wb.B

@@ -27,17 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 W, DISTINCT = 10, 256
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
 OPTION = "prior_information_structured"
-
-
-def _tile(la, wb, B):
-    out = la.WindowBatch(B, *wb.caps)
-    reps = -(-B // wb.B)
-    for name in TABLES:
-        getattr(out, name)[:] = np.concatenate([getattr(wb, name)] * reps)[:B]
-    out.p_info = None if wb.p_info is None else np.concatenate([wb.p_info] * reps)[:B].copy()
-    return out
 
 
 def _stats(xs):
@@ -54,7 +44,7 @@ def _after_one_slide(la, F):
     slot, prior, _, _, rank, status = s.marginal_prior(g, 0)
     assert not status.any() and (slot == 1).all()
     base = F.next_window(la, g, chains, 1, W, slot, prior)
-    g = _tile(la, base, DISTINCT)
+    g = base.tile(DISTINCT)
     s.solve(g)
     slot, prior, _, _, _, status = s.marginal_prior(g, 0)
     s.close()
@@ -82,8 +72,8 @@ def main():
     import _fixed_lag as F
     base, after, rank = _after_one_slide(la, F)
     for B in (int(x) for x in args.batches.split(",")):
-        wb = _tile(la, base, B)
-        bare = _tile(la, base, B)
+        wb = base.tile(B)
+        bare = base.tile(B)
         bare.p_info = None                       # (add_prior_row left diag(W) in p_val: the floor's priors)
         a = la.WindowSolver(F.ANCH, B, *wb.caps, jacobian="numeric")
         f = la.WindowSolver(F.ANCH, B, *wb.caps, jacobian="numeric")
@@ -121,11 +111,11 @@ def main():
         # one full slide on the host path, both settings alternating
         slide = {"slide_general": [], "slide_structured": []}
         parts = {}
-        template = _tile(la, after, B)
+        template = after.tile(B)
         for _ in range(args.reps):
             for structured, key in ((0, "slide_general"), (1, "slide_structured")):
                 a.set_option(OPTION, structured)
-                g = _tile(la, base, B)
+                g = base.tile(B)
                 t0 = time.perf_counter()
                 a.solve(g)
                 t1 = time.perf_counter()

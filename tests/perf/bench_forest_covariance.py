@@ -18,16 +18,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def _tile(la, wb, B):
-    """B windows: the distinct windows of wb repeated"""
-    out = la.WindowBatch(B, *wb.caps)
-    reps = -(-B // wb.B)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(wb, name)
-        getattr(out, name)[:] = np.concatenate([src] * reps)[:B]
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16384)
@@ -37,7 +27,7 @@ def main():
     import localization_amd as la
     from test_gpu_tree_parity import ANCH, _forest_batch
     T = 64
-    wb = _tile(la, _forest_batch(la, np.random.default_rng(0), 256, T, 8, False), args.batch)
+    wb = _forest_batch(la, np.random.default_rng(0), 256, T, 8, False).tile(args.batch)
     B = wb.B
     s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="numeric", bw_max=T - 1)
     s.upload(wb)

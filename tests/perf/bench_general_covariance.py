@@ -21,16 +21,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def _tile(la, wb, B):
-    """B windows: the distinct windows of wb repeated"""
-    out = la.WindowBatch(B, *wb.caps)
-    reps = -(-B // wb.B)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(wb, name)
-        getattr(out, name)[:] = np.concatenate([src] * reps)[:B]
-    return out
-
-
 def _run(la, torch, wb, reps, general):
     from _general_cov_inputs import ANCH
     B, T = wb.B, wb.caps[0]
@@ -70,14 +60,14 @@ def main():
     import localization_amd as la
     import _general_cov_inputs as G
     if args.shape in ("a", "all"):
-        wb = _tile(la, G.chain_batch(la, 1, 64, 128, False, ragged=False), args.batch_a)
+        wb = G.chain_batch(la, 1, 64, 128, False, ragged=False).tile(args.batch_a)
         out = {"shape": "a: translation-only chains x 128 poses", "pass": "envelope_covariance_kernel", **_run(la, torch, wb, args.reps, True)}
         print(json.dumps(out), flush=True)
-        wb = _tile(la, G.chain_batch(la, 1, 64, 64, False, ragged=False), args.batch_a)
+        wb = G.chain_batch(la, 1, 64, 64, False, ragged=False).tile(args.batch_a)
         out = {"shape": "a (scale): the same chains x 64 poses", "pass": "covariance_kernel<3>", **_run(la, torch, wb, args.reps, False)}
         print(json.dumps(out), flush=True)
     if args.shape in ("b", "all"):
-        wb = _tile(la, G.keyframe_batch(la, 2, 8, 500, 10), args.batch_b)
+        wb = G.keyframe_batch(la, 2, 8, 500, 10).tile(args.batch_b)
         out = {"shape": "b: key-frame windows x 500 poses, a key every 10, leaves-first", "pass": "envelope_covariance_kernel", **_run(la, torch, wb, args.reps, True)}
         print(json.dumps(out), flush=True)
 

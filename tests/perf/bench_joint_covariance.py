@@ -24,15 +24,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _tile(la, wb, B):
-    """B windows: the distinct windows of wb repeated"""
-    out = la.WindowBatch(B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(wb, name)
-        getattr(out, name)[:] = np.resize(src, (B,) + src.shape[1:])
-    return out
-
-
 def _tables(B, per_window):
     npm = max(len(p) for p in per_window)
     pairs = np.zeros((B, npm, 2), dtype=np.int32)
@@ -54,23 +45,23 @@ def _shapes(la):
 
     def chain():
         small = _observable_batch(la, np.random.default_rng(0), 1024, 10, False, False, translation_only=True)
-        return _tile(la, small, 65536), ANCH, {}, {}, [[(k, k + 1) for k in range(int(nv) - 1)] for nv in small.counts[:, 0]]
+        return small.tile(65536), ANCH, {}, {}, [[(k, k + 1) for k in range(int(nv) - 1)] for nv in small.counts[:, 0]]
 
     def forest():
         T, every = 64, 8
         small = _forest_batch(la, np.random.default_rng(0), 256, T, every, False)
         key = np.where(np.arange(T) < every, 0, (np.arange(T) // every) * every - 1)
         leaves = [k for k in range(1, T) if k not in set(key.tolist())]
-        return _tile(la, small, 16384), FANCH, {"bw_max": T - 1}, {}, [[(k, int(key[k])) for k in leaves]]
+        return small.tile(16384), FANCH, {"bw_max": T - 1}, {}, [[(k, int(key[k])) for k in leaves]]
 
     def arrow():
         small, _, anchors, nv = bw.build_selfcal(32, np.random.default_rng(21))
         pairs = [[(a, b) for a in range(int(n) - 10, int(n)) for b in range(a + 1, int(n))] for n in small.counts[:, 0]]
-        return _tile(la, small, 1024), anchors, {"maximum_iteration": 10, "bw_max": nv - 1}, {}, pairs
+        return small.tile(1024), anchors, {"maximum_iteration": 10, "bw_max": nv - 1}, {}, pairs
 
     def envelope():
         small = G.keyframe_batch(la, 2, 8, 500, 10)
-        return _tile(la, small, 64), G.ANCH, {}, {"covariance_general": 1}, [[(499, 250)]]
+        return small.tile(64), G.ANCH, {}, {"covariance_general": 1}, [[(499, 250)]]
 
     return {"chain": ("covariance_kernel<3>", "65 536 x T = 10, adjacent pairs", chain),
             "forest": ("forest_covariance_kernel", "16 384 x 64 poses, leaf - key pairs", forest),

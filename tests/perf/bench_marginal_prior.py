@@ -18,14 +18,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _tile(la, wb, B):
-    out = la.WindowBatch(B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(wb, name)
-        getattr(out, name)[:] = np.resize(src, (B,) + src.shape[1:])
-    return out
-
-
 def _row(ms):
     return {"median_ms": round(float(np.median(ms)), 4), "best_ms": round(min(ms), 4), "spread": round(max(ms) / min(ms) - 1, 4)}
 
@@ -44,7 +36,7 @@ def main():
     small = la.WindowBatch(distinct, T, T * 4 + (T - 1), 0, 0)
     for i in range(distinct):
         F.add_chain_poses(small, i, F.Chain(100 + i, T, 4), 0, T)
-    wb = _tile(la, small, args.windows)
+    wb = small.tile(args.windows)
     s = la.WindowSolver(F.ANCH, wb.B, *wb.caps, jacobian=args.jacobian, bw_max=1)
     s.solve(wb)   # (the passes below run at the solved estimates)
     solve_kernel = s.last_kernel_kind()
@@ -57,7 +49,7 @@ def main():
         t_mp = s.last_covariance_ms()
         cov_out = s.covariance(wb, out=cov_out)
         t_cov = s.last_covariance_ms()
-        again = _tile(la, wb, wb.B) if rep == 0 else again
+        again = wb.tile(wb.B) if rep == 0 else again
         again.poses[:] = start
         s.solve(again)
         if rep:   # (the first round allocates)
@@ -79,9 +71,9 @@ def main():
         F.add_chain_poses(small, i, ch, 0, T)
         for k in range(T):
             small.add_prior(i, k, ch.est[k], np.eye(3), np.array([25.0, 25.0, 25.0, 0, 0, 0]))
-    base = _tile(la, small, B)
+    base = small.tile(B)
     s = la.WindowSolver(F.ANCH, B, *base.caps, jacobian=args.jacobian, bw_max=1, chain_threshold=0)
-    work = _tile(la, base, B)
+    work = base.tile(B)
     table = np.zeros((B, T, 36))
     table[:, :, ::7] = base.p_val[:, :, 12:]
     ms = {False: [], True: []}

@@ -36,7 +36,9 @@ DISTINCT = 256
 RANGE, IMU, LIDAR, TWIST = 1, 2, 4, 8
 SHAPES = {"uwb_only": dict(T=10, se3=0, priors=1, chain3=True, kind=RANGE), "uwb_imu": dict(T=12, se3=0, priors=1, chain3=False, kind=RANGE | IMU),
           "uwb_twist": dict(T=15, se3=1, priors=0, chain3=False, kind=TWIST)}
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+from localization_amd.window import WindowBatch
+
+TABLES = WindowBatch.TABLES
 VMAX, OUTLIER = 5.0, 1.0
 
 

@@ -48,14 +48,6 @@ def _base_batch(la, P, name):
     return wb
 
 
-def _tile(la, wb, B):
-    out = la.WindowBatch(B, *wb.caps)
-    pick = np.arange(B) % wb.B
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)[pick]
-    return out
-
-
 def _messages(M, name, base, K, B):
     """K cycles of one message per window (uwb_only: RANGE; uwb_twist: RANGE, TWIST alternating), made for the 64 windows and tiled"""
     f = SHAPES[name]
@@ -124,7 +116,7 @@ def main():
         T = SHAPES[name]["T"]
         base = _base_batch(la, P, name)
         for B in (int(x) for x in args.sizes.split(",")):
-            wb = _tile(la, base, B)
+            wb = base.tile(B)
             s = la.WindowSolver(P.ANCH, B, *wb.caps, jacobian="numeric")
             s.set_option("resident_slide", 1)
             s.set_message_config(T, 5.0, 1.0, M.ANTENNA)

@@ -49,7 +49,7 @@ def main():
     import _fixed_lag as F
     base, after, _ = H._after_one_slide(la, F)
     for B in (int(x) for x in args.batches.split(",")):
-        wb, template = H._tile(la, base, B), H._tile(la, after, B)
+        wb, template = base.tile(B), after.tile(B)
         pose, ranges = _new_rows(template)
         r = la.WindowSolver(F.ANCH, B, *wb.caps, jacobian="numeric")
         h = la.WindowSolver(F.ANCH, B, *wb.caps, jacobian="numeric")
@@ -75,7 +75,7 @@ def main():
             r.download(out)
             t4 = time.perf_counter()
             kinds["resident"] = r.last_kernel_kind()
-            g = H._tile(la, base, B)
+            g = base.tile(B)
             u0 = time.perf_counter()
             h.solve(g)
             m = h.marginal_prior(g, 0)

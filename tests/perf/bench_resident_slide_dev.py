@@ -40,7 +40,7 @@ def main():
     base, after, _ = H._after_one_slide(la, F)
     dev = torch.device("cuda", 0)
     for B in (int(x) for x in args.batches.split(",")):
-        wb, template = H._tile(la, base, B), H._tile(la, after, B)
+        wb, template = base.tile(B), after.tile(B)
         pose, ranges = R._new_rows(template)
         d = la.WindowSolver(F.ANCH, B, *wb.caps, jacobian="numeric")
         h = la.WindowSolver(F.ANCH, B, *wb.caps, jacobian="numeric")

@@ -30,7 +30,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 DISTINCT = 256
 SHAPES = {"uwb_imu": dict(T=12, se3=0, priors=1), "uwb_twist": dict(T=15, se3=1, priors=0)}
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+from localization_amd.window import WindowBatch
+
+TABLES = WindowBatch.TABLES
 
 
 def _stats(xs):

@@ -32,7 +32,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 DISTINCT = 256
 SHAPES = {"uwb_only": dict(T=10, se3=0, priors=1, chain3=True), "uwb_twist": dict(T=15, se3=1, priors=0, chain3=False)}
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+from localization_amd.window import WindowBatch
+
+TABLES = WindowBatch.TABLES
 
 
 def _stats(xs):

@@ -31,7 +31,9 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+from localization_amd.window import WindowBatch
+
+TABLES = WindowBatch.TABLES
 
 
 def batch_of(shape, B):
@@ -43,10 +45,7 @@ def batch_of(shape, B):
         wb, _, anchors, _ = W.build_pose64(B, rng, n_graphs=0)
         return wb, anchors
     small, _, anchors, _ = W.build_selfcal(4, rng)
-    wb = la.WindowBatch(B, *small.caps)
-    for name in TABLES:
-        a = getattr(small, name)
-        getattr(wb, name)[:] = np.tile(a, (B // 4 + 1,) + (1,) * (a.ndim - 1))[:B]
+    wb = small.tile(B)
     wb.poses[:, :, 9:] += rng.normal(0.0, 0.02, wb.poses[:, :, 9:].shape)
     return wb, np.zeros((1, 3))
 

@@ -198,23 +198,20 @@ def main():
     import localization_amd as la
     global POSES_OVERRIDE
     POSES_OVERRIDE = a.poses or None
-    names = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
     if a.cache and os.path.exists(a.cache):
         z = np.load(a.cache)
         wb = la.WindowBatch(a.batch, *[int(v) for v in z["caps"]])
-        for nm in names: getattr(wb, nm)[:] = z[nm]
+        for nm in wb.TABLES: getattr(wb, nm)[:] = z[nm]
         graphs, anchors, T = [], z["anchors"], int(z["T"])
         a.cpu_n = 0
     else:
         if a.tile and a.tile < a.batch:
             small, graphs, anchors, T = build(a.tile, a.shape)
-            wb = la.WindowBatch(a.batch, *small.caps)
-            for nm in names:
-                src = getattr(small, nm); getattr(wb, nm)[:] = np.resize(src, (a.batch,) + src.shape[1:])
+            wb = small.tile(a.batch)
         else:
             wb, graphs, anchors, T = build(a.batch, a.shape)
         if a.cache:
-            np.savez(a.cache, caps=np.array(wb.caps), anchors=anchors, T=T, **{nm: getattr(wb, nm) for nm in names})
+            np.savez(a.cache, caps=np.array(wb.caps), anchors=anchors, T=T, **{nm: getattr(wb, nm) for nm in wb.TABLES})
     if a.bw == "auto":
         bw = 0
         for b in range(a.batch):
@@ -233,9 +230,7 @@ def main():
         t0 = time.perf_counter(); solver.solve(wb); wall = time.perf_counter() - t0
         if r: ms.append((solver.last_kernel_ms(), wall * 1e3))
     k_ms = float(np.median([m[0] for m in ms])); w_ms = float(np.median([m[1] for m in ms]))
-    one = la.WindowBatch(1, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(one, name)[:] = getattr(wb, name)[:1] if name != "poses" else poses0[:1]
+    one = wb.take([0]); one.poses[:] = poses0[:1]
     s1 = la.WindowSolver(anchors, 1, *wb.caps, maximum_iteration=10, bw_max=bw, jacobian=a.jacobian, natural_order=a.natural)
     lat = [float("nan")] if a.no_latency else []
     for r in range(0 if a.no_latency else 20):

@@ -54,7 +54,7 @@ def test_helper_agrees_with_the_closed_form_and_the_oracles_chi2(built):
 
 # ---- (c) the prune inputs, by the reference alone -------------------------------------------------------------------------------------------------------
 def _oracle_solved(la, wb, anchors, iterations=10, poses=None):
-    out = R.copy_batch(la, wb)
+    out = wb.copy()
     if poses is not None:
         out.poses[:] = poses
     for i in range(wb.B):
@@ -89,7 +89,7 @@ def what_the_rule_buys(la, B=8, iterations=F.PROPERTY_ITERATIONS):
         ch = F.Chain(9900 + i, K.PRUNE_T, 4)
         clean = la.WindowBatch(1, *F.window_caps(K.PRUNE_T))
         F.add_chain_poses(clean, 0, ch, 0, K.PRUNE_T, doubled=(1,))
-        dirty = R.copy_batch(la, clean)
+        dirty = clean.copy()
         anchor_rows = [e for e in range(int(clean.counts[0, 1])) if clean.r_idx[0, e, 1] < 0]
         picks = [anchor_rows[(5 + 7 * i) % 40], anchor_rows[-1 - (i % 3)]] + ([anchor_rows[11]] if i % 2 else [])
         for e in picks:

@@ -49,7 +49,7 @@ def test_plan_takes_the_largest_window_and_refuses_bad_tables(built):
     assert blocks == max(per_window) == G.MIXED_NV[2] * (G.MIXED_NV[2] + 1) // 2   # the key-first star
     assert per_window[1] == 2 * G.MIXED_NV[1] - 1
     assert nbytes == wb.B * ((blocks + 24) * 36 + 24 * 6) * 8
-    bad = G.copy_batch(la, wb)
+    bad = wb.copy()
     bad.s_idx[1, 0, 1] = 24
     with pytest.raises(la.LocalizationAmdError) as ex:
         covariance_plan(bad)

@@ -17,13 +17,6 @@ pytestmark = pytest.mark.gpu
 FIXED = np.array([[4.0, -4.0, 0.5], [-4.0, 4.0, 2.5]])   # two surveyed anchors next to the unknown ones
 
 
-def _copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
-
-
 def _arrow_batch(la, rng, B, T, A, rich):
     """Hypotheses in build_selfcal's slot order (tag poses first, unknown anchors last).  rich: ragged trajectory lengths and border
     sizes, a missing smoothness link, doubled (pose, anchor) ranges, ranges to surveyed anchors, ranges between unknown anchors,
@@ -87,7 +80,7 @@ def test_arrow3_kernel_matches_6dof_oracle_and_general_kernel(gpu, T, A, rich, j
     rng = np.random.default_rng(100 * T + A + len(jac))
     wb = _arrow_batch(la, rng, B, T, A, rich)
     before = wb.poses.copy()
-    ref = _copy_batch(la, wb)
+    ref = wb.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     want = [oracle_solve_instance(wb, i, FIXED, jac_mode=mode) for i in range(B)]
     g = la.WindowSolver(FIXED, B, *wb.caps, jacobian=jac)
@@ -100,7 +93,7 @@ def test_arrow3_kernel_matches_6dof_oracle_and_general_kernel(gpu, T, A, rich, j
     res = s.solve(wb).copy()
     assert s.last_kernel_kind() == "arrow3_lm_kernel"
     # resident path: the same bits
-    wb2 = _copy_batch(la, wb); wb2.poses[:] = before
+    wb2 = wb.copy(); wb2.poses[:] = before
     s.upload(wb2); s.solve_resident(); s.download(wb2)
     assert s.last_kernel_kind() == "arrow3_lm_kernel"
     s.close()
@@ -134,7 +127,7 @@ def test_arrow3_is_taken_by_large_translation_only_arrowheads_only(gpu):
     s = la.WindowSolver(FIXED, 2, *big.caps, jacobian="analytic")
 
     def kind(mut):
-        wb = _copy_batch(la, big)
+        wb = big.copy()
         mut(wb)
         s.solve(wb)
         return s.last_kernel_kind()
@@ -166,9 +159,7 @@ def test_cfg4_full_batch_properties(gpu):
     import bench_window as bw
     B, nd = 1024, 32
     small, graphs, anchors, nv = bw.build_selfcal(nd, np.random.default_rng(21))
-    wb = la.WindowBatch(B, *small.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(small, name); getattr(wb, name)[:] = np.resize(src, (B,) + src.shape[1:])
+    wb = small.tile(B)
     poses0 = wb.poses.copy()
     s = la.WindowSolver(anchors, B, *wb.caps, maximum_iteration=10, bw_max=nv - 1, jacobian="analytic")
     res = s.solve(wb).copy()

@@ -15,7 +15,7 @@ import pytest
 from test_gpu_arrow3_parity import FIXED
 from test_gpu_covariance import TOL
 from test_gpu_snapshot_covariance import KAPPA_EPS
-from _arrow_cov_inputs import CASES, SURVEYED, arrow_cov_batch, case_batch, copy_batch, cut_gauge, min_relative_pivot
+from _arrow_cov_inputs import CASES, SURVEYED, arrow_cov_batch, case_batch, cut_gauge, min_relative_pivot
 from _covariance_ref import hessian, reference_covariance
 
 pytestmark = pytest.mark.gpu
@@ -109,7 +109,7 @@ def test_singular_window_is_isolated(gpu):
     s.solve(wb)
     cov0, mask0, st0 = s.covariance(wb)
     assert (st0 == 0).all()
-    bad = copy_batch(la, wb)
+    bad = wb.copy()
     i = 2
     cut_gauge(bad, i)
     assert min_relative_pivot(hessian(bad, i, SURVEYED, O.JAC_NUMERIC_G2O)) < 1e-12
@@ -155,7 +155,7 @@ def test_coverage_rule(gpu):
     def second_link(wb): wb.add_range(0, 10, 11, 0.01, 50.0)           # two edges on one consecutive chain pair
     def long_link(wb): wb.add_range(0, 10, 40, 1.0, 50.0)              # a loop closure inside the chain: the border would be 34 poses
     for mut in (lever, turned, second_link, long_link):
-        wb = copy_batch(la, big)
+        wb = big.copy()
         mut(wb)
         _untouched(la, s, wb)
     s.set_option("arrow3", 0)
@@ -221,7 +221,7 @@ def test_solves_are_unaffected(gpu):
     B, T = wb.B, wb.caps[0]
     other = arrow_cov_batch(la, np.random.default_rng(9600), B, 24, 4, False)
     a, b = _solver(la, wb, "numeric"), _solver(la, wb, "numeric")
-    wa, wc = copy_batch(la, wb), copy_batch(la, wb)
+    wa, wc = wb.copy(), wb.copy()
     for rep in range(3):
         ra = a.solve(wa).copy()
         a.covariance(wa)
@@ -231,7 +231,7 @@ def test_solves_are_unaffected(gpu):
         assert np.array_equal(wa.poses, wc.poses) and np.array_equal(ra, rb)
         assert a.last_kernel_kind() == b.last_kernel_kind() == KERNEL
         wa.poses[:, :, 9:] += 0.01; wc.poses[:, :, 9:] += 0.01
-    wa, wc = copy_batch(la, wb), copy_batch(la, wb)
+    wa, wc = wb.copy(), wb.copy()
     a.upload(wa); b.upload(wc)
     out = (torch.zeros((B, T, 36), dtype=torch.float64, device=gpu), torch.zeros((B, T), dtype=torch.int32, device=gpu), torch.zeros((B,), dtype=torch.int32, device=gpu))
     for rep in range(2):

@@ -19,13 +19,6 @@ pytestmark = pytest.mark.gpu
 ANCH = np.array([[3, -3, 0.58], [3, 3, 1.97], [-3, 3, 0.54], [-3, -3, 1.76]], dtype=float)
 
 
-def _copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
-
-
 def _translation_only_batch(la, rng, B, T, with_z_prior):
     """Windows in addRangeEdge's creation order, identity rotations, no lever arm; ragged lengths, missing links, doubled pairs."""
     nr_max, np_max = max(2 * T + 2, 4), (T if with_z_prior else 0)
@@ -68,7 +61,7 @@ def test_chain3_kernel_matches_6dof_oracle_and_6dof_kernels(gpu, T, jac, with_z_
     before = wb.poses.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     want = [oracle_solve_instance(wb, i, ANCH, jac_mode=mode) for i in range(B)]
-    wave, six = _copy_batch(la, wb), _copy_batch(la, wb)
+    wave, six = wb.copy(), wb.copy()
     general = la.WindowSolver(ANCH, B, *wb.caps, jacobian=jac, chain_threshold=0)
     res_general = general.solve(wave).copy()
     assert general.last_kernel_kind() == "window_lm_kernel"
@@ -100,7 +93,7 @@ def test_chain3_kernel_matches_6dof_oracle_and_6dof_kernels(gpu, T, jac, with_z_
         assert (res[:, 4] != res6[:, 4]).mean() < 0.03 and (res[:, 3] == res6[:, 3]).all()
         assert (res[:, 4] != res_general[:, 4]).mean() < 0.05
     # resident API: the same answer again, and the threshold is looked at per solve
-    wb2 = _copy_batch(la, wb); wb2.poses[:] = before
+    wb2 = wb.copy(); wb2.poses[:] = before
     chain.upload(wb2)
     with pytest.raises(la.LocalizationAmdError):
         chain.download(wb2)                      # nothing solved since the upload
@@ -128,7 +121,7 @@ def test_chain3_is_taken_only_by_translation_only_batches(gpu):
     s = la.WindowSolver(ANCH, B, *base.caps, jacobian="analytic", chain_threshold=1)
 
     def kind(mut):
-        wb = _copy_batch(la, base)
+        wb = base.copy()
         mut(wb)
         s.solve(wb)
         return s.last_kernel_kind()
@@ -158,10 +151,7 @@ def test_lane_per_window_kernels_at_the_batch_size_that_selects_them(gpu, kernel
     import bench_window as bw
     B, n_distinct = 12288, 2048
     small, graphs, anchors, T = bw.build(n_distinct, "uwb_only", seed=99)
-    wb = la.WindowBatch(B, *small.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        src = getattr(small, name)
-        getattr(wb, name)[:] = np.resize(src, (B,) + src.shape[1:])
+    wb = small.tile(B)
     poses0 = wb.poses.copy()
     out = {}
     for jac in ("analytic", "numeric"):

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from test_gpu_chain3_parity import _translation_only_batch
-from test_gpu_wave6_parity import _chain_batch, _copy_batch
+from test_gpu_wave6_parity import _chain_batch
 from test_gpu_window_parity import ANCH, _random_window
 from _covariance_ref import reference_covariance
 
@@ -165,7 +165,7 @@ def test_singular_window_is_isolated(gpu):
     s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="numeric")
     s.solve(wb)
     cov0, mask0, st0 = s.covariance(wb)
-    bad = _copy_batch(la, wb)
+    bad = wb.copy()
     i = 4
     bad.counts[i] = (1, 1, 0, 0)
     bad.r_idx[i, 0] = (0, -1 - 1); bad.r_val[i, 0] = (3.0, 100.0, 0.1, 0.0, -0.05)
@@ -284,7 +284,7 @@ def test_solves_are_unaffected(gpu, kind):
     else:
         wb = _twist_batch(la, rng, B, T, True)
     a, b = la.WindowSolver(ANCH, B, *wb.caps), la.WindowSolver(ANCH, B, *wb.caps)
-    wa, wb2 = _copy_batch(la, wb), _copy_batch(la, wb)
+    wa, wb2 = wb.copy(), wb.copy()
     for rep in range(3):
         ra = a.solve(wa).copy()
         a.covariance(wa)
@@ -303,10 +303,9 @@ def test_covariance_leaves_the_handles_endpoint1_lever_arms_alone(gpu):
     wb = _translation_only_batch(la, rng, B, T, False)
     wb.r_off1 = np.zeros((B, wb.caps[1], 3)); wb.r_off1[:, :, 2] = 0.2
     a, b = la.WindowSolver(ANCH, B, *wb.caps), la.WindowSolver(ANCH, B, *wb.caps)
-    wa, wc = _copy_batch(la, wb), _copy_batch(la, wb)
-    wa.r_off1 = wb.r_off1.copy(); wc.r_off1 = wb.r_off1.copy()
+    wa, wc = wb.copy(), wb.copy()
     a.upload(wa); b.upload(wc)
-    plain = _copy_batch(la, wb)   # the same windows without lever arms on endpoint 1
+    plain = wb.copy(); plain.r_off1 = None   # the same windows without lever arms on endpoint 1: the call reaches the library
     with pytest.raises(la.LocalizationAmdError) as ex:
         a.covariance(plain)
     assert ex.value.code == LOC_ERR_UNSUPPORTED

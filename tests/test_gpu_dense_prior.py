@@ -82,12 +82,6 @@ CASES = {
 }
 
 
-def _copy(la, wb):
-    out = G.copy_batch(la, wb)
-    out.p_info = None if wb.p_info is None else wb.p_info.copy()
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(name, jac):
     """the oracle's poses and chi2 of a case (shared, never modified)"""
@@ -144,10 +138,10 @@ def test_kernel_choice_diagonal_table_and_back(gpu):
     import localization_amd as la
     base = G.chain_batch(la, 9410, 8, 12, True, ragged=False)
     s = la.WindowSolver(ANCH, base.B, *base.caps, jacobian="analytic")
-    first = _copy(la, base)
+    first = base.copy()
     s.solve(first)
     assert s.last_kernel_kind() == "wave6_lm_kernel"
-    diag = _copy(la, base)
+    diag = base.copy()
     diag.p_info = np.zeros((base.B, base.caps[2], 36))
     diag.p_info[:, :, ::7] = base.p_val[:, :, 12:]
     s.solve(diag)
@@ -155,7 +149,7 @@ def test_kernel_choice_diagonal_table_and_back(gpu):
     d = np.abs(diag.poses - first.poses).max()
     print(f"diag(p_val) as a table against the diagonals: {d:.3e}")
     assert d < 1e-9
-    again = _copy(la, base)
+    again = base.copy()
     s.solve(again)   # (p_info None: the harness passes NULL)
     assert s.last_kernel_kind() == "wave6_lm_kernel"
     assert np.array_equal(again.poses, first.poses) and np.array_equal(again.result, first.result)
@@ -165,7 +159,7 @@ def test_kernel_choice_diagonal_table_and_back(gpu):
 def test_resident_solve_reads_the_table(gpu):
     import localization_amd as la
     wb = CASES["chain12"](la)
-    host = _copy(la, wb)
+    host = wb.copy()
     s = la.WindowSolver(ANCH, wb.B, *wb.caps, jacobian="analytic")
     s.solve(host)
     s.upload(wb)
@@ -180,7 +174,7 @@ def test_refusals_change_nothing(gpu):
     import localization_amd as la
     wb = CASES["chain12"](la)
     s = la.WindowSolver(ANCH, wb.B, *wb.caps, jacobian="analytic")
-    good = _copy(la, wb)
+    good = wb.copy()
     s.solve(good)
     dp = C.POINTER(C.c_double)
     bad = wb.p_info.copy()
@@ -191,7 +185,7 @@ def test_refusals_change_nothing(gpu):
     assert s.L.loc_window_set_prior_information(s.h, wb.B, nan.ctypes.data_as(dp)) == LOC_ERR_INVALID
     # the handle still holds the table of the last good call: the same bits
     ip = C.POINTER(C.c_int32)
-    again = _copy(la, wb)
+    again = wb.copy()
     la._lib.check(s.L.loc_window_solve_host(s.h, again.B, again.counts.ctypes.data_as(ip), again.poses.ctypes.data_as(dp), again.r_idx.ctypes.data_as(ip),
                                             again.r_val.ctypes.data_as(dp), again.p_idx.ctypes.data_as(ip), again.p_val.ctypes.data_as(dp),
                                             again.s_idx.ctypes.data_as(ip), again.s_val.ctypes.data_as(dp), again.result.ctypes.data_as(dp)))
@@ -259,7 +253,7 @@ def test_covariance_needs_the_general_option_and_joint_calls_follow(gpu):
     from localization_amd._lib import LocalizationAmdError
     from oracle import oracle as O
     wb, (cov, mask, status) = _solved("chain12", "analytic")
-    wb = _copy(la, wb)
+    wb = wb.copy()
     s = la.WindowSolver(ANCH, wb.B, *wb.caps, jacobian="analytic")
     out = (np.full((wb.B, wb.caps[0], 6, 6), 7.0), np.full((wb.B, wb.caps[0]), 7, dtype=np.int32), np.full(wb.B, 7, dtype=np.int32))
     with pytest.raises(LocalizationAmdError) as e:   # a chain batch of twelve poses: covariance_kernel<6>'s — but that pass reads the diagonals
@@ -292,7 +286,7 @@ def test_covariance_needs_the_general_option_and_joint_calls_follow(gpu):
     torch.cuda.synchronize()
     res = la.WindowBatch(wb.B, *wb.caps)
     s.download(res)
-    host = _copy(la, wb); host.poses[:] = res.poses
+    host = wb.copy(); host.poses[:] = res.poses
     want = s.covariance(host)
     assert np.array_equal(tc.cpu().numpy().reshape(want[0].shape), want[0]) and not ts.cpu().numpy().any()
     s.close()

@@ -80,7 +80,7 @@ def _solved(la, s, wb):
     """upload, one resident solve, the batch at the solved poses"""
     s.upload(wb)
     s.solve_resident()
-    out = R.copy_batch(la, wb)
+    out = wb.copy()
     s.download(out)
     return out
 
@@ -135,7 +135,7 @@ def test_host_resident_jacobian_mode_and_position_give_the_same_bits(gpu, name):
 
 # ---- 3. the removal -------------------------------------------------------------------------------------------------------------------------------------
 def _table_bytes(wb):
-    return {n: getattr(wb, n).tobytes() for n in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")}
+    return {n: getattr(wb, n).tobytes() for n in wb.TABLES}
 
 
 def _prune_run(la, jac, general):
@@ -167,7 +167,7 @@ def test_prune_flags_tables_and_a_second_prune(gpu, general):
     after = s.download_batch()
     want = R.with_rows_zeroed(la, wb, removed)
     assert _table_bytes(after) == _table_bytes(want)
-    x = R.copy_batch(la, wb); s.download(x)
+    x = wb.copy(); s.download(x)
     assert x.poses.tobytes() == at.poses.tobytes()
     # a second prune without a solve in between removes nothing
     out = _prune_outs(wb.B, wb.caps)
@@ -191,7 +191,7 @@ def test_solve_after_the_prune(gpu, jac, general):
     s, wb, at, planted, active, (removed, n_removed), got = _prune_run(la, jac, general)
     assert np.array_equal(got[0], removed)
     s.solve_resident()
-    mine = R.copy_batch(la, wb); s.download(mine)
+    mine = wb.copy(); s.download(mine)
     zeroed = R.with_rows_zeroed(la, wb, removed)
     f = _solver(la, wb, F.ANCH, {"chain_min_batch": 0} if general else {}, jac)
     fresh = _solved(la, f, zeroed)
@@ -233,7 +233,7 @@ def test_prune_then_covariance_and_slide_on_a_resident_slide_handle(gpu):
     removed, n_removed = _fetch(out)
     assert (n_removed >= 1).all()
     r.solve_resident()
-    mine = R.copy_batch(la, wb); r.download(mine)
+    mine = wb.copy(); r.download(mine)
     other = _solved(la, z, R.with_rows_zeroed(la, wb, removed))
     used = np.arange(wb.caps[0])[None, :] < wb.counts[:, :1]
     assert mine.poses[used].tobytes() == other.poses[used].tobytes()
@@ -255,7 +255,7 @@ def test_prune_then_covariance_and_slide_on_a_resident_slide_handle(gpu):
     ends = []
     for h in handles:
         h.solve_resident()
-        x = R.copy_batch(la, slid[0]); h.download(x)
+        x = slid[0].copy(); h.download(x)
         ends.append(x)
     u = np.arange(wb.caps[0])[None, :] < slid[0].counts[:, :1]
     assert ends[0].poses[u].tobytes() == ends[1].poses[u].tobytes()
@@ -325,14 +325,14 @@ def test_refusals_launch_and_write_nothing(gpu):
     _refused(LOC_ERR_INVALID, lambda: s.prune_resident(2.0, 10, *p_out))
     untouched()
     s.solve_resident()
-    first = R.copy_batch(la, wb); s.download(first)
+    first = wb.copy(); s.download(first)
     tables = _table_bytes(s.download_batch())
     for chi2_max, min_edges in ((float("nan"), 10), (-1.0, 10), (2.0, -1)):
         _refused(LOC_ERR_INVALID, lambda: s.prune_resident(chi2_max, min_edges, *p_out))
     untouched()
     assert _table_bytes(s.download_batch()) == tables
     s.solve_resident()
-    second = R.copy_batch(la, wb); s.download(second)
+    second = wb.copy(); s.download(second)
     assert second.poses.tobytes() == first.poses.tobytes() and second.result.tobytes() == first.result.tobytes()
     s.close()
 
@@ -351,6 +351,6 @@ def test_prune_refuses_the_arrowhead_batch(gpu):
         assert (t == 7).all()
     assert _table_bytes(s.download_batch()) == tables
     s.solve_resident()
-    second = R.copy_batch(la, wb); s.download(second)
+    second = wb.copy(); s.download(second)
     assert second.poses.tobytes() == first.poses.tobytes() and second.result.tobytes() == first.result.tobytes()
     s.close()

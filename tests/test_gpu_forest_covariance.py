@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation
 
-from test_gpu_tree_parity import ANCH, _copy_batch, _forest_batch, _rel
+from test_gpu_tree_parity import ANCH, _forest_batch, _rel
 from _covariance_ref import hessian, reference_covariance
 
 pytestmark = pytest.mark.gpu
@@ -223,7 +223,7 @@ def test_singular_window_is_isolated(gpu):
     s.solve(wb)
     cov0, mask0, st0 = s.covariance(wb)
     assert (st0 == 0).all()
-    bad = _copy_batch(la, wb)
+    bad = wb.copy()
     i = 4
     bad.r_val[i, :, 1] = 0.0
     cov, mask, st = s.covariance(bad)
@@ -283,7 +283,7 @@ def test_solves_are_unaffected(gpu):
     other = _forest_batch(la, np.random.default_rng(8501), B, T, 6, False)
     a = la.WindowSolver(ANCH, B, *wb.caps, bw_max=T - 1, chain_threshold=1)
     b = la.WindowSolver(ANCH, B, *wb.caps, bw_max=T - 1, chain_threshold=1)
-    wa, wc = _copy_batch(la, wb), _copy_batch(la, wb)
+    wa, wc = wb.copy(), wb.copy()
     for rep in range(3):
         ra = a.solve(wa).copy()
         a.covariance(wa)
@@ -292,7 +292,7 @@ def test_solves_are_unaffected(gpu):
         assert np.array_equal(wa.poses, wc.poses) and np.array_equal(ra, rb)
         assert a.last_kernel_kind() == b.last_kernel_kind() == "tree_wave_kernel"
         wa.poses[:, :, 9:] += 0.01; wc.poses[:, :, 9:] += 0.01
-    wa, wc = _copy_batch(la, wb), _copy_batch(la, wb)
+    wa, wc = wb.copy(), wb.copy()
     a.upload(wa); b.upload(wc)
     out = (torch.zeros((B, T, 36), dtype=torch.float64, device=gpu), torch.zeros((B, T), dtype=torch.int32, device=gpu), torch.zeros((B,), dtype=torch.int32, device=gpu))
     for rep in range(2):
@@ -330,7 +330,7 @@ def test_coverage_rule(gpu):
     s.set_option("tree", 0)
     untouched(s, wb)                                   # the forest kernels switched off
     s.set_option("tree", -1)
-    odd = _copy_batch(la, wb)
+    odd = wb.copy()
     odd.r_idx[1, 3, 1] = -1 - 2                        # one window ranges another anchor: not ONE topology
     untouched(s, odd)
     s.close()

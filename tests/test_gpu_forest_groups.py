@@ -46,14 +46,14 @@ def test_bits_of_tree_wave_kernel_on_each_group(gpu, jac):
     assert n == G and nbytes > 0
     # tree_wave_kernel takes a group's windows only with equal anchor numbers and flags: the mixed batch rebuilt with those
     mixed = FC.mixed_batch(la, topos, OF, 11, vary=False)
-    got = FC.copy_batch(la, mixed)
+    got = mixed.copy()
     res = s.solve(got).copy()
     assert s.last_kernel_kind() == GROUPS and s.forest_groups()[0] == G
     s.close()
     u = _solver(la, jac, groups=0)
     for g in range(G):
         rows = [b for b in range(B) if OF[b] == g]
-        own = FC.copy_batch(la, mixed, rows)
+        own = mixed.take(rows)
         want = u.solve(own).copy()
         assert u.last_kernel_kind() == "tree_wave_kernel" and u.forest_groups() == (0, 0)
         # poses and all eight result columns of every window, bit for bit — result[7] with the window's own nlev, nv and nroots
@@ -106,8 +106,7 @@ def test_the_option_leaves_everything_else_alone(gpu):
 
     def both(wb, kind, **options):
         """wb on both handles under the same further options: the kernel that ran on each, and the bits"""
-        a, b = FC.copy_batch(la, wb), FC.copy_batch(la, wb)
-        a.p_info = b.p_info = getattr(wb, "p_info", None)
+        a, b = wb.copy(), wb.copy()
         for s in (on, off):
             for k, v in options.items():
                 s.set_option(k, v)
@@ -117,21 +116,21 @@ def test_the_option_leaves_everything_else_alone(gpu):
         assert _same(a, b)
 
     # option off: the mixed batch is the general kernel's
-    x = FC.copy_batch(la, mixed)
+    x = mixed.copy()
     off.solve(x)
     assert off.last_kernel_kind() == "window_lm_kernel" and off.forest_groups() == (0, 0)
     # a one-topology batch keeps today's path, kernel and bits
     both(FC.mixed_batch(la, topos, [2] * B, 14, vary=False), "tree_wave_kernel")
     # one window of the batch refuses all of it
-    cyc = FC.copy_batch(la, mixed)
+    cyc = mixed.copy()
     cyc.add_range(7, 20, 33, 1.0, 10.0)                                       # window 7 (T = 40): a loop closure between two poses of one tree
     both(cyc, "window_lm_kernel")
-    dbl = FC.copy_batch(la, mixed)
+    dbl = mixed.copy()
     vi, vj = (int(v) for v in dbl.s_idx[10, 5, :2])                           # window 10 (T = 64): a second EdgeSE3 on a pair that has one
     dbl.add_se3(10, vi, vj, np.zeros(3), np.eye(3), np.eye(6) * 2e3, True)
     both(dbl, "window_lm_kernel")
     # a table of full information matrices on the handle
-    pin = FC.copy_batch(la, mixed)
+    pin = mixed.copy()
     pin.p_info = np.zeros((B, CAPS[2], 36))
     pin.p_info[:, :, ::7] = pin.p_val[:, :, 12:]
     both(pin, "window_lm_kernel")
@@ -141,7 +140,7 @@ def test_the_option_leaves_everything_else_alone(gpu):
     for s in (on, off):
         s.set_option("chain_min_batch", 1)
     # the grouped path again, then the covariances of the mixed batch: served as without the option, by the envelope pass
-    y = FC.copy_batch(la, mixed)
+    y = mixed.copy()
     on.solve(y)
     assert on.last_kernel_kind() == GROUPS and on.forest_groups()[0] == G
     assert np.abs(y.poses - x.poses).max() < 1e-7                             # (and the general kernel's answer, at the kernels' tolerance)
@@ -157,15 +156,15 @@ def test_resident_path_and_topology_cache(gpu):
     topos = FC.five_topologies()
     mixed = FC.mixed_batch(la, topos, OF, 15)
     s = _solver(la, "analytic")
-    host = FC.copy_batch(la, mixed)
+    host = mixed.copy()
     res = s.solve(host).copy()
     assert s.last_kernel_kind() == GROUPS and not s.last_host_timing()[3]
     # the same structure again: the verdict, the groups and the tables come from the cache
-    again = FC.copy_batch(la, mixed)
+    again = mixed.copy()
     s.solve(again)
     assert s.last_kernel_kind() == GROUPS and s.last_host_timing()[3] and s.forest_groups()[0] == G and _same(again, host)
     # resident: the host path's bits
-    r = FC.copy_batch(la, mixed)
+    r = mixed.copy()
     s.upload(r)
     assert s.forest_groups()[0] == G
     s.solve_resident(); s.download(r)
@@ -196,7 +195,7 @@ def test_every_window_its_own_topology_and_one_topology_with_other_anchors(gpu):
     g = _solver(la, "analytic", groups=0)
     s = _solver(la, "analytic")
     for batch, n_groups in ((wb, B), (one, 1)):
-        ref, got = FC.copy_batch(la, batch), FC.copy_batch(la, batch)
+        ref, got = batch.copy(), batch.copy()
         g.solve(ref)
         res = s.solve(got)
         assert g.last_kernel_kind() == "window_lm_kernel" and s.last_kernel_kind() == GROUPS and s.forest_groups()[0] == n_groups

@@ -143,7 +143,7 @@ def test_structured_batches_keep_their_kernels(gpu):
             s = la.WindowSolver(anchors, wb.B, *wb.caps, jacobian="numeric", **kw)
             setup(s)
             s.set_option("covariance_general", general)
-            w2 = G.copy_batch(la, wb)
+            w2 = wb.copy()
             s.solve(w2)
             res.append(s.covariance(w2))
             s.close()
@@ -162,7 +162,7 @@ def test_singular_window_is_isolated(gpu):
     import localization_amd as la
     from oracle import oracle as O
     wb, (cov0, mask0, st0) = _solved("mixed", "numeric")
-    bad = G.copy_batch(la, wb)
+    bad = wb.copy()
     i = G.MIXED_STAR
     bad.counts[i, 1] = 0
     assert G.min_relative_pivot(hessian(bad, i, ANCH, O.JAC_NUMERIC_G2O)) < 1e-12
@@ -185,7 +185,7 @@ def test_resident_matches_host_bit_for_bit(gpu, name):
     wb = G.case_batch(la, name)
     B, T = wb.B, wb.caps[0]
     a, b = _solver(la, wb, "numeric"), la.WindowSolver(ANCH, B, *wb.caps, jacobian="numeric")
-    wa, wc = G.copy_batch(la, wb), G.copy_batch(la, wb)
+    wa, wc = wb.copy(), wb.copy()
     a.upload(wa); b.upload(wc)
     a.solve_resident(); b.solve_resident()
 
@@ -213,8 +213,8 @@ def test_resident_matches_host_bit_for_bit(gpu, name):
     for c, m, t in outs:
         assert np.array_equal(c.cpu().numpy(), cov) and np.array_equal(m.cpu().numpy(), mask) and np.array_equal(t.cpu().numpy(), st)
     # interleaved host-path calls leave the host solve alone as well
-    w1, w2 = G.copy_batch(la, wb), G.copy_batch(la, wb)
-    r1 = a.solve(w1).copy(); a.covariance(w1); r1b = a.solve(G.copy_batch(la, wb)).copy()
+    w1, w2 = wb.copy(), wb.copy()
+    r1 = a.solve(w1).copy(); a.covariance(w1); r1b = a.solve(wb.copy()).copy()
     r2 = b.solve(w2).copy()
     assert _same_poses(w1, w2) and np.array_equal(r1, r2) and np.array_equal(r1b, r2)
     a.close(); b.close()

@@ -36,10 +36,7 @@ def _head(la, wb, n):
     """the first n windows of a batch"""
     if wb.B <= n:
         return wb
-    out = la.WindowBatch(n, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)[:n]
-    return out
+    return wb.take(np.arange(n))
 
 
 def _tables(wb, per_window, npm=None):
@@ -330,24 +327,24 @@ def _singular_case(la, pass_):
         from test_gpu_covariance import _observable_batch
         from test_gpu_window_parity import ANCH
         wb = _observable_batch(la, np.random.default_rng(11), 8, 12, True, True)
-        bad, i = G.copy_batch(la, wb), 4
+        bad, i = wb.copy(), 4
         bad.counts[i] = (1, 1, 0, 0)
         bad.r_idx[i, 0] = (0, -1 - 1); bad.r_val[i, 0] = (3.0, 100.0, 0.1, 0.0, -0.05)
         return wb, bad, i, ANCH, {}, {}
     if pass_ == "forest":     # one window loses the information of all its range edges: a gauge-free tree
         from test_gpu_tree_parity import ANCH, _forest_batch
         wb = _forest_batch(la, np.random.default_rng(8300), 8, 24, 4, False)
-        bad, i = G.copy_batch(la, wb), 4
+        bad, i = wb.copy(), 4
         bad.r_val[i, :, 1] = 0.0
         return wb, bad, i, ANCH, {"bw_max": 23, "chain_threshold": 1}, {}
     if pass_ == "arrow":      # one window loses its anchor priors and its ranges to surveyed anchors
         from _arrow_cov_inputs import SURVEYED, arrow_cov_batch, cut_gauge
         wb = arrow_cov_batch(la, np.random.default_rng(9300), 5, 24, 4, False)
-        bad, i = G.copy_batch(la, wb), 2
+        bad, i = wb.copy(), 2
         cut_gauge(bad, i)
         return wb, bad, i, SURVEYED, {}, {"arrow3": 1}
     wb = G.mixed_batch(la)    # the leaves-first star loses every range
-    bad, i = G.copy_batch(la, wb), G.MIXED_STAR
+    bad, i = wb.copy(), G.MIXED_STAR
     bad.counts[i, 1] = 0
     assert G.min_relative_pivot(hessian(bad, i, G.ANCH, O.JAC_NUMERIC_G2O)) < 1e-12
     return wb, bad, i, G.ANCH, {}, {"covariance_general": 1}
@@ -387,7 +384,7 @@ def test_resident_matches_host_bit_for_bit(gpu, name):
     wb = case[0]
     B, T = wb.B, wb.caps[0]
     a, b = _solver(la, case, "numeric"), _solver(la, case, "numeric")
-    wa, wc = G.copy_batch(la, wb), G.copy_batch(la, wb)
+    wa, wc = wb.copy(), wb.copy()
     a.upload(wa); b.upload(wc)
     a.solve_resident(); b.solve_resident()
     pairs, counts = _tables(wb, case[5])
@@ -422,8 +419,8 @@ def test_resident_matches_host_bit_for_bit(gpu, name):
         assert all(np.array_equal(t.cpu().numpy(), h) for t, h in zip(outs[k], want)), k
     assert all(np.array_equal(t.cpu().numpy(), h) for t, h in zip(plain_d, a.covariance(wa)))
     # host-path joint calls between host solves leave those alone as well
-    w1, w2 = G.copy_batch(la, wb), G.copy_batch(la, wb)
-    r1 = a.solve(w1).copy(); a.joint_covariance(w1, pairs, counts); r1b = a.solve(G.copy_batch(la, wb)).copy()
+    w1, w2 = wb.copy(), wb.copy()
+    r1 = a.solve(w1).copy(); a.joint_covariance(w1, pairs, counts); r1b = a.solve(wb.copy()).copy()
     r2 = b.solve(w2).copy()
     assert np.array_equal(w1.poses[used], w2.poses[used]) and np.array_equal(r1, r2) and np.array_equal(r1b, r2)
     a.close(); b.close()
@@ -442,7 +439,7 @@ def test_resident_pair_table_grows_and_is_kept(gpu):
 
     def ready():
         s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="numeric")
-        s.upload(G.copy_batch(la, wb)); s.solve_resident()
+        s.upload(wb.copy()); s.solve_resident()
         return s
 
     def call(s, npm):

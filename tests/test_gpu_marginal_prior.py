@@ -25,14 +25,6 @@ ANCH = F.ANCH
 IDENTITY_ROW = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1] + [0] * 39, dtype=float)
 
 
-def _copy(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    out.p_info = None if wb.p_info is None else wb.p_info.copy()
-    return out
-
-
 def _mode(O, jac):
     return O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
 
@@ -131,15 +123,11 @@ def test_same_bits_elsewhere_in_the_batch_on_a_second_run_and_through_the_large_
     s = la.WindowSolver(ANCH, 1300, *wb.caps, jacobian=jac)
     again = s.marginal_prior(wb, drop)
     order = np.array([5, 2, 7, 0, 3, 6, 1, 4])
-    moved = _copy(la, wb)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(moved, name)[:] = getattr(wb, name)[order]
+    moved = wb.take(order)
     there = s.marginal_prior(moved, drop[order])
     # 1 296 windows: beyond the staging block, through the pass's own device block
     reps = 162
-    big = la.WindowBatch(wb.B * reps, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(big, name)[:] = np.concatenate([getattr(wb, name)] * reps)
+    big = wb.tile(wb.B * reps)
     large = s.marginal_prior(big, np.concatenate([drop] * reps))
     s.close()
     for a, b, c, d in zip(out, again, there, large):
@@ -174,11 +162,11 @@ def test_unsupported_and_invalid_calls_write_nothing(gpu):
     refused(wb, d, LOC_ERR_UNSUPPORTED)
     d[2] = 10                                                           # ... and an invalid slot elsewhere is invalid first
     refused(wb, d, LOC_ERR_INVALID)
-    tilted = _copy(la, wb)                                              # not translation-only: one rotated pose
+    tilted = wb.copy()                                              # not translation-only: one rotated pose
     c, sn = np.cos(0.1), np.sin(0.1)
     tilted.poses[6, 3, :9] = (c, -sn, 0, sn, c, 0, 0, 0, 1)
     refused(tilted, drop, LOC_ERR_UNSUPPORTED)
-    levered = _copy(la, wb); levered.r_val[1, 0, 2] = 0.01              # a lever arm
+    levered = wb.copy(); levered.r_val[1, 0, 2] = 0.01              # a lever arm
     refused(levered, drop, LOC_ERR_UNSUPPORTED)
     coupled, cdrop = F.case_batch(la, "fullprior")                       # a full-information prior with a translation-rotation entry
     coupled.p_info[4, 1, 2 * 6 + 5] = coupled.p_info[4, 1, 5 * 6 + 2] = 1e-3
@@ -203,7 +191,7 @@ def test_solves_before_and_after_are_unaffected(gpu):
     import localization_amd as la
     base, drop = F.case_batch(la, "fullprior")
     s = la.WindowSolver(ANCH, base.B, *base.caps, jacobian="numeric")
-    first = _copy(la, base)
+    first = base.copy()
     s.solve(first)
     kind = s.last_kernel_kind()
     s.upload(base)
@@ -211,7 +199,7 @@ def test_solves_before_and_after_are_unaffected(gpu):
     out = s.marginal_prior(first, drop)
     res = la.WindowBatch(base.B, *base.caps)
     s.download(res)
-    second = _copy(la, base)
+    second = base.copy()
     s.solve(second)
     assert s.last_kernel_kind() == kind
     again = s.marginal_prior(second, drop)
@@ -246,7 +234,7 @@ def test_fixed_lag_chain_against_the_oracle_chain(gpu, jac):
     g = F.first_window(la, chains, W)
     tol_max, tol_med = SOLVE_TOL[jac]
     for k in range(SLIDES + 1):
-        o = _copy(la, g)
+        o = g.copy()
         res = s.solve(g)
         assert k == 0 or s.last_kernel_kind() == "window_lm_kernel"   # (a carried prior has a full matrix: the general kernel)
         want_chi = np.zeros(o.B)

@@ -362,7 +362,7 @@ def test_every_other_verdict_leaves_its_window_alone(gpu):
         assert x_after.poses[b].tobytes() == x.poses[b].tobytes(), cs[b // 2][0]
     rows = (want["pose"], (want["nr"], want["r_idx"].reshape(n, 2, 2), want["r_val"].reshape(n, 2, 5)), (want["np"], want["p_val"].reshape(n, 2, 18)),
             (want["ns"], want["s_idx"].reshape(n, 1, 4), want["s_val"].reshape(n, 1, 48)), want["drop"])
-    start = P.copy_batch(la, before); start.poses[:] = x.poses
+    start = before.copy(); start.poses[:] = x.poses
     slid = P.slide_plain_ref(la, start, *rows, refused=refused)
     P.assert_same_tables(after, slid, "neighbours", [b for b in range(n) if b not in refused])
     # TWIST with s == 0 needs trajectory_length 1: one-pose windows at their lag (build only)
@@ -443,9 +443,7 @@ def test_permuted_windows_give_permuted_outputs(gpu):
     for b in range(B):
         M.fill_message(rng, msgs, b, int(rng.choice(M.LEGAL_KINDS)), x[b])
     got = _build(s, ALL, msgs)
-    wbp = P.copy_batch(la, wb)
-    for t in P.TABLES:
-        getattr(wbp, t)[:] = getattr(wb, t)[perm]
+    wbp = wb.take(perm)
     sp = _solver(la, wbp)
     sp.upload(wbp); _config(sp, M.Config(T)); sp.solve_resident()
     used = np.arange(NV_MAX)[None, :] < wbp.counts[:, :1]

@@ -21,15 +21,6 @@ STRUCTURED = "prior_information_structured"
 KIND_AFTER = {1: "wave3_lm_kernel", 0: "window_lm_kernel"}   # with a table: the structured option keeps the wave kernel, without it the general one
 
 
-def _copy(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val", "result"):
-        getattr(out, name)[:] = getattr(wb, name)
-    out.p_info = None if getattr(wb, "p_info", None) is None else wb.p_info.copy()
-    out.r_off1 = None if getattr(wb, "r_off1", None) is None else wb.r_off1.copy()
-    return out
-
-
 def _solver(la, wb, jac="numeric", structured=1, slide=1):
     s = la.WindowSolver(F.ANCH, wb.B, *wb.caps, jacobian=jac)
     s.set_option(STRUCTURED, structured)
@@ -74,11 +65,11 @@ def _chain(la, name, jac, structured, slides, drops=None, first=None, stream=Non
     slide (default: the case's); first: (batch, chains, spec) in the place of the case's; order: the windows' positions in the batch."""
     wb, chains, spec = S.case_batch(la, name) if first is None else first
     if order is not None:
-        wb, chains = _permute(la, wb, order), [chains[k] for k in order]
+        wb, chains = wb.take(order), [chains[k] for k in order]
         spec = dict(spec, consumed=spec["consumed"][order], drop=None if spec["drop"] is None else spec["drop"][order])
     r, h = _solver(la, wb, jac, structured), _solver(la, wb, jac, structured, slide=None)
     r.upload(wb)
-    g = _copy(la, wb)
+    g = wb.copy()
     trail = []
     for step in range(slides + 1):
         what = f"{name} {jac} structured={structured} step {step}"
@@ -108,7 +99,7 @@ def _chain(la, name, jac, structured, slides, drops=None, first=None, stream=Non
             assert got[k].tobytes() == want[k].astype(got[k].dtype).tobytes(), (what, field, got[k], want[k], got[0], got[2], got[3])
         g = S.slide_ref(la, g, slot, prior, pose2, ranges2, priors2, drop)
         S.assert_same_tables(r.download_batch(), g, what)
-        trail.append((_copy(la, g), want))
+        trail.append((g.copy(), want))
     r.close(); h.close()
     return trail
 
@@ -117,15 +108,6 @@ def _again(g, chains, spec):
     """the inputs of the slide just made, built again (the first set was overwritten on purpose)"""
     back = dict(spec, consumed=spec["consumed"] - 1)
     return S.next_inputs(g, chains, back)
-
-
-def _permute(la, wb, order):
-    out = _copy(la, wb)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val"):
-        getattr(out, name)[:] = getattr(wb, name)[order]
-    if out.p_info is not None:
-        out.p_info[:] = wb.p_info[order]
-    return out
 
 
 # ---- 1. bit for bit against the host composition ----------------------------------------------------------------------------------------------------
@@ -210,7 +192,7 @@ def test_a_second_stream_and_another_position_give_the_same_bits(gpu):
     moved = _chain(la, "zprior", "numeric", 1, 2, order=order)
     for (a, ma), (b, mb), (c, mc) in zip(base, other, moved):
         S.assert_same_tables(b, a, "second stream")
-        S.assert_same_tables(c, _permute(la, a, order), "another position")
+        S.assert_same_tables(c, a.take(order), "another position")
         for x, y, z in zip(ma, mb, mc):
             assert x.tobytes() == y.tobytes() and x[order].tobytes() == z.tobytes()
 
@@ -226,7 +208,7 @@ def test_a_small_host_solve_between_two_slides_leaves_the_chain_alone(gpu):
         s.upload(wb); s.solve_resident()
         s.slide_resident(*S.next_inputs(wb, chains, spec))
         if disturb:   # (the C call itself: the wrapper's solve() would first hand the other batch's table, none, to the handle)
-            o = _copy(la, other)
+            o = other.copy()
             assert s.L.loc_window_solve_host(s.h, o.B, o.counts.ctypes.data_as(ip), o.poses.ctypes.data_as(dp), o.r_idx.ctypes.data_as(ip),
                                              o.r_val.ctypes.data_as(dp), o.p_idx.ctypes.data_as(ip), o.p_val.ctypes.data_as(dp),
                                              o.s_idx.ctypes.data_as(ip), o.s_val.ctypes.data_as(dp), o.result.ctypes.data_as(dp)) == 0
@@ -264,7 +246,7 @@ def test_growing_input_blocks_and_alternating_entries(gpu):
         F.add_chain_poses(wb, i, ch, 0, 4)
     r, h = _solver(la, wb), _solver(la, wb, slide=None)
     r.upload(wb)
-    g = _copy(la, wb)
+    g = wb.copy()
     dev = torch.device("cuda", 0)
     for step, (keep, entry) in enumerate(((1, "host"), (2, "host"), (None, "device"), (None, "host"))):
         what = f"step {step}: {entry} entry, nr_new_max {keep or F.NA_MAX + 2}"
@@ -396,7 +378,7 @@ def test_without_the_option_nothing_moves(gpu):
     import localization_amd as la
     wb, _, _ = S.case_batch(la, "zprior")
     s = la.WindowSolver(F.ANCH, wb.B, *wb.caps, jacobian="numeric")
-    host = _copy(la, wb)
+    host = wb.copy()
     s.solve(host)
     s.upload(wb); s.solve_resident()
     _same_solve(la, s, host, "option never touched")

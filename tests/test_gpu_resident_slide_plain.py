@@ -59,7 +59,7 @@ def _solved(la, s):
 
 
 def _with_poses(la, wb, poses):
-    out = P.copy_batch(la, wb)
+    out = wb.copy()
     out.poses[:] = poses
     return out
 

@@ -98,18 +98,18 @@ def test_twin_against_the_general_kernel_and_back(gpu, name):
     import localization_amd as la
     base = S.case_batch(la, name)
     s = _solver(la, base, "analytic", structured=0)
-    general = S.copy_batch(la, base)
+    general = base.copy()
     s.solve(general)
     assert s.last_kernel_kind() == "window_lm_kernel"
     s.set_option(OPTION, 1)
-    twin = S.copy_batch(la, base)
+    twin = base.copy()
     s.solve(twin)
     assert s.last_kernel_kind() == "wave3_lm_kernel"
     d = np.abs(twin.poses - general.poses).max()
     print(f"wave3_lm_kernel<0, true> against window_lm_kernel<.., PINFO> {name}: {d:.3e} m")
     assert d <= KERNEL_TOL
     s.set_option(OPTION, 0)
-    again = S.copy_batch(la, base)
+    again = base.copy()
     s.solve(again)
     assert s.last_kernel_kind() == "window_lm_kernel"
     assert np.array_equal(again.poses, general.poses) and np.array_equal(again.result, general.result)
@@ -134,10 +134,10 @@ def test_diagonal_table_against_the_diagonals_and_back(gpu, jac):
     import localization_amd as la
     base = S.diagonal_batch(la)
     s = _solver(la, base, jac)
-    first = S.copy_batch(la, base)
+    first = base.copy()
     s.solve(first)
     assert s.last_kernel_kind() == "wave3_lm_kernel"
-    diag = S.copy_batch(la, base)
+    diag = base.copy()
     diag.p_info = np.zeros((base.B, base.caps[2], 36))
     diag.p_info[:, :, ::7] = base.p_val[:, :, 12:]
     s.solve(diag)
@@ -145,7 +145,7 @@ def test_diagonal_table_against_the_diagonals_and_back(gpu, jac):
     d = np.abs(diag.poses - first.poses).max()
     print(f"diag(p_val) as a structured table against the diagonals {jac}: {d:.3e} m, same bits: {np.array_equal(diag.poses, first.poses) and np.array_equal(diag.result, first.result)}")
     assert d <= KERNEL_TOL
-    again = S.copy_batch(la, base)
+    again = base.copy()
     s.solve(again)   # (p_info None: the harness passes NULL)
     assert s.last_kernel_kind() == "wave3_lm_kernel"
     assert np.array_equal(again.poses, first.poses) and np.array_equal(again.result, first.result)
@@ -198,7 +198,7 @@ def test_resident_solve_has_the_host_solves_bits(gpu):
     import localization_amd as la
     base = _with_rotation_diagonals(la)
     s = _solver(la, base, "numeric")
-    host = S.copy_batch(la, base)
+    host = base.copy()
     s.solve(host)
     assert s.last_kernel_kind() == "wave3_lm_kernel"
     s.upload(base)
@@ -220,7 +220,7 @@ def test_resident_verdict_does_not_outlive_the_structured_table(gpu, change):
     s.upload(base)
     s.solve_resident()
     assert s.last_kernel_kind() == "wave3_lm_kernel"
-    now = S.copy_batch(la, base)   # the batch a host call would be given now
+    now = base.copy()   # the batch a host call would be given now
     dp = C.POINTER(C.c_double)
     if change == "table_null":
         assert s.L.loc_window_set_prior_information(s.h, 0, None) == 0
@@ -259,7 +259,7 @@ def test_fixed_lag_chain_on_the_wave_kernel(gpu, jac):
     g = F.first_window(la, chains, W)
     tol_max, tol_med = SOLVE_TOL[jac]
     for k in range(SLIDES + 1):
-        o = S.copy_batch(la, g)
+        o = g.copy()
         res = s.solve(g)
         assert s.last_kernel_kind() == "wave3_lm_kernel", (k, s.last_kernel_kind())
         want_chi = np.zeros(o.B)
@@ -381,7 +381,7 @@ def test_resident_covariances_have_the_host_calls_bits(gpu, name):
     s.covariance_resident(tc, tm, ts)
     s.joint_covariance_resident(pairs, PAIR_COUNTS, tj, tm, ts, tx)
     torch.cuda.synchronize()
-    host = S.copy_batch(la, base)
+    host = base.copy()
     host.poses[:] = _download(la, s, base).poses
     host.poses[~_used(base)] = base.poses[~_used(base)]
     cov, mask, status, cross = s.joint_covariance(host, pairs, PAIR_COUNTS)
@@ -397,7 +397,7 @@ def test_covariance_without_the_option_and_the_envelope_pass(gpu):
     from localization_amd._lib import LocalizationAmdError
     for jac in ("analytic", "numeric"):
         wb, (cov, mask, status), _ = _covariances("T10", jac)
-        wb = S.copy_batch(la, wb)
+        wb = wb.copy()
         s = _solver(la, wb, jac, structured=0)
         out = (np.full((wb.B, wb.caps[0], 6, 6), 7.0), np.full((wb.B, wb.caps[0]), 7, dtype=np.int32), np.full(wb.B, 7, dtype=np.int32))
         with pytest.raises(LocalizationAmdError) as e:

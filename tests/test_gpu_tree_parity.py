@@ -14,13 +14,6 @@ pytestmark = pytest.mark.gpu
 ANCH = np.array([[3, -3, 0.58], [3, 3, 1.97], [-3, 3, 0.54], [-3, -3, 1.76]], dtype=float)
 
 
-def _copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
-
-
 def _forest_batch(la, rng, B, T, every, rich):
     """Key-frame stars as addPoseEdge builds them (a new key every `every` poses; the pose before a new key IS that key), one anchor range
     per pose.  rich: two trees (one link missing), a smoothness range next to the EdgeSE3 of some pairs, IMU-style priors on some poses,
@@ -69,7 +62,7 @@ def test_tree_kernel_matches_oracle_and_general_kernel(gpu, T, every, rich, jac)
     rng = np.random.default_rng(7000 + T + every + len(jac))
     wb = _forest_batch(la, rng, B, T, every, rich)
     before = wb.poses.copy()
-    ref = _copy_batch(la, wb)
+    ref = wb.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     n_or = B if T < 64 else 12
     want = [oracle_solve_instance(wb, i, ANCH, jac_mode=mode) for i in range(n_or)]
@@ -94,7 +87,7 @@ def test_tree_kernel_matches_oracle_and_general_kernel(gpu, T, every, rich, jac)
     assert np.array_equal(res[:, 6], res_g[:, 6])          # pose-to-pose edges that share their pair with another edge
     assert (res[:, 4] != res_g[:, 4]).mean() < (0.05 if T > 10 else 0.3)   # (ten-pose windows converge: their last accept / reject decisions are rounding-level ties)
     # resident API: the same bits
-    wb2 = _copy_batch(la, wb); wb2.poses[:] = before
+    wb2 = wb.copy(); wb2.poses[:] = before
     s.upload(wb2); s.solve_resident(); s.download(wb2)
     assert s.last_kernel_kind() == kind and np.array_equal(wb2.poses, wb.poses) and np.array_equal(wb2.result, res)
     # a host-path solve of ANOTHER batch (another topology, another schedule) while this one is resident must not disturb the resident
@@ -130,7 +123,7 @@ def test_lane_per_window_tree_kernel_on_the_same_schedule(gpu, jac):
         assert np.abs(wb.poses[i] - want[i][0]).max() < tol, (i, np.abs(wb.poses[i] - want[i][0]).max())
     # without the doubled EdgeSE3 both variants apply: lane-per-window (forced) against lane-per-pose
     plain_lane = _forest_batch(la, np.random.default_rng(5), B, T, 4, True)
-    plain_wave = _copy_batch(la, plain_lane)
+    plain_wave = plain_lane.copy()
     s.set_option("tree", 2)                                # the lane-per-window variant (was LOCAMD_TREE=lane)
     s.solve(plain_lane)
     s.set_option("tree", -1)
@@ -154,7 +147,7 @@ def test_tree_kernel_needs_one_shared_forest_topology(gpu):
     s = la.WindowSolver(ANCH, B, *base.caps, jacobian="analytic", bw_max=T - 1, chain_threshold=1)
 
     def kind(mut):
-        wb = _copy_batch(la, base)
+        wb = base.copy()
         mut(wb)
         s.solve(wb)
         return s.last_kernel_kind()
@@ -168,7 +161,7 @@ def test_tree_kernel_needs_one_shared_forest_topology(gpu):
         assert kind(mut) == "window_lm_kernel", mut.__name__
     s.close()
     small = la.WindowSolver(ANCH, B, *base.caps, jacobian="analytic", bw_max=T - 1)   # default threshold: 64 windows are a small batch
-    small.solve(_copy_batch(la, base))
+    small.solve(base.copy())
     assert small.last_kernel_kind() == "window_lm_kernel"
     small.close()
 
@@ -222,8 +215,8 @@ def test_tree_wave_kernel_on_random_forests(gpu, seed, T, jac):
                 else: wb.add_range(i, k, p, float(np.linalg.norm(tt[k] - tt[p])), 1 / 0.1 ** 2)
             if prior[k]:
                 wb.add_prior(i, k, et[k], (tR[k] * Rotation.from_rotvec(rng.normal(0, 2e-3, 3))).as_matrix(), np.array([0, 0, 0.5, 1, 1, 1.0]) / 4.592449e-06)
-    ref = _copy_batch(la, wb)
-    wb0 = _copy_batch(la, wb)
+    ref = wb.copy()
+    wb0 = wb.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     want = [oracle_solve_instance(wb, i, ANCH, jac_mode=mode) for i in range(12)]
     g = la.WindowSolver(ANCH, B, *wb.caps, jacobian=jac, bw_max=T - 1, chain_threshold=0)
@@ -266,7 +259,7 @@ def test_tree_wave_kernel_on_a_small_handle_reads_the_staging_block_in_place(gpu
     for rich in (False, True):
         B, T = 2, 24
         wb = _forest_batch(la, np.random.default_rng(77), B, T, 4, rich)
-        ref = _copy_batch(la, wb)
+        ref = wb.copy()
         g = la.WindowSolver(ANCH, B, *wb.caps, jacobian="analytic", bw_max=T - 1, chain_threshold=0)
         g.solve(ref)
         assert g.last_kernel_kind() == "window_lm_kernel"
@@ -274,7 +267,7 @@ def test_tree_wave_kernel_on_a_small_handle_reads_the_staging_block_in_place(gpu
         s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="analytic", bw_max=T - 1, chain_threshold=1)
         s.solve(wb)
         assert s.last_kernel_kind() == "tree_wave_kernel"
-        again = _copy_batch(la, ref); again.poses[:] = _forest_batch(la, np.random.default_rng(77), B, T, 4, rich).poses
+        again = ref.copy(); again.poses[:] = _forest_batch(la, np.random.default_rng(77), B, T, 4, rich).poses
         s.set_option("zero_copy", 0)
         s.solve(again)
         s.close()

@@ -17,7 +17,7 @@ import _window_structure_model as M
 pytestmark = pytest.mark.gpu
 
 LOC_ERR_INVALID = -1
-TABLES = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
+TABLES = P.TABLES
 GENERAL, CHAIN, WAVE3, WAVE6, WAVE6S = "window_lm_kernel", "chain_lm_kernel", "wave3_lm_kernel", "wave6_lm_kernel", "wave6_lm_kernel<SE3>"
 WORDS = {1: "counts exceed capacities", 2: "range edge vertex index", 3: "range edge couples poses further apart than bw_max", 4: "prior edge vertex index",
          5: "SE3 edge vertex index", 6: "SE3 edge couples poses further apart than bw_max"}
@@ -243,15 +243,15 @@ def test_an_ordering_violation_between_rows_63_and_64(gpu):
     import localization_amd as la
     base = _step_window(la, True)
     assert _kinds_and_solutions(la, base, "the ordered window") == CHAIN
-    r = P.copy_batch(la, base)
+    r = base.copy()
     r.r_idx[1, 64] = (31, -1)                                 # pose 31's anchor range behind pose 32's pair row
-    p = P.copy_batch(la, base)
+    p = base.copy()
     p.p_idx[1, 64] = 62                                       # rows 63 .. 69 are on pose 63
-    s = P.copy_batch(la, base)
+    s = base.copy()
     s.s_idx[1, 64, :2] = (61, 62)                             # rows 62 .. 65 join poses 62 and 63
     for name, wb in (("ranges", r), ("priors", p), ("EdgeSE3", s)):
         assert _kinds_and_solutions(la, wb, name) == GENERAL, name
-    inside = P.copy_batch(la, base)
+    inside = base.copy()
     inside.p_idx[1, 63] = 62; inside.p_idx[1, 62] = 63        # the same inside a step, and the step's first row against the carried value
     assert _kinds_and_solutions(la, inside, "inside a step") == GENERAL
 
@@ -261,7 +261,7 @@ def test_a_duplicated_pair_across_rows_63_and_64(gpu):
     base = _step_window(la, False)
     for wb, kernel in ((base, WAVE6), (None, GENERAL)):
         if wb is None:
-            wb = P.copy_batch(la, base)
+            wb = base.copy()
             wb.r_idx[1, 64] = (32, 31)                        # the pair of row 63 again: the verdict is CHAIN, which 3 windows solve on the general kernel
         a, h = _solver(la, wb), _solver(la, wb)
         _upload_dev(a, wb); h.upload(wb)
@@ -302,7 +302,7 @@ def test_the_only_bad_index_in_row_64_and_in_the_last_row(gpu):
     s = _solver(la, base)
     for table, row, column, value, code in (("r_idx", 64, 0, 64, 2), ("r_idx", 129, 1, 64, 2), ("r_idx", 129, 1, -5, 2), ("p_idx", 64, None, 64, 4), ("p_idx", 69, None, -1, 4),
                                             ("s_idx", 64, 1, 64, 5), ("s_idx", 65, 0, -1, 5)):
-        wb = P.copy_batch(la, base)
+        wb = base.copy()
         if column is None:
             getattr(wb, table)[1, row] = value
         else:
@@ -321,7 +321,7 @@ def _rule(wb, bw_max, n_anchors):
 
 
 def _plant(la, base, i, code):
-    wb = P.copy_batch(la, base)
+    wb = base.copy()
     nv = int(base.counts[i, 0])
     if code == 1:
         wb.counts[i, i % 4] = base.caps[i % 4] + 1 if i % 2 else -1
@@ -365,7 +365,7 @@ def test_poisoned_rows_beyond_the_counts_change_nothing(gpu):
     import localization_amd as la
     for name in ("twist", "imu"):
         base = P.case_batch(la, name, (2, 1, 1))[0]
-        wb = P.copy_batch(la, base)
+        wb = base.copy()
         for i in range(wb.B):
             nv, nr, npr, ns = (int(x) for x in wb.counts[i])
             wb.poses[i, nv:] = np.nan; wb.r_idx[i, nr:] = (M.I32_MAX, M.I32_MIN); wb.p_idx[i, npr:] = M.I32_MIN; wb.s_idx[i, ns:] = (M.I32_MIN, M.I32_MAX, 7, 7)

@@ -360,7 +360,7 @@ def test_a_refused_batch_leaves_the_resident_arrowhead_batch(gpu):
     a, h = _both(la, wb)
     _same_kernel_and_bits(la, a, h, wb, ARROW3, "before")
     x0 = U._solved(la, a)
-    bad = P.copy_batch(la, _arrow_batch(la, seed=4))               # other records, other sizes — and window 6 names a pose beyond its count
+    bad = _arrow_batch(la, seed=4).copy()               # other records, other sizes — and window 6 names a pose beyond its count
     bad.r_idx[6, 5, 0] = int(bad.counts[6, 0])
     text, _ = U._refused(la, a, bad)
     assert "range edge vertex index" in text and "window 6" in text

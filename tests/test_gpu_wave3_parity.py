@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_chain3_parity import ANCH, _copy_batch, _translation_only_batch
+from test_gpu_chain3_parity import ANCH, _translation_only_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +35,7 @@ def test_wave3_kernel_matches_6dof_oracle_and_general_kernel(gpu, T, jac, with_z
     before = wb.poses.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     want = [oracle_solve_instance(wb, i, ANCH, jac_mode=mode) for i in range(B)]
-    ref = _copy_batch(la, wb)
+    ref = wb.copy()
     general = la.WindowSolver(ANCH, B, *wb.caps, jacobian=jac, chain_threshold=0)
     res_general = general.solve(ref).copy()
     assert general.last_kernel_kind() == "window_lm_kernel"
@@ -75,7 +75,7 @@ def test_wave3_kernel_matches_6dof_oracle_and_general_kernel(gpu, T, jac, with_z
     if T > 1:   # (a lone well-observed pose converges early: its remaining accept / reject decisions are taken on rounding-level chi differences)
         assert (res[:, 4] != res_general[:, 4]).mean() < 0.06
     # the same window in another workgroup: the same bits; resident API: the same answer again
-    wb2 = _copy_batch(la, wb); wb2.poses[:] = before
+    wb2 = wb.copy(); wb2.poses[:] = before
     wb2.poses[5] = before[1]
     for name in ("counts", "r_idx", "r_val", "p_idx", "p_val"):
         getattr(wb2, name)[5] = getattr(wb2, name)[1]
@@ -109,7 +109,7 @@ def test_wave3_single_window_many_ranges_per_pose(gpu):
         if k > 0:
             wb.add_range(0, k - 1, k, 0.0, 1.0 / (5.0 / 32 / 3) ** 2)
     for jac, mode, tol in (("analytic", O.JAC_ANALYTIC, 1e-7), ("numeric", O.JAC_NUMERIC_G2O, 3e-5)):
-        w = _copy_batch(la, wb)
+        w = wb.copy()
         poses, chi, st = oracle_solve_instance(w, 0, ANCH, jac_mode=mode)
         s = la.WindowSolver(ANCH, 1, *w.caps, jacobian=jac)
         res = s.solve(w).copy()
@@ -149,7 +149,7 @@ def test_wave3_selection_rules(gpu):
     s = la.WindowSolver(ANCH, B, *base.caps, jacobian="analytic")
 
     def kind(mut, solver=s):
-        wb = _copy_batch(la, base)
+        wb = base.copy()
         mut(wb)
         solver.solve(wb)
         return solver.last_kernel_kind()

@@ -15,13 +15,6 @@ from test_gpu_window_parity import ANCH, _random_window
 pytestmark = pytest.mark.gpu
 
 
-def _copy_batch(la, wb):
-    out = la.WindowBatch(wb.B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-        getattr(out, name)[:] = getattr(wb, name)
-    return out
-
-
 def _chain_batch(la, rng, B, T, with_imu, lever, lidar=False):
     """Windows in the reference's creation order (a pose's anchor range, then its smoothness edge to the previous pose), ragged
     lengths, some with a missing link; IMU rotation priors, optionally a lidar-style z prior as a second prior of every other pose."""
@@ -67,7 +60,7 @@ def test_wave6_kernel_matches_oracle_and_general_kernel(gpu, T, with_imu, lever,
     before = wb.poses.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     want = [oracle_solve_instance(wb, i, ANCH, jac_mode=mode) for i in range(B)]
-    ref = _copy_batch(la, wb)
+    ref = wb.copy()
     general = la.WindowSolver(ANCH, B, *wb.caps, jacobian=jac, chain_threshold=0)
     res_general = general.solve(ref).copy()
     assert general.last_kernel_kind() == "window_lm_kernel"
@@ -103,7 +96,7 @@ def test_wave6_kernel_matches_oracle_and_general_kernel(gpu, T, with_imu, lever,
     if T > 1:
         assert (res[:, 4] != res_general[:, 4]).mean() < 0.06   # LM trial counts
     # the same window in another workgroup: the same bits; resident API: the same answer again
-    wb2 = _copy_batch(la, wb); wb2.poses[:] = before
+    wb2 = wb.copy(); wb2.poses[:] = before
     wb2.poses[5] = before[1]
     for name in ("counts", "r_idx", "r_val", "p_idx", "p_val"):
         getattr(wb2, name)[5] = getattr(wb2, name)[1]
@@ -152,7 +145,7 @@ def test_wave6_selection_rules(gpu):
     s = la.WindowSolver(ANCH, B, *caps, jacobian="analytic")
 
     def kind(mut):
-        wb = _copy_batch(la, wbase)
+        wb = wbase.copy()
         mut(wb)
         s.solve(wb)
         return s.last_kernel_kind()
@@ -230,10 +223,10 @@ def test_wave6_se3_kernel_matches_oracle_and_general_kernel(gpu, T, with_imu, le
     wb = _twist_batch(la, rng, B, T, with_imu, lever)
     wb.counts[3, 1:] = 0   # an instance whose poses have no edge at all: comes back untouched
     before = wb.poses.copy()
-    wb0 = _copy_batch(la, wb)
+    wb0 = wb.copy()
     mode = O.JAC_ANALYTIC if jac == "analytic" else O.JAC_NUMERIC_G2O
     want = [oracle_solve_instance(wb, i, ANCH, jac_mode=mode) for i in range(B)]
-    ref = _copy_batch(la, wb)
+    ref = wb.copy()
     general = la.WindowSolver(ANCH, B, *wb.caps, jacobian=jac, chain_threshold=0)
     res_general = general.solve(ref).copy()
     assert general.last_kernel_kind() == "window_lm_kernel"
@@ -266,7 +259,7 @@ def test_wave6_se3_kernel_matches_oracle_and_general_kernel(gpu, T, with_imu, le
     assert np.abs(wb.poses - ref.poses).max() < (tol if jac == "analytic" else 1e-3)
     if T > 2:
         assert (res[:, 4] != res_general[:, 4]).mean() < 0.06   # LM trial counts
-    wb2 = _copy_batch(la, wb); wb2.poses[:] = before
+    wb2 = wb.copy(); wb2.poses[:] = before
     s.upload(wb2); s.solve_resident(); s.download(wb2)
     assert s.last_kernel_kind() == "wave6_lm_kernel<SE3>"
     for i in range(B):
@@ -274,7 +267,7 @@ def test_wave6_se3_kernel_matches_oracle_and_general_kernel(gpu, T, with_imu, le
         assert np.array_equal(wb2.poses[i, :nv], wb.poses[i, :nv]) and np.array_equal(wb2.result[i], res[i]), i
     # option "wave6" = 0: the general kernel, as before
     s.set_option("wave6", 0)
-    wb3 = _copy_batch(la, wb); wb3.poses[:] = before
+    wb3 = wb.copy(); wb3.poses[:] = before
     s.solve(wb3)
     assert s.last_kernel_kind() == "window_lm_kernel"
     s.close()

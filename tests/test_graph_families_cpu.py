@@ -46,7 +46,7 @@ def test_fill_graph_and_relabel(built):
         assert (np.bincount(wb.r_idx[1, :nr, 0][wb.r_idx[1, :nr, 1] < 0], minlength=12) == 4).all()     # every pose: four anchors
         assert _norm(set(_norm(window_pairs(wb, 1)))) == _norm(pairs) and F.shared_edges(wb, 1) == 4
         assert (wb.s_idx[1, :ns, 2] == 1).all() and six == bool((wb.r_val[1, :48, 2:] != 0).any())
-        before = {n: getattr(wb, n).copy() for n in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")}
+        before = {n: getattr(wb, n).copy() for n in wb.TABLES}
         perm = np.random.default_rng(2).permutation(12)
         F.relabel(wb, 1, perm)
         for n in ("counts", "r_val", "p_val", "s_val"):

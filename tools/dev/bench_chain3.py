@@ -8,9 +8,7 @@ import bench_window as bw
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 if len(sys.argv) > 2: bw.POSES_OVERRIDE = int(sys.argv[2])
 small, graphs, anchors, T = bw.build(2048, "uwb_only", seed=1)
-wb = la.WindowBatch(B, *small.caps)
-for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-    src = getattr(small, name); getattr(wb, name)[:] = np.resize(src, (B,) + src.shape[1:])
+wb = small.tile(B)
 for jac in ("analytic", "numeric"):
     s = la.WindowSolver(anchors, B, *wb.caps, maximum_iteration=10, bw_max=1, jacobian=jac)
     s.upload(wb)

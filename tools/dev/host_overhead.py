@@ -8,9 +8,7 @@ import localization_amd as la
 import bench_window as bw
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 small, graphs, anchors, T = bw.build(4096, "uwb_only", seed=3)
-wb = la.WindowBatch(B, *small.caps)
-for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-    src = getattr(small, name); getattr(wb, name)[:] = np.resize(src, (B,) + src.shape[1:])
+wb = small.tile(B)
 poses0 = wb.poses.copy()
 s = la.WindowSolver(anchors, B, *wb.caps, maximum_iteration=10, bw_max=1, jacobian="numeric")
 for label, cache in (("cache on", 1), ("cache off", 0)):

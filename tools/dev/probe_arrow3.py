@@ -7,9 +7,7 @@ import localization_amd as la
 import bench_window as bw
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 small, graphs, anchors, nv = bw.build_selfcal(min(B, 8), np.random.default_rng(11))
-wb = la.WindowBatch(B, *small.caps)
-for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"):
-    src = getattr(small, name); getattr(wb, name)[:] = np.resize(src, (B,) + src.shape[1:])
+wb = small.tile(B)
 s = la.WindowSolver(anchors, B, *wb.caps, maximum_iteration=10, bw_max=nv - 1, jacobian=sys.argv[2] if len(sys.argv) > 2 else "analytic")
 s.solve(wb); r = wb.result.mean(axis=0)
 names = ["", "linearise", "forward+schur", "dense", "B^T x", "chain z,x", "update", "trial eval"] if os.environ.get("ARROW_LEVEL", "1") == "1" else ["", "lin: tail of the chunk loop", "lin: PK += GZ", "lin: CS barrier", "lin: sums", "lin: CS loads+adds", "lin: CS wave sums", "lin: slot loop"]

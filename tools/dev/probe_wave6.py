@@ -10,8 +10,7 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 wb, graphs, anchors, T = bw.build(B, "uwb_imu", seed=3)
 s = la.WindowSolver(anchors, B, *wb.caps, maximum_iteration=10, bw_max=1, jacobian=sys.argv[2] if len(sys.argv) > 2 else "numeric")
 for _ in range(3):
-    w2 = la.WindowBatch(B, *wb.caps)
-    for name in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"): getattr(w2, name)[:] = getattr(wb, name)
+    w2 = wb.copy()
     s.solve(w2)
 r = w2.result.mean(axis=0)
 trials = int(r[7] // 1e12); total = r[7] - 1e12 * trials

@@ -43,16 +43,10 @@ def build(B, Tmax, seed):
     return wb
 
 
-def copy(wb):
-    o = la.WindowBatch(wb.B, *wb.caps)
-    for n in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"): getattr(o, n)[:] = getattr(wb, n)
-    return o
-
-
 worst = None
 for B, Tmax in ((4096, 15), (4096, 31), (2048, 63), (4096, 6)):
     wb = build(B, Tmax, 23 + Tmax)
-    ref = copy(wb); orig = copy(wb)
+    ref = wb.copy(); orig = wb.copy()
     g = la.WindowSolver(ANCH, B, *wb.caps, jacobian="analytic", chain_threshold=0)
     rg = g.solve(ref).copy(); kg = g.last_kernel_kind(); g.close()
     s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="analytic")

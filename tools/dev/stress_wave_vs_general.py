@@ -39,15 +39,9 @@ def build(B, Tmax, six, seed):
     return wb
 
 
-def copy(wb):
-    o = la.WindowBatch(wb.B, *wb.caps)
-    for n in ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val"): getattr(o, n)[:] = getattr(wb, n)
-    return o
-
-
 for six, B, Tmax in ((False, 8192, 64), (False, 8192, 12), (True, 4096, 40), (True, 4096, 12)):
     wb = build(B, Tmax, six, 17 + Tmax)
-    ref = copy(wb)
+    ref = wb.copy()
     g = la.WindowSolver(ANCH, B, *wb.caps, jacobian="analytic", chain_threshold=0)
     rg = g.solve(ref).copy(); kg = g.last_kernel_kind(); g.close()
     s = la.WindowSolver(ANCH, B, *wb.caps, jacobian="analytic")
@@ -63,7 +57,7 @@ for six, B, Tmax in ((False, 8192, 64), (False, 8192, 12), (True, 4096, 40), (Tr
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from _oracle_window import oracle_solve_instance
 wb = build(8192, 64, False, 17 + 64)
-ref = copy(wb); orig = copy(wb)
+ref = wb.copy(); orig = wb.copy()
 g = la.WindowSolver(ANCH, 8192, *wb.caps, jacobian="analytic", chain_threshold=0); g.solve(ref); g.close()
 s = la.WindowSolver(ANCH, 8192, *wb.caps, jacobian="analytic"); rs = s.solve(wb).copy(); s.close()
 d = np.array([np.abs(wb.poses[i, :int(wb.counts[i, 0])] - ref.poses[i, :int(wb.counts[i, 0])]).max() for i in range(8192)])

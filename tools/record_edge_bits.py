@@ -129,7 +129,6 @@ CASES = {
     "marginal_prior": ("marginal_prior", _marginal, BOTH, 3, {}, None),
     "edge_audit": ("edge_chi2", _general(), ("analytic",), 3, {}, None),
 }
-INPUTS = ("counts", "poses", "r_idx", "r_val", "p_idx", "p_val", "s_idx", "s_val")
 
 
 def pack(a):
@@ -149,7 +148,7 @@ def run_case(la, name, jac):
     made = build(la)
     wb, extra = (made[0], made[1:]) if isinstance(made, tuple) else (made, ())
     anchors = extra[-1] if extra else ANCH
-    rec = {"in/" + k: getattr(wb, k).copy() for k in INPUTS}
+    rec = {"in/" + k: getattr(wb, k).copy() for k in wb.TABLES}
     for k in ("r_off1", "p_info"):
         if getattr(wb, k, None) is not None:
             rec["in/" + k] = getattr(wb, k).copy()
