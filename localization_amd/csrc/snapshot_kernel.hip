@@ -92,62 +92,9 @@ __device__ __forceinline__ double range_norm_plain(double dx, double dy, double 
 __device__ __forceinline__ double range_sq_plain(double dx, double dy, double dz) { return dx * dx + dy * dy + dz * dz; }
 #pragma clang fp contract(fast)
 
-// Residuals, robust weights, normal equations and both chi sums at point p, for this lane's APL anchors, combined
-// over the LPI lanes of the tag.  `gate`: finite only on the first evaluation of an update (at the prior estimate) with
-// the outlier gate armed: ranges with | ||p - a|| - d | > gate lose their weight for the whole update.
-template <int LPI, int APL, int JAC>
-__device__ __forceinline__ System evaluate(const double px, const double py, const double pz,
-                                           const double (&ax)[APL], const double (&ay)[APL], const double (&az)[APL],
-                                           const double (&d)[APL], double (&w)[APL], const double gate) {
-    System s = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    double prod = 1.0;
-    int kexp = 0;
-#pragma unroll
-    for (int j = 0; j < APL; ++j) {
-        const double dx = px - ax[j], dy = py - ay[j], dz = pz - az[j];
-        double n, jx, jy, jz;  // J = de/dp
-        if constexpr (JAC == 0) {
-            // coincident endpoints: n2 = 0 is clamped, dx = dy = dz = 0 -> J = 0
-            const double n2 = fmax(dx * dx + dy * dy + dz * dz, 1e-300);
-            double inv;
-            sqrt_and_rsqrt_fast(n2, n, inv);
-            jx = -dx * inv; jy = -dy * inv; jz = -dz * inv;
-        } else {
-            constexpr double delta = 1e-9;
-            constexpr double scalar = 1.0 / (2 * delta);
-            const double x0 = range_sq_plain(dx, dy, dz);
-            double h0, c0;
-            n = sqrt_ieee_unscaled_raw(x0, h0, c0);   // (no +-0 / inf pass-through here: only the slow branch below can see such an argument)
-            const double xp = (px + delta) - ax[j], xm = (px - delta) - ax[j];
-            const double yp = (py + delta) - ay[j], ym = (py - delta) - ay[j];
-            const double zp = (pz + delta) - az[j], zm = (pz - delta) - az[j];
-            if (x0 >= 1e-5 && x0 < 1e300) {
-                // the six perturbed norms from the central one (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers)
-                jx = scalar * ((d[j] - sqrt_ieee_near_c(range_sq_plain(xp, dy, dz), n, h0, c0)) - (d[j] - sqrt_ieee_near_c(range_sq_plain(xm, dy, dz), n, h0, c0)));
-                jy = scalar * ((d[j] - sqrt_ieee_near_c(range_sq_plain(dx, yp, dz), n, h0, c0)) - (d[j] - sqrt_ieee_near_c(range_sq_plain(dx, ym, dz), n, h0, c0)));
-                jz = scalar * ((d[j] - sqrt_ieee_near_c(range_sq_plain(dx, dy, zp), n, h0, c0)) - (d[j] - sqrt_ieee_near_c(range_sq_plain(dx, dy, zm), n, h0, c0)));
-            } else {   // a tag within millimetres of an anchor (or an estimate that has run away)
-                n = (x0 == 0.0 || x0 == __builtin_inf()) ? x0 : n;
-                jx = scalar * ((d[j] - range_norm_plain(xp, dy, dz)) - (d[j] - range_norm_plain(xm, dy, dz)));
-                jy = scalar * ((d[j] - range_norm_plain(dx, yp, dz)) - (d[j] - range_norm_plain(dx, ym, dz)));
-                jz = scalar * ((d[j] - range_norm_plain(dx, dy, zp)) - (d[j] - range_norm_plain(dx, dy, zm)));
-            }
-        }
-        const double e = d[j] - n;
-        w[j] = (fabs(e) > gate) ? 0.0 : w[j];  // |d_hat - d| > distance_outlier, localization.cpp:309 (gate = inf: off)
-        const double we = w[j] * e;
-        const double chi = e * we;
-        const double aux = 1.0 + chi;
-        const double rho1 = fast_rcp_1nr(aux);
-        const double wr = rho1 * w[j];
-        const double wjx = wr * jx, wjy = wr * jy, wjz = wr * jz;
-        s.h00 = __builtin_fma(wjx, jx, s.h00); s.h01 = __builtin_fma(wjx, jy, s.h01); s.h02 = __builtin_fma(wjx, jz, s.h02);
-        s.h11 = __builtin_fma(wjy, jy, s.h11); s.h12 = __builtin_fma(wjy, jz, s.h12); s.h22 = __builtin_fma(wjz, jz, s.h22);
-        s.b0 = __builtin_fma(-wjx, e, s.b0); s.b1 = __builtin_fma(-wjy, e, s.b1); s.b2 = __builtin_fma(-wjz, e, s.b2);
-        prod *= aux;
-        if (APL > 4 && j == 3) { kexp = __builtin_amdgcn_frexp_exp(prod); prod = __builtin_amdgcn_frexp_mant(prod); }
-        s.chi += chi;
-    }
+// A lane's sums over its APL anchors, combined over the LPI lanes of the tag; `prod` 2^`kexp` is the lane's product of (1 + chi).
+template <int LPI>
+__device__ __forceinline__ System combine_over_tag(System s, double prod, int kexp) {
     s.h00 = group_sum<LPI>(s.h00); s.h01 = group_sum<LPI>(s.h01); s.h02 = group_sum<LPI>(s.h02);
     s.h11 = group_sum<LPI>(s.h11); s.h12 = group_sum<LPI>(s.h12); s.h22 = group_sum<LPI>(s.h22);
     s.b0 = group_sum<LPI>(s.b0); s.b1 = group_sum<LPI>(s.b1); s.b2 = group_sum<LPI>(s.b2);
@@ -163,6 +110,135 @@ __device__ __forceinline__ System evaluate(const double px, const double py, con
     }
     s.rchi = fast_log_ge1_scaled(prod, kexp);
     return s;
+}
+
+// Residuals, robust weights, normal equations and both chi sums at point p, for this lane's APL anchors, combined
+// over the LPI lanes of the tag.  `gate`: finite only on the first evaluation of an update (at the prior estimate) with
+// the outlier gate armed: ranges with | ||p - a|| - d | > gate lose their weight for the whole update.
+// The analytic Jacobian (JAC == 0):
+template <int LPI, int APL>
+__device__ __forceinline__ System evaluate(const double px, const double py, const double pz,
+                                           const double (&ax)[APL], const double (&ay)[APL], const double (&az)[APL],
+                                           const double (&d)[APL], double (&w)[APL], const double gate) {
+    System s = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double prod = 1.0;
+    int kexp = 0;
+#pragma unroll
+    for (int j = 0; j < APL; ++j) {
+        const double dx = px - ax[j], dy = py - ay[j], dz = pz - az[j];
+        double n, jx, jy, jz;  // J = de/dp
+        // coincident endpoints: n2 = 0 is clamped, dx = dy = dz = 0 -> J = 0
+        const double n2 = fmax(dx * dx + dy * dy + dz * dz, 1e-300);
+        double inv;
+        sqrt_and_rsqrt_fast(n2, n, inv);
+        jx = -dx * inv; jy = -dy * inv; jz = -dz * inv;
+        const double e = d[j] - n;
+        w[j] = (fabs(e) > gate) ? 0.0 : w[j];  // |d_hat - d| > distance_outlier, localization.cpp:309 (gate = inf: off)
+        const double we = w[j] * e;
+        const double chi = e * we;
+        const double aux = 1.0 + chi;
+        const double rho1 = fast_rcp_1nr(aux);
+        const double wr = rho1 * w[j];
+        const double wjx = wr * jx, wjy = wr * jy, wjz = wr * jz;
+        s.h00 = __builtin_fma(wjx, jx, s.h00); s.h01 = __builtin_fma(wjx, jy, s.h01); s.h02 = __builtin_fma(wjx, jz, s.h02);
+        s.h11 = __builtin_fma(wjy, jy, s.h11); s.h12 = __builtin_fma(wjy, jz, s.h12); s.h22 = __builtin_fma(wjz, jz, s.h22);
+        s.b0 = __builtin_fma(-wjx, e, s.b0); s.b1 = __builtin_fma(-wjy, e, s.b1); s.b2 = __builtin_fma(-wjz, e, s.b2);
+        prod *= aux;
+        if (APL > 4 && j == 3) { kexp = __builtin_amdgcn_frexp_exp(prod); prod = __builtin_amdgcn_frexp_mant(prod); }
+        s.chi += chi;
+    }
+    return combine_over_tag<LPI>(s, prod, kexp);
+}
+
+// ---- g2o's numeric Jacobian (JAC == 1): pinned arithmetic, one range vote per pass --------------------------------
+// An edge takes its six perturbed roots from the central one (sqrt_ieee_near_c) while the central squared distance x0 is in
+// [1e-5, 1e300) and the full IEEE expansion otherwise.  No lane of an ordinary wave is ever outside that range, so the test is made
+// once per pass for the whole wave (the kernel's loop) and not once per edge: a wave with no ACTIVE lane outside it runs the
+// pass without the test (GUARDED = false), any other wave runs the pass that tests every edge (GUARDED = true).  A lane inside the
+// range executes the same operations either way, so its result does not depend on which pass its wave-mates sent it through.
+constexpr unsigned hi_word(double v) { return (unsigned)(__builtin_bit_cast(unsigned long long, v) >> 32); }
+
+#pragma clang fp contract(off)
+// The squared distances to this lane's anchors, and the lane's vote: true if one of them may be outside [1e-5, 1e300).  Compared on the
+// high words as unsigned integers (a squared distance is >= +0 or a NaN: the order of the words is the order of the numbers; a NaN's
+// word is above +inf's, whatever its sign): strictly inside the words of the two bounds is inside the range, so the vote can only
+// err towards the tested pass, and a NaN votes for it.
+template <int APL>
+__device__ __forceinline__ bool range_vote(const double px, const double py, const double pz,
+                                           const double (&ax)[APL], const double (&ay)[APL], const double (&az)[APL], double (&x0)[APL]) {
+    unsigned lo = 0xffffffffu, hi = 0u;
+#pragma unroll
+    for (int j = 0; j < APL; ++j) {
+        x0[j] = range_sq_plain(px - ax[j], py - ay[j], pz - az[j]);
+        const unsigned u = (unsigned)__double2hiint(x0[j]);
+        lo = u < lo ? u : lo;
+        hi = u > hi ? u : hi;
+    }
+    return !(lo > hi_word(1e-5) && hi < hi_word(1e300));
+}
+
+// The ranges and their numeric Jacobians at p, for this lane's APL anchors: n_j = ||p - a_j|| and J_j = de_j/dp by g2o's central
+// differences.  `x0`: range_vote's squared distances at p.  GUARDED: every edge tests its own x0 (what a wave runs whose vote fell).
+template <int APL, bool GUARDED>
+__device__ __forceinline__ void numeric_ranges(const double px, const double py, const double pz,
+                                               const double (&ax)[APL], const double (&ay)[APL], const double (&az)[APL],
+                                               const double (&x0)[APL], const double (&d)[APL],
+                                               double (&n)[APL], double (&jx)[APL], double (&jy)[APL], double (&jz)[APL]) {
+    constexpr double delta = 1e-9;
+    constexpr double scalar = 1.0 / (2 * delta);
+#pragma unroll
+    for (int j = 0; j < APL; ++j) {
+        const double dx = px - ax[j], dy = py - ay[j], dz = pz - az[j];
+        double h0, c0;
+        n[j] = sqrt_ieee_unscaled_raw(x0[j], h0, c0);   // (no +-0 / inf pass-through here: only the slow branch below can see such an argument)
+        const double xp = (px + delta) - ax[j], xm = (px - delta) - ax[j];
+        const double yp = (py + delta) - ay[j], ym = (py - delta) - ay[j];
+        const double zp = (pz + delta) - az[j], zm = (pz - delta) - az[j];
+        bool near = true;
+        if constexpr (GUARDED) near = x0[j] >= 1e-5 && x0[j] < 1e300;
+        if (near) {
+            // the six perturbed norms from the central one (device_math.h: sqrt_ieee_near_c — the same correctly rounded numbers)
+            jx[j] = scalar * ((d[j] - sqrt_ieee_near_c(range_sq_plain(xp, dy, dz), n[j], h0, c0)) - (d[j] - sqrt_ieee_near_c(range_sq_plain(xm, dy, dz), n[j], h0, c0)));
+            jy[j] = scalar * ((d[j] - sqrt_ieee_near_c(range_sq_plain(dx, yp, dz), n[j], h0, c0)) - (d[j] - sqrt_ieee_near_c(range_sq_plain(dx, ym, dz), n[j], h0, c0)));
+            jz[j] = scalar * ((d[j] - sqrt_ieee_near_c(range_sq_plain(dx, dy, zp), n[j], h0, c0)) - (d[j] - sqrt_ieee_near_c(range_sq_plain(dx, dy, zm), n[j], h0, c0)));
+        } else {   // a tag within millimetres of an anchor (or an estimate that has run away)
+            n[j] = (x0[j] == 0.0 || x0[j] == __builtin_inf()) ? x0[j] : n[j];
+            jx[j] = scalar * ((d[j] - range_norm_plain(xp, dy, dz)) - (d[j] - range_norm_plain(xm, dy, dz)));
+            jy[j] = scalar * ((d[j] - range_norm_plain(dx, yp, dz)) - (d[j] - range_norm_plain(dx, ym, dz)));
+            jz[j] = scalar * ((d[j] - range_norm_plain(dx, dy, zp)) - (d[j] - range_norm_plain(dx, dy, zm)));
+        }
+    }
+}
+
+// What `evaluate` computes, from numeric_ranges' (n, J).  Compiled with contraction off and every fused operation written out, so
+// that the roundings are this text's and not the instruction selector's: 1 + chi is fma(e, w e, 1) while sum chi adds the rounded
+// product (DESIGN.md §4 lists which is which, read off the machine code this replaced).
+template <int LPI, int APL>
+__device__ __forceinline__ System evaluate_numeric(const double (&n)[APL], const double (&jx)[APL], const double (&jy)[APL], const double (&jz)[APL],
+                                                   const double (&d)[APL], double (&w)[APL], const double gate) {
+    System s = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double prod = 1.0;
+    int kexp = 0;
+#pragma unroll
+    for (int j = 0; j < APL; ++j) {
+        const double e = d[j] - n[j];
+        w[j] = (fabs(e) > gate) ? 0.0 : w[j];  // |d_hat - d| > distance_outlier, localization.cpp:309 (gate = inf: off)
+        const double we = w[j] * e;
+        const double chi = e * we;
+        const double aux = __builtin_fma(e, we, 1.0);
+        const double rho1 = fast_rcp_1nr(aux);
+        const double wr = rho1 * w[j];
+        const double wjx = wr * jx[j], wjy = wr * jy[j], wjz = wr * jz[j];
+        s.h00 = __builtin_fma(wjx, jx[j], s.h00); s.h01 = __builtin_fma(wjx, jy[j], s.h01); s.h02 = __builtin_fma(wjx, jz[j], s.h02);
+        s.h11 = __builtin_fma(wjy, jy[j], s.h11); s.h12 = __builtin_fma(wjy, jz[j], s.h12); s.h22 = __builtin_fma(wjz, jz[j], s.h22);
+        s.b0 = __builtin_fma(-wjx, e, s.b0); s.b1 = __builtin_fma(-wjy, e, s.b1); s.b2 = __builtin_fma(-wjz, e, s.b2);
+        prod = prod * aux;
+        if (APL > 4 && j == 3) { kexp = __builtin_amdgcn_frexp_exp(prod); prod = __builtin_amdgcn_frexp_mant(prod); }
+        // (sum chi is only reported: one lane per tag adds the rounded product, several lanes per tag accumulate it by FMA — what each
+        //  mapping's machine code did before the arithmetic was pinned)
+        if constexpr (LPI == 1) s.chi = s.chi + chi; else s.chi = __builtin_fma(e, we, s.chi);
+    }
+    return combine_over_tag<LPI>(s, prod, kexp);
 }
 
 // (H + lambda I) x = b by LDL^T; false if not positive definite (g2o: Cholesky failure).
@@ -185,6 +261,7 @@ __device__ __forceinline__ bool solve3(const System& s, double lambda, double& x
     x0 = __builtin_fma(-l20, x2, __builtin_fma(-l10, x1, y0 * i0));
     return ok;
 }
+#pragma clang fp contract(fast)
 
 // float ranges of one epoch for this lane (16 / 8 / 4 B per lane, unit stride over tags)
 template <int APL>
@@ -342,6 +419,13 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const std::conditional
     }
     // the prior's loads retire here, not at their first use inside the loop (where the wait would sit on every pass)
     asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
+    // The numeric pass reads the anchors in two blocks (the vote's and the ranges').  As parts of the wide scalar loads that brought
+    // them, the register allocator gives each block a copy of its own, and the second set does not fit: 20 of the 24 were spilled to
+    // VGPR lanes and read back in every pass (40 v_readlane).  From here on each one is a scalar of its own, and one copy serves both.
+    if constexpr (LPI == 1 && JAC == 1) {
+#pragma unroll
+        for (int j = 0; j < APL; ++j) asm volatile("" : "+s"(ax[j]), "+s"(ay[j]), "+s"(az[j]));
+    }
 
     System cur = {1, 0, 0, 1, 0, 1, 0, 0, 0, 0, 0};
     double cur_chi = 0, last_chi = 0, lambda = 1.0, ni = 2.0;
@@ -352,6 +436,8 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const std::conditional
     bool waiting = false;
 
     while (__any(!exhausted)) {
+        // the pass's own f64 expressions (computeScale, the gain ratio, the trace) keep the roundings written here
+#pragma clang fp contract(off)
         const bool active = !exhausted && !waiting;
         // ---- step: (H + lambda I) x = b; first pass of an update evaluates the prior itself -------------------
         double x0, x1, x2;
@@ -360,7 +446,22 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const std::conditional
         const double tx = px + x0, ty = py + x1, tz = pz + x2;  // oplus: t += R dt with R = I
         // outlier gate armed only on the first pass of an update, after warm-up: an infinite threshold elsewhere
         const bool gate_now = active && init && (a.gate > 0.0) && (k >= a.gate_from_epoch);
-        const System tr = evaluate<LPI, APL, JAC>(tx, ty, tz, ax, ay, az, d, w, gate_now ? a.gate : DBL_MAX);
+        const double gate = gate_now ? a.gate : DBL_MAX;
+        System tr;
+        if constexpr (JAC == 0) {
+            tr = evaluate<LPI, APL>(tx, ty, tz, ax, ay, az, d, w, gate);
+        } else {
+            // One range vote per pass (evaluate_numeric).  Only active lanes vote: what an exhausted, waiting or dead lane
+            // evaluates is dropped by the `active` selects below, wherever its stale estimate sits.
+            double x0sq[APL], n[APL], jx[APL], jy[APL], jz[APL];
+            const bool off_range = range_vote<APL>(tx, ty, tz, ax, ay, az, x0sq) && active;
+            if (__builtin_expect(__any(off_range), 0)) {
+                numeric_ranges<APL, true>(tx, ty, tz, ax, ay, az, x0sq, d, n, jx, jy, jz);
+            } else {
+                numeric_ranges<APL, false>(tx, ty, tz, ax, ay, az, x0sq, d, n, jx, jy, jz);
+            }
+            tr = evaluate_numeric<LPI, APL>(n, jx, jy, jz, d, w, gate);
+        }
 
         // ---- per-lane LM bookkeeping (g2o OptimizationAlgorithmLevenberg::solve + SparseOptimizer::optimize) ---
         // Written as selects on per-lane predicates (one exec region only, for the 11-double system copy): a lone wave
@@ -368,9 +469,10 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const std::conditional
         const bool first = active && init;   // this pass evaluated the prior: computeActiveErrors + buildSystem, iteration 0
         const bool lm = active && !init;     // this pass was an LM trial
         const double temp_chi = ok2 ? tr.rchi : DBL_MAX;
-        double scale = x0 * __builtin_fma(lambda, x0, cur.b0) + x1 * __builtin_fma(lambda, x1, cur.b1) +
-                       x2 * __builtin_fma(lambda, x2, cur.b2);  // computeScale
-        scale += lm_scale_eps;
+        // computeScale: sum_j dx_j (lambda dx_j + b_j), accumulated by FMA
+        double scale = __builtin_fma(x2, __builtin_fma(lambda, x2, cur.b2),
+                                     __builtin_fma(x1, __builtin_fma(lambda, x1, cur.b1), x0 * __builtin_fma(lambda, x0, cur.b0)));
+        scale = scale + lm_scale_eps;
         const double rho = (cur_chi - temp_chi) * fast_rcp(scale);
         const bool accept = lm && (rho > 0.0) && (fabs(temp_chi) < DBL_MAX) && ok2;
         if (first || accept) {  // the trial's system is the next iteration's system (discardTop); first: it IS the system
@@ -388,8 +490,10 @@ __global__ void __launch_bounds__(256) snapshot_lm_kernel(const std::conditional
         const bool end_iter = lm && !((rho < 0.0) && (q < lm_max_trials));
         it = first ? 0 : it + (end_iter ? 1 : 0);
         // no active edge ("0 vertices to optimize") or nothing to iterate; LM: Terminate (10 failed trials or rho == 0) or done
-        const bool finished = (first && ((a.iterations <= 0) || !((tr.h00 + tr.h11 + tr.h22) > 0.0))) ||
-                              (end_iter && ((q == lm_max_trials) || (rho == 0.0) || (it >= a.iterations)));
+        // (`&` and `|`: every term is evaluated, so nothing here becomes a branch around the trace's two additions)
+        const bool no_system = (a.iterations <= 0) | !((tr.h00 + tr.h11 + tr.h22) > 0.0);
+        const bool lm_done = (q == lm_max_trials) | (rho == 0.0) | (it >= a.iterations);
+        const bool finished = (first & no_system) | (end_iter & lm_done);
         q = end_iter ? 0 : q;
         init = active ? false : init;
 
