@@ -331,9 +331,13 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *                      poses; under option "tree" = 0 or 2; below TREE's batch threshold; with endpoint-1 lever arms or a table of full
  *                      information matrices; on a handle with nv_max > 64.  loc_window_upload_dev does not group (such a batch solves on the
  *                      general kernel), and covariances of such a batch are served as without the option (the envelope pass under
- *                      "covariance_general", else LOC_ERR_UNSUPPORTED).  Measured at 16 384 x 64 poses: the solve 3.5 ... 4.8 times faster than on
+ *                      "covariance_general", else LOC_ERR_UNSUPPORTED) unless option "forest_groups_covariance" is 1 as well.  Measured at 16 384 x 64 poses: the solve 3.5 ... 4.8 times faster than on
  *                      the general kernel for 1 ... 16 384 groups; the upload 3 ... 7 ms slower up to 256 groups and 46 ms slower (102 MB of
  *                      schedule tables) with a topology per window — there the option pays from the fourth resident solve on (README).
+ *   "forest_groups_covariance"  0 (default) / 1: with "forest_groups" = 1, loc_window_covariance_* and loc_window_joint_covariance_* serve a
+ *                      batch of forest windows of differing topologies on the forest pass, one wave per window on the schedule of the window's
+ *                      group (see there).  0, or "forest_groups" = 0: every call takes the pass it took without the option, bit for bit.  Looked
+ *                      at per call; a resident batch that was refused, or held by the envelope pass, is classified again after a change.
  *   "upload_dev_structures"  0 (default) / 1: loc_window_upload_dev also takes the ARROWHEAD and FOREST verdicts on the device (see there), so
  *                      that such a batch runs on LOC_WINDOW_KERNEL_ARROW3 / _TREE and their covariance passes exactly as after loc_window_upload
  *                      of the same arrays; read at upload time.  0: loc_window_upload_dev does exactly what it did without the option.
@@ -425,7 +429,15 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
  *     the chain threshold where loc_window_set_chain_threshold lowered it: 1 serves a single window), every window the same counts and index
  *     tables, 2 <= nv <= 64, and the pose-to-pose edges form a forest (several edges per pair, either direction, several trees, isolated
  *     poses).  Always 6x6 blocks.  A tree that no range, prior or lever arm ties to the world is singular (LOC_ERR_SINGULAR for its window);
- *   - with loc_window_set_option(w, "covariance_general", 1) — default 0: the three tests above and nothing else, bit for bit — ANY batch the
+ *   - forests of DIFFERING topologies (nv_max <= 64), only after the one-topology test has declined the batch and only with options
+ *     "forest_groups" and "forest_groups_covariance" both 1, iff the handle would solve the batch on LOC_WINDOW_KERNEL_TREE_GROUPS: option "tree"
+ *     neither 0 nor 2, n at least the forest threshold, no table of full information matrices, every window a forest of 2 <= nv <= 64 poses with
+ *     at most one EdgeSE3 per pair of poses.  The windows are grouped by topology (anchor numbers and robust flags do not count) and every window
+ *     is computed by the forest pass's arithmetic on its group's schedule: the bits a one-topology batch of that group's windows gets.  The
+ *     launch's LDS is the largest group's: one 64-pose group puts every window of the batch at 60 KB (two windows per CU).
+ *     loc_window_covariance_resident: a batch that loc_window_upload put on the grouped solve path walks the groups block already on the device
+ *     (no copy-back, asynchronous); any other resident batch is classified by the first call as below and builds a block of its own;
+ *   - with loc_window_set_option(w, "covariance_general", 1) — default 0: the tests above and nothing else, bit for bit — ANY batch the
  *     tests above leave: chains and forests of more than 64 poses, ragged or mixed batches (another graph in every window), 6-DoF arrowheads,
  *     windows with loops (an EdgeSE3 or a range that closes a cycle), any nv_max the handle takes.  Batches the tests above take keep their
  *     kernels and their bits.  Always 6x6 blocks (a translation-only window gets its rotation bits from the exactly-zero rule).  One workgroup
@@ -525,6 +537,13 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream,
                                          void* cov_dev, void* mask_dev, void* status_dev, void* cross_dev);
 int loc_window_joint_covariance_plan(const loc_window_caps* caps, int64_t n, const int32_t* counts, const int32_t* r_idx, const int32_t* s_idx,
                                      int32_t npair_max, const int32_t* pair_counts, const int32_t* pairs, int64_t* blocks_max, size_t* workspace_bytes);
+/* The pass that served the LAST loc_window_covariance_* / loc_window_joint_covariance_* call of this handle that launched, host path or
+ * resident (a refused call leaves it as it was; LOC_WINDOW_COV_NONE before the first): under option "covariance_general" a caller cannot
+ * tell otherwise whether a structured pass or the envelope pass computed a batch. */
+enum { LOC_WINDOW_COV_NONE = 0, LOC_WINDOW_COV_CHAIN3 = 1 /* chains, 3x3 blocks */, LOC_WINDOW_COV_CHAIN6 = 2 /* chains, 6x6 blocks */, LOC_WINDOW_COV_ARROW = 3,
+       LOC_WINDOW_COV_FOREST = 4 /* forests of one shared topology */, LOC_WINDOW_COV_ENVELOPE = 5 /* option "covariance_general" */,
+       LOC_WINDOW_COV_FOREST_GROUPS = 6 /* forests of differing topologies: options "forest_groups" + "forest_groups_covariance" */ };
+int loc_window_last_covariance_kind(const loc_window* w, int32_t* kind);
 /* kernel time of the last covariance, marginal-prior or slide launch(es) of this handle (HIP events on its stream; a resident launch is
  * waited for), milliseconds */
 int loc_window_last_covariance_ms(loc_window* w, double* ms);

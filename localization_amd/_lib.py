@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = [
     "loc_window_last_kernel_ms", "loc_window_set_endpoint1_offsets", "loc_window_set_prior_information", "loc_window_set_jacobian", "loc_window_set_ordering", "loc_window_set_chain_threshold", "loc_window_last_kernel_kind", "loc_window_set_option", "loc_window_last_host_timing", "loc_window_forest_groups", "loc_window_upload", "loc_window_upload_dev",
     "loc_window_solve_resident", "loc_window_download", "loc_window_poses_device", "loc_window_result_device",
     "loc_window_timing_begin", "loc_window_timing_end",
-    "loc_window_covariance_host", "loc_window_covariance_resident", "loc_window_last_covariance_ms", "loc_window_covariance_plan",
+    "loc_window_covariance_host", "loc_window_covariance_resident", "loc_window_last_covariance_ms", "loc_window_last_covariance_kind", "loc_window_covariance_plan",
     "loc_window_marginal_prior_host", "loc_window_joint_covariance_host", "loc_window_joint_covariance_resident", "loc_window_joint_covariance_plan",
     "loc_window_slide_resident", "loc_window_slide_resident_dev", "loc_window_slide_plain_resident_dev", "loc_window_download_tables",
     "loc_window_edge_chi2_host", "loc_window_edge_chi2_resident", "loc_window_prune_resident",
@@ -115,6 +115,7 @@ def lib():
     L.loc_window_set_chain_threshold.argtypes = [vp, C.c_int64]
     L.loc_window_last_kernel_kind.argtypes = [vp, ip]
     L.loc_window_last_host_timing.argtypes = [vp, dp]
+    L.loc_window_last_covariance_kind.argtypes = [vp, ip]
     L.loc_window_forest_groups.argtypes =[vp, ip, C.POINTER(C.c_int64)]
     L.loc_window_upload.argtypes = [vp, C.c_int64, ip, dp, ip, dp, ip, dp, ip, dp]
     L.loc_window_upload_dev.argtypes = [vp, vp, C.c_int64] + [vp] * 9

@@ -33,6 +33,8 @@ struct Resident {
     int min_anchors = 0;            // anchors the batch references (loc_window_set_anchors may not shrink below it)
     bool solved = false;            // a resident solve has run since the upload (loc_window_download has something to fetch)
     CovKind cov = CovKind::None;    // the batch's covariance pass; Unclassified: the first covariance call finds out
+    bool groups_no_chain = false;   // loc_window_upload put the batch on the grouped solve path (slot[1].aux's groups block is on the device) and found no chain in any
+                                    // edge order: under options "forest_groups" + "forest_groups_covariance" its covariance pass walks that block (resident_groups_covariance)
     long long env_switches = 0;     // cov_switches() when it was classified: a change of the switches the structured tests read classifies an Envelope batch again
     // joint covariance calls: the counts as uploaded (the pair check needs every window's nv) and, once the envelope pass holds the batch,
     // its pose-to-pose index tables (the pairs enlarge the envelope)
@@ -63,8 +65,9 @@ struct loc_window {
     // from its upload on (a host-path call in between must not disturb it).
     struct BatchSlot {
         locamd::WinAux aux;       // the solve's host-built tables.  The host path's topology cache and the resident solve rely on them: no covariance call writes here
-        // forest batches (forest_covariance_kernel.hip): the schedule the covariance pass builds itself — slot[0]'s is kept with the hash of
-        // the structure it was built for (cov_sched), slot[1]'s is for a resident batch no solve classified as a forest.
+        // forest batches (forest_covariance_kernel.hip): the schedule — or, for windows of differing topologies, the groups block — the covariance
+        // pass builds itself: slot[0]'s is kept with the hash of the structure it was built for (cov_sched), slot[1]'s is for a resident
+        // batch no solve classified as a forest.
         // arrowhead batches (arrow_covariance_kernel.hip): cov_aux takes build_arrow_aux's structure test (never aux: the solve's packed tables stay as they are)
         locamd::WinAux cov_aux;
         double* d_cov_ws = nullptr;   // the arrowhead pass's HBM workspace (records, B, Y, the poses' edge lists), allocated on first use and grown on demand
@@ -84,6 +87,7 @@ struct loc_window {
     long long n_pinfo = 0;          // instances the table describes: a call with more is refused
     Resident res;
     int last_kind = -1;             // LOC_WINDOW_KERNEL_* of the last launch
+    int last_cov_kind = LOC_WINDOW_COV_NONE;   // loc_window_last_covariance_kind: the pass of the last covariance call that launched
     hipEvent_t resident_done = nullptr;  // recorded after every resident launch on the stream it ran on: whatever touches the shared
     bool resident_inflight = false;      // device state waits for THIS (the caller's stream is not kept: it may be destroyed any time)
     locamd::DispatchOpts opt;       // the kernel-selection switches (window_dispatch.h)
@@ -196,6 +200,9 @@ int loc_window_create(loc_window** out, int32_t device, int64_t batch, const loc
     auto alloc = [&](void** p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 8); };
     for (int t = 0; t < locamd::kWindowTables && e == hipSuccess; ++t) e = alloc(&w->dev.t[t], B * locamd::table_bytes(w->caps, t));
     if (e != hipSuccess || (e = alloc((void**)&w->d_anchors, na * 3 * sizeof(double))) != hipSuccess ||
+        // (the solve kernels write the pose slots a window uses: what lies behind a window's nv in the output array reads as 0 after a
+        //  download, on every handle alike, not as whatever a recycled allocation held)
+        (e = hipMemset(w->dev.t[kPoses], 0, B * locamd::table_bytes(w->caps, kPoses))) != hipSuccess ||
         (e = alloc((void**)&w->d_result, B * kResultBytes)) != hipSuccess ||
         (global_a && (e = hipMalloc((void**)&w->d_workspace, B * locamd::window_workspace_doubles(w->caps) * sizeof(double))) != hipSuccess) ||
         (e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -526,7 +533,21 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
     if (k == "chain_min_batch") { o.chain_min = value; return LOC_OK; }
     if (k == "arrow3") { if (value < -1 || value > 1) return locamd_fail(LOC_ERR_INVALID, "set_option arrow3: -1, 0 or 1"); o.arrow3 = (int)value; w->topo_cache.valid = false; return LOC_OK; }
     if (k == "tree") { if (value != -1 && value != 0 && value != 2) return locamd_fail(LOC_ERR_INVALID, "set_option tree: -1, 0 or 2"); o.tree = (int)value; w->topo_cache.valid = false; return LOC_OK; }
-    if (k == "forest_groups") { w->topo_cache.valid = false; return flag(o.forest_groups); }   // (read by the structure test: loc_window_solve_host, loc_window_upload)
+    if (k == "forest_groups") {   // (read by the structure test: loc_window_solve_host, loc_window_upload)
+        w->topo_cache.valid = false;
+        const bool before = o.forest_groups;
+        const int rc = flag(o.forest_groups);
+        // (with "forest_groups_covariance" 1 it is one of the two switches of the grouped covariance pass: a resident batch that was refused is classified again)
+        if (rc == LOC_OK && before != o.forest_groups && o.forest_groups_cov && w->res.n > 0 && w->res.cov == CovKind::None) w->res.cov = CovKind::Unclassified;
+        return rc;
+    }
+    if (k == "forest_groups_covariance") {
+        const bool before = o.forest_groups_cov;
+        const int rc = flag(o.forest_groups_cov);
+        // as "covariance_general": a resident batch the other value refused, or left to the envelope pass, is classified again by the next covariance call
+        if (rc == LOC_OK && before != o.forest_groups_cov && w->res.n > 0 && (w->res.cov == CovKind::None || w->res.cov == CovKind::Envelope)) w->res.cov = CovKind::Unclassified;
+        return rc;
+    }
     if (k == "wave3") return flag(o.wave3);
     if (k == "wave6") return flag(o.wave6);
     if (k == "chain3") return flag(o.chain3);
@@ -748,8 +769,14 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
     const int topology = locamd::batch_topology(c, w->opt, w->fits, w->n_anchors, b, S.aux, nullptr).kind;
     if (topology == LOC_WINDOW_KERNEL_ARROW3) LOC_HIP(upload_arrow_aux(w, S, n, w->stream));
     if (topology == LOC_WINDOW_KERNEL_TREE) LOC_HIP(upload_tree_sched(w, S.aux, w->stream));
-    // (the grouped forest: its covariance pass is classified by the first covariance call, as any batch the structured passes may decline)
-    if (topology == LOC_WINDOW_KERNEL_TREE_GROUPS) LOC_HIP(upload_tree_sched(w, S.aux, w->stream, true, true));
+    // (the grouped forest: its covariance verdict stays open — the first covariance call takes it under the options as they are then; what
+    //  that call needs to walk the block just uploaded without a copy-back is noted here: the batch is no chain in any edge order)
+    if (topology == LOC_WINDOW_KERNEL_TREE_GROUPS) {
+        LOC_HIP(upload_tree_sched(w, S.aux, w->stream, true, true));
+        bool chain = false, single_pairs = false, se3_pairs = false;
+        locamd::chain_scan(c, b, false, chain, single_pairs, se3_pairs);
+        R.groups_no_chain = !chain;
+    }
     note_groups(w, S.aux, topology);
     R.min_anchors = locamd::max_anchor_referenced(c, n, counts, r_idx);
     R.counts.assign(counts, counts + (size_t)n * 4);
@@ -947,6 +974,12 @@ int loc_window_timing_end(loc_window* w, int32_t* n_launches, double* total_ms, 
     return w ? w->timer.end(w->device, n_launches, total_ms, avg_ms) : locamd_fail(LOC_ERR_INVALID, "timing_end");
 }
 
+int loc_window_last_covariance_kind(const loc_window* w, int32_t* kind) {
+    if (!w || !kind) return locamd_fail(LOC_ERR_INVALID, "null");
+    *kind = w->last_cov_kind;
+    return LOC_OK;
+}
+
 int loc_window_last_kernel_ms(loc_window* w, double* ms) {
     if (!w || !ms) return locamd_fail(LOC_ERR_INVALID, "null");
     *ms = w->last_ms;
@@ -956,10 +989,12 @@ int loc_window_last_kernel_ms(loc_window* w, double* ms) {
 // ---- marginal covariances (covariance_kernel.hip: chains; arrow_covariance_kernel.hip: arrowheads; forest_covariance_kernel.hip: forests) -------------------------------------------------------------------------------------
 #define LOC_COV_UNSUPPORTED ": every window must be a chain of <= 64 poses, or the batch an arrowhead that the handle solves on arrow3_lm_kernel (option arrow3), " \
                             "or a forest of one shared topology of <= 64 poses that the handle solves on a forest kernel (option tree, batch threshold), " \
+                            "or forests of differing topologies that the handle solves on the grouped forest kernel with options forest_groups and forest_groups_covariance both 1, " \
                             "or option covariance_general must be 1 (any structure and length, in the caller's pose order: the only pass for full-information priors); no endpoint-1 lever arms"
 
 // the pass of a batch of covariance_kind's `kind`; S: the batch's table sets and workspaces (a forest that loc_window_upload classified,
-// Forest, walks the resident solve's schedule slot[1].aux; ForestOwn the covariance's own, S.cov_aux)
+// Forest, walks the resident solve's schedule slot[1].aux; ForestOwn the covariance's own, S.cov_aux; ForestGroups / ForestGroupsOwn likewise
+// the groups block of the resident solve / of the covariance's own)
 // env_blocks: the envelope the workspace was sized for (a joint call's includes its pairs); pp: the pairs on the device, cross = nullptr for none
 static hipError_t launch_covariance(loc_window* w, loc_window::BatchSlot& S, CovKind kind, long long env_blocks, const locamd::WindowArgs& a, double* cov, int32_t* mask,
                                     int32_t* status, const locamd::CovPairs& pp, hipStream_t st) {
@@ -967,6 +1002,12 @@ static hipError_t launch_covariance(loc_window* w, loc_window::BatchSlot& S, Cov
     if (kind == CovKind::Envelope) return locamd::launch_window_envelope_covariance(a, S.d_env_ws, env_blocks, cov, mask, status, pp, st);
     if (kind == CovKind::Forest) return locamd::launch_window_forest_covariance(a, w->slot[1].aux.tsched, cov, mask, status, pp, st);
     if (kind == CovKind::ForestOwn) return locamd::launch_window_forest_covariance(a, S.cov_aux.tsched, cov, mask, status, pp, st);
+    if (kind == CovKind::ForestGroups || kind == CovKind::ForestGroupsOwn) {
+        const locamd::WinAux& A = kind == CovKind::ForestGroups ? w->slot[1].aux : S.cov_aux;
+        if (A.n_groups <= 0 || !A.d_groups) return hipErrorInvalidValue;
+        const locamd::TreeGroups g{A.d_groups, A.d_groups + A.groups_of_at, A.d_groups + A.groups_tab_at, A.n_groups};
+        return locamd::launch_window_forest_covariance_groups(a, g, A.h_groups.data(), cov, mask, status, pp, st);
+    }
     return locamd::launch_window_covariance(a, kind == CovKind::Chain3, cov, mask, status, pp, st);
 }
 // the pair arguments of a joint call as given (npair_max = 0: none, the plain call): 0, or the error
@@ -1045,18 +1086,20 @@ int loc_window_joint_covariance_host(loc_window* w, int64_t n, const int32_t* co
     if (kind == CovKind::Arrow) LOC_HIP(grow_cov_workspace(w, S, n, S.cov_list_cap));
     if (kind == CovKind::Envelope) LOC_HIP(grow_env_workspace(w, S, n, S.env_blocks));
     if (v.need_upload) {
-        LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false));
+        LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false, kind == CovKind::ForestGroupsOwn));
         w->cov_sched.valid = true;
     }
     if (int rc = flush_anchors(w)) return rc;
     const locamd::BlockLayout L = locamd::covariance_layout(c, (size_t)n, (size_t)npair_max);
     // (a plain call's block has no piece 3 .. 5, whatever the caller passed for them)
-    return staged_call(w, L, b, {{joint ? pair_counts : nullptr, 4}, {joint ? pairs : nullptr, 5}}, {{cov, 0}, {mask, 1}, {status, 2}, {joint ? cross : nullptr, 3}}, "launch_window_covariance",
+    const int rc = staged_call(w, L, b, {{joint ? pair_counts : nullptr, 4}, {joint ? pairs : nullptr, 5}}, {{cov, 0}, {mask, 1}, {status, 2}, {joint ? cross : nullptr, 3}}, "launch_window_covariance",
                        [&](const locamd::WindowArgs& a, char* d, hipStream_t st) {
         const locamd::CovPairs pp = joint ? locamd::CovPairs{(const int32_t*)(d + L.pre[4]), (const int32_t*)(d + L.pre[5]), (double*)(d + L.pre[3]), npair_max}
                                           : locamd::CovPairs{nullptr, nullptr, nullptr, 0};
         return launch_covariance(w, S, kind, S.env_blocks, a, (double*)(d + L.pre[0]), (int32_t*)(d + L.pre[1]), (int32_t*)(d + L.pre[2]), pp, st);
     });
+    if (rc == LOC_OK) w->last_cov_kind = locamd::cov_public_kind(kind);
+    return rc;
 }
 
 // ---- the marginal prior of a dropped pose (marginal_prior_kernel.hip) ------------------------------------------------------------
@@ -1103,6 +1146,10 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
     LOC_HIP(hipSetDevice(w->device));
     loc_window::BatchSlot& S = w->slot[1];
     if (locamd::cov_stale(w->opt, w->fits, R.n, R.cov, R.env_switches)) R.cov = CovKind::Unclassified;
+    if (R.cov == CovKind::Unclassified) {   // (a batch on the grouped solve path: the block of its upload, no copy-back)
+        R.cov = locamd::resident_groups_covariance(w->opt, w->fits, R.n, R.groups_no_chain);
+        if (R.cov != CovKind::Unclassified) R.env_switches = locamd::cov_switches(w->opt);
+    }
     if (R.cov == CovKind::Unclassified && !w->opt.has_off1) {
         // first call on an upload no solve kernel classified as a chain: the uploaded tables come back once and are scanned on the host
         if (int rc = wait_resident(w)) return rc;
@@ -1115,7 +1162,7 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         LOC_HIP(copy_tables(c, N, dst, uploaded_tables(w).t, hipMemcpyDeviceToHost, nullptr));
         const locamd::HostBatch b{(int64_t)N, poses.data(), counts.data(), rval.data(), pval.data(), nullptr, ridx.data(), pidx.data(), sidx.data()};
         const locamd::CovVerdict v = locamd::covariance_kind(c, w->opt, w->fits, w->n_anchors, b, locamd::PairTables{0, nullptr, nullptr}, S.cov_aux, nullptr);
-        if (v.need_upload) LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false));
+        if (v.need_upload) LOC_HIP(upload_tree_sched(w, S.cov_aux, w->stream, false, v.kind == CovKind::ForestGroupsOwn));
         R.cov = v.kind;
         S.cov_list_cap = v.list_cap; S.env_blocks = v.env_blocks;
         R.env_switches = locamd::cov_switches(w->opt);
@@ -1153,13 +1200,15 @@ int loc_window_joint_covariance_resident(loc_window* w, void* hip_stream, int32_
         std::memcpy(h + L.pre[1], pairs_host, L.len[1]);
         pp = locamd::CovPairs{(const int32_t*)(w->pairs.d + L.pre[0]), (const int32_t*)(w->pairs.d + L.pre[1]), (double*)cross_dev, npair_max};
     }
-    return resident_bracket(w, st, Timing::Covariance, [&](hipStream_t st) {
+    const int rc = resident_bracket(w, st, Timing::Covariance, [&](hipStream_t st) {
         if (joint) LOC_HIP(w->pairs.send(L.end, st));   // (after the bracket's wait: an earlier joint launch on another stream has finished reading the table)
         return (int)LOC_OK;
     }, [&](hipStream_t st) {
         const locamd::WindowArgs a = window_args(w, w->dev, R.n, nullptr, w->d_anchors, nullptr);
         return launched(launch_covariance(w, S, R.cov, env_blocks, a, (double*)cov_dev, (int32_t*)mask_dev, (int32_t*)status_dev, pp, st), "launch_window_covariance");
     });
+    if (rc == LOC_OK) w->last_cov_kind = locamd::cov_public_kind(R.cov);
+    return rc;
 }
 
 int loc_window_covariance_resident(loc_window* w, void* hip_stream, void* cov_dev, void* mask_dev, void* status_dev) {

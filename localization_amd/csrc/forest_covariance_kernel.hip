@@ -16,8 +16,13 @@
 //   * the two sweeps node after node in schedule order (cov_eliminate_block / cov_back_substitute_block of cov_block_device.h, the
 //     chain pass's steps with "parent" in place of "next pose"): a parent collects from its children in schedule order.
 // Every window of the batch has the schedule's counts and index tables (the host compared them), so the loops below are uniform.
+//
+// Windows of DIFFERING topologies (option "forest_groups_covariance") run the same kernel with one schedule per group of windows of one
+// topology: SCHED = TreeGroups, wave_sched of tree_sched_device.h, instantiated in forest_covariance_groups_kernel.hip.  nv, nr, np, ns and the
+// LDS offsets are then per-wave values (uniform over the wave: one workgroup of one wave per window), everything else is shared word for word.
 #include "cov_block_device.h"
 #include "window_kernel.h"
+#include "tree_sched_device.h"
 
 namespace locamd {
 
@@ -25,11 +30,12 @@ namespace {
 
 extern __shared__ double fclds[];
 
-template <int JAC, bool JOINT>
-__global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs a, const TreeSched ts, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
+template <int JAC, bool JOINT, class SCHED>
+__global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs a, const SCHED sched, double* cov, int32_t* mask, int32_t* status, const CovPairs pp) {
     constexpr int D = 6, DD = 36, RS = 13;
     const int lane = threadIdx.x;
     const long long inst = blockIdx.x;
+    const TreeSched& ts = wave_sched(sched, a, inst);
     const WindowCaps& cp = a.caps;
     const int nvm = cp.nv_max;
     const int nv = ts.nv, nr = ts.nr, np = ts.np, ns = ts.ns;
@@ -136,29 +142,44 @@ __global__ void __launch_bounds__(64) forest_covariance_kernel(const WindowArgs 
     if (JOINT) cov_store_cross<D>(Hd, Ho, Kb, mk, nv, ok, lane, r, c, ent, inst, pp, [ps](int v) { return ps[v]; });
 }
 
-template <int JAC, bool JOINT>
-hipError_t launch_forest_cov_j(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC, JOINT>>((int)kCovMaxLds);
+template <int JAC, bool JOINT, class SCHED>
+hipError_t launch_forest_cov_j(const WindowArgs& a, const SCHED& s, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<&forest_covariance_kernel<JAC, JOINT, SCHED>>((int)kCovMaxLds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((forest_covariance_kernel<JAC, JOINT>), dim3((unsigned)a.B), dim3(64), lds, stream, a, ts, cov, mask, status, pp);
+    hipLaunchKernelGGL((forest_covariance_kernel<JAC, JOINT, SCHED>), dim3((unsigned)a.B), dim3(64), lds, stream, a, s, cov, mask, status, pp);
     return hipGetLastError();
 }
-template <int JAC>
-hipError_t launch_forest_cov_t(const WindowArgs& a, const TreeSched& ts, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
-    return pp.cross ? launch_forest_cov_j<JAC, true>(a, ts, lds, cov, mask, status, pp, stream) : launch_forest_cov_j<JAC, false>(a, ts, lds, cov, mask, status, pp, stream);
+template <class SCHED>
+hipError_t launch_forest_cov(const WindowArgs& a, const SCHED& s, size_t lds, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
+    if (a.jacobian) return pp.cross ? launch_forest_cov_j<1, true>(a, s, lds, cov, mask, status, pp, stream) : launch_forest_cov_j<1, false>(a, s, lds, cov, mask, status, pp, stream);
+    return pp.cross ? launch_forest_cov_j<0, true>(a, s, lds, cov, mask, status, pp, stream) : launch_forest_cov_j<0, false>(a, s, lds, cov, mask, status, pp, stream);
 }
 
 }  // namespace
 
+// (one instantiation family per translation unit, as tree_wave_kernel.hip's: forest_covariance_groups_kernel.hip includes this file for
+//  SCHED = TreeGroups, so that the four TreeSched kernels stay alone in their module and keep their machine code)
+#ifndef LOCAMD_FOREST_COV_GROUPS
 size_t window_forest_covariance_lds_bytes(const TreeSched& ts) { return forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes; }
 
 hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream) {
     if (a.B <= 0) return hipSuccess;
     // (the LDS blocks are indexed by pose slot and the tables by edge number: the schedule must be the batch's own)
-    if (ts.nv < 2 || ts.nv > 64 || ts.nv > a.caps.nv_max || ts.nr > a.caps.nr_max || ts.np > a.caps.np_max || ts.ns > a.caps.ns_max) return hipErrorInvalidValue;
-    if (!cov_forest_fits(ts.nv, ts.np > 0, ts.ns > 0)) return hipErrorInvalidValue;
-    const size_t lds = forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes;
-    return a.jacobian ? launch_forest_cov_t<1>(a, ts, lds, cov, mask, status, pp, stream) : launch_forest_cov_t<0>(a, ts, lds, cov, mask, status, pp, stream);
+    if (!forest_cov_sizes_ok(ts, a.caps)) return hipErrorInvalidValue;
+    return launch_forest_cov(a, ts, forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes, cov, mask, status, pp, stream);
 }
+#else
+// Every group's sizes are held to the one-topology launcher's bounds on the host's copy of the headers; the launch's dynamic LDS is the
+// largest group's layout and every wave uses its own group's offsets inside it.  KNOWN LIMIT: one 64-pose group in the batch puts every
+// window of the launch at that group's 60 KB (two windows per CU), whatever its own length.
+hipError_t launch_window_forest_covariance_groups(const WindowArgs& a, const TreeGroups& g, const int32_t* host_hdr, double* cov, int32_t* mask, int32_t* status,
+                                                  const CovPairs& pp, hipStream_t stream) {
+    if (a.B <= 0) return hipSuccess;
+    if (!g.hdr || !g.sched_of || !g.tables) return hipErrorInvalidValue;
+    const size_t lds = forest_cov_groups_lds_bytes(host_hdr, g.n_groups, a.caps);
+    if (lds == 0) return hipErrorInvalidValue;
+    return launch_forest_cov(a, g, lds, cov, mask, status, pp, stream);
+}
+#endif
 
 }  // namespace locamd

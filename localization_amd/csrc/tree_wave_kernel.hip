@@ -5,7 +5,7 @@
 // kernel here; the elimination schedule (parent, height, children and edge lists per pose slot) is built once per batch by the host
 // (capi_window.cpp: build_tree_sched) and shared by every window.
 // Windows of DIFFERING topologies — cut from different robots, or at different phases of the key cadence of localization.cpp:254-290 — run the
-// same kernel with one schedule per group of windows of one topology (option "forest_groups"; SCHED = TreeGroups, wave_sched below;
+// same kernel with one schedule per group of windows of one topology (option "forest_groups"; SCHED = TreeGroups, wave_sched of tree_sched_device.h;
 // instantiated in tree_wave_groups_kernel.hip).
 //
 // tree_lm_kernel (tree_kernel.hip) walks a window's 64 nodes one after the other in one lane.  Here the 64 nodes are the 64 lanes:
@@ -34,6 +34,7 @@
 #include "se3_edge_device.h"
 #include "lm_damping.h"
 #include "window_layouts.h"
+#include "tree_sched_device.h"
 
 namespace locamd {
 namespace {
@@ -279,24 +280,7 @@ __device__ __forceinline__ void wave_node_edges(const WindowArgs& a, const TreeS
     }
 }
 
-// The schedule of the wave's window.  SCHED = TreeSched: the one schedule of the batch, whose r_idx / s_idx sections are every window's rows.
-// SCHED = TreeGroups (option "forest_groups"): windows of differing topologies, cut from different robots or at different phases of the key
-// cadence of Localization::addPoseEdge (localization.cpp:254-290) — the wave reads its window's group and that group's header (wave-uniform
-// loads through blockIdx.x), binds the schedule's pointers from the group's table with the host's own function (tree_sched_bind), and points
-// r_idx / s_idx at the window's OWN rows: a group's windows share parents, heights and edge lists, not anchor numbers or robust flags, and
-// every index look-up of the kernel — the prologue's, the generic loops', the anchor number, the robust flag — goes through these two
-// pointers.  nv, nu, nlev, nroots are then per-wave values; lanes >= nv idle as before.
-__device__ __forceinline__ const TreeSched& wave_sched(const TreeSched& ts, const WindowArgs&, long long) { return ts; }
-__device__ __forceinline__ TreeSched wave_sched(const TreeGroups& g, const WindowArgs& a, long long inst) {
-    const int32_t* h = g.hdr + (size_t)g.sched_of[inst] * kTreeGroupHdr;
-    TreeSched ts;
-    tree_group_sizes(ts, h);
-    tree_sched_bind(ts, g.tables + h[10]);
-    ts.r_idx = a.r_idx + (size_t)inst * a.caps.nr_max * 2;
-    ts.s_idx = a.s_idx + (size_t)inst * a.caps.ns_max * 4;
-    return ts;
-}
-
+// (the schedule of the wave's window, wave_sched: tree_sched_device.h — forest_covariance_kernel.hip binds its schedule with the same function)
 template <int JAC, class SCHED>
 __global__ void __launch_bounds__(64, 1) tree_wave_kernel(const WindowArgs a, const SCHED sched) {
     __shared__ double sv_lds[48 * 64];    // [entry][lane]: the EdgeSE3 record of the lane's node (Z^-1 as R t, information 6x6)

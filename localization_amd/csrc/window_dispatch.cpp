@@ -44,6 +44,10 @@ DispatchFits dispatch_fits(const WindowCaps& c) {
 // wave-per-window kernel keeps everything in LDS and is the better choice
 bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f) { return o.arrow3 >= 0 ? o.arrow3 == 1 : f.nv_max > 64; }
 
+bool forest_groups_wanted(const DispatchOpts& o, const WindowCaps& c, int64_t n) {
+    return o.forest_groups && o.tree != 0 && o.tree != 2 && n >= tree_min_batch(o) && c.nv_max <= 64 && !general_only(o);
+}
+
 // what the batch qualifies for BY ITS STRUCTURE: LOC_WINDOW_KERNEL_GENERAL, _CHAIN (block-tridiagonal, 6-DoF), _CHAIN3, _WAVE6, _WAVE6S,
 // _ARROW3, _TREE or _TREE_GROUPS.  aux: the set of host-built tables that ARROW3 (row order, packed edge records) / TREE (the schedule) fill.
 // Host-path calls (tc != nullptr; the resident batch passes none) keep the structural verdict of the previous batch in *tc: the same counts
@@ -88,7 +92,7 @@ Topology batch_topology(const WindowCaps& c, const DispatchOpts& o, const Dispat
         // option "forest_groups": forest windows of differing topologies, only after build_tree_sched has declined the batch — a one-topology batch
         // takes the path above.  Never under option "tree" = 2 (tree_lm_kernel has no per-window-schedule twin) or on a handle of longer windows.
         // On a hit aux's groups and tables are still those built for this structure (hash_structure covers the full index tables).
-        if (o.forest_groups && o.tree != 2 && c.nv_max <= 64) {
+        if (forest_groups_wanted(o, c, b.n)) {   // (under general_only build_tree_groups refuses the batch itself, as build_tree_sched above)
             if (hit && tc->groups_tried) {
                 if (tc->groups_ok) return {LOC_WINDOW_KERNEL_TREE_GROUPS, hit};
             } else {
@@ -172,6 +176,10 @@ static int pick_plain(const DispatchOpts& o, const DispatchFits& f, int64_t n, i
 //    tree_min_batch, build_tree_sched's verdict) — forest_covariance_kernel.hip on the schedule built into `own`, which the caller then sends
 //    to the device (need_upload).  keyed (the host path): the set is kept with the hash of the structure it was built for, and a batch of
 //    the same structure reuses it, device copy included.
+// 3b. only after build_tree_sched has declined: ForestGroupsOwn when options "forest_groups" and "forest_groups_covariance" are both 1 and the
+//    handle would solve the batch on the grouped kernel (forest_groups_wanted, build_tree_groups' verdict: no window with nv < 2, no cycle, at
+//    most one EdgeSE3 per pair) — forest_covariance_groups_kernel.hip on the groups block built into `own` (need_upload).  keyed: the key
+//    remembers WHICH of the two table sets it holds; a hit returns that kind, and a grouped one only while the two options still hold.
 static CovVerdict structured_covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b,
                                              WinAux& own, SchedKey* keyed) {
     const CovVerdict none{CovKind::None, false, 0, 0};
@@ -194,23 +202,33 @@ static CovVerdict structured_covariance_kind(const WindowCaps& c, const Dispatch
         return {CovKind::Arrow, false, own.arrow_list_cap, 0};
     if (!small) return none;
     if (o.tree == 0 || b.n < tree_min_batch(o)) return none;
+    const bool groups = o.forest_groups_cov && forest_groups_wanted(o, c, b.n);
     if (keyed) {
         const unsigned long long key = hash_structure(c, general_only(o), b);
-        if (keyed->valid && keyed->key == key && keyed->n == b.n) return {CovKind::ForestOwn, false, 0, 0};
+        if (keyed->valid && keyed->key == key && keyed->n == b.n) {
+            if (keyed->kind == CovKind::ForestOwn) return {CovKind::ForestOwn, false, 0, 0};
+            // (a groups block: build_tree_sched declined this structure when it was built, and does so again)
+            if (keyed->kind == CovKind::ForestGroupsOwn) return groups ? CovVerdict{CovKind::ForestGroupsOwn, false, 0, 0} : none;
+        }
         keyed->valid = false;   // (valid again once the caller has uploaded the new tables)
-        keyed->key = key; keyed->n = b.n;
+        keyed->key = key; keyed->n = b.n; keyed->kind = CovKind::None;
     }
-    if (!build_tree_sched(c, general_only(o), b, own)) return none;
-    return {CovKind::ForestOwn, true, 0, 0};
+    if (build_tree_sched(c, general_only(o), b, own)) {
+        if (keyed) keyed->kind = CovKind::ForestOwn;
+        return {CovKind::ForestOwn, true, 0, 0};
+    }
+    if (!groups || !build_tree_groups(c, general_only(o), b, own)) return none;
+    if (keyed) keyed->kind = CovKind::ForestGroupsOwn;
+    return {CovKind::ForestGroupsOwn, true, 0, 0};
 }
 
 long long cov_switches(const DispatchOpts& o) {
     const long long mn = tree_min_batch(o);
     return (((long long)(o.arrow3 + 1) << 4 | (long long)(o.tree + 1)) ^ ((mn > (1ll << 40) ? (1ll << 40) : mn) << 8)) | (o.has_pinfo ? 1ll << 60 : 0) |
-           (o.pinfo_structured ? 1ll << 59 : 0) | (o.has_pinfo && o.pinfo_translation ? 1ll << 58 : 0);
+           (o.pinfo_structured ? 1ll << 59 : 0) | (o.has_pinfo && o.pinfo_translation ? 1ll << 58 : 0) | (o.forest_groups && o.forest_groups_cov ? 1ll << 57 : 0);
 }
 
-// 4. option "covariance_general" = 1: whatever the three tests above leave (no endpoint-1 lever arms) is Envelope —
+// 4. option "covariance_general" = 1: whatever the tests above leave (no endpoint-1 lever arms) is Envelope —
 //    envelope_covariance_kernel.hip in the caller's pose order; the batch's largest envelope goes to the verdict's env_blocks.
 //    pt: the pairs of a joint call count as edges of that envelope (none: the plain envelope).
 CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, const PairTables& pt,
@@ -226,11 +244,29 @@ CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const Dis
 // (a forest batch is served while the handle would solve it on a forest kernel: the threshold is looked at per call, as pick_kernel does)
 // (an arrowhead batch likewise while option "arrow3" still admits it; the envelope pass while option "covariance_general" is 1)
 bool cov_admitted(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind) {
-    const bool forest = kind == CovKind::Forest || kind == CovKind::ForestOwn;
+    const bool groups = kind == CovKind::ForestGroups || kind == CovKind::ForestGroupsOwn;
+    const bool forest = kind == CovKind::Forest || kind == CovKind::ForestOwn || groups;
     const bool arrow = kind == CovKind::Arrow, envelope = kind == CovKind::Envelope;
     const bool refused = o.has_off1 || (o.has_pinfo && !envelope && !(kind == CovKind::Chain3 && structured_pinfo(o))) || (f.nv_max > 64 && !arrow && !envelope) || kind == CovKind::Unclassified || kind == CovKind::None ||
-                         (forest && (n < tree_min_batch(o) || o.tree == 0)) || (arrow && (!arrow3_wanted(o, f) || !f.cov_arrow)) || (envelope && !o.cov_general);
+                         (forest && (n < tree_min_batch(o) || o.tree == 0)) || (arrow && (!arrow3_wanted(o, f) || !f.cov_arrow)) || (envelope && !o.cov_general) ||
+                         (groups && (!o.forest_groups || !o.forest_groups_cov || o.tree == 2));   // (the grouped forest: both options, and the solve's own rule)
     return !refused;
+}
+
+int cov_public_kind(CovKind kind) {
+    switch (kind) {
+        case CovKind::Chain3: return LOC_WINDOW_COV_CHAIN3;
+        case CovKind::Chain6: return LOC_WINDOW_COV_CHAIN6;
+        case CovKind::Forest: case CovKind::ForestOwn: return LOC_WINDOW_COV_FOREST;
+        case CovKind::Arrow: return LOC_WINDOW_COV_ARROW;
+        case CovKind::Envelope: return LOC_WINDOW_COV_ENVELOPE;
+        case CovKind::ForestGroups: case CovKind::ForestGroupsOwn: return LOC_WINDOW_COV_FOREST_GROUPS;
+        default: return LOC_WINDOW_COV_NONE;
+    }
+}
+
+CovKind resident_groups_covariance(const DispatchOpts& o, const DispatchFits& f, int64_t n, bool groups_no_chain) {
+    return groups_no_chain && cov_admitted(o, f, n, CovKind::ForestGroups) ? CovKind::ForestGroups : CovKind::Unclassified;
 }
 
 bool cov_stale(const DispatchOpts& o, const DispatchFits& f, int64_t n, CovKind kind, long long env_switches) {

@@ -28,6 +28,8 @@ struct DispatchOpts {
                                        // wave3_lm_kernel<JAC, true> and the chain 3x3 covariance pass (structured_pinfo); 0: the general kernel, the envelope pass
     bool forest_groups = false;        // "forest_groups" 1: a batch of forest windows whose topologies DIFFER (build_tree_sched declines it) is grouped by topology
                                        // (build_tree_groups) and solved by tree_wave_kernel<JAC, TreeGroups>; 0: such a batch is LOC_WINDOW_KERNEL_GENERAL
+    bool forest_groups_cov = false;    // "forest_groups_covariance" 1 (with "forest_groups" 1): the covariances of such a batch are served by
+                                       // forest_covariance_kernel<JAC, JOINT, TreeGroups> on the groups' schedules; 0: the envelope pass under "covariance_general", else unsupported
     bool upload_dev_structures = false; // "upload_dev_structures" 1: loc_window_upload_dev takes batch_topology's arrowhead and forest tests on the device
                                        // (window_structure_kernel.hip) for a batch that is no chain; 0: such a batch is LOC_WINDOW_KERNEL_GENERAL
 };
@@ -50,7 +52,9 @@ enum class CovKind : int {
     Chain3, Chain6,      // covariance_kernel.hip with 3x3 (translation-only batches) / 6x6 blocks
     Forest, ForestOwn,   // forest_covariance_kernel.hip on the solve's schedule / on the schedule the covariance pass built itself
     Arrow,               // arrow_covariance_kernel.hip
-    Envelope             // envelope_covariance_kernel.hip (option "covariance_general")
+    Envelope,            // envelope_covariance_kernel.hip (option "covariance_general")
+    ForestGroups, ForestGroupsOwn   // forest_covariance_groups_kernel.hip (options "forest_groups" + "forest_groups_covariance") on the resident solve's groups
+                                    // block / on the block the covariance pass built itself
 };
 
 // the handle's table of full information matrices is one the 3 x 3 kernels take: option "prior_information_structured", a translation-only table,
@@ -59,8 +63,17 @@ bool structured_pinfo(const DispatchOpts& o);
 long long effective_chain_min(const DispatchOpts& o);
 long long tree_min_batch(const DispatchOpts& o);
 bool arrow3_wanted(const DispatchOpts& o, const DispatchFits& f);
+// The grouped forest's rule short of the structure test, stated once for the solve (batch_topology) and the covariances
+// (structured_covariance_kind): option "forest_groups", option "tree" neither 0 nor 2 (tree_lm_kernel has no per-window-schedule twin), a batch of
+// at least tree_min_batch windows, a handle of windows of <= 64 poses, nothing that only the general kernel evaluates.  build_tree_groups decides the rest.
+bool forest_groups_wanted(const DispatchOpts& o, const WindowCaps& c, int64_t n);
+// the LOC_WINDOW_COV_* of a pass (loc_window_last_covariance_kind): Forest / ForestOwn and ForestGroups / ForestGroupsOwn are one pass each
+int cov_public_kind(CovKind kind);
+// A resident batch whose covariance verdict is open, and which loc_window_upload put on the grouped solve path (its groups block is on the device)
+// without finding a chain in any edge order (groups_no_chain), is ForestGroups under the switches as they are now — no copy-back, no scan; else Unclassified
+CovKind resident_groups_covariance(const DispatchOpts& o, const DispatchFits& f, int64_t n, bool groups_no_chain);
 // the switches the three structured covariance tests read besides the batch itself, as one word (option "arrow3", option "tree", the forest threshold, has_pinfo,
-// option "prior_information_structured", the table's translation-only verdict)
+// option "prior_information_structured", the table's translation-only verdict; options "forest_groups" and "forest_groups_covariance" both 1)
 long long cov_switches(const DispatchOpts& o);
 // the kernel a batch of n windows of that structure (batch_topology's verdict) takes NOW (threshold, ordering override, the options)
 int pick_kernel(const DispatchOpts& o, const DispatchFits& f, int64_t n, int topology);
@@ -95,8 +108,9 @@ struct SchedKey {
     bool valid = false;
     unsigned long long key = 0;
     int64_t n = 0;
+    CovKind kind = CovKind::None;   // what the tables of that structure are: ForestOwn (a one-topology schedule) or ForestGroupsOwn (a groups block)
 };
-// need_upload: `own` holds a new forest schedule for the caller to send to the device; list_cap: the arrowhead pass's list size;
+// need_upload: `own` holds a new forest schedule (ForestOwn) or groups block (ForestGroupsOwn) for the caller to send to the device; list_cap: the arrowhead pass's list size;
 // env_blocks: the batch's largest envelope
 struct CovVerdict { CovKind kind; bool need_upload; int list_cap; long long env_blocks; };
 CovVerdict covariance_kind(const WindowCaps& c, const DispatchOpts& o, const DispatchFits& f, int n_anchors, const HostBatch& b, const PairTables& pt,

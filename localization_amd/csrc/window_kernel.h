@@ -156,6 +156,10 @@ hipError_t launch_window_covariance(const WindowArgs& a, bool d3, double* cov, i
 // kernels' elimination schedule, always 6x6 blocks
 size_t window_forest_covariance_lds_bytes(const TreeSched& ts);
 hipError_t launch_window_forest_covariance(const WindowArgs& a, const TreeSched& ts, double* cov, int32_t* mask, int32_t* status, const CovPairs& pp, hipStream_t stream);
+// the same for forest windows of DIFFERING topologies (option "forest_groups_covariance"; forest_covariance_groups_kernel.hip): every wave walks
+// the schedule of its window's group.  host_hdr: the host's copy of g.hdr, whose sizes are checked before the launch
+hipError_t launch_window_forest_covariance_groups(const WindowArgs& a, const TreeGroups& g, const int32_t* host_hdr, double* cov, int32_t* mask, int32_t* status,
+                                                  const CovPairs& pp, hipStream_t stream);
 
 // the same for translation-only arrowhead windows (arrow_covariance_kernel.hip: the windows arrow3_lm_kernel solves; border = the last slots
 // by build_arrow_aux's rule, recomputed on the device), one workgroup per window, 3x3 blocks.  ws: [B][window_arrow_covariance_workspace_doubles]

@@ -460,5 +460,26 @@ LOCAMD_HD inline void tree_group_sizes(TreeSched& ts, const int32_t* h) {
 }
 // what both launchers of tree_wave_kernel.hip hold a schedule's sizes to (lane = pose: 64 lanes, 64 LDS columns)
 LOCAMD_HD inline bool tree_wave_sizes_ok(const TreeSched& ts) { return ts.nv > 0 && ts.nv <= 64 && ts.nlev > 0 && ts.nu >= 0 && ts.nu <= 64; }
+// what both launchers of forest_covariance_kernel.hip hold a schedule's sizes to: the LDS blocks are indexed by pose slot and the value tables
+// by edge number, so the sizes stay within the handle's capacities, and the window's layout within the covariance passes' LDS limit
+LOCAMD_HD inline bool forest_cov_sizes_ok(const TreeSched& ts, const WindowCaps& c) {
+    return ts.nv >= 2 && ts.nv <= 64 && ts.nv <= c.nv_max && ts.nr >= 0 && ts.nr <= c.nr_max && ts.np >= 0 && ts.np <= c.np_max && ts.ns >= 0 && ts.ns <= c.ns_max &&
+           cov_forest_fits(ts.nv, ts.np > 0, ts.ns > 0);
+}
+// ... every group of a TreeGroups block, on the host's copy of its headers ([n_groups][kTreeGroupHdr]; a table offset is never negative): the
+// dynamic LDS of forest_covariance_kernel<JAC, JOINT, TreeGroups>'s launch — the largest group's layout —, or 0 when a group is refused
+LOCAMD_HD inline size_t forest_cov_groups_lds_bytes(const int32_t* host_hdr, int n_groups, const WindowCaps& c) {
+    if (!host_hdr || n_groups <= 0) return 0;
+    size_t lds = 0;
+    for (int k = 0; k < n_groups; ++k) {
+        const int32_t* h = host_hdr + (size_t)k * kTreeGroupHdr;
+        TreeSched ts{};
+        tree_group_sizes(ts, h);
+        if (!forest_cov_sizes_ok(ts, c) || h[10] < 0) return 0;
+        const size_t b = forest_cov_layout(ts.nv, ts.np > 0, ts.ns > 0).bytes;
+        if (b > lds) lds = b;
+    }
+    return lds;
+}
 
 }  // namespace locamd

@@ -286,7 +286,8 @@ class WindowSolver(_lib.Handle):
         """Sigma_i = [H^-1]_ii of every pose of every window at wb.poses: chain windows of <= 64 poses, arrowhead batches (anchor
         self-calibration; the unknown anchors are the last pose slots) whenever the handle would solve them on arrow3_lm_kernel (option
         "arrow3"; by default handles of more than 64 poses), and forest batches (one shared topology, <= 64 poses) whenever the handle
-        would solve them on a forest kernel (option "tree", batch threshold); with set_option("covariance_general", 1) any other batch
+        would solve them on a forest kernel (option "tree", batch threshold); forest batches of DIFFERING topologies under options
+        "forest_groups" + "forest_groups_covariance"; with set_option("covariance_general", 1) any other batch
         as well, on the envelope pass in the caller's pose order (covariance_plan reports its memory).  Returns (cov [B][nv_max][6][6],
         mask [B][nv_max] — excluded coordinates, bits 0-5 = tx ty tz qx qy qz —, status [B]: 0 or LOC_ERR_SINGULAR, that window's blocks NaN).
         The C call is stateless; THIS method first hands wb's prior table to the handle (_prior_information: wb.p_info, or none), as
@@ -502,6 +503,16 @@ class WindowSolver(_lib.Handle):
         check(self.L.loc_window_last_covariance_ms(self.h, C.byref(ms)))
         return ms.value
 
+    COVARIANCE_KINDS = {0: "none", 1: "covariance_kernel<3>", 2: "covariance_kernel<6>", 3: "arrow_covariance_kernel", 4: "forest_covariance_kernel",
+                        5: "envelope_covariance_kernel", 6: "forest_covariance_kernel<groups>"}
+
+    def last_covariance_kind(self):
+        """name of the pass that served the last covariance() / joint_covariance() / *_resident() call that launched
+        (loc_window_last_covariance_kind); "none" before the first"""
+        k = C.c_int32()
+        check(self.L.loc_window_last_covariance_kind(self.h, C.byref(k)))
+        return self.COVARIANCE_KINDS.get(k.value, str(k.value))
+
     KERNEL_KINDS = {-1: "none", 0: "window_lm_kernel", 1: "chain_lm_kernel", 2: "chain3_lm_kernel", 3: "arrow3_lm_kernel", 4: "tree_wave_kernel", 5: "tree_lm_kernel", 6: "wave3_lm_kernel", 7: "wave6_lm_kernel", 8: "wave6_lm_kernel<SE3>",
                     9: "tree_wave_kernel<groups>"}
 
@@ -529,7 +540,10 @@ class WindowSolver(_lib.Handle):
         "forest_groups": 1 = a batch of forest windows of <= 64 poses whose topologies differ (other parents, lengths, anchors: key-frame windows
         of different robots or phases) is grouped by topology and solved by tree_wave_kernel<groups> with one schedule per group, from solve()
         and from upload() + solve_resident(); a one-topology batch keeps tree_wave_kernel; upload_dev() does not group and covariances of a
-        mixed batch are served as without the option; default 0: such a batch solves on the general kernel)"""
+        mixed batch are served as without the option; default 0: such a batch solves on the general kernel;
+        "forest_groups_covariance": 1 (with "forest_groups" 1) = the covariances and cross blocks of such a mixed batch are computed by
+        forest_covariance_kernel<groups>, one wave per window on its group's schedule, from covariance() / joint_covariance() and their
+        resident forms; default 0: the envelope pass under "covariance_general", else unsupported)"""
         check(self.L.loc_window_set_option(self.h, str(name).encode(), int(value)))
 
     def forest_groups(self):
