@@ -329,8 +329,8 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *                      has declined the batch: a batch of one topology takes LOC_WINDOW_KERNEL_TREE as without the option, bit for bit.  The
  *                      batch stays on the general kernel when any window has fewer than 2 poses, a cycle, or two EdgeSE3 factors on one pair of
  *                      poses; under option "tree" = 0 or 2; below TREE's batch threshold; with endpoint-1 lever arms or a table of full
- *                      information matrices; on a handle with nv_max > 64.  loc_window_upload_dev does not group (such a batch solves on the
- *                      general kernel), and covariances of such a batch are served as without the option (the envelope pass under
+ *                      information matrices; on a handle with nv_max > 64.  loc_window_upload_dev groups only under option "upload_dev_forest_groups" (else such a
+ *                      batch solves on the general kernel), and covariances of such a batch are served as without the option (the envelope pass under
  *                      "covariance_general", else LOC_ERR_UNSUPPORTED) unless option "forest_groups_covariance" is 1 as well.  Measured at 16 384 x 64 poses: the solve 3.5 ... 4.8 times faster than on
  *                      the general kernel for 1 ... 16 384 groups; the upload 3 ... 7 ms slower up to 256 groups and 46 ms slower (102 MB of
  *                      schedule tables) with a topology per window — there the option pays from the fourth resident solve on (README).
@@ -341,13 +341,23 @@ int loc_window_last_kernel_kind(const loc_window* w, int32_t* kind);
  *   "upload_dev_structures"  0 (default) / 1: loc_window_upload_dev also takes the ARROWHEAD and FOREST verdicts on the device (see there), so
  *                      that such a batch runs on LOC_WINDOW_KERNEL_ARROW3 / _TREE and their covariance passes exactly as after loc_window_upload
  *                      of the same arrays; read at upload time.  0: loc_window_upload_dev does exactly what it did without the option.
+ *   "upload_dev_forest_groups"  0 (default) / 1: with "upload_dev_structures" = 1 and "forest_groups" = 1, loc_window_upload_dev groups a batch
+ *                      of forest windows of differing topologies on the device (see there) and leaves the handle as loc_window_upload of the
+ *                      same arrays does: LOC_WINDOW_KERNEL_TREE_GROUPS, the same groups block byte for byte, the same loc_window_forest_groups,
+ *                      and under "forest_groups_covariance" the grouped covariance pass on the uploaded block from the first call on.  Read at
+ *                      upload time.  0, or either of the other two options 0: loc_window_upload_dev does exactly what it did without the option.
+ *   "upload_dev_groups_hash_bits"  0 ... 64 (default 64).  A TEST SEAM, not a tuning knob: the candidate hash of the device grouping pass is
+ *                      masked to this many low bits before it is used, which forces hash collisions (0: every window collides with window 0).
+ *                      The groups are defined by key equality and first appearance, so no value changes any answer; a collision only makes
+ *                      the call group the batch on the host instead.
  * LOC_ERR_INVALID for an unknown name or value. */
 int loc_window_set_option(loc_window* w, const char* name, int64_t value);
 /* Host-side cost of the last loc_window_solve_host call, milliseconds: [0] argument validation, [1] structure analysis (kernel
  * choice: hash of the index tables, chain / forest / arrowhead tests, host-built schedules), [2] staging + launch + copy back +
  * synchronise, [3] 1.0 when the structural verdict came from the handle's cache, else 0.0 */
 int loc_window_last_host_timing(const loc_window* w, double* validate_topology_run_cached);
-/* Option "forest_groups": what the handle's LAST structural verdict — of a loc_window_solve_host call or of an upload, whichever came last —
+/* Option "forest_groups": what the handle's LAST structural verdict — of a loc_window_solve_host call or of an upload (loc_window_upload, or
+ * loc_window_upload_dev under option "upload_dev_forest_groups"), whichever came last —
  * found: the number of topology groups and the size in bytes of the block sent to the device (headers, window -> group map, the groups'
  * schedule tables).  0 and 0 when that batch is not on the grouped path. */
 int loc_window_forest_groups(const loc_window* w, int32_t* n_groups, int64_t* table_bytes);
@@ -382,15 +392,24 @@ int loc_window_upload(loc_window* w, int64_t n_instances, const int32_t* counts,
  * batch — every window's counts and used index rows equal window 0's — the host fetches window 0's counts and index rows, ONE window's, and
  * builds the schedule from them.  Kernel, covariance pass and solve bits are loc_window_upload's; so are the resident entries' answers
  * (loc_window_prune_resident refuses an ARROW3 batch).  hip_stream is then synchronised once or twice more.  Still on the host only: the
- * topology cache (every upload is analysed), loc_window_set_endpoint1_offsets / _set_prior_information (host arrays), and forest batches
- * whose windows differ in topology (the general kernel, as after loc_window_upload).
+ * topology cache (every upload is analysed), loc_window_set_endpoint1_offsets / _set_prior_information (host arrays), and — unless the next
+ * option is set — forest batches whose windows differ in topology (the general kernel).
+ * Option "upload_dev_forest_groups" = 1 (with "upload_dev_structures" = 1 and "forest_groups" = 1) takes loc_window_upload's last test as well:
+ * a batch the two tests above leave — no chain, no arrowhead, not of one topology — that "forest_groups" admits (its rule, unchanged) is
+ * grouped by topology on the device: one wave per window hashes the window's topology key and finds the lowest window of that hash, compares
+ * its key with that window's, and a one-workgroup scan numbers the groups by first appearance.  The host reads back one record, then the
+ * window -> group map (4 bytes per window) and ONE window per group (counts and used index rows), builds the groups' schedules from those and
+ * sends the block loc_window_upload sends, byte for byte.  A batch loc_window_upload would refuse to group (a window with fewer than 2 poses,
+ * a cycle, two EdgeSE3 factors on one pair) solves on the general kernel, as there.  A hash collision (see "upload_dev_groups_hash_bits")
+ * fetches the counts and index tables and groups on the host: the answer never depends on the hash.  The schedules themselves are still built
+ * on the host.
  * Synchronisation: hip_stream is synchronised ONCE for the record (work the caller queued on it before the call — a kernel that writes the
  * arrays — is seen), and an admitted batch waits for the previous batch's resident work and for its own copies: like loc_window_upload the call
  * returns when the arrays are free again.  The host copies of the integer tables (the counts, and the mirror of option "resident_slide") are
  * fetched from the device by the first entry that reads them.
  * Timing: the pass's two launches are bracketed by the events loc_window_last_covariance_ms reads, as the slides' launches are (when option
  * "upload_dev_structures" adds launches the closing event is recorded again behind the last of them: the figure then spans admission, the
- * device-to-device copy and the structure / pack launches).  After the
+ * device-to-device copy and the structure / pack / grouping launches).  After the
  * call — a REFUSED one included — loc_window_last_covariance_ms reports the admit pass, no longer the previous batch's last covariance or
  * slide launch: read that figure before calling. */
 int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n_instances, const void* counts_dev, const void* poses_dev,

@@ -15,6 +15,7 @@
 #include "slide_plain_admit.h"
 #include "window_admit.h"
 #include "window_dispatch.h"
+#include "window_groups.h"
 #include "window_kernel.h"
 #include "window_layouts.h"
 #include "window_structure.h"
@@ -129,6 +130,12 @@ struct loc_window {
     // ... under option "upload_dev_structures": the structure pass's device block [kStructMaxWaves partial records | the record] and the record's page-locked copy
     char* d_struct = nullptr;
     locamd::WindowStructRecord* h_struct_record = nullptr;
+    // ... under option "upload_dev_forest_groups": the grouping pass's device block for B windows (dev_forest_groups lays it out), the record's
+    // page-locked copy, and the compact tables of the representatives [counts | r_idx | p_idx | s_idx], grown to the groups of the batch
+    char* d_groups_pass = nullptr;
+    locamd::WindowGroupsRecord* h_groups_record = nullptr;
+    int32_t* d_groups_compact = nullptr;
+    size_t groups_compact_cap = 0;   // windows
 };
 static constexpr size_t kStageBytes = 4u << 20;
 static constexpr size_t kResultBytes = 8 * sizeof(double);   // one instance's row of `result`
@@ -161,9 +168,10 @@ int loc_window_destroy(loc_window* w) {
     if (!w) return LOC_OK;
     (void)hipSetDevice(w->device);
     void* ptrs[] = {w->d_anchors, w->d_result, w->d_workspace, w->d_poses_in, w->d_chain_ws, w->d_chain3_ws, w->d_roff1, w->d_pinfo, w->d_tree_ws, w->d_arrow_ws,
-                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows, w->d_admit, w->d_struct};
+                    w->d_stage, w->d_cov, w->d_slide_mp, w->d_antenna, w->d_msg_rows, w->d_admit, w->d_struct, w->d_groups_pass, w->d_groups_compact};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (w->h_struct_record) (void)hipHostFree(w->h_struct_record);
+    if (w->h_groups_record) (void)hipHostFree(w->h_groups_record);
     for (loc_window::BatchSlot& S : w->slot) release_slot(S);
     for (void* p : w->dev.t) if (p) (void)hipFree(p);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -570,6 +578,12 @@ int loc_window_set_option(loc_window* w, const char* name, int64_t value) {
     if (k == "resident_slide") return flag(w->opt_slide);   // (read by loc_window_upload: the batch resident now keeps what its upload decided)
     if (k == "topology_cache") { w->topo_cache.valid = false; return flag(o.topology_cache); }
     if (k == "upload_dev_structures") return flag(o.upload_dev_structures);   // (read by loc_window_upload_dev: the batch resident now keeps what its upload decided)
+    if (k == "upload_dev_forest_groups") return flag(o.upload_dev_forest_groups);   // (likewise)
+    if (k == "upload_dev_groups_hash_bits") {   // (a test seam: the device's candidate hash keeps this many low bits)
+        if (value < 0 || value > 64) return locamd_fail(LOC_ERR_INVALID, "set_option upload_dev_groups_hash_bits: 0 .. 64");
+        o.upload_dev_groups_hash_bits = (int)value;
+        return LOC_OK;
+    }
     return locamd_fail(LOC_ERR_INVALID, "set_option: unknown option name");
 }
 
@@ -814,7 +828,9 @@ int loc_window_upload(loc_window* w, int64_t n, const int32_t* counts, const dou
 // build_tree_sched.  topology / cov: what loc_window_upload of the same arrays leaves in Resident — untouched when neither test takes the
 // batch.  slot[1].aux is written here alone, after the previous batch was dropped.  The launches end the call's cov_ev0 / cov_ev1 bracket:
 // cov_ev1 is recorded again behind them, so loc_window_last_covariance_ms spans admission, copy and these launches.
-static int dev_structures(loc_window* w, int64_t n, const locamd::WindowBatchFlags& flags, hipStream_t st, int& topology, CovKind& cov) {
+// mixed: the forest test ran, neither test took the batch, and the windows are NOT all equal to window 0 (what dev_forest_groups below is for).
+static int dev_structures(loc_window* w, int64_t n, const locamd::WindowBatchFlags& flags, hipStream_t st, int& topology, CovKind& cov, bool& mixed) {
+    mixed = false;
     const locamd::WindowCaps& c = w->caps;
     const locamd::DispatchOpts& o = w->opt;
     loc_window::BatchSlot& S = w->slot[1];
@@ -872,6 +888,84 @@ static int dev_structures(loc_window* w, int64_t n, const locamd::WindowBatchFla
             cov = chain ? CovKind::Unclassified : CovKind::Forest;
         }
     }
+    mixed = forest && (rec.and_bits & locamd::kStructEqual0) == 0;
+    return LOC_OK;
+}
+
+// Option "upload_dev_forest_groups": batch_topology's last test, build_tree_groups, for an admitted batch that dev_structures found to be
+// neither an arrowhead nor of one topology and that forest_groups_wanted admits (window_groups_kernel.hip; DESIGN.md §2, "Upload from device
+// arrays").  The windows are grouped by topology key on the device; the host reads ONE record, then sched_of (4 bytes per window) and the G
+// representatives' counts and used index rows, and part (b) of build_tree_groups (build_tree_groups_block) builds the block that
+// loc_window_upload of the same arrays builds — byte for byte, refusals included.  A hash collision or a table overflow (the record says so)
+// fetches the batch's counts and index tables and calls build_tree_groups itself: rare, and always exact.  topology / groups_no_chain: what
+// loc_window_upload leaves in Resident; slot[1].aux describes no groups when the batch is refused.  The launches sit inside the call's
+// cov_ev0 / cov_ev1 bracket: cov_ev1 is recorded again behind the last of them.
+static int dev_forest_groups(loc_window* w, int64_t n, hipStream_t st, int& topology, bool& groups_no_chain) {
+    const locamd::WindowCaps& c = w->caps;
+    const locamd::DispatchOpts& o = w->opt;
+    locamd::WinAux& A = w->slot[1].aux;
+    A.n_groups = 0;
+    A.h_groups.clear();
+    const size_t B = (size_t)w->B, N = (size_t)n;
+    // the pass's block: hash u64 [B] | tab_key u64 [slots] | tab_inv u32 [slots] | rep0, sched_of, rep i32 [B] each | kGroupsMaxWaves partial records | the record
+    const uint64_t slots = locamd::groups_table_slots(w->B);
+    const size_t at_key = B * sizeof(uint64_t), at_inv = at_key + slots * sizeof(uint64_t), at_rep0 = at_inv + slots * sizeof(uint32_t), at_of = at_rep0 + B * sizeof(int32_t),
+                 at_rep = at_of + B * sizeof(int32_t), at_partial = (at_rep + B * sizeof(int32_t) + 7) / 8 * 8,
+                 at_record = at_partial + (size_t)locamd::kGroupsMaxWaves * sizeof(locamd::WindowGroupsRecord);
+    if (!w->d_groups_pass) LOC_HIP(hipMalloc((void**)&w->d_groups_pass, at_record + sizeof(locamd::WindowGroupsRecord)));
+    if (!w->h_groups_record) LOC_HIP(hipHostMalloc((void**)&w->h_groups_record, sizeof(locamd::WindowGroupsRecord), hipHostMallocDefault));
+    const locamd::DeviceTables& d = w->dev;
+    char* blk = w->d_groups_pass;
+    locamd::WindowGroupsArgs a{};
+    a.counts = (const int32_t*)d.t[kCounts]; a.r_idx = (const int32_t*)d.t[locamd::kRIdx]; a.p_idx = (const int32_t*)d.t[locamd::kPIdx]; a.s_idx = (const int32_t*)d.t[locamd::kSIdx];
+    a.hash = (uint64_t*)blk; a.tab_key = (uint64_t*)(blk + at_key); a.tab_inv = (uint32_t*)(blk + at_inv); a.slots = slots;
+    a.rep0 = (int32_t*)(blk + at_rep0); a.sched_of = (int32_t*)(blk + at_of); a.rep = (int32_t*)(blk + at_rep);
+    a.partial = (locamd::WindowGroupsRecord*)(blk + at_partial); a.record = (locamd::WindowGroupsRecord*)(blk + at_record);
+    a.hash_bits = o.upload_dev_groups_hash_bits; a.B = n; a.caps = c;
+    LOC_HIP(locamd::launch_window_groups(a, st));
+    LOC_HIP(hipEventRecord(w->cov_ev1, st));
+    LOC_HIP(hipMemcpyAsync(w->h_groups_record, a.record, sizeof(locamd::WindowGroupsRecord), hipMemcpyDeviceToHost, st));
+    LOC_HIP(hipStreamSynchronize(st));
+    const locamd::WindowGroupsRecord rec = *w->h_groups_record;
+    if ((rec.or_bits & locamd::kGroupsBadNv) != 0) return LOC_OK;   // (build_tree_groups refuses a window with nv outside [2, 64]: the general kernel)
+    bool ok = false, chain = false, single_pairs = false, se3_pairs = false;
+    if ((rec.or_bits & (locamd::kGroupsCollision | locamd::kGroupsOverflow)) != 0 || rec.n_groups < 1 || rec.n_groups > n) {
+        std::vector<int32_t> counts(N * 4), ridx(N * c.nr_max * 2), pidx(N * c.np_max), sidx(N * c.ns_max * 4);
+        LOC_HIP(hipMemcpy(counts.data(), a.counts, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!ridx.empty()) LOC_HIP(hipMemcpy(ridx.data(), a.r_idx, ridx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!pidx.empty()) LOC_HIP(hipMemcpy(pidx.data(), a.p_idx, pidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!sidx.empty()) LOC_HIP(hipMemcpy(sidx.data(), a.s_idx, sidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        const locamd::HostBatch all{n, nullptr, counts.data(), nullptr, nullptr, nullptr, ridx.data(), pidx.data(), sidx.data()};
+        ok = locamd::build_tree_groups(c, locamd::general_only(o), all, A);
+        if (ok) locamd::chain_scan(c, all, false, chain, single_pairs, se3_pairs);
+    } else {
+        const size_t G = (size_t)rec.n_groups;
+        const size_t per = 4 + (size_t)c.nr_max * 2 + c.np_max + (size_t)c.ns_max * 4;   // int32s of one window's compact rows
+        LOC_HIP(locamd::grow_buffers(w->groups_compact_cap, G, {{w->d_groups_compact, G * per * sizeof(int32_t)}}));
+        const size_t cap = w->groups_compact_cap;   // (the tables are laid out for the buffer's capacity, not for G)
+        locamd::WindowGroupsGatherArgs g{};
+        g.counts = a.counts; g.r_idx = a.r_idx; g.p_idx = a.p_idx; g.s_idx = a.s_idx; g.rep = a.rep;
+        g.c_counts = w->d_groups_compact; g.c_r_idx = g.c_counts + cap * 4; g.c_p_idx = g.c_r_idx + cap * c.nr_max * 2; g.c_s_idx = g.c_p_idx + cap * c.np_max;
+        g.G = (long long)G; g.B = n; g.caps = c;
+        LOC_HIP(locamd::launch_window_groups_gather(g, st));
+        LOC_HIP(hipEventRecord(w->cov_ev1, st));
+        std::vector<int32_t> of(N), counts(G * 4), ridx(G * c.nr_max * 2), pidx(G * c.np_max), sidx(G * c.ns_max * 4);
+        LOC_HIP(hipMemcpyAsync(of.data(), a.sched_of, of.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipMemcpyAsync(counts.data(), g.c_counts, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (!ridx.empty()) LOC_HIP(hipMemcpyAsync(ridx.data(), g.c_r_idx, ridx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (!pidx.empty()) LOC_HIP(hipMemcpyAsync(pidx.data(), g.c_p_idx, pidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (!sidx.empty()) LOC_HIP(hipMemcpyAsync(sidx.data(), g.c_s_idx, sidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        LOC_HIP(hipStreamSynchronize(st));
+        const locamd::HostBatch reps{(int64_t)G, nullptr, counts.data(), nullptr, nullptr, nullptr, ridx.data(), pidx.data(), sidx.data()};
+        ok = locamd::build_tree_groups_block(c, locamd::general_only(o), reps, n, of.data(), A);
+        // (chain_scan(ordered = false) reads a window's counts, the sign of v1 and |v0 - v1| of its range rows and columns 0 - 1 of its EdgeSE3
+        //  rows: all of them words of the topology key, and the batch's verdict is the AND over its windows — the representatives answer for the batch)
+        if (ok) locamd::chain_scan(c, reps, false, chain, single_pairs, se3_pairs);
+    }
+    if (!ok) return LOC_OK;
+    LOC_HIP(upload_tree_sched(w, A, w->stream, true, true));
+    topology = LOC_WINDOW_KERNEL_TREE_GROUPS;
+    groups_no_chain = !chain;
     return LOC_OK;
 }
 
@@ -879,7 +973,7 @@ static int dev_structures(loc_window* w, int64_t n, const locamd::WindowBatchFla
 // the chain family's structure on hip_stream, the host reads back one record (the call's ONE synchronisation of that stream), and an admitted
 // batch is copied device-to-device.  A refused batch copies nothing and leaves the previous resident batch as it was.  The host copies of the
 // integer tables are not made: they are sized and marked stale (refresh_mirror).  Option "upload_dev_structures": a batch that is no chain
-// goes on to dev_structures above.
+// goes on to dev_structures above, and what that leaves of mixed forest windows, under option "upload_dev_forest_groups", to dev_forest_groups.
 int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void* counts_dev, const void* poses_dev, const void* r_idx_dev, const void* r_val_dev,
                           const void* p_idx_dev, const void* p_val_dev, const void* s_idx_dev, const void* s_val_dev, void* admit_dev) {
     const locamd::HostBatch b{n, (const double*)poses_dev, (const int32_t*)counts_dev, (const double*)r_val_dev, (const double*)p_val_dev, (const double*)s_val_dev,
@@ -924,8 +1018,14 @@ int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void
     const locamd::WindowBatchFlags flags = locamd::window_batch_flags(rec);
     int topology = locamd::topology_from_flags(w->opt, w->fits, flags);
     CovKind cov = topology == LOC_WINDOW_KERNEL_CHAIN3 ? CovKind::Chain3 : topology == LOC_WINDOW_KERNEL_GENERAL ? CovKind::Unclassified : CovKind::Chain6;
-    if (w->opt.upload_dev_structures && !flags.chain)
-        if (int rc = dev_structures(w, n, flags, st, topology, cov)) return rc;
+    bool groups_no_chain = false;
+    if (w->opt.upload_dev_structures && !flags.chain) {
+        bool mixed = false;
+        if (int rc = dev_structures(w, n, flags, st, topology, cov, mixed)) return rc;
+        if (mixed && topology == LOC_WINDOW_KERNEL_GENERAL && w->opt.upload_dev_forest_groups && locamd::forest_groups_wanted(w->opt, c, n))
+            if (int rc = dev_forest_groups(w, n, st, topology, groups_no_chain)) return rc;
+    }
+    R.groups_no_chain = groups_no_chain;
     R.min_anchors = rec.max_anchor;
     R.counts.assign((size_t)n * 4, 0);
     if (w->opt_slide) {
@@ -934,7 +1034,7 @@ int loc_window_upload_dev(loc_window* w, void* hip_stream, int64_t n, const void
         R.mirror_valid = true;
     }
     R.mirror_stale = true;   // (refresh_mirror: the first reader of counts or the mirror fetches them)
-    note_groups(w, w->slot[1].aux, topology);   // (never the grouped path: a mixed forest batch in device arrays solves on the general kernel)
+    note_groups(w, w->slot[1].aux, topology);   // (the grouped path under option "upload_dev_forest_groups" alone)
     R.topology = topology;
     R.skip = locamd::structured_pinfo(w->opt);
     R.cov = cov;

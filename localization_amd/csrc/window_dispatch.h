@@ -32,6 +32,9 @@ struct DispatchOpts {
                                        // forest_covariance_kernel<JAC, JOINT, TreeGroups> on the groups' schedules; 0: the envelope pass under "covariance_general", else unsupported
     bool upload_dev_structures = false; // "upload_dev_structures" 1: loc_window_upload_dev takes batch_topology's arrowhead and forest tests on the device
                                        // (window_structure_kernel.hip) for a batch that is no chain; 0: such a batch is LOC_WINDOW_KERNEL_GENERAL
+    bool upload_dev_forest_groups = false; // "upload_dev_forest_groups" 1 (with "upload_dev_structures" and "forest_groups" 1): loc_window_upload_dev groups a mixed
+                                       // forest batch by topology on the device (window_groups_kernel.hip) and leaves it on the grouped kernel; 0: the general kernel
+    int upload_dev_groups_hash_bits = 64;  // "upload_dev_groups_hash_bits": a test seam — that pass's candidate hash keeps this many low bits (fewer: collisions, the same answer)
 };
 
 // what depends on the handle's capacities alone: the kernels' LDS needs against their limits (window_layouts.h), taken once by loc_window_create

@@ -325,6 +325,36 @@ size_t window_structure_lds_bytes(const WindowCaps& c);   // launch_window_struc
 hipError_t launch_window_structure(const WindowStructArgs& a, hipStream_t stream);
 hipError_t launch_window_arrow_pack(const ArrowPackArgs& a, hipStream_t stream);
 
+// the grouping of an ADMITTED batch of forest windows of differing topologies in device arrays (window_groups_kernel.hip; DESIGN.md §2, "Upload
+// from device arrays"; option "upload_dev_forest_groups"): passes 1 and 2 of build_tree_groups by window_groups.h's key, one wave per window.
+// launch_window_groups zeroes the table on the stream and runs four launches — hash and insert; look up and verify, one partial record per
+// wave; a one-wave merge into *record; a one-workgroup scan that numbers the groups by first appearance into sched_of / rep.
+// launch_window_groups_gather copies the G representatives' counts and used index rows into the compact tables c_* at the capacities `caps`.
+// All device arrays.  hash / rep0 / sched_of / rep: [B]; tab_key / tab_inv: `slots` entries (groups_table_slots(B), a power of two),
+// contiguous — tab_inv directly behind tab_key — so that one memset clears both; partial: kGroupsMaxWaves records.
+struct WindowGroupsRecord;   // window_groups.h
+constexpr int kGroupsMaxWaves = 2048;
+struct WindowGroupsArgs {
+    const int32_t* counts; const int32_t* r_idx; const int32_t* p_idx; const int32_t* s_idx;
+    uint64_t* hash;                                       // [B] the masked hash of window b's key (0: the window was not hashed)
+    uint64_t* tab_key; uint32_t* tab_inv;                 // open-addressed: a slot's hash (0: empty) and ~(the lowest window index that carries it)
+    uint64_t slots;
+    int32_t* rep0; int32_t* sched_of; int32_t* rep;       // [B] the lowest window of b's hash; b's group; group g's first window
+    WindowGroupsRecord* partial; WindowGroupsRecord* record;
+    int hash_bits;                                        // option "upload_dev_groups_hash_bits"
+    long long B;
+    WindowCaps caps;
+};
+struct WindowGroupsGatherArgs {
+    const int32_t* counts; const int32_t* r_idx; const int32_t* p_idx; const int32_t* s_idx;
+    const int32_t* rep;                                   // [G]
+    int32_t* c_counts; int32_t* c_r_idx; int32_t* c_p_idx; int32_t* c_s_idx;   // [G][4], [G][nr_max][2], [G][np_max], [G][ns_max][4]
+    long long G, B;
+    WindowCaps caps;
+};
+hipError_t launch_window_groups(const WindowGroupsArgs& a, hipStream_t stream);
+hipError_t launch_window_groups_gather(const WindowGroupsGatherArgs& a, hipStream_t stream);
+
 size_t window_tree_workspace_doubles(const WindowCaps& c, long long B);
 hipError_t launch_window_tree(const WindowArgs& a, const TreeSched& ts, double* ws, hipStream_t stream);
 hipError_t launch_window_tree_wave(const WindowArgs& a, const TreeSched& ts, hipStream_t stream);

@@ -2,6 +2,7 @@
 #include "window_structure.h"
 #include "window_layouts.h"
 #include "arrow_pack.h"
+#include "window_groups.h"
 
 #include <cstring>
 #include <algorithm>
@@ -589,26 +590,21 @@ size_t bind_tree_sched(TreeSched& ts, const int32_t* base) { return tree_sched_b
 // localization.cpp:254-290), have different parents and lengths and range different anchors.  A window's TOPOLOGY KEY: its four counts, its
 // used r_idx rows with every fixed endpoint (v1 < 0) collapsed to -1, its used p_idx rows, columns 0 - 1 of its used s_idx rows.  Anchor
 // numbers and robust flags are not part of it: tree_wave_groups_kernel reads them from the window's own rows.
-static void topology_key(const WindowCaps& c, const HostBatch& b, int64_t i, std::vector<int32_t>& k) {
+static void topology_key(const WindowCaps& c, const HostBatch& b, int64_t i, std::vector<int32_t>& k) {   // (window_groups.h: the one statement)
     const int32_t* cn = b.counts + i * 4;
-    k.assign(cn, cn + 4);
-    const int32_t* r = b.r_idx + (size_t)i * c.nr_max * 2;
-    for (int e = 0; e < cn[1]; ++e) { k.push_back(r[2 * e]); k.push_back(r[2 * e + 1] < 0 ? -1 : r[2 * e + 1]); }
-    const int32_t* p = b.p_idx + (size_t)i * c.np_max;
-    k.insert(k.end(), p, p + cn[2]);
-    const int32_t* s = b.s_idx + (size_t)i * c.ns_max * 4;
-    for (int e = 0; e < cn[3]; ++e) { k.push_back(s[4 * e]); k.push_back(s[4 * e + 1]); }
+    const int32_t *r = b.r_idx + (size_t)i * c.nr_max * 2, *p = b.p_idx + (size_t)i * c.np_max, *s = b.s_idx + (size_t)i * c.ns_max * 4;
+    const long long nw = topology_key_words(cn);
+    k.resize((size_t)nw);
+    for (long long j = 0; j < nw; ++j) k[(size_t)j] = topology_key_word(cn, r, p, s, j);
 }
 
-// Groups the windows by topology key (ids in order of first appearance; a hash finds the candidates, a memcmp of the keys decides), runs
-// every group's first window through tree_sched_one and writes A.h_groups = [hdr | sched_of | pad | tables] (window_kernel.h: TreeGroups).
-// The batch is refused as a whole — false, A.n_groups = 0 — when any window has nv outside [2, 64], any group has a cycle or more than one
-// EdgeSE3 on a node's edge to its parent (tree_lm_kernel, which takes those, has no twin), under has_off1, or when the handle's nv_max > 64.
-bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
-    A.n_groups = 0;
-    A.h_groups.clear();
+// Part (a), the grouping: of[b] = window b's group, ids in order of first appearance; rep[g] = group g's first window.  A hash finds the
+// candidates, a memcmp of the keys decides.  false: a window with nv outside [2, 64] (of and rep are then worth nothing).
+bool group_windows(const WindowCaps& c, const HostBatch& b, std::vector<int32_t>& of, std::vector<int64_t>& rep) {
     const int64_t n = b.n;
-    if (has_off1 || c.nv_max > 64 || n <= 0) return false;
+    of.assign((size_t)(n > 0 ? n : 0), 0);
+    rep.clear();
+    if (n <= 0) return false;
     // pass 1, split over the windows: a 64-bit FNV-1a of every key
     std::vector<uint64_t> hash((size_t)n);
     std::atomic<bool> bad{false};
@@ -625,46 +621,53 @@ bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, W
     });
     if (bad.load()) return false;
     // pass 2, in window order: a window joins the first group of its hash whose representative's key equals its own
-    std::vector<int32_t> of((size_t)n), k;
-    std::vector<int64_t> rep;                    // a group's first window
-    std::vector<std::vector<int32_t>> rep_key;   // ... and its key
-    {
-        std::vector<std::pair<uint64_t, int64_t>> order((size_t)n);
-        for (int64_t i = 0; i < n; ++i) order[(size_t)i] = {hash[(size_t)i], i};
-        std::sort(order.begin(), order.end());   // (equal hashes in window order: a group's representative is its first window)
-        std::vector<int32_t> local((size_t)n, -1);   // per window: index of its group among the groups found in hash order
-        std::vector<int64_t> lrep;
-        std::vector<std::vector<int32_t>> lkey;
-        for (size_t a0 = 0; a0 < order.size();) {
-            size_t a1 = a0;
-            while (a1 < order.size() && order[a1].first == order[a0].first) ++a1;
-            const size_t g0 = lrep.size();
-            for (size_t q = a0; q < a1; ++q) {
-                const int64_t i = order[q].second;
-                topology_key(c, b, i, k);
-                size_t g = g0;
-                for (; g < lrep.size(); ++g)
-                    if (lkey[g].size() == k.size() && std::memcmp(lkey[g].data(), k.data(), k.size() * sizeof(int32_t)) == 0) break;
-                if (g == lrep.size()) { lrep.push_back(i); lkey.push_back(k); }
-                local[(size_t)i] = (int32_t)g;
-            }
-            a0 = a1;
+    std::vector<int32_t> k;
+    std::vector<std::pair<uint64_t, int64_t>> order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) order[(size_t)i] = {hash[(size_t)i], i};
+    std::sort(order.begin(), order.end());   // (equal hashes in window order: a group's representative is its first window)
+    std::vector<int32_t> local((size_t)n, -1);   // per window: index of its group among the groups found in hash order
+    std::vector<int64_t> lrep;
+    std::vector<std::vector<int32_t>> lkey;
+    for (size_t a0 = 0; a0 < order.size();) {
+        size_t a1 = a0;
+        while (a1 < order.size() && order[a1].first == order[a0].first) ++a1;
+        const size_t g0 = lrep.size();
+        for (size_t q = a0; q < a1; ++q) {
+            const int64_t i = order[q].second;
+            topology_key(c, b, i, k);
+            size_t g = g0;
+            for (; g < lrep.size(); ++g)
+                if (lkey[g].size() == k.size() && std::memcmp(lkey[g].data(), k.data(), k.size() * sizeof(int32_t)) == 0) break;
+            if (g == lrep.size()) { lrep.push_back(i); lkey.push_back(k); }
+            local[(size_t)i] = (int32_t)g;
         }
-        // group ids in order of first appearance
-        std::vector<int32_t> id(lrep.size(), -1);
-        for (int64_t i = 0; i < n; ++i) {
-            int32_t& g = id[(size_t)local[(size_t)i]];
-            if (g < 0) { g = (int32_t)rep.size(); rep.push_back(i); }
-            of[(size_t)i] = g;
-        }
+        a0 = a1;
     }
-    const int64_t G = (int64_t)rep.size();
+    // group ids in order of first appearance
+    std::vector<int32_t> id(lrep.size(), -1);
+    for (int64_t i = 0; i < n; ++i) {
+        int32_t& g = id[(size_t)local[(size_t)i]];
+        if (g < 0) { g = (int32_t)rep.size(); rep.push_back(i); }
+        of[(size_t)i] = g;
+    }
+    return true;
+}
+
+// Part (b), representatives -> block: group g's representative is window rep[g] of b (rep == nullptr: window g — b is then the compact batch
+// of the G representatives, each with its counts and used index rows at the capacities c).  Runs every representative through
+// tree_sched_one, applies the refusals and writes A.h_groups = [hdr | sched_of | pad | tables] for the n windows of of[].
+static bool groups_block(const WindowCaps& c, const HostBatch& b, const int64_t* rep, int64_t G, int64_t n, const int32_t* of, WinAux& A) {
+    A.n_groups = 0;
+    A.h_groups.clear();
+    if (G <= 0 || n < G) return false;
+    for (int64_t i = 0; i < n; ++i) if (of[i] < 0 || of[i] >= G) return false;   // (the kernels index the headers by sched_of unchecked)
     // every group's schedule, split over the groups
+    std::atomic<bool> bad{false};
     std::vector<std::vector<int32_t>> tab((size_t)G);
     std::vector<TreeSched> sizes((size_t)G);
     parallel_chunks(G, [&](int64_t lo, int64_t hi, int) {
         for (int64_t g = lo; g < hi && !bad.load(std::memory_order_relaxed); ++g) {
-            const int64_t i = rep[(size_t)g];
+            const int64_t i = rep ? rep[g] : g;
             TreeSched& ts = sizes[(size_t)g];
             ts = TreeSched{};
             if (!tree_sched_one(b.counts + i * 4, b.r_idx + (size_t)i * c.nr_max * 2, b.p_idx + (size_t)i * c.np_max, b.s_idx + (size_t)i * c.ns_max * 4, tab[(size_t)g], ts) ||
@@ -679,7 +682,7 @@ bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, W
     for (const auto& x : tab) total += (x.size() + 3) / 4 * 4;
     if (total > (size_t)INT32_MAX) return false;   // (a header holds its table's offset as an int32)
     t.assign(tab_at + total, kTreeGroupPoison);
-    std::memcpy(t.data() + of_at, of.data(), (size_t)n * sizeof(int32_t));
+    std::memcpy(t.data() + of_at, of, (size_t)n * sizeof(int32_t));
     size_t at = 0;
     for (int64_t g = 0; g < G; ++g) {
         const TreeSched& ts = sizes[(size_t)g];
@@ -692,6 +695,30 @@ bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, W
     A.groups_of_at = of_at;
     A.groups_tab_at = tab_at;
     return true;
+}
+
+// Part (b) for a caller that has grouped the batch elsewhere (loc_window_upload_dev under option "upload_dev_forest_groups": on the device):
+// reps = the compact batch of the G = reps.n representatives in group order, of [n] = every window's group.  The block and the refusals are
+// build_tree_groups' for the batch those representatives were taken from (a window's nv is part of its key: the representatives' suffice).
+bool build_tree_groups_block(const WindowCaps& c, bool has_off1, const HostBatch& reps, int64_t n, const int32_t* of, WinAux& A) {
+    A.n_groups = 0;
+    A.h_groups.clear();
+    if (has_off1 || c.nv_max > 64 || n <= 0 || !of) return false;
+    return groups_block(c, reps, nullptr, reps.n, n, of, A);
+}
+
+// Groups the windows by topology key (group_windows), runs every group's first window through tree_sched_one and writes
+// A.h_groups = [hdr | sched_of | pad | tables] (window_kernel.h: TreeGroups).
+// The batch is refused as a whole — false, A.n_groups = 0 — when any window has nv outside [2, 64], any group has a cycle or more than one
+// EdgeSE3 on a node's edge to its parent (tree_lm_kernel, which takes those, has no twin), under has_off1, or when the handle's nv_max > 64.
+bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A) {
+    A.n_groups = 0;
+    A.h_groups.clear();
+    if (has_off1 || c.nv_max > 64 || b.n <= 0) return false;
+    std::vector<int32_t> of;
+    std::vector<int64_t> rep;
+    if (!group_windows(c, b, of, rep)) return false;
+    return groups_block(c, b, rep.data(), (int64_t)rep.size(), b.n, of.data(), A);
 }
 
 }  // namespace locamd

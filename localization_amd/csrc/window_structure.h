@@ -79,5 +79,12 @@ size_t bind_tree_sched(TreeSched& ts, const int32_t* base);   // ts's pointers i
 // Forest windows of DIFFERING topologies: groups by topology key (counts, index rows without anchor numbers and robust flags), one
 // build_tree_sched table per group; fills A.h_groups, A.n_groups, A.groups_*_at.  false: the batch stays with the general kernel
 bool build_tree_groups(const WindowCaps& c, bool has_off1, const HostBatch& b, WinAux& A);
+// ... in two parts (build_tree_groups is (a) followed by (b)).  (a) the grouping (window_groups.h states the key): of [n] = every window's
+// group, ids in order of first appearance; rep = every group's first window.  false: a window with nv outside [2, 64]
+bool group_windows(const WindowCaps& c, const HostBatch& b, std::vector<int32_t>& of, std::vector<int64_t>& rep);
+// (b) representatives -> block, for a batch grouped elsewhere (loc_window_upload_dev: window_groups_kernel.hip): reps = the compact batch of
+// the G = reps.n representatives in group order (counts and used index rows at the capacities c; no value table is read), of [n] = every
+// window's group.  Fills A as build_tree_groups does for the batch the representatives were taken from, refusals included
+bool build_tree_groups_block(const WindowCaps& c, bool has_off1, const HostBatch& reps, int64_t n, const int32_t* of, WinAux& A);
 
 }  // namespace locamd

@@ -259,7 +259,8 @@ class WindowSolver(_lib.Handle):
         [n][np_max][18], s_idx int32 [n][ns_max][4], s_val float64 [n][ns_max][48] — each a device pointer, an object with data_ptr() or None (a
         table under a capacity of 0).  n: the windows (None: counts.shape[0]).  admit: int32 [n] on the device or None; window b's code (0
         admitted, 1 .. 6 the check it fails).  Every window is admitted and the chain family's structure scanned by a HIP pass on stream (a torch
-        stream; None: the handle's own; set_option("upload_dev_structures", 1): the arrowhead and forest verdicts as well); a batch with a refused window raises (LOC_ERR_INVALID; the error names the check and the lowest refused
+        stream; None: the handle's own; set_option("upload_dev_structures", 1): the arrowhead and forest verdicts as well; with
+        set_option("upload_dev_forest_groups", 1) and set_option("forest_groups", 1) also the groups of a mixed forest batch); a batch with a refused window raises (LOC_ERR_INVALID; the error names the check and the lowest refused
         window) and leaves the previous resident batch as it was.  Returns when the arrays are free again, like upload().  The handle's tables of
         endpoint-1 lever arms / full information matrices stay as they are.  Plumbing only: the library checks everything."""
         n = int(counts.shape[0]) if n is None else int(n)
@@ -539,8 +540,13 @@ class WindowSolver(_lib.Handle):
         uploaded from device arrays that is no chain solves on the general kernel;
         "forest_groups": 1 = a batch of forest windows of <= 64 poses whose topologies differ (other parents, lengths, anchors: key-frame windows
         of different robots or phases) is grouped by topology and solved by tree_wave_kernel<groups> with one schedule per group, from solve()
-        and from upload() + solve_resident(); a one-topology batch keeps tree_wave_kernel; upload_dev() does not group and covariances of a
+        and from upload() + solve_resident(); a one-topology batch keeps tree_wave_kernel; upload_dev() groups only under "upload_dev_forest_groups", and covariances of a
         mixed batch are served as without the option; default 0: such a batch solves on the general kernel;
+        "upload_dev_forest_groups": 1 (with "upload_dev_structures" and "forest_groups" 1) = upload_dev() groups such a mixed batch by topology
+        on the device and leaves the handle as upload() of the same arrays does — tree_wave_kernel<groups>, the same forest_groups(), the grouped
+        covariance pass on the uploaded block; default 0: a mixed batch in device arrays solves on the general kernel;
+        "upload_dev_groups_hash_bits": 0 .. 64, default 64 — a TEST SEAM: that pass's candidate hash keeps this many low bits (fewer bits force
+        hash collisions; the answer does not change);
         "forest_groups_covariance": 1 (with "forest_groups" 1) = the covariances and cross blocks of such a mixed batch are computed by
         forest_covariance_kernel<groups>, one wave per window on its group's schedule, from covariance() / joint_covariance() and their
         resident forms; default 0: the envelope pass under "covariance_general", else unsupported)"""
@@ -548,7 +554,7 @@ class WindowSolver(_lib.Handle):
 
     def forest_groups(self):
         """(number of topology groups, bytes of schedule tables sent to the device) of the handle's last structural verdict — solve() or
-        upload(), whichever came last; (0, 0) when that batch is not on the grouped path (option "forest_groups")"""
+        upload() / upload_dev(), whichever came last; (0, 0) when that batch is not on the grouped path (option "forest_groups")"""
         n, nbytes = C.c_int32(), C.c_int64()
         check(self.L.loc_window_forest_groups(self.h, C.byref(n), C.byref(nbytes)))
         return int(n.value), int(nbytes.value)
